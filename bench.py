@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """clips/s of the AltFreezing i3d_ori forward on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--dtype bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--dtype bf16] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 A step = one `model.forward(clip_batch)` of the drop-in Classifier on a (B,3,32,224,224) fp32 normalised
@@ -714,6 +714,14 @@ def bench_conv3x3x3(args, rank, world, dev):
         dist.destroy_process_group()
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor as <dirname>/<name>.npy, float32 on the host."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def self_launch(n_gpus: int, argv=None, poll_s: float = 0.2) -> int:
     """`python bench.py --gpus N` with no launcher: start N fresh rank processes of this script (one per GPU,
     RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set the way torch.distributed.run sets them), relay rank 0's JSON line,
@@ -800,7 +808,15 @@ def main():
     ap.add_argument("--no-parity-mode", action="store_true", help="skip the f16 (tolerance-meeting) leg next to a bf16 headline")
     ap.add_argument("--layers-json", default=None, help="write per-layer device times / rates to this file")
     ap.add_argument("--emit-logits", action="store_true", help="add the gathered per-clip logits of the last step to the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="--model i3d / slowfast / ftcn_tt: after the timed steps, write what the last step handed its caller "
+                         "(the gathered final_output logits) to DIR/<name>.npy as float32; inputs and weights are seeded, so two "
+                         "builds given the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.model not in ("i3d", "slowfast", "ftcn_tt"):
+        ap.error("--dump-outputs is implemented for --model i3d, slowfast and ftcn_tt")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -891,6 +907,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     clips_per_s = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:                  # every rank holds the gathered logits: rank 0 writes them
+        dump_outputs(args.dump_outputs, {"final_output": out})
 
     line = {
         "metric": "clips/sec (32x3x224x224)", "value": round(clips_per_s, 2), "unit": "clips/s",

@@ -19,15 +19,26 @@ Fixtures
   f9_dualrgb.*      the reference's tri-modal DualEncoderRGB (dualrun/model/dual_rgb.py): logits fp32 / fp64, masked / unmasked /
                     broadcast V
   f4_load.json      behaviour table of ``ModelBase.load`` on crafted checkpoints
+  plugin_host.json  the plugin contract the integration shim meets: PluginLoader's package / attribute, the yaml's
+                    clip geometry, the ModelBase surface
 """
 import json
 from collections import OrderedDict
 import os
+import subprocess
 import sys
 import tempfile
 
-import numpy as np
-import torch
+# F3 (compared bit for bit) and F7 (compared at a few fp32 ulps) are made with arithmetic whose rounding does not depend on
+# the host CPU: oneDNN off (Conv3d falls back to im2col + MKL sgemm), MKL's reproducible COMPATIBLE branch, one thread.  MKL
+# reads these at start-up, hence `--f3` / `--dualrun` run in a process of their own; tests/test_oracle.py runs the oracle
+# the same way for these two fixtures.
+REPRODUCIBLE_ENV = {"MKL_CBWR": "COMPATIBLE", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+if "--f3" in sys.argv or "--dualrun" in sys.argv:
+    os.environ.update(REPRODUCIBLE_ENV)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -41,6 +52,12 @@ import ref_import  # noqa: E402
 GOLD = os.path.join(ROOT, "tests", "golden")
 WEIGHT_SEED = 0
 CLIP_SEED = 2026
+
+
+def _reproducible():
+    assert all(os.environ.get(k) == v for k, v in REPRODUCIBLE_ENV.items()), "run as `gen_golden.py --f3` / `--dualrun`"
+    torch.set_num_threads(1)
+    return torch.backends.mkldnn.flags(enabled=False)
 
 
 def _layout_of(module):
@@ -185,7 +202,7 @@ def gen_f3():
         module.eval()
         lay = _fill(module, seed, name + ".", final_bn, linear)
         x = synth.synthetic_tensor(in_shape, seed, scale)
-        with torch.no_grad():
+        with torch.no_grad(), _reproducible():
             y = module(x.clone())
         arrays[name + "_out"] = y.numpy()
         meta = dict(meta)
@@ -256,7 +273,8 @@ def gen_f3():
     np.savez_compressed(os.path.join(GOLD, "f3_kats.npz"), **arrays)
     with open(os.path.join(GOLD, "f3_kats.json"), "w") as f:
         json.dump({"source": "reference layer modules (stem_helper/resnet_helper/head_helper/"
-                             "video_model_builder.FuseFastToSlow), eval mode, PyTorch CPU fp32",
+                             "video_model_builder.FuseFastToSlow), eval mode, PyTorch CPU fp32, oneDNN off, "
+                             "MKL_CBWR=COMPATIBLE, 1 thread",
                    "cases": cases}, f)
 
 
@@ -467,10 +485,10 @@ def gen_dualrun():
             lengths = None
         if tag == "b2_t5":
             lengths = torch.tensor([5, 0], dtype=torch.int32)          # a clip with no valid frame (keeps frame 0)
-        with torch.no_grad():
+        with torch.no_grad(), _reproducible():
             o32 = net(A, L, lengths, return_z=True)
         net.double()
-        with torch.no_grad():
+        with torch.no_grad(), _reproducible():
             o64 = net(A.double(), L.double(), lengths, return_z=True)
         net.float()
         out[tag + "_lengths"] = np.array([-1]) if lengths is None else lengths.numpy().astype(np.int64)
@@ -489,14 +507,15 @@ def gen_dualrun():
                       for k, v in moe.state_dict().items())
     moe.load_state_dict(msd)
     zr, zd = torch.randn(9, 1, generator=gm) * 3, torch.randn(9, 1, generator=gm) * 3
-    with torch.no_grad():
+    with torch.no_grad(), _reproducible():
         zf, gate = moe(zr, zd)
     for k, v in msd.items():
         out["moe_w_" + k] = v.numpy()
     out["moe_z_rgb"], out["moe_z_dual"], out["moe_z"], out["moe_gate"] = zr.numpy(), zd.numpy(), zf.numpy(), gate.numpy()
     with open(os.path.join(GOLD, "f7_dualrun.json"), "w") as f:
         json.dump({"source": "reference dualrun/model/dual_encoder.py DualEncoderAU_LMK (au 36, lmk 132, d_model 256, depth 4, "
-                             "heads 4, mlp_ratio 3.0, pool_tau 1.0), eval, PyTorch CPU, weights dual_synthetic_state_dict(seed), "
+                             "heads 4, mlp_ratio 3.0, pool_tau 1.0), eval, PyTorch CPU, oneDNN off, MKL_CBWR=COMPATIBLE, 1 thread, "
+                             "weights dual_synthetic_state_dict(seed), "
                              "inputs synthetic_dual_inputs(seed)",
                    "num_keys": len(lay), "num_params": int(sum(p.numel() for p in net.parameters())),
                    "weights_seed": WEIGHT_SEED, "inputs_seed": CLIP_SEED,
@@ -599,29 +618,50 @@ def gen_aligner():
     np.savez_compressed(os.path.join(GOLD, "f8_aligner.npz"), **out)
 
 
+def gen_plugin_host():
+    """What the integration shim relies on in the host tree: the package PluginLoader.get_classifier imports a plugin from,
+    the attribute it takes, the clip geometry of i3d_ori.yaml, and the ModelBase surface its callers use."""
+    cfg, PluginLoader = ref_import.import_reference()
+    ref_cls = PluginLoader.get_classifier(cfg.classifier_type)
+    out = {"source": "reference utils/plugin_loader.py PluginLoader.get_classifier('%s'), setting/i3d_ori.yaml via config, "
+                     "ModelBase methods of the returned class" % cfg.classifier_type,
+           "package": ref_cls.__module__.rsplit(".", 1)[0], "attribute": ref_cls.__name__,
+           "clip_size": int(cfg.clip_size), "imsize": int(cfg.imsize),
+           "surface": sorted(a for a in ("load", "forward", "module_to_build", "freeze") if hasattr(ref_cls, a))}
+    with open(os.path.join(GOLD, "plugin_host.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    print("plugin host:", out)
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     torch.manual_seed(0)
     torch.set_num_threads(8)
     clf = ref_import.build_reference_classifier()
     gen_layout(clf)
-    gen_f3()
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--f3"])
     gen_f4(clf)
     gen_f1_f2(clf)
     gen_f1b(clf)
     gen_slowfast()
-    gen_dualrun()
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--dualrun"])
     gen_dualrun_rgb()
     gen_aligner()
+    gen_plugin_host()
 
 
 if __name__ == "__main__":
-    if "--aligner" in sys.argv:
+    if "--f3" in sys.argv:
+        os.makedirs(GOLD, exist_ok=True)
+        gen_f3()
+    elif "--plugin-host" in sys.argv:
+        os.makedirs(GOLD, exist_ok=True)
+        gen_plugin_host()
+    elif "--aligner" in sys.argv:
         os.makedirs(GOLD, exist_ok=True)
         gen_aligner()
     elif "--dualrun" in sys.argv:
         os.makedirs(GOLD, exist_ok=True)
-        torch.set_num_threads(8)
         gen_dualrun()
     elif "--dualrun-rgb" in sys.argv:
         os.makedirs(GOLD, exist_ok=True)

@@ -497,6 +497,29 @@ def test_bench_two_rank_rehearsal_shards_the_real_forward():
     assert got.shape == want.shape and torch.equal(got, want), (got, want)
 
 
+def test_bench_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: the line reports the timed steps it ran, and DIR/final_output.npy holds the float32 logits
+    of the last timed step - the line's own gathered logits, equal to a forward of the same seeded clips in this process."""
+    import json
+    import subprocess
+    B = 2
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", str(B),
+                        "--cpu-clips", "0", "--no-roofline", "--emit-logits", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    line = json.loads(p.stdout.decode().strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    got = np.load(os.path.join(str(tmp_path), "final_output.npy"))
+    assert got.dtype == np.float32 and got.shape == (B, 1)
+    assert got.flatten().tolist() == line["gathered_logits"]
+    clf = Classifier(precision="bf16")
+    clf.network.load_state_dict(synth.synthetic_state_dict(seed=0))
+    clf = clf.cuda().eval()
+    with torch.inference_mode():
+        want = clf(synth.normalize_like_callers(synth.synthetic_clips_u8(B, seed=2026, kind="uniform").cuda()))["final_output"]
+    assert np.array_equal(got, want.float().cpu().numpy())
+
+
 def test_live_scorer_graph_replay_equals_infer_scores():
     """LiveScorer: the B = 1 forward recorded once into a HIP graph and replayed per window gives infer_scores' value bit for bit,
     for a clip passed in and for one written into its static input (as the streaming aligner does), several windows in a row."""

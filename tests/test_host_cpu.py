@@ -304,6 +304,16 @@ def test_self_launch_returns_quickly_when_a_rank_dies():
     assert dt < 30.0, dt                                            # (python + torch start-up of the children included)
 
 
+@pytest.mark.parametrize("args", [["--steps", "0"], ["--model", "aligner", "--dump-outputs", "unused"]])
+def test_bench_rejects_arguments_it_cannot_honour(args):
+    """bench.py refuses, before it touches a GPU, a run with no timed step and --dump-outputs on a model that does not dump."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, timeout=120)
+    assert p.returncode == 2 and p.stdout.strip() == b"", p.stderr.decode()[-2000:]
+    assert b"error:" in p.stderr
+
+
 def _device_asm(src):
     """gfx950 assembly of one .hip source (device side only; no GPU needed)"""
     import subprocess

@@ -1,30 +1,33 @@
-"""CPU, build container only: the reference-side shim integration/i3d_mi355x.py exercised through the reference's OWN
-plugin loader (altfreezing/utils/plugin_loader.py:27-52) and ModelBase lifecycle (model/_base.py:39-104):
-PluginLoader.get_classifier("i3d_mi355x")() -> .eval() -> .load(wrapped checkpoint) -> state_dict keys == the reference
-layout.  Skipped where /root/reference does not exist (the GPU box).  Runs in a child process: importing the reference
-puts its top-level packages (config, utils, model, ...) into sys.modules."""
+"""CPU: the reference-side shim integration/i3d_mi355x.py exercised the way the reference's plugin loader
+(altfreezing/utils/plugin_loader.py:27-52) and ModelBase lifecycle (model/_base.py:39-104) use it:
+get_classifier("i3d_mi355x")() -> .eval() -> .load(wrapped checkpoint) -> state_dict keys == the reference layout.
+The host tree is a stand-in built in a temporary directory from the contract recorded in tests/golden/plugin_host.json
+(oracle/gen_golden.py --plugin-host): a ``config`` singleton with the yaml's clip geometry, the plugin package, and a
+loader that imports ``<package>.<name>`` and takes its ``Classifier``.  Runs in a child process: the stand-in's
+top-level packages (config, model) go into sys.modules."""
 import json
 import os
 import subprocess
 import sys
 
-import pytest
-
 from conftest import ROOT, load_json
 
 SCRIPT = r'''
-import json, os, sys, tempfile
-ROOT = sys.argv[1]
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import importlib, json, os, sys, tempfile
+ROOT, HOST = sys.argv[1], sys.argv[2]
+sys.path.insert(0, ROOT); sys.path.insert(0, HOST)
 import torch
-import ref_import
-cfg, PluginLoader = ref_import.import_reference()          # the reference's config singleton + loader, i3d_ori.yaml
-import model.classifier as plugins                           # the reference's plugin package
+host = json.load(open(os.path.join(ROOT, "tests", "golden", "plugin_host.json")))
+
+
+def get_classifier(name):                                    # the loader's contract: <package>.<name> -> its Classifier
+    return getattr(importlib.import_module(host["package"] + "." + name.replace("-", "_")), host["attribute"])
+
+
+plugins = importlib.import_module(host["package"])          # the host's plugin package
 plugins.__path__.append(os.path.join(ROOT, "integration"))  # = "copy i3d_mi355x.py next to i3d_ori.py"
 os.environ["AF_MI355X_ROOT"] = ROOT
-Cls = PluginLoader.get_classifier("i3d_mi355x")             # what `classifier_type: i3d_mi355x` resolves to
-from model._base import ModelBase
-ref_cls = PluginLoader.get_classifier(cfg.classifier_type)
+Cls = get_classifier("i3d_mi355x")                           # what `classifier_type: i3d_mi355x` resolves to
 clf = Cls()
 clf.eval()
 from af_mi355x import synth
@@ -46,22 +49,34 @@ print(json.dumps({
     "layout": [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in got.items()],
     "loaded_equal": all(torch.equal(got[k], sd[k]) for k in sd),
     "has_surface": all(hasattr(clf, a) for a in ("network", "_warped_network", "load", "forward", "module_to_build")),
-    "ref_surface": sorted(a for a in ("load", "forward", "module_to_build", "freeze") if hasattr(ref_cls, a)),
+    "host_surface": sorted(a for a in host["surface"] if hasattr(Cls, a)),
     "cpu_call": cpu_call,
 }))
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/altfreezing"), reason="reference tree not present (GPU box)")
+def _host_tree(root, host):
+    """A minimal host tree: config.config carries the yaml's clip_size / imsize; <package> is an empty package."""
+    with open(os.path.join(root, "config.py"), "w") as f:
+        f.write("class _Config:\n    clip_size = %d\n    imsize = %d\n\n\nconfig = _Config()\n" % (host["clip_size"], host["imsize"]))
+    d = root
+    for part in host["package"].split("."):
+        d = os.path.join(d, part)
+        os.makedirs(d)
+        open(os.path.join(d, "__init__.py"), "w").close()
+
+
 def test_shim_through_the_reference_plugin_loader(tmp_path):
-    r = subprocess.run([sys.executable, "-c", SCRIPT, ROOT], capture_output=True, text=True, timeout=600)
+    host = load_json("plugin_host.json")
+    _host_tree(str(tmp_path), host)
+    r = subprocess.run([sys.executable, "-c", SCRIPT, ROOT, str(tmp_path)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["class"] == "Classifier" and out["module"] == "model.classifier.i3d_mi355x"
-    assert out["clip"] == 32                                        # read from the reference's yaml via its config singleton
+    assert out["clip"] == 32                                        # read from the host's config singleton
     assert out["load"] == [True, -1] and out["load_missing"] == [False, -1]
     lay = load_json("layout.json")
     assert out["layout"] == lay["entries"] and len(out["layout"]) == 320
     assert out["loaded_equal"] and out["has_surface"]
-    assert out["ref_surface"] == ["forward", "freeze", "load", "module_to_build"]
+    assert out["host_surface"] == host["surface"] == ["forward", "freeze", "load", "module_to_build"]
     assert out["cpu_call"].startswith("RuntimeError")              # no CPU fallback behind the plugin surface either

@@ -57,11 +57,52 @@ def run_oracle_kat(case):
     raise KeyError(kind)
 
 
-def test_kats_bit_exact(golden_f3):
+# oneDNN and MKL round differently with the thread count and the host CPU, so F3 and F7 were made with arithmetic that does
+# not (oracle/gen_golden.py REPRODUCIBLE_ENV) and the oracle is run here the same way, in a child process because MKL reads
+# these settings at start-up
+REPRODUCIBLE_ENV = {"MKL_CBWR": "COMPATIBLE", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+KAT_SCRIPT = r'''
+from test_oracle import run_oracle_kat
+outputs = {c["name"] + "_out": run_oracle_kat(c).numpy() for c in load_json("f3_kats.json")["cases"]}
+'''
+DUAL_SCRIPT = r'''
+import dualrun_oracle
+from af_mi355x import dualrun
+g, st = load_json("f7_dualrun.json"), load_npz("f7_dualrun.npz")
+sp = dualrun.DualSpec()
+sd = dualrun.dual_synthetic_state_dict(sp, seed=g["weights_seed"])
+outputs = {}
+for tag, batch, frames in (("b6_t8", 6, 8), ("b3_t8_full", 3, 8), ("b2_t5", 2, 5)):
+    A, L, _ = dualrun.synthetic_dual_inputs(batch, sp, frames=frames, seed=g["inputs_seed"])
+    ln = st[tag + "_lengths"]
+    lengths = None if ln[0] < 0 else torch.from_numpy(ln)
+    logits, z = dualrun_oracle.dual_forward(sd, A, L, lengths, heads=sp.heads, tau=sp.pool_tau)
+    outputs[tag + "_logits_f32"], outputs[tag + "_z_f32"] = logits.numpy(), z.numpy()
+msd = {k[len("moe_w_"):]: torch.from_numpy(st[k]) for k in st.files if k.startswith("moe_w_")}
+zf, gate = dualrun_oracle.gated_moe(msd, torch.from_numpy(st["moe_z_rgb"]), torch.from_numpy(st["moe_z_dual"]))
+outputs["moe_z"], outputs["moe_gate"] = zf.numpy(), gate.numpy()
+'''
+
+
+def run_reproducibly(script, tmp_path):
+    """runs `script` (which fills the dict `outputs`) in a child under REPRODUCIBLE_ENV, oneDNN off, one thread"""
+    import subprocess
+    out = os.path.join(str(tmp_path), "outputs.npz")
+    head = ("import sys\nimport numpy as np\nimport torch\nsys.path[:0] = [%r, %r]\nfrom conftest import load_json, load_npz\n"
+            "torch.set_num_threads(1)\ntorch.backends.mkldnn.enabled = False\n" % (os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")))
+    tail = "\nnp.savez(%r, **outputs)\n" % out
+    r = subprocess.run([sys.executable, "-c", head + script + tail], env=dict(os.environ, **REPRODUCIBLE_ENV),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return np.load(out)
+
+
+def test_kats_bit_exact(golden_f3, tmp_path):
     cases, arrays = golden_f3
     assert len(cases) >= 13
+    got_all = run_reproducibly(KAT_SCRIPT, tmp_path)
     for case in cases:
-        got = run_oracle_kat(case).numpy()
+        got = got_all[case["name"] + "_out"]
         want = arrays[case["name"] + "_out"]
         assert got.shape == want.shape, case["name"]
         if case["kind"] == "head":      # torch.cat in the reference changes the GEMV's memory layout: last-bit noise
@@ -136,10 +177,9 @@ def test_ftcn_tt_logits_stages_and_head():
         np.testing.assert_allclose(got, st["%s_val" % name], rtol=1e-4, atol=1e-5)
 
 
-def test_dualrun_oracle_matches_reference():
+def test_dualrun_oracle_matches_reference(tmp_path):
     """oracle/dualrun_oracle.py against the reference's DualEncoderAU_LMK (tests/golden/f7_dualrun.*): ragged lengths, no
     lengths, and a clip without a single valid frame."""
-    import dualrun_oracle
     from af_mi355x import dualrun
     g = load_json("f7_dualrun.json")
     st = load_npz("f7_dualrun.npz")
@@ -147,17 +187,12 @@ def test_dualrun_oracle_matches_reference():
     sd = dualrun.dual_synthetic_state_dict(sp, seed=g["weights_seed"])
     assert synth.state_dict_sha256(sd) == g["weights_sha256"] and len(sd) == g["num_keys"] == 136
     assert sum(v.numel() for v in sd.values()) == g["num_params"] == 5789989
-    for tag, batch, frames in (("b6_t8", 6, 8), ("b3_t8_full", 3, 8), ("b2_t5", 2, 5)):
-        A, L, _ = dualrun.synthetic_dual_inputs(batch, sp, frames=frames, seed=g["inputs_seed"])
-        ln = st[tag + "_lengths"]
-        lengths = None if ln[0] < 0 else torch.from_numpy(ln)
-        logits, z = dualrun_oracle.dual_forward(sd, A, L, lengths, heads=sp.heads, tau=sp.pool_tau)
-        np.testing.assert_allclose(logits.numpy(), st[tag + "_logits_f32"], rtol=0, atol=2e-6)
-        np.testing.assert_allclose(z.numpy(), st[tag + "_z_f32"], rtol=2e-6, atol=5e-6)
-    msd = {k[len("moe_w_"):]: torch.from_numpy(st[k]) for k in st.files if k.startswith("moe_w_")}
-    zf, gate = dualrun_oracle.gated_moe(msd, torch.from_numpy(st["moe_z_rgb"]), torch.from_numpy(st["moe_z_dual"]))
-    np.testing.assert_allclose(zf.numpy(), st["moe_z"], rtol=1e-6, atol=1e-6)
-    np.testing.assert_allclose(gate.numpy(), st["moe_gate"], rtol=1e-6, atol=1e-7)
+    got = run_reproducibly(DUAL_SCRIPT, tmp_path)
+    for tag in ("b6_t8", "b3_t8_full", "b2_t5"):
+        np.testing.assert_allclose(got[tag + "_logits_f32"], st[tag + "_logits_f32"], rtol=0, atol=2e-6)
+        np.testing.assert_allclose(got[tag + "_z_f32"], st[tag + "_z_f32"], rtol=2e-6, atol=5e-6)
+    np.testing.assert_allclose(got["moe_z"], st["moe_z"], rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(got["moe_gate"], st["moe_gate"], rtol=1e-6, atol=1e-7)
 
 
 def test_checkpoint_unwrap_rules():
