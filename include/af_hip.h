@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define AF_ABI_VERSION 4
+#define AF_ABI_VERSION 5
 
 enum af_dtype { AF_F32 = 0, AF_BF16 = 1, AF_F16 = 2 };
 
@@ -451,6 +451,41 @@ typedef struct af_op {
 int af_run_ops(const af_op* ops, int n_ops, void* stream);
 /* Same, bracketing every op with hipEvents on `stream`; ms[i] = device time of op i.  Synchronises. */
 int af_run_ops_timed(const af_op* ops, int n_ops, void* stream, float* ms);
+
+/* ---- YuNet face detector (ABI 5) ---------------------------------------------------------
+ * The live-call loop's detection stage: preprocessing/yunet/yunet.py YuNet.infer ->
+ * cv2.FaceDetectorYN.detect on face_detection_yunet_2023mar.onnx (test/af_realtime.py), for a batch
+ * of `batch` uint8 BGR frames of one size.  Each frame is zero-padded bottom / right to a multiple of
+ * 32 and fed as float 0..255 (no mean, no scale, no channel swap); the whole network is fp32.
+ * Decode and NMS restate OpenCV's FaceDetectorYN::postProcess and dnn::NMSBoxes (csrc/af_yunet.hip).
+ *
+ * `weights`: af_yunet_weight_floats() fp32 values packed by detector.py (pack_weights) from the ONNX file.
+ * `frames`: frame b starts at frames + b * frame_stride, rows row_pitch bytes apart, 3 bytes per pixel.
+ * `workspace`: af_yunet_workspace_bytes(desc) bytes of device scratch (16-byte aligned).
+ * `out_rows`: [batch][top_k][15] f32 (x, y, w, h, 5 landmarks (x, y), score); rows past out_count[b]
+ * are not written.  `out_count`: [batch] int32.  `raw` (optional, may be NULL): [batch][anchors][16]
+ * f32, per anchor (stride 8, 16, 32 levels in order, row-major) the 16 head outputs cls, obj (after the
+ * sigmoid), bbox[4], kps[10].  Every argument is checked on the host before the first launch.
+ * AF_YUNET_LAUNCHES kernels are enqueued; *_timed also returns their device times (synchronises).
+ * Cost of the per-frame sort: up to 16 384 candidates (score >= conf) are sorted in one pass in LDS; above that the sort
+ * runs as candidates / 8 192 LDS passes of 16 384 keys, so a very low conf on a very large frame (all 1.38 M anchors of an
+ * 8192 x 8192 frame at conf 0) costs one workgroup about 170 such passes.  At the default conf 0.6 real frames stay far
+ * below 16 384.  A workspace serves one stream at a time: concurrent calls need separate workspaces. */
+#define AF_YUNET_MAX_TOPK 8192
+#define AF_YUNET_MAX_SIDE 8192
+#define AF_YUNET_LAUNCHES 18
+typedef struct af_yunet_desc {
+    int32_t batch, height, width;
+    int32_t top_k;
+    int64_t frame_stride, row_pitch;   /* bytes */
+    float conf_threshold, nms_threshold;
+} af_yunet_desc;
+int64_t af_yunet_weight_floats(void);
+int64_t af_yunet_workspace_bytes(const af_yunet_desc* desc);
+int af_yunet_detect(const af_yunet_desc* desc, const float* weights, const void* frames, void* workspace, int64_t workspace_bytes,
+                    float* out_rows, int32_t* out_count, float* raw, void* stream);
+int af_yunet_detect_timed(const af_yunet_desc* desc, const float* weights, const void* frames, void* workspace,
+                          int64_t workspace_bytes, float* out_rows, int32_t* out_count, float* raw, void* stream, float* ms);
 
 #ifdef __cplusplus
 }

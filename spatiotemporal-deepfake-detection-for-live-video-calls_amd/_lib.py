@@ -10,7 +10,7 @@ AF_F32, AF_BF16, AF_F16 = 0, 1, 2
 (AF_OP_STEM, AF_OP_CONV, AF_OP_MAXPOOL, AF_OP_HEAD, AF_OP_PACK_F32, AF_OP_PACK_U8, AF_OP_CONV_DUAL, AF_OP_STEM_POOL, AF_OP_AVGPOOL,
  AF_OP_LINEAR, AF_OP_TSTEM, AF_OP_TOKENS, AF_OP_LAYERNORM, AF_OP_ATTENTION, AF_OP_GELU, AF_OP_CONV_BC, AF_OP_PACK3_F32,
  AF_OP_PACK3_U8, AF_OP_STEM3_POOL, AF_OP_CONV_CA, AF_OP_BLOCK_ABC, AF_OP_TSTEM_POOL3, AF_OP_CONV_CPA) = range(23)
-AF_ABI_VERSION = 4
+AF_ABI_VERSION = 5
 STEM_PAD_T, STEM_PAD_H, STEM_PAD_W_LEFT, STEM_PAD_W_TOTAL, STEM_CPAD = 2, 3, 3, 8, 4
 
 DTYPE_CODES = {"f32": AF_F32, "bf16": AF_BF16, "f16": AF_F16}
@@ -62,6 +62,13 @@ class Op(C.Structure):
         ("x_sub", C.c_int32), ("reserved0", C.c_int32),
     ]
 
+
+class YunetDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("top_k", C.c_int32),
+                ("frame_stride", C.c_int64), ("row_pitch", C.c_int64), ("conf_threshold", C.c_float), ("nms_threshold", C.c_float)]
+
+
+YUNET_MAX_TOPK, YUNET_MAX_SIDE, YUNET_LAUNCHES = 8192, 8192, 18
 
 # name -> (restype, argtypes); tests/test_host_cpu.py::test_c_abi_exports_every_declared_symbol checks this table against
 # include/af_hip.h and the built library
@@ -137,6 +144,11 @@ ABI = {
     "af_dual_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "af_run_ops": (C.c_int, [C.POINTER(Op), C.c_int, C.c_void_p]),
     "af_run_ops_timed": (C.c_int, [C.POINTER(Op), C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "af_yunet_weight_floats": (C.c_int64, []),
+    "af_yunet_workspace_bytes": (C.c_int64, [C.POINTER(YunetDesc)]),
+    "af_yunet_detect": (C.c_int, [C.POINTER(YunetDesc)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4),
+    "af_yunet_detect_timed": (C.c_int, [C.POINTER(YunetDesc)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4
+                              + [C.POINTER(C.c_float)]),
 }
 
 
