@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define AF_ABI_VERSION 5
+#define AF_ABI_VERSION 6
 
 enum af_dtype { AF_F32 = 0, AF_BF16 = 1, AF_F16 = 2 };
 
@@ -486,6 +486,54 @@ int af_yunet_detect(const af_yunet_desc* desc, const float* weights, const void*
                     float* out_rows, int32_t* out_count, float* raw, void* stream);
 int af_yunet_detect_timed(const af_yunet_desc* desc, const float* weights, const void* frames, void* workspace,
                           int64_t workspace_bytes, float* out_rows, int32_t* out_count, float* raw, void* stream, float* ms);
+
+/* ---- RetinaFace detector (ABI 6) ---------------------------------------------------------
+ * The offline evaluator's face detector: test_tools/ct/detection (RetinaFace(cfg_mnet, phase="test"),
+ * mobilenet0.25, and batch_detect's post_process with confidence 0.02, top_k 5000, NMS 0.4,
+ * keep_top_k 750) for a batch of `batch` uint8 HWC frames of one size.  The mean (104, 117, 123) is
+ * subtracted by channel index, whatever the channel order; the whole network is fp32 (csrc/af_retinaface.hip).
+ *
+ * `weights`: af_retinaface_weight_floats() fp32 values packed by retinaface.py (pack_weights), BN folded.
+ * `frames`: frame b starts at frames + b * frame_stride, rows row_pitch bytes apart, 3 bytes per pixel.
+ * `workspace`: af_retinaface_workspace_bytes(desc) bytes of device scratch (16-byte aligned).
+ * `out_rows`: [batch][af_retinaface_max_rows(desc)][15] f32 (x1, y1, x2, y2, score, 5 landmarks (x, y)),
+ * in descending score order; rows past out_count[b] are not written.  `out_count`: [batch] int32.
+ * The rows are post_process's detections cut to min(keep_top_k, max_count) (max_count <= 0: no cut),
+ * then to the leading rows with score >= min_score (get_valid_faces; min_score 0: no cut).
+ * Exact score ties are ordered by descending anchor index (the reference leaves them unordered).
+ * `raw` (optional, may be NULL): 16 * batch * anchors f32 as three planes, loc [batch][anchors][4],
+ * conf [batch][anchors][2] (after the softmax), landms [batch][anchors][10]; anchors in PriorBox order
+ * (level, row, col, anchor).
+ * af_retinaface_postprocess runs the decode and post-process alone on caller-supplied planes of that
+ * layout (`loc`, `conf` after the softmax, `landms`); it does not read `frames`.
+ * AF_RETINAFACE_LAUNCHES kernels are enqueued by detect; *_timed also returns their device times
+ * (synchronises).  A workspace serves one stream at a time. */
+#define AF_RETINAFACE_MAX_SIDE 8192
+#define AF_RETINAFACE_TOP_K 5000
+#define AF_RETINAFACE_MAX_KEEP 5000
+#define AF_RETINAFACE_LAUNCHES 54
+#define AF_RETINAFACE_POST_LAUNCHES 5
+typedef struct af_retinaface_desc {
+    int32_t batch, height, width;
+    int32_t keep_top_k;                /* 750 in batch_detect; 1 .. AF_RETINAFACE_MAX_KEEP */
+    int64_t frame_stride, row_pitch;   /* bytes */
+    int32_t max_count;                 /* get_valid_faces' max_count; <= 0: no cut */
+    int32_t reserved;
+    double min_score;                  /* get_valid_faces' thres: rows with score < min_score are dropped */
+} af_retinaface_desc;
+int64_t af_retinaface_weight_floats(void);
+int64_t af_retinaface_anchors(const af_retinaface_desc* desc);
+int32_t af_retinaface_max_rows(const af_retinaface_desc* desc);
+int64_t af_retinaface_workspace_bytes(const af_retinaface_desc* desc);
+int af_retinaface_detect(const af_retinaface_desc* desc, const float* weights, const void* frames, void* workspace,
+                         int64_t workspace_bytes, float* out_rows, int32_t* out_count, float* raw, void* stream);
+int af_retinaface_detect_timed(const af_retinaface_desc* desc, const float* weights, const void* frames, void* workspace,
+                               int64_t workspace_bytes, float* out_rows, int32_t* out_count, float* raw, void* stream, float* ms);
+int af_retinaface_postprocess(const af_retinaface_desc* desc, const float* loc, const float* conf, const float* landms,
+                              void* workspace, int64_t workspace_bytes, float* out_rows, int32_t* out_count, void* stream);
+int af_retinaface_postprocess_timed(const af_retinaface_desc* desc, const float* loc, const float* conf, const float* landms,
+                                    void* workspace, int64_t workspace_bytes, float* out_rows, int32_t* out_count, void* stream,
+                                    float* ms);
 
 #ifdef __cplusplus
 }

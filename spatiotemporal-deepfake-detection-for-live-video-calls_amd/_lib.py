@@ -10,7 +10,7 @@ AF_F32, AF_BF16, AF_F16 = 0, 1, 2
 (AF_OP_STEM, AF_OP_CONV, AF_OP_MAXPOOL, AF_OP_HEAD, AF_OP_PACK_F32, AF_OP_PACK_U8, AF_OP_CONV_DUAL, AF_OP_STEM_POOL, AF_OP_AVGPOOL,
  AF_OP_LINEAR, AF_OP_TSTEM, AF_OP_TOKENS, AF_OP_LAYERNORM, AF_OP_ATTENTION, AF_OP_GELU, AF_OP_CONV_BC, AF_OP_PACK3_F32,
  AF_OP_PACK3_U8, AF_OP_STEM3_POOL, AF_OP_CONV_CA, AF_OP_BLOCK_ABC, AF_OP_TSTEM_POOL3, AF_OP_CONV_CPA) = range(23)
-AF_ABI_VERSION = 5
+AF_ABI_VERSION = 6
 STEM_PAD_T, STEM_PAD_H, STEM_PAD_W_LEFT, STEM_PAD_W_TOTAL, STEM_CPAD = 2, 3, 3, 8, 4
 
 DTYPE_CODES = {"f32": AF_F32, "bf16": AF_BF16, "f16": AF_F16}
@@ -69,6 +69,16 @@ class YunetDesc(C.Structure):
 
 
 YUNET_MAX_TOPK, YUNET_MAX_SIDE, YUNET_LAUNCHES = 8192, 8192, 18
+
+
+class RetinafaceDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("keep_top_k", C.c_int32),
+                ("frame_stride", C.c_int64), ("row_pitch", C.c_int64), ("max_count", C.c_int32), ("reserved", C.c_int32),
+                ("min_score", C.c_double)]
+
+
+RETINAFACE_MAX_SIDE, RETINAFACE_TOP_K, RETINAFACE_MAX_KEEP = 8192, 5000, 5000
+RETINAFACE_LAUNCHES, RETINAFACE_POST_LAUNCHES = 54, 5
 
 # name -> (restype, argtypes); tests/test_host_cpu.py::test_c_abi_exports_every_declared_symbol checks this table against
 # include/af_hip.h and the built library
@@ -149,6 +159,16 @@ ABI = {
     "af_yunet_detect": (C.c_int, [C.POINTER(YunetDesc)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4),
     "af_yunet_detect_timed": (C.c_int, [C.POINTER(YunetDesc)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4
                               + [C.POINTER(C.c_float)]),
+    "af_retinaface_weight_floats": (C.c_int64, []),
+    "af_retinaface_anchors": (C.c_int64, [C.POINTER(RetinafaceDesc)]),
+    "af_retinaface_max_rows": (C.c_int32, [C.POINTER(RetinafaceDesc)]),
+    "af_retinaface_workspace_bytes": (C.c_int64, [C.POINTER(RetinafaceDesc)]),
+    "af_retinaface_detect": (C.c_int, [C.POINTER(RetinafaceDesc)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4),
+    "af_retinaface_detect_timed": (C.c_int, [C.POINTER(RetinafaceDesc)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4
+                                   + [C.POINTER(C.c_float)]),
+    "af_retinaface_postprocess": (C.c_int, [C.POINTER(RetinafaceDesc)] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3),
+    "af_retinaface_postprocess_timed": (C.c_int, [C.POINTER(RetinafaceDesc)] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3
+                                        + [C.POINTER(C.c_float)]),
 }
 
 

@@ -134,3 +134,79 @@ def pixel_mean_std_f32(device="cpu"):
     mean = torch.tensor(IMAGENET_MEAN, dtype=torch.float32, device=device) * 255
     std = torch.tensor(IMAGENET_STD, dtype=torch.float32, device=device) * 255
     return mean, std
+
+
+# ---- RetinaFace (retinaface.py): seeded weights in the reference's layout and seeded frames of any size
+RETINAFACE_RECIPES = {
+    # class-head logit bias (face - background) per level and spread: "sparse" leaves a few to a few hundred anchors above
+    # the 0.02 threshold per frame (some above 0.5); "dense" puts most anchors above it, the small stride-8 ones first
+    # (> top_k candidates and > keep_top_k kept at 1080p)
+    "sparse": ((-8.0, -8.0, -8.0), 2.0),
+    "dense": ((3.0, 0.0, -2.0), 0.5),
+}
+
+
+def retinaface_state_dict(seed: int = 0, recipe: str = "sparse") -> "OrderedDict[str, torch.Tensor]":
+    """W(seed) for RetinaFace mobilenet0.25: the reference's 300 keys, shapes and order (retinaface.state_dict_layout),
+    one generator per key.  Conv weights are He-scaled by fan-in (the first conv also by 1/64 for the 0..255 input) and BN
+    keeps gamma / sqrt(var) near 1, so activations stay O(1) through all 56 convs."""
+    from .retinaface import state_dict_layout
+    if recipe not in RETINAFACE_RECIPES:
+        raise ValueError(recipe)
+    cls_bias, cls_gain = RETINAFACE_RECIPES[recipe]
+    sd = OrderedDict()
+    for idx, (key, shape) in enumerate(state_dict_layout()):
+        g = _gen(seed, 50000 + idx)
+        leaf = key.rsplit(".", 1)[1]
+        if leaf == "num_batches_tracked":
+            t = torch.zeros((), dtype=torch.int64)
+        elif len(shape) == 4:
+            fan_in = shape[1] * shape[2] * shape[3]
+            std = math.sqrt(2.0 / fan_in)
+            if key.startswith("body.stage1.0.0."):
+                std /= 64.0
+            elif "Head" in key:
+                std = math.sqrt(1.0 / fan_in) * (cls_gain if key.startswith("ClassHead") else 1.0)
+            t = torch.randn(shape, generator=g) * std
+        elif "Head" in key:                                   # head conv bias
+            t = torch.randn(shape, generator=g) * 0.1
+            if key.startswith("ClassHead"):
+                t[1::2] += cls_bias[int(key.split(".")[1])]
+        elif leaf == "weight":
+            t = torch.rand(shape, generator=g) * 0.4 + 0.8
+        elif leaf == "bias":
+            t = torch.randn(shape, generator=g) * 0.1
+        elif leaf == "running_mean":
+            t = torch.randn(shape, generator=g) * 0.1
+        elif leaf == "running_var":
+            t = torch.rand(shape, generator=g) * 0.4 + 0.8
+        else:
+            raise KeyError(key)
+        sd[key] = t.contiguous()
+    return sd
+
+
+def retinaface_frames(n: int, h: int, w: int, seed: int = 0) -> np.ndarray:
+    """(n, h, w, 3) uint8 frames: a smooth colour field (bilinear from a coarse grid), a few flat rectangles and mild
+    noise, from numpy PCG64 and float64 arithmetic only (bit-reproducible on any host)"""
+    out = np.empty((n, h, w, 3), np.uint8)
+    for b in range(n):
+        r = np.random.Generator(np.random.PCG64([int(seed), b, h, w]))
+        gy, gx = 6, 8
+        grid = r.uniform(0, 255, (gy, gx, 3))
+        fy = np.linspace(0, gy - 1, h)
+        fx = np.linspace(0, gx - 1, w)
+        y0 = np.minimum(np.floor(fy).astype(int), gy - 2)
+        x0 = np.minimum(np.floor(fx).astype(int), gx - 2)
+        ty = (fy - y0)[:, None, None]
+        tx = (fx - x0)[None, :, None]
+        top = grid[y0][:, x0] * (1 - tx) + grid[y0][:, x0 + 1] * tx
+        bot = grid[y0 + 1][:, x0] * (1 - tx) + grid[y0 + 1][:, x0 + 1] * tx
+        img = top * (1 - ty) + bot * ty
+        for _ in range(12):
+            rh, rw = int(r.integers(max(h // 16, 1), max(h // 3, 2))), int(r.integers(max(w // 16, 1), max(w // 3, 2)))
+            y, x = int(r.integers(0, max(h - rh, 1))), int(r.integers(0, max(w - rw, 1)))
+            img[y:y + rh, x:x + rw] = r.uniform(0, 255, 3)
+        img = img + r.normal(0, 8, img.shape)
+        out[b] = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    return out
