@@ -1,8 +1,6 @@
 // C-ABI glue: version / error text / device probe and the whole-forward op-list runner.
 #include "af_common.h"
 
-#include <vector>
-
 namespace af {
 
 static thread_local char g_err[512] = "";
@@ -120,19 +118,14 @@ extern "C" int af_run_ops(const af_op* ops, int n_ops, void* stream) {
 extern "C" int af_run_ops_timed(const af_op* ops, int n_ops, void* stream, float* ms) {
     AF_REQUIRE(ops && n_ops > 0 && ms, "run_ops_timed: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    std::vector<hipEvent_t> ev(n_ops + 1);
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) return af::set_error(AF_ERR_LAUNCH, "run_ops_timed: hipEventCreate failed");
-    int rc = AF_OK;
-    (void)hipEventRecord(ev[0], s);
-    for (int i = 0; i < n_ops && rc == AF_OK; ++i) {
-        rc = af::run_one(ops[i], s);
-        (void)hipEventRecord(ev[i + 1], s);
-    }
-    hipError_t e = hipStreamSynchronize(s);
-    if (rc == AF_OK && e != hipSuccess) rc = af::set_error(AF_ERR_LAUNCH, "run_ops_timed: %s", hipGetErrorString(e));
-    if (rc == AF_OK)
-        for (int i = 0; i < n_ops; ++i) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-    for (auto& ev_ : ev) (void)hipEventDestroy(ev_);
-    return rc;
+    return af::timed("run_ops_timed", s, n_ops, ms, [&](hipEvent_t* ev) -> int {
+        af::Marks mark{s, ev, 0};
+        mark();
+        for (int i = 0; i < n_ops; ++i) {
+            int rc = af::run_one(ops[i], s);
+            if (rc != AF_OK) return rc;
+            mark();
+        }
+        return AF_OK;
+    });
 }

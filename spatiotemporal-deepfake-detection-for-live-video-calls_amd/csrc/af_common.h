@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdarg.h>
 
+#include <vector>
+
 #include "../../include/af_hip.h"
 
 namespace af {
@@ -225,6 +227,38 @@ int device_cus();
         if (e__ != hipSuccess)                                                       \
             return af::set_error(AF_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e__)); \
     } while (0)
+
+// the event marks of a launch sequence: the i-th call records ev[i] on s, so mark() before launch 0 and after every
+// launch gives launch i the span between ev[i] and ev[i + 1].  Does nothing when ev is null (an untimed run).
+struct Marks {
+    hipStream_t s;
+    hipEvent_t* ev;
+    int k;
+    void operator()() { if (ev) (void)hipEventRecord(ev[k++], s); }
+};
+
+// The *_timed entry points: runs fn(ev) with n + 1 fresh events (fn marks its n launches with a Marks on ev), waits for
+// the stream and writes the n device times in ms.  `who` prefixes the error messages.
+template <class F>
+int timed(const char* who, hipStream_t s, int n, float* ms, F fn) {
+    AF_REQUIRE(ms, "%s: null ms", who);
+    std::vector<hipEvent_t> ev;
+    for (int i = 0; i <= n; ++i) {
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) {
+            for (auto& e_ : ev) (void)hipEventDestroy(e_);
+            return set_error(AF_ERR_LAUNCH, "%s: cannot create event %d", who, i);
+        }
+        ev.push_back(e);
+    }
+    int rc = fn(ev.data());
+    hipError_t e = hipStreamSynchronize(s);
+    if (rc == AF_OK && e != hipSuccess) rc = set_error(AF_ERR_LAUNCH, "%s: %s", who, hipGetErrorString(e));
+    if (rc == AF_OK)
+        for (int i = 0; i < n; ++i) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+    for (auto& e_ : ev) (void)hipEventDestroy(e_);
+    return rc;
+}
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int dtype_size(int dt) { return dt == AF_F32 ? 4 : 2; }

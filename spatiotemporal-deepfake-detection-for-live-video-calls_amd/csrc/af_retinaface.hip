@@ -17,22 +17,21 @@
 //                           boxes or at the first kept score below min_score
 // The dense convolutions are implicit GEMMs on v_mfma_f32_16x16x4_f32 (exact fp32 products and sums): A[pixel][k] with
 // k = (tap, input channel), B[k][output channel] packed by the host so that each lane loads one float4 per 16 k.
-#include "af_common.h"
+#include "af_detect.h"
 
 #include <algorithm>
-#include <vector>
 
 namespace af {
 namespace retinaface {
+
+using detect::kSortHalf;
+using detect::kSortLdsBytes;
+using detect::kSortThreads;
 
 constexpr int kThreads = 256;
 constexpr int kMB = 4;                       // 16-pixel blocks per wave in rf_conv
 constexpr int kTopK = AF_RETINAFACE_TOP_K;
 constexpr int kWords = (kTopK + 63) / 64;    // bitmask words per NMS row
-constexpr int kSortThreads = 1024;
-constexpr int kSortLdsBytes = 128 * 1024;
-constexpr int kSortLdsKeys = kSortLdsBytes / 8;
-constexpr int kSortHalf = kSortLdsKeys / 2;
 constexpr float kConf = 0.02f, kNms = 0.4f, kVar0 = 0.1f, kVar1 = 0.2f;
 constexpr int kBlocks = 13;
 // MobileNetV1 stage1..3 after the first conv_bn: (cin, cout, stride) of each conv_dw
@@ -344,24 +343,6 @@ __global__ void rf_zero_counts(int* counts, int n) {
     if (i < n) counts[i] = 0;
 }
 
-// ascending bitonic sort of buf[0, n2) (n2 a power of two) by the whole block
-__device__ __forceinline__ void bitonic_sort(unsigned long long* buf, int n2) {
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n2; i += kSortThreads) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long x = buf[i], y = buf[l];
-                    if ((x > y) == ((i & k) == 0)) {
-                        buf[i] = y;
-                        buf[l] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-}
-
 struct SortArgs {
     const int* counts;
     const unsigned long long* keys;
@@ -372,28 +353,13 @@ struct SortArgs {
     float4* sboxes;             // [B][kTopK]
 };
 
-// Per frame (one block): up to kSortLdsKeys candidates are sorted whole in LDS; above that the block keeps the kSortHalf
-// smallest keys as a running set and sorts it together with each next chunk of kSortHalf keys.  The first min(n, top_k)
-// keys and their boxes are written in order.
+// Per frame (one block): the candidate keys are sorted in LDS (detect::sort_keys); the first min(n, top_k) keys and their
+// boxes are written in order.
 __global__ __launch_bounds__(kSortThreads) void rf_sort(SortArgs a) {
     extern __shared__ unsigned long long lds[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n = min(a.counts[b], a.anchors);
-    const unsigned long long* gk = a.keys + (size_t)b * a.anchors;
-    if (n <= kSortLdsKeys) {
-        int n2 = 2;
-        while (n2 < n) n2 <<= 1;
-        for (int i = tid; i < n2; i += kSortThreads) lds[i] = i < n ? gk[i] : ~0ull;
-        __syncthreads();
-        bitonic_sort(lds, n2);
-    } else {
-        for (int i = tid; i < kSortHalf; i += kSortThreads) lds[i] = gk[i];
-        for (int base = kSortHalf; base < n; base += kSortHalf) {
-            for (int i = tid; i < kSortHalf; i += kSortThreads) lds[kSortHalf + i] = base + i < n ? gk[base + i] : ~0ull;
-            __syncthreads();
-            bitonic_sort(lds, kSortLdsKeys);
-        }
-    }
+    detect::sort_keys(a.keys + (size_t)b * a.anchors, n, lds);
     const int m = min(n, kTopK);
     for (int i = tid; i < m; i += kSortThreads) {
         const unsigned long long key = lds[i];
@@ -557,15 +523,8 @@ static Plan make_plan(const af_retinaface_desc& d) {
 static int max_rows(const af_retinaface_desc& d) { return d.max_count > 0 ? std::min(d.keep_top_k, d.max_count) : d.keep_top_k; }
 
 static int check_desc(const af_retinaface_desc* d, bool frames) {
-    AF_REQUIRE(d, "retinaface: null descriptor");
-    AF_REQUIRE(d->batch >= 1 && d->batch <= 65535, "retinaface: batch %d out of [1, 65535]", d->batch);
-    AF_REQUIRE(d->height >= 1 && d->width >= 1 && d->height <= AF_RETINAFACE_MAX_SIDE && d->width <= AF_RETINAFACE_MAX_SIDE,
-               "retinaface: frame %dx%d out of [1, %d]", d->width, d->height, AF_RETINAFACE_MAX_SIDE);
-    if (frames) {
-        AF_REQUIRE(d->row_pitch >= 3LL * d->width, "retinaface: row pitch %lld < 3 * width", (long long)d->row_pitch);
-        AF_REQUIRE(d->batch == 1 || d->frame_stride >= d->row_pitch * d->height, "retinaface: frame stride %lld < pitch * height",
-                   (long long)d->frame_stride);
-    }
+    const int rc = detect::check_frames(d, "retinaface", AF_RETINAFACE_MAX_SIDE, frames);
+    if (rc != AF_OK) return rc;
     AF_REQUIRE(d->keep_top_k >= 1 && d->keep_top_k <= AF_RETINAFACE_MAX_KEEP, "retinaface: keep_top_k %d out of [1, %d]",
                d->keep_top_k, AF_RETINAFACE_MAX_KEEP);
     AF_REQUIRE(d->min_score == d->min_score, "retinaface: NaN min_score");
@@ -623,18 +582,9 @@ static void launch_dw(int ho, int wo, int B, hipStream_t s, const DwArgs& da) {
     hipLaunchKernelGGL((rf_dw<C>), dim3((ho * wo * (C / 4) + kThreads - 1) / kThreads, B), dim3(kThreads), 0, s, da);
 }
 
-struct Ctx {
-    const Plan& p;
-    hipStream_t s;
-    hipEvent_t* ev;
-    int k;
-    void mark() { if (ev) (void)hipEventRecord(ev[k++], s); }
-};
-
 // decode + sort + NMS mask + scan (launches 6..9 of the sequence above)
-static int post(Ctx& c, const af_retinaface_desc* d, char* ws, const float* loc, float* conf, const float* landms, int softmax,
-                float* out_rows, int32_t* out_count) {
-    const Plan& p = c.p;
+static int post(const Plan& p, hipStream_t s, Marks& mark, const af_retinaface_desc* d, char* ws, const float* loc, float* conf,
+                const float* landms, int softmax, float* out_rows, int32_t* out_count) {
     int* counts = (int*)(ws + p.counts_off);
     unsigned long long* keys = (unsigned long long*)(ws + p.keys_off);
     float* rows = (float*)(ws + p.rows_off);
@@ -644,22 +594,22 @@ static int post(Ctx& c, const af_retinaface_desc* d, char* ws, const float* loc,
     unsigned long long* mask = (unsigned long long*)(ws + p.mask_off);
     DecodeArgs da{loc, conf, landms, softmax, p.h, p.w, p.anchors, {p.lw[0], p.lw[1], p.lw[2]},
                   {p.lvl_off[0], p.lvl_off[1], p.lvl_off[2], p.lvl_off[3]}, counts, keys, rows};
-    hipLaunchKernelGGL(rf_decode, dim3((p.anchors + kThreads - 1) / kThreads, p.B), dim3(kThreads), 0, c.s, da);
+    hipLaunchKernelGGL(rf_decode, dim3((p.anchors + kThreads - 1) / kThreads, p.B), dim3(kThreads), 0, s, da);
     AF_CHECK_LAUNCH("rf_decode");
-    c.mark();
+    mark();
     AF_SET_MAX_LDS(rf_sort, kSortLdsBytes, "rf_sort");
     SortArgs sa{counts, keys, rows, p.anchors, mm, skeys, sboxes};
-    hipLaunchKernelGGL(rf_sort, dim3(p.B), dim3(kSortThreads), kSortLdsBytes, c.s, sa);
+    hipLaunchKernelGGL(rf_sort, dim3(p.B), dim3(kSortThreads), kSortLdsBytes, s, sa);
     AF_CHECK_LAUNCH("rf_sort");
-    c.mark();
+    mark();
     MaskArgs ma{mm, sboxes, mask};
-    hipLaunchKernelGGL(rf_nms_mask, dim3(kWords, kWords, p.B), dim3(64), 0, c.s, ma);
+    hipLaunchKernelGGL(rf_nms_mask, dim3(kWords, kWords, p.B), dim3(64), 0, s, ma);
     AF_CHECK_LAUNCH("rf_nms_mask");
-    c.mark();
+    mark();
     ScanArgs na{mm, skeys, mask, rows, p.anchors, max_rows(*d), max_rows(*d), d->min_score, out_rows, out_count};
-    hipLaunchKernelGGL(rf_nms_scan, dim3(p.B), dim3(64), 0, c.s, na);
+    hipLaunchKernelGGL(rf_nms_scan, dim3(p.B), dim3(64), 0, s, na);
     AF_CHECK_LAUNCH("rf_nms_scan");
-    c.mark();
+    mark();
     return AF_OK;
 }
 
@@ -675,15 +625,15 @@ static int detect(const af_retinaface_desc* d, const float* weights, const void*
                (long long)p.total_bytes);
     char* ws = (char*)workspace;
     float* act = (float*)workspace;
-    Ctx c{p, s, ev, 0};
-    c.mark();
+    Marks mark{s, ev, 0};
+    mark();
     const int B = p.B;
 
     StemArgs sa{(const uint8_t*)frames, d->frame_stride, d->row_pitch, p.h, p.w, p.h1, p.w1, weights + L.stem, act + p.x_off,
                 (int*)(ws + p.counts_off)};
     hipLaunchKernelGGL(rf_stem, dim3((p.h1 * p.w1 + kThreads - 1) / kThreads, B), dim3(kThreads), 0, s, sa);
     AF_CHECK_LAUNCH("rf_stem");
-    c.mark();
+    mark();
 
     // backbone: x -> dw -> t -> 1x1 -> x (or an FPN tap, which the next block then reads)
     const float* cur = act + p.x_off;
@@ -700,13 +650,13 @@ static int detect(const af_retinaface_desc* d, const float* weights, const void*
             default: launch_dw<256>(ho, wo, B, s, da); break;
         }
         AF_CHECK_LAUNCH("rf_dw");
-        c.mark();
+        mark();
         float* out = act + p.x_off;
         for (int l = 0; l < 3; ++l)
             if (kTapBlock[l] == i) out = act + p.tap_off[l];
         rc = run_conv(1, kBlockCin[i], B, s, conv_args(act + p.t_off, weights + L.pw[i], ho, wo, kBlockCout[i], kLeaky, out));
         if (rc != AF_OK) return rc;
-        c.mark();
+        mark();
         cur = out;
         h = ho;
         w = wo;
@@ -715,27 +665,27 @@ static int detect(const af_retinaface_desc* d, const float* weights, const void*
     // FPN: output3; output2 + up(output3) -> merge2; output1 + up(merge2) -> merge1
     rc = run_conv(1, 256, B, s, conv_args(act + p.tap_off[2], weights + L.fpn_out[2], p.lh[2], p.lw[2], 64, kLeaky, act + p.o3_off));
     if (rc != AF_OK) return rc;
-    c.mark();
+    mark();
     ConvArgs o2 = conv_args(act + p.tap_off[1], weights + L.fpn_out[1], p.lh[1], p.lw[1], 64, kLeaky, act + p.o2_off);
     o2.add = act + p.o3_off;
     o2.ah = p.lh[2];
     o2.aw = p.lw[2];
     rc = run_conv(1, 128, B, s, o2);
     if (rc != AF_OK) return rc;
-    c.mark();
+    mark();
     rc = run_conv(3, 64, B, s, conv_args(act + p.o2_off, weights + L.fpn_merge[1], p.lh[1], p.lw[1], 64, kLeaky, act + p.m2_off));
     if (rc != AF_OK) return rc;
-    c.mark();
+    mark();
     ConvArgs o1 = conv_args(act + p.tap_off[0], weights + L.fpn_out[0], p.lh[0], p.lw[0], 64, kLeaky, act + p.o1_off);
     o1.add = act + p.m2_off;
     o1.ah = p.lh[1];
     o1.aw = p.lw[1];
     rc = run_conv(1, 64, B, s, o1);
     if (rc != AF_OK) return rc;
-    c.mark();
+    mark();
     rc = run_conv(3, 64, B, s, conv_args(act + p.o1_off, weights + L.fpn_merge[0], p.lh[0], p.lw[0], 64, kLeaky, act + p.m1_off));
     if (rc != AF_OK) return rc;
-    c.mark();
+    mark();
 
     // SSH + heads per level; the heads write the three planes (the caller's raw buffer when given)
     float* planes = raw ? raw : act + p.planes_off;
@@ -759,7 +709,7 @@ static int detect(const af_retinaface_desc* d, const float* weights, const void*
         for (int k = 0; k < 5; ++k) {
             rc = run_conv(3, kSshCin[k], B, s, ssh[k]);
             if (rc != AF_OK) return rc;
-            c.mark();
+            mark();
         }
         ConvArgs hd = conv_args(cat, weights + L.head[l], lh, lw, 32, kNone, loc);
         const long long A = p.anchors, o = p.lvl_off[l];
@@ -769,9 +719,9 @@ static int detect(const af_retinaface_desc* d, const float* weights, const void*
         hd.seg[2] = Seg{landms + o * 10, A * 10, 20, 12};
         rc = run_conv(1, 64, B, s, hd);
         if (rc != AF_OK) return rc;
-        c.mark();
+        mark();
     }
-    return post(c, d, ws, loc, conf, landms, 1, out_rows, out_count);
+    return post(p, s, mark, d, ws, loc, conf, landms, 1, out_rows, out_count);
 }
 
 static int postprocess(const af_retinaface_desc* d, const float* loc, const float* conf, const float* landms, void* workspace,
@@ -783,36 +733,14 @@ static int postprocess(const af_retinaface_desc* d, const float* loc, const floa
     const Plan p = make_plan(*d);
     AF_REQUIRE(workspace_bytes >= (int64_t)p.total_bytes, "retinaface_postprocess: workspace %lld bytes < %lld",
                (long long)workspace_bytes, (long long)p.total_bytes);
-    Ctx c{p, s, ev, 0};
-    c.mark();
+    Marks mark{s, ev, 0};
+    mark();
     int* counts = (int*)((char*)workspace + p.counts_off);
     hipLaunchKernelGGL(rf_zero_counts, dim3((p.B + 255) / 256), dim3(256), 0, s, counts, p.B);
     AF_CHECK_LAUNCH("rf_zero_counts");
-    c.mark();
+    mark();
     // conf is only read when softmax == 0
-    return post(c, d, (char*)workspace, loc, const_cast<float*>(conf), landms, 0, out_rows, out_count);
-}
-
-// runs fn with n + 1 events on the stream and returns the n device times
-template <class F>
-static int timed(hipStream_t s, int n, float* ms, F fn) {
-    AF_REQUIRE(ms, "retinaface timed: null ms");
-    std::vector<hipEvent_t> ev;
-    for (int i = 0; i <= n; ++i) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) {
-            for (auto& e_ : ev) (void)hipEventDestroy(e_);
-            return set_error(AF_ERR_LAUNCH, "retinaface timed: hipEventCreate failed");
-        }
-        ev.push_back(e);
-    }
-    int rc = fn(ev.data());
-    hipError_t e = hipStreamSynchronize(s);
-    if (rc == AF_OK && e != hipSuccess) rc = set_error(AF_ERR_LAUNCH, "retinaface timed: %s", hipGetErrorString(e));
-    if (rc == AF_OK)
-        for (int i = 0; i < n; ++i) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-    for (auto& e_ : ev) (void)hipEventDestroy(e_);
-    return rc;
+    return post(p, s, mark, d, (char*)workspace, loc, const_cast<float*>(conf), landms, 0, out_rows, out_count);
 }
 
 }  // namespace retinaface
@@ -847,7 +775,7 @@ extern "C" int af_retinaface_detect_timed(const af_retinaface_desc* d, const flo
     int rc = af::retinaface::check_desc(d, true);
     if (rc != AF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    return af::retinaface::timed(s, AF_RETINAFACE_LAUNCHES, ms, [&](hipEvent_t* ev) {
+    return af::timed("retinaface_detect_timed", s, AF_RETINAFACE_LAUNCHES, ms, [&](hipEvent_t* ev) {
         return af::retinaface::detect(d, weights, frames, workspace, workspace_bytes, out_rows, out_count, raw, s, ev);
     });
 }
@@ -864,7 +792,7 @@ extern "C" int af_retinaface_postprocess_timed(const af_retinaface_desc* d, cons
     int rc = af::retinaface::check_desc(d, false);
     if (rc != AF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    return af::retinaface::timed(s, AF_RETINAFACE_POST_LAUNCHES, ms, [&](hipEvent_t* ev) {
+    return af::timed("retinaface_postprocess_timed", s, AF_RETINAFACE_POST_LAUNCHES, ms, [&](hipEvent_t* ev) {
         return af::retinaface::postprocess(d, loc, conf, landms, workspace, workspace_bytes, out_rows, out_count, s, ev);
     });
 }

@@ -10,14 +10,14 @@
 //   4. yunet_sort_nms         : per frame, sort (score desc, anchor index asc), drop score <= conf, cut to top_k, greedy NMS
 // A "DP unit" is YuNet's ConvDPUnit: Conv1x1 (bias, no activation) -> depthwise Conv3x3 (pad 1, bias) -> ReLU.  Zero padding
 // of the depthwise conv applies to the 1x1 conv's OUTPUT (bias included), so halo pixels outside the map are 0 in LDS.
-#include "af_common.h"
-
-#include <stdlib.h>
-
-#include <vector>
+#include "af_detect.h"
 
 namespace af {
 namespace yunet {
+
+using detect::kSortHalf;
+using detect::kSortLdsBytes;
+using detect::kSortThreads;
 
 constexpr int kT = 16;                 // output tile edge, in pixels of the unit's own resolution
 constexpr int kHalo = kT + 2;          // 1x1-conv tile incl. the depthwise conv's 1-pixel halo
@@ -28,13 +28,10 @@ constexpr int kUnitCout[kUnits] = {16, 16, 32, 32, 64, 64, 64, 64, 64, 64, 64, 6
 constexpr int kHeadCh = 16;            // cls, obj, bbox[4], kps[10]
 constexpr int kStemFloats = 27 * 16 + 16;
 constexpr int kHeadFloats = 64 * kHeadCh + kHeadCh + 9 * kHeadCh + kHeadCh;
-constexpr int kSortThreads = 1024;
-constexpr int kSortLdsBytes = 128 * 1024;                              // u64 keys while sorting, int4 kept boxes during NMS
-constexpr int kSortLdsKeys = kSortLdsBytes / 8;
 constexpr int kLaunches = 1 + (kUnits - 1) + 3 + 1;
 
 static_assert(AF_YUNET_MAX_TOPK * 16 <= kSortLdsBytes, "kept boxes must fit the sort kernel's LDS");
-static_assert(AF_YUNET_MAX_TOPK <= kSortLdsKeys / 2, "the chunked sort keeps kSortLdsKeys / 2 keys");
+static_assert(AF_YUNET_MAX_TOPK <= kSortHalf, "the chunked sort keeps kSortHalf keys");
 static_assert(AF_YUNET_LAUNCHES == kLaunches, "header launch count");
 
 constexpr int unit_floats(int u) { return kUnitCin[u] * kUnitCout[u] + kUnitCout[u] + 9 * kUnitCout[u] + kUnitCout[u]; }
@@ -266,7 +263,7 @@ __global__ __launch_bounds__(kThreads) void yunet_stem_unit0_pool(StemArgs a) {
 
 // One DP unit over a 16x16 output tile, 16 output channels at a time (a 18x18x16 f32 LDS tile, 20 KB): 1x1 conv into LDS, then
 // each thread one 2x2 quad x 4 channels of the depthwise conv, stored full and / or 2x2-max-pooled.
-template <int CIN, int COUT, bool MFMA>
+template <int CIN, int COUT>
 __global__ __launch_bounds__(kThreads) void yunet_dp_unit(UnitArgs a) {
     __shared__ float mid[kHalo * kHalo * 16];
     const int b = blockIdx.z;
@@ -280,10 +277,7 @@ __global__ __launch_bounds__(kThreads) void yunet_dp_unit(UnitArgs a) {
     const int fy = blockIdx.y * kT + 2 * qy, fx = blockIdx.x * kT + 2 * qx;
 #pragma unroll 1
     for (int g = 0; g < COUT / 16; ++g) {
-        if (MFMA)
-            pw_tile_mfma<CIN, COUT>(in, up, pw, pb, g, blockIdx.y * kT - 1, blockIdx.x * kT - 1, a.h, a.w, mid);
-        else
-            pw_tile<CIN, COUT>(in, up, pw, pb, g, blockIdx.y * kT - 1, blockIdx.x * kT - 1, a.h, a.w, mid);
+        pw_tile_mfma<CIN, COUT>(in, up, pw, pb, g, blockIdx.y * kT - 1, blockIdx.x * kT - 1, a.h, a.w, mid);
         __syncthreads();
         if (fy < a.h && fx < a.w) {
             const int ch = g * 16 + c4 * 4;
@@ -381,29 +375,8 @@ __device__ __forceinline__ float rect_overlap(int4 p, int4 q) {
     return 1.f - dist;
 }
 
-// ascending bitonic sort of lds[0, n2) (n2 a power of two) by the whole block
-__device__ __forceinline__ void lds_bitonic_sort(unsigned long long* buf, int n2) {
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n2; i += kSortThreads) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long x = buf[i], y = buf[l];
-                    if ((x > y) == ((i & k) == 0)) {
-                        buf[i] = y;
-                        buf[l] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// Per frame (one block): the candidate keys are sorted in LDS.  Up to kSortLdsKeys candidates are sorted whole; above that
-// only the smallest kSortLdsKeys / 2 keys can matter (top_k <= AF_YUNET_MAX_TOPK = kSortLdsKeys / 2), so the block keeps them
-// as a running set in the lower half of LDS and sorts it together with each next chunk of kSortLdsKeys / 2 keys: n / 8192
-// LDS sorts of 16 384 keys instead of one sort of n in memory.  Then one wave runs the greedy NMS over the sorted list; it
-// stops at the first score <= conf or after top_k candidates.
+// Per frame (one block): the candidate keys are sorted in LDS (detect::sort_keys; top_k <= AF_YUNET_MAX_TOPK = kSortHalf).
+// Then one wave runs the greedy NMS over the sorted list; it stops at the first score <= conf or after top_k candidates.
 __global__ __launch_bounds__(kSortThreads) void yunet_sort_nms(NmsArgs a) {
     extern __shared__ unsigned long long lds[];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -416,22 +389,8 @@ __global__ __launch_bounds__(kSortThreads) void yunet_sort_nms(NmsArgs a) {
         if (tid == 0) a.out_count[b] = n;
         return;
     }
-    if (n <= kSortLdsKeys) {
-        int n2 = 2;
-        while (n2 < n) n2 <<= 1;
-        for (int i = tid; i < n2; i += kSortThreads) lds[i] = i < n ? gk[i] : ~0ull;
-        __syncthreads();
-        lds_bitonic_sort(lds, n2);
-    } else {
-        constexpr int kHalf = kSortLdsKeys / 2;
-        for (int i = tid; i < kHalf; i += kSortThreads) lds[i] = gk[i];          // n > kSortLdsKeys > kHalf
-        for (int base = kHalf; base < n; base += kHalf) {
-            for (int i = tid; i < kHalf; i += kSortThreads) lds[kHalf + i] = base + i < n ? gk[base + i] : ~0ull;
-            __syncthreads();
-            lds_bitonic_sort(lds, kSortLdsKeys);           // lower half: the kHalf smallest keys so far, in order
-        }
-    }
-    const int m = min(n, a.top_k);                         // <= kSortLdsKeys / 2 on the chunked path
+    detect::sort_keys(gk, n, lds);
+    const int m = min(n, a.top_k);                         // <= kSortHalf
     for (int i = tid; i < m; i += kSortThreads) gk[i] = lds[i];
     __syncthreads();
     if (tid >= 64) return;
@@ -512,31 +471,16 @@ static Plan make_plan(const af_yunet_desc& d) {
 }
 
 static int check_desc(const af_yunet_desc* d) {
-    AF_REQUIRE(d, "yunet: null descriptor");
-    AF_REQUIRE(d->batch >= 1 && d->batch <= 65535, "yunet: batch %d out of [1, 65535]", d->batch);
-    AF_REQUIRE(d->height >= 1 && d->width >= 1 && d->height <= AF_YUNET_MAX_SIDE && d->width <= AF_YUNET_MAX_SIDE,
-               "yunet: frame %dx%d out of [1, %d]", d->width, d->height, AF_YUNET_MAX_SIDE);
-    AF_REQUIRE(d->row_pitch >= 3LL * d->width, "yunet: row pitch %lld < 3 * width", (long long)d->row_pitch);
-    AF_REQUIRE(d->batch == 1 || d->frame_stride >= d->row_pitch * d->height, "yunet: frame stride %lld < pitch * height",
-               (long long)d->frame_stride);
+    const int rc = detect::check_frames(d, "yunet", AF_YUNET_MAX_SIDE);
+    if (rc != AF_OK) return rc;
     AF_REQUIRE(d->top_k >= 1 && d->top_k <= AF_YUNET_MAX_TOPK, "yunet: top_k %d out of [1, %d]", d->top_k, AF_YUNET_MAX_TOPK);
     AF_REQUIRE(d->conf_threshold == d->conf_threshold && d->nms_threshold == d->nms_threshold, "yunet: NaN threshold");
     return AF_OK;
 }
 
 template <int CIN, int COUT>
-static void launch_unit(bool mfma, dim3 grid, hipStream_t s, const UnitArgs& ua) {
-    if (mfma)
-        hipLaunchKernelGGL((yunet_dp_unit<CIN, COUT, true>), grid, dim3(kThreads), 0, s, ua);
-    else
-        hipLaunchKernelGGL((yunet_dp_unit<CIN, COUT, false>), grid, dim3(kThreads), 0, s, ua);
-}
-
-// the DP units' 1x1 conv: MFMA (default; 2.2x the FMA form's frames/s at 1080p, B = 16) or FMA
-// (AF_YUNET_PW_MFMA=0), kept as the A/B form for measurements; read once
-static bool pw_mfma() {
-    static const bool on = [] { const char* e = getenv("AF_YUNET_PW_MFMA"); return !(e && e[0] == '0'); }();
-    return on;
+static void launch_unit(dim3 grid, hipStream_t s, const UnitArgs& ua) {
+    hipLaunchKernelGGL((yunet_dp_unit<CIN, COUT>), grid, dim3(kThreads), 0, s, ua);
 }
 
 static int detect(const af_yunet_desc* d, const float* weights, const void* frames, void* workspace, int64_t workspace_bytes,
@@ -552,8 +496,7 @@ static int detect(const af_yunet_desc* d, const float* weights, const void* fram
     int* counts = (int*)((char*)workspace + p.counts_off);
     unsigned long long* keys = (unsigned long long*)((char*)workspace + p.keys_off);
     float* rows = (float*)((char*)workspace + p.rows_off);
-    int k = 0;
-    auto mark = [&]() { if (ev) (void)hipEventRecord(ev[k++], s); };
+    Marks mark{s, ev, 0};
     mark();
 
     const int h4 = p.ph / 4, w4 = p.pw / 4;
@@ -576,17 +519,16 @@ static int detect(const af_yunet_desc* d, const float* weights, const void* fram
         {12, p.t223, p.t236, p.t246, N, hs[2], ws[2]},   // 242 = 223 + up2(236) -> 246
         {13, p.t214, p.t246, p.t256, N, hs[1], ws[1]},   // 252 = 214 + up2(246) -> 256
     };
-    const bool mfma = pw_mfma();
     for (const U& u : units) {
         UnitArgs ua{act + u.in, u.up == N ? nullptr : act + u.up, weights + unit_offset(u.unit), u.full == N ? nullptr : act + u.full,
                     u.pool == N ? nullptr : act + u.pool, u.h, u.w};
         const dim3 grid((u.w + kT - 1) / kT, (u.h + kT - 1) / kT, p.B);
         switch (kUnitCin[u.unit] * 1000 + kUnitCout[u.unit]) {
-            case 16016: launch_unit<16, 16>(mfma, grid, s, ua); break;
-            case 16032: launch_unit<16, 32>(mfma, grid, s, ua); break;
-            case 32032: launch_unit<32, 32>(mfma, grid, s, ua); break;
-            case 32064: launch_unit<32, 64>(mfma, grid, s, ua); break;
-            default: launch_unit<64, 64>(mfma, grid, s, ua); break;
+            case 16016: launch_unit<16, 16>(grid, s, ua); break;
+            case 16032: launch_unit<16, 32>(grid, s, ua); break;
+            case 32032: launch_unit<32, 32>(grid, s, ua); break;
+            case 32064: launch_unit<32, 64>(grid, s, ua); break;
+            default: launch_unit<64, 64>(grid, s, ua); break;
         }
         AF_CHECK_LAUNCH("yunet_dp_unit");
         mark();
@@ -626,24 +568,10 @@ extern "C" int af_yunet_detect(const af_yunet_desc* d, const float* weights, con
 
 extern "C" int af_yunet_detect_timed(const af_yunet_desc* d, const float* weights, const void* frames, void* workspace,
                                      int64_t workspace_bytes, float* out_rows, int32_t* out_count, float* raw, void* stream, float* ms) {
-    AF_REQUIRE(ms, "yunet_detect_timed: null ms");
     int rc = af::yunet::check_desc(d);
     if (rc != AF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    std::vector<hipEvent_t> ev;
-    for (int i = 0; i <= AF_YUNET_LAUNCHES; ++i) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) {
-            for (auto& ev_ : ev) (void)hipEventDestroy(ev_);
-            return af::set_error(AF_ERR_LAUNCH, "yunet_detect_timed: hipEventCreate failed");
-        }
-        ev.push_back(e);
-    }
-    rc = af::yunet::detect(d, weights, frames, workspace, workspace_bytes, out_rows, out_count, raw, s, ev.data());
-    hipError_t e = hipStreamSynchronize(s);
-    if (rc == AF_OK && e != hipSuccess) rc = af::set_error(AF_ERR_LAUNCH, "yunet_detect_timed: %s", hipGetErrorString(e));
-    if (rc == AF_OK)
-        for (int i = 0; i < AF_YUNET_LAUNCHES; ++i) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-    for (auto& ev_ : ev) (void)hipEventDestroy(ev_);
-    return rc;
+    return af::timed("yunet_detect_timed", s, AF_YUNET_LAUNCHES, ms, [&](hipEvent_t* ev) {
+        return af::yunet::detect(d, weights, frames, workspace, workspace_bytes, out_rows, out_count, raw, s, ev);
+    });
 }

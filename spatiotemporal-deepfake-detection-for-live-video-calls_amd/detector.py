@@ -15,6 +15,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from . import onnx_min
+from ._device import DeviceModel
 
 OUTPUT_NAMES = ["%s_%d" % (k, s) for k in ("cls", "obj", "bbox", "kps") for s in (8, 16, 32)]
 HEAD_KINDS = (("cls", 1), ("obj", 1), ("bbox", 4), ("kps", 10))      # channel order of the packed head: 16 channels
@@ -204,8 +205,12 @@ def split_raw(raw: np.ndarray, w: int, h: int) -> Dict[str, np.ndarray]:
     return {k: out[k] for k in OUTPUT_NAMES}
 
 
-class YuNet:
+class YuNet(DeviceModel):
     """Drop-in for preprocessing/yunet/yunet.py YuNet (cv2.FaceDetectorYN), running on the current HIP device."""
+
+    _weight_floats_fn = "af_yunet_weight_floats"
+    _workspace_bytes_fn = "af_yunet_workspace_bytes"
+    _detect_fn = ("af_yunet_detect", "YUNET_LAUNCHES")
 
     def __init__(self, modelPath, inputSize=[320, 320], confThreshold=0.6, nmsThreshold=0.3, topK=5000, backendId=0, targetId=0):
         self._modelPath = modelPath
@@ -221,9 +226,7 @@ class YuNet:
             data = f.read()
         self.sha256 = hashlib.sha256(data).hexdigest()
         self.plan = build_plan(onnx_min.parse_model(data))
-        self.weights_host = pack_weights(self.plan)
-        self._dev_weights = {}
-        self._workspaces = {}
+        super().__init__(pack_weights(self.plan))
 
     @property
     def name(self):
@@ -238,40 +241,9 @@ class YuNet:
         self._inputSize = tuple(int(v) for v in input_size)
 
     # ---- device side
-    def _weights(self, dev):
-        """the packed weights on `dev`, shared read-only by every stream: the one upload per device is waited for on the
-        host (set-up, once), so that a call on any other stream can read them"""
-        import torch
-        from . import _lib
-        w = self._dev_weights.get(dev)
-        if w is None:
-            if self.weights_host.size != _lib.lib.af_yunet_weight_floats():
-                raise RuntimeError("packed weights %d floats, libafhip expects %d" % (self.weights_host.size,
-                                                                                   _lib.lib.af_yunet_weight_floats()))
-            w = torch.from_numpy(self.weights_host).to(dev)
-            torch.cuda.current_stream(dev).synchronize()
-            self._dev_weights[dev] = w
-        return w
-
     def _desc(self, b, h, w, frame_stride, row_pitch, conf, nms, top_k):
         from . import _lib
         return _lib.YunetDesc(b, h, w, top_k, frame_stride, row_pitch, conf, nms)
-
-    def _workspace(self, dev, stream, desc):
-        """scratch of one (device, stream): activations, candidate counters, sort keys and decoded rows.  Calls on one
-        stream reuse it in stream order; calls on different streams never share it.  It is allocated while `stream` is
-        current, so when a larger frame replaces it, the caching allocator orders that free after the stream's kernels."""
-        import torch
-        from . import _lib
-        need = _lib.lib.af_yunet_workspace_bytes(C.byref(desc))
-        if need <= 0:
-            raise ValueError(_lib.lib.af_last_error().decode())
-        key = (dev, stream.cuda_stream)
-        ws = self._workspaces.get(key)
-        if ws is None or ws.numel() < need:
-            with torch.cuda.stream(stream):
-                ws = self._workspaces[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-        return ws
 
     def detect(self, frames_u8, raw: bool = False, conf: Optional[float] = None, nms: Optional[float] = None,
                top_k: Optional[int] = None, timings=None):
@@ -281,7 +253,6 @@ class YuNet:
         (device, stream) has its own scratch workspace, and the kernels of one call touch no other call's memory.  raw=True also returns the (B, anchors, 16) head outputs
         (see split_raw).  `timings`: a list that receives the per-kernel device times in ms (this call synchronises)."""
         import torch
-        from . import _lib
         if not isinstance(frames_u8, torch.Tensor) or frames_u8.device.type != "cuda":
             raise RuntimeError("YuNet.detect needs a (B, H, W, 3) uint8 tensor on a HIP device (there is no CPU path)")
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
@@ -303,12 +274,7 @@ class YuNet:
             stream = C.c_void_p(cur.cuda_stream)
             args = [C.byref(desc), C.c_void_p(wt.data_ptr()), C.c_void_p(frames_u8.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
                     C.c_void_p(rows.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(rawt.data_ptr() if raw else None), stream]
-            if timings is None:
-                _lib.check(_lib.lib.af_yunet_detect(*args), "yunet_detect")
-            else:
-                ms = (C.c_float * _lib.YUNET_LAUNCHES)()
-                _lib.check(_lib.lib.af_yunet_detect_timed(*args, ms), "yunet_detect_timed")
-                timings[:] = list(ms)
+            self._call(self._detect_fn, args, timings)
         return (rows, counts, rawt) if raw else (rows, counts)
 
     def infer(self, image):

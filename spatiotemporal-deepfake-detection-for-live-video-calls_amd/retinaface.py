@@ -17,6 +17,8 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from ._device import DeviceModel
+
 STEPS = (8, 16, 32)
 MIN_SIZES = ((16, 32), (64, 128), (256, 512))
 VARIANCE = (0.1, 0.2)
@@ -165,8 +167,13 @@ def _split_rows(rows: np.ndarray, n: int):
     return [(rows[i, :4].copy(), rows[i, 5:15].reshape(5, 2).copy(), rows[i, 4]) for i in range(n)]
 
 
-class FaceDetector:
+class FaceDetector(DeviceModel):
     """Drop-in for test_tools/ct/detection.FaceDetector (RetinaFace, mobilenet0.25) on HIP device `gpu_id`."""
+
+    _weight_floats_fn = "af_retinaface_weight_floats"
+    _workspace_bytes_fn = "af_retinaface_workspace_bytes"
+    _detect_fn = ("af_retinaface_detect", "RETINAFACE_LAUNCHES")
+    _postprocess_fn = ("af_retinaface_postprocess", "RETINAFACE_POST_LAUNCHES")
 
     def __init__(self, gpu_id=0, model_path=None, network="mobilenet"):
         if network != "mobilenet":
@@ -176,9 +183,7 @@ class FaceDetector:
         self.gpu_id = int(gpu_id)
         self.network = network
         self.state_dict = load(model_path)
-        self.weights_host = pack_weights(self.state_dict)
-        self._dev_weights = {}
-        self._workspaces = {}
+        super().__init__(pack_weights(self.state_dict))
 
     @classmethod
     def from_state_dict(cls, sd, gpu_id=0):
@@ -190,8 +195,7 @@ class FaceDetector:
         sd = _strip(sd)
         check_state_dict(sd)
         self.state_dict = sd
-        self.weights_host = pack_weights(sd)
-        self._dev_weights, self._workspaces = {}, {}
+        DeviceModel.__init__(self, pack_weights(sd))
         return self
 
     @property
@@ -200,34 +204,6 @@ class FaceDetector:
         return torch.device("cuda", self.gpu_id)
 
     # ---- device side
-    def _weights(self, dev):
-        """the packed weights on `dev`, shared read-only by every stream (uploaded once per device and waited for)"""
-        import torch
-        from . import _lib
-        w = self._dev_weights.get(dev)
-        if w is None:
-            if self.weights_host.size != _lib.lib.af_retinaface_weight_floats():
-                raise RuntimeError("packed weights %d floats, libafhip expects %d" % (
-                    self.weights_host.size, _lib.lib.af_retinaface_weight_floats()))
-            w = torch.from_numpy(self.weights_host).to(dev)
-            torch.cuda.current_stream(dev).synchronize()
-            self._dev_weights[dev] = w
-        return w
-
-    def _workspace(self, dev, stream, desc):
-        """scratch of one (device, stream), reused in stream order; allocated while `stream` is current"""
-        import torch
-        from . import _lib
-        need = _lib.lib.af_retinaface_workspace_bytes(C.byref(desc))
-        if need <= 0:
-            raise ValueError(_lib.lib.af_last_error().decode())
-        key = (dev, stream.cuda_stream)
-        ws = self._workspaces.get(key)
-        if ws is None or ws.numel() < need:
-            with torch.cuda.stream(stream):
-                ws = self._workspaces[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-        return ws
-
     @staticmethod
     def _desc(b, h, w, frame_stride, row_pitch, keep_top_k, max_count, min_score):
         from . import _lib
@@ -267,12 +243,7 @@ class FaceDetector:
             args = [C.byref(desc), C.c_void_p(wt.data_ptr()), C.c_void_p(frames_u8.data_ptr()), C.c_void_p(ws.data_ptr()),
                     ws.numel(), C.c_void_p(rows.data_ptr()), C.c_void_p(counts.data_ptr()),
                     C.c_void_p(rawt.data_ptr() if raw else None), C.c_void_p(cur.cuda_stream)]
-            if timings is None:
-                _lib.check(_lib.lib.af_retinaface_detect(*args), "retinaface_detect")
-            else:
-                ms = (C.c_float * _lib.RETINAFACE_LAUNCHES)()
-                _lib.check(_lib.lib.af_retinaface_detect_timed(*args, ms), "retinaface_detect_timed")
-                timings[:] = list(ms)
+            self._call(self._detect_fn, args, timings)
         if not raw:
             return rows, counts
         loc = rawt[:4 * b * a].view(b, a, 4)
@@ -302,12 +273,7 @@ class FaceDetector:
             args = [C.byref(desc), C.c_void_p(loc.data_ptr()), C.c_void_p(conf.data_ptr()), C.c_void_p(landms.data_ptr()),
                     C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(rows.data_ptr()), C.c_void_p(counts.data_ptr()),
                     C.c_void_p(cur.cuda_stream)]
-            if timings is None:
-                _lib.check(_lib.lib.af_retinaface_postprocess(*args), "retinaface_postprocess")
-            else:
-                ms = (C.c_float * _lib.RETINAFACE_POST_LAUNCHES)()
-                _lib.check(_lib.lib.af_retinaface_postprocess_timed(*args, ms), "retinaface_postprocess_timed")
-                timings[:] = list(ms)
+            self._call(self._postprocess_fn, args, timings)
         return rows, counts
 
     # ---- the reference's interface

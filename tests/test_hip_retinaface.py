@@ -120,11 +120,14 @@ def test_detect_matches_batch_detect(golden, dets):
 
 
 def test_batch_and_run_to_run_bitwise():
+    from af_mi355x import _lib
     det = detector(1, "sparse")
     frames = torch.from_numpy(synth.retinaface_frames(16, 181, 243, seed=7)).cuda()
     r16, c16 = det.detect_device(frames)
-    r16b, c16b = det.detect_device(frames)
+    ms = []
+    r16b, c16b = det.detect_device(frames, timings=ms)     # the timed entry point
     torch.cuda.synchronize()
+    assert len(ms) == _lib.RETINAFACE_LAUNCHES and all(t > 0 for t in ms), ms
     assert torch.equal(c16, c16b) and int(c16.max()) > 0
     for b in range(16):                    # rows past counts[b] are unspecified
         n = int(c16[b])

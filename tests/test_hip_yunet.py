@@ -101,9 +101,12 @@ def test_batch_equals_single_frames_bitwise(det):
 
 @pytest.mark.gpu
 def test_two_runs_are_bitwise_identical(det):
+    from af_mi355x import _lib
     x = torch.from_numpy(frames(3, 1920, 1080, seed=41)).to(_dev())
     a = [t.cpu() for t in det.detect(x, conf=0.0, top_k=2000)]
-    b = [t.cpu() for t in det.detect(x, conf=0.0, top_k=2000)]
+    ms = []
+    b = [t.cpu() for t in det.detect(x, conf=0.0, top_k=2000, timings=ms)]       # the timed entry point
+    assert len(ms) == _lib.YUNET_LAUNCHES and all(t > 0 for t in ms), ms
     assert torch.equal(a[1], b[1]) and int(a[1].min()) > 0
     for i in range(3):
         n = int(a[1][i])

@@ -4,7 +4,7 @@
 
 Per frame size (640x360, 1280x720, 1920x1080) and batch (1, 16): frames/s from device events over `iters` back-to-back
 af_yunet_detect calls after `warmup` calls; per-kernel device times (af_yunet_detect_timed: events between launches, so
-launch gaps are included); AF_YUNET_PW_MFMA=0 selects the DP units' FMA 1x1 instead of MFMA; FLOP and byte counts from shapes; and each launch's fraction of its lower bound
+launch gaps are included); FLOP and byte counts from shapes; and each launch's fraction of its lower bound
 max(FLOP / 157.3 TFLOP/s fp32, bytes / 8 TB/s), naming the bound.  Kernel times from a profiler: run
 `rocprofv3 --kernel-trace --stats -- python tools/bench_yunet.py` separately."""
 import argparse
@@ -90,9 +90,8 @@ def main():
             for k in kernels:
                 print("    %-22s %8.4f ms  %8.3f GFLOP %9.2f MB  %-5s bound, %.3f of it" % (
                     k["kernel"], k["ms"], k["gflop"], k["mb"], k["bound"], k["frac_of_bound"] or 0.0))
-    print(json.dumps({"device": torch.cuda.get_device_name(dev), "pw_1x1": "fma" if os.environ.get("AF_YUNET_PW_MFMA") == "0" else "mfma",
-                      "results": [{k: v for k, v in r.items() if k != "kernels"}
-                                                                              for r in results]}))
+    print(json.dumps({"device": torch.cuda.get_device_name(dev),
+                      "results": [{k: v for k, v in r.items() if k != "kernels"} for r in results]}))
     if args.json:
         with open(args.json, "w") as f:
             json.dump(results, f, indent=1)
