@@ -16,6 +16,7 @@ Fixtures
   f1b_logits.json   B=16 logits of BASELINE config[1]'s batch (W(0)) + 8 clips on the "hot" checkpoint W(3, hot), fp32/fp64
   f2_stages.npz     per-stage statistics + sampled activations for clip 0
   f3_kats.npz/.json per-layer-class known-answer tests on small tensors
+  f7b_dualrun_configs.*  the reference's DualEncoderAU_LMK at other head counts / depths / widths and 9..16 frames
   f9_dualrgb.*      the reference's tri-modal DualEncoderRGB (dualrun/model/dual_rgb.py): logits fp32 / fp64, masked / unmasked /
                     broadcast V
   f4_load.json      behaviour table of ``ModelBase.load`` on crafted checkpoints
@@ -34,7 +35,7 @@ import tempfile
 # reads these at start-up, hence `--f3` / `--dualrun` run in a process of their own; tests/test_oracle.py runs the oracle
 # the same way for these two fixtures.
 REPRODUCIBLE_ENV = {"MKL_CBWR": "COMPATIBLE", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
-if "--f3" in sys.argv or "--dualrun" in sys.argv:
+if "--f3" in sys.argv or "--dualrun" in sys.argv or "--dualrun-configs" in sys.argv:
     os.environ.update(REPRODUCIBLE_ENV)
 
 import numpy as np  # noqa: E402
@@ -55,7 +56,7 @@ CLIP_SEED = 2026
 
 
 def _reproducible():
-    assert all(os.environ.get(k) == v for k, v in REPRODUCIBLE_ENV.items()), "run as `gen_golden.py --f3` / `--dualrun`"
+    assert all(os.environ.get(k) == v for k, v in REPRODUCIBLE_ENV.items()), "run as `gen_golden.py --f3` / `--dualrun[-configs]`"
     torch.set_num_threads(1)
     return torch.backends.mkldnn.flags(enabled=False)
 
@@ -523,6 +524,60 @@ def gen_dualrun():
     np.savez_compressed(os.path.join(GOLD, "f7_dualrun.npz"), **out)
 
 
+# F7b: (tag, DualEncoderAU_LMK keyword arguments, frames, lengths or None).  The reference defaults (mlp_ratio 2.0: ff 512) at
+# 9..16 frames take the K-split linears with G = 1; lengths hold 0 (frame 0 kept), 1, T and more than T.  Depth 0 is not
+# recorded: the reference's nn.TransformerEncoder(num_layers=0) fails in eval mode (it reads layers[0]).
+DUAL_CONFIGS = (
+    ("ref_t16", dict(), 16, [16, 0, 1, 21, 9]),
+    ("ref_t12", dict(), 12, [12, 1, 0, 7, 13]),
+    ("ref_t12_full", dict(), 12, None),
+    ("h8_d2_ff384_t9", dict(heads=8, depth=2, mlp_ratio=1.5), 9, [9, 4, 0, 10]),
+    ("h1_d1_au4_lmk256_ff128_t16", dict(au_dim=4, lmk_dim=256, heads=1, depth=1, mlp_ratio=0.5), 16, [16, 3, 11]),
+    ("h32_d2_t16", dict(heads=32, depth=2), 16, [16, 2, 0, 17]),
+    ("h256_d1_t8", dict(heads=256, depth=1), 8, [8, 1, 5]),
+)
+
+
+def gen_dualrun_configs():
+    """F7b: the reference's ``DualEncoderAU_LMK`` away from the shipped setup (DUAL_CONFIGS): the constructor's defaults
+    (mlp_ratio 2.0, pool_tau 1.0), other head counts / depths / widths and input widths, at up to 16 frames.  Weights
+    ``dual_synthetic_state_dict(spec, seed)`` (hash recorded), inputs ``synthetic_dual_inputs``; outputs only."""
+    import importlib.util
+    from af_mi355x import dualrun
+    path = os.path.join(ref_import.REFERENCE_ROOT, "dualrun", "model", "dual_encoder.py")
+    spec_ = importlib.util.spec_from_file_location("ref_dual_encoder", path)
+    mod = importlib.util.module_from_spec(spec_)
+    spec_.loader.exec_module(mod)
+    out, cases = {}, []
+    for i, (tag, kw, frames, lengths) in enumerate(DUAL_CONFIGS):
+        args = dict(au_dim=36, lmk_dim=132, d_model=256, depth=4, heads=4, mlp_ratio=2.0, pool_tau=1.0)
+        args.update(kw)
+        net = mod.DualEncoderAU_LMK(dropout=0.1, **args).eval()
+        sp = dualrun.DualSpec(args["au_dim"], args["lmk_dim"], 256, args["depth"], args["heads"], int(256 * args["mlp_ratio"]),
+                              args["pool_tau"])
+        lay = [(k, tuple(v.shape)) for k, v in net.state_dict().items()]
+        assert lay == [(k, tuple(sh)) for k, sh in dualrun.dual_state_dict_layout(sp)], "product dualrun table disagrees (%s)" % tag
+        seed = WEIGHT_SEED + 11 + i
+        sd = dualrun.dual_synthetic_state_dict(sp, seed=seed)
+        net.load_state_dict(sd)
+        batch = 3 if lengths is None else len(lengths)
+        A, L, _ = dualrun.synthetic_dual_inputs(batch, sp, frames=frames, seed=CLIP_SEED + 11 + i)
+        ln = None if lengths is None else torch.tensor(lengths, dtype=torch.int32)
+        with torch.no_grad(), _reproducible():
+            o32 = net(A, L, ln, return_z=True)
+        out[tag + "_logits_f32"] = o32["bin_logits"].numpy()
+        out[tag + "_z_f32"] = o32["z"].numpy()
+        cases.append({"tag": tag, "args": args, "ff": sp.ff, "frames": frames, "batch": batch, "lengths": lengths,
+                      "weights_seed": seed, "inputs_seed": CLIP_SEED + 11 + i, "weights_sha256": synth.state_dict_sha256(sd)})
+        print("F7b dualrun", tag, "logits", o32["bin_logits"].numpy().round(5).tolist())
+    with open(os.path.join(GOLD, "f7b_dualrun_configs.json"), "w") as f:
+        json.dump({"source": "reference dualrun/model/dual_encoder.py DualEncoderAU_LMK, eval, PyTorch CPU, oneDNN off, "
+                             "MKL_CBWR=COMPATIBLE, 1 thread, weights dual_synthetic_state_dict(spec, weights_seed), inputs "
+                             "synthetic_dual_inputs(batch, spec, frames, inputs_seed), lengths as listed (null: none)",
+                   "cases": cases}, f, indent=1)
+    np.savez_compressed(os.path.join(GOLD, "f7b_dualrun_configs.npz"), **out)
+
+
 def synthetic_aligner_case(rng, frames, size, mirrored=False):
     """per-frame (ldm5, ldm68, big box): a face whose 5 points are the aligner's standard points under a random similarity
     (+ per-frame jitter), boxes of slightly different origin / size per frame, as the trackers upstream produce"""
@@ -645,6 +700,7 @@ def main():
     gen_f1b(clf)
     gen_slowfast()
     subprocess.check_call([sys.executable, os.path.abspath(__file__), "--dualrun"])
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--dualrun-configs"])
     gen_dualrun_rgb()
     gen_aligner()
     gen_plugin_host()
@@ -663,6 +719,9 @@ if __name__ == "__main__":
     elif "--dualrun" in sys.argv:
         os.makedirs(GOLD, exist_ok=True)
         gen_dualrun()
+    elif "--dualrun-configs" in sys.argv:
+        os.makedirs(GOLD, exist_ok=True)
+        gen_dualrun_configs()
     elif "--dualrun-rgb" in sys.argv:
         os.makedirs(GOLD, exist_ok=True)
         torch.set_num_threads(8)

@@ -33,14 +33,18 @@ struct DualArgs {
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 
 // y[t][n] = act(bias[n] + sum_k x[t][k] * Wt[k][n]) (+ res[t][n]);  x, y, res in LDS, Wt / bias in global memory.
-// The 1024 threads cover the N columns once (N = 768) or G = 1024 / N times (N = 256: the K range is split over G thread
-// groups whose partial sums meet in `part` [G][TT][N], G = 4 for T <= 8, else 2); ends with the workgroup synchronised.
+// The 1024 threads cover the N columns once (N = 768) or G times (N = 256: the K range is split over G thread groups whose
+// partial sums meet in `part` [G][TT][N], G = 4 for T <= 8, else 2); ends with the workgroup synchronised.
+// G is the largest of GMAX, 2, 1 with G * N threads and G * TT * N floats of `part` (DUAL_PART): at TT = 16 an MLP width
+// N in (256, 512] gets G = 1, since G = 2 would need up to 16384 floats.
+constexpr int DUAL_PART = 32 * DUAL_D;  // floats reserved for `part` (32 KB): GMAX * TT * 256 at both TT
 template <int TT>
 __device__ __forceinline__ void linear_rows(const float* xs, int ldx, int K, const float* Wt, const float* bias, int N,
                                             float* ys, int ldy, int T, bool gelu, const float* res, int ldr, float* part) {
     const int tid = threadIdx.x;
-    constexpr int GMAX = TT <= 8 ? 4 : 2;                                // `part` holds GMAX x TT x 256 floats (32 KB)
-    const int G = N * GMAX <= DUAL_THREADS ? GMAX : (N * 2 <= DUAL_THREADS ? 2 : 1);     // N = 256 -> K groups; N = 768 -> 1
+    constexpr int GMAX = TT <= 8 ? 4 : 2;
+    const int G = N * GMAX <= DUAL_THREADS && GMAX * TT * N <= DUAL_PART ? GMAX
+                : (N * 2 <= DUAL_THREADS && 2 * TT * N <= DUAL_PART ? 2 : 1);          // N = 256 -> GMAX K groups; N = 768 -> 1
     const int n = tid % N, kg = tid / N;
     const int kspan = ((K / G + 3) / 4) * 4;                             // K slice per group, a multiple of 4
     float acc[TT];
@@ -118,8 +122,8 @@ __global__ __launch_bounds__(DUAL_THREADS) void dual_branch_kernel(const DualArg
     float* y = h + TT * D;                  // [TT][D]   LayerNorm output / scratch
     float* o = y + TT * D;                  // [TT][D]   attention output / input rows
     float* big = o + TT * D;                // [TT][768] qkv, MLP hidden
-    float* part = big + TT * DUAL_MAXW;     // [G][TT][D]  partial sums of the K-split linears (32 KB)
-    float* sc = part + 32 * D;          // [heads][TT][TT] attention probabilities; pooling weights
+    float* part = big + TT * DUAL_MAXW;     // [G][TT][N]  partial sums of the K-split linears (DUAL_PART floats)
+    float* sc = part + DUAL_PART;       // [heads][TT][TT] attention probabilities; pooling weights
     const int tid = threadIdx.x, clip = blockIdx.x, br = blockIdx.y, T = a.T;
     const int din = a.din[br];
     int len = a.lengths ? a.lengths[clip] : T;
@@ -399,7 +403,7 @@ extern "C" int af_dual_branch_encoders(int branches, const float* const* x, cons
     a.inv_tau = 1.0f / (pool_tau > 1e-3f ? pool_tau : 1e-3f);
     const int tt = frames <= 8 ? 8 : 16;
     const int hmax = heads > 4 ? heads : 4;
-    const int lds = (3 * tt * DUAL_D + tt * DUAL_MAXW + 32 * DUAL_D + hmax * tt * tt) * 4;
+    const int lds = (3 * tt * DUAL_D + tt * DUAL_MAXW + DUAL_PART + hmax * tt * tt) * 4;
     AF_REQUIRE(lds <= 160 * 1024, "dual_branch_encoders: %d heads do not fit LDS", heads);
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = tt == 8 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&dual_branch_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)

@@ -220,6 +220,8 @@ extern "C" int af_linear(const float* x, const float* w, const float* b, int row
 extern "C" int af_avgpool_fc_scores(const af_pool_desc* d, const void* in, const float* fc_w, const float* fc_b,
                                     int num_classes, float* pooled, float* logits, float* scores, void* stream) {
     AF_REQUIRE(in && fc_w && fc_b && pooled && logits && num_classes > 0, "avgpool_fc: null argument");
+    AF_REQUIRE(!scores || num_classes == 1 || num_classes == 2,                 // checked again by af_linear_scores, after the pool
+               "avgpool_fc: scores are defined for 1 (sigmoid) or 2 (softmax[:,1]) classes, got %d", num_classes);
     int rc = check_avgpool(d, "avgpool_fc");
     if (rc) return rc;
     rc = launch_avgpool(d, in, pooled, d->c, (hipStream_t)stream);

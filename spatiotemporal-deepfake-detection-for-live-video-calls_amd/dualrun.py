@@ -113,6 +113,33 @@ def sinusoid_table(frames: int, d_model: int) -> torch.Tensor:
     return pe
 
 
+# af_dual_branch_encoders' LDS check (csrc/af_dual.hip): one dual_branch_kernel workgroup, frames padded to 8 or 16
+_BRANCH_LDS_LIMIT = 160 * 1024
+
+
+def _branch_lds_bytes(frames: int, heads: int) -> int:
+    tt = 8 if frames <= 8 else 16
+    return (3 * tt * 256 + tt * 768 + 32 * 256 + max(heads, 4) * tt * tt) * 4
+
+
+def check_branch_spec(spec: DualSpec, max_frames: int = 16) -> int:
+    """Raises ValueError for a setup that af_dual_branch_encoders cannot run; returns the most frames per clip it can run
+    (16, or 8 for 64..256 heads, whose attention probabilities fit LDS only at 8 frames)."""
+    if spec.d_model != 256 or spec.heads < 1 or spec.d_model % spec.heads:
+        raise ValueError("the HIP branch kernel is built for d_model = 256 (one channel per thread) and heads dividing it "
+                         "(got d_model %d, heads %d)" % (spec.d_model, spec.heads))
+    if spec.depth < 0:
+        raise ValueError("depth must be >= 0 (got %d)" % spec.depth)
+    for name, din in spec.branches():
+        if din < 4 or din > 256 or din % 4:
+            raise ValueError("%s: the HIP branch kernel takes 4..256 input features, a multiple of 4 (got %d)" % (name, din))
+    if spec.ff < 4 or spec.ff > 768 or spec.ff % 4:
+        raise ValueError("dim_feedforward = int(d_model * mlp_ratio) must be 4..768, a multiple of 4, for the HIP branch kernel "
+                         "(got %d)" % spec.ff)
+    # every head count that divides 256 fits at 8 frames (256 heads: 144 KB)
+    return max_frames if _branch_lds_bytes(max_frames, spec.heads) <= _BRANCH_LDS_LIMIT else 8
+
+
 class _Pool(nn.Module):
     def __init__(self, d):
         super().__init__()
@@ -194,9 +221,8 @@ class DualEncoderAU_LMK(nn.Module):
         super().__init__()
         if use_dat:
             raise NotImplementedError("the domain-adversarial head is training-only")
-        if d_model != 256 or d_model % heads:
-            raise ValueError("the HIP branch kernel is built for d_model = 256 (one channel per thread)")
         self.spec = DualSpec(au_dim, lmk_dim, d_model, depth, heads, int(d_model * mlp_ratio), float(pool_tau), proj_dim)
+        self.max_frames = check_branch_spec(self.spec, self.MAX_FRAMES)
         self.au_enc = _Branch(au_dim, self.spec)
         self.lmk_enc = _Branch(lmk_dim, self.spec)
         self.head = nn.Sequential(nn.LayerNorm(2 * d_model), nn.Linear(2 * d_model, 2 * d_model), nn.GELU(), nn.Dropout(0.2),
@@ -241,8 +267,8 @@ class DualEncoderAU_LMK(nn.Module):
         sp = self.spec
         if L.shape[:2] != (B, T) or A.shape[2] != sp.au_dim or L.shape[2] != sp.lmk_dim:
             raise ValueError("expected A (B,T,%d) and L (B,T,%d)" % (sp.au_dim, sp.lmk_dim))
-        if T < 1 or T > self.MAX_FRAMES:
-            raise ValueError("1..%d frames per clip (got %d)" % (self.MAX_FRAMES, T))
+        if T < 1 or T > self.max_frames:
+            raise ValueError("1..%d frames per clip with %d heads (got %d)" % (self.max_frames, sp.heads, T))
         dev = A.device
         if B == 0:
             out = {"bin_logits": A.new_zeros((0,), dtype=torch.float32), "dom_logits": None}
@@ -338,9 +364,8 @@ class DualEncoderRGB(nn.Module):
             raise ValueError("dim_feedforward = int(d_model * ff_dim) = %d: upstream passes ff_dim into BranchEncoder's mlp_ratio "
                              "slot (dual_rgb.py:59-60); the HIP branch kernel holds <= 768 - pass ff_dim = 3.0 for the shipped "
                              "checkpoints' 768-wide layers" % ff)
-        if d_model != 256 or d_model % heads:
-            raise ValueError("the HIP branch kernel is built for d_model = 256 (one channel per thread)")
         self.spec = DualSpec(au_dim, lmk_dim, d_model, depth, heads, ff, 0.7, 128)     # BranchEncoder's default pool_tau
+        self.max_frames = check_branch_spec(self.spec, self.MAX_FRAMES)
         self.au_enc = _Branch(au_dim, self.spec)
         self.lmk_enc = _Branch(lmk_dim, self.spec)
         self.vis_dim = int(vis_dim)
@@ -401,8 +426,8 @@ class DualEncoderRGB(nn.Module):
         dev = A.device
         if L.shape[:2] != (B, T) or A.shape[2] != sp.au_dim or L.shape[2] != sp.lmk_dim:
             raise ValueError("expected A (B,T,%d) and L (B,T,%d)" % (sp.au_dim, sp.lmk_dim))
-        if T < 1 or T > self.MAX_FRAMES:
-            raise ValueError("1..%d frames per clip (got %d)" % (self.MAX_FRAMES, T))
+        if T < 1 or T > self.max_frames:
+            raise ValueError("1..%d frames per clip with %d heads (got %d)" % (self.max_frames, sp.heads, T))
         lengths = None
         if key_padding_mask is not None:
             if key_padding_mask.shape != (B, T) or key_padding_mask.dtype != torch.bool:

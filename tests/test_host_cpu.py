@@ -87,6 +87,36 @@ def test_dualrun_encoder_layout_and_errors():
         dualrun.DualEncoderAU_LMK(use_dat=True, domain_classes=3)
 
 
+@pytest.mark.parametrize("kw,why", [
+    (dict(au_dim=17), "multiple of 4"), (dict(lmk_dim=260), "4..256"), (dict(lmk_dim=0), "4..256"),
+    (dict(mlp_ratio=2.0 + 1 / 256), "dim_feedforward"), (dict(mlp_ratio=3.5), "dim_feedforward"),
+    (dict(mlp_ratio=0.01), "dim_feedforward"), (dict(heads=3), "heads dividing"), (dict(heads=0), "heads dividing"),
+    (dict(d_model=512, mlp_ratio=1.5), "d_model = 256"), (dict(depth=-1), "depth")])
+def test_dual_classes_reject_setups_the_kernel_cannot_run(kw, why):
+    """af_dual_branch_encoders takes 4..256 input features and dim_feedforward 4..768, each a multiple of 4, and a head
+    count that divides 256: both drop-in classes refuse anything else when they are built, not at the first forward"""
+    from af_mi355x import dualrun
+    with pytest.raises(ValueError, match=re.escape(why)):
+        dualrun.DualEncoderAU_LMK(**kw)
+    rgb = dict(au_dim=36, lmk_dim=132, vis_dim=2048, ff_dim=3.0)
+    rgb.update({"ff_dim" if k == "mlp_ratio" else k: v for k, v in kw.items()})
+    with pytest.raises(ValueError, match=re.escape(why)):
+        dualrun.DualEncoderRGB(**rgb)
+
+
+def test_dual_classes_frame_limit_follows_the_head_count():
+    """up to 32 heads fit LDS at 16 frames; 64..256 heads only at 8 (af_dual_branch_encoders' LDS check): such a module is
+    built, and its forward refuses a longer clip with a ValueError (tests/test_hip_dual_configs.py)"""
+    from af_mi355x import dualrun
+    for heads, frames in ((1, 16), (4, 16), (32, 16), (64, 8), (256, 8)):
+        assert dualrun.DualEncoderAU_LMK(heads=heads).max_frames == frames
+        assert dualrun.DualEncoderRGB(36, 132, 2048, heads=heads, ff_dim=2.0).max_frames == frames
+        assert dualrun._branch_lds_bytes(frames, heads) <= 160 * 1024
+    assert dualrun._branch_lds_bytes(16, 64) > 160 * 1024
+    ok = dualrun.DualEncoderAU_LMK(au_dim=4, lmk_dim=256, depth=0, heads=1, mlp_ratio=0.5)
+    assert ok.spec.ff == 128 and ok.max_frames == 16
+
+
 def test_last_linear_is_head_projection(clf):
     lin = [m for m in clf.modules() if isinstance(m, torch.nn.Linear)][-1]
     assert lin is clf.network.resnet.head.projection and lin.in_features == 2048 and lin.out_features == 1

@@ -83,6 +83,21 @@ zf, gate = dualrun_oracle.gated_moe(msd, torch.from_numpy(st["moe_z_rgb"]), torc
 outputs["moe_z"], outputs["moe_gate"] = zf.numpy(), gate.numpy()
 '''
 
+DUAL_CONFIGS_SCRIPT = r'''
+import dualrun_oracle
+from af_mi355x import dualrun
+outputs = {}
+for c in load_json("f7b_dualrun_configs.json")["cases"]:
+    a = c["args"]
+    sp = dualrun.DualSpec(a["au_dim"], a["lmk_dim"], a["d_model"], a["depth"], a["heads"], c["ff"], a["pool_tau"])
+    sd = dualrun.dual_synthetic_state_dict(sp, seed=c["weights_seed"])
+    A, L, _ = dualrun.synthetic_dual_inputs(c["batch"], sp, frames=c["frames"], seed=c["inputs_seed"])
+    lengths = None if c["lengths"] is None else torch.tensor(c["lengths"], dtype=torch.int32)
+    logits, z = dualrun_oracle.dual_forward(sd, A, L, lengths, heads=sp.heads, tau=sp.pool_tau)
+    outputs[c["tag"] + "_logits_f32"], outputs[c["tag"] + "_z_f32"] = logits.numpy(), z.numpy()
+    outputs[c["tag"] + "_sha"] = np.frombuffer(synth_sha(sd).encode(), dtype=np.uint8)
+'''
+
 
 def run_reproducibly(script, tmp_path):
     """runs `script` (which fills the dict `outputs`) in a child under REPRODUCIBLE_ENV, oneDNN off, one thread"""
@@ -193,6 +208,24 @@ def test_dualrun_oracle_matches_reference(tmp_path):
         np.testing.assert_allclose(got[tag + "_z_f32"], st[tag + "_z_f32"], rtol=2e-6, atol=5e-6)
     np.testing.assert_allclose(got["moe_z"], st["moe_z"], rtol=1e-6, atol=1e-6)
     np.testing.assert_allclose(got["moe_gate"], st["moe_gate"], rtol=1e-6, atol=1e-7)
+
+
+def test_dualrun_oracle_matches_reference_at_other_configs(tmp_path):
+    """oracle/dualrun_oracle.py against the reference's DualEncoderAU_LMK away from the shipped setup
+    (tests/golden/f7b_dualrun_configs.*): its defaults (ff 512, pool_tau 1.0) at 12 and 16 frames, 1 / 8 / 32 / 256 heads,
+    input widths 4 and 256, ff 128 and 384, and lengths of 0, 1, T and more than T.  This pins the oracle that the GPU
+    sweep in tests/test_hip_dual_configs.py uses at every shape.  Both sides are fp32 with different summation orders: the
+    logits agree to 1.0e-6, z to 6.7e-5 (ref_t12_full; the 16-frame clip of length 9 in ref_t16 is the least well
+    conditioned: there both sit 2e-4 from the fp64 oracle), so z is held to the fp32 GPU gate."""
+    g = load_json("f7b_dualrun_configs.json")
+    st = load_npz("f7b_dualrun_configs.npz")
+    assert len(g["cases"]) == 7
+    got = run_reproducibly("from af_mi355x.synth import state_dict_sha256 as synth_sha\n" + DUAL_CONFIGS_SCRIPT, tmp_path)
+    for c in g["cases"]:
+        tag = c["tag"]
+        assert bytes(got[tag + "_sha"]).decode() == c["weights_sha256"], tag
+        np.testing.assert_allclose(got[tag + "_logits_f32"], st[tag + "_logits_f32"], rtol=0, atol=2e-6, err_msg=tag)
+        np.testing.assert_allclose(got[tag + "_z_f32"], st[tag + "_z_f32"], rtol=2e-5, atol=1e-4, err_msg=tag)
 
 
 def test_checkpoint_unwrap_rules():
