@@ -380,6 +380,36 @@ typedef struct af_align_crop {
 int af_align_plan_u8(const af_align_crop* crops, int n, int canvas_h, int canvas_w, const double* tfm, int size,
                      af_stage_rect* rects, af_align_frame* frames, int64_t* total_bytes, int32_t* bad_frame);
 
+/* Window-batch warp: the offline evaluator's clip loop (altfreezing/demo.py:304-339) aligns EVERY clip_size-frame window of a face
+ * track, stride 1, so consecutive windows share all but one crop.  The crops of the track sit once in a caller-owned device pool;
+ * one launch warps up to AF_WINDOW_MAX_BATCH windows x clip_size frames out of it into `out`, device (n_windows, clip_size, size,
+ * size, 3) uint8 - the layout af_pack_input_u8 takes.  Same arithmetic as af_warp_affine_clip_u8, bit for bit.
+ *
+ * af_window_batch_plan_u8 (host only, no device work) fills the launch's table into `table`, a caller-owned HOST buffer (pinned,
+ * for an asynchronous copy) of af_window_batch_table_bytes(n_windows, clip_size) bytes, 8-byte aligned; the caller copies it to
+ * the device and hands af_warp_affine_windows_u8 the device copy with the same n_windows / clip_size / size.  The library
+ * allocates nothing.
+ *   windows[w]: the forward 2x3 matrix as passed to cv2.warpAffine (inverted here in OpenCV's order of operations) and the canvas;
+ *   frames[w * clip_size + t]: byte offset of the frame's HxWx3 crop (tightly packed rows) in the pool, its size, its paste
+ *     position on window w's canvas.  A crop that does not fit its window's canvas is AF_ERR_ARG with *bad_window / *bad_frame
+ *     set (numpy's slice assignment raises there in the reference); 3 readable bytes must follow every crop (pool_bytes is checked:
+ *     the kernel reads the two taps of a source row as 6 bytes and gives a tap outside the crop weight 0);
+ *   size: a multiple of 4, at most AF_WINDOW_MAX_SIZE.
+ * What the launch cannot check: the table is device memory, so af_warp_affine_windows_u8 trusts its offsets, crop sizes and paste
+ * positions as the planner wrote them - hand it only a copy of a table af_window_batch_plan_u8 filled for this pool.  The kernel
+ * compares the table's header with n_windows / clip_size / size and writes nothing on a mismatch; the call still returns AF_OK and
+ * `out` keeps its old contents, which the caller cannot detect - plan and launch with the same three numbers. */
+#define AF_WINDOW_MAX_BATCH 64
+#define AF_WINDOW_MAX_SIZE 1024
+typedef struct af_window_desc {
+    double tfm[6];
+    int32_t canvas_h, canvas_w;
+} af_window_desc;
+int64_t af_window_batch_table_bytes(int n_windows, int clip_size);
+int af_window_batch_plan_u8(const af_window_desc* windows, const af_align_frame* frames, int n_windows, int clip_size, int size,
+                            int64_t pool_bytes, void* table, int64_t table_bytes, int32_t* bad_window, int32_t* bad_frame);
+int af_warp_affine_windows_u8(const void* pool, const void* table, int n_windows, int clip_size, int size, void* out, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,

@@ -37,6 +37,13 @@ class AlignCrop(C.Structure):
 ALIGN_MAX_FRAMES = 64
 
 
+class WindowDesc(C.Structure):
+    _fields_ = [("tfm", C.c_double * 6), ("canvas_h", C.c_int32), ("canvas_w", C.c_int32)]
+
+
+WINDOW_MAX_BATCH, WINDOW_MAX_SIZE, WINDOW_TABLE_HEADER = 64, 1024, 16
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n", "t", "h", "w", "c", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw", "to", "ho", "wo", "dtype",
@@ -114,6 +121,10 @@ ABI = {
     "af_conv_ca_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 3),
     "af_stage_rows_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "af_align_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "af_window_batch_table_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "af_window_batch_plan_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p]),
+    "af_warp_affine_windows_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6

@@ -11,6 +11,7 @@
 // Integer work: bit-exact against oracle/aligner_oracle.py; against cv2 itself the parity is unpinned (cv2 is absent
 // from the build image and the reference holds no aligned frame).
 // HBM-bound byte work: one thread per destination pixel, 4 x 3 source bytes in, 3 bytes out; a clip is ~5 MB.
+// (warp_affine_windows_kernel further down does the same for many windows of a track in one launch, four pixels per thread.)
 #include "af_common.h"
 #include <cmath>
 #include <string.h>
@@ -68,7 +69,166 @@ __global__ __launch_bounds__(256) void warp_affine_clip_kernel(const AlignArgs a
     }
 }
 
+// warpAffine(): forward 2x3 matrix -> dst-to-src map, in double, same order of operations (volatile: no contraction)
+static void invert_affine_cv(const double* tfm, double* inv) {
+    volatile double M[6];
+    for (int i = 0; i < 6; ++i) M[i] = tfm[i];
+    volatile double D = M[0] * M[4] - M[1] * M[3];
+    D = D != 0 ? 1.0 / D : 0.0;
+    volatile double A11 = M[4] * D, A22 = M[0] * D;
+    M[0] = A11; M[1] = M[1] * -D; M[3] = M[3] * -D; M[4] = A22;
+    volatile double t0 = -M[0] * M[2], t1 = M[1] * M[5], t2 = -M[3] * M[2], t3 = M[4] * M[5];
+    volatile double b1 = t0 - t1, b2 = t2 - t3;
+    M[2] = b1; M[5] = b2;
+    for (int i = 0; i < 6; ++i) inv[i] = M[i];
+}
+
+// ---- window-batch warp: every (window, frame) of up to AF_WINDOW_MAX_BATCH sliding windows of one face track in one launch ----
+// The windows of a track share their crops (stride 1: 31 of 32), so the crops sit once in a device pool and each window brings
+// its own dst -> src map and paste offsets.  Those tables are too big for kernel arguments: af_window_batch_plan_u8 writes them
+// into a caller-owned host buffer (layout below), the caller copies it to the device once per batch.
+// Same integers as warp_affine_clip_kernel.  What differs is how they are produced: a block owns WB_ROWS rows of one
+// (window, frame); the column terms adelta[x] / bdelta[x] and the row terms X0[y] / Y0[y] (the only double arithmetic) are
+// tabulated in LDS once per block, as OpenCV tabulates them; a thread makes four consecutive pixels and stores them as one
+// 12-byte store; the two taps of a source row are read as 6 contiguous bytes (a dword and a half-word load, unaligned) from a
+// clamped address, and a tap outside the crop gets weight 0 instead of a branch.
+constexpr int WB_ROWS = 32, WB_THREADS = 256;
+struct WindowTableHeader { int32_t n_windows, clip_size, size, reserved; };
+struct WindowXform { double m[6]; };                             // dst -> src map (already inverted)
+
+static inline int64_t window_table_bytes(int n_windows, int clip_size) {
+    return (int64_t)sizeof(WindowTableHeader) + (int64_t)n_windows * sizeof(WindowXform) + (int64_t)n_windows * clip_size * sizeof(af_align_frame);
+}
+
+__global__ __launch_bounds__(WB_THREADS) void warp_affine_windows_kernel(const unsigned char* __restrict__ pool, const unsigned char* __restrict__ table,
+                                                                         unsigned char* __restrict__ out, int n_windows, int clip_size, int size,
+                                                                         int tiles) {
+    __shared__ int s_ad[AF_WINDOW_MAX_SIZE], s_bd[AF_WINDOW_MAX_SIZE], s_x0[WB_ROWS], s_y0[WB_ROWS];
+    const WindowTableHeader hd = *(const WindowTableHeader*)table;
+    if (hd.n_windows != n_windows || hd.clip_size != clip_size || hd.size != size) return;   // not this launch's table
+    const int bid = blockIdx.x;                                   // work item k = window * clip_size + frame, window-major
+    const int k = bid / tiles, tile = bid - k * tiles, y0 = tile * WB_ROWS;
+    const WindowXform* xf = (const WindowXform*)(table + sizeof(WindowTableHeader));
+    const af_align_frame f = ((const af_align_frame*)(xf + n_windows))[k];
+    const int window = k / clip_size;
+    const double m0 = xf[window].m[0], m1 = xf[window].m[1], m2 = xf[window].m[2];
+    const double m3 = xf[window].m[3], m4 = xf[window].m[4], m5 = xf[window].m[5];
+    for (int x = threadIdx.x; x < size; x += WB_THREADS) {
+        s_ad[x] = cv_round_sat(__dmul_rn(__dmul_rn(m0, (double)x), 1024.0));
+        s_bd[x] = cv_round_sat(__dmul_rn(__dmul_rn(m3, (double)x), 1024.0));
+    }
+    if (threadIdx.x < WB_ROWS) {
+        const double y = (double)(y0 + (int)threadIdx.x);
+        s_x0[threadIdx.x] = cv_round_sat(__dmul_rn(__dadd_rn(__dmul_rn(m1, y), m2), 1024.0)) + 16;
+        s_y0[threadIdx.x] = cv_round_sat(__dmul_rn(__dadd_rn(__dmul_rn(m4, y), m5), 1024.0)) + 16;
+    }
+    __syncthreads();
+    const int rows = size - y0 < WB_ROWS ? size - y0 : WB_ROWS, quads = size >> 2;
+    const unsigned char* img = pool + f.offset;
+    unsigned char* dst = out + ((long long)k * size + y0) * (long long)size * 3;
+    for (int i = threadIdx.x; i < rows * quads; i += WB_THREADS) {
+        const int r = i / quads, q = i - r * quads;
+        const long long X0 = s_x0[r], Y0 = s_y0[r];
+        unsigned px[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = q * 4 + j;
+            const long long X = (X0 + s_ad[x]) >> 5, Y = (Y0 + s_bd[x]) >> 5;
+            const long long sxl = X >> 5, syl = Y >> 5;
+            const int sx = (int)(sxl < -32768 ? -32768 : sxl > 32767 ? 32767 : sxl);      // saturate_cast<short>
+            const int sy = (int)(syl < -32768 ? -32768 : syl > 32767 ? 32767 : syl);
+            const int fx = (int)(X & 31), fy = (int)(Y & 31);
+            const int ix = sx - f.x, iy = sy - f.y;                   // crop coordinates of the top-left tap (the crop lies inside the canvas)
+            // the pair (A, B) is read at column clamp(ix): A is tap ix (or tap ix + 1 when ix = -1), B is tap ix + 1
+            const bool in0 = (unsigned)ix < (unsigned)f.iw;
+            const int wa = in0 ? 32 - fx : ix == -1 ? fx : 0;
+            const int wb = in0 && ix + 1 < f.iw ? fx : 0;
+            const int wy0 = (unsigned)iy < (unsigned)f.ih ? (32 - fy) * 32 : 0;
+            const int wy1 = (unsigned)(iy + 1) < (unsigned)f.ih ? fy * 32 : 0;
+            const int col = ix < 0 ? 0 : ix > f.iw - 1 ? f.iw - 1 : ix;
+            const int ra = iy < 0 ? 0 : iy > f.ih - 1 ? f.ih - 1 : iy;
+            const int rb = iy + 1 < 0 ? 0 : iy + 1 > f.ih - 1 ? f.ih - 1 : iy + 1;
+            const unsigned char* pa = img + ((long long)ra * f.iw + col) * 3;
+            const unsigned char* pb = img + ((long long)rb * f.iw + col) * 3;
+            unsigned a4, b4; unsigned short a2, b2;
+            __builtin_memcpy(&a4, pa, 4); __builtin_memcpy(&a2, pa + 4, 2);
+            __builtin_memcpy(&b4, pb, 4); __builtin_memcpy(&b2, pb + 4, 2);
+            const int w00 = wa * wy0, w01 = wb * wy0, w10 = wa * wy1, w11 = wb * wy1;     // = the four (32-fx)(32-fy)*32 ... weights, or 0
+            const int c0 = w00 * (int)(a4 & 255) + w01 * (int)(a4 >> 24) + w10 * (int)(b4 & 255) + w11 * (int)(b4 >> 24);
+            const int c1 = w00 * (int)((a4 >> 8) & 255) + w01 * (int)(a2 & 255) + w10 * (int)((b4 >> 8) & 255) + w11 * (int)(b2 & 255);
+            const int c2 = w00 * (int)((a4 >> 16) & 255) + w01 * (int)(a2 >> 8) + w10 * (int)((b4 >> 16) & 255) + w11 * (int)(b2 >> 8);
+            const int v0 = (c0 + (1 << 14)) >> 15, v1 = (c1 + (1 << 14)) >> 15, v2 = (c2 + (1 << 14)) >> 15;
+            px[j] = (unsigned)(v0 > 255 ? 255 : v0) | (unsigned)(v1 > 255 ? 255 : v1) << 8 | (unsigned)(v2 > 255 ? 255 : v2) << 16;
+        }
+        uint3 o;                                                      // 4 x RGB = 3 dwords (size % 4 == 0: every quad is dword-aligned)
+        o.x = px[0] | px[1] << 24;
+        o.y = px[1] >> 8 | px[2] << 16;
+        o.z = px[2] >> 16 | px[3] << 8;
+        *(uint3*)(dst + ((long long)r * size + q * 4) * 3) = o;
+    }
+}
+
 }  // namespace af
+
+extern "C" int64_t af_window_batch_table_bytes(int n_windows, int clip_size) {
+    if (n_windows <= 0 || n_windows > AF_WINDOW_MAX_BATCH || clip_size <= 0 || clip_size > AF_ALIGN_MAX_FRAMES) return 0;
+    return af::window_table_bytes(n_windows, clip_size);
+}
+
+extern "C" int af_window_batch_plan_u8(const af_window_desc* windows, const af_align_frame* frames, int n_windows, int clip_size, int size,
+                                       int64_t pool_bytes, void* table, int64_t table_bytes, int32_t* bad_window, int32_t* bad_frame) {
+    using namespace af;
+    if (bad_window) *bad_window = -1;
+    if (bad_frame) *bad_frame = -1;
+    AF_REQUIRE(windows && frames && table, "window_batch_plan: null argument");
+    AF_REQUIRE(n_windows > 0 && n_windows <= AF_WINDOW_MAX_BATCH && clip_size > 0 && clip_size <= AF_ALIGN_MAX_FRAMES,
+               "window_batch_plan: %d windows of %d frames (at most %d of %d)", n_windows, clip_size, AF_WINDOW_MAX_BATCH, AF_ALIGN_MAX_FRAMES);
+    AF_REQUIRE(size > 0 && size <= AF_WINDOW_MAX_SIZE && size % 4 == 0, "window_batch_plan: size %d (a multiple of 4, at most %d)", size, AF_WINDOW_MAX_SIZE);
+    AF_REQUIRE(pool_bytes > 0 && table_bytes >= window_table_bytes(n_windows, clip_size), "window_batch_plan: table of %lld bytes, %lld needed",
+               (long long)table_bytes, (long long)window_table_bytes(n_windows, clip_size));
+    WindowTableHeader* hd = (WindowTableHeader*)table;
+    WindowXform* xf = (WindowXform*)(hd + 1);
+    af_align_frame* out = (af_align_frame*)(xf + n_windows);
+    for (int w = 0; w < n_windows; ++w) {
+        const af_window_desc& d = windows[w];
+        AF_REQUIRE(d.canvas_h > 0 && d.canvas_w > 0 && d.canvas_h <= 32767 && d.canvas_w <= 32767, "window_batch_plan: window %d: bad canvas %dx%d",
+                   w, d.canvas_w, d.canvas_h);
+        invert_affine_cv(d.tfm, xf[w].m);
+        for (int t = 0; t < clip_size; ++t) {
+            const af_align_frame& f = frames[w * clip_size + t];
+            // the kernel reads the two taps of a row as 6 bytes: 3 readable bytes must follow every crop
+            AF_REQUIRE(f.ih > 0 && f.iw > 0 && f.offset >= 0 && f.offset + (int64_t)f.ih * f.iw * 3 + 3 <= pool_bytes,
+                       "window_batch_plan: window %d frame %d: crop %dx%d at byte %lld leaves the pool of %lld bytes", w, t, f.iw, f.ih,
+                       (long long)f.offset, (long long)pool_bytes);
+            // the reference pastes with new_image[y:y+ih, x:x+iw] = image, which numpy refuses unless the crop fits the canvas
+            if (f.x < 0 || f.y < 0 || (long long)f.x + f.iw > d.canvas_w || (long long)f.y + f.ih > d.canvas_h) {
+                if (bad_window) *bad_window = w;
+                if (bad_frame) *bad_frame = t;
+                return set_error(AF_ERR_ARG, "aligner: window %d frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas", w, t, f.iw, f.ih, f.x, f.y,
+                                 d.canvas_w, d.canvas_h);
+            }
+            out[w * clip_size + t] = f;
+        }
+    }
+    hd->n_windows = n_windows; hd->clip_size = clip_size; hd->size = size; hd->reserved = 0;
+    return AF_OK;
+}
+
+extern "C" int af_warp_affine_windows_u8(const void* pool, const void* table, int n_windows, int clip_size, int size, void* out,
+                                         void* stream) {
+    using namespace af;
+    AF_REQUIRE(pool && table && out, "warp_affine_windows: null argument");
+    AF_REQUIRE(n_windows > 0 && n_windows <= AF_WINDOW_MAX_BATCH && clip_size > 0 && clip_size <= AF_ALIGN_MAX_FRAMES,
+               "warp_affine_windows: %d windows of %d frames (at most %d of %d)", n_windows, clip_size, AF_WINDOW_MAX_BATCH, AF_ALIGN_MAX_FRAMES);
+    AF_REQUIRE(size > 0 && size <= AF_WINDOW_MAX_SIZE && size % 4 == 0, "warp_affine_windows: size %d (a multiple of 4, at most %d)", size, AF_WINDOW_MAX_SIZE);
+    AF_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)table & 7) == 0, "warp_affine_windows: out must be 4-byte, table 8-byte aligned");
+    const int tiles = (size + WB_ROWS - 1) / WB_ROWS;
+    const unsigned grid = (unsigned)(n_windows * clip_size * tiles);
+    hipLaunchKernelGGL(warp_affine_windows_kernel, dim3(grid), dim3(WB_THREADS), 0, (hipStream_t)stream, (const unsigned char*)pool,
+                       (const unsigned char*)table, (unsigned char*)out, n_windows, clip_size, size, tiles);
+    AF_CHECK_LAUNCH("warp_affine_windows_kernel");
+    return AF_OK;
+}
 
 extern "C" int af_warp_affine_clip_u8(const void* crops, const af_align_frame* frames, int n_frames, int canvas_h, int canvas_w,
                                       const double* tfm, int size, void* out, void* stream) {
@@ -88,17 +248,7 @@ extern "C" int af_warp_affine_clip_u8(const void* crops, const af_align_frame* f
                    "warp_affine_clip: frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas", i, f.iw, f.ih, f.x, f.y, canvas_w, canvas_h);
         a.f[i] = f;
     }
-    // warpAffine(): forward 2x3 matrix -> dst-to-src map, in double, same order of operations (volatile: no contraction)
-    volatile double M[6];
-    for (int i = 0; i < 6; ++i) M[i] = tfm[i];
-    volatile double D = M[0] * M[4] - M[1] * M[3];
-    D = D != 0 ? 1.0 / D : 0.0;
-    volatile double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11; M[1] = M[1] * -D; M[3] = M[3] * -D; M[4] = A22;
-    volatile double t0 = -M[0] * M[2], t1 = M[1] * M[5], t2 = -M[3] * M[2], t3 = M[4] * M[5];
-    volatile double b1 = t0 - t1, b2 = t2 - t3;
-    M[2] = b1; M[5] = b2;
-    for (int i = 0; i < 6; ++i) a.m[i] = M[i];
+    invert_affine_cv(tfm, a.m);
     const dim3 grid((unsigned)((size * size + 255) / 256), (unsigned)n_frames);
     hipLaunchKernelGGL(warp_affine_clip_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
     AF_CHECK_LAUNCH("warp_affine_clip_kernel");
