@@ -50,6 +50,22 @@ class PoolDesc(C.Structure):
         "out_ld")]
 
 
+def _out_dims(dims, kernel, stride, pad):
+    return tuple((d + 2 * p - k) // s + 1 for d, k, s, p in zip(dims, kernel, stride, pad))
+
+
+def conv_desc(n, dims, cin, cout, kernel, stride, pad, relu, code, dout=None, tpool=0) -> ConvDesc:
+    """The one place a ConvDesc is filled.  dims / kernel / stride / pad / dout are (t, h, w) triples; ``dout`` None = the
+    usual (d + 2 p - k) // s + 1."""
+    dout = _out_dims(dims, kernel, stride, pad) if dout is None else dout
+    return ConvDesc(n, *dims, cin, cout, *kernel, *stride, *pad, *dout, int(relu), code, int(tpool))
+
+
+def pool_desc(n, dims, c, kernel, stride, pad, code, dout=None, out_ld=0) -> PoolDesc:
+    dout = _out_dims(dims, kernel, stride, pad) if dout is None else dout
+    return PoolDesc(n, *dims, c, *kernel, *stride, *pad, *dout, code, out_ld)
+
+
 class Op(C.Structure):
     _fields_ = [
         ("kind", C.c_int32), ("out_ld", C.c_int32),

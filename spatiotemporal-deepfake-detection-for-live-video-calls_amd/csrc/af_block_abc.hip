@@ -22,7 +22,6 @@
 // is the 1x1x1 projection `branch1` (resnet_helper.py:411-436) accumulated into c's tile like af_conv3d_dual_bn_act does - both
 // weight sets carry their BN scale (folded in fp32 by the caller), shift = shift_c + shift_1 - and no residual is added.
 #include "af_common.h"
-#include <stdlib.h>
 
 namespace af {
 
@@ -286,7 +285,7 @@ static bool abc_geometry(const af_conv_desc* da, const af_conv_desc* db, const a
     const int inner = da->cout, cin = da->cin;
     // (inner 32 - s4 of the Fast pathway - runs and is parity-tested, but its 50 KB of weight fragments leave room for 3-row patches
     //  only and it measured 0.082 ms against 0.075 for the three launches: offered only with AF_ABC_INNER32=1)
-    if (inner == 32 && !(getenv("AF_ABC_INNER32") && atoi(getenv("AF_ABC_INNER32")))) return false;
+    if (inner == 32 && !env_int("AF_ABC_INNER32", 0)) return false;
     if ((inner != 8 && inner != 16 && inner != 32) || db->cin != inner || db->cout != inner || dc->cin != inner || dc->cout != 4 * inner) return false;
     if (d1) {   // projection form: instantiated for the Fast pathway's s2 (8 -> 8 -> 8 -> 32)
         if (inner != 8 || cin != 8 || d1->dtype != da->dtype || d1->cin != cin || d1->cout != dc->cout) return false;
@@ -309,8 +308,7 @@ static bool abc_geometry(const af_conv_desc* da, const af_conv_desc* db, const a
     // AF_ABC_PH sweeps it): s2 (inner 8) 14 / 10 / 7 / 5 / 4 / 3 rows -> 0.097 / 0.098 / 0.080 / 0.082 / 0.099 / 0.104 ms per
     // block (7 rows = 58 KB of LDS: two workgroups per CU, 8 even bands of a 56-row frame); s3 (inner 16) 10 / 7 / 5 / 4 / 3 rows ->
     // 0.070 / 0.053 / 0.081 / 0.054 / 0.082 ms.
-    const char* eph = getenv("AF_ABC_PH");
-    int p = eph ? atoi(eph) : 7;
+    int p = env_int("AF_ABC_PH", 7);
     if (p > da->h) p = da->h;
     if (p < 1) p = 1;
     while (p > 1 && abc_lds_bytes(inner, cin, p, da->kt) > 160 * 1024) --p;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 
 #include <vector>
 
@@ -12,6 +13,22 @@
 namespace af {
 
 int set_error(int code, const char* fmt, ...);
+
+// an integer knob from the environment (A/B runs, experiments, tests); `dflt` when it is not set
+inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// Diagnostic build (-DAF_STAMPS) only: the stamp buffer of AF_STAMP_PTR and the kernel's timing-ablation knob into its arguments
+template <class Args>
+inline void fill_stamps(Args& a, const char* dbg_knob) {
+#ifdef AF_STAMPS
+    const char* ep = getenv("AF_STAMP_PTR");
+    a.stamps = ep ? (unsigned long long*)strtoull(ep, nullptr, 0) : nullptr;
+    a.dbg = env_int(dbg_knob, 0);
+#endif
+}
 
 // ---- LDS-DMA helpers shared by the convolution kernels
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

@@ -22,7 +22,6 @@
 //   * pipeline: 3-slot LDS ring, K-steps s+1 and s+2 in flight while step s is multiplied; one raw
 //     s_barrier per K-step; explicit counted s_waitcnt vmcnt (hipcc does not see the DMA loads).
 #include "af_common.h"
-#include <stdlib.h>
 
 namespace af {
 
@@ -789,8 +788,7 @@ static int pick_variant(int cout, int cin, int taps, int dtype, long long M, int
         // 256x224 (64x112 per wave): the positions of the deep stages are multiples of 49 - 224-row tiles are 224 / 448 / 896
         // workgroups where 256-row tiles are 196 / 392 / 784 (77 % of the CUs in the last round); a 224-row tile costs ~0.89 of
         // a 256-row one.  AF_IGEMM_224 = 0 / 2 forces never / always (experiments).
-        const char* e224 = getenv("AF_IGEMM_224");
-        const int mode224 = e224 ? atoi(e224) : 1;
+        const int mode224 = env_int("AF_IGEMM_224", 1);
         const long long tm = (M + 255) / 256, big = tm * (cout / 256), v0 = tm * (cout / 128);
         const long long b224 = (M + 223) / 224 * (cout / 256);
         const double c256 = (double)((big + 255) / 256), c224 = 0.89 * (double)((b224 + 255) / 256);
@@ -979,10 +977,7 @@ static int conv_common(const af_conv_desc* d, const void* in, const void* w_pack
     a.relu = d->relu; a.out_ld = out_ld;
     AF_REQUIRE(aligned16(workspace) && workspace_bytes >= 0, "conv: the workspace must be 16-byte aligned");
     a.ws = (float*)workspace; a.ws_bytes = workspace ? workspace_bytes : 0;
-#ifdef AF_STAMPS
-    { const char* ep = getenv("AF_STAMP_PTR"); a.stamps = ep ? (unsigned long long*)strtoull(ep, nullptr, 0) : nullptr;
-      const char* ed = getenv("AF_G_DBG"); a.dbg = ed ? atoi(ed) : 0; }
-#endif
+    fill_stamps(a, "AF_G_DBG");
     AF_REQUIRE(d->tpool >= 0 && d->tpool <= 2, "conv: tpool must be 0, 1 (temporal pairs) or 2 (2x2 pixels)");
     a.tpool = d->tpool;
     AF_REQUIRE(a.tpool != 1 || (to % 2 == 0), "conv: fused temporal pool needs an even number of output frames (%d)", to);

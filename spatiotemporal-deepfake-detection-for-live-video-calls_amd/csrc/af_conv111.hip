@@ -22,7 +22,6 @@
 // Temporal pool (tpool): tile = (clip, frame pair, 64 pixels).  Rows are ordered so that the two frames of a pixel
 // are accumulator tiles j and j + 2 of the SAME lane: the pair max needs no exchange at all.
 #include "af_common.h"
-#include <stdlib.h>
 
 namespace af {
 
@@ -401,8 +400,7 @@ int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, con
     // 58.6 -> 49.9 us (tools/exp_c111_wc64.py, interleaved on one box).  AF_C111_WC64=0: the 32-channel form, for A/B runs.
     // (A three-slot ring with the BN parameters moved to LDS - 256 registers, no spills - measured the same as two slots: 49.0 us.)
     if (d->cin == 256) {
-        const char* ewc = getenv("AF_C111_WC64");
-        if (!(ewc && atoi(ewc) == 0))
+        if (env_int("AF_C111_WC64", 1) != 0)
             return residual ? (bf ? launch111<AF_BF16, 4, 0, false, true, 64, 64, 2>(a, blocks, stream) : launch111<AF_F16, 4, 0, false, true, 64, 64, 2>(a, blocks, stream))
                             : (bf ? launch111<AF_BF16, 4, 0, false, false, 64, 64, 2>(a, blocks, stream) : launch111<AF_F16, 4, 0, false, false, 64, 64, 2>(a, blocks, stream));
         return residual ? (bf ? launch111<AF_BF16, 4, 0, false, true, 32, 64, 4>(a, blocks, stream) : launch111<AF_F16, 4, 0, false, true, 32, 64, 4>(a, blocks, stream))

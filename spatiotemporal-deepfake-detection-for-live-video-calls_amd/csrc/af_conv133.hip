@@ -18,7 +18,6 @@
 // through an LDS output tile ([position][64 channels], swizzled like the patches): the workgroup stores whole 128-byte
 // rows, and does so under the MFMAs of the NEXT strip.
 #include "af_common.h"
-#include <stdlib.h>
 
 namespace af {
 
@@ -437,8 +436,7 @@ static int launch_c133(C133Args& a, hipStream_t stream) {
     const int lds = 2 * a.rows_alloc * 128 + 16 * 16 * 128 + 128 * 4 + 2 * 512 * 16 + (a.rows_alloc / 8) * 64 * 4;   // (+ the last two taps' fragments: 8-wave form)
     const int grid = a.total_strips < g_num_cus ? a.total_strips : g_num_cus;
     // AF_C64_WAVES=4: the round-1 / 2 form (one wave per SIMD, all 64 channels per wave) for A/B runs
-    const char* ew = getenv("AF_C64_WAVES");
-    if (ew && atoi(ew) == 4) {
+    if (env_int("AF_C64_WAVES", 8) == 4) {
         AF_SET_MAX_LDS((&conv133_c64_kernel<DT, R>), 160 * 1024, "conv133");
         hipLaunchKernelGGL((conv133_c64_kernel<DT, R>), dim3(grid), dim3(256), lds, stream, a);
     } else {
@@ -464,12 +462,7 @@ int conv133_run(const af_conv_desc* d, const void* in, const void* w_packed, con
     C133Args a;
     a.in = (const char*)in; a.w = (const char*)w_packed; a.scale = scale; a.shift = shift; a.out = (char*)out;
     a.H = d->h; a.W = d->w; a.frames = d->n * d->t;
-#ifdef AF_STAMPS
-    const char* ep = getenv("AF_STAMP_PTR");
-    a.stamps = ep ? (unsigned long long*)strtoull(ep, nullptr, 0) : nullptr;
-    const char* ed = getenv("AF_C64_DBG");
-    a.dbg = ed ? atoi(ed) : 0;
-#endif
+    fill_stamps(a, "AF_C64_DBG");
     return d->dtype == AF_BF16 ? launch_c133<AF_BF16>(a, stream) : launch_c133<AF_F16>(a, stream);
 }
 

@@ -20,7 +20,6 @@
 //     tiles per wave); the K loop is software-pipelined by k-halves like the generic kernel's 2-slot variant;
 //   * at B = 16 the 256 frames of s4 are exactly one unit per CU, the 512 half-frames of s3 exactly two rounds.
 #include "af_common.h"
-#include <stdlib.h>
 
 namespace af {
 
@@ -569,7 +568,7 @@ static int launch133g_n(const C133GArgs& a, hipStream_t stream) {
     AF_SET_MAX_LDS((&conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), 160 * 1024, "conv133g");
     // persistent workgroups (one per CU: the kernel uses all of LDS): unit blockIdx.x, + gridDim.x, ...
     const int units = a.frames * a.upf, cus = device_cus();
-    static const int persist = [] { const char* e = getenv("AF_G_PERSIST"); return e ? atoi(e) : 1; }();   // 0: one unit per workgroup (A/B runs)
+    static const int persist = env_int("AF_G_PERSIST", 1);   // 0: one unit per workgroup (A/B runs)
     const int grid = (FUSEC || !persist || units <= cus || cus <= 0) ? units : cus;
     hipLaunchKernelGGL((conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), dim3(grid), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("conv133g_kernel");
@@ -623,14 +622,8 @@ static void fill133g(C133GArgs& a, const af_conv_desc* d, const void* in, const 
     a.kslabs = d->cin / 64; a.relu = d->relu;
     a.inv_wp = 1.0f / (float)a.WP;
     a.w2 = nullptr; a.scale2 = a.shift2 = nullptr; a.res = nullptr; a.Cout2 = 0; a.relu2 = 0;
-    const char* es = getenv("AF_G_STAGGER");
-    a.stagger = es ? atoi(es) : 1;
-#ifdef AF_STAMPS
-    const char* ep = getenv("AF_STAMP_PTR");
-    a.stamps = ep ? (unsigned long long*)strtoull(ep, nullptr, 0) : nullptr;
-    const char* ed = getenv("AF_G_DBG");
-    a.dbg = ed ? atoi(ed) : 0;
-#endif
+    a.stagger = env_int("AF_G_STAGGER", 1);
+    fill_stamps(a, "AF_G_DBG");
 }
 
 // ---- TEMPORAL mode: 3x1x1 / stride 1 / pad (1,0,0) convs into 128 / 256 channels (the `a` convs of s3 / s4) on the same kernel.
@@ -654,7 +647,7 @@ static int conv311g_pixels(const af_conv_desc* d) {
 }
 
 bool conv311g_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    static const int enabled = [] { const char* e = getenv("AF_T311G"); return e ? atoi(e) : 1; }();
+    static const int enabled = env_int("AF_T311G", 1);
     return enabled && !residual && (out_ld == 0 || out_ld % 8 == 0) && conv311g_pixels(d) != 0;
 }
 
@@ -669,14 +662,8 @@ int conv311g_run(const af_conv_desc* d, const void* in, const void* w_packed, co
     a.kslabs = d->cin / 64; a.relu = d->relu;
     a.inv_wp = 1.0f / (float)a.R;
     a.w2 = nullptr; a.scale2 = a.shift2 = nullptr; a.res = nullptr; a.Cout2 = 0; a.relu2 = 0;
-    const char* es = getenv("AF_G_STAGGER");
-    a.stagger = es ? atoi(es) : 1;
-#ifdef AF_STAMPS
-    const char* ep = getenv("AF_STAMP_PTR");
-    a.stamps = ep ? (unsigned long long*)strtoull(ep, nullptr, 0) : nullptr;
-    const char* ed = getenv("AF_G_DBG");
-    a.dbg = ed ? atoi(ed) : 0;
-#endif
+    a.stagger = env_int("AF_G_STAGGER", 1);
+    fill_stamps(a, "AF_G_DBG");
     a.out = (char*)out; a.out_ld = out_ld ? out_ld : d->cout;
     const bool three = 2 * a.prows * 128 + 3 * d->cout * 128 + (d->cout == 128 ? a.prows * 4 : 0) <= 160 * 1024;     // 256 channels, P = 14: 2 x 32 KB + 3 x 32 KB = all of LDS
     if (d->cout == 256) {

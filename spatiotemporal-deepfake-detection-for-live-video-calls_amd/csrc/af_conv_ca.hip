@@ -16,7 +16,6 @@
 // the b fragments (K = 64: four 16-byte fragments per lane and tile) go global -> registers a stage / a tile ahead; BN
 // parameters sit in LDS (a plain global load between the DMA issue and its use would make hipcc wait for the DMA in flight).
 #include "af_common.h"
-#include <stdlib.h>
 
 namespace af {
 
@@ -448,15 +447,13 @@ int conv_ca_run(const af_conv_desc* dc, const void* inb, const void* wc, const v
     a.T = dc->t; a.HW = dc->h * dc->w; a.C = dc->cout; a.kslabs = dc->cout / 64;
     a.P = 256 / dc->t; a.chunks = (a.HW + a.P - 1) / a.P; a.tiles = dc->n * a.chunks;
 #ifdef AF_STAMPS
-    const char* ed = getenv("AF_CA_DBG");
-    a.dbg = ed ? atoi(ed) : 0;
+    a.dbg = env_int("AF_CA_DBG", 0);
 #endif
     const int cus = device_cus();
     const int blocks = a.tiles < cus ? a.tiles : cus;
     if (in1) return dc->dtype == AF_BF16 ? launch_ca<AF_BF16, true, false>(a, blocks, stream) : launch_ca<AF_F16, true, false>(a, blocks, stream);
     // the stage's c weights as an LDS image where its 8 KB fit (T = 32 with a 256-channel trunk; AF_CA_CWL=0: the fragment loads, for A/B runs)
-    const char* ecw = getenv("AF_CA_CWL");
-    if (conv_ca_lds_bytes(false, a.P, a.C, true) <= 160 * 1024 && !(ecw && atoi(ecw) == 0))
+    if (conv_ca_lds_bytes(false, a.P, a.C, true) <= 160 * 1024 && env_int("AF_CA_CWL", 1) != 0)
         return dc->dtype == AF_BF16 ? launch_ca<AF_BF16, false, true>(a, blocks, stream) : launch_ca<AF_F16, false, true>(a, blocks, stream);
     return dc->dtype == AF_BF16 ? launch_ca<AF_BF16, false, false>(a, blocks, stream) : launch_ca<AF_F16, false, false>(a, blocks, stream);
 }

@@ -18,15 +18,15 @@ from ._lib import Op, check, lib
 from .arch import BN_EPS, ConvSpec, FtcnTTSpec, NetSpec, PoolSpec, SlowFastSpec
 
 _TORCH_DTYPE = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+_ELEM_SIZE = {"f32": 4, "bf16": 2, "f16": 2}
 
 # op tags (echoed by the timed runner; used by bench.py to attribute device time to kernel classes)
 TAG_PACK, TAG_STEM, TAG_POOL, TAG_HEAD = 0, 1, 2, 3
 TAG_CONV_1x1x1, TAG_CONV_Tx1x1, TAG_CONV_1x3x3, TAG_CONV_OTHER, TAG_CONV_BC, TAG_CONV_CA, TAG_BLOCK_ABC = 10, 11, 12, 13, 14, 15, 16
-TAG_NAMES = {TAG_PACK: "input_pack", TAG_STEM: "stem_5x7x7", TAG_POOL: "maxpool", TAG_HEAD: "head",
+TAG_NAMES = {TAG_PACK: "input_pack", TAG_STEM: "stem", TAG_POOL: "maxpool", TAG_HEAD: "head",
              TAG_CONV_1x1x1: "conv_1x1x1", TAG_CONV_Tx1x1: "conv_3x1x1", TAG_CONV_1x3x3: "conv_1x3x3",
              TAG_CONV_OTHER: "conv_other", TAG_CONV_BC: "conv_1x3x3+1x1x1_fused", TAG_CONV_CA: "conv_1x1x1+3x1x1_fused",
              TAG_BLOCK_ABC: "bottleneck_block_fused"}
-TAG_NAMES[TAG_STEM] = "stem"
 
 
 def _conv_tag(cv: ConvSpec) -> int:
@@ -61,22 +61,23 @@ def _stages_of(spec):
         return [st for pair in spec.stages for st in pair]
     return list(spec.stages)
 
+
 class PackedWeights:
     """Device-resident, kernel-ready copy of a checkpoint: per conv a packed weight in the compute
     dtype plus fp32 BatchNorm scale/shift; fp32 head.  Built with HIP kernels (af_pack.hip)."""
 
     def __init__(self, spec, state: Dict[str, torch.Tensor], dtype: str, device):
-        self.dtype = dtype
+        self.dtype, self.device = dtype, device
         code = _lib.DTYPE_CODES[dtype]
-        es = 4 if dtype == "f32" else 2
-        st = _stream_ptr(device)
+        st = self._stream = _stream_ptr(device)
+        f32 = lambda k: state[k].detach().to(device=device, dtype=torch.float32).contiguous()
         stems = set(c.conv for c in (spec.stems if isinstance(spec, SlowFastSpec) else (spec.stem,)))
         self.w, self.scale, self.shift = {}, {}, {}
+        self.w3 = {}             # stem conv -> the K-packed image of the same weights (fused 16-bit stem, af_stem3.hip); may be empty
         for cv in spec.convs():
-            w = state[cv.conv + ".weight"].detach().to(device=device, dtype=torch.float32).contiguous()
+            w = f32(cv.conv + ".weight")
             assert tuple(w.shape) == cv.weight_shape, (cv.conv, tuple(w.shape), cv.weight_shape)
-            bn = [state[cv.bn_key + s].detach().to(device=device, dtype=torch.float32).contiguous()
-                  for s in (".weight", ".bias", ".running_mean", ".running_var")]
+            bn = [f32(cv.bn_key + s) for s in (".weight", ".bias", ".running_mean", ".running_var")]
             cpad = lib.af_padded_channels(cv.cout)           # kernels read scale/shift over the padded channel tile
             scale = torch.zeros(cpad, dtype=torch.float32, device=device)
             shift = torch.zeros(cpad, dtype=torch.float32, device=device)
@@ -84,28 +85,17 @@ class PackedWeights:
                                  _ptr(scale), _ptr(shift), st), "af_fold_bn")
             kt, kh, kw = cv.kernel
             if cv.conv in stems and isinstance(spec, FtcnTTSpec):        # temporal stem: MFMA A-fragment image
-                nbytes = lib.af_packed_tstem_weight_bytes(code)
-                packed = torch.empty(nbytes // es, dtype=_TORCH_DTYPE[dtype], device=device)
-                check(lib.af_pack_tstem_weight(_ptr(w), cv.cout, kt, code, _ptr(packed), st), "af_pack_tstem_weight")
+                packed = self._pack(lib.af_pack_tstem_weight, lib.af_packed_tstem_weight_bytes(code), _ptr(w), cv.cout, kt, code)
             elif cv.conv in stems:
-                nbytes = lib.af_packed_stem_weight_bytes(cv.cout, kt, kh, code)
-                packed = torch.empty(nbytes // es, dtype=_TORCH_DTYPE[dtype], device=device)
-                check(lib.af_pack_stem_weight(_ptr(w), cv.cout, kt, kh, kw, code, _ptr(packed), st),
-                      "af_pack_stem_weight")
+                packed = self._pack(lib.af_pack_stem_weight, lib.af_packed_stem_weight_bytes(cv.cout, kt, kh, code),
+                                    _ptr(w), cv.cout, kt, kh, kw, code)
             else:
-                nbytes = lib.af_packed_conv_weight_bytes(cv.cout, cv.cin, kt, kh, kw, code)
-                packed = torch.empty(nbytes // es, dtype=_TORCH_DTYPE[dtype], device=device)
-                check(lib.af_pack_conv_weight(_ptr(w), cv.cout, cv.cin, kt, kh, kw, code, _ptr(packed), st),
-                      "af_pack_conv_weight")
+                packed = self._pack_conv(w, code)
             self.w[cv.conv], self.scale[cv.conv], self.shift[cv.conv] = packed, scale, shift
             if (cv.conv in stems and not isinstance(spec, FtcnTTSpec) and dtype != "f32" and cv.cout == 64
                     and (kh, kw) == (7, 7)):
-                # the K-packed image of the same stem weights for the fused 16-bit stem (3 real channels, af_stem3.hip)
-                nb3 = lib.af_packed_stem_weight_bytes_rgb3(kt, code)
-                p3 = torch.empty(nb3 // es, dtype=_TORCH_DTYPE[dtype], device=device)
-                check(lib.af_pack_stem_weight_rgb3(_ptr(w), cv.cout, kt, code, _ptr(p3), st), "af_pack_stem_weight_rgb3")
-                self.w3 = getattr(self, "w3", {})
-                self.w3[cv.conv] = p3
+                self.w3[cv.conv] = self._pack(lib.af_pack_stem_weight_rgb3, lib.af_packed_stem_weight_bytes_rgb3(kt, code),
+                                              _ptr(w), cv.cout, kt, code)
         # block 0 of every stage: last 1x1x1 + projection shortcut share one accumulator (af_conv3d_dual_bn_act):
         # both weights get their BN scale folded in (fp32, before the rounding), shifts are summed
         self.w_folded, self.shift_sum, self.ones = {}, {}, {}
@@ -114,22 +104,14 @@ class PackedWeights:
                 if blk.branch1 is None or blk.branch1.pool_after_bn is not None:
                     continue                 # (FTCN: a pooled shortcut cannot share the c conv's accumulator)
                 for cv in (blk.c, blk.branch1):
-                    w = state[cv.conv + ".weight"].detach().to(device=device, dtype=torch.float32).contiguous()
-                    kt, kh, kw = cv.kernel
-                    nbytes = lib.af_packed_conv_weight_bytes(cv.cout, cv.cin, kt, kh, kw, code)
-                    packed = torch.empty(nbytes // es, dtype=_TORCH_DTYPE[dtype], device=device)
-                    check(lib.af_pack_conv_weight_scaled(_ptr(w), _ptr(self.scale[cv.conv]), cv.cout, cv.cin, kt, kh, kw,
-                                                         code, _ptr(packed), st), "af_pack_conv_weight_scaled")
-                    self.w_folded[cv.conv] = packed
+                    self.w_folded[cv.conv] = self._pack_conv(f32(cv.conv + ".weight"), code, self.scale[cv.conv])
                 self.shift_sum[blk.c.conv] = (self.shift[blk.c.conv] + self.shift[blk.branch1.conv]).contiguous()
                 self.ones[blk.c.conv] = torch.ones(lib.af_padded_channels(blk.c.cout), dtype=torch.float32, device=device)
-        f32 = lambda k: state[k].detach().to(device=device, dtype=torch.float32).contiguous()
         if isinstance(spec, FtcnTTSpec):
             # transformer head, fp32 whatever the trunk's dtype: Linear weights packed for the fp32 conv kernel,
             # bias as its `shift` (scale = ones), LayerNorm / token parameters as they are
             h = spec.head
             l0, l1 = h + ".transformer.layers.0.0.fn", h + ".transformer.layers.0.1.fn"
-            f32code = _lib.DTYPE_CODES["f32"]
             self.lin = {}
             for name, wkey, bkey in (("qkv", l0 + ".fn.to_qkv.weight", None),
                                      ("out", l0 + ".fn.to_out.0.weight", l0 + ".fn.to_out.0.bias"),
@@ -137,9 +119,7 @@ class PackedWeights:
                                      ("ff2", l1 + ".fn.net.3.weight", l1 + ".fn.net.3.bias")):
                 w = f32(wkey)
                 cout, cin = w.shape
-                nbytes = lib.af_packed_conv_weight_bytes(cout, cin, 1, 1, 1, f32code)
-                packed = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-                check(lib.af_pack_conv_weight(_ptr(w), cout, cin, 1, 1, 1, f32code, _ptr(packed), st), "af_pack_conv_weight")
+                packed = self._pack_conv(w.reshape(cout, cin, 1, 1, 1), _lib.AF_F32, dtype="f32")
                 cpad = lib.af_padded_channels(cout)
                 bias = torch.zeros(cpad, dtype=torch.float32, device=device)
                 if bkey is not None:
@@ -155,34 +135,55 @@ class PackedWeights:
             self.fc_w, self.fc_b = f32(spec.head + ".weight"), f32(spec.head + ".bias")
         torch.cuda.current_stream(device).synchronize()      # sources may be freed by the caller
 
+    def _pack(self, fn, nbytes, *args, dtype=None):
+        """One pack call of the library: a buffer of the size it asks for, the call, its status."""
+        dtype = dtype or self.dtype
+        packed = torch.empty(nbytes // _ELEM_SIZE[dtype], dtype=_TORCH_DTYPE[dtype], device=self.device)
+        check(fn(*args, _ptr(packed), self._stream), fn.__name__)
+        return packed
 
-def _fill_conv_desc(cd, batch, code, cv: ConvSpec, din, dout, relu):
-    cd.n, (cd.t, cd.h, cd.w), cd.cin, cd.cout = batch, din, cv.cin, cv.cout
-    cd.kt, cd.kh, cd.kw = cv.kernel
-    cd.st, cd.sh, cd.sw = cv.stride
-    cd.pt, cd.ph, cd.pw = cv.pad
-    cd.to, cd.ho, cd.wo = dout
-    cd.relu, cd.dtype = int(relu), code
+    def _pack_conv(self, w, code, scale=None, dtype=None):
+        """(Cout, Cin, kT, kH, kW) fp32 weights in the conv kernels' layout; ``scale``: folded into the rows before the rounding."""
+        shape = tuple(w.shape)
+        nbytes = lib.af_packed_conv_weight_bytes(*shape, code)
+        if scale is None:
+            return self._pack(lib.af_pack_conv_weight, nbytes, _ptr(w), *shape, code, dtype=dtype)
+        return self._pack(lib.af_pack_conv_weight_scaled, nbytes, _ptr(w), _ptr(scale), *shape, code, dtype=dtype)
+
+    def bn(self, cv: ConvSpec):
+        """(weight, scale, shift) device pointers of a conv with its own BatchNorm."""
+        return self.w[cv.conv].data_ptr(), self.scale[cv.conv].data_ptr(), self.shift[cv.conv].data_ptr()
+
+    def folded(self, c: ConvSpec, branch1: ConvSpec):
+        """(w_c, w_1, ones, shift_sum) device pointers of a c conv and its projection shortcut sharing one accumulator: both
+        weights carry their BN scale, the kernel's scale is ones and its shift the sum of the two shifts."""
+        return (self.w_folded[c.conv].data_ptr(), self.w_folded[branch1.conv].data_ptr(), self.ones[c.conv].data_ptr(),
+                self.shift_sum[c.conv].data_ptr())
+
+
+def _conv_desc(batch, code, cv: ConvSpec, din, dout, relu=True, tpool=0):
+    return _lib.conv_desc(batch, din, cv.cin, cv.cout, cv.kernel, cv.stride, cv.pad, relu, code, dout, tpool)
+
+
+# The plan's switches (A/B runs and tests): name -> on by default.  Read whenever a plan is built; "1" is on, anything else off.
+SWITCHES = {"AF_FUSE_BC": False, "AF_FUSE_CA": True, "AF_FUSE_CPA": False, "AF_FUSE_ABC": True, "AF_FUSE_TSTEM_POOL": True,
+            "AF_SLOWFAST_STEM3": True}
+
+
+def _read_switches():
+    return {name: os.environ.get(name, "1" if on else "0") == "1" for name, on in SWITCHES.items()}
 
 
 class _Plan:
-    """Accumulates plan entries (dicts) and the element count every named activation buffer must hold."""
+    """Accumulates plan entries (dicts) and the element count every named activation buffer must hold; the network planners add
+    what the engine needs besides: ``inputs`` [(stem-input buffer, dims, temporal stride)], ``rgb3`` (the single input feeds a
+    K-packed stem), ``rgb3_inputs`` (SlowFast: the inputs that do), ``head_dims`` and ``head_width``."""
 
-    def __init__(self, batch, code=None):
-        self.batch, self.entries, self.sizes, self.code = batch, [], {}, code
+    def __init__(self, batch, dtype):
+        self.batch, self.dtype, self.code = batch, dtype, _lib.DTYPE_CODES[dtype]
+        self.entries, self.sizes, self.switch = [], {}, _read_switches()
         self.boundary = None                 # set by a stage whose last launch already ran the next stage's first a conv
-
-    def bc_fusable(self, b: ConvSpec, c: ConvSpec, da, db, dc) -> bool:
-        """does the library run this bottleneck's b (1x3x3) and c (1x1x1 + residual) convs as one launch (af_conv3d_bc_bn_act)?
-        OFF unless AF_FUSE_BC=1: measured slower (B=16, bf16: s3 0.205 ms against 0.068 + 0.080 ms for the two launches, s4
-        0.134 against 0.056 + 0.070) - the b conv is MFMA-bound, the c conv with its residual an HBM stream, and inside one
-        workgroup the two phases run back to back on every CU at the same time instead of overlapping (DESIGN.md 3.1e)."""
-        if self.code is None or os.environ.get("AF_FUSE_BC") != "1":
-            return False
-        d1, d2 = _lib.ConvDesc(), _lib.ConvDesc()
-        _fill_conv_desc(d1, self.batch, self.code, b, da, db, True)
-        _fill_conv_desc(d2, self.batch, self.code, c, db, dc, True)
-        return bool(lib.af_conv_bc_fusable(C.byref(d1), C.byref(d2)))
+        self.inputs, self.rgb3, self.rgb3_inputs, self.head_dims, self.head_width = [], False, set(), None, None
 
     def need(self, buf, dims, width):
         self.sizes[buf] = max(self.sizes.get(buf, 0), self.batch * dims[0] * dims[1] * dims[2] * width)
@@ -190,29 +191,34 @@ class _Plan:
     def add(self, **e):
         self.entries.append(e)
 
+    def desc(self, cv: ConvSpec, din, dout, tpool=0):
+        return _conv_desc(self.batch, self.code, cv, din, dout, True, tpool)
+
+    def _fusable(self, switch, ask, convs, *more) -> bool:
+        """the shared body of the *_fusable questions: the switch, then the library's own predicate over the descriptors of
+        ``convs``: (ConvSpec, din, dout[, tpool]) each, or None for a conv the launch does not have"""
+        if not self.switch[switch]:
+            return False
+        return bool(ask(*(None if c is None else C.byref(self.desc(*c)) for c in convs), *more))
+
+    def bc_fusable(self, b: ConvSpec, c: ConvSpec, da, db, dc) -> bool:
+        """does the library run this bottleneck's b (1x3x3) and c (1x1x1 + residual) convs as one launch (af_conv3d_bc_bn_act)?
+        OFF unless AF_FUSE_BC=1: measured slower (B=16, bf16: s3 0.205 ms against 0.068 + 0.080 ms for the two launches, s4
+        0.134 against 0.056 + 0.070) - the b conv is MFMA-bound, the c conv with its residual an HBM stream, and inside one
+        workgroup the two phases run back to back on every CU at the same time instead of overlapping (DESIGN.md 3.1e)."""
+        return self._fusable("AF_FUSE_BC", lib.af_conv_bc_fusable, [(b, da, db), (c, db, dc)])
+
     def ca_fusable(self, c: ConvSpec, a_next: ConvSpec, db, dc, branch1: ConvSpec = None, d_in=None) -> bool:
         """does the library run this block's c conv (+ residual or projection shortcut, + ReLU) and the NEXT block's a conv as one
-        launch (af_conv3d_ca_bn_act)?"""
-        if self.code is None or os.environ.get("AF_FUSE_CA", "1") != "1":
-            return False
-        d1, d2, d3 = _lib.ConvDesc(), _lib.ConvDesc(), _lib.ConvDesc()
-        _fill_conv_desc(d1, self.batch, self.code, c, db, dc, True)
-        _fill_conv_desc(d2, self.batch, self.code, a_next, dc, a_next.out_dims(*dc), True)
-        if branch1 is not None:
-            _fill_conv_desc(d3, self.batch, self.code, branch1, d_in, dc, True)
-        return bool(lib.af_conv_ca_fusable(C.byref(d1), C.byref(d3) if branch1 is not None else None, C.byref(d2)))
+        launch (af_conv3d_ca_bn_act)?  AF_FUSE_CA=0 switches it off (A/B runs)."""
+        return self._fusable("AF_FUSE_CA", lib.af_conv_ca_fusable,
+                             [(c, db, dc), branch1 and (branch1, d_in, dc), (a_next, dc, a_next.out_dims(*dc))])
 
     def cpa_fusable(self, c: ConvSpec, a_next: ConvSpec, db, dc, x_sub) -> bool:
         """does the library run the stage's last c conv (+ residual + ReLU), the temporal max-pool behind the stage and the NEXT
-        stage's first a conv as one launch (af_conv3d_cpa_bn_act)?  AF_FUSE_CPA=0 switches it off (A/B runs)."""
-        if self.code is None or os.environ.get("AF_FUSE_CPA", "0") != "1":
-            return False
+        stage's first a conv as one launch (af_conv3d_cpa_bn_act)?  OFF unless AF_FUSE_CPA=1."""
         dp = (dc[0] // 2,) + tuple(dc[1:])
-        d1, d2 = _lib.ConvDesc(), _lib.ConvDesc()
-        _fill_conv_desc(d1, self.batch, self.code, c, db, dc, True)
-        d1.tpool = 1
-        _fill_conv_desc(d2, self.batch, self.code, a_next, dp, a_next.out_dims(*dp), True)
-        return bool(lib.af_conv_cpa_fusable(C.byref(d1), C.byref(d2), x_sub))
+        return self._fusable("AF_FUSE_CPA", lib.af_conv_cpa_fusable, [(c, db, dc, 1), (a_next, dp, a_next.out_dims(*dp))], x_sub)
 
     def _boundary_fusable(self, c: ConvSpec, next_stage, db, dc) -> int:
         """0, or the x_sub of the fused stage-boundary launch: 2 when the next stage's block 0 reads the pooled trunk only through
@@ -230,22 +236,15 @@ class _Plan:
     def abc_fusable(self, blk, d) -> bool:
         """does the library run this whole block (a, b, c + identity or stride-1 projection shortcut + ReLU) as one launch
         (af_block_abc_bn_act: the narrow blocks of SlowFast's Fast pathway)?  AF_FUSE_ABC=0 switches it off (A/B runs)."""
-        if self.code is None or os.environ.get("AF_FUSE_ABC", "1") != "1":
-            return False
         if any(cv is not None and cv.pool_after_bn is not None for cv in (blk.a, blk.b, blk.c, blk.branch1)):
             return False
         da = blk.a.out_dims(*d)
         db = blk.b.out_dims(*da)
         dc = blk.c.out_dims(*db)
-        d1, d2, d3, d4 = _lib.ConvDesc(), _lib.ConvDesc(), _lib.ConvDesc(), _lib.ConvDesc()
-        _fill_conv_desc(d1, self.batch, self.code, blk.a, d, da, True)
-        _fill_conv_desc(d2, self.batch, self.code, blk.b, da, db, True)
-        _fill_conv_desc(d3, self.batch, self.code, blk.c, db, dc, True)
-        if blk.branch1 is not None:
-            if blk.branch1.out_dims(*d) != dc:
-                return False
-            _fill_conv_desc(d4, self.batch, self.code, blk.branch1, d, dc, True)
-        return bool(lib.af_block_abc_fusable(C.byref(d1), C.byref(d2), C.byref(d3), C.byref(d4) if blk.branch1 is not None else None))
+        if blk.branch1 is not None and blk.branch1.out_dims(*d) != dc:
+            return False
+        return self._fusable("AF_FUSE_ABC", lib.af_block_abc_fusable,
+                             [(blk.a, d, da), (blk.b, da, db), (blk.c, db, dc), blk.branch1 and (blk.branch1, d, dc)])
 
     def stage(self, stage, d, cur, nxt, a_buf, b_buf, last_ld=None, tpool_last=False, next_stage=None):
         """One pathway's ResStage.  ``last_ld``: row stride of the stage's final output (room for the lateral's
@@ -342,11 +341,11 @@ class _Plan:
                 self.add(kind="ca", cv=blk.c, cv2=nxa, din=db, dout=dc, src=c_src, res=res_src, dst=nxt, dst2=a_buf)
                 self.need(a_buf, nxa.out_dims(*dc), nxa.cout)
                 a_done = True
-            elif tp and next_stage is not None and res_src == cur and ld == blk.c.cout and self._boundary_fusable(blk.c, next_stage, db, dc):
+            elif tp and next_stage is not None and res_src == cur and ld == blk.c.cout and (
+                    sub := self._boundary_fusable(blk.c, next_stage, db, dc)):
                 # s2 -> s3: c + residual + ReLU, the temporal pool and the next stage's first a conv in one launch; the pooled trunk
                 # is stored only where the next stage's projection shortcut reads it
                 nb = next_stage.blocks[0]
-                sub = self._boundary_fusable(blk.c, next_stage, db, dc)
                 self.add(kind="cpa", cv=blk.c, cv2=nb.a, din=db, dout=dc, src=c_src, res=res_src, dst=nxt, dst2=a_buf, x_sub=sub, tpool=True)
                 self.need(a_buf, nb.a.out_dims(*dstore), nb.a.cout)
                 self.boundary = {"sub": sub == 2}
@@ -358,6 +357,137 @@ class _Plan:
         return d, c, cur, nxt
 
 
+def _plan_i3d(plan: _Plan, spec: NetSpec, T, H, W, has_rgb3):
+    plan.inputs = [("IN", (T, H, W), 1)]                       # (stem-input buffer, dims, temporal stride)
+    cur, nxt = "P0", "P1"
+    d = spec.stem.out_dims(T, H, W)
+    d2 = _pool_out(d, spec.stem_pool)
+    fuse_stem_pool = (plan.dtype != "f32" and d[2] <= 128 and spec.stem.cout == 64 and
+                      _is_pool(spec.stem_pool, (1, 3, 3), (1, 2, 2), (0, 1, 1)))
+    plan.rgb3 = bool(fuse_stem_pool and spec.stem.conv in has_rgb3)
+    if fuse_stem_pool:        # conv + BN + ReLU + max-pool in one launch; the conv output never reaches HBM
+        plan.add(kind="stem3_pool" if plan.rgb3 else "stem_pool", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur)
+        plan.need(cur, d2, spec.stem.cout)
+    else:
+        plan.add(kind="stem", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur); plan.need(cur, d, spec.stem.cout)
+        plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stem.cout, din=d, dout=d2, src=cur, dst=nxt)
+        plan.need(nxt, d2, spec.stem.cout)
+        cur, nxt = nxt, cur
+    d = d2
+    fuse_tpool = _is_pool(spec.pool_after_s2, (2, 1, 1), (2, 1, 1), (0, 0, 0))
+    c = spec.stem.cout
+    for si, stage in enumerate(spec.stages):
+        d, c, cur, nxt = plan.stage(stage, d, cur, nxt, "A", "B", tpool_last=(fuse_tpool and si == 0),
+                                    next_stage=spec.stages[1] if (si == 0 and len(spec.stages) > 1) else None)
+        if si == 0 and not plan.entries[-1].get("tpool"):
+            # pathway0_pool as its own launch (odd frame counts / other pool shapes)
+            d2 = _pool_out(d, spec.pool_after_s2)
+            plan.add(kind="pool", pool=spec.pool_after_s2, ch=c, din=d, dout=d2, src=cur, dst=nxt); plan.need(nxt, d2, c)
+            cur, nxt = nxt, cur
+            d = d2
+    hp = tuple(spec.head_pool)
+    dh = tuple(di - k + 1 for di, k in zip(d, hp))
+    if min(dh) < 1:
+        raise ValueError("input %s too small for the head pool %s" % ((T, H, W), hp))
+    plan.head_dims, plan.head_width = dh, c
+    plan.add(kind="head", pool=hp, ch=c, din=d, dout=dh, src=cur)
+
+
+def _plan_ftcn(plan: _Plan, spec: FtcnTTSpec, T, H, W, has_rgb3):
+    """FTCN-TT (reference i3d_temporal_var_fix_dropout_tt_cfg.py:290-359): temporal stem, s2..s4 with every spatial
+    kernel 1x1, per-frame average-pooled tokens, one pre-norm transformer layer, LayerNorm + Linear on the class
+    token (time_transformer.py:268-281)."""
+    plan.inputs = [("IN", (T, H, W), 1)]
+    cur, nxt = "P0", "P1"
+    d = _pool_out(spec.stem.out_dims(T, H, W), spec.stem.pool_after_bn)
+    d2 = _pool_out(d, spec.stem_pool)
+    if (plan.dtype != "f32" and plan.switch["AF_FUSE_TSTEM_POOL"]
+            and _is_pool(spec.stem_pool, (1, 3, 3), (1, 2, 2), (0, 1, 1))):
+        # 16-bit: the stem's own 1x3x3 / stride-2 max-pool rides behind the temporal stem (the half-resolution tensor -
+        # 822 MB at 16 clips - is neither written nor read back)
+        plan.add(kind="tstem_pool3", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur); plan.need(cur, d2, spec.stem.cout)
+        d = d2
+    else:
+        plan.add(kind="tstem", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur); plan.need(cur, d, spec.stem.cout)
+        plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stem.cout, din=d, dout=d2, src=cur, dst=nxt); plan.need(nxt, d2, spec.stem.cout)
+        cur, nxt, d = nxt, cur, d2
+    fuse_tpool = _is_pool(spec.pool_after_s2, (2, 1, 1), (2, 1, 1), (0, 0, 0))
+    c = spec.stem.cout
+    for si, stage in enumerate(spec.stages):
+        d, c, cur, nxt = plan.stage(stage, d, cur, nxt, "A", "B", tpool_last=(fuse_tpool and si == 0))
+        if si == 0 and not plan.entries[-1].get("tpool"):
+            dp = _pool_out(d, spec.pool_after_s2)
+            plan.add(kind="pool", pool=spec.pool_after_s2, ch=c, din=d, dout=dp, src=cur, dst=nxt); plan.need(nxt, dp, c)
+            cur, nxt, d = nxt, cur, dp
+    # TransformerHead 'time' patches (:133-135): AvgPool3d((1, S, S)) sized from the crop, one token per frame
+    if tuple(d[1:]) != tuple(spec.token_pool[1:]) or d[0] != spec.tokens or c != spec.dim:
+        raise ValueError("FTCN-TT head expects a (%d,%d,%d)x%d feature map, got %s x %d"
+                         % (spec.tokens, spec.token_pool[1], spec.token_pool[2], spec.dim, d, c))
+    plan.head_dims, plan.head_width = (1, 1, 1), spec.dim
+    plan.add(kind="tt_head", ch=c, din=d, src=cur)
+
+
+def _plan_slowfast(plan: _Plan, spec: SlowFastSpec, T, H, W, has_rgb3):
+    if T % spec.alpha:
+        raise ValueError("SlowFast needs a frame count divisible by alpha=%d (got %d)" % (spec.alpha, T))
+    Ts = T // spec.alpha
+    plan.inputs = [("IN_S", (Ts, H, W), spec.alpha), ("IN_F", (T, H, W), 1)]
+    fuse_w = [f.cout for f in spec.fuses]                         # channels each lateral adds to the Slow tensor
+    # stems (+ max-pool); the Slow pool writes at the widened row stride so the lateral can append its channels
+    ds = spec.stems[0].out_dims(Ts, H, W); ds2 = _pool_out(ds, spec.stem_pool)
+    df = spec.stems[1].out_dims(T, H, W); df2 = _pool_out(df, spec.stem_pool)
+    ld0 = spec.stems[0].cout + fuse_w[0]
+    if (spec.stems[0].conv in has_rgb3 and plan.switch["AF_SLOWFAST_STEM3"]
+            and _is_pool(spec.stem_pool, (1, 3, 3), (1, 2, 2), (0, 1, 1)) and ds[2] <= 128):
+        # 16-bit: the Slow stem + its max-pool as the K-packed fused stem (3-channel input layout), pooled rows at the widened stride
+        plan.rgb3_inputs.add("IN_S")
+        plan.add(kind="stem3_pool", cv=spec.stems[0], din=(Ts, H, W), dout=ds, src="IN_S", dst="S0", ld=ld0)
+        plan.need("S1", ds2, spec.stems[0].cout)
+    else:
+        plan.add(kind="stem", cv=spec.stems[0], din=(Ts, H, W), dout=ds, src="IN_S", dst="S1"); plan.need("S1", ds, spec.stems[0].cout)
+        plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stems[0].cout, din=ds, dout=ds2, src="S1", dst="S0", ld=ld0)
+    plan.need("S0", ds2, ld0)
+    plan.add(kind="stem", cv=spec.stems[1], din=(T, H, W), dout=df, src="IN_F", dst="F1"); plan.need("F1", df, spec.stems[1].cout)
+    plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stems[1].cout, din=df, dout=df2, src="F1", dst="F0")
+    plan.need("F0", df2, spec.stems[1].cout)
+    scur, snxt, fcur, fnxt = "S0", "S1", "F0", "F1"
+    ds, df, cs = ds2, df2, spec.stems[0].cout
+
+    def lateral(fz: ConvSpec, dfast, fbuf, sbuf, c_slow, ld):
+        do = fz.out_dims(*dfast)                                   # FuseFastToSlow: conv + BN + ReLU into the Slow rows
+        plan.add(kind="conv", cv=fz, din=dfast, dout=do, src=fbuf, dst=sbuf, ld=ld, ch_off=c_slow)
+        return do
+
+    if lateral(spec.fuses[0], df, fcur, scur, cs, ld0) != ds:
+        raise ValueError("the Fast->Slow lateral does not land on the Slow grid")
+    cf = spec.stems[1].cout
+    for si, (slow, fast) in enumerate(spec.stages):
+        has_fuse = si + 1 < len(spec.fuses)
+        ld = slow.blocks[-1].c.cout + (fuse_w[si + 1] if has_fuse else 0)
+        ds, cs, scur, snxt = plan.stage(slow, ds, scur, snxt, "A_S", "B_S", last_ld=ld)
+        df, cf, fcur, fnxt = plan.stage(fast, df, fcur, fnxt, "A_F", "B_F")
+        if has_fuse and lateral(spec.fuses[si + 1], df, fcur, scur, cs, ld) != ds:
+            raise ValueError("the Fast->Slow lateral does not land on the Slow grid")
+    hs, hf = (tuple(p) for p in spec.head_pools)
+    dhs = tuple(di - k + 1 for di, k in zip(ds, hs))
+    dhf = tuple(di - k + 1 for di, k in zip(df, hf))
+    if min(dhs) < 1 or dhs != dhf:
+        raise ValueError("input %s does not fit the SlowFast head pools %s / %s" % ((T, H, W), hs, hf))
+    plan.head_dims, plan.head_width = dhs, cs + cf
+    plan.add(kind="avgpool", pool=hs, ch=cs, din=ds, dout=dhs, src=scur, ch_off=0)
+    plan.add(kind="avgpool", pool=hf, ch=cf, din=df, dout=dhf, src=fcur, ch_off=cs)
+    plan.add(kind="linear")
+
+
+def plan_network(spec, dtype: str, batch: int, dims, has_rgb3=()) -> _Plan:
+    """The launch plan of one (network, dtype, batch, input dims); needs no device.  ``has_rgb3``: the stem convs whose weights
+    also exist as the K-packed image of the fused 16-bit stem (PackedWeights.w3)."""
+    plan = _Plan(batch, dtype)
+    planner = _plan_slowfast if isinstance(spec, SlowFastSpec) else _plan_ftcn if isinstance(spec, FtcnTTSpec) else _plan_i3d
+    planner(plan, spec, *dims, has_rgb3)
+    return plan
+
+
 class Engine:
     """Op list + activation buffers for one (batch, dtype).  ``run_*`` enqueue the whole forward on
     the current torch stream and return the engine-owned logits / pooled-feature tensors."""
@@ -366,147 +496,19 @@ class Engine:
         self.spec, self.weights, self.batch, self.device = spec, weights, batch, device
         self.dtype = weights.dtype
         self.code = _lib.DTYPE_CODES[self.dtype]
-        T, H, W = dims or (spec.num_frames, spec.crop, spec.crop)
-        self.in_dims = (T, H, W)
-        plan = _Plan(batch, self.code)
-        if isinstance(spec, SlowFastSpec):
-            self._plan_slowfast(plan, spec, T, H, W)
-        elif isinstance(spec, FtcnTTSpec):
-            self._plan_ftcn(plan, spec, T, H, W)
-        else:
-            self._plan_i3d(plan, spec, T, H, W)
+        self.in_dims = tuple(dims or (spec.num_frames, spec.crop, spec.crop))
+        plan = plan_network(spec, self.dtype, batch, self.in_dims, weights.w3)
+        self.inputs, self.rgb3, self.head_dims, self.head_width = plan.inputs, plan.rgb3, plan.head_dims, plan.head_width
         self._materialise(plan)
-
-    # -- plans -----------------------------------------------------------------------------------------
-    def _plan_i3d(self, plan: _Plan, spec: NetSpec, T, H, W):
-        self.inputs = [("IN", (T, H, W), 1)]                       # (stem-input buffer, dims, temporal stride)
-        cur, nxt = "P0", "P1"
-        d = spec.stem.out_dims(T, H, W)
-        d2 = _pool_out(d, spec.stem_pool)
-        fuse_stem_pool = (self.dtype != "f32" and d[2] <= 128 and spec.stem.cout == 64 and
-                          _is_pool(spec.stem_pool, (1, 3, 3), (1, 2, 2), (0, 1, 1)))
-        self.rgb3 = bool(fuse_stem_pool and spec.stem.conv in getattr(self.weights, "w3", {}))
-        if fuse_stem_pool:        # conv + BN + ReLU + max-pool in one launch; the conv output never reaches HBM
-            plan.add(kind="stem3_pool" if self.rgb3 else "stem_pool", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur)
-            plan.need(cur, d2, spec.stem.cout)
-        else:
-            plan.add(kind="stem", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur); plan.need(cur, d, spec.stem.cout)
-            plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stem.cout, din=d, dout=d2, src=cur, dst=nxt)
-            plan.need(nxt, d2, spec.stem.cout)
-            cur, nxt = nxt, cur
-        d = d2
-        fuse_tpool = _is_pool(spec.pool_after_s2, (2, 1, 1), (2, 1, 1), (0, 0, 0))
-        c = spec.stem.cout
-        for si, stage in enumerate(spec.stages):
-            d, c, cur, nxt = plan.stage(stage, d, cur, nxt, "A", "B", tpool_last=(fuse_tpool and si == 0),
-                                        next_stage=spec.stages[1] if (si == 0 and len(spec.stages) > 1) else None)
-            if si == 0 and not plan.entries[-1].get("tpool"):
-                # pathway0_pool as its own launch (odd frame counts / other pool shapes)
-                d2 = _pool_out(d, spec.pool_after_s2)
-                plan.add(kind="pool", pool=spec.pool_after_s2, ch=c, din=d, dout=d2, src=cur, dst=nxt); plan.need(nxt, d2, c)
-                cur, nxt = nxt, cur
-                d = d2
-        hp = tuple(spec.head_pool)
-        dh = tuple(di - k + 1 for di, k in zip(d, hp))
-        if min(dh) < 1:
-            raise ValueError("input %s too small for the head pool %s" % ((T, H, W), hp))
-        self.head_dims, self.head_width = dh, c
-        plan.add(kind="head", pool=hp, ch=c, din=d, dout=dh, src=cur)
-
-    def _plan_ftcn(self, plan: _Plan, spec: FtcnTTSpec, T, H, W):
-        """FTCN-TT (reference i3d_temporal_var_fix_dropout_tt_cfg.py:290-359): temporal stem, s2..s4 with every spatial
-        kernel 1x1, per-frame average-pooled tokens, one pre-norm transformer layer, LayerNorm + Linear on the class
-        token (time_transformer.py:268-281)."""
-        self.inputs = [("IN", (T, H, W), 1)]
-        cur, nxt = "P0", "P1"
-        d = _pool_out(spec.stem.out_dims(T, H, W), spec.stem.pool_after_bn)
-        d2 = _pool_out(d, spec.stem_pool)
-        if (self.dtype != "f32" and os.environ.get("AF_FUSE_TSTEM_POOL", "1") == "1"
-                and _is_pool(spec.stem_pool, (1, 3, 3), (1, 2, 2), (0, 1, 1))):
-            # 16-bit: the stem's own 1x3x3 / stride-2 max-pool rides behind the temporal stem (the half-resolution tensor -
-            # 822 MB at 16 clips - is neither written nor read back)
-            plan.add(kind="tstem_pool3", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur); plan.need(cur, d2, spec.stem.cout)
-            d = d2
-        else:
-            plan.add(kind="tstem", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur); plan.need(cur, d, spec.stem.cout)
-            plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stem.cout, din=d, dout=d2, src=cur, dst=nxt); plan.need(nxt, d2, spec.stem.cout)
-            cur, nxt, d = nxt, cur, d2
-        fuse_tpool = _is_pool(spec.pool_after_s2, (2, 1, 1), (2, 1, 1), (0, 0, 0))
-        c = spec.stem.cout
-        for si, stage in enumerate(spec.stages):
-            d, c, cur, nxt = plan.stage(stage, d, cur, nxt, "A", "B", tpool_last=(fuse_tpool and si == 0))
-            if si == 0 and not plan.entries[-1].get("tpool"):
-                dp = _pool_out(d, spec.pool_after_s2)
-                plan.add(kind="pool", pool=spec.pool_after_s2, ch=c, din=d, dout=dp, src=cur, dst=nxt); plan.need(nxt, dp, c)
-                cur, nxt, d = nxt, cur, dp
-        # TransformerHead 'time' patches (:133-135): AvgPool3d((1, S, S)) sized from the crop, one token per frame
-        if tuple(d[1:]) != tuple(spec.token_pool[1:]) or d[0] != spec.tokens or c != spec.dim:
-            raise ValueError("FTCN-TT head expects a (%d,%d,%d)x%d feature map, got %s x %d"
-                             % (spec.tokens, spec.token_pool[1], spec.token_pool[2], spec.dim, d, c))
-        self.head_dims, self.head_width = (1, 1, 1), spec.dim
-        plan.add(kind="tt_head", ch=c, din=d, src=cur)
-
-    def _plan_slowfast(self, plan: _Plan, spec: SlowFastSpec, T, H, W):
-        if T % spec.alpha:
-            raise ValueError("SlowFast needs a frame count divisible by alpha=%d (got %d)" % (spec.alpha, T))
-        Ts = T // spec.alpha
-        self.inputs = [("IN_S", (Ts, H, W), spec.alpha), ("IN_F", (T, H, W), 1)]
-        fuse_w = [f.cout for f in spec.fuses]                         # channels each lateral adds to the Slow tensor
-        # stems (+ max-pool); the Slow pool writes at the widened row stride so the lateral can append its channels
-        ds = spec.stems[0].out_dims(Ts, H, W); ds2 = _pool_out(ds, spec.stem_pool)
-        df = spec.stems[1].out_dims(T, H, W); df2 = _pool_out(df, spec.stem_pool)
-        ld0 = spec.stems[0].cout + fuse_w[0]
-        self.rgb3_inputs = set()
-        if (spec.stems[0].conv in getattr(self.weights, "w3", {}) and os.environ.get("AF_SLOWFAST_STEM3", "1") == "1"
-                and _is_pool(spec.stem_pool, (1, 3, 3), (1, 2, 2), (0, 1, 1)) and ds[2] <= 128):
-            # 16-bit: the Slow stem + its max-pool as the K-packed fused stem (3-channel input layout), pooled rows at the widened stride
-            self.rgb3_inputs.add("IN_S")
-            plan.add(kind="stem3_pool", cv=spec.stems[0], din=(Ts, H, W), dout=ds, src="IN_S", dst="S0", ld=ld0)
-            plan.need("S1", ds2, spec.stems[0].cout)
-        else:
-            plan.add(kind="stem", cv=spec.stems[0], din=(Ts, H, W), dout=ds, src="IN_S", dst="S1"); plan.need("S1", ds, spec.stems[0].cout)
-            plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stems[0].cout, din=ds, dout=ds2, src="S1", dst="S0", ld=ld0)
-        plan.need("S0", ds2, ld0)
-        plan.add(kind="stem", cv=spec.stems[1], din=(T, H, W), dout=df, src="IN_F", dst="F1"); plan.need("F1", df, spec.stems[1].cout)
-        plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stems[1].cout, din=df, dout=df2, src="F1", dst="F0")
-        plan.need("F0", df2, spec.stems[1].cout)
-        scur, snxt, fcur, fnxt = "S0", "S1", "F0", "F1"
-        ds, df, cs = ds2, df2, spec.stems[0].cout
-
-        def lateral(fz: ConvSpec, dfast, fbuf, sbuf, c_slow, ld):
-            do = fz.out_dims(*dfast)                                   # FuseFastToSlow: conv + BN + ReLU into the Slow rows
-            plan.add(kind="conv", cv=fz, din=dfast, dout=do, src=fbuf, dst=sbuf, ld=ld, ch_off=c_slow)
-            return do
-
-        if lateral(spec.fuses[0], df, fcur, scur, cs, ld0) != ds:
-            raise ValueError("the Fast->Slow lateral does not land on the Slow grid")
-        cf = spec.stems[1].cout
-        for si, (slow, fast) in enumerate(spec.stages):
-            has_fuse = si + 1 < len(spec.fuses)
-            ld = slow.blocks[-1].c.cout + (fuse_w[si + 1] if has_fuse else 0)
-            ds, cs, scur, snxt = plan.stage(slow, ds, scur, snxt, "A_S", "B_S", last_ld=ld)
-            df, cf, fcur, fnxt = plan.stage(fast, df, fcur, fnxt, "A_F", "B_F")
-            if has_fuse and lateral(spec.fuses[si + 1], df, fcur, scur, cs, ld) != ds:
-                raise ValueError("the Fast->Slow lateral does not land on the Slow grid")
-        hs, hf = (tuple(p) for p in spec.head_pools)
-        dhs = tuple(di - k + 1 for di, k in zip(ds, hs))
-        dhf = tuple(di - k + 1 for di, k in zip(df, hf))
-        if min(dhs) < 1 or dhs != dhf:
-            raise ValueError("input %s does not fit the SlowFast head pools %s / %s" % ((T, H, W), hs, hf))
-        self.head_dims, self.head_width = dhs, cs + cf
-        plan.add(kind="avgpool", pool=hs, ch=cs, din=ds, dout=dhs, src=scur, ch_off=0)
-        plan.add(kind="avgpool", pool=hf, ch=cf, din=df, dout=dhf, src=fcur, ch_off=cs)
-        plan.add(kind="linear")
 
     # -- buffers + op list ------------------------------------------------------------------------------
     def _materialise(self, plan: _Plan):
-        batch, device, weights, spec = self.batch, self.device, self.weights, self.spec
+        batch, device, spec = self.batch, self.device, self.spec
         tdt = _TORCH_DTYPE[self.dtype]
-        es = 4 if self.dtype == "f32" else 2
+        es = _ELEM_SIZE[self.dtype]
         self.buf = {k: torch.empty(max(v, 8), dtype=tdt, device=device) for k, v in plan.sizes.items()}
-        self.rgb3 = getattr(self, "rgb3", False)
         # inputs that feed a K-packed stem take the 3-channel layout (the single input of the i3d engine; SlowFast: the Slow one)
-        r3 = set(getattr(self, "rgb3_inputs", ())) | ({self.inputs[0][0]} if self.rgb3 else set())
+        r3 = plan.rgb3_inputs | ({self.inputs[0][0]} if self.rgb3 else set())
         self.k_pack_f32 = [_lib.AF_OP_PACK3_F32 if name in r3 else _lib.AF_OP_PACK_F32 for name, _, _ in self.inputs]
         self.k_pack_u8 = _lib.AF_OP_PACK3_U8 if self.rgb3 else _lib.AF_OP_PACK_U8
         for name, dims, _ in self.inputs:                           # padded stem inputs: halos stay zero forever
@@ -532,172 +534,18 @@ class Engine:
             pk.out = self.buf[name].data_ptr()
             self.op_names.append("input_pack" if n_pack == 1 else "input_pack_" + name)
             self.op_macs.append(0)
-
-        def fill_conv(cd, cv: ConvSpec, din, dout, relu):
-            _fill_conv_desc(cd, batch, self.code, cv, din, dout, relu)
-
-        def fill_pool(pd, din, ch, kernel, stride, pad, dout):
-            pd.n, (pd.t, pd.h, pd.w), pd.c = batch, din, ch
-            pd.kt, pd.kh, pd.kw = kernel
-            pd.st, pd.sh, pd.sw = stride
-            pd.pt, pd.ph, pd.pw = pad
-            pd.to, pd.ho, pd.wo = dout
-            pd.dtype = self.code
-
         for k, e in enumerate(plan.entries):
             op = self.ops[n_pack + k]
-            kind = e["kind"]
             if "src" in e:
-                op.in_ = self.buf[e["src"]].data_ptr()
+                op.in_ = self._at(e["src"])
             if "dst" in e:
-                op.out = self.buf[e["dst"]].data_ptr() + e.get("ch_off", 0) * es
-            if kind == "tt_head":
+                op.out = self._at(e["dst"]) + e.get("ch_off", 0) * es
+            if e["kind"] == "tt_head":
                 self._materialise_tt_head(n_pack + k, e)
                 continue
-            if kind in ("stem", "stem_pool", "stem3_pool", "conv", "tstem", "tstem_pool3"):
-                cv: ConvSpec = e["cv"]
-                op.kind = {"stem": _lib.AF_OP_STEM, "stem_pool": _lib.AF_OP_STEM_POOL, "stem3_pool": _lib.AF_OP_STEM3_POOL,
-                           "tstem": _lib.AF_OP_TSTEM, "tstem_pool3": _lib.AF_OP_TSTEM_POOL3}.get(kind, _lib.AF_OP_CONV)
-                op.tag = TAG_STEM if kind != "conv" else _conv_tag(cv)
-                # a, b, stems and laterals carry their own ReLU; c (final_bn) takes the block's add + ReLU; the
-                # projection shortcut has neither (resnet_helper.py:311-326, 438-444; video_model_builder.py:136-143)
-                fill_conv(op.conv, cv, e["din"], e["dout"], cv.relu or cv.final_bn)
-                op.conv.tpool = int(e.get("tpool") or 0)
-                op.weight = (weights.w3 if kind == "stem3_pool" else weights.w)[cv.conv].data_ptr()
-                op.scale = weights.scale[cv.conv].data_ptr()
-                op.shift = weights.shift[cv.conv].data_ptr()
-                op.residual = self.buf[e["res"]].data_ptr() if e.get("res") else None
-                op.out_ld = e.get("ld", cv.cout)
-                self.op_names.append(cv.conv)
-                self.op_macs.append(batch * cv.macs(*e["din"]))
-            elif kind == "ca":
-                cvc, cva = e["cv"], e["cv2"]
-                op.kind, op.tag = _lib.AF_OP_CONV_CA, TAG_CONV_CA
-                fill_conv(op.conv, cvc, e["din"], e["dout"], True)
-                fill_conv(op.conv2, cva, e["dout"], cva.out_dims(*e["dout"]), True)
-                op.weight2, op.scale2, op.shift2 = (weights.w[cva.conv].data_ptr(), weights.scale[cva.conv].data_ptr(),
-                                                    weights.shift[cva.conv].data_ptr())
-                macs = cvc.macs(*e["din"]) + cva.macs(*e["dout"])
-                if e.get("cv3") is not None:                 # projection block: folded weights, scale = ones, summed shifts
-                    cv1 = e["cv3"]
-                    fill_conv(op.conv3, cv1, e["din3"], e["dout"], True)
-                    op.weight, op.weight3 = weights.w_folded[cvc.conv].data_ptr(), weights.w_folded[cv1.conv].data_ptr()
-                    op.in3 = self.buf[e["src3"]].data_ptr()
-                    op.scale, op.shift = weights.ones[cvc.conv].data_ptr(), weights.shift_sum[cvc.conv].data_ptr()
-                    op.residual = None
-                    macs += cv1.macs(*e["din3"])
-                else:
-                    op.weight, op.scale, op.shift = (weights.w[cvc.conv].data_ptr(), weights.scale[cvc.conv].data_ptr(),
-                                                     weights.shift[cvc.conv].data_ptr())
-                    op.residual = self.buf[e["res"]].data_ptr()
-                op.aux = self.buf[e["dst2"]].data_ptr()
-                op.out_ld = cvc.cout
-                self.op_names.append(cvc.conv + ("+branch1" if e.get("cv3") is not None else "") + "->" + cva.conv.split("resnet.")[-1])
-                self.op_macs.append(batch * macs)
-            elif kind == "cpa":
-                cvc, cva = e["cv"], e["cv2"]
-                dp = (e["dout"][0] // 2,) + tuple(e["dout"][1:])
-                op.kind, op.tag = _lib.AF_OP_CONV_CPA, TAG_CONV_CA
-                fill_conv(op.conv, cvc, e["din"], e["dout"], True)
-                op.conv.tpool = 1
-                fill_conv(op.conv2, cva, dp, cva.out_dims(*dp), True)
-                op.weight, op.scale, op.shift = (weights.w[cvc.conv].data_ptr(), weights.scale[cvc.conv].data_ptr(),
-                                                 weights.shift[cvc.conv].data_ptr())
-                op.weight2, op.scale2, op.shift2 = (weights.w[cva.conv].data_ptr(), weights.scale[cva.conv].data_ptr(),
-                                                    weights.shift[cva.conv].data_ptr())
-                op.residual = self.buf[e["res"]].data_ptr()
-                op.aux = self.buf[e["dst2"]].data_ptr()
-                op.out_ld, op.x_sub = cvc.cout, e["x_sub"]
-                self.op_names.append(cvc.conv + "+pool->" + cva.conv.split("resnet.")[-1])
-                self.op_macs.append(batch * (cvc.macs(*e["din"]) + cva.macs(*dp)))
-            elif kind == "abc":
-                cva, cvb, cvc = e["cv"], e["cv2"], e["cv3"]
-                op.kind, op.tag = _lib.AF_OP_BLOCK_ABC, TAG_BLOCK_ABC
-                fill_conv(op.conv, cva, e["din"], e["din"], True)
-                fill_conv(op.conv2, cvb, e["din"], e["din"], True)
-                fill_conv(op.conv3, cvc, e["din"], e["din"], True)       # final_bn: takes the block's add + ReLU
-                op.weight, op.scale, op.shift = (weights.w[cva.conv].data_ptr(), weights.scale[cva.conv].data_ptr(),
-                                                 weights.shift[cva.conv].data_ptr())
-                op.weight2, op.scale2, op.shift2 = (weights.w[cvb.conv].data_ptr(), weights.scale[cvb.conv].data_ptr(),
-                                                    weights.shift[cvb.conv].data_ptr())
-                macs = cva.macs(*e["din"]) + cvb.macs(*e["din"]) + cvc.macs(*e["din"])
-                if e.get("cv4") is not None:                 # projection block: folded weights, scale = ones, summed shifts
-                    cv1 = e["cv4"]
-                    fill_conv(op.conv4, cv1, e["din"], e["din"], True)
-                    op.weight3, op.weight4 = weights.w_folded[cvc.conv].data_ptr(), weights.w_folded[cv1.conv].data_ptr()
-                    op.scale3, op.shift3 = weights.ones[cvc.conv].data_ptr(), weights.shift_sum[cvc.conv].data_ptr()
-                    macs += cv1.macs(*e["din"])
-                else:
-                    op.weight3, op.scale3, op.shift3 = (weights.w[cvc.conv].data_ptr(), weights.scale[cvc.conv].data_ptr(),
-                                                        weights.shift[cvc.conv].data_ptr())
-                op.out_ld = e.get("ld", cvc.cout)
-                self.op_names.append(cva.conv.rsplit(".", 1)[0] + ".a+b+c" + ("+branch1" if e.get("cv4") is not None else ""))
-                self.op_macs.append(batch * macs)
-            elif kind == "bc":
-                cvb, cvc = e["cv"], e["cv2"]
-                op.kind, op.tag = _lib.AF_OP_CONV_BC, TAG_CONV_BC
-                fill_conv(op.conv, cvb, e["din"], e["dmid"], True)
-                fill_conv(op.conv2, cvc, e["dmid"], e["dout"], True)      # final_bn: takes the block's add + ReLU
-                op.weight, op.scale, op.shift = (weights.w[cvb.conv].data_ptr(), weights.scale[cvb.conv].data_ptr(),
-                                                 weights.shift[cvb.conv].data_ptr())
-                op.weight2, op.scale2, op.shift2 = (weights.w[cvc.conv].data_ptr(), weights.scale[cvc.conv].data_ptr(),
-                                                    weights.shift[cvc.conv].data_ptr())
-                op.residual = self.buf[e["res"]].data_ptr()
-                op.out_ld = e.get("ld", cvc.cout)
-                self.op_names.append(cvb.conv + "+c")
-                self.op_macs.append(batch * (cvb.macs(*e["din"]) + cvc.macs(*e["dmid"])))
-            elif kind == "dual":
-                cvc, cv1 = e["cv"], e["cv2"]
-                op.kind, op.tag = _lib.AF_OP_CONV_DUAL, _conv_tag(cvc)
-                fill_conv(op.conv, cvc, e["din"], e["dout"], True)
-                fill_conv(op.conv2, cv1, e["din2"], e["dout"], True)
-                op.weight = weights.w_folded[cvc.conv].data_ptr()
-                op.weight2 = weights.w_folded[cv1.conv].data_ptr()
-                op.in2 = self.buf[e["src2"]].data_ptr()
-                op.scale = weights.ones[cvc.conv].data_ptr()
-                op.shift = weights.shift_sum[cvc.conv].data_ptr()
-                op.residual = None
-                op.out_ld = e.get("ld", cvc.cout)
-                self.op_names.append(cvc.conv + "+branch1")
-                self.op_macs.append(batch * (cvc.macs(*e["din"]) + cv1.macs(*e["din2"])))
-            elif kind == "pool":
-                p = e["pool"]
-                op.kind, op.tag = _lib.AF_OP_MAXPOOL, TAG_POOL
-                fill_pool(op.pool, e["din"], e["ch"], p.kernel, p.stride, p.pad, e["dout"])
-                op.pool.out_ld = e.get("ld", 0)
-                self.op_names.append("maxpool_%dx%dx%d" % tuple(p.kernel))
-                self.op_macs.append(0)
-            elif kind == "head":
-                op.kind, op.tag = _lib.AF_OP_HEAD, TAG_HEAD
-                fill_pool(op.pool, e["din"], e["ch"], e["pool"], (1, 1, 1), (0, 0, 0), e["dout"])
-                op.weight = weights.fc_w.data_ptr()
-                op.scale = weights.fc_b.data_ptr()
-                op.aux = self.pooled.data_ptr()
-                op.out = self.logits.data_ptr()
-                op.scores = self.scores.data_ptr() if self.scores is not None else None
-                op.num_classes = spec.num_classes
-                self.op_names.append("head")
-                self.op_macs.append(0)
-            elif kind == "avgpool":
-                op.kind, op.tag = _lib.AF_OP_AVGPOOL, TAG_HEAD
-                fill_pool(op.pool, e["din"], e["ch"], e["pool"], (1, 1, 1), (0, 0, 0), e["dout"])
-                op.out = self.pooled.data_ptr() + e["ch_off"] * 4
-                op.out_ld = self.head_width
-                self.op_names.append("head_avgpool_%d" % e["ch_off"])
-                self.op_macs.append(0)
-            elif kind == "linear":
-                op.kind, op.tag = _lib.AF_OP_LINEAR, TAG_HEAD
-                op.in_ = self.pooled.data_ptr()
-                op.weight = weights.fc_w.data_ptr()
-                op.scale = weights.fc_b.data_ptr()
-                op.pool.n, op.pool.c = batch * self.head_positions, self.head_width
-                op.num_classes = spec.num_classes
-                op.out = self.logits.data_ptr()
-                op.scores = self.scores.data_ptr() if self.scores is not None else None
-                self.op_names.append("head_linear")
-                self.op_macs.append(0)
-            else:
-                raise KeyError(kind)
+            name, macs = self._EMIT[e["kind"]](self, op, e)
+            self.op_names.append(name)
+            self.op_macs.append(batch * macs)
         # split-K scratch (small batches, long-K layers): sized by the library, owned by this engine (one per engine =
         # one per device and per stream of work, since an engine enqueues its forward on one stream); consecutive
         # launches of one forward reuse it in stream order
@@ -711,6 +559,143 @@ class Engine:
                 self.ops[i].workspace = self.workspace.data_ptr()
                 self.ops[i].workspace_bytes = need
 
+    # One function per plan-entry kind: fills ``op`` (in_ / out are already bound) and returns (op name, MACs per clip).
+    # Every conv of a fused launch is described with relu = 1, as the library's *_fusable predicates were asked.
+    def _at(self, buf: Optional[str]):
+        return self.buf[buf].data_ptr() if buf else None
+
+    def _desc(self, cv: ConvSpec, din, dout, relu=True, tpool=0):
+        return _conv_desc(self.batch, self.code, cv, din, dout, relu, tpool)
+
+    def _pool_desc(self, e, kernel, stride=(1, 1, 1), pad=(0, 0, 0)):
+        return _lib.pool_desc(self.batch, e["din"], e["ch"], kernel, stride, pad, self.code, e["dout"], e.get("ld", 0))
+
+    _CONV_KINDS = {"stem": _lib.AF_OP_STEM, "stem_pool": _lib.AF_OP_STEM_POOL, "stem3_pool": _lib.AF_OP_STEM3_POOL,
+                   "tstem": _lib.AF_OP_TSTEM, "tstem_pool3": _lib.AF_OP_TSTEM_POOL3, "conv": _lib.AF_OP_CONV}
+
+    def _emit_conv(self, op, e):
+        cv: ConvSpec = e["cv"]
+        op.kind = self._CONV_KINDS[e["kind"]]
+        op.tag = TAG_STEM if e["kind"] != "conv" else _conv_tag(cv)
+        # a, b, stems and laterals carry their own ReLU; c (final_bn) takes the block's add + ReLU; the
+        # projection shortcut has neither (resnet_helper.py:311-326, 438-444; video_model_builder.py:136-143)
+        op.conv = self._desc(cv, e["din"], e["dout"], cv.relu or cv.final_bn, e.get("tpool") or 0)
+        op.weight, op.scale, op.shift = self.weights.bn(cv)
+        if e["kind"] == "stem3_pool":
+            op.weight = self.weights.w3[cv.conv].data_ptr()
+        op.residual = self._at(e.get("res"))
+        op.out_ld = e.get("ld", cv.cout)
+        return cv.conv, cv.macs(*e["din"])
+
+    def _emit_ca(self, op, e):
+        cvc, cva, cv1 = e["cv"], e["cv2"], e.get("cv3")
+        op.kind, op.tag = _lib.AF_OP_CONV_CA, TAG_CONV_CA
+        op.conv = self._desc(cvc, e["din"], e["dout"])
+        op.conv2 = self._desc(cva, e["dout"], cva.out_dims(*e["dout"]))
+        op.weight2, op.scale2, op.shift2 = self.weights.bn(cva)
+        macs = cvc.macs(*e["din"]) + cva.macs(*e["dout"])
+        if cv1 is not None:                          # projection block: no residual tensor
+            op.conv3 = self._desc(cv1, e["din3"], e["dout"])
+            op.weight, op.weight3, op.scale, op.shift = self.weights.folded(cvc, cv1)
+            op.in3 = self._at(e["src3"])
+            macs += cv1.macs(*e["din3"])
+        else:
+            op.weight, op.scale, op.shift = self.weights.bn(cvc)
+            op.residual = self._at(e["res"])
+        op.aux = self._at(e["dst2"])
+        op.out_ld = cvc.cout
+        return cvc.conv + ("+branch1" if cv1 is not None else "") + "->" + cva.conv.split("resnet.")[-1], macs
+
+    def _emit_cpa(self, op, e):
+        cvc, cva = e["cv"], e["cv2"]
+        dp = (e["dout"][0] // 2,) + tuple(e["dout"][1:])
+        op.kind, op.tag = _lib.AF_OP_CONV_CPA, TAG_CONV_CA
+        op.conv = self._desc(cvc, e["din"], e["dout"], tpool=1)
+        op.conv2 = self._desc(cva, dp, cva.out_dims(*dp))
+        op.weight, op.scale, op.shift = self.weights.bn(cvc)
+        op.weight2, op.scale2, op.shift2 = self.weights.bn(cva)
+        op.residual = self._at(e["res"])
+        op.aux = self._at(e["dst2"])
+        op.out_ld, op.x_sub = cvc.cout, e["x_sub"]
+        return cvc.conv + "+pool->" + cva.conv.split("resnet.")[-1], cvc.macs(*e["din"]) + cva.macs(*dp)
+
+    def _emit_abc(self, op, e):
+        cva, cvb, cvc, cv1 = e["cv"], e["cv2"], e["cv3"], e.get("cv4")
+        d = e["din"]
+        op.kind, op.tag = _lib.AF_OP_BLOCK_ABC, TAG_BLOCK_ABC
+        op.conv, op.conv2, op.conv3 = self._desc(cva, d, d), self._desc(cvb, d, d), self._desc(cvc, d, d)
+        op.weight, op.scale, op.shift = self.weights.bn(cva)
+        op.weight2, op.scale2, op.shift2 = self.weights.bn(cvb)
+        macs = cva.macs(*d) + cvb.macs(*d) + cvc.macs(*d)
+        if cv1 is not None:                          # projection block
+            op.conv4 = self._desc(cv1, d, d)
+            op.weight3, op.weight4, op.scale3, op.shift3 = self.weights.folded(cvc, cv1)
+            macs += cv1.macs(*d)
+        else:
+            op.weight3, op.scale3, op.shift3 = self.weights.bn(cvc)
+        op.out_ld = e.get("ld", cvc.cout)
+        return cva.conv.rsplit(".", 1)[0] + ".a+b+c" + ("+branch1" if cv1 is not None else ""), macs
+
+    def _emit_bc(self, op, e):
+        cvb, cvc = e["cv"], e["cv2"]
+        op.kind, op.tag = _lib.AF_OP_CONV_BC, TAG_CONV_BC
+        op.conv = self._desc(cvb, e["din"], e["dmid"])
+        op.conv2 = self._desc(cvc, e["dmid"], e["dout"])
+        op.weight, op.scale, op.shift = self.weights.bn(cvb)
+        op.weight2, op.scale2, op.shift2 = self.weights.bn(cvc)
+        op.residual = self._at(e["res"])
+        op.out_ld = e.get("ld", cvc.cout)
+        return cvb.conv + "+c", cvb.macs(*e["din"]) + cvc.macs(*e["dmid"])
+
+    def _emit_dual(self, op, e):
+        cvc, cv1 = e["cv"], e["cv2"]
+        op.kind, op.tag = _lib.AF_OP_CONV_DUAL, _conv_tag(cvc)
+        op.conv = self._desc(cvc, e["din"], e["dout"])
+        op.conv2 = self._desc(cv1, e["din2"], e["dout"])
+        op.weight, op.weight2, op.scale, op.shift = self.weights.folded(cvc, cv1)
+        op.in2 = self._at(e["src2"])
+        op.out_ld = e.get("ld", cvc.cout)
+        return cvc.conv + "+branch1", cvc.macs(*e["din"]) + cv1.macs(*e["din2"])
+
+    def _emit_pool(self, op, e):
+        p = e["pool"]
+        op.kind, op.tag = _lib.AF_OP_MAXPOOL, TAG_POOL
+        op.pool = self._pool_desc(e, p.kernel, p.stride, p.pad)
+        return "maxpool_%dx%dx%d" % tuple(p.kernel), 0
+
+    def _bind_fc(self, op):
+        """the head's Linear (+ the score epilogue) into ``logits`` / ``scores``"""
+        op.tag = TAG_HEAD
+        op.weight, op.scale = self.weights.fc_w.data_ptr(), self.weights.fc_b.data_ptr()
+        op.num_classes = self.spec.num_classes
+        op.out = self.logits.data_ptr()
+        op.scores = self.scores.data_ptr() if self.scores is not None else None
+
+    def _emit_head(self, op, e):
+        op.kind = _lib.AF_OP_HEAD
+        op.pool = self._pool_desc(e, e["pool"])
+        op.aux = self.pooled.data_ptr()
+        self._bind_fc(op)
+        return "head", 0
+
+    def _emit_linear(self, op, e):
+        op.kind = _lib.AF_OP_LINEAR
+        op.in_ = self.pooled.data_ptr()
+        op.pool.n, op.pool.c = self.batch * self.head_positions, self.head_width
+        self._bind_fc(op)
+        return "head_linear", 0
+
+    def _emit_avgpool(self, op, e):
+        op.kind, op.tag = _lib.AF_OP_AVGPOOL, TAG_HEAD
+        op.pool = self._pool_desc(e, e["pool"])
+        op.out = self.pooled.data_ptr() + e["ch_off"] * 4
+        op.out_ld = self.head_width
+        return "head_avgpool_%d" % e["ch_off"], 0
+
+    _EMIT = {"stem": _emit_conv, "stem_pool": _emit_conv, "stem3_pool": _emit_conv, "tstem": _emit_conv, "tstem_pool3": _emit_conv,
+             "conv": _emit_conv, "ca": _emit_ca, "cpa": _emit_cpa, "abc": _emit_abc, "bc": _emit_bc, "dual": _emit_dual,
+             "pool": _emit_pool, "head": _emit_head, "avgpool": _emit_avgpool, "linear": _emit_linear}
+
     TT_HEAD_OPS = 12
 
     def _materialise_tt_head(self, first: int, e):
@@ -722,7 +707,6 @@ class Engine:
         self.tokens_pooled = fb(batch, spec.tokens, dim)
         self.fbuf = {"x": fb(rows, dim), "h": fb(rows, dim), "qkv": fb(rows, 3 * inner), "att": fb(rows, inner),
                      "x2": fb(rows, dim), "ff": fb(rows, spec.mlp_dim), "x3": fb(rows, dim)}
-        f32code = _lib.DTYPE_CODES["f32"]
         i = [first]
 
         def nxt(name, tag=TAG_HEAD, macs=0):
@@ -739,12 +723,7 @@ class Engine:
             packed, ones, bias, cin, cout = w.lin[key]
             op = nxt(name, TAG_CONV_1x1x1, rows * cin * cout)
             op.kind = _lib.AF_OP_CONV
-            cd = op.conv
-            cd.n, cd.t, cd.h, cd.w, cd.cin, cd.cout = 1, 1, 1, rows, cin, cout
-            cd.kt = cd.kh = cd.kw = cd.st = cd.sh = cd.sw = 1
-            cd.pt = cd.ph = cd.pw = 0
-            cd.to, cd.ho, cd.wo = 1, 1, rows
-            cd.relu, cd.dtype, cd.tpool = 0, f32code, 0
+            op.conv = _lib.conv_desc(1, (1, 1, rows), cin, cout, (1, 1, 1), (1, 1, 1), (0, 0, 0), False, _lib.AF_F32)
             op.in_, op.out = self.fbuf[src].data_ptr(), self.fbuf[dst].data_ptr()
             op.weight, op.scale, op.shift = packed.data_ptr(), ones.data_ptr(), bias.data_ptr()
             op.residual = self.fbuf[res].data_ptr() if res else None
@@ -759,13 +738,7 @@ class Engine:
 
         op = nxt("avgpool_tokens")                                         # (B, T/2, dim) per-frame tokens
         op.kind = _lib.AF_OP_AVGPOOL
-        pd = op.pool
-        pd.n, (pd.t, pd.h, pd.w), pd.c = batch, e["din"], e["ch"]
-        pd.kt, pd.kh, pd.kw = spec.token_pool
-        pd.st = pd.sh = pd.sw = 1
-        pd.pt = pd.ph = pd.pw = 0
-        pd.to, pd.ho, pd.wo = e["din"][0], 1, 1
-        pd.dtype = self.code
+        op.pool = _lib.pool_desc(batch, e["din"], e["ch"], spec.token_pool, (1, 1, 1), (0, 0, 0), self.code, dout=(e["din"][0], 1, 1))
         op.in_, op.out, op.out_ld = self.buf[e["src"]].data_ptr(), self.tokens_pooled.data_ptr(), dim
         op = nxt("tokens")                                                 # class token + position embedding
         op.kind = _lib.AF_OP_TOKENS
@@ -790,11 +763,9 @@ class Engine:
         layernorm("head_norm", "head", self.fbuf["x3"], self.pooled, batch, n1 * dim, dim)
         op = nxt("head_linear")
         op.kind = _lib.AF_OP_LINEAR
-        op.in_, op.weight, op.scale = self.pooled.data_ptr(), w.fc_w.data_ptr(), w.fc_b.data_ptr()
+        op.in_ = self.pooled.data_ptr()
         op.pool.n, op.pool.c = batch, dim
-        op.num_classes = spec.num_classes
-        op.out = self.logits.data_ptr()
-        op.scores = self.scores.data_ptr() if self.scores is not None else None
+        self._bind_fc(op)
         assert i[0] - first == self.TT_HEAD_OPS
 
     # -- input binding -------------------------------------------------------------------------------------

@@ -551,3 +551,46 @@ def test_align_plan_host_helper_matches_the_python_path():
     crops[4].x = W - images[4].shape[1] + 1                                    # one pixel over the right edge of the canvas
     rc = _lib.lib.af_align_plan_u8(crops, n, H, W, m, 224, rects, frames, C.byref(tot), C.byref(bad))
     assert rc != 0 and bad.value == 4
+
+
+def _kinds(text):
+    """'conv*2 ca' -> ['conv', 'conv', 'ca']"""
+    out = []
+    for word in text.split():
+        kind, _, n = word.partition("*")
+        out += [kind] * int(n or 1)
+    return out
+
+
+# launch kinds of the bf16 plans at 16 clips of 32 x 224 x 224, default switches (name*n = n launches in a row)
+PLAN_KINDS = {
+    "i3d": "stem3_pool conv*2 ca conv ca conv*4 dual conv*11 dual conv*17 dual conv*6 head",
+    "slowfast": "stem3_pool stem pool conv*3 dual conv*6 abc*3 conv*3 dual conv*11 dual abc*3 conv*3 dual conv*17 dual conv*18 dual "
+                "conv*8 dual conv*6 avgpool*2 linear",
+    "ftcn_tt": "tstem_pool3 conv*2 ca conv ca conv*34 tt_head",
+}
+PLAN_KINDS_I3D_CPA = "stem3_pool conv*2 ca conv ca conv cpa conv dual conv*11 dual conv*17 dual conv*6 head"
+
+
+def test_plans_need_no_device_and_keep_their_launch_kinds(monkeypatch):
+    """planning is host logic (spec + the library's *_fusable predicates): a drifting switch default or fusion decision shows up
+    here as a changed sequence of launch kinds"""
+    from af_mi355x import engine
+    for name in engine.SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    specs = {"i3d": arch.i3d_r50_spec(), "slowfast": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
+    rgb3 = {"i3d": {specs["i3d"].stem.conv}, "slowfast": {specs["slowfast"].stems[0].conv}, "ftcn_tt": set()}   # PackedWeights.w3 at 16 bits
+
+    def plan(net):
+        spec = specs[net]
+        return engine.plan_network(spec, "bf16", 16, (spec.num_frames, spec.crop, spec.crop), rgb3[net])
+
+    for net, want in PLAN_KINDS.items():
+        p = plan(net)
+        assert [e["kind"] for e in p.entries] == _kinds(want), net
+        assert p.rgb3 == (net == "i3d") and p.rgb3_inputs == ({"IN_S"} if net == "slowfast" else set())
+        assert len(p.inputs) == (2 if net == "slowfast" else 1) and p.head_dims is not None and p.head_width > 0
+    assert engine.SWITCHES == {"AF_FUSE_BC": False, "AF_FUSE_CA": True, "AF_FUSE_CPA": False, "AF_FUSE_ABC": True,
+                               "AF_FUSE_TSTEM_POOL": True, "AF_SLOWFAST_STEM3": True}
+    monkeypatch.setenv("AF_FUSE_CPA", "1")           # read when the plan is built
+    assert [e["kind"] for e in plan("i3d").entries] == _kinds(PLAN_KINDS_I3D_CPA)
