@@ -29,6 +29,20 @@ inline void fill_stamps(Args& a, const char* dbg_knob) {
     a.dbg = env_int(dbg_knob, 0);
 #endif
 }
+// ... and its device side: shader-clock stamps around the phases of a tile / unit, kept in registers and written behind the last
+// output store to a buffer nothing else reads (tools/stamps_lib.sh; never the shipped library).  `block` is the kernel's workgroup index.
+#ifdef AF_STAMPS
+#define AF_STAMP_DECL unsigned long long stamp_v[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define AF_DBG(bit) (a.dbg & (bit))
+#define AF_STAMP(slot) stamp_v[slot] = (slot) >= 6 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime()
+#define AF_STAMP_FLUSH(block) do { if (a.stamps && lane < 8) a.stamps[((long long)(block) * 8 + wave) * 8 + lane] = \
+    lane == 0 ? stamp_v[0] : lane == 1 ? stamp_v[1] : lane == 2 ? stamp_v[2] : lane == 3 ? stamp_v[3] : lane == 4 ? stamp_v[4] : lane == 5 ? stamp_v[5] : lane == 6 ? stamp_v[6] : stamp_v[7]; } while (0)
+#else
+#define AF_STAMP_DECL do {} while (0)
+#define AF_DBG(bit) false
+#define AF_STAMP(slot) do {} while (0)
+#define AF_STAMP_FLUSH(block) do {} while (0)
+#endif
 
 // ---- LDS-DMA helpers shared by the convolution kernels
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -164,6 +178,10 @@ template <int I> struct IC { static constexpr int value = I; constexpr operator 
 template <int N, int I = 0, class F> __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) { f(IC<I>{}); static_for<N, I + 1>(f); }
 }
+// run-time dtype -> template argument: f(IC<AF_BF16>{}) or f(IC<AF_F16>{}) for the 16-bit kernels (`f` is a generic lambda that
+// launches kernel<dt, ...>); with_dtype adds fp32 where a kernel has that form
+template <class F> inline auto with_dtype16(int dtype, F&& f) { return dtype == AF_BF16 ? f(IC<AF_BF16>{}) : f(IC<AF_F16>{}); }
+template <class F> inline auto with_dtype(int dtype, F&& f) { return dtype == AF_F32 ? f(IC<AF_F32>{}) : with_dtype16(dtype, f); }
 
 // af_conv133.hip: register-resident-weights 1x3x3 64->64 kernel (s2 `b` convs), 16-bit dtypes
 bool conv133_applies(const af_conv_desc* d, const void* residual, int out_ld);
@@ -211,6 +229,7 @@ int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, con
 // One-time PER-DEVICE setup.  hipFuncSetAttribute and the CU count belong to a device, and one process may drive several
 // (one engine per device): every "done once" flag is therefore indexed by the current device ordinal.
 constexpr int kMaxDevices = 64;
+constexpr int kLdsBudget = 160 * 1024;   // LDS of a CU: what one workgroup may ask for
 static inline int current_device() {
     int d = 0;
     return (hipGetDevice(&d) == hipSuccess && d >= 0 && d < kMaxDevices) ? d : -1;
@@ -337,32 +356,34 @@ template <> struct Vec4<AF_F32> {
     static __device__ __forceinline__ void store(void* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
     static __device__ __forceinline__ f32x4 load(const void* p) { return *reinterpret_cast<const f32x4*>(p); }
 };
-// store_relu: ReLU (NaN kept, like torch's clamp_min) + the one rounding + store
-template <> struct Vec4<AF_BF16> {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
+// the 16-bit types (T = __bf16 / _Float16).  store_relu: ReLU (NaN kept, like torch's clamp_min) + the one rounding + store
+template <class T> struct Vec4x16 {
+    typedef T t4 __attribute__((ext_vector_type(4)));
     static __device__ __forceinline__ void store(void* p, f32x4 v) {
-        b4 o; o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
-        *reinterpret_cast<b4*>(p) = o;
+        t4 o; o[0] = (T)v[0]; o[1] = (T)v[1]; o[2] = (T)v[2]; o[3] = (T)v[3];
+        *reinterpret_cast<t4*>(p) = o;
     }
     static __device__ __forceinline__ void store_relu(void* p, f32x4 v) {
         v[0] = relu_f(v[0]); v[1] = relu_f(v[1]); v[2] = relu_f(v[2]); v[3] = relu_f(v[3]);
         store(p, v);
     }
     static __device__ __forceinline__ unsigned __attribute__((ext_vector_type(2))) pack_relu(f32x4 v) {
-        b4 o; o[0] = (__bf16)relu_f(v[0]); o[1] = (__bf16)relu_f(v[1]); o[2] = (__bf16)relu_f(v[2]); o[3] = (__bf16)relu_f(v[3]);
+        t4 o; o[0] = (T)relu_f(v[0]); o[1] = (T)relu_f(v[1]); o[2] = (T)relu_f(v[2]); o[3] = (T)relu_f(v[3]);
         return __builtin_bit_cast(unsigned __attribute__((ext_vector_type(2))), o);
     }
     static __device__ __forceinline__ f32x4 load(const void* p) {
-        b4 i = *reinterpret_cast<const b4*>(p);
+        t4 i = *reinterpret_cast<const t4*>(p);
         f32x4 o; o[0] = (float)i[0]; o[1] = (float)i[1]; o[2] = (float)i[2]; o[3] = (float)i[3];
         return o;
     }
     static __device__ __forceinline__ f32x4 unpack(unsigned __attribute__((ext_vector_type(2))) raw) {   // 8 bytes read earlier
-        b4 i = __builtin_bit_cast(b4, raw);
+        t4 i = __builtin_bit_cast(t4, raw);
         f32x4 o; o[0] = (float)i[0]; o[1] = (float)i[1]; o[2] = (float)i[2]; o[3] = (float)i[3];
         return o;
     }
 };
+template <> struct Vec4<AF_BF16> : Vec4x16<__bf16> {};
+template <> struct Vec4<AF_F16> : Vec4x16<_Float16> {};
 // Two MFMA accumulator tiles (lane = 4 consecutive channels of position frow, k-group fg) -> 16 contiguous bytes per lane
 // without LDS: v_permlane16_swap_b32 (gfx950) exchanges the odd 16-lane rows of its first operand with the even rows of the second,
 // so after swapping the packed halves of tile A and tile B a lane holds 8 consecutive channels: fg = 0 / 2: A's channels
@@ -373,30 +394,4 @@ __device__ __forceinline__ u32x4 swap_pair16(u32x2 a, u32x2 b) {
     const u32x2 r1 = __builtin_amdgcn_permlane16_swap(a[1], b[1], false, false);
     return u32x4{r0[0], r1[0], r0[1], r1[1]};
 }
-template <> struct Vec4<AF_F16> {
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ void store(void* p, f32x4 v) {
-        h4 o; o[0] = (_Float16)v[0]; o[1] = (_Float16)v[1]; o[2] = (_Float16)v[2]; o[3] = (_Float16)v[3];
-        *reinterpret_cast<h4*>(p) = o;
-    }
-    static __device__ __forceinline__ void store_relu(void* p, f32x4 v) {
-        v[0] = relu_f(v[0]); v[1] = relu_f(v[1]); v[2] = relu_f(v[2]); v[3] = relu_f(v[3]);
-        store(p, v);
-    }
-    static __device__ __forceinline__ unsigned __attribute__((ext_vector_type(2))) pack_relu(f32x4 v) {
-        h4 o; o[0] = (_Float16)relu_f(v[0]); o[1] = (_Float16)relu_f(v[1]); o[2] = (_Float16)relu_f(v[2]); o[3] = (_Float16)relu_f(v[3]);
-        return __builtin_bit_cast(unsigned __attribute__((ext_vector_type(2))), o);
-    }
-    static __device__ __forceinline__ f32x4 load(const void* p) {
-        h4 i = *reinterpret_cast<const h4*>(p);
-        f32x4 o; o[0] = (float)i[0]; o[1] = (float)i[1]; o[2] = (float)i[2]; o[3] = (float)i[3];
-        return o;
-    }
-    static __device__ __forceinline__ f32x4 unpack(unsigned __attribute__((ext_vector_type(2))) raw) {
-        h4 i = __builtin_bit_cast(h4, raw);
-        f32x4 o; o[0] = (float)i[0]; o[1] = (float)i[1]; o[2] = (float)i[2]; o[3] = (float)i[3];
-        return o;
-    }
-};
-
 }  // namespace af

@@ -25,20 +25,6 @@
 
 namespace af {
 
-// Diagnostic build (-DAF_STAMPS, tools/stamps_lib.sh; never the shipped library): shader-clock stamps around the phases of a tile
-#ifdef AF_STAMPS
-#define AF_STAMP_DECL unsigned long long stamp_v[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define AF_DBG(bit) (a.dbg & (bit))
-#define AF_STAMP(slot) stamp_v[slot] = (slot) >= 6 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime()
-#define AF_STAMP_FLUSH do { if (a.stamps && lane < 8) a.stamps[((long long)bid * 8 + wave) * 8 + lane] = \
-    lane == 0 ? stamp_v[0] : lane == 1 ? stamp_v[1] : lane == 2 ? stamp_v[2] : lane == 3 ? stamp_v[3] : lane == 4 ? stamp_v[4] : lane == 5 ? stamp_v[5] : lane == 6 ? stamp_v[6] : stamp_v[7]; } while (0)
-#else
-#define AF_STAMP_DECL do {} while (0)
-#define AF_DBG(bit) false
-#define AF_STAMP(slot) do {} while (0)
-#define AF_STAMP_FLUSH do {} while (0)
-#endif
-
 struct ConvArgs {
     const char* in;
     const char* w;
@@ -586,7 +572,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& a, const int bid
                 __builtin_amdgcn_wave_barrier();
             }
             AF_STAMP(3); AF_STAMP(7);
-            AF_STAMP_FLUSH;
+            AF_STAMP_FLUSH(bid);
             return;
         }
     }
@@ -717,7 +703,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& a, const int bid
         __builtin_amdgcn_wave_barrier();
     }
     AF_STAMP(3); AF_STAMP(7);
-    AF_STAMP_FLUSH;
+    AF_STAMP_FLUSH(bid);
 }
 
 // (Round 4, late: PERSISTENT workgroups - a workgroup walking tiles blockIdx.x, blockIdx.x + gridDim.x, ... - were built on this body and
@@ -757,25 +743,39 @@ static int launch(const ConvArgs& a, hipStream_t stream) {
 // other's load / store phases.
 enum { VAR_128x256 = 0, VAR_64x256 = 1, VAR_128x128 = 2, VAR_64x128 = 3, VAR_C133 = 4, VAR_128x128_R2 = 5, VAR_256x256 = 6,
        VAR_128x512 = 7, VAR_C311 = 8, VAR_SMALL = 9, VAR_C111 = 10, VAR_C133G = 11, VAR_256x224 = 12, VAR_C311G = 13, VAR_COUNT = 14 };
-static const char* const kVariantNames[] = {"conv_igemm<BN=128,BM=256>", "conv_igemm<BN=64,BM=256>",
-                                            "conv_igemm<BN=128,BM=128>", "conv_igemm<BN=64,BM=128>",
-                                            "conv133_c64<weights in registers>", "conv_igemm<BN=128,BM=128>",
-                                            "conv_igemm<BN=256,BM=256>", "conv_igemm<BN=128,BM=512>",
-                                            "conv311_c64<time-tiled, taps share one LDS image>",
-                                            "conv_small<direct-gather MFMA, narrow layers>",
-                                            "conv111<persistent stream, weights in registers>",
-                                            "conv133g<frame-resident halo patch, 9 taps share it>",
-                                            "conv_igemm<BN=256,BM=224>",
-                                            "conv311g<clip-resident (T + 2) x P patch, 3 taps share it>"};
+
+// What there is to know about a variant id, written once.  A conv_igemm tile (bn != 0): its template tuple - BMR < BM: see above -,
+// the LDS ring slots its lean K loop uses and whether its projection-block (DUAL) form is compiled; a specialised path: its name.
+struct Variant { const char* name; int bn, bm, wn, wm, ks, minw, nstage, bmr, ring; bool dual; };
+constexpr Variant variant_info(int v) {
+    switch (v) {
+        case VAR_128x256: return {"conv_igemm<BN=128,BM=256>", 128, 256, 2, 4, 1, 2, 3, 256, 3, true};
+        case VAR_64x256: return {"conv_igemm<BN=64,BM=256>", 64, 256, 1, 8, 1, 2, 3, 256, 3, true};
+        case VAR_128x128: return {"conv_igemm<BN=128,BM=128>", 128, 128, 2, 4, 1, 6, 3, 128, 3, true};
+        case VAR_128x128_R2: return {"conv_igemm<BN=128,BM=128>", 128, 128, 2, 4, 1, 6, 3, 128, 2, true};
+        case VAR_64x128: return {"conv_igemm<BN=64,BM=128>", 64, 128, 1, 8, 1, 4, 3, 128, 3, true};
+        case VAR_256x256: return {"conv_igemm<BN=256,BM=256>", 256, 256, 2, 4, 1, 2, 2, 256, 3, true};
+        case VAR_256x224: return {"conv_igemm<BN=256,BM=224>", 256, 256, 4, 2, 1, 2, 2, 224, 3, true};
+        case VAR_128x512: return {"conv_igemm<BN=128,BM=512>", 128, 512, 2, 4, 1, 2, 2, 512, 3, false};
+        case VAR_C133: return {"conv133_c64<weights in registers>"};
+        case VAR_C311: return {"conv311_c64<time-tiled, taps share one LDS image>"};
+        case VAR_SMALL: return {"conv_small<direct-gather MFMA, narrow layers>"};
+        case VAR_C111: return {"conv111<persistent stream, weights in registers>"};
+        case VAR_C133G: return {"conv133g<frame-resident halo patch, 9 taps share it>"};
+        case VAR_C311G: return {"conv311g<clip-resident (T + 2) x P patch, 3 taps share it>"};
+        default: return {"?"};
+    }
+}
+static int variant_bm(int v) { return variant_info(v).bmr; }   // M-rows of a variant's tile
+static int variant_bn(int v) { return variant_info(v).bn; }
 
 static int pick_variant(int cout, int cin, int taps, int dtype, long long M, int cin2 = 0, int pooled = 0) {
     // AF_FORCE_VAR=<variant id>: tile sweeps of tools/exp_variants.py (experiments only; a tile whose channel count does not
     // divide the layer's is refused)
     if (const char* fv = getenv("AF_FORCE_VAR")) {
         const int v = atoi(fv);
-        const int bn = (v == VAR_256x256 || v == VAR_256x224) ? 256 : (v == VAR_128x256 || v == VAR_128x512 || v == VAR_128x128 || v == VAR_128x128_R2) ? 128 : 64;
-        const bool generic = v == VAR_128x256 || v == VAR_64x256 || v == VAR_128x128 || v == VAR_64x128 || v == VAR_128x128_R2 ||
-                             v == VAR_256x256 || v == VAR_128x512 || v == VAR_256x224;
+        const int bn = variant_bn(v);
+        const bool generic = bn != 0;
         if (generic && cout % bn == 0 && !(pooled && v == VAR_256x224)) return v;
     }
     const int ksteps = (taps * cin + cin2) / (dtype == AF_F32 ? 32 : 64);
@@ -827,11 +827,6 @@ __global__ void splitk_finish_kernel(const float* ws, int ksplit, long long M, i
     Vec4<DT>::store(out + (m * out_ld + c) * ES, v);
 }
 
-// M-rows of a variant's tile
-static int variant_bm(int v) { return v == VAR_128x512 ? 512 : v == VAR_256x224 ? 224 : (v == VAR_128x256 || v == VAR_64x256 || v == VAR_256x256) ? 256 : 128; }
-static int variant_bn(int v) {
-    return (v == VAR_256x256 || v == VAR_256x224) ? 256 : (v == VAR_128x256 || v == VAR_128x512 || v == VAR_128x128 || v == VAR_128x128_R2) ? 128 : 64;
-}
 // split K when the tiles alone leave most CUs idle (one clip, the deep stages): up to 8 K ranges of >= 8 K-steps each whose
 // fp32 partial sums meet in the CALLER's workspace (ksplit * M * Cout floats); 1 = no split
 static int plan_ksplit(int v, long long M, int coutp, int cout, int s_all, int tpool, bool dual) {
@@ -843,54 +838,55 @@ static int plan_ksplit(int v, long long M, int coutp, int cout, int s_all, int t
     return ks >= 2 ? ks : 1;
 }
 
-template <int DT>
-static int dispatch(ConvArgs& a, hipStream_t stream) {
-    constexpr int BK = 8 * Elem<DT>::EPC;
-    a.kpt = (a.Cin + BK - 1) / BK;
-    a.CinP = a.kpt * BK;
-    a.kpt2 = a.in2 ? (a.Cin2 + BK - 1) / BK : 0;
-    a.Cin2P = a.kpt2 * BK;
-    a.CoutP = (a.Cout + 63) / 64 * 64;
-    const int v = pick_variant(a.CoutP, a.CinP, a.kt * a.kh * a.kw, DT, a.M, a.in2 ? a.Cin2P : 0, a.tpool);
-    a.tiles_n = a.CoutP / variant_bn(v);
-    a.ring = v == VAR_128x128_R2 ? 2 : 3;
-    // split K (small batches) only into a workspace the caller handed over and that is large enough
-    a.ksplit = plan_ksplit(v, a.M, a.CoutP, a.Cout, a.kt * a.kh * a.kw * a.kpt + a.kpt2, a.tpool, a.in2 != nullptr);
-    if (a.ksplit > 1 && (!a.ws || a.ws_bytes < (long long)a.ksplit * a.M * a.Cout * (long long)sizeof(float))) a.ksplit = 1;
-    int rc;
-    if (a.in2) {                                 // projection blocks (64-wide tiles: SlowFast's Fast pathway)
-        switch (v) {
-            case VAR_256x256: rc = launch<DT, 256, 256, 2, 4, 1, 2, true, 2>(a, stream); break;
-            case VAR_256x224: rc = launch<DT, 256, 256, 4, 2, 1, 2, true, 2, false, 224>(a, stream); break;
-            case VAR_128x256: rc = launch<DT, 128, 256, 2, 4, 1, 2, true>(a, stream); break;
-            case VAR_64x256: rc = launch<DT, 64, 256, 1, 8, 1, 2, true>(a, stream); break;
-            case VAR_128x128:
-            case VAR_128x128_R2: rc = launch<DT, 128, 128, 2, 4, 1, 6, true>(a, stream); break;
-            default: rc = launch<DT, 64, 128, 1, 8, 1, 4, true>(a, stream); break;
-        }
-    } else if (a.ksplit > 1) {
-        switch (v) {
-            case VAR_256x256: rc = launch<DT, 256, 256, 2, 4, 1, 2, false, 2, true>(a, stream); break;
-            case VAR_256x224: rc = launch<DT, 256, 256, 4, 2, 1, 2, false, 2, true, 224>(a, stream); break;
-            case VAR_128x512: rc = launch<DT, 128, 512, 2, 4, 1, 2, false, 2, true>(a, stream); break;
-            case VAR_128x256: rc = launch<DT, 128, 256, 2, 4, 1, 2, false, 3, true>(a, stream); break;
-            case VAR_64x256: rc = launch<DT, 64, 256, 1, 8, 1, 2, false, 3, true>(a, stream); break;
-            case VAR_128x128:
-            case VAR_128x128_R2: rc = launch<DT, 128, 128, 2, 4, 1, 6, false, 3, true>(a, stream); break;
-            default: rc = launch<DT, 64, 128, 1, 8, 1, 4, false, 3, true>(a, stream); break;
-        }
-    } else {
-        switch (v) {
-            case VAR_256x256: rc = launch<DT, 256, 256, 2, 4, 1, 2, false, 2>(a, stream); break;
-            case VAR_256x224: rc = launch<DT, 256, 256, 4, 2, 1, 2, false, 2, false, 224>(a, stream); break;
-            case VAR_128x512: rc = launch<DT, 128, 512, 2, 4, 1, 2, false, 2>(a, stream); break;
-            case VAR_128x256: rc = launch<DT, 128, 256, 2, 4, 1, 2, false>(a, stream); break;
-            case VAR_64x256: rc = launch<DT, 64, 256, 1, 8, 1, 2, false>(a, stream); break;
-            case VAR_128x128:
-            case VAR_128x128_R2: rc = launch<DT, 128, 128, 2, 4, 1, 6, false>(a, stream); break;
-            default: rc = launch<DT, 64, 128, 1, 8, 1, 4, false>(a, stream); break;
-        }
+// channel counts as the kernel sees them: Cin (and the second segment's) rounded up to the K-step of 64 (fp32: 32) elements
+// - zero-padded weight columns -, Cout to 64 (zero rows); K-steps per tap and in all; output positions
+struct ConvPad { int coutp, cinp, cin2p, kpt, kpt2, taps, ksteps; long long M; };
+static ConvPad conv_pad(const af_conv_desc* d, const af_conv_desc* d2) {
+    const int bk = d->dtype == AF_F32 ? 32 : 64;
+    ConvPad p;
+    p.coutp = (d->cout + 63) / 64 * 64;
+    p.kpt = (d->cin + bk - 1) / bk; p.cinp = p.kpt * bk;
+    p.kpt2 = d2 ? (d2->cin + bk - 1) / bk : 0; p.cin2p = p.kpt2 * bk;
+    p.taps = d->kt * d->kh * d->kw; p.ksteps = p.taps * p.kpt + p.kpt2;
+    p.M = (long long)d->n * d->to * d->ho * d->wo;
+    return p;
+}
+static int pick_variant(const af_conv_desc* d, const ConvPad& p) { return pick_variant(p.coutp, p.cinp, p.taps, d->dtype, p.M, p.cin2p, d->tpool); }
+
+// The path a layer takes, as a VAR_* value; the specialised kernels in their order of precedence, then the generic tile.
+// af_conv_variant reports it (the engine plans from that) and conv_common runs it.
+static int conv_path(const af_conv_desc* d, const af_conv_desc* d2, const void* residual, int out_ld, const ConvPad& p) {
+    if (conv_small_applies(d, d2, residual, out_ld)) return VAR_SMALL;
+    if (!d2 && conv133_applies(d, residual, out_ld)) return VAR_C133;
+    if (!d2 && conv133g_applies(d, residual, out_ld)) return VAR_C133G;
+    if (!d2 && conv311g_applies(d, residual, out_ld)) return VAR_C311G;
+    if (!d2 && conv311_applies(d, residual, out_ld)) return VAR_C311;
+    if (conv111_applies(d, d2, residual, out_ld)) return VAR_C111;
+    return pick_variant(d, p);
+}
+
+// launches tile `v` in one of the three forms of the kernel: plain, DUAL (second K segment) or SPLITK.  An id without a tile of its
+// own in that form (DUAL x 128x512, which pick_variant never chooses for a projection block) runs the 64x128 tile.
+template <int DT, bool DUAL, bool SPLITK, int V = 0>
+static int launch_variant(int v, const ConvArgs& a, hipStream_t stream) {
+    constexpr Variant t = variant_info(V < VAR_COUNT ? V : VAR_64x128);
+    if constexpr (V < VAR_COUNT && (t.bn == 0 || (DUAL && !t.dual))) return launch_variant<DT, DUAL, SPLITK, V + 1>(v, a, stream);
+    else {
+        if constexpr (V < VAR_COUNT) if (v != V) return launch_variant<DT, DUAL, SPLITK, V + 1>(v, a, stream);
+        return launch<DT, t.bn, t.bm, t.wn, t.wm, t.ks, t.minw, DUAL, t.nstage, SPLITK, t.bmr>(a, stream);
     }
+}
+
+template <int DT>
+static int dispatch(ConvArgs& a, const ConvPad& p, int v, hipStream_t stream) {
+    a.kpt = p.kpt; a.CinP = p.cinp; a.kpt2 = p.kpt2; a.Cin2P = p.cin2p; a.CoutP = p.coutp;
+    a.tiles_n = a.CoutP / variant_bn(v);
+    a.ring = variant_info(v).ring;
+    // split K (small batches) only into a workspace the caller handed over and that is large enough
+    a.ksplit = plan_ksplit(v, a.M, a.CoutP, a.Cout, p.ksteps, a.tpool, a.in2 != nullptr);
+    if (a.ksplit > 1 && (!a.ws || a.ws_bytes < (long long)a.ksplit * a.M * a.Cout * (long long)sizeof(float))) a.ksplit = 1;
+    const int rc = a.in2 ? launch_variant<DT, true, false>(v, a, stream)       // (projection blocks: also 64-wide tiles - SlowFast's Fast pathway)
+                   : a.ksplit > 1 ? launch_variant<DT, false, true>(v, a, stream) : launch_variant<DT, false, false>(v, a, stream);
     if (rc != AF_OK || a.ksplit == 1) return rc;
     const long long quads = a.M * (a.Cout / 4);
     hipLaunchKernelGGL((splitk_finish_kernel<DT>), dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, a.ws, a.ksplit, a.M, a.Cout,
@@ -903,30 +899,19 @@ static int dispatch(ConvArgs& a, hipStream_t stream) {
 
 extern "C" int af_conv_variant(const af_conv_desc* d, const af_conv_desc* d2) {
     AF_REQUIRE(d && d->cout > 0 && d->cin > 0 && af::dtype_ok(d->dtype), "conv_variant: bad descriptor");
-    if (af::conv_small_applies(d, d2, nullptr, 0)) return af::VAR_SMALL;
-    if (!d2 && af::conv133_applies(d, nullptr, 0)) return af::VAR_C133;
-    if (!d2 && af::conv133g_applies(d, nullptr, 0)) return af::VAR_C133G;
-    if (!d2 && af::conv311g_applies(d, nullptr, 0)) return af::VAR_C311G;
-    if (!d2 && af::conv311_applies(d, nullptr, 0)) return af::VAR_C311;
-    if (af::conv111_applies(d, d2, nullptr, 0)) return af::VAR_C111;
-    const int bk = d->dtype == AF_F32 ? 32 : 64;
-    return af::pick_variant((d->cout + 63) / 64 * 64, (d->cin + bk - 1) / bk * bk, d->kt * d->kh * d->kw, d->dtype,
-                            (long long)d->n * d->to * d->ho * d->wo, d2 ? (d2->cin + bk - 1) / bk * bk : 0, d->tpool);
+    return af::conv_path(d, d2, nullptr, 0, af::conv_pad(d, d2));
 }
 
 extern "C" const char* af_conv_variant_name(int variant) {
-    return (variant >= 0 && variant < af::VAR_COUNT) ? af::kVariantNames[variant] : "?";
+    return af::variant_info(variant).name;
 }
 
 extern "C" int64_t af_conv_workspace_bytes(const af_conv_desc* d) {
     using namespace af;
     if (!d || d->cout <= 0 || d->cin <= 0 || !dtype_ok(d->dtype) || d->n <= 0 || d->to <= 0 || d->ho <= 0 || d->wo <= 0) return 0;
-    const int bk = d->dtype == AF_F32 ? 32 : 64;
-    const int coutp = (d->cout + 63) / 64 * 64, cinp = (d->cin + bk - 1) / bk * bk, taps = d->kt * d->kh * d->kw;
-    const long long M = (long long)d->n * d->to * d->ho * d->wo;
-    const int v = pick_variant(coutp, cinp, taps, d->dtype, M, 0, d->tpool);
-    const int ks = plan_ksplit(v, M, coutp, d->cout, taps * (cinp / bk), d->tpool, false);
-    return ks > 1 ? (int64_t)ks * M * d->cout * (int64_t)sizeof(float) : 0;
+    const ConvPad p = conv_pad(d, nullptr);
+    const int ks = plan_ksplit(pick_variant(d, p), p.M, p.coutp, d->cout, p.ksteps, d->tpool, false);
+    return ks > 1 ? (int64_t)ks * p.M * d->cout * (int64_t)sizeof(float) : 0;
 }
 
 static int conv_common(const af_conv_desc* d, const void* in, const void* w_packed, const af_conv_desc* d2,
@@ -958,16 +943,15 @@ static int conv_common(const af_conv_desc* d, const void* in, const void* w_pack
     AF_REQUIRE((256 / ((long long)to * ho * wo) + 3) * d->t * d->h * d->w * d->cin * dtype_size(d->dtype) < (1LL << 31),
                "conv: one clip of input is too large for 32-bit tile offsets");
 
-    const bool small = conv_small_applies(d, d2, residual, out_ld);
-    if (!small && !d2 && conv133_applies(d, residual, out_ld))
-        return conv133_run(d, in, w_packed, scale, shift, out, (hipStream_t)stream);
-    if (!small && !d2 && conv133g_applies(d, residual, out_ld))
-        return conv133g_run(d, in, w_packed, scale, shift, out, out_ld, (hipStream_t)stream);
-    if (!small && !d2 && conv311g_applies(d, residual, out_ld))
-        return conv311g_run(d, in, w_packed, scale, shift, out, out_ld, (hipStream_t)stream);
-    if (!small && !d2 && conv311_applies(d, residual, out_ld))
-        return conv311_run(d, in, w_packed, scale, shift, out, out_ld, (hipStream_t)stream);
-
+    const ConvPad p = conv_pad(d, d2);
+    const int path = conv_path(d, d2, residual, out_ld, p);
+    switch (path) {
+        case VAR_C133: return conv133_run(d, in, w_packed, scale, shift, out, (hipStream_t)stream);
+        case VAR_C133G: return conv133g_run(d, in, w_packed, scale, shift, out, out_ld, (hipStream_t)stream);
+        case VAR_C311G: return conv311g_run(d, in, w_packed, scale, shift, out, out_ld, (hipStream_t)stream);
+        case VAR_C311: return conv311_run(d, in, w_packed, scale, shift, out, out_ld, (hipStream_t)stream);
+        default: break;   // the other paths take a second segment or a residual: their checks come first
+    }
     ConvArgs a;
     a.in = (const char*)in; a.w = (const char*)w_packed; a.scale = scale; a.shift = shift;
     a.res = (const char*)residual; a.out = (char*)out;
@@ -1008,16 +992,11 @@ static int conv_common(const af_conv_desc* d, const void* in, const void* w_pack
         a.in2 = (const char*)in2; a.w2 = (const char*)w2_packed;
         a.T2 = d2->t; a.H2 = d2->h; a.W2 = d2->w; a.Cin2 = d2->cin; a.st2 = d2->st; a.sh2 = d2->sh; a.sw2 = d2->sw;
     }
-    if (small)
+    if (path == VAR_SMALL)
         return conv_small_run(d, in, w_packed, d2, in2, w2_packed, scale, shift, residual, out, out_ld, (hipStream_t)stream);
-    if (conv111_applies(d, d2, residual, out_ld))
+    if (path == VAR_C111)
         return conv111_run(d, in, w_packed, d2, in2, w2_packed, scale, shift, residual, out, out_ld, (hipStream_t)stream);
-    hipStream_t s = (hipStream_t)stream;
-    switch (d->dtype) {
-        case AF_F32: return dispatch<AF_F32>(a, s);
-        case AF_BF16: return dispatch<AF_BF16>(a, s);
-        default: return dispatch<AF_F16>(a, s);
-    }
+    return with_dtype(d->dtype, [&](auto dt) { return dispatch<dt>(a, p, path, (hipStream_t)stream); });
 }
 
 extern "C" int af_conv3d_bn_act(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale,

@@ -346,32 +346,34 @@ static int launch111(const C111Args& a, int blocks, hipStream_t stream) {
     return AF_OK;
 }
 
-// positions per tile: 64 for K = 128 / 256 (16- / 32-KB stages, four of them in the ring), 128 for K = 64
-static int conv111_bm(const af_conv_desc* d) { return d->cin >= 128 ? 64 : 128; }
-
-// position tiles of the layer if it takes this path, 0 otherwise
-static long long conv111_tiles(const af_conv_desc* d, const af_conv_desc* d2, int out_ld) {
-    if (d->dtype == AF_F32) return 0;
-    if (d->kt != 1 || d->kh != 1 || d->kw != 1 || d->st != 1 || d->sh != 1 || d->sw != 1 || d->pt || d->ph || d->pw) return 0;
-    if (d->cout % 256 != 0 || (d->tpool != 0 && d->tpool != 1)) return 0;
+// How a layer runs on the persistent stream: position tiles over columns of 256 channels (ok == false: not this path)
+struct Geom111 { bool ok; int ncol, HW, chunks, tiles; long long M; };
+static Geom111 geom111(const af_conv_desc* d, const af_conv_desc* d2) {
+    Geom111 g = {};
+    if (d->dtype == AF_F32) return g;
+    if (d->kt != 1 || d->kh != 1 || d->kw != 1 || d->st != 1 || d->sh != 1 || d->sw != 1 || d->pt || d->ph || d->pw) return g;
+    if (d->cout % 256 != 0 || (d->tpool != 0 && d->tpool != 1)) return g;
     if (d2) {
-        if (d->cin != 64 || d2->cin != 64 || d->tpool) return 0;
-        if (d2->st != 1 || d2->sh != 1 || d2->sw != 1 || d2->t != d->t || d2->h != d->h || d2->w != d->w) return 0;
-    } else if (d->cin != 64 && d->cin != 128 && d->cin != 256) return 0;
-    if (d->tpool && (d->cin != 64 || d->t % 2 != 0)) return 0;
-    const long long hw = (long long)d->h * d->w;
-    if ((hw + 128) * 128 * 2 * 2 >= (1LL << 31)) return 0;                 // 32-bit row offsets inside a tile
-    const int bm = conv111_bm(d);
-    const long long tiles = d->tpool ? (long long)d->n * (d->t / 2) * ((hw + 63) / 64) : ((long long)d->n * d->t * hw + bm - 1) / bm;
-    if (tiles >= (1LL << 30)) return 0;
+        if (d->cin != 64 || d2->cin != 64 || d->tpool) return g;
+        if (d2->st != 1 || d2->sh != 1 || d2->sw != 1 || d2->t != d->t || d2->h != d->h || d2->w != d->w) return g;
+    } else if (d->cin != 64 && d->cin != 128 && d->cin != 256) return g;
+    if (d->tpool && (d->cin != 64 || d->t % 2 != 0)) return g;
+    const long long hw = (long long)d->h * d->w, chunks = (hw + 63) / 64;
+    if ((hw + 128) * 128 * 2 * 2 >= (1LL << 31)) return g;                 // 32-bit row offsets inside a tile
+    // positions per tile: 64 for K = 128 / 256 (16- / 32-KB stages, four of them in the ring), 128 for K = 64
+    const int bm = d->cin >= 128 ? 64 : 128;
+    const long long M = (long long)d->n * d->t * hw;
+    const long long tiles = d->tpool ? (long long)d->n * (d->t / 2) * chunks : (M + bm - 1) / bm;
+    if (tiles >= (1LL << 30)) return g;
     // persistent streams only pay with several tiles per workgroup (one clip of the deep stages stays on the generic path)
-    if (tiles * bm / 128 * (d->cout / 256) < 4LL * device_cus()) return 0;                // (counted in 128-position tiles)
-    return tiles;
+    if (tiles * bm / 128 * (d->cout / 256) < 4LL * device_cus()) return g;                // (counted in 128-position tiles)
+    g.ok = true; g.ncol = d->cout / 256; g.HW = (int)hw; g.chunks = (int)chunks; g.tiles = (int)tiles; g.M = M;
+    return g;
 }
 
 bool conv111_applies(const af_conv_desc* d, const af_conv_desc* d2, const void* residual, int out_ld) {
     if (d2 && residual) return false;
-    return conv111_tiles(d, d2, out_ld) != 0;
+    return geom111(d, d2).ok;
 }
 
 int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, const af_conv_desc* d2, const void* in2,
@@ -381,35 +383,29 @@ int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, con
     a.in = (const char*)in; a.in2 = (const char*)in2; a.w = (const char*)w_packed; a.w2 = (const char*)w2_packed;
     a.scale = scale; a.shift = shift; a.res = (const char*)residual; a.out = (char*)out;
     a.Cin = d->cin; a.Cin2 = d2 ? d2->cin : 0; a.Cout = d->cout; a.out_ld = out_ld; a.relu = d->relu;
-    a.ncol = d->cout / 256;
-    a.T = d->t; a.HW = d->h * d->w; a.chunks = (a.HW + 63) / 64;
-    a.M = (long long)d->n * d->t * a.HW;
-    a.tiles = (int)conv111_tiles(d, d2, out_ld);
+    const Geom111 g = geom111(d, d2);
+    a.ncol = g.ncol; a.T = d->t; a.HW = g.HW; a.chunks = g.chunks; a.M = g.M; a.tiles = g.tiles;
     int streams = device_cus() / a.ncol;
     if (streams > a.tiles) streams = a.tiles;
     const int blocks = streams * a.ncol;
-    const bool bf = d->dtype == AF_BF16;
-#define AF_C111(K1, K2, TP, RS) (bf ? launch111<AF_BF16, K1, K2, TP, RS>(a, blocks, stream) : launch111<AF_F16, K1, K2, TP, RS>(a, blocks, stream))
-    if (d2) return AF_C111(1, 1, false, false);
-    if (d->tpool) return residual ? AF_C111(1, 0, true, true) : AF_C111(1, 0, true, false);
-    if (d->cin == 64) return residual ? AF_C111(1, 0, false, true) : AF_C111(1, 0, false, false);
-    // K = 256 (s4 `c`).  Round 4, late: 64-channel wave columns - 128-byte row segments for the residual rows and the output instead of
-    // 64 - with a TWO-slot ring.  128 weight registers next to the three residual sets of the 4-slot ring spilled 11 registers (and a
-    // scratch reload's vmcnt(0) is poison in this loop), which is why rounds 2-4 ran this layer on 32-channel columns; with ONE residual
-    // set (one tile ahead) it is 242 registers, and one tile of look-ahead on full lines beats three tiles of it on half lines:
-    // 58.6 -> 49.9 us (tools/exp_c111_wc64.py, interleaved on one box).  AF_C111_WC64=0: the 32-channel form, for A/B runs.
-    // (A three-slot ring with the BN parameters moved to LDS - 256 registers, no spills - measured the same as two slots: 49.0 us.)
-    if (d->cin == 256) {
-        if (env_int("AF_C111_WC64", 1) != 0)
-            return residual ? (bf ? launch111<AF_BF16, 4, 0, false, true, 64, 64, 2>(a, blocks, stream) : launch111<AF_F16, 4, 0, false, true, 64, 64, 2>(a, blocks, stream))
-                            : (bf ? launch111<AF_BF16, 4, 0, false, false, 64, 64, 2>(a, blocks, stream) : launch111<AF_F16, 4, 0, false, false, 64, 64, 2>(a, blocks, stream));
-        return residual ? (bf ? launch111<AF_BF16, 4, 0, false, true, 32, 64, 4>(a, blocks, stream) : launch111<AF_F16, 4, 0, false, true, 32, 64, 4>(a, blocks, stream))
-                        : (bf ? launch111<AF_BF16, 4, 0, false, false, 32, 64, 4>(a, blocks, stream) : launch111<AF_F16, 4, 0, false, false, 32, 64, 4>(a, blocks, stream));
-    }
-    // K = 128: tiles of 64 positions as well (16-KB stages), three tiles ahead
-    return residual ? (bf ? launch111<AF_BF16, 2, 0, false, true, 64, 64, 4>(a, blocks, stream) : launch111<AF_F16, 2, 0, false, true, 64, 64, 4>(a, blocks, stream))
-                    : (bf ? launch111<AF_BF16, 2, 0, false, false, 64, 64, 4>(a, blocks, stream) : launch111<AF_F16, 2, 0, false, false, 64, 64, 4>(a, blocks, stream));
-#undef AF_C111
+    return with_dtype16(d->dtype, [&](auto dt) {
+        if (d2) return launch111<dt, 1, 1, false, false>(a, blocks, stream);
+        if (d->tpool) return residual ? launch111<dt, 1, 0, true, true>(a, blocks, stream) : launch111<dt, 1, 0, true, false>(a, blocks, stream);
+        if (d->cin == 64) return residual ? launch111<dt, 1, 0, false, true>(a, blocks, stream) : launch111<dt, 1, 0, false, false>(a, blocks, stream);
+        // K = 256 (s4 `c`).  Round 4, late: 64-channel wave columns - 128-byte row segments for the residual rows and the output instead of
+        // 64 - with a TWO-slot ring.  128 weight registers next to the three residual sets of the 4-slot ring spilled 11 registers (and a
+        // scratch reload's vmcnt(0) is poison in this loop), which is why rounds 2-4 ran this layer on 32-channel columns; with ONE residual
+        // set (one tile ahead) it is 242 registers, and one tile of look-ahead on full lines beats three tiles of it on half lines:
+        // 58.6 -> 49.9 us (tools/exp_c111_wc64.py, interleaved on one box).  AF_C111_WC64=0: the 32-channel form, for A/B runs.
+        // (A three-slot ring with the BN parameters moved to LDS - 256 registers, no spills - measured the same as two slots: 49.0 us.)
+        if (d->cin == 256) {
+            if (env_int("AF_C111_WC64", 1) != 0)
+                return residual ? launch111<dt, 4, 0, false, true, 64, 64, 2>(a, blocks, stream) : launch111<dt, 4, 0, false, false, 64, 64, 2>(a, blocks, stream);
+            return residual ? launch111<dt, 4, 0, false, true, 32, 64, 4>(a, blocks, stream) : launch111<dt, 4, 0, false, false, 32, 64, 4>(a, blocks, stream);
+        }
+        // K = 128: tiles of 64 positions as well (16-KB stages), three tiles ahead
+        return residual ? launch111<dt, 2, 0, false, true, 64, 64, 4>(a, blocks, stream) : launch111<dt, 2, 0, false, false, 64, 64, 4>(a, blocks, stream);
+    });
 }
 
 }  // namespace af

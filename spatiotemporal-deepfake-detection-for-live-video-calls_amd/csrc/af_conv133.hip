@@ -425,23 +425,34 @@ __global__ __launch_bounds__(512, 2) void conv133_c64x2_kernel(const C133Args a)
 // the MFMA phase of the two waves of a SIMD is MFMA-bound while both multiply (5.0-5.4 k cycles per strip for 288 MFMAs), the older
 // wave of the two wins the issue arbitration and the younger one starves until it is alone, and alone a wave with one tap-step of
 // LDS look-ahead runs at ~25 cycles per MFMA - so putting one wave's epilogue under the other's MFMAs buys what the lone stretches lose.
+// How a layer runs on this path: strips of kStripRows rows of a frame at the padded pitch W + 2 (ok == false: not this path)
+constexpr int kStripRows = 4;
+struct Geom133 { bool ok; int strips_per_frame, total_strips, rows_alloc, lds; };
+static Geom133 geom133(const af_conv_desc* d) {
+    Geom133 g = {};
+    const int positions = kStripRows * (d->w + 2);           // of the 256 every workgroup multiplies
+    if (d->dtype == AF_F32 || d->cin != 64 || d->cout != 64 || d->kt != 1 || d->kh != 3 || d->kw != 3 || d->st != 1 || d->sh != 1 ||
+        d->sw != 1 || d->pt != 0 || d->ph != 1 || d->pw != 1 || !d->relu || d->tpool || positions > 256) return g;
+    // narrow frames (SlowFast's Fast pathway in s5: 7 x 7) would run at 14 % and took 2.4x the generic kernel's time
+    if (positions < 112) return g;
+    g.ok = true; g.strips_per_frame = (d->h + kStripRows - 1) / kStripRows;
+    g.total_strips = d->n * d->t * g.strips_per_frame;
+    g.rows_alloc = (((kStripRows + 2) * (d->w + 2) + 2 + 16) + 7) & ~7;
+    g.lds = 2 * g.rows_alloc * 128 + 16 * 16 * 128 + 128 * 4 + 2 * 512 * 16 + (g.rows_alloc / 8) * 64 * 4;   // (+ the last two taps' fragments: 8-wave form)
+    return g;
+}
+
 template <int DT>
-static int launch_c133(C133Args& a, hipStream_t stream) {
-    constexpr int R = 4;
+static int launch_c133(const C133Args& a, int lds, hipStream_t stream) {
     const int g_num_cus = device_cus();
-    const int WP = a.W + 2;
-    a.strips_per_frame = (a.H + R - 1) / R;
-    a.total_strips = a.frames * a.strips_per_frame;
-    a.rows_alloc = (((R + 2) * WP + 2 + 16) + 7) & ~7;
-    const int lds = 2 * a.rows_alloc * 128 + 16 * 16 * 128 + 128 * 4 + 2 * 512 * 16 + (a.rows_alloc / 8) * 64 * 4;   // (+ the last two taps' fragments: 8-wave form)
     const int grid = a.total_strips < g_num_cus ? a.total_strips : g_num_cus;
     // AF_C64_WAVES=4: the round-1 / 2 form (one wave per SIMD, all 64 channels per wave) for A/B runs
     if (env_int("AF_C64_WAVES", 8) == 4) {
-        AF_SET_MAX_LDS((&conv133_c64_kernel<DT, R>), 160 * 1024, "conv133");
-        hipLaunchKernelGGL((conv133_c64_kernel<DT, R>), dim3(grid), dim3(256), lds, stream, a);
+        AF_SET_MAX_LDS((&conv133_c64_kernel<DT, kStripRows>), kLdsBudget, "conv133");
+        hipLaunchKernelGGL((conv133_c64_kernel<DT, kStripRows>), dim3(grid), dim3(256), lds, stream, a);
     } else {
-        AF_SET_MAX_LDS((&conv133_c64x2_kernel<DT, R>), 160 * 1024, "conv133");
-        hipLaunchKernelGGL((conv133_c64x2_kernel<DT, R>), dim3(grid), dim3(512), lds, stream, a);
+        AF_SET_MAX_LDS((&conv133_c64x2_kernel<DT, kStripRows>), kLdsBudget, "conv133");
+        hipLaunchKernelGGL((conv133_c64x2_kernel<DT, kStripRows>), dim3(grid), dim3(512), lds, stream, a);
     }
     AF_CHECK_LAUNCH("conv133_c64_kernel");
     return AF_OK;
@@ -449,21 +460,18 @@ static int launch_c133(C133Args& a, hipStream_t stream) {
 
 // true iff this layer takes the register-resident-weights path (also used by af_conv_variant)
 bool conv133_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    return d->dtype != AF_F32 && d->cin == 64 && d->cout == 64 && d->kt == 1 && d->kh == 3 && d->kw == 3 &&
-           d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->ph == 1 && d->pw == 1 && d->relu && !d->tpool &&
-           residual == nullptr && (out_ld == 0 || out_ld == 64) && 4 * (d->w + 2) <= 256 &&
-           // a strip is 4 x (W + 2) positions of the 256 every workgroup multiplies: narrow frames (SlowFast's Fast pathway in
-           // s5: 7 x 7) would run at 14 % and took 2.4x the generic kernel's time
-           4 * (d->w + 2) >= 112;
+    return residual == nullptr && (out_ld == 0 || out_ld == 64) && geom133(d).ok;
 }
 
 int conv133_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
                 void* out, hipStream_t stream) {
     C133Args a;
     a.in = (const char*)in; a.w = (const char*)w_packed; a.scale = scale; a.shift = shift; a.out = (char*)out;
+    const Geom133 g = geom133(d);
     a.H = d->h; a.W = d->w; a.frames = d->n * d->t;
+    a.strips_per_frame = g.strips_per_frame; a.total_strips = g.total_strips; a.rows_alloc = g.rows_alloc;
     fill_stamps(a, "AF_C64_DBG");
-    return d->dtype == AF_BF16 ? launch_c133<AF_BF16>(a, stream) : launch_c133<AF_F16>(a, stream);
+    return with_dtype16(d->dtype, [&](auto dt) { return launch_c133<dt>(a, g.lds, stream); });
 }
 
 }  // namespace af

@@ -23,21 +23,6 @@
 
 namespace af {
 
-// Diagnostic build (-DAF_STAMPS, tools/stamps_lib.sh; never the shipped library): shader-clock stamps around the phases of a
-// unit, kept in scalar registers and written behind the last output store, to a buffer nothing else reads.
-#ifdef AF_STAMPS
-#define AF_STAMP_DECL unsigned long long stamp_v[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define AF_DBG(bit) (a.dbg & (bit))
-#define AF_STAMP(slot) stamp_v[slot] = (slot) >= 6 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime()
-#define AF_STAMP_FLUSH do { if (a.stamps && lane < 8) a.stamps[((long long)blockIdx.x * 8 + wave) * 8 + lane] = \
-    lane == 0 ? stamp_v[0] : lane == 1 ? stamp_v[1] : lane == 2 ? stamp_v[2] : lane == 3 ? stamp_v[3] : lane == 4 ? stamp_v[4] : lane == 5 ? stamp_v[5] : lane == 6 ? stamp_v[6] : stamp_v[7]; } while (0)
-#else
-#define AF_STAMP_DECL do {} while (0)
-#define AF_DBG(bit) false
-#define AF_STAMP(slot) do {} while (0)
-#define AF_STAMP_FLUSH do {} while (0)
-#endif
-
 struct C133GArgs {
     const char* in;
     const char* w;       // packed [Cout][9][Cin]
@@ -453,7 +438,7 @@ __global__ __launch_bounds__(512, 2) void conv133g_kernel(const C133GArgs a) {
         }
         if (epi_more) continue;
         AF_STAMP(3); AF_STAMP(7);
-        AF_STAMP_FLUSH;
+        AF_STAMP_FLUSH(blockIdx.x);
         return;
     }
     }                                                  // (unit loop; the fused `c` instantiations leave it behind their one unit's K loop)
@@ -556,16 +541,31 @@ __global__ __launch_bounds__(512, 2) void conv133g_kernel(const C133GArgs a) {
     }
 }
 
+// LDS rows of a patch buffer: `lines` lines (spatial: band rows at pitch W + 1, + 1 zero column behind the last; temporal: frames at pitch P) + 2 halo lines
+static int patch_rows(int lines, int pitch, int tail) { return ((lines + 2) * pitch + tail + 7) & ~7; }
+// two patch buffers + the weight ring + the patch-row offset table (128 channels)
+static int lds133g_bytes(int prows, int cout, int slots) { return 2 * prows * 128 + slots * cout * 128 + (cout == 128 ? prows * 4 : 0); }
+
+// How a layer runs on conv133g_kernel (spatial: geom133g, temporal: geom311g); ok == false: it does not take the path
+constexpr int kPieceRows = 64, kMaxPieces = 9;   // patch rows one DMA piece of a wave brings; pieces per wave of the largest instantiation
+struct Geom133g {
+    bool ok;
+    int frames, kt;      // frames (temporal: clips) the units are cut from; the kernel's temporal taps (temporal: 1 - its three taps are the kernel's own)
+    int R, upf, WP, prows;   // output rows (temporal: pixels) per unit, units per frame (clip); pitch of a patch line: W + 1 (temporal: R); LDS rows per patch buffer
+    int maxp;            // patch DMA pieces per wave of the instantiation that runs it (its MAXP: prows <= kPieceRows * maxp)
+    int slots;           // weight ring slots: 3 where the two patches leave room for them (s4: 2 x 31 KB + 3 x 32 KB), else 2
+};
+
 template <int DT, int WN, int WM, bool FUSEC, int MT, int MAXP, int NSLOT, bool TEMPORAL = false>
 static int launch133g_n(const C133GArgs& a, hipStream_t stream) {
-    if (a.prows > 64 * MAXP) return set_error(AF_ERR_ARG, "conv133g: %d patch rows for %d pieces per wave", a.prows, MAXP);
-    int lds = 2 * a.prows * 128 + NSLOT * WN * 64 * 128 + (WN == 2 ? a.prows * 4 : 0);      // patches, ring, the patch-row offset table (128 channels)
+    if (a.prows > kPieceRows * MAXP) return set_error(AF_ERR_ARG, "conv133g: %d patch rows for %d pieces per wave", a.prows, MAXP);
+    int lds = lds133g_bytes(a.prows, WN * 64, NSLOT);
     const int lds_c = WN * (WM * MT * 16) * 128 + 8 * 16 * (64 + 4) * 4;      // T + the per-wave fp32 staging rows
     if (FUSEC && lds_c > lds) lds = lds_c;
     const int lds_e = 8 * 16 * (64 + 8) * 2;                                   // the epilogue's per-wave patches
     if (lds < lds_e) lds = lds_e;
-    if (lds > 160 * 1024) return set_error(AF_ERR_ARG, "conv133g: %d bytes of LDS needed", lds);
-    AF_SET_MAX_LDS((&conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), 160 * 1024, "conv133g");
+    if (lds > kLdsBudget) return set_error(AF_ERR_ARG, "conv133g: %d bytes of LDS needed", lds);
+    AF_SET_MAX_LDS((&conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), kLdsBudget, "conv133g");
     // persistent workgroups (one per CU: the kernel uses all of LDS): unit blockIdx.x, + gridDim.x, ...
     const int units = a.frames * a.upf, cus = device_cus();
     static const int persist = env_int("AF_G_PERSIST", 1);   // 0: one unit per workgroup (A/B runs)
@@ -575,104 +575,101 @@ static int launch133g_n(const C133GArgs& a, hipStream_t stream) {
     return AF_OK;
 }
 
-// three ring slots (two K-steps of weights in flight) where the two patch buffers leave room for them (s4: 2 x 31 KB + 3 x 32 KB)
-template <int DT, int WN, int WM, bool FUSEC, int MT = 7, int MAXP = 9>
-static int launch133g(const C133GArgs& a, hipStream_t stream) {
-    if (!FUSEC && 2 * a.prows * 128 + 3 * WN * 64 * 128 + (WN == 2 ? a.prows * 4 : 0) <= 160 * 1024) return launch133g_n<DT, WN, WM, FUSEC, MT, MAXP, FUSEC ? 2 : 3>(a, stream);
-    return launch133g_n<DT, WN, WM, FUSEC, MT, MAXP, 2>(a, stream);
+// the ring depth of the geometry (the fused form has two slots only)
+template <int DT, int WN, int WM, bool FUSEC, int MT, int MAXP, bool TEMPORAL = false>
+static int launch133g(const C133GArgs& a, const Geom133g& g, hipStream_t stream) {
+    if constexpr (!FUSEC) if (g.slots == 3) return launch133g_n<DT, WN, WM, FUSEC, MT, MAXP, 3, TEMPORAL>(a, stream);
+    return launch133g_n<DT, WN, WM, FUSEC, MT, MAXP, 2, TEMPORAL>(a, stream);
 }
 
-// rows of a frame one unit covers (0: the layer does not take this path)
-static int conv133g_rows(const af_conv_desc* d) {
-    if (d->dtype == AF_F32 || d->tpool) return 0;
-    if ((d->kt != 1 && d->kt != 3) || d->kh != 3 || d->kw != 3 || d->st != 1 || d->sh != 1 || d->sw != 1) return 0;
-    if (d->pt != d->kt / 2 || d->ph != 1 || d->pw != 1) return 0;
+// ---- spatial mode: bands of R rows of a frame
+static Geom133g geom133g(const af_conv_desc* d, bool fused = false) {
+    Geom133g g = {};
+    if (d->dtype == AF_F32 || d->tpool) return g;
+    if ((d->kt != 1 && d->kt != 3) || d->kh != 3 || d->kw != 3 || d->st != 1 || d->sh != 1 || d->sw != 1) return g;
+    if (d->pt != d->kt / 2 || d->ph != 1 || d->pw != 1) return g;
     // 64 output channels only for the 3x3x3 case (the 1x3x3 64 -> 64 layers of s2 keep their weights-in-registers kernel)
-    if (d->cin % 64 != 0 || (d->cout != 128 && d->cout != 256 && !(d->cout == 64 && d->kt == 3))) return 0;
+    if (d->cin % 64 != 0 || (d->cout != 128 && d->cout != 256 && !(d->cout == 64 && d->kt == 3))) return g;
     const int mpad = d->cout == 256 ? 224 : d->cout == 128 ? 448 : 512;   // positions of a unit: WM x MT m-tiles
     const int wp = d->w + 1;
     int r = mpad / wp;
     if (r > d->h) r = d->h;
-    auto patch_rows = [&](int rows) { return ((rows + 2) * wp + 1 + 7) & ~7; };
-    const int tab = d->cout == 128 ? 4 : 0;                   // bytes per patch row of the offset table (128 channels)
-    while (r >= 7 && (patch_rows(r) > 576 || 2 * patch_rows(r) * 128 + 2 * d->cout * 128 + patch_rows(r) * tab > 160 * 1024)) --r;   // two patches + the ring (+ the table)
-    if (r < 7) return 0;                                       // bands of >= 7 rows: the halo rows stay <= 2/7 of the patch
+    // at most 9 pieces per wave; two patches + the ring (+ the table)
+    while (r >= 7 && (patch_rows(r, wp, 1) > kPieceRows * kMaxPieces || lds133g_bytes(patch_rows(r, wp, 1), d->cout, 2) > kLdsBudget)) --r;
+    if (r < 7) return g;                                       // bands of >= 7 rows: the halo rows stay <= 2/7 of the patch
     int upf = (d->h + r - 1) / r;
     r = (d->h + upf - 1) / upf;                                // even bands
     upf = (d->h + r - 1) / r;
     // worth it when the units fill the chip and most of a unit's positions are real
     const long long units = (long long)d->n * d->t * upf;
-    if (units < 192 || units > 0x7fffffffLL) return 0;
-    if ((double)d->h * d->w / ((double)upf * mpad) < 0.6) return 0;
-    if ((long long)(d->h + 2) * d->w * d->cin * 2 * (d->kt + 1) >= (1LL << 31)) return 0;
-    return r;
+    if (units < 192 || units > 0x7fffffffLL) return g;
+    if ((double)d->h * d->w / ((double)upf * mpad) < 0.6) return g;
+    if ((long long)(d->h + 2) * d->w * d->cin * 2 * (d->kt + 1) >= (1LL << 31)) return g;
+    g.ok = true; g.frames = d->n * d->t; g.kt = d->kt; g.R = r; g.upf = upf; g.WP = wp; g.prows = patch_rows(r, wp, 1);
+    // pieces per wave: 256 channels: <= 224 + 2 WP + 1 <= 296 patch rows (5); 128 channels: the s3 band of 472 rows takes 8
+    // (the fused form has the 9-piece instantiation only)
+    g.maxp = d->cout == 256 ? 5 : (d->cout == 128 && !fused && g.prows <= 8 * kPieceRows) ? 8 : kMaxPieces;
+    g.slots = lds133g_bytes(g.prows, d->cout, 3) <= kLdsBudget ? 3 : 2;
+    return g;
 }
 
 bool conv133g_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    return !residual && (out_ld == 0 || out_ld % 8 == 0) && conv133g_rows(d) != 0;
+    return !residual && (out_ld == 0 || out_ld % 8 == 0) && geom133g(d).ok;
 }
 
-static void fill133g(C133GArgs& a, const af_conv_desc* d, const void* in, const void* w_packed, const float* scale,
-                     const float* shift) {
+// ---- TEMPORAL mode: 3x1x1 / stride 1 / pad (1,0,0) convs into 128 / 256 channels (the `a` convs of s3 / s4) on the same kernel.
+// P = pixels per unit so that T x P is the kernel's position count (224 for 256 channels, 448 for 128)
+static Geom133g geom311g(const af_conv_desc* d) {
+    Geom133g g = {};
+    if (d->dtype == AF_F32 || d->tpool) return g;
+    if (d->kt != 3 || d->kh != 1 || d->kw != 1 || d->st != 1 || d->sh != 1 || d->sw != 1) return g;
+    if (d->pt != 1 || d->ph != 0 || d->pw != 0) return g;
+    if (d->cin % 64 != 0 || (d->cout != 128 && d->cout != 256)) return g;
+    const int mpad = d->cout == 256 ? 224 : 448;
+    if (d->t < 4 || mpad % d->t != 0) return g;
+    const int P = mpad / d->t;
+    const int prows = patch_rows(d->t, P, 0);
+    const int maxp = d->cout == 256 ? 5 : kMaxPieces;                            // the 256- / 128-channel instantiation
+    if (P < 7 || prows > kPieceRows * maxp || lds133g_bytes(prows, d->cout, 2) > kLdsBudget) return g;
+    const long long hw = (long long)d->h * d->w, chunks = (hw + P - 1) / P, units = (long long)d->n * chunks;
+    if (units < 192 || units > 0x7fffffffLL) return g;
+    if ((double)hw / ((double)chunks * P) < 0.6) return g;                       // most positions of a unit are real
+    if ((long long)(d->t + 2) * hw * d->cin * 2 >= (1LL << 31)) return g;          // 32-bit offsets inside a clip (+ the halo frames)
+    g.ok = true; g.frames = d->n; g.kt = 1; g.R = P; g.upf = (int)chunks; g.WP = P; g.prows = prows; g.maxp = maxp;
+    g.slots = lds133g_bytes(prows, d->cout, 3) <= kLdsBudget ? 3 : 2;      // 256 channels, P = 14: 2 x 32 KB + 3 x 32 KB = all of LDS
+    return g;
+}
+
+bool conv311g_applies(const af_conv_desc* d, const void* residual, int out_ld) {
+    static const int enabled = env_int("AF_T311G", 1);
+    return enabled && !residual && (out_ld == 0 || out_ld % 8 == 0) && geom311g(d).ok;
+}
+
+// the kernel's arguments for layer `d` cut into units as `g` says, without a fused c conv
+static void fill133g(C133GArgs& a, const Geom133g& g, const af_conv_desc* d, const void* in, const void* w_packed, const float* scale,
+                     const float* shift, void* out, int out_ld) {
     a.in = (const char*)in; a.w = (const char*)w_packed; a.scale = scale; a.shift = shift;
-    a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Cout = d->cout; a.frames = d->n * d->t;
-    a.T = d->t; a.kt = d->kt;
-    a.R = conv133g_rows(d); a.upf = (d->h + a.R - 1) / a.R; a.WP = d->w + 1;
-    a.prows = ((a.R + 2) * a.WP + 1 + 7) & ~7;
+    a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Cout = d->cout; a.frames = g.frames;
+    a.T = d->t; a.kt = g.kt;
+    a.R = g.R; a.upf = g.upf; a.WP = g.WP; a.prows = g.prows;
     a.kslabs = d->cin / 64; a.relu = d->relu;
     a.inv_wp = 1.0f / (float)a.WP;
     a.w2 = nullptr; a.scale2 = a.shift2 = nullptr; a.res = nullptr; a.Cout2 = 0; a.relu2 = 0;
     a.stagger = env_int("AF_G_STAGGER", 1);
     fill_stamps(a, "AF_G_DBG");
-}
-
-// ---- TEMPORAL mode: 3x1x1 / stride 1 / pad (1,0,0) convs into 128 / 256 channels (the `a` convs of s3 / s4) on the same kernel.
-// P = pixels per unit so that T x P is the kernel's position count (224 for 256 channels, 448 for 128); 0: not this path.
-static int conv311g_pixels(const af_conv_desc* d) {
-    if (d->dtype == AF_F32 || d->tpool) return 0;
-    if (d->kt != 3 || d->kh != 1 || d->kw != 1 || d->st != 1 || d->sh != 1 || d->sw != 1) return 0;
-    if (d->pt != 1 || d->ph != 0 || d->pw != 0) return 0;
-    if (d->cin % 64 != 0 || (d->cout != 128 && d->cout != 256)) return 0;
-    const int mpad = d->cout == 256 ? 224 : 448;
-    if (d->t < 4 || mpad % d->t != 0) return 0;
-    const int P = mpad / d->t;
-    const int prows = ((d->t + 2) * P + 7) & ~7;
-    // (patch rows: 64 per DMA piece of a wave - 5 pieces in the 256-channel instantiation, 9 in the 128-channel one)
-    if (P < 7 || prows > (d->cout == 256 ? 320 : 576) || 2 * prows * 128 + 2 * d->cout * 128 + (d->cout == 128 ? prows * 4 : 0) > 160 * 1024) return 0;
-    const long long hw = (long long)d->h * d->w, chunks = (hw + P - 1) / P, units = (long long)d->n * chunks;
-    if (units < 192 || units > 0x7fffffffLL) return 0;
-    if ((double)hw / ((double)chunks * P) < 0.6) return 0;                       // most positions of a unit are real
-    if ((long long)(d->t + 2) * hw * d->cin * 2 >= (1LL << 31)) return 0;          // 32-bit offsets inside a clip (+ the halo frames)
-    return P;
-}
-
-bool conv311g_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    static const int enabled = env_int("AF_T311G", 1);
-    return enabled && !residual && (out_ld == 0 || out_ld % 8 == 0) && conv311g_pixels(d) != 0;
+    a.out = (char*)out; a.out_ld = out_ld;
 }
 
 int conv311g_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
                  void* out, int out_ld, hipStream_t stream) {
+    const Geom133g g = geom311g(d);
     C133GArgs a;
-    a.in = (const char*)in; a.w = (const char*)w_packed; a.scale = scale; a.shift = shift;
-    a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Cout = d->cout; a.frames = d->n;   // a "frame" of the unit decomposition is a clip
-    a.T = d->t; a.kt = 1;                                                         // (the temporal taps are the kernel's taps)
-    a.R = conv311g_pixels(d); a.upf = (d->h * d->w + a.R - 1) / a.R; a.WP = a.R;
-    a.prows = ((d->t + 2) * a.R + 7) & ~7;
-    a.kslabs = d->cin / 64; a.relu = d->relu;
-    a.inv_wp = 1.0f / (float)a.R;
-    a.w2 = nullptr; a.scale2 = a.shift2 = nullptr; a.res = nullptr; a.Cout2 = 0; a.relu2 = 0;
-    a.stagger = env_int("AF_G_STAGGER", 1);
-    fill_stamps(a, "AF_G_DBG");
-    a.out = (char*)out; a.out_ld = out_ld ? out_ld : d->cout;
-    const bool three = 2 * a.prows * 128 + 3 * d->cout * 128 + (d->cout == 128 ? a.prows * 4 : 0) <= 160 * 1024;     // 256 channels, P = 14: 2 x 32 KB + 3 x 32 KB = all of LDS
-    if (d->cout == 256) {
-        if (a.prows > 64 * 5) return set_error(AF_ERR_ARG, "conv311g: %d patch rows", a.prows);
-        if (three) return d->dtype == AF_BF16 ? launch133g_n<AF_BF16, 4, 2, false, 7, 5, 3, true>(a, stream) : launch133g_n<AF_F16, 4, 2, false, 7, 5, 3, true>(a, stream);
-        return d->dtype == AF_BF16 ? launch133g_n<AF_BF16, 4, 2, false, 7, 5, 2, true>(a, stream) : launch133g_n<AF_F16, 4, 2, false, 7, 5, 2, true>(a, stream);
-    }
-    if (three) return d->dtype == AF_BF16 ? launch133g_n<AF_BF16, 2, 4, false, 7, 9, 3, true>(a, stream) : launch133g_n<AF_F16, 2, 4, false, 7, 9, 3, true>(a, stream);
-    return d->dtype == AF_BF16 ? launch133g_n<AF_BF16, 2, 4, false, 7, 9, 2, true>(a, stream) : launch133g_n<AF_F16, 2, 4, false, 7, 9, 2, true>(a, stream);
+    fill133g(a, g, d, in, w_packed, scale, shift, out, out_ld ? out_ld : d->cout);
+    return with_dtype16(d->dtype, [&](auto dt) {
+        if (d->cout == 256 && a.prows > kPieceRows * g.maxp) return set_error(AF_ERR_ARG, "conv311g: %d patch rows", a.prows);
+        if (d->cout == 256) return launch133g<dt, 4, 2, false, 7, 5, true>(a, g, stream);
+        return launch133g<dt, 2, 4, false, 7, 9, true>(a, g, stream);
+    });
 }
 
 // b (1x3x3) + c (1x1x1, + residual, + ReLU) of a bottleneck as one launch: true iff `db` takes the frame-resident path and
@@ -689,24 +686,27 @@ bool conv133g_fused_applies(const af_conv_desc* db, const af_conv_desc* dc, int 
 int conv133g_fused_run(const af_conv_desc* db, const void* in, const void* wb, const float* scale_b, const float* shift_b,
                        const af_conv_desc* dc, const void* wc, const float* scale_c, const float* shift_c, const void* residual,
                        void* out, int out_ld, hipStream_t stream) {
+    const Geom133g g = geom133g(db, true);
     C133GArgs a;
-    fill133g(a, db, in, wb, scale_b, shift_b);
-    a.out = (char*)out; a.out_ld = out_ld ? out_ld : dc->cout;
+    fill133g(a, g, db, in, wb, scale_b, shift_b, out, out_ld ? out_ld : dc->cout);
     a.w2 = (const char*)wc; a.scale2 = scale_c; a.shift2 = shift_c; a.res = (const char*)residual; a.Cout2 = dc->cout; a.relu2 = dc->relu;
-    if (db->cout == 256) return db->dtype == AF_BF16 ? launch133g<AF_BF16, 4, 2, true, 7, 5>(a, stream) : launch133g<AF_F16, 4, 2, true, 7, 5>(a, stream);
-    return db->dtype == AF_BF16 ? launch133g<AF_BF16, 2, 4, true>(a, stream) : launch133g<AF_F16, 2, 4, true>(a, stream);
+    return with_dtype16(db->dtype, [&](auto dt) {
+        if (db->cout == 256) return launch133g<dt, 4, 2, true, 7, 5>(a, g, stream);
+        return launch133g<dt, 2, 4, true, 7, 9>(a, g, stream);
+    });
 }
 
 int conv133g_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
                  void* out, int out_ld, hipStream_t stream) {
+    const Geom133g g = geom133g(d);
     C133GArgs a;
-    fill133g(a, d, in, w_packed, scale, shift);
-    a.out = (char*)out; a.out_ld = out_ld ? out_ld : d->cout;
-    if (d->cout == 256) return d->dtype == AF_BF16 ? launch133g<AF_BF16, 4, 2, false, 7, 5>(a, stream) : launch133g<AF_F16, 4, 2, false, 7, 5>(a, stream);
-    if (d->cout == 64) return d->dtype == AF_BF16 ? launch133g<AF_BF16, 1, 8, false, 4>(a, stream) : launch133g<AF_F16, 1, 8, false, 4>(a, stream);
-    // pieces per wave: 256 channels: <= 224 + 2 WP + 1 <= 296 patch rows (5); 128 channels: the s3 band of 472 rows takes 8
-    if (a.prows <= 512) return d->dtype == AF_BF16 ? launch133g<AF_BF16, 2, 4, false, 7, 8>(a, stream) : launch133g<AF_F16, 2, 4, false, 7, 8>(a, stream);
-    return d->dtype == AF_BF16 ? launch133g<AF_BF16, 2, 4, false>(a, stream) : launch133g<AF_F16, 2, 4, false>(a, stream);
+    fill133g(a, g, d, in, w_packed, scale, shift, out, out_ld ? out_ld : d->cout);
+    return with_dtype16(d->dtype, [&](auto dt) {
+        if (d->cout == 256) return launch133g<dt, 4, 2, false, 7, 5>(a, g, stream);
+        if (d->cout == 64) return launch133g<dt, 1, 8, false, 4, 9>(a, g, stream);
+        if (g.maxp == 8) return launch133g<dt, 2, 4, false, 7, 8>(a, g, stream);
+        return launch133g<dt, 2, 4, false, 7, 9>(a, g, stream);
+    });
 }
 
 }  // namespace af

@@ -173,49 +173,49 @@ template <int DT, int BN>
 static int launch311(const C311Args& a, int blocks, hipStream_t stream) {
     constexpr int BM = 256 / (BN / 64), EPC = Elem<DT>::EPC;
     const int lds = 2 * (3 * BN + BM + 2 * a.P) * 128 + 8 * 16 * (64 + EPC) * (16 / EPC);
-    AF_SET_MAX_LDS((&conv311_kernel<DT, BN>), 160 * 1024, "conv311");
+    AF_SET_MAX_LDS((&conv311_kernel<DT, BN>), kLdsBudget, "conv311");
     hipLaunchKernelGGL((conv311_kernel<DT, BN>), dim3(blocks), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("conv311_kernel");
     return AF_OK;
 }
 
-// tile height for a layer, 0 if the layer does not take the time-tiled path
-static int conv311_tile_rows(const af_conv_desc* d) {
-    if (d->tpool) return 0;
-    if (d->kt != 3 || d->kh != 1 || d->kw != 1 || d->st != 1 || d->sh != 1 || d->sw != 1) return 0;
-    if (d->pt != 1 || d->ph != 0 || d->pw != 0) return 0;
+// How a layer runs on the time-tiled path: tiles of all T frames x P pixels (ok == false: it does not take the path)
+struct Geom311 { bool ok; int P, chunks, tiles, kpt; };
+static Geom311 geom311(const af_conv_desc* d) {
+    Geom311 g = {};
+    if (d->tpool) return g;
+    if (d->kt != 3 || d->kh != 1 || d->kw != 1 || d->st != 1 || d->sh != 1 || d->sw != 1) return g;
+    if (d->pt != 1 || d->ph != 0 || d->pw != 0) return g;
     const int bke = d->dtype == AF_F32 ? 32 : 64;
-    if (d->cin % bke != 0) return 0;
+    if (d->cin % bke != 0) return g;
     int bm = 0;
     if (d->cout == 64 && (d->t == 16 || d->t == 32)) bm = 256;                        // P = 16 or 8
     else if (d->cout == 128 && d->t == 16 && d->dtype != AF_F32) bm = 128;            // P = 8 (fp32: ring + patch exceed LDS)
-    if (!bm) return 0;
-    if ((long long)d->t * d->h * d->w * d->cin * dtype_size(d->dtype) >= (1LL << 31)) return 0;
-    const int p = bm / d->t;
-    if ((long long)d->n * ((d->h * d->w + p - 1) / p) >= (1LL << 31)) return 0;
-    return bm;
+    if (!bm) return g;
+    if ((long long)d->t * d->h * d->w * d->cin * dtype_size(d->dtype) >= (1LL << 31)) return g;
+    const int p = bm / d->t, chunks = (d->h * d->w + p - 1) / p;
+    if ((long long)d->n * chunks >= (1LL << 31)) return g;
+    g.ok = true; g.P = p; g.chunks = chunks; g.tiles = d->n * chunks; g.kpt = d->cin / bke;
+    return g;
 }
 
 // true iff this layer takes the time-tiled path (also used by af_conv_variant)
 bool conv311_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    return !residual && conv311_tile_rows(d) != 0;
+    return !residual && geom311(d).ok;
 }
 
 int conv311_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
                 void* out, int out_ld, hipStream_t stream) {
     C311Args a;
     a.in = (const char*)in; a.w = (const char*)w_packed; a.scale = scale; a.shift = shift; a.out = (char*)out;
-    a.T = d->t; a.HW = d->h * d->w; a.Cin = d->cin; a.kpt = d->cin / (d->dtype == AF_F32 ? 32 : 64);
-    a.P = conv311_tile_rows(d) / d->t; a.chunks = (a.HW + a.P - 1) / a.P; a.tiles = d->n * a.chunks;
+    const Geom311 g = geom311(d);
+    a.T = d->t; a.HW = d->h * d->w; a.Cin = d->cin; a.kpt = g.kpt;
+    a.P = g.P; a.chunks = g.chunks; a.tiles = g.tiles;
     a.relu = d->relu; a.out_ld = out_ld;
     const int cus = device_cus();                        // persistent grid: one workgroup per CU
     const int blocks = a.tiles < cus ? a.tiles : cus;
-    if (d->cout == 128) return d->dtype == AF_BF16 ? launch311<AF_BF16, 128>(a, blocks, stream) : launch311<AF_F16, 128>(a, blocks, stream);
-    switch (d->dtype) {
-        case AF_F32: return launch311<AF_F32, 64>(a, blocks, stream);
-        case AF_BF16: return launch311<AF_BF16, 64>(a, blocks, stream);
-        default: return launch311<AF_F16, 64>(a, blocks, stream);
-    }
+    if (d->cout == 128) return with_dtype16(d->dtype, [&](auto dt) { return launch311<dt, 128>(a, blocks, stream); });
+    return with_dtype(d->dtype, [&](auto dt) { return launch311<dt, 64>(a, blocks, stream); });
 }
 
 }  // namespace af

@@ -402,11 +402,34 @@ static long long conv_ca_lds_bytes(bool dual, int P, int C, bool cwl = false) {
 template <int DT, bool DUAL, bool CWL>
 static int launch_ca(const CAArgs& a, int blocks, hipStream_t stream) {
     const int lds = (int)conv_ca_lds_bytes(DUAL, a.P, a.C, CWL);
-    if (lds > 160 * 1024) return set_error(AF_ERR_ARG, "conv_ca: %d bytes of LDS needed", lds);
-    AF_SET_MAX_LDS((&conv_ca_kernel<DT, DUAL, CWL>), 160 * 1024, "conv_ca");
+    if (lds > kLdsBudget) return set_error(AF_ERR_ARG, "conv_ca: %d bytes of LDS needed", lds);
+    AF_SET_MAX_LDS((&conv_ca_kernel<DT, DUAL, CWL>), kLdsBudget, "conv_ca");
     hipLaunchKernelGGL((conv_ca_kernel<DT, DUAL, CWL>), dim3(blocks), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("conv_ca_kernel");
     return AF_OK;
+}
+
+// How the pair runs: tiles of all T frames x P pixels (ok == false: not on this path).  `dual`: with the projection shortcut
+struct GeomCA { bool ok; int P, chunks, tiles; bool cwl; };
+static GeomCA geom_ca(const af_conv_desc* dc, bool dual) {
+    GeomCA g = {};
+    if (dc->t != 16 && dc->t != 32) return g;                         // tile = all T frames x 256 / T pixels
+    const long long hw = (long long)dc->h * dc->w;
+    if ((long long)dc->t * hw * dc->cout * 2 >= (1LL << 31)) return g;     // 32-bit offsets inside a clip
+    const int p = 256 / dc->t;
+    // the launch must fit LDS (wide trunks: the plain form with T = 16 and C >= 512, the projection form with C >= 512 do not):
+    // such a pair keeps its two launches instead of failing in launch_ca
+    if (conv_ca_lds_bytes(dual, p, dc->cout) > kLdsBudget) return g;
+    // whole tiles only: the kernel's counted s_waitcnt vmcnt assume that every wave issues every store of an iteration; a
+    // ragged last chunk could mask ALL lanes of a wave's store, hipcc would branch around it and the count would be off
+    if (hw % p != 0) return g;
+    const long long tiles = (long long)dc->n * (hw / p);
+    // persistent stream: pays with several tiles per workgroup (small batches keep the two launches)
+    if (tiles < 4LL * device_cus() || tiles >= (1LL << 31)) return g;
+    g.ok = true; g.P = p; g.chunks = (int)(hw / p); g.tiles = (int)tiles;
+    // the stage's c weights as an LDS image where its 8 KB fit (T = 32 with a 256-channel trunk)
+    g.cwl = !dual && conv_ca_lds_bytes(false, p, dc->cout, true) <= kLdsBudget;
+    return g;
 }
 
 // dc: the 1x1x1 `c` conv (64 -> C, with residual + ReLU), da: the 3x1x1 `a` conv of the next block (C -> 64) over its output
@@ -422,19 +445,7 @@ bool conv_ca_applies(const af_conv_desc* dc, const af_conv_desc* d1, const af_co
     if (da->kt != 3 || da->kh != 1 || da->kw != 1 || da->st != 1 || da->sh != 1 || da->sw != 1 || da->pt != 1 || da->ph || da->pw) return false;
     if (dc->cin != 64 || da->cout != 64 || dc->cout != da->cin || dc->cout % 64 != 0 || dc->cout > 1024 || !dc->relu || !da->relu) return false;
     if (dc->n != da->n || dc->t != da->t || dc->h != da->h || dc->w != da->w) return false;
-    if (dc->t != 16 && dc->t != 32) return false;                     // tile = all T frames x 256 / T pixels
-    const long long hw = (long long)dc->h * dc->w;
-    if ((long long)dc->t * hw * dc->cout * 2 >= (1LL << 31)) return false;     // 32-bit offsets inside a clip
-    const int p = 256 / dc->t;
-    // the launch must fit LDS (wide trunks: the plain form with T = 16 and C >= 512, the projection form with C >= 512 do not):
-    // such a pair keeps its two launches instead of failing in launch_ca
-    if (conv_ca_lds_bytes(d1 != nullptr, p, dc->cout) > 160 * 1024) return false;
-    // whole tiles only: the kernel's counted s_waitcnt vmcnt assume that every wave issues every store of an iteration; a
-    // ragged last chunk could mask ALL lanes of a wave's store, hipcc would branch around it and the count would be off
-    if (hw % p != 0) return false;
-    const long long tiles = (long long)dc->n * (hw / p);
-    // persistent stream: pays with several tiles per workgroup (small batches keep the two launches)
-    return tiles >= 4LL * device_cus() && tiles < (1LL << 31);
+    return geom_ca(dc, d1 != nullptr).ok;
 }
 
 int conv_ca_run(const af_conv_desc* dc, const void* inb, const void* wc, const void* in1, const void* w1, const float* scale_c,
@@ -445,17 +456,17 @@ int conv_ca_run(const af_conv_desc* dc, const void* inb, const void* wc, const v
     a.in1 = (const char*)in1; a.w1 = (const char*)w1;
     a.outx = (char*)outx; a.wa = (const char*)wa; a.scale_a = scale_a; a.shift_a = shift_a; a.outa = (char*)outa;
     a.T = dc->t; a.HW = dc->h * dc->w; a.C = dc->cout; a.kslabs = dc->cout / 64;
-    a.P = 256 / dc->t; a.chunks = (a.HW + a.P - 1) / a.P; a.tiles = dc->n * a.chunks;
+    const GeomCA g = geom_ca(dc, in1 != nullptr);
+    a.P = g.P; a.chunks = g.chunks; a.tiles = g.tiles;
 #ifdef AF_STAMPS
     a.dbg = env_int("AF_CA_DBG", 0);
 #endif
     const int cus = device_cus();
     const int blocks = a.tiles < cus ? a.tiles : cus;
-    if (in1) return dc->dtype == AF_BF16 ? launch_ca<AF_BF16, true, false>(a, blocks, stream) : launch_ca<AF_F16, true, false>(a, blocks, stream);
-    // the stage's c weights as an LDS image where its 8 KB fit (T = 32 with a 256-channel trunk; AF_CA_CWL=0: the fragment loads, for A/B runs)
-    if (conv_ca_lds_bytes(false, a.P, a.C, true) <= 160 * 1024 && env_int("AF_CA_CWL", 1) != 0)
-        return dc->dtype == AF_BF16 ? launch_ca<AF_BF16, false, true>(a, blocks, stream) : launch_ca<AF_F16, false, true>(a, blocks, stream);
-    return dc->dtype == AF_BF16 ? launch_ca<AF_BF16, false, false>(a, blocks, stream) : launch_ca<AF_F16, false, false>(a, blocks, stream);
+    if (in1) return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, true, false>(a, blocks, stream); });
+    if (g.cwl && env_int("AF_CA_CWL", 1) != 0)                           // (AF_CA_CWL=0: the fragment loads, for A/B runs)
+        return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, false, true>(a, blocks, stream); });
+    return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, false, false>(a, blocks, stream); });
 }
 
 }  // namespace af

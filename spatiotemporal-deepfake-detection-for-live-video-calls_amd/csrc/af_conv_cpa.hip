@@ -344,11 +344,24 @@ __global__ __launch_bounds__(512) void conv_cpa_kernel(const CPAArgs a) {
 template <int DT>
 static int launch_cpa(const CPAArgs& a, int blocks, hipStream_t stream) {
     const int lds = (int)conv_cpa_lds_bytes(a.C);
-    if (lds > 160 * 1024) return set_error(AF_ERR_ARG, "conv_cpa: %d bytes of LDS needed", lds);
-    AF_SET_MAX_LDS((&conv_cpa_kernel<DT>), 160 * 1024, "conv_cpa");
+    if (lds > kLdsBudget) return set_error(AF_ERR_ARG, "conv_cpa: %d bytes of LDS needed", lds);
+    AF_SET_MAX_LDS((&conv_cpa_kernel<DT>), kLdsBudget, "conv_cpa");
     hipLaunchKernelGGL((conv_cpa_kernel<DT>), dim3(blocks), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("conv_cpa_kernel");
     return AF_OK;
+}
+
+// How the pair runs: tiles of 2 rows x 4 columns of a clip, all frames (ok == false: not on this path)
+struct GeomCPA { bool ok; int wq, per_clip, tiles; };
+static GeomCPA geom_cpa(const af_conv_desc* dc) {
+    GeomCPA g = {};
+    if (dc->h % 2 != 0 || dc->w % 4 != 0) return g;                   // tile = 2 rows x 4 columns
+    if ((long long)dc->t * dc->h * dc->w * dc->cout * 2 >= (1LL << 31)) return g;     // 32-bit offsets inside a clip
+    if (conv_cpa_lds_bytes(dc->cout) > kLdsBudget) return g;
+    const long long tiles = (long long)dc->n * (dc->h / 2) * (dc->w / 4);
+    if (tiles < 4LL * device_cus() || tiles >= (1LL << 31)) return g;   // persistent stream: several tiles per workgroup
+    g.ok = true; g.wq = dc->w / 4; g.per_clip = (dc->h / 2) * g.wq; g.tiles = (int)tiles;
+    return g;
 }
 
 // dc: the 1x1x1 `c` conv (64 -> C, residual + ReLU) with the temporal pool behind it (tpool = 1);
@@ -361,11 +374,7 @@ bool conv_cpa_applies(const af_conv_desc* dc, const af_conv_desc* da, int x_sub)
     if (dc->cin != 64 || da->cout != 128 || dc->cout != da->cin || dc->cout % 64 != 0 || !dc->relu || !da->relu) return false;
     if (dc->t != 32 || da->t != 16 || dc->n != da->n || dc->h != da->h || dc->w != da->w) return false;
     if (dc->to != dc->t || dc->ho != dc->h || dc->wo != dc->w || da->to != da->t || da->ho != da->h || da->wo != da->w) return false;
-    if (dc->h % 2 != 0 || dc->w % 4 != 0) return false;               // tile = 2 rows x 4 columns
-    if ((long long)dc->t * dc->h * dc->w * dc->cout * 2 >= (1LL << 31)) return false;     // 32-bit offsets inside a clip
-    if (conv_cpa_lds_bytes(dc->cout) > 160 * 1024) return false;
-    const long long tiles = (long long)dc->n * (dc->h / 2) * (dc->w / 4);
-    return tiles >= 4LL * device_cus() && tiles < (1LL << 31);       // persistent stream: several tiles per workgroup
+    return geom_cpa(dc).ok;
 }
 
 int conv_cpa_run(const af_conv_desc* dc, const void* inb, const void* wc, const float* scale_c, const float* shift_c,
@@ -375,11 +384,12 @@ int conv_cpa_run(const af_conv_desc* dc, const void* inb, const void* wc, const 
     a.inb = (const char*)inb; a.wc = (const char*)wc; a.scale_c = scale_c; a.shift_c = shift_c; a.res = (const char*)residual;
     a.outx = (char*)outx; a.wa = (const char*)wa; a.scale_a = scale_a; a.shift_a = shift_a; a.outa = (char*)outa;
     a.T = dc->t; a.H = dc->h; a.W = dc->w; a.C = dc->cout; a.kslabs = dc->cout / 64;
-    a.wq = dc->w / 4; a.per_clip = (dc->h / 2) * a.wq; a.tiles = dc->n * a.per_clip;
+    const GeomCPA g = geom_cpa(dc);
+    a.wq = g.wq; a.per_clip = g.per_clip; a.tiles = g.tiles;
     a.sub = x_sub == 2;
     const int cus = device_cus();
     const int blocks = a.tiles < cus ? a.tiles : cus;
-    return dc->dtype == AF_BF16 ? launch_cpa<AF_BF16>(a, blocks, stream) : launch_cpa<AF_F16>(a, blocks, stream);
+    return with_dtype16(dc->dtype, [&](auto dt) { return launch_cpa<dt>(a, blocks, stream); });
 }
 
 }  // namespace af

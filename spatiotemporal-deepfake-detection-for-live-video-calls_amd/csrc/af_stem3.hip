@@ -413,8 +413,8 @@ extern "C" int af_stem_conv_bn_relu_maxpool_rgb3_ld(const af_conv_desc* d, const
     a.in += (long long)(AF_STEM_PAD_T - d->pt) * a.Hp * a.row_bytes;
     hipStream_t s = (hipStream_t)stream;
     switch (d->kt) {
-        case 1: return d->dtype == AF_BF16 ? launch_stem3_kt<AF_BF16, 1>(a, s) : launch_stem3_kt<AF_F16, 1>(a, s);
-        case 3: return d->dtype == AF_BF16 ? launch_stem3_kt<AF_BF16, 3>(a, s) : launch_stem3_kt<AF_F16, 3>(a, s);
-        default: return d->dtype == AF_BF16 ? launch_stem3_kt<AF_BF16, 5>(a, s) : launch_stem3_kt<AF_F16, 5>(a, s);
+        case 1: return with_dtype16(d->dtype, [&](auto dt) { return launch_stem3_kt<dt, 1>(a, s); });
+        case 3: return with_dtype16(d->dtype, [&](auto dt) { return launch_stem3_kt<dt, 3>(a, s); });
+        default: return with_dtype16(d->dtype, [&](auto dt) { return launch_stem3_kt<dt, 5>(a, s); });
     }
 }

@@ -223,5 +223,5 @@ extern "C" int af_stem_conv_bn_relu_maxpool(const af_conv_desc* d, const void* s
     }
     a.in += (long long)(AF_STEM_PAD_T - d->pt) * a.Hp * a.Wp * 4 * dtype_size(d->dtype);
     hipStream_t s = (hipStream_t)stream;
-    return d->dtype == AF_BF16 ? launch_stem_pool<AF_BF16>(a, s) : launch_stem_pool<AF_F16>(a, s);
+    return with_dtype16(d->dtype, [&](auto dt) { return launch_stem_pool<dt>(a, s); });
 }

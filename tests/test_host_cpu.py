@@ -594,3 +594,19 @@ def test_plans_need_no_device_and_keep_their_launch_kinds(monkeypatch):
                                "AF_FUSE_TSTEM_POOL": True, "AF_SLOWFAST_STEM3": True}
     monkeypatch.setenv("AF_FUSE_CPA", "1")           # read when the plan is built
     assert [e["kind"] for e in plan("i3d").entries] == _kinds(PLAN_KINDS_I3D_CPA)
+
+
+def test_conv_paths_and_fusion_answers_equal_the_recorded_ones():
+    """for every conv of the three networks (f32 / bf16 / f16, batch 1 / 8 / 16) af_conv_variant gives the recorded id, the id has the
+    recorded name and af_conv_workspace_bytes the recorded size; the engine's bc / ca / cpa / abc fusion questions get the recorded
+    answers in the recorded order (fixture: tests/golden/conv_paths.json, written by tools/gen_conv_paths_golden.py)"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_conv_paths_golden", os.path.join(ROOT, "tools", "gen_conv_paths_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want, got = load_json("conv_paths.json"), gen.collect()
+    assert sorted(got) == sorted(want) and len(want) == 3 * 3 * 3
+    for key in sorted(want):
+        assert got[key]["convs"] == want[key]["convs"], key
+        assert got[key]["fusable"] == want[key]["fusable"], key
+        assert len(want[key]["convs"]) >= 40 and len(want[key]["fusable"]) >= 10, key
