@@ -410,6 +410,38 @@ int af_window_batch_plan_u8(const af_window_desc* windows, const af_align_frame*
                             int64_t pool_bytes, void* table, int64_t table_bytes, int32_t* bad_window, int32_t* bad_frame);
 int af_warp_affine_windows_u8(const void* pool, const void* table, int n_windows, int clip_size, int size, void* out, void* stream);
 
+/* The window-batch warp out of RESIDENT FRAMES: the same launch, but every (window, frame) reads its crop as a sub-rectangle of a
+ * decoded frame that already sits in a caller-owned device frame store (the frames a detector has just read), so no crop is cut,
+ * staged or uploaded.  Same arithmetic and the same bytes as af_warp_affine_windows_u8 on crops cut from those frames.
+ *   store: n_frames frames of height x width RGB pixels (3 packed bytes), frame i at byte i * frame_stride, rows row_pitch bytes
+ *     apart (any value >= 3 * width, no alignment asked: 1 923 for a 641-wide frame); store_bytes: the readable bytes of the buffer.
+ *   rects[w * clip_size + t]: the frame's index in the store, the rectangle's top-left pixel (rx, ry) and size (ih, iw) in that
+ *     frame, and its paste position (x, y) on window w's canvas.
+ * af_window_rects_plan_u8 (host only) fills the table (af_window_rects_table_bytes bytes, 8-byte aligned) and refuses with
+ * AF_ERR_ARG: a rectangle that does not fit its window's canvas (*bad_window / *bad_frame set, as af_window_batch_plan_u8 does); a
+ * rectangle that leaves its frame or names a frame outside the store; a rectangle whose last pixel is followed by fewer than 3
+ * readable bytes.  Inside a frame those bytes are the frame's next pixels, so this only asks for 3 bytes of slack behind the last
+ * frame of the store.  The kernel reads tap pairs as 6 bytes from an address clamped into the rectangle and gives a tap outside the
+ * rectangle weight 0: the pixels next to a rectangle never reach the result.
+ * The launch trusts the table as af_warp_affine_windows_u8 does, compares the header (a table of the pool form is a mismatch too)
+ * and writes nothing on a mismatch.  (Added within ABI 6, like the pool form.) */
+typedef struct af_frame_store {
+    int64_t store_bytes;
+    int64_t frame_stride, row_pitch;
+    int32_t n_frames, height, width, reserved;
+} af_frame_store;
+typedef struct af_frame_rect {
+    int32_t frame;
+    int32_t rx, ry;
+    int32_t ih, iw;
+    int32_t x, y;
+    int32_t reserved;
+} af_frame_rect;
+int64_t af_window_rects_table_bytes(int n_windows, int clip_size);
+int af_window_rects_plan_u8(const af_window_desc* windows, const af_frame_rect* rects, int n_windows, int clip_size, int size,
+                            const af_frame_store* store, void* table, int64_t table_bytes, int32_t* bad_window, int32_t* bad_frame);
+int af_warp_affine_window_rects_u8(const void* store, const void* table, int n_windows, int clip_size, int size, void* out, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,

@@ -2,3 +2,11 @@
 Mariachiar/Spatiotemporal-Deepfake-Detection-for-Live-Video-Calls, rebuilt as hand-written
 HIP (gfx950) behind the reference's classifier-plugin surface.  See DESIGN.md."""
 from . import arch, synth  # noqa: F401
+
+
+def __getattr__(name):
+    # the evaluator's classes by their short names; loaded on first use, so importing the package stays light
+    if name in ("VideoScorer", "TrackScorer"):
+        from . import evaluator
+        return getattr(evaluator, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -44,6 +44,15 @@ class WindowDesc(C.Structure):
 WINDOW_MAX_BATCH, WINDOW_MAX_SIZE, WINDOW_TABLE_HEADER = 64, 1024, 16
 
 
+class FrameStore(C.Structure):
+    _fields_ = [("store_bytes", C.c_int64), ("frame_stride", C.c_int64), ("row_pitch", C.c_int64), ("n_frames", C.c_int32),
+                ("height", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FrameRect(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("frame", "rx", "ry", "ih", "iw", "x", "y", "reserved")]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n", "t", "h", "w", "c", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw", "to", "ho", "wo", "dtype",
@@ -141,6 +150,10 @@ ABI = {
     "af_window_batch_plan_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64,
                                           C.c_void_p, C.c_void_p]),
     "af_warp_affine_windows_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "af_window_rects_table_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "af_window_rects_plan_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FrameStore), C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p]),
+    "af_warp_affine_window_rects_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6

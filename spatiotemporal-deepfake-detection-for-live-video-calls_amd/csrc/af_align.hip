@@ -92,24 +92,39 @@ static void invert_affine_cv(const double* tfm, double* inv) {
 // tabulated in LDS once per block, as OpenCV tabulates them; a thread makes four consecutive pixels and stores them as one
 // 12-byte store; the two taps of a source row are read as 6 contiguous bytes (a dword and a half-word load, unaligned) from a
 // clamped address, and a tap outside the crop gets weight 0 instead of a branch.
+// Two forms of one kernel body, told apart by the work item's type.  af_align_frame: a tightly packed crop in a pool (row pitch
+// iw * 3).  WindowRect: a sub-rectangle of a frame that is resident in a device frame store, with the frame's own row pitch in
+// bytes (any value: 1 923 for a 641-wide frame; the 6-byte tap reads are unaligned in both forms).  The bytes around a rectangle
+// are the frame's other pixels, not padding: only the clamp of (row, column) into the rectangle together with the zero weight of
+// a tap outside it keeps them out of the result, and only the last rectangle of the store needs 3 readable bytes behind it.
 constexpr int WB_ROWS = 32, WB_THREADS = 256;
-struct WindowTableHeader { int32_t n_windows, clip_size, size, reserved; };
+constexpr int32_t WB_KIND_POOL = 0, WB_KIND_RECTS = 1;           // WindowTableHeader::kind
+struct WindowTableHeader { int32_t n_windows, clip_size, size, kind; };
 struct WindowXform { double m[6]; };                             // dst -> src map (already inverted)
+struct WindowRect { int64_t offset; int32_t ih, iw, x, y, pitch, reserved; };    // offset: the rectangle's first pixel in the store
 
-static inline int64_t window_table_bytes(int n_windows, int clip_size) {
-    return (int64_t)sizeof(WindowTableHeader) + (int64_t)n_windows * sizeof(WindowXform) + (int64_t)n_windows * clip_size * sizeof(af_align_frame);
+// byte of pixel (row, col) of the work item's image, the one expression in which the two forms differ
+__device__ __forceinline__ long long wb_byte(const af_align_frame& f, int row, int col) { return ((long long)row * f.iw + col) * 3; }
+__device__ __forceinline__ long long wb_byte(const WindowRect& f, int row, int col) { return (long long)row * f.pitch + col * 3; }
+template <typename Item> struct WbKind;
+template <> struct WbKind<af_align_frame> { static constexpr int32_t value = WB_KIND_POOL; };
+template <> struct WbKind<WindowRect> { static constexpr int32_t value = WB_KIND_RECTS; };
+
+static inline int64_t window_table_bytes(int n_windows, int clip_size, size_t item = sizeof(af_align_frame)) {
+    return (int64_t)sizeof(WindowTableHeader) + (int64_t)n_windows * sizeof(WindowXform) + (int64_t)n_windows * clip_size * (int64_t)item;
 }
 
+template <typename Item>
 __global__ __launch_bounds__(WB_THREADS) void warp_affine_windows_kernel(const unsigned char* __restrict__ pool, const unsigned char* __restrict__ table,
                                                                          unsigned char* __restrict__ out, int n_windows, int clip_size, int size,
                                                                          int tiles) {
     __shared__ int s_ad[AF_WINDOW_MAX_SIZE], s_bd[AF_WINDOW_MAX_SIZE], s_x0[WB_ROWS], s_y0[WB_ROWS];
     const WindowTableHeader hd = *(const WindowTableHeader*)table;
-    if (hd.n_windows != n_windows || hd.clip_size != clip_size || hd.size != size) return;   // not this launch's table
+    if (hd.n_windows != n_windows || hd.clip_size != clip_size || hd.size != size || hd.kind != WbKind<Item>::value) return;   // not this launch's table
     const int bid = blockIdx.x;                                   // work item k = window * clip_size + frame, window-major
     const int k = bid / tiles, tile = bid - k * tiles, y0 = tile * WB_ROWS;
     const WindowXform* xf = (const WindowXform*)(table + sizeof(WindowTableHeader));
-    const af_align_frame f = ((const af_align_frame*)(xf + n_windows))[k];
+    const Item f = ((const Item*)(xf + n_windows))[k];
     const int window = k / clip_size;
     const double m0 = xf[window].m[0], m1 = xf[window].m[1], m2 = xf[window].m[2];
     const double m3 = xf[window].m[3], m4 = xf[window].m[4], m5 = xf[window].m[5];
@@ -148,8 +163,8 @@ __global__ __launch_bounds__(WB_THREADS) void warp_affine_windows_kernel(const u
             const int col = ix < 0 ? 0 : ix > f.iw - 1 ? f.iw - 1 : ix;
             const int ra = iy < 0 ? 0 : iy > f.ih - 1 ? f.ih - 1 : iy;
             const int rb = iy + 1 < 0 ? 0 : iy + 1 > f.ih - 1 ? f.ih - 1 : iy + 1;
-            const unsigned char* pa = img + ((long long)ra * f.iw + col) * 3;
-            const unsigned char* pb = img + ((long long)rb * f.iw + col) * 3;
+            const unsigned char* pa = img + wb_byte(f, ra, col);
+            const unsigned char* pb = img + wb_byte(f, rb, col);
             unsigned a4, b4; unsigned short a2, b2;
             __builtin_memcpy(&a4, pa, 4); __builtin_memcpy(&a2, pa + 4, 2);
             __builtin_memcpy(&b4, pb, 4); __builtin_memcpy(&b2, pb + 4, 2);
@@ -210,24 +225,94 @@ extern "C" int af_window_batch_plan_u8(const af_window_desc* windows, const af_a
             out[w * clip_size + t] = f;
         }
     }
-    hd->n_windows = n_windows; hd->clip_size = clip_size; hd->size = size; hd->reserved = 0;
+    hd->n_windows = n_windows; hd->clip_size = clip_size; hd->size = size; hd->kind = WB_KIND_POOL;
     return AF_OK;
 }
 
-extern "C" int af_warp_affine_windows_u8(const void* pool, const void* table, int n_windows, int clip_size, int size, void* out,
-                                         void* stream) {
-    using namespace af;
-    AF_REQUIRE(pool && table && out, "warp_affine_windows: null argument");
+namespace af {
+template <typename Item>
+static int launch_window_warp(const char* what, const void* src, const void* table, int n_windows, int clip_size, int size, void* out, void* stream) {
+    AF_REQUIRE(src && table && out, "%s: null argument", what);
     AF_REQUIRE(n_windows > 0 && n_windows <= AF_WINDOW_MAX_BATCH && clip_size > 0 && clip_size <= AF_ALIGN_MAX_FRAMES,
-               "warp_affine_windows: %d windows of %d frames (at most %d of %d)", n_windows, clip_size, AF_WINDOW_MAX_BATCH, AF_ALIGN_MAX_FRAMES);
-    AF_REQUIRE(size > 0 && size <= AF_WINDOW_MAX_SIZE && size % 4 == 0, "warp_affine_windows: size %d (a multiple of 4, at most %d)", size, AF_WINDOW_MAX_SIZE);
-    AF_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)table & 7) == 0, "warp_affine_windows: out must be 4-byte, table 8-byte aligned");
+               "%s: %d windows of %d frames (at most %d of %d)", what, n_windows, clip_size, AF_WINDOW_MAX_BATCH, AF_ALIGN_MAX_FRAMES);
+    AF_REQUIRE(size > 0 && size <= AF_WINDOW_MAX_SIZE && size % 4 == 0, "%s: size %d (a multiple of 4, at most %d)", what, size, AF_WINDOW_MAX_SIZE);
+    AF_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)table & 7) == 0, "%s: out must be 4-byte, table 8-byte aligned", what);
     const int tiles = (size + WB_ROWS - 1) / WB_ROWS;
     const unsigned grid = (unsigned)(n_windows * clip_size * tiles);
-    hipLaunchKernelGGL(warp_affine_windows_kernel, dim3(grid), dim3(WB_THREADS), 0, (hipStream_t)stream, (const unsigned char*)pool,
+    hipLaunchKernelGGL(warp_affine_windows_kernel<Item>, dim3(grid), dim3(WB_THREADS), 0, (hipStream_t)stream, (const unsigned char*)src,
                        (const unsigned char*)table, (unsigned char*)out, n_windows, clip_size, size, tiles);
     AF_CHECK_LAUNCH("warp_affine_windows_kernel");
     return AF_OK;
+}
+}  // namespace af
+
+extern "C" int af_warp_affine_windows_u8(const void* pool, const void* table, int n_windows, int clip_size, int size, void* out,
+                                         void* stream) {
+    return af::launch_window_warp<af_align_frame>("warp_affine_windows", pool, table, n_windows, clip_size, size, out, stream);
+}
+
+// ---- the same launch out of frames that are resident on the device (af_hip.h: af_frame_store / af_frame_rect) ----
+extern "C" int64_t af_window_rects_table_bytes(int n_windows, int clip_size) {
+    if (n_windows <= 0 || n_windows > AF_WINDOW_MAX_BATCH || clip_size <= 0 || clip_size > AF_ALIGN_MAX_FRAMES) return 0;
+    return af::window_table_bytes(n_windows, clip_size, sizeof(af::WindowRect));
+}
+
+extern "C" int af_window_rects_plan_u8(const af_window_desc* windows, const af_frame_rect* rects, int n_windows, int clip_size, int size,
+                                       const af_frame_store* store, void* table, int64_t table_bytes, int32_t* bad_window, int32_t* bad_frame) {
+    using namespace af;
+    if (bad_window) *bad_window = -1;
+    if (bad_frame) *bad_frame = -1;
+    AF_REQUIRE(windows && rects && store && table, "window_rects_plan: null argument");
+    AF_REQUIRE(n_windows > 0 && n_windows <= AF_WINDOW_MAX_BATCH && clip_size > 0 && clip_size <= AF_ALIGN_MAX_FRAMES,
+               "window_rects_plan: %d windows of %d frames (at most %d of %d)", n_windows, clip_size, AF_WINDOW_MAX_BATCH, AF_ALIGN_MAX_FRAMES);
+    AF_REQUIRE(size > 0 && size <= AF_WINDOW_MAX_SIZE && size % 4 == 0, "window_rects_plan: size %d (a multiple of 4, at most %d)", size, AF_WINDOW_MAX_SIZE);
+    const int64_t need = window_table_bytes(n_windows, clip_size, sizeof(WindowRect));
+    AF_REQUIRE(table_bytes >= need, "window_rects_plan: table of %lld bytes, %lld needed", (long long)table_bytes, (long long)need);
+    const af_frame_store& s = *store;
+    AF_REQUIRE(s.n_frames > 0 && s.height > 0 && s.width > 0 && s.height <= 32767 && s.width <= 32767, "window_rects_plan: store of %d frames %dx%d",
+               s.n_frames, s.width, s.height);
+    const int64_t frame_span = (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3;      // first to last byte of one frame
+    AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span,
+               "window_rects_plan: row pitch %lld, frame stride %lld for frames of %dx%d", (long long)s.row_pitch, (long long)s.frame_stride, s.width, s.height);
+    AF_REQUIRE(s.store_bytes >= (int64_t)(s.n_frames - 1) * s.frame_stride + frame_span, "window_rects_plan: %d frames do not fit a store of %lld bytes",
+               s.n_frames, (long long)s.store_bytes);
+    WindowTableHeader* hd = (WindowTableHeader*)table;
+    WindowXform* xf = (WindowXform*)(hd + 1);
+    WindowRect* out = (WindowRect*)(xf + n_windows);
+    for (int w = 0; w < n_windows; ++w) {
+        const af_window_desc& d = windows[w];
+        AF_REQUIRE(d.canvas_h > 0 && d.canvas_w > 0 && d.canvas_h <= 32767 && d.canvas_w <= 32767, "window_rects_plan: window %d: bad canvas %dx%d",
+                   w, d.canvas_w, d.canvas_h);
+        invert_affine_cv(d.tfm, xf[w].m);
+        for (int t = 0; t < clip_size; ++t) {
+            const af_frame_rect& r = rects[w * clip_size + t];
+            AF_REQUIRE(r.frame >= 0 && r.frame < s.n_frames && r.ih > 0 && r.iw > 0 && r.rx >= 0 && r.ry >= 0 &&
+                       (int64_t)r.rx + r.iw <= s.width && (int64_t)r.ry + r.ih <= s.height,
+                       "window_rects_plan: window %d frame %d: rectangle %dx%d at (%d,%d) of frame %d leaves the %d frames of %dx%d", w, t, r.iw, r.ih,
+                       r.rx, r.ry, r.frame, s.n_frames, s.width, s.height);
+            const int64_t offset = (int64_t)r.frame * s.frame_stride + (int64_t)r.ry * s.row_pitch + (int64_t)r.rx * 3;
+            // the kernel reads the two taps of a row as 6 bytes: inside a frame the 3 bytes behind a rectangle's last pixel are the
+            // frame's next pixels, so only a rectangle that ends with the store needs them to be there
+            AF_REQUIRE(offset + (int64_t)(r.ih - 1) * s.row_pitch + (int64_t)r.iw * 3 + 3 <= s.store_bytes,
+                       "window_rects_plan: window %d frame %d: 3 readable bytes must follow the rectangle that ends the store of %lld bytes", w, t,
+                       (long long)s.store_bytes);
+            // the reference pastes with new_image[y:y+ih, x:x+iw] = image, which numpy refuses unless the crop fits the canvas
+            if (r.x < 0 || r.y < 0 || (long long)r.x + r.iw > d.canvas_w || (long long)r.y + r.ih > d.canvas_h) {
+                if (bad_window) *bad_window = w;
+                if (bad_frame) *bad_frame = t;
+                return set_error(AF_ERR_ARG, "aligner: window %d frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas", w, t, r.iw, r.ih, r.x, r.y,
+                                 d.canvas_w, d.canvas_h);
+            }
+            out[w * clip_size + t] = WindowRect{offset, r.ih, r.iw, r.x, r.y, (int32_t)s.row_pitch, 0};
+        }
+    }
+    hd->n_windows = n_windows; hd->clip_size = clip_size; hd->size = size; hd->kind = WB_KIND_RECTS;
+    return AF_OK;
+}
+
+extern "C" int af_warp_affine_window_rects_u8(const void* store, const void* table, int n_windows, int clip_size, int size, void* out,
+                                              void* stream) {
+    return af::launch_window_warp<af::WindowRect>("warp_affine_window_rects", store, table, n_windows, clip_size, size, out, stream);
 }
 
 extern "C" int af_warp_affine_clip_u8(const void* crops, const af_align_frame* frames, int n_frames, int canvas_h, int canvas_w,

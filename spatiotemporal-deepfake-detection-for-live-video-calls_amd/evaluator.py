@@ -1,4 +1,5 @@
-"""The offline evaluator's clip loop on the MI355X: every sliding window of a face track aligned and scored on the GPU.
+"""The offline evaluator on the MI355X: decoded frames in, video score out (``VideoScorer``), and the clip loop it ends in - every
+sliding window of a face track aligned and scored on the GPU (``TrackScorer``).
 
 The reference (altfreezing/demo.py:304-339) walks over EVERY ``clip_size``-frame window of a face track, stride 1: align the
 window's crops (``FasterCropAlignXRay``), normalise, forward at batch 1, sigmoid; the mean over the windows is the video's
@@ -7,11 +8,20 @@ pool, fits every window's similarity on the host with the aligner's own arithmet
 aligns ``batch`` windows per launch straight out of the pool (``af_warp_affine_windows_u8``, csrc/af_align.hip) into the uint8
 clip buffer ``I3D8x8.forward_clips_u8`` consumes.  Nothing is synchronised before the end of the track.
 
+``VideoScorer`` joins the stages in front of it (demo.py ``eval_video_demo_timed``): every decoded frame is uploaded ONCE into a
+device frame store, the RetinaFace detector reads views of that store, the detections come back in one copy, the tracks are
+built on the host, and the window batches are warped out of rectangles of the resident frames
+(``af_warp_affine_window_rects_u8``) - no crop is cut on the host and no pixel crosses PCIe twice.
+
 Restated from the reference: the window index lists (demo.py:275-302, ``clip_windows``), the crop box and the per-face record
 (demo.py:245-269 with ``get_crop_box``, test_tools/utils.py:13-24: ``crop_records``), the per-video summary (demo.py:333-340,
-346-349: ``summarise``).  NOT here: grouping detections into tracks (``multiple_tracking`` / ``find_longest``: their module
-imports matplotlib and filterpy, absent here, so it cannot be pinned), video decoding, the visualisation writer.  There is no
-CPU fallback: without the HIP library the calls fail.
+346-349: ``summarise``), and the grouping of detections into tracks: ``get_valid_faces`` (test_tools/ct/detection/utils.py:75-89),
+``iou`` (test_tools/ct/tracking/sort.py:30-45), ``simple_tracking`` / ``multiple_tracking`` / ``find_longest``
+(test_tools/ct/operations.py:13-80).  The tracking functions are pinned by tests/golden/video_tracks.json, which
+tools/gen_video_golden.py records from the reference's own functions (their modules are loaded by file path with empty stand-ins
+for cv2, matplotlib, scipy and filterpy, which they import and these functions never call).  NOT here: the 68-point landmarks
+(the aligner fits on the five points only and RetinaFace always supplies them, so no score depends on lm68), video decoding,
+the visualisation writer.  There is no CPU fallback: without the HIP library the calls fail.
 """
 import ctypes as C
 from typing import List, Optional, Sequence
@@ -22,6 +32,7 @@ import torch
 from .aligner import STD_POINTS_256, _COPY_THREADS, _pool, estimate_batch_transform
 
 _FRAME_DTYPE = np.dtype([("offset", "<i8"), ("ih", "<i4"), ("iw", "<i4"), ("x", "<i4"), ("y", "<i4")])       # af_align_frame
+_RECT_DTYPE = np.dtype([(n, "<i4") for n in ("frame", "rx", "ry", "ih", "iw", "x", "y", "reserved")])            # af_frame_rect
 _WINDOW_DTYPE = np.dtype([("tfm", "<f8", (6,)), ("canvas_h", "<i4"), ("canvas_w", "<i4")])                  # af_window_desc
 _POOL_SLACK = 16          # the kernel reads tap pairs as 6 bytes: 3 readable bytes behind the last crop (af_hip.h)
 _STAGE_BYTES = 16 << 20   # one staging slot: about a clip's worth of crops, the size the aligner's ring was measured at
@@ -89,6 +100,133 @@ def summarise(frame_ids_per_clip, preds, threshold: float = 0.04) -> dict:
             "frame_res": {k: float(np.mean(v)) for k, v in seen.items()}}
 
 
+def get_valid_faces(detect_results, max_count: int = 10, thres: float = 0.5, at_least: bool = False):
+    """Per frame the detector's faces ``(box, lm5, score)`` that count (test_tools/ct/detection/utils.py:75-89): the first
+    ``max_count`` of the frame, of those the ones with ``score >= thres`` - and, with ``at_least``, the frame's first face whatever
+    its score.  Box and landmarks come back as float64 copies, the score as it was."""
+    out = []
+    for faces in detect_results:
+        kept = []
+        for j, face in enumerate(faces[:max_count]):
+            if face[-1] < thres and not (j == 0 and at_least):
+                continue
+            box, lm, score = face
+            kept.append((box.astype(np.float64), lm.astype(np.float64), score))
+        out.append(kept)
+    return out
+
+
+def iou(a, b):
+    """intersection over union of two ``[x1, y1, x2, y2]`` boxes (test_tools/ct/tracking/sort.py:30-45), in that order of operations"""
+    w = np.maximum(0.0, np.minimum(a[2], b[2]) - np.maximum(a[0], b[0]))
+    h = np.maximum(0.0, np.minimum(a[3], b[3]) - np.maximum(a[1], b[1]))
+    both = w * h
+    return both / ((a[2] - a[0]) * (a[3] - a[1]) + (b[2] - b[0]) * (b[3] - b[1]) - both)
+
+
+def _admitted(faces, index: int, thres: float) -> bool:
+    """frame 0's gate of ``simple_tracking``: face ``index`` exists, scores at least 0.8 and overlaps no earlier face of the frame
+    by more than ``thres``"""
+    if len(faces) <= index or faces[index][-1] < 0.8:
+        return False
+    return not any(iou(faces[k][0], faces[index][0]) > thres for k in range(index))
+
+
+def _successor(faces, last, thres: float):
+    """the face of the next frame a track goes on with: the first one of the largest IoU with the track's last face; None (the
+    track dies) on a frame without faces or when that IoU is below ``thres``"""
+    if len(faces) == 0:
+        return None
+    overlaps = [iou(f[0], last[0]) for f in faces]
+    best = 0
+    for k in range(1, len(faces)):                                # the first of equals, as a stable descending sort puts it in front
+        if overlaps[k] > overlaps[best]:
+            best = k
+    return None if overlaps[best] < thres else faces[best]
+
+
+def simple_tracking(batch_landmarks, index: int = 0, thres: float = 0.5):
+    """The track that starts at face ``index`` of frame 0 and takes, frame by frame, the face that overlaps its last one most
+    (test_tools/ct/operations.py:13-35); None when frame 0 refuses the face or the track dies before the last frame.  A face is
+    ``(box, ..., score)``; the track holds the input's own face objects."""
+    track = []
+    for i, faces in enumerate(batch_landmarks):
+        if i == 0:
+            if not _admitted(faces, index, thres):
+                return None
+            track.append(faces[index])
+        else:
+            face = _successor(faces, track[-1], thres)
+            if face is None:
+                return None
+            track.append(face)
+    return track
+
+
+def multiple_tracking(batch_landmarks):
+    """one ``simple_tracking`` per face of FRAME 0 (operations.py:38-45): a face that first shows up later starts no track"""
+    tracks = [simple_tracking(batch_landmarks, index=i) for i in range(len(batch_landmarks[0]))]
+    return [t for t in tracks if t is not None]
+
+
+class _GrowingTracks:
+    """``multiple_tracking(detect_res[start:start + length])`` for growing ``length`` without starting over: a greedy track over a
+    longer run of frames is the track over the shorter run plus one face, and a track that has died stays dead"""
+
+    def __init__(self, detect_res, start: int, thres: float = 0.5):
+        self.res, self.start, self.thres = detect_res, start, thres
+        first = detect_res[start]
+        self.tracks = [[first[i]] for i in range(len(first)) if _admitted(first, i, thres)]
+        self.limit = [None] * len(self.tracks)                    # the longest run of frames the track spans, None while it lives
+        self.done = 1
+
+    def upto(self, length: int):
+        while self.done < length:
+            faces = self.res[self.start + self.done]
+            for t, track in enumerate(self.tracks):
+                if self.limit[t] is None:
+                    face = _successor(faces, track[-1], self.thres)
+                    if face is None:
+                        self.limit[t] = self.done
+                    else:
+                        track.append(face)
+            self.done += 1
+        return [track[:length] for track, limit in zip(self.tracks, self.limit) if limit is None or limit >= length]
+
+
+def find_longest(detect_res):
+    """The runs of frames that can be tracked when no track spans the whole video (operations.py:47-80): from ``start`` the run
+    grows while the number of tracks stays what it was and is not 0; a run of more than two frames gives the span
+    ``(start, un_reach_end)`` - the frame that broke the run is left out, the video's end is kept - and its FIRST track; the next
+    run starts where this one ended.  Returns ``(spans, tracks)``.  The reference tracks every prefix of every run from scratch;
+    here a run's tracks grow by one frame at a time, with the same results."""
+    fc = len(detect_res)
+    spans, all_tracks = [], []
+    start = end = 0
+    while start < fc - 1:
+        grow = _GrowingTracks(detect_res, start)
+        previous_count = -1
+        for end in range(start + 2, fc + 1):
+            count = len(grow.upto(end - start))
+            if (count != previous_count and previous_count != -1) or count == 0:
+                break
+            previous_count = count
+        if end - start > 2:
+            un_reach_end = end - 1 if end != fc else end
+            sub_tracks = grow.upto(un_reach_end - start)
+            if end == fc and len(sub_tracks) == 0:
+                un_reach_end = end - 1
+                sub_tracks = grow.upto(un_reach_end - start)
+            if len(sub_tracks) > 0:
+                spans.append((start, un_reach_end))
+                all_tracks.append(sub_tracks[0])
+            else:
+                raise NotImplementedError
+            end = un_reach_end
+        start = end
+    return spans, all_tracks
+
+
 def _is_crop(im) -> bool:
     return isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3
 
@@ -112,23 +250,14 @@ class _Track:
             self.bytes = (self.ih * self.iw * 3 + 15) // 16 * 16
 
 
-class TrackScorer:
-    """``TrackScorer(network)``: all sliding windows of a face track, aligned and scored on the GPU.
+class _WindowScorer:
+    """What TrackScorer and VideoScorer share: the partition of a track's windows into forwards, the per-window fit, the table ring
+    and the double clip buffer, the window-batch warp launch, the segments of a track that does not fit the device memory it may
+    use, and the loop that enqueues a track.  A subclass says where a track's pixels live: ``_upload`` brings frames [lo, hi) of a
+    track onto the device and returns where each one sits, ``_fill_items`` writes that into the planner's per-(window, frame)
+    records of ``_ITEM``, and ``_TABLE_BYTES`` / ``_PLAN`` / ``_LAUNCH`` name the C entry points of its form of the warp."""
 
-    ``network``: an ``I3D8x8`` on a HIP device in eval mode, or a ``Classifier`` (its ``.network`` is used).  One scorer works on
-    the stream that is current when it is called and owns its pool, clip buffers and tables; the network's engines are not
-    shared between streams, so scorers that run at the same time on different streams each take a network of their own.
-
-    ``score_track(infos, crops)`` equals, per window ``w`` of ``clip_windows(len(crops), clip_size)``,
-    ``sigmoid(classifier(normalise(FasterCropAlignXRay(size)(infos[w], crops[w]))))``: the fits are the aligner's own doubles,
-    the warp is bit-exact with its kernel, and the forward is ``forward_clips_u8`` on batches of ``partition(n_windows)``.
-
-    The last batch of a track is usually short.  It is padded by repeating its last window up to the next power of two (at most
-    ``batch``): the forward then only ever runs at 1, 2, 4 ... ``batch`` clips - a handful of engines, each a few GB of
-    activations - and wastes less than half a batch; a clip's score does not depend on its position in a batch.
-
-    ``pool_bytes`` bounds the device memory for crops (default 512 MiB, about a thousand 420-pixel crops).  A longer track is cut
-    into segments that overlap by ``clip_size - 1`` frames; the scores do not depend on where the cuts fall."""
+    _ITEM, _TABLE_BYTES, _PLAN, _LAUNCH = None, None, None, None
 
     def __init__(self, network, clip_size: int = 32, size: int = 224, batch: int = 16, device: Optional[torch.device] = None,
                  pool_bytes: int = 512 << 20):
@@ -147,7 +276,7 @@ class TrackScorer:
         self.device = dev
         self.pool_bytes = int(pool_bytes)
         self.std_points = STD_POINTS_256 * self.size / 256.0
-        self.table_bytes = int(_lib.lib.af_window_batch_table_bytes(self.batch, self.clip_size))
+        self.table_bytes = int(getattr(_lib.lib, self._TABLE_BYTES)(self.batch, self.clip_size))
         self.uploaded_bytes = 0                                   # crop bytes sent to the device by the last call
         self._pool_dev = None
         self._clips = None
@@ -184,62 +313,24 @@ class TrackScorer:
                 self._stage = [[torch.empty(_STAGE_BYTES, dtype=torch.uint8, pin_memory=True), None] for _ in range(3)]
         return self._clips
 
-    def _upload(self, track: _Track, lo: int, hi: int) -> np.ndarray:
-        """crops [lo, hi) of the track -> the device pool, each crop whole and once: a few pinned staging slots in turn (filled by
-        the aligner's copy threads), one asynchronous copy per slot.  Returns the crops' pool offsets (index: frame - lo)."""
-        from . import _lib
-        offs = np.zeros(hi - lo, dtype=np.int64)
-        offs[1:] = np.cumsum(track.bytes[lo:hi])[:-1]
-        total = int(track.bytes[lo:hi].sum())
-        if total + _POOL_SLACK > self.pool_bytes:
-            raise ValueError("evaluator: %d frames (%d bytes) do not fit the pool of %d bytes" % (hi - lo, total, self.pool_bytes))
-        if self._pool_dev is None or self._pool_dev.numel() < total + _POOL_SLACK:
-            self._pool_dev = None                                  # give the old pool back before taking a larger one
+    def _stage_slot(self, used: int):
+        """the next pinned staging slot, free again (the copy of three slots ago has left it) and at least `used` bytes large"""
+        slot = self._stage[self._stage_turn % len(self._stage)]
+        self._stage_turn += 1
+        if slot[1] is not None:
+            slot[1].synchronize()
+        if slot[0].numel() < used:                                 # one crop / frame larger than a slot
             with torch.inference_mode(False):
-                self._pool_dev = torch.empty(min(self.pool_bytes, max(total + _POOL_SLACK, 64 << 20)), dtype=torch.uint8, device=self.device)
-        i = lo
-        while i < hi:
-            j, used = i, 0
-            while j < hi and (j == i or used + int(track.bytes[j]) <= _STAGE_BYTES):
-                used += int(track.bytes[j])
-                j += 1
-            slot = self._stage[self._stage_turn % len(self._stage)]
-            self._stage_turn += 1
-            if slot[1] is not None:
-                slot[1].synchronize()                              # the copy of three slots ago has left the pinned buffer
-            if slot[0].numel() < used:                             # one crop larger than a slot
-                with torch.inference_mode(False):
-                    slot[0] = torch.empty(used, dtype=torch.uint8, pin_memory=True)
-            rects = (_lib.StageRect * (j - i))()
-            keep = []                                              # arrays whose addresses are in `rects` live until the copies return
-            for k in range(i, j):
-                im = track.crops[k]
-                st = im.strides
-                if st[2] != 1 or st[1] != 3 or st[0] < im.shape[1] * 3:
-                    im = np.ascontiguousarray(im)
-                    st = im.strides
-                keep.append(im)
-                rects[k - i] = _lib.StageRect(im.__array_interface__["data"][0], int(offs[k - lo] - offs[i - lo]),
-                                              st[0] if im.shape[0] > 1 else im.shape[1] * 3, im.shape[0], im.shape[1] * 3)
-            base, n = slot[0].data_ptr(), j - i
-            nt = min(_COPY_THREADS, n)
-            if nt > 1 and used >= (1 << 20):
-                cuts = [n * t // nt for t in range(nt + 1)]
-                def part(t):
-                    _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), C.byref(rects, cuts[t] * C.sizeof(_lib.StageRect)), cuts[t + 1] - cuts[t]),
-                               "stage_rows_u8")
-                list(_pool().map(part, range(nt)))
-            else:
-                _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), rects, n), "stage_rows_u8")
-            del keep
-            o = int(offs[i - lo])
-            self._pool_dev[o:o + used].copy_(slot[0][:used], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            slot[1] = ev
-            self.uploaded_bytes += used
-            i = j
-        return offs
+                slot[0] = torch.empty(used, dtype=torch.uint8, pin_memory=True)
+        return slot
+
+    def _send_slot(self, slot, used: int, offset: int):
+        """pinned slot -> device memory at `offset`, asynchronous; the event lets the host know when the slot may be refilled"""
+        self._pool_dev[offset:offset + used].copy_(slot[0][:used], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        slot[1] = ev
+        self.uploaded_bytes += used
 
     def _fit(self, track: _Track, idx: Sequence[int]):
         """one window's canvas, paste offsets and transform, exactly as FasterCropAlignXRay.__call__ computes them
@@ -257,12 +348,12 @@ class TrackScorer:
         from . import _lib
         n = len(windows)
         desc = np.zeros(n, dtype=_WINDOW_DTYPE)
-        frames = np.zeros((n, self.clip_size), dtype=_FRAME_DTYPE)
+        frames = np.zeros((n, self.clip_size), dtype=self._ITEM)
         for w, idx in enumerate(windows):
             tfm, h, wd, diff = fits[w] if fits is not None else self._fit(track, idx)
             desc[w] = (np.asarray(tfm, dtype=np.float64).reshape(6), h, wd)
             ii = np.asarray(idx)
-            frames["offset"][w] = offs[ii - first_frame]
+            self._fill_items(frames, w, track, ii, offs[ii - first_frame])
             frames["ih"][w], frames["iw"][w] = track.ih[ii], track.iw[ii]
             frames["x"][w], frames["y"][w] = diff[:, 0], diff[:, 1]
         slot = self._tables[self._table_turn % len(self._tables)]
@@ -270,22 +361,22 @@ class TrackScorer:
         if slot[2] is not None:
             slot[2].synchronize()
         bad_w, bad_f = C.c_int32(-1), C.c_int32(-1)
-        rc = _lib.lib.af_window_batch_plan_u8(desc.ctypes.data, frames.ctypes.data, n, self.clip_size, self.size, self._pool_dev.numel(),
-                                              slot[0].data_ptr(), self.table_bytes, C.byref(bad_w), C.byref(bad_f))
+        rc = getattr(_lib.lib, self._PLAN)(desc.ctypes.data, frames.ctypes.data, n, self.clip_size, self.size, self._plan_source(),
+                                           slot[0].data_ptr(), self.table_bytes, C.byref(bad_w), C.byref(bad_f))
         if rc != 0 and bad_w.value >= 0:
             f = frames[bad_w.value, bad_f.value]
             # numpy refuses new_image[y:y+ih, x:x+iw] = image for a crop that sticks out of the canvas
             raise ValueError("aligner: window %d frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas"
                              % (bad_w.value, bad_f.value, f["iw"], f["ih"], f["x"], f["y"], desc[bad_w.value]["canvas_w"], desc[bad_w.value]["canvas_h"]))
-        _lib.check(rc, "window_batch_plan_u8")
-        used = int(_lib.lib.af_window_batch_table_bytes(n, self.clip_size))
+        _lib.check(rc, self._PLAN[3:])
+        used = int(getattr(_lib.lib, self._TABLE_BYTES)(n, self.clip_size))
         slot[1][:used].copy_(slot[0][:used], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         slot[2] = ev
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(_lib.lib.af_warp_affine_windows_u8(C.c_void_p(self._pool_dev.data_ptr()), C.c_void_p(slot[1].data_ptr()), n, self.clip_size,
-                                                      self.size, C.c_void_p(out.data_ptr()), stream), "warp_affine_windows_u8")
+        _lib.check(getattr(_lib.lib, self._LAUNCH)(C.c_void_p(self._pool_dev.data_ptr()), C.c_void_p(slot[1].data_ptr()), n, self.clip_size,
+                                                   self.size, C.c_void_p(out.data_ptr()), stream), self._LAUNCH[3:])
 
     def _segments(self, track: _Track, windows):
         """[(first frame, end frame, windows)]: the whole track if its crops fit the pool, else runs of consecutive windows whose
@@ -309,11 +400,8 @@ class TrackScorer:
             k = j
         return segs
 
-    # -- public ------------------------------------------------------------------------------------
-    def aligned_windows(self, infos, crops, windows) -> torch.Tensor:
-        """the warp stage alone: uint8 CUDA tensor (len(windows), clip_size, size, size, 3), window ``w`` =
-        ``FasterCropAlignXRay(size)(infos[windows[w]], crops[windows[w]])``.  The frames the windows use must fit the pool."""
-        track = _Track(infos, crops)
+    def _aligned(self, track, windows) -> torch.Tensor:
+        """the warp stage alone for windows (index lists) of one track whose frames fit the device memory at once"""
         windows = [list(map(int, w)) for w in windows]
         for w in windows:
             if len(w) != self.clip_size or min(w) < 0 or max(w) >= track.n:
@@ -321,7 +409,6 @@ class TrackScorer:
         out = torch.empty((len(windows), self.clip_size, self.size, self.size, 3), dtype=torch.uint8, device=self.device)
         if not windows:
             return out
-        self.uploaded_bytes = 0
         with torch.cuda.device(self.device):
             self._buffers()
             lo, hi = min(min(w) for w in windows), max(max(w) for w in windows) + 1
@@ -360,6 +447,102 @@ class TrackScorer:
                     parts.append(self.network.forward_clips_u8(buf, return_scores=True)["scores"][:n])
         return parts
 
+    def _score_tracks(self, tracks, threshold: float) -> dict:
+        """demo.py:304-340, 346-349 over ``(first frame, track)`` pairs: all tracks are enqueued before the first score is read
+        back - the only synchronisation - and summarised"""
+        clips, frame_ids, parts = [], [], []
+        for track_i, (start, track) in enumerate(tracks):
+            windows = clip_windows(track.n, self.clip_size)
+            if not windows:
+                continue
+            clips += [[(track_i, j) for j in w] for w in windows]
+            frame_ids += [[start + j for j in w] for w in windows]
+            parts += self._score_device(track, windows)
+        preds = torch.cat(parts).float().cpu().numpy() if parts else np.zeros(0, dtype=np.float32)
+        res = summarise(frame_ids, preds, threshold)
+        res["clips"] = clips
+        return res
+
+
+class TrackScorer(_WindowScorer):
+    """``TrackScorer(network)``: all sliding windows of a face track, aligned and scored on the GPU.
+
+    ``network``: an ``I3D8x8`` on a HIP device in eval mode, or a ``Classifier`` (its ``.network`` is used).  One scorer works on
+    the stream that is current when it is called and owns its pool, clip buffers and tables; the network's engines are not
+    shared between streams, so scorers that run at the same time on different streams each take a network of their own.
+
+    ``score_track(infos, crops)`` equals, per window ``w`` of ``clip_windows(len(crops), clip_size)``,
+    ``sigmoid(classifier(normalise(FasterCropAlignXRay(size)(infos[w], crops[w]))))``: the fits are the aligner's own doubles,
+    the warp is bit-exact with its kernel, and the forward is ``forward_clips_u8`` on batches of ``partition(n_windows)``.
+
+    The last batch of a track is usually short.  It is padded by repeating its last window up to the next power of two (at most
+    ``batch``): the forward then only ever runs at 1, 2, 4 ... ``batch`` clips - a handful of engines, each a few GB of
+    activations - and wastes less than half a batch; a clip's score does not depend on its position in a batch.
+
+    ``pool_bytes`` bounds the device memory for crops (default 512 MiB, about a thousand 420-pixel crops).  A longer track is cut
+    into segments that overlap by ``clip_size - 1`` frames; the scores do not depend on where the cuts fall."""
+
+    _ITEM, _TABLE_BYTES, _PLAN, _LAUNCH = _FRAME_DTYPE, "af_window_batch_table_bytes", "af_window_batch_plan_u8", "af_warp_affine_windows_u8"
+
+    def _upload(self, track: _Track, lo: int, hi: int) -> np.ndarray:
+        """crops [lo, hi) of the track -> the device pool, each crop whole and once: a few pinned staging slots in turn (filled by
+        the aligner's copy threads), one asynchronous copy per slot.  Returns the crops' pool offsets (index: frame - lo)."""
+        from . import _lib
+        offs = np.zeros(hi - lo, dtype=np.int64)
+        offs[1:] = np.cumsum(track.bytes[lo:hi])[:-1]
+        total = int(track.bytes[lo:hi].sum())
+        if total + _POOL_SLACK > self.pool_bytes:
+            raise ValueError("evaluator: %d frames (%d bytes) do not fit the pool of %d bytes" % (hi - lo, total, self.pool_bytes))
+        if self._pool_dev is None or self._pool_dev.numel() < total + _POOL_SLACK:
+            self._pool_dev = None                                  # give the old pool back before taking a larger one
+            with torch.inference_mode(False):
+                self._pool_dev = torch.empty(min(self.pool_bytes, max(total + _POOL_SLACK, 64 << 20)), dtype=torch.uint8, device=self.device)
+        i = lo
+        while i < hi:
+            j, used = i, 0
+            while j < hi and (j == i or used + int(track.bytes[j]) <= _STAGE_BYTES):
+                used += int(track.bytes[j])
+                j += 1
+            slot = self._stage_slot(used)
+            rects = (_lib.StageRect * (j - i))()
+            keep = []                                              # arrays whose addresses are in `rects` live until the copies return
+            for k in range(i, j):
+                im = track.crops[k]
+                st = im.strides
+                if st[2] != 1 or st[1] != 3 or st[0] < im.shape[1] * 3:
+                    im = np.ascontiguousarray(im)
+                    st = im.strides
+                keep.append(im)
+                rects[k - i] = _lib.StageRect(im.__array_interface__["data"][0], int(offs[k - lo] - offs[i - lo]),
+                                              st[0] if im.shape[0] > 1 else im.shape[1] * 3, im.shape[0], im.shape[1] * 3)
+            base, n = slot[0].data_ptr(), j - i
+            nt = min(_COPY_THREADS, n)
+            if nt > 1 and used >= (1 << 20):
+                cuts = [n * t // nt for t in range(nt + 1)]
+                def part(t):
+                    _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), C.byref(rects, cuts[t] * C.sizeof(_lib.StageRect)), cuts[t + 1] - cuts[t]),
+                               "stage_rows_u8")
+                list(_pool().map(part, range(nt)))
+            else:
+                _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), rects, n), "stage_rows_u8")
+            del keep
+            self._send_slot(slot, used, int(offs[i - lo]))
+            i = j
+        return offs
+
+    def _fill_items(self, items, w: int, track: _Track, idx: np.ndarray, where: np.ndarray):
+        items["offset"][w] = where
+
+    def _plan_source(self):
+        return self._pool_dev.numel()
+
+    # -- public ------------------------------------------------------------------------------------
+    def aligned_windows(self, infos, crops, windows) -> torch.Tensor:
+        """the warp stage alone: uint8 CUDA tensor (len(windows), clip_size, size, size, 3), window ``w`` =
+        ``FasterCropAlignXRay(size)(infos[windows[w]], crops[windows[w]])``.  The frames the windows use must fit the pool."""
+        self.uploaded_bytes = 0
+        return self._aligned(_Track(infos, crops), windows)
+
     def score_track(self, infos, crops) -> np.ndarray:
         """float32 fake probabilities, one per window of ``clip_windows(len(crops), clip_size)``, in that order"""
         track = _Track(infos, crops)
@@ -375,20 +558,226 @@ class TrackScorer:
         track i, one per frame of ``range(*spans[i])``; ``frames``: the decoded HxWx3 uint8 frames.  Returns ``video_score``,
         ``pred_label``, ``preds`` (per clip, track by track), ``clips`` (per clip its ``(track, index in track)`` pairs) and
         ``frame_res`` (``summarise``).  All tracks are enqueued before the first score is read back."""
-        clips, frame_ids, parts = [], [], []
         self.uploaded_bytes = 0
-        for track_i, ((start, end), faces) in enumerate(zip(spans, tracks)):
-            assert end - start == len(faces)
-            recs = crop_records(frame_shape, faces)
-            crops = [frames[f][b[1]:b[3], b[0]:b[2]] for f, (b, _) in zip(range(start, end), recs)]
-            track = _Track([info for _, info in recs], crops)
-            windows = clip_windows(track.n, self.clip_size)
-            if not windows:
-                continue
-            clips += [[(track_i, j) for j in w] for w in windows]
-            frame_ids += [[start + j for j in w] for w in windows]
-            parts += self._score_device(track, windows)
-        preds = torch.cat(parts).float().cpu().numpy() if parts else np.zeros(0, dtype=np.float32)
-        res = summarise(frame_ids, preds, threshold)
-        res["clips"] = clips
+
+        def host_cut_tracks():
+            for (start, end), faces in zip(spans, tracks):
+                assert end - start == len(faces)
+                recs = crop_records(frame_shape, faces)
+                crops = [frames[f][b[1]:b[3], b[0]:b[2]] for f, (b, _) in zip(range(start, end), recs)]
+                yield start, _Track([info for _, info in recs], crops)
+        return self._score_tracks(host_cut_tracks(), threshold)
+
+
+DETECT_BATCH = 50         # test_tools/common.py:82: the detector sees partition(frames, 50)
+_NO_LM68 = np.zeros((0, 2))
+
+
+class _FrameTrack:
+    """host arrays of one track whose crops are rectangles of decoded frames: ``frame_ids[j]`` is the frame of track position j
+    and ``rects[j]`` = (x0, y0, x1, y1) the rectangle ``frame[y0:y1, x0:x1]`` (default: the record's crop box, cut to the frame as
+    a numpy slice cuts it)"""
+
+    def __init__(self, infos, frame_ids, frame_shape, rects=None):
+        if len(infos) != len(frame_ids):
+            raise ValueError("evaluator: %d landmark records for %d frames" % (len(infos), len(frame_ids)))
+        self.n = len(infos)
+        self.frame = np.asarray(list(frame_ids), dtype=np.int64)
+        if self.n:
+            self.boxes = np.array([info[3] for info in infos])
+            self.five = np.array([info[1] for info in infos])
+            r = np.asarray(self.boxes if rects is None else rects, dtype=np.int64).reshape(self.n, 4)
+            if (r < 0).any():
+                raise ValueError("evaluator: a crop rectangle with a negative coordinate")
+            self.rx, self.ry = r[:, 0], r[:, 1]
+            self.iw = np.minimum(r[:, 2], int(frame_shape[1])) - self.rx
+            self.ih = np.minimum(r[:, 3], int(frame_shape[0])) - self.ry
+            self.bytes = np.full(self.n, int(frame_shape[0]) * int(frame_shape[1]) * 3, dtype=np.int64)
+
+
+class VideoScorer(_WindowScorer):
+    """``VideoScorer(detector, network).score(frames)``: the reference's offline evaluator (demo.py ``eval_video_demo_timed``) from
+    decoded frames to the video's score, on ONE device-resident copy of the frames.
+
+    ``detector``: a ``retinaface.FaceDetector`` on the network's device (None when detections are always handed in);
+    ``network``: as for ``TrackScorer``, whose fit, partition, padding, table ring and double clip buffer this class shares.
+
+    ``score`` stages the frames through pinned slots into a device frame store, ``DETECT_BATCH`` frames at a time, and calls
+    ``detector.detect_device(max_count=10, min_score=0.5)`` on views of the store as each batch lands - the host stages the next
+    batch while the device works on this one.  The detections come back in one copy (the first of the call's two waits), are
+    grouped into tracks on the host (``multiple_tracking``, else ``find_longest``) and every window of every track is warped out
+    of rectangles of the resident frames (``af_warp_affine_window_rects_u8``) and scored; reading the scores back is the second
+    wait.  Everything is enqueued on the stream that is current when ``score`` is called.  (Refilling a pinned slot waits for the
+    copy that last left it, as every staging ring does.)
+
+    ``frame_bytes`` bounds the frame store.  A video that does not fit is detected batch by batch through the store and then
+    scored track by track in frame segments that overlap by ``clip_size - 1`` and are uploaded again from the host frames; the
+    scores do not depend on where the cuts fall.  ``uploaded_bytes`` is what the last call sent to the device."""
+
+    _ITEM, _TABLE_BYTES, _PLAN, _LAUNCH = _RECT_DTYPE, "af_window_rects_table_bytes", "af_window_rects_plan_u8", "af_warp_affine_window_rects_u8"
+
+    def __init__(self, detector, network, clip_size: int = 32, size: int = 224, batch: int = 16, frame_bytes: int = 4 << 30):
+        super().__init__(network, clip_size, size, batch, None, frame_bytes)
+        self.detector = detector
+        if detector is not None and torch.device(detector.device) != self.device:
+            raise ValueError("evaluator: the detector is on %s, the network on %s" % (detector.device, self.device))
+        self._frames, self._shape, self._resident = None, None, False
+
+    # -- the frame store -----------------------------------------------------------------------------
+    def _open_store(self, frames):
+        """checks the frames and sizes the store for them: all of them when ``frame_bytes`` allows, else as many as it holds"""
+        shape = frames[0].shape
+        for im in frames:
+            if not _is_crop(im) or im.shape != shape:
+                raise AssertionError("evaluator: frames must be HxWx3 uint8 numpy arrays of one size")
+        self._frames, self._shape = frames, shape
+        self._frame_nbytes = shape[0] * shape[1] * 3
+        self._capacity = min(len(frames), (self.pool_bytes - _POOL_SLACK) // self._frame_nbytes)
+        self._resident = self._capacity == len(frames)
+        if self._capacity < min(len(frames), max(DETECT_BATCH if self.detector is not None else 1, self.clip_size)):
+            raise ValueError("evaluator: frame_bytes %d holds %d frames of %d bytes, fewer than a detector batch or a window"
+                             % (self.pool_bytes, self._capacity, self._frame_nbytes))
+        need = self._capacity * self._frame_nbytes + _POOL_SLACK   # 3 readable bytes behind the last frame (af_hip.h)
+        if self._pool_dev is None or self._pool_dev.numel() < need:
+            self._pool_dev = None
+            with torch.inference_mode(False):
+                self._pool_dev = torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    def _store_frames(self, ids, first_slot: int):
+        """host frames `ids` -> consecutive slots of the store from `first_slot`: pinned slots in turn, each filled by the aligner's
+        copy threads in bands of rows, one asynchronous copy per slot.  A frame whose pixels are not packed RGB bytes (a
+        channel-reversed view) costs a strided host pass here instead of a memcpy per band."""
+        from . import _lib
+        ids = list(ids)
+        h, w = self._shape[:2]
+        fb, row = self._frame_nbytes, w * 3
+        per_slot = max(1, _STAGE_BYTES // fb)
+        for i in range(0, len(ids), per_slot):
+            chunk = ids[i:i + per_slot]
+            used = len(chunk) * fb
+            slot = self._stage_slot(used)
+            base = slot[0].data_ptr()
+            host = slot[0].numpy()[:used].reshape(len(chunk), h, w, 3)
+            bands = max(1, min(h, -(-_COPY_THREADS // len(chunk)))) if used >= (1 << 20) else 1
+            jobs = []
+            for k, f in enumerate(chunk):
+                im = self._frames[f]
+                packed = im.strides[2] == 1 and im.strides[1] == 3 and im.strides[0] >= row
+                for t in range(bands):
+                    r0, r1 = h * t // bands, h * (t + 1) // bands
+                    if packed:
+                        jobs.append(_lib.StageRect(im.__array_interface__["data"][0] + r0 * im.strides[0], k * fb + r0 * row,
+                                                   im.strides[0], r1 - r0, row))
+                    else:
+                        jobs.append((host[k, r0:r1], im[r0:r1]))
+
+            def run(job):
+                if isinstance(job, tuple):
+                    np.copyto(job[0], job[1])
+                else:
+                    _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), C.byref(job), 1), "stage_rows_u8")
+            if len(jobs) > 1:
+                list(_pool().map(run, jobs))
+            else:
+                run(jobs[0])
+            self._send_slot(slot, used, (first_slot + i) * fb)
+
+    def _upload(self, track: _FrameTrack, lo: int, hi: int) -> np.ndarray:
+        """the store slots of track positions [lo, hi): where the frames already sit when the whole video is resident, else the
+        segment's frames are uploaded again into the front of the store"""
+        if self._resident:
+            return track.frame[lo:hi]
+        if hi - lo > self._capacity:
+            raise ValueError("evaluator: %d frames do not fit the frame store of %d" % (hi - lo, self._capacity))
+        self._store_frames(track.frame[lo:hi], 0)
+        return np.arange(hi - lo, dtype=np.int64)
+
+    def _segments(self, track: _FrameTrack, windows):
+        return [(0, track.n, windows)] if self._resident else super()._segments(track, windows)
+
+    def _fill_items(self, items, w: int, track: _FrameTrack, idx: np.ndarray, where: np.ndarray):
+        items["frame"][w], items["rx"][w], items["ry"][w] = where, track.rx[idx], track.ry[idx]
+
+    def _plan_source(self):
+        from . import _lib
+        h, w = self._shape[:2]
+        self._store_desc = _lib.FrameStore(self._pool_dev.numel(), self._frame_nbytes, w * 3, self._capacity, h, w, 0)
+        return C.byref(self._store_desc)
+
+    # -- the detector stage --------------------------------------------------------------------------
+    def _detect(self):
+        """upload + detect in ``partition(frames, DETECT_BATCH)`` batches, one read-back: ``get_valid_faces(detector.detect(batch))``
+        per batch, bit for bit"""
+        if self.detector is None:
+            raise ValueError("evaluator: no detector and no detections")
+        n, (h, w) = len(self._frames), self._shape[:2]
+        store = self._pool_dev[:self._capacity * self._frame_nbytes].view(self._capacity, h, w, 3)
+        found = []
+        for lo in range(0, n, DETECT_BATCH):
+            hi = min(lo + DETECT_BATCH, n)
+            first = lo if self._resident else 0                    # not resident: every batch passes through the front of the store
+            self._store_frames(range(lo, hi), first)
+            rows, counts = self.detector.detect_device(store[first:first + hi - lo], max_count=10, min_score=0.5)
+            found.append(torch.cat([rows.view(torch.int32).reshape(hi - lo, -1), counts.reshape(hi - lo, 1)], 1))    # bits, no arithmetic
+        back = torch.cat(found).cpu().numpy()                      # rows and counts of all frames in one copy: the first wait
+        counts = back[:, -1]
+        rows = np.ascontiguousarray(back[:, :-1]).view(np.float32).reshape(n, -1, 15)
+        return [[(rows[b, i, :4].astype(np.float64), rows[b, i, 5:15].reshape(5, 2).astype(np.float64), rows[b, i, 4])
+                 for i in range(int(counts[b]))] for b in range(n)]
+
+    # -- public ------------------------------------------------------------------------------------
+    def aligned_windows(self, frames, frame_ids, infos, windows, rects=None) -> torch.Tensor:
+        """the warp stage alone: uint8 CUDA tensor (len(windows), clip_size, size, size, 3).  Track position j is the rectangle
+        ``rects[j]`` = (x0, y0, x1, y1) (default: the crop box ``infos[j][3]``) of ``frames[frame_ids[j]]``; window ``w`` equals
+        ``TrackScorer.aligned_windows`` on the crops ``frame[y0:y1, x0:x1]`` cut on the host.  All frames are uploaded, so they
+        must fit ``frame_bytes``."""
+        frames = list(frames)
+        self.uploaded_bytes = 0
+        with torch.cuda.device(self.device):
+            self._buffers()
+            self._open_store(frames)
+            if not self._resident:
+                raise ValueError("evaluator: %d frames do not fit frame_bytes %d" % (len(frames), self.pool_bytes))
+            track = _FrameTrack(infos, frame_ids, self._shape, rects)
+            if track.n and (track.frame.min() < 0 or track.frame.max() >= len(frames)):
+                raise ValueError("evaluator: a frame index outside the %d frames" % len(frames))
+            self._store_frames(range(len(frames)), 0)
+            return self._aligned(track, windows)
+
+    def score(self, frames, detections=None, threshold: float = 0.04) -> dict:
+        """``frames``: the decoded HxWx3 uint8 frames of one video, all of one size (a channel-reversed view, as
+        ``grab_all_frames(cvt=True)`` returns, is taken as it is).  ``detections``: per frame the faces ``(box, lm5, score)``, the
+        first value ``detect_all`` returns and demo.py caches; given, they replace the detector stage.  Returns what
+        ``TrackScorer.score_video`` returns (``video_score``, ``pred_label``, ``preds``, ``clips``, ``frame_res``) for the tracks
+        demo.py:235-238 builds, plus ``detections``, ``tracks`` (each face ``(box, lm5, score)``) and ``spans``."""
+        frames = list(frames)
+        self.uploaded_bytes = 0
+        if not frames:
+            res = summarise([], [], threshold)
+            res.update(clips=[], detections=[], tracks=[], spans=[])
+            return res
+        with torch.cuda.device(self.device):
+            self._buffers()
+            self._open_store(frames)
+            if detections is None:
+                detections = self._detect()
+            else:
+                detections = [list(faces) for faces in detections]
+                if len(detections) != len(frames):
+                    raise ValueError("evaluator: detections for %d frames, %d frames" % (len(detections), len(frames)))
+                if self._resident:
+                    self._store_frames(range(len(frames)), 0)
+            tracks = multiple_tracking(detections)
+            spans = [(0, len(detections))] * len(tracks)
+            if len(tracks) == 0:
+                spans, tracks = find_longest(detections)
+
+            def resident_tracks():
+                for (start, end), faces in zip(spans, tracks):
+                    assert end - start == len(faces)
+                    recs = crop_records(self._shape, [(f[0], f[1], _NO_LM68, f[-1]) for f in faces])
+                    yield start, _FrameTrack([info for _, info in recs], range(start, end), self._shape)
+            res = self._score_tracks(resident_tracks(), threshold)
+        res.update(detections=detections, tracks=tracks, spans=spans)
+        self._frames = None                                        # the host frames are the caller's
         return res
