@@ -142,6 +142,16 @@ int af_pack_input_f32_rgb3(const float* x, int n, int t, int h, int w,
                            int dtype, void* stem_in, void* stream);
 int af_pack_input_u8_rgb3(const uint8_t* clips, int n, int t, int h, int w,
                           const float mean[3], const float std_[3], int dtype, void* stem_in, void* stream);
+/* SlowFast's two inputs out of ONE read of the clip (added within ABI 6): caller-layout uint8 clips (n,t,h,w,3) ->
+ * fast_in = all t frames, slow_in = frames 0, alpha, 2 alpha, ... (t / alpha frames; t % alpha != 0 is AF_ERR_ARG) - what
+ * SlowFast's pack_pathway_output does with torch.index_select on the normalised tensor.  Each output is written in the layout
+ * its stem reads: AF_PACK_C4 = the 4-channel padded layout of af_pack_input_u8 (af_stem_input_bytes), AF_PACK_RGB3 = the K-packed
+ * layout of af_pack_input_u8_rgb3 (af_stem_input_bytes_rgb3; 16-bit dtypes only), with exactly the bytes those two entry points
+ * write for the same frames: (x - mean[c]) / std[c], one rounding, interior cells only (the caller zero-fills both buffers once).
+ * Both outputs 16-byte aligned.  A frame's pixels are loaded and normalised once and stored into both outputs. */
+enum af_pack_layout { AF_PACK_C4 = 0, AF_PACK_RGB3 = 1 };
+int af_pack_input_u8_pathways(const uint8_t* clips, int n, int t, int h, int w, const float mean[3], const float std_[3],
+                              int alpha, int dtype, void* slow_in, int slow_layout, void* fast_in, int fast_layout, void* stream);
 int64_t af_packed_stem_weight_bytes_rgb3(int kt, int dtype);
 int af_pack_stem_weight_rgb3(const float* w_oidhw, int cout, int kt, int dtype, void* packed, void* stream);
 int af_stem_conv_bn_relu_maxpool_rgb3(const af_conv_desc* d, const void* stem_in, const void* w_packed,
@@ -464,7 +474,14 @@ enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD 
                   AF_OP_TSTEM_POOL3 = 21,
                   /* c of s2's last block + temporal pool + a of s3's block 0: fields as CONV_CA (no conv3 segment), x_sub
                      (af_conv3d_cpa_bn_act) */
-                  AF_OP_CONV_CPA = 22 };
+                  AF_OP_CONV_CPA = 22,
+                  /* both SlowFast inputs from one uint8 clip (af_pack_input_u8_pathways): in = clips, conv.n / t / h / w = the Fast
+                     input's dims, conv.dtype, mean, std_, out = the Slow input, aux = the Fast input, x_sub = alpha, pack_rgb3
+                     (added within ABI 6) */
+                  AF_OP_PACK_PATHWAYS_U8 = 23,
+                  /* launches nothing: the slot of an op whose work another op of the list does (SlowFast's second input pack
+                     in a uint8 run); keeps op indices the same for every input form */
+                  AF_OP_NOP = 24 };
 
 typedef struct af_op {
     int32_t kind;                    /* af_op_kind */
@@ -504,9 +521,10 @@ typedef struct af_op {
     const float* shift3;
     af_conv_desc conv4;
     const void* weight4;
-    /* CONV_CPA: 1 = the whole pooled trunk is stored, 2 = its even (h, w) positions, packed (ABI 3) */
+    /* CONV_CPA: 1 = the whole pooled trunk is stored, 2 = its even (h, w) positions, packed (ABI 3); PACK_PATHWAYS_U8: alpha */
     int32_t x_sub;
-    int32_t reserved0;
+    /* PACK_PATHWAYS_U8: bit 0 = the Slow input (out) is AF_PACK_RGB3, bit 1 = the Fast input (aux) is; the former reserved0 */
+    int32_t pack_rgb3;
 } af_op;
 
 /* Enqueue ops[0..n) in order on `stream` (AltFreezing: ResNet.forward, video_model_builder.py:561-578). */

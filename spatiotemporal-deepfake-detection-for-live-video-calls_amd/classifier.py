@@ -170,62 +170,11 @@ class _HipNetwork(nn.Module):
             return proj(feat.clone()).reshape(B, -1)
         return logits.clone().view(B, -1)
 
-
-class I3D8x8(_HipNetwork):
-    """The plugin's network module (``module_to_build`` of the reference Classifier)."""
-
-    def __init__(self, clip_size: int = 32, imsize: int = 224, precision: str = "auto", crop_size: int = 224,
-                 streams: Optional[int] = None) -> None:
-        # the head pool is sized from DATA.CROP_SIZE=224 (defaults.py:277), not from imsize (SURVEY App. B);
-        # crop_size is only changed by tests that run a shrunken network
-        super().__init__(i3d_r50_spec(num_frames=clip_size, crop=crop_size), precision)
-        self.clip_size, self.imsize = clip_size, imsize
-        # streams = 2: a batch of >= split_min_batch clips runs as two half-batches on two HIP streams (two engines).  The forward
-        # alternates between MFMA-bound and HBM-bound launches; the launches of two independent half-batches can fill some of each
-        # other's idle time.  Measured with the round-2 kernels: B=16 +2-3 %, B=32 +5 %; with the round-3 / round-4 kernels (whole
-        # rounds of persistent workgroups per launch) it is a LOSS at B=16 (driver's round-3 line: 3 047 against 3 121 clips/s) -
-        # DESIGN.md 7.  Off by default (1): opt in with the argument or AF_MI355X_STREAMS=2, and measure.
-        self.streams = int(streams if streams is not None else os.environ.get("AF_MI355X_STREAMS", "1"))
-        self.split_min_batch = 16
-        self._side = {}
-
     def _run(self, B, dims, dev, runner):
         """runner(engine, lo, hi) -> (logits, pooled) for clips [lo, hi).  Returns (an engine of the run, logits, pooled, scores)."""
-        dtype = self._select_dtype()
-        ns = self.streams if (self.streams > 1 and B >= self.split_min_batch) else 1
-        if ns == 1:
-            eng = self._engine(dtype, B, dims, dev)
-            logits, pooled = runner(eng, 0, B)
-            return eng, logits, pooled, eng.scores
-        cur = torch.cuda.current_stream(dev)
-        if (str(dev), ns) not in self._side:
-            self._side[(str(dev), ns)] = [torch.cuda.Stream(dev) for _ in range(ns)]
-        side = self._side[(str(dev), ns)]
-        parts = []
-        for slot in range(ns):
-            lo, hi = slot * B // ns, (slot + 1) * B // ns
-            side[slot].wait_stream(cur)                       # the caller's input is ready
-            with torch.cuda.stream(side[slot]):
-                eng = self._engine(dtype, hi - lo, dims, dev, slot=slot)
-                logits, pooled = runner(eng, lo, hi)
-                parts.append((eng, logits, pooled, eng.scores))
-        for s in side:
-            cur.wait_stream(s)
-        cat = lambda i: None if parts[0][i] is None else torch.cat([p[i] for p in parts])
-        return parts[0][0], cat(1), cat(2), cat(3)
-
-    def forward(self, images, noise=None, has_mask=None, freeze_backbone=False, return_feature_maps=False, return_scores=False):
-        assert not freeze_backbone
-        x = self._check_input(images)
-        B, _, T, H, W = x.shape
-        if B == 0:                                   # an empty batch is an empty answer (no launch)
-            return {"final_output": x.new_zeros((0, self.spec.num_classes))}
-        with torch.cuda.device(x.device):
-            eng, logits, pooled, scores = self._run(B, (T, H, W), x.device, lambda e, lo, hi: e.run_f32(x[lo:hi]))
-            out = {"final_output": self._finish(eng, logits, pooled, B)}
-            if return_scores:                        # not a reference argument: the callers' sigmoid, from the head kernel
-                out["scores"] = self._scores_of(eng, scores, B)
-        return out
+        eng = self._engine(self._select_dtype(), B, dims, dev)
+        logits, pooled = runner(eng, 0, B)
+        return eng, logits, pooled, eng.scores
 
     @staticmethod
     def _scores_of(eng, scores, B):
@@ -238,8 +187,8 @@ class I3D8x8(_HipNetwork):
         as_tensor/permute/sub/div of ``ClassifierSvc.infer_scores`` (test/af_realtime.py:77-83).
         ``return_scores`` adds ``"scores"``: (B,) sigmoid(logit) - or softmax[:,1] for a 2-class head - computed by the
         head kernel itself (the callers' epilogue, af_realtime.py:88-95); ``return_pooled`` adds ``"pooled"``: the
-        (B, 2048) average-pooled feature that the head's Linear consumes (what feature.py:105-114 extracts with a hook
-        and dualrun's RGB stream consumes, dualrun/model/dual_rgb.py:27-44)."""
+        feature row that the head's Linear consumes - I3D: the (B, 2048) average-pooled feature (what feature.py:105-114
+        extracts with a hook and dualrun's RGB stream consumes, dualrun/model/dual_rgb.py:27-44)."""
         from .synth import pixel_mean_std_f32
         if mean is None or std is None:
             m, s = pixel_mean_std_f32()
@@ -270,16 +219,72 @@ class I3D8x8(_HipNetwork):
         return s.float().cpu().numpy() if as_numpy else s
 
 
+class I3D8x8(_HipNetwork):
+    """The plugin's network module (``module_to_build`` of the reference Classifier)."""
+
+    def __init__(self, clip_size: int = 32, imsize: int = 224, precision: str = "auto", crop_size: int = 224,
+                 streams: Optional[int] = None) -> None:
+        # the head pool is sized from DATA.CROP_SIZE=224 (defaults.py:277), not from imsize (SURVEY App. B);
+        # crop_size is only changed by tests that run a shrunken network
+        super().__init__(i3d_r50_spec(num_frames=clip_size, crop=crop_size), precision)
+        self.clip_size, self.imsize = clip_size, imsize
+        # streams = 2: a batch of >= split_min_batch clips runs as two half-batches on two HIP streams (two engines).  The forward
+        # alternates between MFMA-bound and HBM-bound launches; the launches of two independent half-batches can fill some of each
+        # other's idle time.  Measured with the round-2 kernels: B=16 +2-3 %, B=32 +5 %; with the round-3 / round-4 kernels (whole
+        # rounds of persistent workgroups per launch) it is a LOSS at B=16 (driver's round-3 line: 3 047 against 3 121 clips/s) -
+        # DESIGN.md 7.  Off by default (1): opt in with the argument or AF_MI355X_STREAMS=2, and measure.
+        self.streams = int(streams if streams is not None else os.environ.get("AF_MI355X_STREAMS", "1"))
+        self.split_min_batch = 16
+        self._side = {}
+
+    def _run(self, B, dims, dev, runner):
+        """the base class's run, or (streams = 2, a large batch) two half-batches on two HIP streams"""
+        ns = self.streams if (self.streams > 1 and B >= self.split_min_batch) else 1
+        if ns == 1:
+            return super()._run(B, dims, dev, runner)
+        dtype = self._select_dtype()
+        cur = torch.cuda.current_stream(dev)
+        if (str(dev), ns) not in self._side:
+            self._side[(str(dev), ns)] = [torch.cuda.Stream(dev) for _ in range(ns)]
+        side = self._side[(str(dev), ns)]
+        parts = []
+        for slot in range(ns):
+            lo, hi = slot * B // ns, (slot + 1) * B // ns
+            side[slot].wait_stream(cur)                       # the caller's input is ready
+            with torch.cuda.stream(side[slot]):
+                eng = self._engine(dtype, hi - lo, dims, dev, slot=slot)
+                logits, pooled = runner(eng, lo, hi)
+                parts.append((eng, logits, pooled, eng.scores))
+        for s in side:
+            cur.wait_stream(s)
+        cat = lambda i: None if parts[0][i] is None else torch.cat([p[i] for p in parts])
+        return parts[0][0], cat(1), cat(2), cat(3)
+
+    def forward(self, images, noise=None, has_mask=None, freeze_backbone=False, return_feature_maps=False, return_scores=False):
+        assert not freeze_backbone
+        x = self._check_input(images)
+        B, _, T, H, W = x.shape
+        if B == 0:                                   # an empty batch is an empty answer (no launch)
+            return {"final_output": x.new_zeros((0, self.spec.num_classes))}
+        with torch.cuda.device(x.device):
+            eng, logits, pooled, scores = self._run(B, (T, H, W), x.device, lambda e, lo, hi: e.run_f32(x[lo:hi]))
+            out = {"final_output": self._finish(eng, logits, pooled, B)}
+            if return_scores:                        # not a reference argument: the callers' sigmoid, from the head kernel
+                out["scores"] = self._scores_of(eng, scores, B)
+        return out
+
+
 class LiveScorer:
     """One tracked face of a live call: ``score = scorer(aligned_clip_u8)`` = ``ClassifierSvc.infer_scores`` for a single window
     (test/af_realtime.py:75-96), with the ~50 launches of the B = 1 forward recorded ONCE into a HIP graph and replayed per window:
     after a second of idle between windows the host side runs cold and issuing those launches one by one (0.5 - 0.9 ms) was on the
     critical path of enqueue -> score; a replay is one call.  ``scorer.clip`` is the static (1, T, H, W, 3) uint8 input - the
     aligner can write the window straight into it (``StreamingCropAligner.align_last(n, out=scorer.clip[0])``) - and the returned
-    scores are those of ``infer_scores`` bit for bit (same kernels, same order)."""
+    scores are those of ``infer_scores`` bit for bit (same kernels, same order).  ``network``: any of ``I3D8x8`` / ``FtcnTT8x8`` /
+    ``SlowFast8x8`` (or a ``Classifier`` around one); the graph is captured from that network's ``forward_clips_u8``."""
 
-    def __init__(self, network: "I3D8x8", clip_size: int = 32, crop: int = 224):
-        self.network = network
+    def __init__(self, network: "_HipNetwork", clip_size: int = 32, crop: int = 224):
+        self.network = network = getattr(network, "network", network)
         dev = next(network.parameters()).device
         self.clip = torch.zeros((1, clip_size, crop, crop, 3), dtype=torch.uint8, device=dev)
         with torch.inference_mode(), torch.cuda.device(dev):
@@ -321,13 +326,14 @@ class SlowFast8x8(_HipNetwork):
 
     ``forward(inputs)``: ``inputs = [slow, fast]`` exactly like ``SlowFast.forward`` (slow = T/alpha frames, fast = T
     frames, both (B,3,t,H,W)); a single (B,3,T,H,W) clip is also accepted and read with a frame stride of alpha for
-    the Slow pathway."""
+    the Slow pathway.  ``forward_clips_u8`` takes one full-rate uint8 clip (B,T,H,W,3) the same way: one pack launch writes
+    both pathway inputs; ``return_pooled`` is the (B, 2304) concatenated [slow | fast] row the head's Linear consumes."""
 
     def __init__(self, clip_size: int = 32, precision: str = "auto", crop_size: int = 224, alpha: int = 8) -> None:
         super().__init__(slowfast_r50_spec(num_frames=clip_size, crop=crop_size, alpha=alpha), precision)
         self.clip_size = clip_size
 
-    def forward(self, inputs, bboxes=None):
+    def forward(self, inputs, bboxes=None, return_scores=False):
         xs = [inputs] if isinstance(inputs, torch.Tensor) else list(inputs)
         if len(xs) not in (1, 2):
             raise ValueError("SlowFast takes [slow, fast] (or one clip)")
@@ -335,10 +341,11 @@ class SlowFast8x8(_HipNetwork):
         fast = xs[-1]
         B, _, T, H, W = fast.shape
         with torch.cuda.device(fast.device):
-            eng = self._engine(self._select_dtype(), B, (T, H, W), fast.device)
-            logits, pooled = eng.run_f32(*xs)
-            pred = self._finish(eng, logits, pooled, B)
-        return {"final_output": pred}
+            eng, logits, pooled, scores = self._run(B, (T, H, W), fast.device, lambda e, lo, hi: e.run_f32(*xs))
+            out = {"final_output": self._finish(eng, logits, pooled, B)}
+            if return_scores:
+                out["scores"] = self._scores_of(eng, scores, B)
+        return out
 
 
 class _TokenParams(_Node):
@@ -355,7 +362,8 @@ class FtcnTT8x8(_HipNetwork):
     with ``setting/ftcn_tt.yaml``; altfreezing/model/classifier/i3d_temporal_var_fix_dropout_tt_cfg.py:290-359):
     I3D-R50 trunk with every spatial kernel shrunk to 1x1 (strides replaced by 2x2 max-pools after the BN), s5
     dropped, and a one-layer TimeTransformer over 16 per-frame tokens + class token as the head.  Same parameter
-    names as the reference module (the BNs followed by a pool live under ``<bn>.0``), same forward contract."""
+    names as the reference module (the BNs followed by a pool live under ``<bn>.0``), same forward contract.
+    ``forward_clips_u8(..., return_pooled=True)`` gives the (B, 1024) LayerNorm'ed class token that ``mlp_head``'s Linear consumes."""
 
     def __init__(self, clip_size: int = 32, imsize: int = 224, precision: str = "auto", crop_size: int = 224) -> None:
         super().__init__(ftcn_tt_spec(num_frames=clip_size, crop=crop_size), precision)
@@ -378,17 +386,18 @@ class FtcnTT8x8(_HipNetwork):
     def _head_linear(self) -> nn.Linear:
         return getattr(self.resnet.head.time_T.mlp_head, "1")
 
-    def forward(self, images, noise=None, has_mask=None, freeze_backbone=False, return_feature_maps=False):
+    def forward(self, images, noise=None, has_mask=None, freeze_backbone=False, return_feature_maps=False, return_scores=False):
         assert not freeze_backbone
         x = self._check_input(images)
         B, _, T, H, W = x.shape
         if B == 0:
             return {"final_output": x.new_zeros((0, self.spec.num_classes))}
         with torch.cuda.device(x.device):
-            eng = self._engine(self._select_dtype(), B, (T, H, W), x.device)
-            logits, pooled = eng.run_f32(x)
-            pred = self._finish(eng, logits, pooled, B)
-        return {"final_output": pred}
+            eng, logits, pooled, scores = self._run(B, (T, H, W), x.device, lambda e, lo, hi: e.run_f32(x))
+            out = {"final_output": self._finish(eng, logits, pooled, B)}
+            if return_scores:
+                out["scores"] = self._scores_of(eng, scores, B)
+        return out
 
 
 def _unwrap_checkpoint(saved):

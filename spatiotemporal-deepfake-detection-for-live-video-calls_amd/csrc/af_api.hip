@@ -75,6 +75,11 @@ static int run_one(const af_op& op, hipStream_t s) {
         case AF_OP_PACK3_U8:
             return af_pack_input_u8_rgb3((const uint8_t*)op.in, op.conv.n, op.conv.t, op.conv.h, op.conv.w, op.mean, op.std_,
                                          op.conv.dtype, op.out, s);
+        case AF_OP_PACK_PATHWAYS_U8:   /* out = the Slow input, aux = the Fast input, x_sub = alpha, pack_rgb3: bit 0 Slow, bit 1 Fast */
+            return af_pack_input_u8_pathways((const uint8_t*)op.in, op.conv.n, op.conv.t, op.conv.h, op.conv.w, op.mean, op.std_,
+                                             op.x_sub, op.conv.dtype, op.out, op.pack_rgb3 & 1, op.aux, (op.pack_rgb3 >> 1) & 1, s);
+        case AF_OP_NOP:
+            return AF_OK;
         case AF_OP_TSTEM:
             return af_tstem_conv_bn_pool_relu(&op.conv, op.in, op.weight, op.scale, op.shift, op.out, s);
         case AF_OP_TSTEM_POOL3:

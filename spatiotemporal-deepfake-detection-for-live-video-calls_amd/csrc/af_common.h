@@ -299,6 +299,8 @@ int timed(const char* who, hipStream_t s, int n, float* ms, F fn) {
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int dtype_size(int dt) { return dt == AF_F32 ? 4 : 2; }
 static inline bool dtype_ok(int dt) { return dt == AF_F32 || dt == AF_BF16 || dt == AF_F16; }
+// bytes of one row of the rgb3 stem input: (w + halo) pixels of 3 x 16 bit, rounded up to 16 (af_stem3.hip reads it, af_pack*.hip write it)
+static inline int rgb3_row_bytes(int w) { return ((w + AF_STEM_PAD_W_TOTAL) * 6 + 15) & ~15; }
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

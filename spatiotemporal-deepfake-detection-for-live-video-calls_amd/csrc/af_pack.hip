@@ -84,6 +84,82 @@ struct SrcU8 {
     }
 };
 
+// ---- SlowFast: both pathway inputs out of ONE read of the uint8 clip (af_pack_input_u8_pathways) ----
+// A destination: rows [n][frames + 2 PAD_T][h + 2 PAD_H] of row_bytes each, pixel x of a row at byte (x + PAD_W_LEFT) * pixel size;
+// pixel = 4 channels of DT (the padded layout of pack_input_kernel) or, rgb3, 3 x 16 bit (that of pack_input3_kernel, af_stem3.hip)
+struct PackDst {
+    char* p; long long row_bytes; int frames, rgb3;
+    __device__ char* row(long long b, int z, int y, int h) const {
+        return p + ((b * (frames + 2 * AF_STEM_PAD_T) + z + AF_STEM_PAD_T) * (h + 2 * AF_STEM_PAD_H) + y + AF_STEM_PAD_H) * row_bytes;
+    }
+};
+struct PathwaysArgs { const uint8_t* clips; int n, t, h, w, alpha; float mean[3], stdv[3]; PackDst fast, slow; };
+
+// NPX normalised pixels x0 .. x0 + NPX - 1 of one row.  NPX = 8 (x0 % 8 == 0): the 48 bytes of an rgb3 run start 18 bytes behind a
+// 16-byte boundary, so they leave as 2 + 4 + 8 + 16 + 16 + 2 bytes, every store aligned to its own size; 4 channels: one 8- or
+// 16-byte store per pixel, as pack_input_kernel writes them
+template <int DT, int NPX>
+__device__ __forceinline__ void store_pixels(const PackDst& d, char* row, int x0, const float (&v)[NPX][3]) {
+    typedef typename Elem<DT>::type elem_t;
+    constexpr int ES = sizeof(elem_t);
+    if constexpr (DT != AF_F32) {
+        if (d.rgb3) {
+            char* o = row + (x0 + AF_STEM_PAD_W_LEFT) * 6;
+            elem_t e[NPX * 3];
+#pragma unroll
+            for (int j = 0; j < NPX * 3; ++j) e[j] = Elem<DT>::from_f32(v[j / 3][j % 3]);
+            if constexpr (NPX == 8) {
+                typedef elem_t e2 __attribute__((ext_vector_type(2)));
+                typedef elem_t e4 __attribute__((ext_vector_type(4)));
+                typedef elem_t e8 __attribute__((ext_vector_type(8)));
+                *reinterpret_cast<elem_t*>(o) = e[0];
+                *reinterpret_cast<e2*>(o + 2) = e2{e[1], e[2]};
+                *reinterpret_cast<e4*>(o + 6) = e4{e[3], e[4], e[5], e[6]};
+                *reinterpret_cast<e8*>(o + 14) = e8{e[7], e[8], e[9], e[10], e[11], e[12], e[13], e[14]};
+                *reinterpret_cast<e8*>(o + 30) = e8{e[15], e[16], e[17], e[18], e[19], e[20], e[21], e[22]};
+                *reinterpret_cast<elem_t*>(o + 46) = e[23];
+            } else {
+#pragma unroll
+                for (int j = 0; j < NPX * 3; ++j) reinterpret_cast<elem_t*>(o)[j] = e[j];
+            }
+            return;
+        }
+    }
+    char* o = row + (long long)(x0 + AF_STEM_PAD_W_LEFT) * 4 * ES;
+#pragma unroll
+    for (int k = 0; k < NPX; ++k) Vec4<DT>::store(o + k * 4 * ES, f32x4{v[k][0], v[k][1], v[k][2], 0.f});
+}
+
+// One thread per run of NPX pixels of a clip row: the run is loaded once (VEC: 24 bytes as three 8-byte loads - w % 8 == 0 and an
+// 8-byte aligned clip make every run of every row aligned; otherwise a pixel's 3 bytes), normalised once and stored into the Fast
+// input and, for every alpha-th frame, into the Slow input as well.  Only interior cells are written; no LDS.
+template <int DT, bool VEC>
+__global__ void __launch_bounds__(256) pack_pathways_kernel(PathwaysArgs a) {
+    constexpr int NPX = VEC ? 8 : 1;
+    const int runs = a.w / NPX;
+    const long long total = (long long)a.n * a.t * a.h * runs;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const int x0 = (int)(idx % runs) * NPX; const long long r = idx / runs;       // r: row of the clip tensor
+        const int y = (int)(r % a.h); const long long f = r / a.h;
+        const int z = (int)(f % a.t); const long long b = f / a.t;
+        const uint8_t* src = a.clips + (r * a.w + x0) * 3;
+        float v[NPX][3];
+        if constexpr (VEC) {
+            const uint2 q0 = reinterpret_cast<const uint2*>(src)[0], q1 = reinterpret_cast<const uint2*>(src)[1],
+                        q2 = reinterpret_cast<const uint2*>(src)[2];
+            const unsigned wd[6] = {q0.x, q0.y, q1.x, q1.y, q2.x, q2.y};
+#pragma unroll
+            for (int j = 0; j < 24; ++j)
+                v[j / 3][j % 3] = ((float)((wd[j >> 2] >> (8 * (j & 3))) & 0xffu) - a.mean[j % 3]) / a.stdv[j % 3];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[0][c] = ((float)src[c] - a.mean[c]) / a.stdv[c];
+        }
+        store_pixels<DT, NPX>(a.fast, a.fast.row(b, z, y, a.h), x0, v);
+        if (z % a.alpha == 0) store_pixels<DT, NPX>(a.slow, a.slow.row(b, z / a.alpha, y, a.h), x0, v);
+    }
+}
+
 static inline unsigned grid_for(long long total, int block) { return (unsigned)((total + block - 1) / block); }
 
 }  // namespace af
@@ -186,4 +262,38 @@ extern "C" int af_pack_input_u8(const uint8_t* clips, int n, int t, int h, int w
     src.p = clips; src.t = t; src.h = h; src.w = w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = mean[i]; src.stdv[i] = std_[i]; }
     return launch_pack_input(src, n, t, h, w, dtype, stem_in, (hipStream_t)stream);
+}
+
+static PackDst pack_dst(void* p, int frames, int w, int layout, int dtype) {
+    const bool rgb3 = layout == AF_PACK_RGB3;
+    return PackDst{(char*)p, rgb3 ? (long long)rgb3_row_bytes(w) : (long long)(w + AF_STEM_PAD_W_TOTAL) * AF_STEM_CPAD * dtype_size(dtype),
+                   frames, rgb3 ? 1 : 0};
+}
+
+extern "C" int af_pack_input_u8_pathways(const uint8_t* clips, int n, int t, int h, int w, const float mean[3], const float std_[3],
+                                         int alpha, int dtype, void* slow_in, int slow_layout, void* fast_in, int fast_layout,
+                                         void* stream) {
+    AF_REQUIRE(clips && slow_in && fast_in && mean && std_, "pack_input_u8_pathways: null pointer");
+    AF_REQUIRE(dtype_ok(dtype) && n > 0 && t > 0 && h > 0 && w > 0 && alpha > 0, "pack_input_u8_pathways: bad argument");
+    AF_REQUIRE(t % alpha == 0, "pack_input_u8_pathways: %d frames are not a multiple of alpha = %d", t, alpha);
+    for (int layout : {slow_layout, fast_layout}) {
+        AF_REQUIRE(layout == AF_PACK_C4 || layout == AF_PACK_RGB3, "pack_input_u8_pathways: unknown layout %d", layout);
+        AF_REQUIRE(layout == AF_PACK_C4 || dtype != AF_F32, "pack_input_u8_pathways: the rgb3 layout is 16-bit only");
+    }
+    AF_REQUIRE(aligned16(slow_in) && aligned16(fast_in), "pack_input_u8_pathways: outputs must be 16-byte aligned");
+    PathwaysArgs a;
+    a.clips = clips; a.n = n; a.t = t; a.h = h; a.w = w; a.alpha = alpha;
+    for (int i = 0; i < 3; ++i) { a.mean[i] = mean[i]; a.stdv[i] = std_[i]; }
+    a.fast = pack_dst(fast_in, t, w, fast_layout, dtype);
+    a.slow = pack_dst(slow_in, t / alpha, w, slow_layout, dtype);
+    const bool vec = w % 8 == 0 && (reinterpret_cast<uintptr_t>(clips) & 7u) == 0;
+    const long long blocks = ((long long)n * t * h * (vec ? w / 8 : w) + 255) / 256, cap = (long long)device_cus() * 8;
+    dim3 g((unsigned)(blocks < cap ? blocks : cap)), b(256);
+    hipStream_t s = (hipStream_t)stream;
+    with_dtype(dtype, [&](auto dt) {
+        if (vec) hipLaunchKernelGGL((pack_pathways_kernel<decltype(dt)::value, true>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((pack_pathways_kernel<decltype(dt)::value, false>), g, b, 0, s, a);
+    });
+    AF_CHECK_LAUNCH("pack_pathways_kernel");
+    return AF_OK;
 }

@@ -290,8 +290,6 @@ struct Src3U8 {
     }
 };
 
-static inline int rgb3_row_bytes(int w) { return ((w + AF_STEM_PAD_W_TOTAL) * 6 + 15) & ~15; }
-
 template <int DT, int KT, bool PW>
 static int launch_stem3_pw(const Stem3Args& a, hipStream_t stream) {
     constexpr int NBLK = (KT * 21 + 3) / 4;

@@ -351,7 +351,8 @@ class DualEncoderRGB(nn.Module):
     branches pool with ``BranchEncoder``'s default ``pool_tau = 0.7``.  ``key_padding_mask`` (True = padding) must be a
     prefix mask (what ``lengths_to_mask`` produces, :87-89): the kernels take the count of valid frames.
     With ``rgb_backbone`` = an ``I3D8x8`` / ``Classifier`` of this package and ``rgb_from_features=False``, ``V`` is a uint8
-    clip batch (B,T,H,W,3) and the pooled feature comes from the AltFreezing engine (one window per sample)."""
+    clip batch (B,T,H,W,3) and the pooled feature comes from the AltFreezing engine (one window per sample).  A backbone whose
+    pooled feature is not 2048 wide (``FtcnTT8x8``: 1024, ``SlowFast8x8``: 2304) is refused with ``ValueError`` at construction."""
 
     MAX_FRAMES = 16
 
@@ -370,6 +371,14 @@ class DualEncoderRGB(nn.Module):
         self.lmk_enc = _Branch(lmk_dim, self.spec)
         self.vis_dim = int(vis_dim)
         self.rgb = _Identity()                                        # AltFreezingRGBEncoder: no parameters of its own here
+        if rgb_backbone is not None:
+            # rgb_proj multiplies the backbone's pooled row: only the 2048-wide AltFreezing (I3D) feature fits it
+            net = getattr(rgb_backbone, "network", rgb_backbone)
+            width = net._head_linear().in_features if hasattr(net, "_head_linear") else None
+            if width != 2048 or self.vis_dim != 2048:
+                raise ValueError("rgb_backbone must hand rgb_proj the 2048-wide pooled AltFreezing feature (an af_mi355x I3D8x8 / "
+                                 "Classifier, vis_dim = 2048): got %s with a %s-wide feature and vis_dim = %d"
+                                 % (type(net).__name__, width, self.vis_dim))
         self.rgb_backbone = [rgb_backbone]                            # not a submodule: frozen and owned by the caller
         self.rgb_from_features = bool(rgb_from_features)
         self.rgb_proj = nn.Linear(vis_dim, d_model, bias=False)

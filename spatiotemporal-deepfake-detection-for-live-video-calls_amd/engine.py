@@ -510,7 +510,9 @@ class Engine:
         # inputs that feed a K-packed stem take the 3-channel layout (the single input of the i3d engine; SlowFast: the Slow one)
         r3 = plan.rgb3_inputs | ({self.inputs[0][0]} if self.rgb3 else set())
         self.k_pack_f32 = [_lib.AF_OP_PACK3_F32 if name in r3 else _lib.AF_OP_PACK_F32 for name, _, _ in self.inputs]
-        self.k_pack_u8 = _lib.AF_OP_PACK3_U8 if self.rgb3 else _lib.AF_OP_PACK_U8
+        # a uint8 run: the one input's pack op, or (SlowFast) one launch that writes both inputs in slot 0 and nothing in slot 1
+        self.k_pack_u8 = ([_lib.AF_OP_PACK3_U8 if self.rgb3 else _lib.AF_OP_PACK_U8] if len(self.inputs) == 1
+                          else [_lib.AF_OP_PACK_PATHWAYS_U8, _lib.AF_OP_NOP])
         for name, dims, _ in self.inputs:                           # padded stem inputs: halos stay zero forever
             nbytes = (lib.af_stem_input_bytes_rgb3 if name in r3 else lib.af_stem_input_bytes)(batch, dims[0], dims[1], dims[2], self.code)
             self.buf[name] = torch.zeros(nbytes // es, dtype=tdt, device=device)
@@ -534,6 +536,10 @@ class Engine:
             pk.out = self.buf[name].data_ptr()
             self.op_names.append("input_pack" if n_pack == 1 else "input_pack_" + name)
             self.op_macs.append(0)
+        if n_pack == 2:                      # what PACK_PATHWAYS_U8 reads besides the pack fields; the fp32 pack ops ignore them
+            pk = self.ops[0]
+            pk.aux, pk.x_sub = self.buf[self.inputs[1][0]].data_ptr(), self.inputs[0][2]
+            pk.pack_rgb3 = sum(1 << i for i, (name, _, _) in enumerate(self.inputs) if name in r3)
         for k, e in enumerate(plan.entries):
             op = self.ops[n_pack + k]
             if "src" in e:
@@ -781,6 +787,7 @@ class Engine:
             raise ValueError("inputs must be fp32 HIP tensors")
         pk = self.ops[i]
         pk.kind = self.k_pack_f32[i]
+        (pk.conv.t, pk.conv.h, pk.conv.w) = dims
         pk.in_ = x.data_ptr()
         st = list(x.stride())
         st[2] *= tstride
@@ -802,16 +809,17 @@ class Engine:
         return self.logits, self.pooled
 
     def run_u8(self, clips: torch.Tensor, mean, std):
-        """clips: (B,T,H,W,3) uint8 device tensor in caller layout; normalisation fused into the prologue."""
+        """clips: (B,T,H,W,3) uint8 device tensor in caller layout; normalisation fused into the prologue.  SlowFast: one
+        full-rate clip; the Slow input is every alpha-th frame of it, written by the same launch as the Fast input."""
         assert clips.dtype == torch.uint8 and clips.is_cuda
-        if len(self.inputs) != 1:
-            raise ValueError("the uint8 prologue is wired for single-input networks")
         B, T, H, W, Cc = clips.shape
         if (B, T, H, W, Cc) != (self.batch,) + self.in_dims + (3,) or not clips.is_contiguous():
             raise ValueError("expected contiguous uint8 clips (%d,%d,%d,%d,3)" % ((self.batch,) + self.in_dims))
+        for i, kind in enumerate(self.k_pack_u8):
+            self.ops[i].kind = kind
         pk = self.ops[0]
-        pk.kind = self.k_pack_u8
         pk.in_ = clips.data_ptr()
+        (pk.conv.t, pk.conv.h, pk.conv.w) = self.in_dims          # SlowFast: slot 0 describes the Slow input in an fp32 run
         for i in range(3):
             pk.mean[i], pk.std_[i] = float(mean[i]), float(std[i])
         check(lib.af_run_ops(self.ops, self.n_ops, _stream_ptr(self.device)), "af_run_ops")
