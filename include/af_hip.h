@@ -451,6 +451,11 @@ int64_t af_window_rects_table_bytes(int n_windows, int clip_size);
 int af_window_rects_plan_u8(const af_window_desc* windows, const af_frame_rect* rects, int n_windows, int clip_size, int size,
                             const af_frame_store* store, void* table, int64_t table_bytes, int32_t* bad_window, int32_t* bad_frame);
 int af_warp_affine_window_rects_u8(const void* store, const void* table, int n_windows, int clip_size, int size, void* out, void* stream);
+/* The same launch for a store whose pixels are B, G, R in memory (cv2.VideoCapture, a screen capture, what YuNet takes): the byte at
+ * row * row_pitch + col * 3 is B, and `out` is still R, G, B - the bytes af_warp_affine_window_rects_u8 writes for the store with
+ * every pixel's first and third byte exchanged.  Same table (af_window_rects_plan_u8 plans for both), same argument check, same
+ * reads; the exchange is a choice of which accumulated channel goes to which byte of the store.  (Added within ABI 6.) */
+int af_warp_affine_window_rects_bgr_u8(const void* store, const void* table, int n_windows, int clip_size, int size, void* out, void* stream);
 
 /* ---- whole-forward op list ------------------------------------------------------------ */
 

@@ -9,4 +9,7 @@ def __getattr__(name):
     if name in ("VideoScorer", "TrackScorer"):
         from . import evaluator
         return getattr(evaluator, name)
+    if name == "LiveCall":
+        from . import live
+        return live.LiveCall
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -281,12 +281,19 @@ class LiveScorer:
     critical path of enqueue -> score; a replay is one call.  ``scorer.clip`` is the static (1, T, H, W, 3) uint8 input - the
     aligner can write the window straight into it (``StreamingCropAligner.align_last(n, out=scorer.clip[0])``) - and the returned
     scores are those of ``infer_scores`` bit for bit (same kernels, same order).  ``network``: any of ``I3D8x8`` / ``FtcnTT8x8`` /
-    ``SlowFast8x8`` (or a ``Classifier`` around one); the graph is captured from that network's ``forward_clips_u8``."""
+    ``SlowFast8x8`` (or a ``Classifier`` around one); the graph is captured from that network's ``forward_clips_u8``.
+    ``batch``: the number of clips of the recorded forward (``live.LiveCall`` scores the windows that close together as one batch);
+    ``clip``: the static input to record on, a contiguous uint8 (batch, T, H, W, 3) tensor of the caller's (default: a new one)."""
 
-    def __init__(self, network: "_HipNetwork", clip_size: int = 32, crop: int = 224):
+    def __init__(self, network: "_HipNetwork", clip_size: int = 32, crop: int = 224, batch: int = 1, clip: Optional[torch.Tensor] = None):
         self.network = network = getattr(network, "network", network)
         dev = next(network.parameters()).device
-        self.clip = torch.zeros((1, clip_size, crop, crop, 3), dtype=torch.uint8, device=dev)
+        shape = (int(batch), clip_size, crop, crop, 3)
+        if clip is None:
+            clip = torch.zeros(shape, dtype=torch.uint8, device=dev)
+        elif clip.shape != shape or clip.dtype != torch.uint8 or not clip.is_contiguous() or clip.device != dev:
+            raise ValueError("LiveScorer: `clip` must be a contiguous uint8 %s tensor on %s" % (shape, dev))
+        self.clip = clip
         with torch.inference_mode(), torch.cuda.device(dev):
             for _ in range(2):                                          # engine construction, weight packing, kernel attributes
                 network.forward_clips_u8(self.clip, return_scores=True)
@@ -304,6 +311,16 @@ class LiveScorer:
         dev = self.clip.device
         with torch.cuda.device(dev):                  # (a multi-GPU process: the caller's current device may be another one)
             cur = torch.cuda.current_stream(dev)
+            self._host.copy_(self.replay(aligned_clip_u8, wait_for).float(), non_blocking=True)
+            cur.synchronize()
+        return self._host.numpy().copy()
+
+    def replay(self, aligned_clip_u8: Optional[torch.Tensor] = None, wait_for=None) -> torch.Tensor:
+        """``__call__`` without the read-back: enqueues the replay on the current stream and returns the graph's (batch,) score
+        tensor on the device, which the next replay overwrites."""
+        dev = self.clip.device
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
             if isinstance(wait_for, torch.cuda.Event):
                 cur.wait_event(wait_for)
             elif isinstance(wait_for, torch.cuda.Stream):
@@ -313,9 +330,7 @@ class LiveScorer:
             if aligned_clip_u8 is not None:
                 self.clip.copy_(aligned_clip_u8.reshape(self.clip.shape), non_blocking=True)
             self.graph.replay()
-            self._host.copy_(self._scores.float(), non_blocking=True)
-            cur.synchronize()
-        return self._host.numpy().copy()
+        return self._scores
 
 
 class SlowFast8x8(_HipNetwork):

@@ -97,6 +97,8 @@ static void invert_affine_cv(const double* tfm, double* inv) {
 // bytes (any value: 1 923 for a 641-wide frame; the 6-byte tap reads are unaligned in both forms).  The bytes around a rectangle
 // are the frame's other pixels, not padding: only the clamp of (row, column) into the rectangle together with the zero weight of
 // a tap outside it keeps them out of the result, and only the last rectangle of the store needs 3 readable bytes behind it.
+// The WindowRect form also comes for frames whose pixels are B, G, R in memory (what a capture API delivers): kBgr only chooses
+// which of the three accumulated channels goes to which byte of the R, G, B store - the reads and the arithmetic are the same.
 constexpr int WB_ROWS = 32, WB_THREADS = 256;
 constexpr int32_t WB_KIND_POOL = 0, WB_KIND_RECTS = 1;           // WindowTableHeader::kind
 struct WindowTableHeader { int32_t n_windows, clip_size, size, kind; };
@@ -114,7 +116,7 @@ static inline int64_t window_table_bytes(int n_windows, int clip_size, size_t it
     return (int64_t)sizeof(WindowTableHeader) + (int64_t)n_windows * sizeof(WindowXform) + (int64_t)n_windows * clip_size * (int64_t)item;
 }
 
-template <typename Item>
+template <typename Item, bool kBgr = false>
 __global__ __launch_bounds__(WB_THREADS) void warp_affine_windows_kernel(const unsigned char* __restrict__ pool, const unsigned char* __restrict__ table,
                                                                          unsigned char* __restrict__ out, int n_windows, int clip_size, int size,
                                                                          int tiles) {
@@ -173,7 +175,8 @@ __global__ __launch_bounds__(WB_THREADS) void warp_affine_windows_kernel(const u
             const int c1 = w00 * (int)((a4 >> 8) & 255) + w01 * (int)(a2 & 255) + w10 * (int)((b4 >> 8) & 255) + w11 * (int)(b2 & 255);
             const int c2 = w00 * (int)((a4 >> 16) & 255) + w01 * (int)(a2 >> 8) + w10 * (int)((b4 >> 16) & 255) + w11 * (int)(b2 >> 8);
             const int v0 = (c0 + (1 << 14)) >> 15, v1 = (c1 + (1 << 14)) >> 15, v2 = (c2 + (1 << 14)) >> 15;
-            px[j] = (unsigned)(v0 > 255 ? 255 : v0) | (unsigned)(v1 > 255 ? 255 : v1) << 8 | (unsigned)(v2 > 255 ? 255 : v2) << 16;
+            const int vr = kBgr ? v2 : v0, vb = kBgr ? v0 : v2;            // source byte 0 is B in a BGR frame; the store is R, G, B
+            px[j] = (unsigned)(vr > 255 ? 255 : vr) | (unsigned)(v1 > 255 ? 255 : v1) << 8 | (unsigned)(vb > 255 ? 255 : vb) << 16;
         }
         uint3 o;                                                      // 4 x RGB = 3 dwords (size % 4 == 0: every quad is dword-aligned)
         o.x = px[0] | px[1] << 24;
@@ -230,7 +233,7 @@ extern "C" int af_window_batch_plan_u8(const af_window_desc* windows, const af_a
 }
 
 namespace af {
-template <typename Item>
+template <typename Item, bool kBgr = false>
 static int launch_window_warp(const char* what, const void* src, const void* table, int n_windows, int clip_size, int size, void* out, void* stream) {
     AF_REQUIRE(src && table && out, "%s: null argument", what);
     AF_REQUIRE(n_windows > 0 && n_windows <= AF_WINDOW_MAX_BATCH && clip_size > 0 && clip_size <= AF_ALIGN_MAX_FRAMES,
@@ -239,7 +242,7 @@ static int launch_window_warp(const char* what, const void* src, const void* tab
     AF_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)table & 7) == 0, "%s: out must be 4-byte, table 8-byte aligned", what);
     const int tiles = (size + WB_ROWS - 1) / WB_ROWS;
     const unsigned grid = (unsigned)(n_windows * clip_size * tiles);
-    hipLaunchKernelGGL(warp_affine_windows_kernel<Item>, dim3(grid), dim3(WB_THREADS), 0, (hipStream_t)stream, (const unsigned char*)src,
+    hipLaunchKernelGGL((warp_affine_windows_kernel<Item, kBgr>), dim3(grid), dim3(WB_THREADS), 0, (hipStream_t)stream, (const unsigned char*)src,
                        (const unsigned char*)table, (unsigned char*)out, n_windows, clip_size, size, tiles);
     AF_CHECK_LAUNCH("warp_affine_windows_kernel");
     return AF_OK;
@@ -313,6 +316,11 @@ extern "C" int af_window_rects_plan_u8(const af_window_desc* windows, const af_f
 extern "C" int af_warp_affine_window_rects_u8(const void* store, const void* table, int n_windows, int clip_size, int size, void* out,
                                               void* stream) {
     return af::launch_window_warp<af::WindowRect>("warp_affine_window_rects", store, table, n_windows, clip_size, size, out, stream);
+}
+
+extern "C" int af_warp_affine_window_rects_bgr_u8(const void* store, const void* table, int n_windows, int clip_size, int size, void* out,
+                                                  void* stream) {
+    return af::launch_window_warp<af::WindowRect, true>("warp_affine_window_rects_bgr", store, table, n_windows, clip_size, size, out, stream);
 }
 
 extern "C" int af_warp_affine_clip_u8(const void* crops, const af_align_frame* frames, int n_frames, int canvas_h, int canvas_w,

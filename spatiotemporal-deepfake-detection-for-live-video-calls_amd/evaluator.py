@@ -258,6 +258,7 @@ class _WindowScorer:
     records of ``_ITEM``, and ``_TABLE_BYTES`` / ``_PLAN`` / ``_LAUNCH`` name the C entry points of its form of the warp."""
 
     _ITEM, _TABLE_BYTES, _PLAN, _LAUNCH = None, None, None, None
+    _CLIP_BUFFERS = 2         # one batch is warped while the forward of the one before reads its own
 
     def __init__(self, network, clip_size: int = 32, size: int = 224, batch: int = 16, device: Optional[torch.device] = None,
                  pool_bytes: int = 512 << 20):
@@ -305,7 +306,7 @@ class _WindowScorer:
         if self._clips is None:
             with torch.inference_mode(False):                     # buffers that outlive a caller's inference_mode block stay writable
                 shape = (self.batch, self.clip_size, self.size, self.size, 3)
-                self._clips = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2)]
+                self._clips = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(self._CLIP_BUFFERS)]
                 # tables: pinned host + device twin + the event behind the copy out of the pinned one (the host rewrites a slot
                 # only after that copy has left it).  Three slots: the host runs up to two batches ahead of the device.
                 self._tables = [[torch.empty(self.table_bytes, dtype=torch.uint8, pin_memory=True),
@@ -342,6 +343,12 @@ class _WindowScorer:
         diff = boxes[:, :2] - left_top[None]
         tfm, _ = estimate_batch_transform(five + diff[:, None, :], self.std_points)
         return tfm, int(h), int(w), diff.astype(np.int64)
+
+    def _padded(self, track, windows, first: int, n: int, run: int):
+        """window numbers and fits of one forward of ``partition``: windows [first, first + n), the last one repeated up to `run`"""
+        ids = list(range(first, first + n)) + [first + n - 1] * (run - n)
+        fits = [self._fit(track, windows[k]) for k in ids[:n]]
+        return ids, fits + [fits[-1]] * (run - n)
 
     def _warp(self, track: _Track, windows, offs: np.ndarray, first_frame: int, out: torch.Tensor, fits=None):
         """table of one batch of windows (index lists into the track) -> pinned slot -> device; one launch into `out`"""
@@ -429,10 +436,8 @@ class _WindowScorer:
             # kernels, so the scores would otherwise move with the cuts): a batch that straddles a cut is warped in two launches,
             # one before and one after the next segment's upload, into the same clip buffer
             for turn, (first, n, run) in enumerate(self.partition(len(windows))):
-                ids = list(range(first, first + n)) + [first + n - 1] * (run - n)
-                fits = [self._fit(track, windows[k]) for k in ids[:n]]
-                fits += [fits[-1]] * (run - n)
-                buf = clips[turn % 2][:run]
+                ids, fits = self._padded(track, windows, first, n, run)
+                buf = clips[turn % len(clips)][:run]
                 a = 0
                 while a < run:
                     b = a
