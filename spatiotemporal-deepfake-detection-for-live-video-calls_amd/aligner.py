@@ -18,13 +18,12 @@ cv2 itself its parity is unpinned (cv2 is absent from the build image, the refer
 aligned frame).  There is no CPU fallback: without the HIP library the call fails.
 """
 import ctypes as C
-import os
-import threading
-from concurrent.futures import ThreadPoolExecutor
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
+
+from ._staging import PinnedRing, crop_rect, cuda_device, is_crop, stage_rects
 
 STD_POINTS_317 = np.array([[85.82991, 115.7792], [169.0532, 114.3381], [127.574, 167.0006],
                            [90.6964, 204.7014], [167.3069, 203.3733]]) + 30.0            # warp_for_xray.py:532-545
@@ -70,53 +69,21 @@ def estimate_batch_transform(all_src_pts, tgt_pts: np.ndarray):
     return trans[:, 0:2].T, trans
 
 
-class _StagingRing:
-    """persistent pinned host buffers + their device twins, used round-robin: a slot is rewritten only after the event
-    recorded behind its last consumer (the warp launch) has completed, so neither the asynchronous copy nor the kernel can
-    see a buffer change under them; `slots` clips may be in flight."""
-
-    def __init__(self, slots: int = 3):
-        self.host = [None] * slots
-        self.dev = [None] * slots
-        self.done = [None] * slots
-        self.next = 0
-        self.lock = threading.Lock()
-
-    def acquire(self, nbytes: int, dev) -> int:
-        with self.lock:
-            k = self.next
-            self.next = (k + 1) % len(self.host)
-        if self.done[k] is not None:
-            self.done[k].synchronize()
-        if self.host[k] is None or self.host[k].numel() < nbytes or self.dev[k].device != dev:
-            cap = max(nbytes + nbytes // 4, 1 << 20)
-            self.host[k] = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
-            self.dev[k] = torch.empty(cap, dtype=torch.uint8, device=dev)
-        return k
+def fit_window(boxes: np.ndarray, five: np.ndarray, std_points: np.ndarray):
+    """``(tfm, trans, h, w, diff)`` of the frames of one clip or window (faster_crop_align_xray.py:29-50): the canvas ``w`` x ``h``
+    all crops are pasted on, every crop's paste offset ``diff`` on it, and the similarity fitted over the five points of all
+    frames in canvas coordinates.  ``boxes`` (T, 4) and ``five`` (T, 5, 2) are relative to each frame's crop."""
+    left_top = boxes[:, :2].min(0)
+    w, h = boxes[:, 2:].max(0) - left_top
+    diff = boxes[:, :2] - left_top[None]
+    tfm, trans = estimate_batch_transform(five + diff[:, None, :], std_points)
+    return tfm, trans, h, w, diff
 
 
-# also cut the COLUMNS the warp cannot sample (rows are always cut)?  Measured on one box with the C staging copy: rows only 1 448
-# clips/s host-inclusive, rows + columns 1 020-1 100 - 22 % fewer bytes, but 8 000 short strided memcpys per clip run far below the
-# rate of 32 long ones.  Off; AF_ALIGN_COLS=1 switches it on for A/B runs.
-_CLIP_COLUMNS = os.environ.get("AF_ALIGN_COLS", "0") == "1"
-_PLAN_IN_C = os.environ.get("AF_ALIGN_PLAN", "1") == "1"        # 0: the per-frame planning in Python (round 3), for A/B runs
-_COPY_THREADS = 2          # measured on the MI355X host: 1 thread 45 GB/s, 2 threads 72 GB/s, 4+ slower (memory-bound copies)
-_copy_pool = None
-
-
-def _pool():
-    global _copy_pool
-    if _copy_pool is None:
-        _copy_pool = ThreadPoolExecutor(max_workers=_COPY_THREADS, thread_name_prefix="af-align-stage")
-    return _copy_pool
-
-
-def _copy_group(pairs):
-    for dst, im in pairs:
-        if im.flags.c_contiguous:
-            np.copyto(dst, im.reshape(-1))
-        else:                                    # a column-clipped view: one strided copy, row by row, no temporary
-            np.copyto(dst.reshape(im.shape), im)
+def canvas_misfit(frame: int, iw: int, ih: int, x: int, y: int, w: int, h: int, window: Optional[int] = None):
+    """numpy refuses ``new_image[y:y+ih, x:x+iw] = image`` (faster_crop_align_xray.py:83) for a crop that sticks out of the canvas"""
+    where = "frame %d" % frame if window is None else "window %d frame %d" % (window, frame)
+    raise ValueError("aligner: %s (%dx%d at %d,%d) does not fit the %dx%d canvas" % (where, iw, ih, x, y, w, h))
 
 
 class FasterCropAlignXRay:
@@ -130,22 +97,16 @@ class FasterCropAlignXRay:
         self.std_points = STD_POINTS_256 * size / 256.0
         self.return_ldm5 = return_ldm5
         self.device = device
-        self._ring = _StagingRing()
+        self._ring = PinnedRing(min_bytes=1 << 20, headroom=True)
 
     def __call__(self, landmarks, images: Optional[Sequence[np.ndarray]] = None, jitter: bool = False, device_output: bool = False):
         landmarks = [lm[:4] for lm in landmarks]
         boxes = np.array([box for _, _, _, box in landmarks])
         five = np.array([l5 for _, l5, _, _ in landmarks])
         l68 = np.array([l for _, _, l, _ in landmarks])
-        left_top = boxes[:, :2].min(0)
-        w, h = boxes[:, 2:].max(0) - left_top                      # the canvas all crops are pasted on
-        diff = boxes[:, :2] - left_top[None]
-        five_c, l68_c = five + diff[:, None, :], l68 + diff[:, None, :]
-        fit_pts = five_c.copy()
-        if jitter:
-            fit_pts += np.random.uniform(-4, 4, fit_pts.shape)
-        tfm, trans = estimate_batch_transform(fit_pts, self.std_points)
-        t68, t5 = _apply(trans, l68_c), _apply(trans, five_c)
+        fit_pts = five + np.random.uniform(-4, 4, five.shape) if jitter else five
+        tfm, trans, h, w, diff = fit_window(boxes, fit_pts, self.std_points)
+        t68, t5 = _apply(trans, l68 + diff[:, None, :]), _apply(trans, five + diff[:, None, :])
         if images is None:
             return (t5, t68) if self.return_ldm5 else t68
         aligned = self.warp_clip(images, diff, int(h), int(w), tfm)
@@ -154,59 +115,28 @@ class FasterCropAlignXRay:
         return (t5, t68, aligned) if self.return_ldm5 else (t68, aligned)
 
     def warp_clip(self, images: Sequence[np.ndarray], diff: np.ndarray, h: int, w: int, tfm: np.ndarray) -> torch.Tensor:
-        """the ``process_single`` loop (:75-88) for the whole clip: upload the crops, one launch per <= 64 frames.  Everything
-        is enqueued on the current stream and the call returns without synchronising (the staging slot is protected by an
-        event, see _StagingRing); `out` is valid for stream-ordered consumers, `.cpu()` waits for it."""
-        dev = self.device or torch.device("cuda", torch.cuda.current_device())
-        dev = torch.device(dev)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        out = torch.empty((len(images), self.image_size, self.image_size, 3), dtype=torch.uint8, device=dev)
-        if len(images) == 0:
-            return out
-        if not _CLIP_COLUMNS and _PLAN_IN_C:
-            return self._warp_clip_planned(images, diff, h, w, tfm, out, dev)
-        # only the part of a crop the warp can touch is uploaded: the destination square maps to a parallelogram of the canvas;
-        # a crop cut to rows [r0, r1) x columns [c0, c1) is the same picture as that smaller crop pasted (c0, r0) further in
-        # (everything else it would have covered is never sampled), so the kernel's frame table takes the moved origin and the
-        # smaller size and nothing else changes
-        for i, im in enumerate(images):
-            x, y = int(diff[i][0]), int(diff[i][1])
-            if im.ndim == 3 and (x < 0 or y < 0 or x + im.shape[1] > w or y + im.shape[0] > h):
-                # numpy refuses new_image[y:y+ih, x:x+iw] = image for a crop that sticks out of the canvas
-                raise ValueError("aligner: frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas" % (i, im.shape[1], im.shape[0], x, y, w, h))
-        shapes = []
-        for im in images:
-            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
-                raise AssertionError("aligner: images must be HxWx3 uint8 numpy arrays")
-        images, shapes, diff = self._clip_rect(images, diff, tfm)
-        with torch.cuda.device(dev):
-            crops, offs, slot = self.stage_crops_ring(images, dev)
-            self.launch_warps(crops, offs, shapes, diff, h, w, tfm, out)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._ring.done[slot] = ev
-        return out
-
-    def _warp_clip_planned(self, images, diff, h: int, w: int, tfm, out: torch.Tensor, dev) -> torch.Tensor:
-        """warp_clip with the per-frame work in C (round 4): ONE Python pass over the crops collects (address, pitch, shape, paste
-        offset); af_align_plan_u8 checks the canvas fit, cuts every crop to the rows the warp can sample and fills the staging
-        table and the kernel's frame table; then the staging copy (two threads), one H2D copy, one warp launch per <= 64 frames.
-        Same arithmetic as the Python path it replaces (_clip_rect + stage_crops_ring + launch_warps, still used by the column-cut
-        experiment and the streaming aligner): the clip is bit for bit the same."""
+        """the ``process_single`` loop (:75-88) for the whole clip: ONE Python pass over the crops collects (address, pitch, shape,
+        paste offset); af_align_plan_u8 checks the canvas fit, cuts every crop to the rows the warp can sample (the destination
+        square maps to a parallelogram of the canvas; a crop cut to rows [r0, r1) is the same picture as that smaller crop pasted
+        r0 further down) and fills the staging table and the kernel's frame table; then the staging copy, one H2D copy, one warp
+        launch per <= 64 frames.  Cutting the columns the warp cannot sample as well lost: 22 % fewer bytes, but 8 000 short
+        strided memcpys per clip run far below the rate of 32 long ones (1 448 clips/s host-inclusive with rows only, 1 020-1 100
+        with rows and columns, one box).  Everything is enqueued on the current stream and the call returns without
+        synchronising; `out` is valid for stream-ordered consumers, `.cpu()` waits for it."""
         from . import _lib
+        dev = cuda_device(self.device)
         n = len(images)
+        out = torch.empty((n, self.image_size, self.image_size, 3), dtype=torch.uint8, device=dev)
+        if n == 0:
+            return out
         crops = (_lib.AlignCrop * n)()
         keep = []                                      # every array whose address goes into `crops` lives until the copies return
         for i, im in enumerate(images):
-            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
+            if not is_crop(im):
                 raise AssertionError("aligner: images must be HxWx3 uint8 numpy arrays")
-            st = im.strides
-            if st[2] != 1 or st[1] != 3 or st[0] < im.shape[1] * 3:
-                im = np.ascontiguousarray(im)
-                st = im.strides
+            (address, pitch, _, _), im = crop_rect(im)
             keep.append(im)
-            crops[i] = _lib.AlignCrop(im.__array_interface__["data"][0], st[0], im.shape[0], im.shape[1], int(diff[i][0]), int(diff[i][1]))
+            crops[i] = _lib.AlignCrop(address, pitch, im.shape[0], im.shape[1], int(diff[i][0]), int(diff[i][1]))
         rects = (_lib.StageRect * n)()
         frames = (_lib.AlignFrame * n)()
         total, bad = C.c_int64(0), C.c_int32(-1)
@@ -214,73 +144,21 @@ class FasterCropAlignXRay:
         rc = _lib.lib.af_align_plan_u8(crops, n, int(h), int(w), m, self.image_size, rects, frames, C.byref(total), C.byref(bad))
         if rc != 0 and bad.value >= 0:
             i, im = bad.value, keep[bad.value]
-            # numpy refuses new_image[y:y+ih, x:x+iw] = image for a crop that sticks out of the canvas
-            raise ValueError("aligner: frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas"
-                             % (i, im.shape[1], im.shape[0], int(diff[i][0]), int(diff[i][1]), w, h))
+            canvas_misfit(i, im.shape[1], im.shape[0], int(diff[i][0]), int(diff[i][1]), w, h)
         _lib.check(rc, "align_plan_u8")
         with torch.cuda.device(dev):
-            k = self._ring.acquire(total.value, dev)
-            base = self._ring.host[k].data_ptr()
-            nt = min(_COPY_THREADS, n)
-            if nt > 1 and total.value >= (1 << 20):
-                cuts = [n * t // nt for t in range(nt + 1)]
-                def part(t):
-                    _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), C.byref(rects, cuts[t] * C.sizeof(_lib.StageRect)), cuts[t + 1] - cuts[t]),
-                               "stage_rows_u8")
-                list(_pool().map(part, range(nt)))
-            else:
-                _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), rects, n), "stage_rows_u8")
+            slot = self._ring.acquire(total.value, dev)
+            stage_rects(slot.host.data_ptr(), rects, n, total.value)
             del keep
-            d = self._ring.dev[k]
-            d[:total.value].copy_(self._ring.host[k][:total.value], non_blocking=True)
+            slot.dev[:total.value].copy_(slot.host[:total.value], non_blocking=True)
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             for lo in range(0, n, _lib.ALIGN_MAX_FRAMES):
                 hi = min(n, lo + _lib.ALIGN_MAX_FRAMES)
-                _lib.check(_lib.lib.af_warp_affine_clip_u8(C.c_void_p(d.data_ptr()), C.byref(frames, lo * C.sizeof(_lib.AlignFrame)), hi - lo,
+                _lib.check(_lib.lib.af_warp_affine_clip_u8(C.c_void_p(slot.dev.data_ptr()), C.byref(frames, lo * C.sizeof(_lib.AlignFrame)), hi - lo,
                                                            int(h), int(w), m, self.image_size, C.c_void_p(out[lo:hi].data_ptr()), stream),
                            "warp_affine_clip_u8")
-            ev = torch.cuda.Event()
-            ev.record()
-            self._ring.done[k] = ev
+            slot.record()          # behind the warps, not the copy: they read the slot's device twin, which the next filling overwrites
         return out
-
-    def _clip_rect(self, images: Sequence[np.ndarray], diff: np.ndarray, tfm: np.ndarray):
-        """the rectangle of the canvas the size x size destination can sample (bilinear taps, fixed-point rounding: 3 pixels of
-        margin) -> per frame the part of the crop inside it (a rows x bytes view, no copy), its (h, w, 3) shape and the paste offset
-        moved accordingly.  Rows are always cut (a contiguous view); columns only with AF_ALIGN_COLS=1 (see _CLIP_COLUMNS)."""
-        m = np.asarray(tfm, dtype=np.float64).reshape(2, 3)
-        det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
-        if not np.isfinite(det) or abs(det) < 1e-12:
-            return images, [im.shape for im in images], diff # singular map: OpenCV's D = 0 path samples around one point; keep everything
-        s = float(self.image_size - 1)
-        corners = np.array([[0.0, 0.0], [s, 0.0], [0.0, s], [s, s]])
-        # dst = M [x y 1]^T  ->  src = M^-1 (dst - t)
-        dx, dy = corners[:, 0] - m[0, 2], corners[:, 1] - m[1, 2]
-        xs = (m[1, 1] * dx - m[0, 1] * dy) / det
-        ys = (-m[1, 0] * dx + m[0, 0] * dy) / det
-        if not (np.isfinite(xs).all() and np.isfinite(ys).all()):
-            return images, [im.shape for im in images], diff
-        ylo, yhi = int(np.floor(ys.min())) - 3, int(np.ceil(ys.max())) + 4
-        xlo, xhi = int(np.floor(xs.min())) - 3, int(np.ceil(xs.max())) + 4
-        out_images, shapes, out_diff = [], [], np.array(diff, dtype=np.int64, copy=True)
-        for i, im in enumerate(images):
-            x0, y0 = int(out_diff[i][0]), int(out_diff[i][1])
-            r0, r1 = max(0, ylo - y0), min(im.shape[0], yhi - y0)
-            c0, c1 = max(0, xlo - x0), min(im.shape[1], xhi - x0)
-            if not _CLIP_COLUMNS:
-                c0, c1 = 0, im.shape[1]
-            if r1 <= r0 or c1 <= c0:                         # the warp never reaches this crop: one pixel keeps the frame table valid
-                r0, r1, c0, c1 = 0, 1, 0, 1
-            rows = im[r0:r1]
-            if rows.flags.c_contiguous:
-                # rows x bytes: the column cut of a (rows, W * 3) view copies as one memcpy per row (the (h, w, 3) view of the
-                # same pixels went element by element: 5 GB/s instead of 45)
-                out_images.append(rows.reshape(r1 - r0, im.shape[1] * 3)[:, c0 * 3:c1 * 3])
-            else:
-                out_images.append(np.ascontiguousarray(rows[:, c0:c1]).reshape(r1 - r0, (c1 - c0) * 3))
-            shapes.append((r1 - r0, c1 - c0, 3))
-            out_diff[i][0], out_diff[i][1] = x0 + c0, y0 + r0
-        return out_images, shapes, out_diff
 
     @staticmethod
     def _layout(images: Sequence[np.ndarray]):
@@ -292,46 +170,10 @@ class FasterCropAlignXRay:
             total += (im.size + 15) // 16 * 16
         return offs, total
 
-    def stage_crops_ring(self, images: Sequence[np.ndarray], dev):
-        """crops -> a pinned ring slot (copy threads; numpy releases the GIL for these copies) -> one asynchronous H2D copy
-        into the slot's device twin; returns (device bytes, per-frame byte offsets, slot)"""
-        from . import _lib
-        offs, total = self._layout(images)
-        k = self._ring.acquire(total, dev)
-        host = self._ring.host[k]
-        # one C call per copy thread (af_stage_rows_u8: a memcpy per row; ctypes releases the GIL): numpy copies a column-cut view
-        # with ~100 ns of iterator overhead per row - 8 000 rows per clip, half of the whole call
-        rects = (_lib.StageRect * len(images))()
-        keep = []              # every array whose address goes into `rects` - contiguous temporaries included - lives until the copies return
-        for i, (im, o) in enumerate(zip(images, offs)):
-            if im.ndim == 3:
-                im = im.reshape(im.shape[0], im.shape[1] * 3) if im.flags.c_contiguous else np.ascontiguousarray(im).reshape(im.shape[0], -1)
-            if im.strides[1] != 1:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            rects[i] = _lib.StageRect(im.ctypes.data, o, im.strides[0] if im.shape[0] > 1 else im.shape[1], im.shape[0], im.shape[1])
-        base = host.data_ptr()
-        # (staging in four chunks, each crossing PCIe while the next is copied, was tried: the extra pool round trips and small
-        #  copies cost more than the overlap gained - host-inclusive 1 780 -> 860 clips/s)
-        nt = min(_COPY_THREADS, len(images))
-        if nt > 1 and total >= (1 << 20):
-            n = len(images)
-            cuts = [n * t // nt for t in range(nt + 1)]
-            def part(t):
-                _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), C.byref(rects, cuts[t] * C.sizeof(_lib.StageRect)), cuts[t + 1] - cuts[t]),
-                           "stage_rows_u8")
-            list(_pool().map(part, range(nt)))
-        else:
-            _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), rects, len(images)), "stage_rows_u8")
-        del keep
-        d = self._ring.dev[k]
-        d[:total].copy_(host[:total], non_blocking=True)
-        return d, offs, k
-
     @staticmethod
     def stage_crops(images: Sequence[np.ndarray], dev):
         """crops -> one fresh pinned host buffer -> one H2D copy; returns (device bytes, per-frame byte offsets, host buffer).
-        (For callers that keep the crops resident, e.g. bench.py --model aligner; __call__ goes through the ring.)"""
+        (For callers that keep the crops resident, e.g. bench.py --model aligner; __call__ goes through the ring of warp_clip.)"""
         offs, total = FasterCropAlignXRay._layout(images)
         host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
         hv = host.numpy()
@@ -353,8 +195,7 @@ class FasterCropAlignXRay:
                 ih, iw = int(shapes[i][0]), int(shapes[i][1])
                 x, y = int(diff[i][0]), int(diff[i][1])
                 if x < 0 or y < 0 or x + iw > w or y + ih > h:
-                    # numpy refuses new_image[y:y+ih, x:x+iw] = image for a crop that sticks out of the canvas
-                    raise ValueError("aligner: frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas" % (i, iw, ih, x, y, w, h))
+                    canvas_misfit(i, iw, ih, x, y, w, h)
                 frames[k] = _lib.AlignFrame(offs[i], ih, iw, x, y)
             _lib.check(_lib.lib.af_warp_affine_clip_u8(C.c_void_p(crops.data_ptr()), C.cast(frames, C.c_void_p), hi - lo, h, w, m,
                                                        size, C.c_void_p(out[lo:hi].data_ptr()), stream), "warp_affine_clip_u8")
@@ -374,10 +215,7 @@ class StreamingCropAligner:
         self.aligner = FasterCropAlignXRay(size, device=device)
         self.capacity = int(capacity)
         self.slot_bytes = (max_crop_pixels * 3 + 15) // 16 * 16
-        dev = torch.device(device or torch.device("cuda", torch.cuda.current_device()))
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
+        self.device = dev = cuda_device(device)
         self.host = torch.empty(self.capacity * self.slot_bytes, dtype=torch.uint8, pin_memory=True)
         self.dev = torch.empty(self.capacity * self.slot_bytes, dtype=torch.uint8, device=dev)
         self._hv = self.host.numpy()
@@ -390,7 +228,7 @@ class StreamingCropAligner:
 
     def push(self, info, crop: np.ndarray) -> None:
         """a captured frame of the track: landmark record ``(_, ldm5, ldm68, box)`` + its HxWx3 uint8 crop"""
-        if not (isinstance(crop, np.ndarray) and crop.dtype == np.uint8 and crop.ndim == 3 and crop.shape[2] == 3):
+        if not is_crop(crop):
             raise AssertionError("aligner: images must be HxWx3 uint8 numpy arrays")
         if crop.size > self.slot_bytes:
             raise ValueError("aligner: a %dx%d crop exceeds the slot size (max_crop_pixels)" % (crop.shape[1], crop.shape[0]))
@@ -419,13 +257,8 @@ class StreamingCropAligner:
             raise ValueError("aligner: %d frames requested, %d resident" % (n, len(self.frames)))
         win = self.frames[-n:]
         al = self.aligner
-        boxes = np.array([f[0][3] for f in win])
-        five = np.array([f[0][1] for f in win])
         l68 = np.array([f[0][2] for f in win])
-        left_top = boxes[:, :2].min(0)
-        w, h = boxes[:, 2:].max(0) - left_top
-        diff = boxes[:, :2] - left_top[None]
-        tfm, trans = estimate_batch_transform(five + diff[:, None, :], al.std_points)
+        tfm, trans, h, w, diff = fit_window(np.array([f[0][3] for f in win]), np.array([f[0][1] for f in win]), al.std_points)
         t68 = _apply(trans, l68 + diff[:, None, :])
         if out is None:
             out = torch.empty((n, al.image_size, al.image_size, 3), dtype=torch.uint8, device=self.device)
@@ -435,7 +268,7 @@ class StreamingCropAligner:
         for i, shp in enumerate(shapes):
             x, y = int(diff[i][0]), int(diff[i][1])
             if x < 0 or y < 0 or x + shp[1] > int(w) or y + shp[0] > int(h):
-                raise ValueError("aligner: frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas" % (i, shp[1], shp[0], x, y, int(w), int(h)))
+                canvas_misfit(i, shp[1], shp[0], x, y, int(w), int(h))
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             for f in win:                                # crops pushed from another stream: their uploads come first

@@ -4,7 +4,7 @@ sliding window of a face track aligned and scored on the GPU (``TrackScorer``).
 The reference (altfreezing/demo.py:304-339) walks over EVERY ``clip_size``-frame window of a face track, stride 1: align the
 window's crops (``FasterCropAlignXRay``), normalise, forward at batch 1, sigmoid; the mean over the windows is the video's
 score (:339).  Consecutive windows share all but one crop.  ``TrackScorer`` uploads each crop of a track ONCE into a device
-pool, fits every window's similarity on the host with the aligner's own arithmetic (``aligner.estimate_batch_transform``), and
+pool, fits every window's similarity on the host with the aligner's own arithmetic (``aligner.fit_window``), and
 aligns ``batch`` windows per launch straight out of the pool (``af_warp_affine_windows_u8``, csrc/af_align.hip) into the uint8
 clip buffer ``I3D8x8.forward_clips_u8`` consumes.  Nothing is synchronised before the end of the track.
 
@@ -24,12 +24,13 @@ for cv2, matplotlib, scipy and filterpy, which they import and these functions n
 the visualisation writer.  There is no CPU fallback: without the HIP library the calls fail.
 """
 import ctypes as C
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from .aligner import STD_POINTS_256, _COPY_THREADS, _pool, estimate_batch_transform
+from ._staging import _COPY_THREADS, _SPLIT_BYTES, PinnedRing, _pool, crop_rect, cuda_device, is_crop, packed_rgb, stage_rects
+from .aligner import STD_POINTS_256, canvas_misfit, fit_window
 
 _FRAME_DTYPE = np.dtype([("offset", "<i8"), ("ih", "<i4"), ("iw", "<i4"), ("x", "<i4"), ("y", "<i4")])       # af_align_frame
 _RECT_DTYPE = np.dtype([(n, "<i4") for n in ("frame", "rx", "ry", "ih", "iw", "x", "y", "reserved")])            # af_frame_rect
@@ -227,10 +228,6 @@ def find_longest(detect_res):
     return spans, all_tracks
 
 
-def _is_crop(im) -> bool:
-    return isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3
-
-
 class _Track:
     """host arrays of one track: what every window's fit and table rows are cut from"""
 
@@ -238,7 +235,7 @@ class _Track:
         if len(infos) != len(crops):
             raise ValueError("evaluator: %d landmark records for %d crops" % (len(infos), len(crops)))
         for im in crops:
-            if not _is_crop(im):
+            if not is_crop(im):
                 raise AssertionError("aligner: images must be HxWx3 uint8 numpy arrays")
         self.crops = list(crops)
         self.n = len(crops)
@@ -249,143 +246,266 @@ class _Track:
             self.iw = np.array([im.shape[1] for im in crops], dtype=np.int64)
             self.bytes = (self.ih * self.iw * 3 + 15) // 16 * 16
 
+    def source(self, idx: np.ndarray, where: np.ndarray):
+        """the values of ``POOL.source`` for track positions `idx` that sit at `where`: the crops' pool offsets"""
+        return (where,)
 
-class _WindowScorer:
-    """What TrackScorer and VideoScorer share: the partition of a track's windows into forwards, the per-window fit, the table ring
-    and the double clip buffer, the window-batch warp launch, the segments of a track that does not fit the device memory it may
-    use, and the loop that enqueues a track.  A subclass says where a track's pixels live: ``_upload`` brings frames [lo, hi) of a
-    track onto the device and returns where each one sits, ``_fill_items`` writes that into the planner's per-(window, frame)
-    records of ``_ITEM``, and ``_TABLE_BYTES`` / ``_PLAN`` / ``_LAUNCH`` name the C entry points of its form of the warp."""
 
-    _ITEM, _TABLE_BYTES, _PLAN, _LAUNCH = None, None, None, None
-    _CLIP_BUFFERS = 2         # one batch is warped while the forward of the one before reads its own
+class _WarpForm(NamedTuple):
+    """one form of the window-batch warp (csrc/af_align.hip)"""
+    item: np.dtype                # the planner's record per (window, frame)
+    source: Tuple[str, ...]       # its fields that say where the frame's pixels are; a track's ``source`` gives their values
+    table_bytes: str              # the C entry points: the size of a batch's table, the planner that fills it, the launch that reads it
+    plan: str
+    launch: str
 
-    def __init__(self, network, clip_size: int = 32, size: int = 224, batch: int = 16, device: Optional[torch.device] = None,
-                 pool_bytes: int = 512 << 20):
+
+POOL = _WarpForm(_FRAME_DTYPE, ("offset",), "af_window_batch_table_bytes", "af_window_batch_plan_u8", "af_warp_affine_windows_u8")
+RECTS = _WarpForm(_RECT_DTYPE, ("frame", "rx", "ry"), "af_window_rects_table_bytes", "af_window_rects_plan_u8", "af_warp_affine_window_rects_u8")
+RECTS_BGR = RECTS._replace(launch="af_warp_affine_window_rects_bgr_u8")     # the same rectangles of frames whose bytes are B, G, R
+
+
+def partition(n_windows: int, batch: int):
+    """``[(first window, windows, clips in the forward)]``: full batches, then the rest padded to a power of two"""
+    out, lo = [], 0
+    while lo < n_windows:
+        n = min(batch, n_windows - lo)
+        run = batch
+        if n < batch:
+            run = 1
+            while run < n:
+                run *= 2
+            run = min(run, batch)
+        out.append((lo, n, run))
+        lo += n
+    return out
+
+
+def _fit(track, idx: Sequence[int], std_points: np.ndarray):
+    """one window's transform, canvas and paste offsets, exactly as FasterCropAlignXRay.__call__ computes them"""
+    idx = np.asarray(idx)
+    tfm, _, h, w, diff = fit_window(track.boxes[idx], track.five[idx], std_points)
+    return tfm, int(h), int(w), diff.astype(np.int64)
+
+
+def _padded(track, windows, first: int, n: int, run: int, std_points: np.ndarray):
+    """window numbers and fits of one forward of ``partition``: windows [first, first + n), the last one repeated up to `run`"""
+    ids = list(range(first, first + n)) + [first + n - 1] * (run - n)
+    fits = [_fit(track, windows[k], std_points) for k in ids[:n]]
+    return ids, fits + [fits[-1]] * (run - n)
+
+
+def _network_device(network, device=None) -> torch.device:
+    dev = cuda_device(device if device is not None else next(network.parameters()).device)
+    if dev.type != "cuda":
+        raise RuntimeError("the MI355X evaluator only runs on a HIP device (no CPU fallback); the network is on %s" % dev)
+    return dev
+
+
+def _clip_buffers(count: int, batch: int, clip_size: int, size: int, device) -> List[torch.Tensor]:
+    with torch.inference_mode(False):                             # buffers that outlive a caller's inference_mode block stay writable
+        return [torch.empty((batch, clip_size, size, size, 3), dtype=torch.uint8, device=device) for _ in range(count)]
+
+
+class _Resident:
+    """pixels on the device (``dev``, with the slack bytes the kernel may read behind the last one) that arrive through a ring of
+    pinned staging slots; ``uploaded_bytes`` counts what was sent"""
+
+    def __init__(self, device):
+        self.device, self.dev, self.uploaded_bytes = device, None, 0
+        self._stage = PinnedRing(min_bytes=_STAGE_BYTES)
+
+    def _reserve(self, need: int, nbytes: int):
+        if self.dev is None or self.dev.numel() < need:
+            self.dev = None                                        # give the old buffer back before taking a larger one
+            with torch.inference_mode(False):
+                self.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _send(self, slot, used: int, offset: int):
+        """pinned slot -> device memory at `offset`, asynchronous"""
+        self.dev[offset:offset + used].copy_(slot.host[:used], non_blocking=True)
+        slot.record()          # behind the copy: nothing else reads the pinned slot (the warps read `dev`, in stream order behind it)
+        self.uploaded_bytes += used
+
+
+class CropPool(_Resident):
+    """the crops of a track, each whole and once, 16-byte aligned one behind the other in at most `pool_bytes` of device memory"""
+
+    def __init__(self, device, pool_bytes: int):
+        super().__init__(device)
+        self.pool_bytes = int(pool_bytes)
+
+    def upload(self, track: _Track, lo: int, hi: int) -> np.ndarray:
+        """crops [lo, hi) of the track -> the pool: a few pinned staging slots in turn (filled by the copy threads), one
+        asynchronous copy per slot.  Returns the crops' pool offsets (index: frame - lo)."""
+        from . import _lib
+        offs = np.zeros(hi - lo, dtype=np.int64)
+        offs[1:] = np.cumsum(track.bytes[lo:hi])[:-1]
+        total = int(track.bytes[lo:hi].sum())
+        if total + _POOL_SLACK > self.pool_bytes:
+            raise ValueError("evaluator: %d frames (%d bytes) do not fit the pool of %d bytes" % (hi - lo, total, self.pool_bytes))
+        self._reserve(total + _POOL_SLACK, min(self.pool_bytes, max(total + _POOL_SLACK, 64 << 20)))
+        i = lo
+        while i < hi:
+            j, used = i, 0
+            while j < hi and (j == i or used + int(track.bytes[j]) <= _STAGE_BYTES):
+                used += int(track.bytes[j])
+                j += 1
+            slot = self._stage.acquire(used)                       # one crop larger than a slot gets a slot of its size
+            rects = (_lib.StageRect * (j - i))()
+            keep = []                                              # arrays whose addresses are in `rects` live until the copies return
+            for k in range(i, j):
+                (address, pitch, rows, row), im = crop_rect(track.crops[k])
+                keep.append(im)
+                rects[k - i] = _lib.StageRect(address, int(offs[k - lo] - offs[i - lo]), pitch, rows, row)
+            stage_rects(slot.host.data_ptr(), rects, j - i, used)
+            del keep
+            self._send(slot, used, int(offs[i - lo]))
+            i = j
+        return offs
+
+    def plan_source(self):
+        return self.dev.numel()
+
+
+class FrameStore(_Resident):
+    """`capacity` decoded frames of one `shape`, packed, slot after slot in one device buffer: a whole video, a window through
+    which a longer one passes, or a ring of a call's last frames"""
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.shape, self.frame_nbytes, self.capacity = None, 0, 0
+
+    def open(self, shape, capacity: int):
+        self.shape, self.capacity = tuple(shape), int(capacity)
+        self.frame_nbytes = int(shape[0]) * int(shape[1]) * 3
+        need = self.capacity * self.frame_nbytes + _POOL_SLACK    # 3 readable bytes behind the last frame (af_hip.h)
+        self._reserve(need, need)
+
+    def put(self, frames, first_slot: int):
+        """host frames -> consecutive slots of the store from `first_slot`: pinned slots in turn, each filled by the copy threads
+        in bands of rows, one asynchronous copy per slot.  A frame whose pixels are not packed RGB bytes (a channel-reversed
+        view) costs a strided host pass here instead of a memcpy per band."""
+        from . import _lib
+        h, w = self.shape[:2]
+        fb, row = self.frame_nbytes, w * 3
+        per_slot = max(1, _STAGE_BYTES // fb)
+        for i in range(0, len(frames), per_slot):
+            chunk = frames[i:i + per_slot]
+            used = len(chunk) * fb
+            slot = self._stage.acquire(used)                       # one frame larger than a slot gets a slot of its size
+            host = slot.host.numpy()[:used].reshape(len(chunk), h, w, 3)
+            bands = max(1, min(h, -(-_COPY_THREADS // len(chunk)))) if used >= _SPLIT_BYTES else 1
+            rects, n, strided = (_lib.StageRect * (len(chunk) * bands))(), 0, []
+            for k, im in enumerate(chunk):
+                packed = packed_rgb(im)
+                for t in range(bands):
+                    r0, r1 = h * t // bands, h * (t + 1) // bands
+                    if packed:
+                        rects[n] = _lib.StageRect(im.__array_interface__["data"][0] + r0 * im.strides[0], k * fb + r0 * row,
+                                                  im.strides[0], r1 - r0, row)
+                        n += 1
+                    else:
+                        strided.append((host[k, r0:r1], im[r0:r1]))
+            if n:
+                stage_rects(slot.host.data_ptr(), rects, n, used)
+            if len(strided) > 1:
+                list(_pool().map(lambda job: np.copyto(*job), strided))
+            elif strided:
+                np.copyto(*strided[0])
+            self._send(slot, used, (first_slot + i) * fb)
+
+    def view(self, slot: int, n: Optional[int] = None) -> torch.Tensor:
+        """the device (H, W, 3) view of slot `slot`, or the (n, H, W, 3) view of the `n` slots from it on"""
+        h, w = self.shape[:2]
+        frames = self.dev[slot * self.frame_nbytes:(slot + (1 if n is None else n)) * self.frame_nbytes]
+        return frames.view(h, w, 3) if n is None else frames.view(n, h, w, 3)
+
+    def plan_source(self):
+        from . import _lib
+        h, w = self.shape[:2]
+        self._desc = _lib.FrameStore(self.dev.numel(), self.frame_nbytes, w * 3, self.capacity, h, w, 0)
+        return C.byref(self._desc)
+
+
+class WindowWarp:
+    """One form of the window-batch warp over the device pixels of `source`: fills the planner's records for a batch of windows,
+    has the planner write the batch's table into a slot of its ring of tables, sends the table and launches."""
+
+    def __init__(self, form: _WarpForm, source: _Resident, clip_size: int = 32, size: int = 224, batch: int = 16):
         from . import _lib                                        # fails loudly when libafhip.so is missing
-        self.network = getattr(network, "network", network)
+        self.form, self.source = form, source
         self.clip_size, self.size, self.batch = int(clip_size), int(size), int(batch)
         if not (1 <= self.batch <= _lib.WINDOW_MAX_BATCH and 1 <= self.clip_size <= _lib.ALIGN_MAX_FRAMES):
             raise ValueError("evaluator: batch 1..%d, clip_size 1..%d" % (_lib.WINDOW_MAX_BATCH, _lib.ALIGN_MAX_FRAMES))
         if self.size % 4 or not 0 < self.size <= _lib.WINDOW_MAX_SIZE:
             raise ValueError("evaluator: size must be a multiple of 4, at most %d" % _lib.WINDOW_MAX_SIZE)
-        dev = torch.device(device if device is not None else next(self.network.parameters()).device)
-        if dev.type != "cuda":
-            raise RuntimeError("the MI355X evaluator only runs on a HIP device (no CPU fallback); the network is on %s" % dev)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
-        self.pool_bytes = int(pool_bytes)
-        self.std_points = STD_POINTS_256 * self.size / 256.0
-        self.table_bytes = int(getattr(_lib.lib, self._TABLE_BYTES)(self.batch, self.clip_size))
-        self.uploaded_bytes = 0                                   # crop bytes sent to the device by the last call
-        self._pool_dev = None
-        self._clips = None
-        self._tables = None
-        self._stage = None
-        self._stage_turn = self._table_turn = 0                  # each ring is walked round-robin on its own
+        self._table_bytes, self._plan, self._launch = (getattr(_lib.lib, name) for name in (form.table_bytes, form.plan, form.launch))
+        self.table_bytes = int(self._table_bytes(self.batch, self.clip_size))
+        self.tables = PinnedRing(min_bytes=self.table_bytes)      # three slots: the host runs up to two batches ahead of the device
 
-    # -- the partition of a track's windows into forwards -----------------------------------------
-    def partition(self, n_windows: int):
-        """``[(first window, windows, clips in the forward)]``: full batches, then the rest padded to a power of two"""
-        out, lo = [], 0
-        while lo < n_windows:
-            n = min(self.batch, n_windows - lo)
-            run = self.batch
-            if n < self.batch:
-                run = 1
-                while run < n:
-                    run *= 2
-                run = min(run, self.batch)
-            out.append((lo, n, run))
-            lo += n
-        return out
-
-    # -- device state ------------------------------------------------------------------------------
-    def _buffers(self):
-        if self._clips is None:
-            with torch.inference_mode(False):                     # buffers that outlive a caller's inference_mode block stay writable
-                shape = (self.batch, self.clip_size, self.size, self.size, 3)
-                self._clips = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(self._CLIP_BUFFERS)]
-                # tables: pinned host + device twin + the event behind the copy out of the pinned one (the host rewrites a slot
-                # only after that copy has left it).  Three slots: the host runs up to two batches ahead of the device.
-                self._tables = [[torch.empty(self.table_bytes, dtype=torch.uint8, pin_memory=True),
-                                 torch.empty(self.table_bytes, dtype=torch.uint8, device=self.device), None] for _ in range(3)]
-                self._stage = [[torch.empty(_STAGE_BYTES, dtype=torch.uint8, pin_memory=True), None] for _ in range(3)]
-        return self._clips
-
-    def _stage_slot(self, used: int):
-        """the next pinned staging slot, free again (the copy of three slots ago has left it) and at least `used` bytes large"""
-        slot = self._stage[self._stage_turn % len(self._stage)]
-        self._stage_turn += 1
-        if slot[1] is not None:
-            slot[1].synchronize()
-        if slot[0].numel() < used:                                 # one crop / frame larger than a slot
-            with torch.inference_mode(False):
-                slot[0] = torch.empty(used, dtype=torch.uint8, pin_memory=True)
-        return slot
-
-    def _send_slot(self, slot, used: int, offset: int):
-        """pinned slot -> device memory at `offset`, asynchronous; the event lets the host know when the slot may be refilled"""
-        self._pool_dev[offset:offset + used].copy_(slot[0][:used], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        slot[1] = ev
-        self.uploaded_bytes += used
-
-    def _fit(self, track: _Track, idx: Sequence[int]):
-        """one window's canvas, paste offsets and transform, exactly as FasterCropAlignXRay.__call__ computes them
-        (faster_crop_align_xray.py:21-66)"""
-        idx = np.asarray(idx)
-        boxes, five = track.boxes[idx], track.five[idx]
-        left_top = boxes[:, :2].min(0)
-        w, h = boxes[:, 2:].max(0) - left_top
-        diff = boxes[:, :2] - left_top[None]
-        tfm, _ = estimate_batch_transform(five + diff[:, None, :], self.std_points)
-        return tfm, int(h), int(w), diff.astype(np.int64)
-
-    def _padded(self, track, windows, first: int, n: int, run: int):
-        """window numbers and fits of one forward of ``partition``: windows [first, first + n), the last one repeated up to `run`"""
-        ids = list(range(first, first + n)) + [first + n - 1] * (run - n)
-        fits = [self._fit(track, windows[k]) for k in ids[:n]]
-        return ids, fits + [fits[-1]] * (run - n)
-
-    def _warp(self, track: _Track, windows, offs: np.ndarray, first_frame: int, out: torch.Tensor, fits=None):
-        """table of one batch of windows (index lists into the track) -> pinned slot -> device; one launch into `out`"""
+    def __call__(self, track, windows, offs: np.ndarray, first_frame: int, out: torch.Tensor, fits):
+        """windows (index lists into the track, whose frame j sits at ``offs[j - first_frame]`` of the source) with their `fits`
+        -> table -> pinned slot -> device; one launch into `out`"""
         from . import _lib
-        n = len(windows)
+        n, src = len(windows), self.source
         desc = np.zeros(n, dtype=_WINDOW_DTYPE)
-        frames = np.zeros((n, self.clip_size), dtype=self._ITEM)
-        for w, idx in enumerate(windows):
-            tfm, h, wd, diff = fits[w] if fits is not None else self._fit(track, idx)
+        items = np.zeros((n, self.clip_size), dtype=self.form.item)
+        for w, (idx, (tfm, h, wd, diff)) in enumerate(zip(windows, fits)):
             desc[w] = (np.asarray(tfm, dtype=np.float64).reshape(6), h, wd)
             ii = np.asarray(idx)
-            self._fill_items(frames, w, track, ii, offs[ii - first_frame])
-            frames["ih"][w], frames["iw"][w] = track.ih[ii], track.iw[ii]
-            frames["x"][w], frames["y"][w] = diff[:, 0], diff[:, 1]
-        slot = self._tables[self._table_turn % len(self._tables)]
-        self._table_turn += 1
-        if slot[2] is not None:
-            slot[2].synchronize()
+            for name, values in zip(self.form.source, track.source(ii, offs[ii - first_frame])):
+                items[name][w] = values
+            items["ih"][w], items["iw"][w] = track.ih[ii], track.iw[ii]
+            items["x"][w], items["y"][w] = diff[:, 0], diff[:, 1]
+        slot = self.tables.acquire(self.table_bytes, src.device)
         bad_w, bad_f = C.c_int32(-1), C.c_int32(-1)
-        rc = getattr(_lib.lib, self._PLAN)(desc.ctypes.data, frames.ctypes.data, n, self.clip_size, self.size, self._plan_source(),
-                                           slot[0].data_ptr(), self.table_bytes, C.byref(bad_w), C.byref(bad_f))
+        rc = self._plan(desc.ctypes.data, items.ctypes.data, n, self.clip_size, self.size, src.plan_source(), slot.host.data_ptr(),
+                        self.table_bytes, C.byref(bad_w), C.byref(bad_f))
         if rc != 0 and bad_w.value >= 0:
-            f = frames[bad_w.value, bad_f.value]
-            # numpy refuses new_image[y:y+ih, x:x+iw] = image for a crop that sticks out of the canvas
-            raise ValueError("aligner: window %d frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas"
-                             % (bad_w.value, bad_f.value, f["iw"], f["ih"], f["x"], f["y"], desc[bad_w.value]["canvas_w"], desc[bad_w.value]["canvas_h"]))
-        _lib.check(rc, self._PLAN[3:])
-        used = int(getattr(_lib.lib, self._TABLE_BYTES)(n, self.clip_size))
-        slot[1][:used].copy_(slot[0][:used], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        slot[2] = ev
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(getattr(_lib.lib, self._LAUNCH)(C.c_void_p(self._pool_dev.data_ptr()), C.c_void_p(slot[1].data_ptr()), n, self.clip_size,
-                                                   self.size, C.c_void_p(out.data_ptr()), stream), self._LAUNCH[3:])
+            f, d = items[bad_w.value, bad_f.value], desc[bad_w.value]
+            canvas_misfit(bad_f.value, f["iw"], f["ih"], f["x"], f["y"], d["canvas_w"], d["canvas_h"], window=bad_w.value)
+        _lib.check(rc, self.form.plan[3:])
+        used = int(self._table_bytes(n, self.clip_size))
+        slot.dev[:used].copy_(slot.host[:used], non_blocking=True)
+        # behind the copy, not the launch: the host rewrites only the pinned table; its twin is next written by the copy of three
+        # batches later, which the stream orders behind this launch
+        slot.record()
+        stream = C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+        _lib.check(self._launch(C.c_void_p(src.dev.data_ptr()), C.c_void_p(slot.dev.data_ptr()), n, self.clip_size, self.size,
+                                C.c_void_p(out.data_ptr()), stream), self.form.launch[3:])
 
-    def _segments(self, track: _Track, windows):
+
+class _WindowScorer:
+    """What TrackScorer and VideoScorer share: the double clip buffer, the segments of a track that does not fit the device memory
+    it may use, and the loop that enqueues a track - ``partition``, the per-window fits, the warps, the forwards - over the
+    ``WindowWarp`` and the device pixels (``source``) it has.  A subclass says how a track's pixels get there: ``_upload`` brings
+    frames [lo, hi) of a track onto the device and returns where each one sits."""
+
+    def __init__(self, network, form: _WarpForm, source: _Resident, clip_size: int, size: int, batch: int, pool_bytes: int):
+        self.network = getattr(network, "network", network)
+        self.device = source.device
+        self.source = source
+        self.warp = WindowWarp(form, source, clip_size, size, batch)
+        self.clip_size, self.size, self.batch = self.warp.clip_size, self.warp.size, self.warp.batch
+        self.pool_bytes = int(pool_bytes)
+        self.std_points = STD_POINTS_256 * self.size / 256.0
+        self._clips = None
+
+    @property
+    def uploaded_bytes(self) -> int:
+        """pixel bytes sent to the device by the last call"""
+        return self.source.uploaded_bytes
+
+    def partition(self, n_windows: int):
+        return partition(n_windows, self.batch)
+
+    def _buffers(self):
+        if self._clips is None:                                   # two: one batch is warped while the forward of the one before reads its own
+            self._clips = _clip_buffers(2, self.batch, self.clip_size, self.size, self.device)
+        return self._clips
+
+    def _segments(self, track, windows):
         """[(first frame, end frame, windows)]: the whole track if its crops fit the pool, else runs of consecutive windows whose
         frames fit - the next run starts at the next window, so neighbours overlap by clip_size - 1 frames"""
         room = self.pool_bytes - _POOL_SLACK
@@ -417,14 +537,14 @@ class _WindowScorer:
         if not windows:
             return out
         with torch.cuda.device(self.device):
-            self._buffers()
             lo, hi = min(min(w) for w in windows), max(max(w) for w in windows) + 1
             offs = self._upload(track, lo, hi)
             for k in range(0, len(windows), self.batch):
-                self._warp(track, windows[k:k + self.batch], offs, lo, out[k:k + self.batch])
+                batch = windows[k:k + self.batch]
+                self.warp(track, batch, offs, lo, out[k:k + self.batch], [_fit(track, idx, self.std_points) for idx in batch])
         return out
 
-    def _score_device(self, track: _Track, windows) -> List[torch.Tensor]:
+    def _score_device(self, track, windows) -> List[torch.Tensor]:
         """enqueue everything for the windows of one track; returns the per-forward score tensors (device, unsynchronised)"""
         parts = []
         with torch.cuda.device(self.device):
@@ -436,7 +556,7 @@ class _WindowScorer:
             # kernels, so the scores would otherwise move with the cuts): a batch that straddles a cut is warped in two launches,
             # one before and one after the next segment's upload, into the same clip buffer
             for turn, (first, n, run) in enumerate(self.partition(len(windows))):
-                ids, fits = self._padded(track, windows, first, n, run)
+                ids, fits = _padded(track, windows, first, n, run, self.std_points)
                 buf = clips[turn % len(clips)][:run]
                 a = 0
                 while a < run:
@@ -446,7 +566,7 @@ class _WindowScorer:
                     if seg_of[ids[a]] != resident:
                         resident = seg_of[ids[a]]
                         offs = self._upload(track, segs[resident][0], segs[resident][1])
-                    self._warp(track, [windows[k] for k in ids[a:b]], offs, segs[resident][0], buf[a:b], fits[a:b])
+                    self.warp(track, [windows[k] for k in ids[a:b]], offs, segs[resident][0], buf[a:b], fits[a:b])
                     a = b
                 with torch.inference_mode():
                     parts.append(self.network.forward_clips_u8(buf, return_scores=True)["scores"][:n])
@@ -487,71 +607,25 @@ class TrackScorer(_WindowScorer):
     ``pool_bytes`` bounds the device memory for crops (default 512 MiB, about a thousand 420-pixel crops).  A longer track is cut
     into segments that overlap by ``clip_size - 1`` frames; the scores do not depend on where the cuts fall."""
 
-    _ITEM, _TABLE_BYTES, _PLAN, _LAUNCH = _FRAME_DTYPE, "af_window_batch_table_bytes", "af_window_batch_plan_u8", "af_warp_affine_windows_u8"
+    def __init__(self, network, clip_size: int = 32, size: int = 224, batch: int = 16, device: Optional[torch.device] = None,
+                 pool_bytes: int = 512 << 20):
+        pool = CropPool(_network_device(getattr(network, "network", network), device), pool_bytes)
+        super().__init__(network, POOL, pool, clip_size, size, batch, pool_bytes)
 
     def _upload(self, track: _Track, lo: int, hi: int) -> np.ndarray:
-        """crops [lo, hi) of the track -> the device pool, each crop whole and once: a few pinned staging slots in turn (filled by
-        the aligner's copy threads), one asynchronous copy per slot.  Returns the crops' pool offsets (index: frame - lo)."""
-        from . import _lib
-        offs = np.zeros(hi - lo, dtype=np.int64)
-        offs[1:] = np.cumsum(track.bytes[lo:hi])[:-1]
-        total = int(track.bytes[lo:hi].sum())
-        if total + _POOL_SLACK > self.pool_bytes:
-            raise ValueError("evaluator: %d frames (%d bytes) do not fit the pool of %d bytes" % (hi - lo, total, self.pool_bytes))
-        if self._pool_dev is None or self._pool_dev.numel() < total + _POOL_SLACK:
-            self._pool_dev = None                                  # give the old pool back before taking a larger one
-            with torch.inference_mode(False):
-                self._pool_dev = torch.empty(min(self.pool_bytes, max(total + _POOL_SLACK, 64 << 20)), dtype=torch.uint8, device=self.device)
-        i = lo
-        while i < hi:
-            j, used = i, 0
-            while j < hi and (j == i or used + int(track.bytes[j]) <= _STAGE_BYTES):
-                used += int(track.bytes[j])
-                j += 1
-            slot = self._stage_slot(used)
-            rects = (_lib.StageRect * (j - i))()
-            keep = []                                              # arrays whose addresses are in `rects` live until the copies return
-            for k in range(i, j):
-                im = track.crops[k]
-                st = im.strides
-                if st[2] != 1 or st[1] != 3 or st[0] < im.shape[1] * 3:
-                    im = np.ascontiguousarray(im)
-                    st = im.strides
-                keep.append(im)
-                rects[k - i] = _lib.StageRect(im.__array_interface__["data"][0], int(offs[k - lo] - offs[i - lo]),
-                                              st[0] if im.shape[0] > 1 else im.shape[1] * 3, im.shape[0], im.shape[1] * 3)
-            base, n = slot[0].data_ptr(), j - i
-            nt = min(_COPY_THREADS, n)
-            if nt > 1 and used >= (1 << 20):
-                cuts = [n * t // nt for t in range(nt + 1)]
-                def part(t):
-                    _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), C.byref(rects, cuts[t] * C.sizeof(_lib.StageRect)), cuts[t + 1] - cuts[t]),
-                               "stage_rows_u8")
-                list(_pool().map(part, range(nt)))
-            else:
-                _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), rects, n), "stage_rows_u8")
-            del keep
-            self._send_slot(slot, used, int(offs[i - lo]))
-            i = j
-        return offs
-
-    def _fill_items(self, items, w: int, track: _Track, idx: np.ndarray, where: np.ndarray):
-        items["offset"][w] = where
-
-    def _plan_source(self):
-        return self._pool_dev.numel()
+        return self.source.upload(track, lo, hi)
 
     # -- public ------------------------------------------------------------------------------------
     def aligned_windows(self, infos, crops, windows) -> torch.Tensor:
         """the warp stage alone: uint8 CUDA tensor (len(windows), clip_size, size, size, 3), window ``w`` =
         ``FasterCropAlignXRay(size)(infos[windows[w]], crops[windows[w]])``.  The frames the windows use must fit the pool."""
-        self.uploaded_bytes = 0
+        self.source.uploaded_bytes = 0
         return self._aligned(_Track(infos, crops), windows)
 
     def score_track(self, infos, crops) -> np.ndarray:
         """float32 fake probabilities, one per window of ``clip_windows(len(crops), clip_size)``, in that order"""
         track = _Track(infos, crops)
-        self.uploaded_bytes = 0
+        self.source.uploaded_bytes = 0
         windows = clip_windows(track.n, self.clip_size)
         if not windows:
             return np.zeros(0, dtype=np.float32)
@@ -563,7 +637,7 @@ class TrackScorer(_WindowScorer):
         track i, one per frame of ``range(*spans[i])``; ``frames``: the decoded HxWx3 uint8 frames.  Returns ``video_score``,
         ``pred_label``, ``preds`` (per clip, track by track), ``clips`` (per clip its ``(track, index in track)`` pairs) and
         ``frame_res`` (``summarise``).  All tracks are enqueued before the first score is read back."""
-        self.uploaded_bytes = 0
+        self.source.uploaded_bytes = 0
 
         def host_cut_tracks():
             for (start, end), faces in zip(spans, tracks):
@@ -599,6 +673,10 @@ class _FrameTrack:
             self.ih = np.minimum(r[:, 3], int(frame_shape[0])) - self.ry
             self.bytes = np.full(self.n, int(frame_shape[0]) * int(frame_shape[1]) * 3, dtype=np.int64)
 
+    def source(self, idx: np.ndarray, where: np.ndarray):
+        """the values of ``RECTS.source`` for track positions `idx` whose frames sit in the store's slots `where`"""
+        return where, self.rx[idx], self.ry[idx]
+
 
 class VideoScorer(_WindowScorer):
     """``VideoScorer(detector, network).score(frames)``: the reference's offline evaluator (demo.py ``eval_video_demo_timed``) from
@@ -619,95 +697,40 @@ class VideoScorer(_WindowScorer):
     scored track by track in frame segments that overlap by ``clip_size - 1`` and are uploaded again from the host frames; the
     scores do not depend on where the cuts fall.  ``uploaded_bytes`` is what the last call sent to the device."""
 
-    _ITEM, _TABLE_BYTES, _PLAN, _LAUNCH = _RECT_DTYPE, "af_window_rects_table_bytes", "af_window_rects_plan_u8", "af_warp_affine_window_rects_u8"
-
     def __init__(self, detector, network, clip_size: int = 32, size: int = 224, batch: int = 16, frame_bytes: int = 4 << 30):
-        super().__init__(network, clip_size, size, batch, None, frame_bytes)
+        super().__init__(network, RECTS, FrameStore(_network_device(getattr(network, "network", network))), clip_size, size, batch, frame_bytes)
         self.detector = detector
         if detector is not None and torch.device(detector.device) != self.device:
             raise ValueError("evaluator: the detector is on %s, the network on %s" % (detector.device, self.device))
-        self._frames, self._shape, self._resident = None, None, False
+        self._frames, self._resident = None, False
 
     # -- the frame store -----------------------------------------------------------------------------
     def _open_store(self, frames):
         """checks the frames and sizes the store for them: all of them when ``frame_bytes`` allows, else as many as it holds"""
         shape = frames[0].shape
         for im in frames:
-            if not _is_crop(im) or im.shape != shape:
+            if not is_crop(im) or im.shape != shape:
                 raise AssertionError("evaluator: frames must be HxWx3 uint8 numpy arrays of one size")
-        self._frames, self._shape = frames, shape
-        self._frame_nbytes = shape[0] * shape[1] * 3
-        self._capacity = min(len(frames), (self.pool_bytes - _POOL_SLACK) // self._frame_nbytes)
-        self._resident = self._capacity == len(frames)
-        if self._capacity < min(len(frames), max(DETECT_BATCH if self.detector is not None else 1, self.clip_size)):
+        nbytes = shape[0] * shape[1] * 3
+        capacity = min(len(frames), (self.pool_bytes - _POOL_SLACK) // nbytes)
+        self._frames, self._resident = frames, capacity == len(frames)
+        if capacity < min(len(frames), max(DETECT_BATCH if self.detector is not None else 1, self.clip_size)):
             raise ValueError("evaluator: frame_bytes %d holds %d frames of %d bytes, fewer than a detector batch or a window"
-                             % (self.pool_bytes, self._capacity, self._frame_nbytes))
-        need = self._capacity * self._frame_nbytes + _POOL_SLACK   # 3 readable bytes behind the last frame (af_hip.h)
-        if self._pool_dev is None or self._pool_dev.numel() < need:
-            self._pool_dev = None
-            with torch.inference_mode(False):
-                self._pool_dev = torch.empty(need, dtype=torch.uint8, device=self.device)
-
-    def _store_frames(self, ids, first_slot: int):
-        """host frames `ids` -> consecutive slots of the store from `first_slot`: pinned slots in turn, each filled by the aligner's
-        copy threads in bands of rows, one asynchronous copy per slot.  A frame whose pixels are not packed RGB bytes (a
-        channel-reversed view) costs a strided host pass here instead of a memcpy per band."""
-        from . import _lib
-        ids = list(ids)
-        h, w = self._shape[:2]
-        fb, row = self._frame_nbytes, w * 3
-        per_slot = max(1, _STAGE_BYTES // fb)
-        for i in range(0, len(ids), per_slot):
-            chunk = ids[i:i + per_slot]
-            used = len(chunk) * fb
-            slot = self._stage_slot(used)
-            base = slot[0].data_ptr()
-            host = slot[0].numpy()[:used].reshape(len(chunk), h, w, 3)
-            bands = max(1, min(h, -(-_COPY_THREADS // len(chunk)))) if used >= (1 << 20) else 1
-            jobs = []
-            for k, f in enumerate(chunk):
-                im = self._frames[f]
-                packed = im.strides[2] == 1 and im.strides[1] == 3 and im.strides[0] >= row
-                for t in range(bands):
-                    r0, r1 = h * t // bands, h * (t + 1) // bands
-                    if packed:
-                        jobs.append(_lib.StageRect(im.__array_interface__["data"][0] + r0 * im.strides[0], k * fb + r0 * row,
-                                                   im.strides[0], r1 - r0, row))
-                    else:
-                        jobs.append((host[k, r0:r1], im[r0:r1]))
-
-            def run(job):
-                if isinstance(job, tuple):
-                    np.copyto(job[0], job[1])
-                else:
-                    _lib.check(_lib.lib.af_stage_rows_u8(C.c_void_p(base), C.byref(job), 1), "stage_rows_u8")
-            if len(jobs) > 1:
-                list(_pool().map(run, jobs))
-            else:
-                run(jobs[0])
-            self._send_slot(slot, used, (first_slot + i) * fb)
+                             % (self.pool_bytes, capacity, nbytes))
+        self.source.open(shape, capacity)
 
     def _upload(self, track: _FrameTrack, lo: int, hi: int) -> np.ndarray:
         """the store slots of track positions [lo, hi): where the frames already sit when the whole video is resident, else the
         segment's frames are uploaded again into the front of the store"""
         if self._resident:
             return track.frame[lo:hi]
-        if hi - lo > self._capacity:
-            raise ValueError("evaluator: %d frames do not fit the frame store of %d" % (hi - lo, self._capacity))
-        self._store_frames(track.frame[lo:hi], 0)
+        if hi - lo > self.source.capacity:
+            raise ValueError("evaluator: %d frames do not fit the frame store of %d" % (hi - lo, self.source.capacity))
+        self.source.put([self._frames[f] for f in track.frame[lo:hi]], 0)
         return np.arange(hi - lo, dtype=np.int64)
 
     def _segments(self, track: _FrameTrack, windows):
         return [(0, track.n, windows)] if self._resident else super()._segments(track, windows)
-
-    def _fill_items(self, items, w: int, track: _FrameTrack, idx: np.ndarray, where: np.ndarray):
-        items["frame"][w], items["rx"][w], items["ry"][w] = where, track.rx[idx], track.ry[idx]
-
-    def _plan_source(self):
-        from . import _lib
-        h, w = self._shape[:2]
-        self._store_desc = _lib.FrameStore(self._pool_dev.numel(), self._frame_nbytes, w * 3, self._capacity, h, w, 0)
-        return C.byref(self._store_desc)
 
     # -- the detector stage --------------------------------------------------------------------------
     def _detect(self):
@@ -715,14 +738,13 @@ class VideoScorer(_WindowScorer):
         per batch, bit for bit"""
         if self.detector is None:
             raise ValueError("evaluator: no detector and no detections")
-        n, (h, w) = len(self._frames), self._shape[:2]
-        store = self._pool_dev[:self._capacity * self._frame_nbytes].view(self._capacity, h, w, 3)
+        n, store = len(self._frames), self.source
         found = []
         for lo in range(0, n, DETECT_BATCH):
             hi = min(lo + DETECT_BATCH, n)
             first = lo if self._resident else 0                    # not resident: every batch passes through the front of the store
-            self._store_frames(range(lo, hi), first)
-            rows, counts = self.detector.detect_device(store[first:first + hi - lo], max_count=10, min_score=0.5)
+            store.put(self._frames[lo:hi], first)
+            rows, counts = self.detector.detect_device(store.view(first, hi - lo), max_count=10, min_score=0.5)
             found.append(torch.cat([rows.view(torch.int32).reshape(hi - lo, -1), counts.reshape(hi - lo, 1)], 1))    # bits, no arithmetic
         back = torch.cat(found).cpu().numpy()                      # rows and counts of all frames in one copy: the first wait
         counts = back[:, -1]
@@ -737,16 +759,15 @@ class VideoScorer(_WindowScorer):
         ``TrackScorer.aligned_windows`` on the crops ``frame[y0:y1, x0:x1]`` cut on the host.  All frames are uploaded, so they
         must fit ``frame_bytes``."""
         frames = list(frames)
-        self.uploaded_bytes = 0
+        self.source.uploaded_bytes = 0
         with torch.cuda.device(self.device):
-            self._buffers()
             self._open_store(frames)
             if not self._resident:
                 raise ValueError("evaluator: %d frames do not fit frame_bytes %d" % (len(frames), self.pool_bytes))
-            track = _FrameTrack(infos, frame_ids, self._shape, rects)
+            track = _FrameTrack(infos, frame_ids, self.source.shape, rects)
             if track.n and (track.frame.min() < 0 or track.frame.max() >= len(frames)):
                 raise ValueError("evaluator: a frame index outside the %d frames" % len(frames))
-            self._store_frames(range(len(frames)), 0)
+            self.source.put(frames, 0)
             return self._aligned(track, windows)
 
     def score(self, frames, detections=None, threshold: float = 0.04) -> dict:
@@ -756,13 +777,12 @@ class VideoScorer(_WindowScorer):
         ``TrackScorer.score_video`` returns (``video_score``, ``pred_label``, ``preds``, ``clips``, ``frame_res``) for the tracks
         demo.py:235-238 builds, plus ``detections``, ``tracks`` (each face ``(box, lm5, score)``) and ``spans``."""
         frames = list(frames)
-        self.uploaded_bytes = 0
+        self.source.uploaded_bytes = 0
         if not frames:
             res = summarise([], [], threshold)
             res.update(clips=[], detections=[], tracks=[], spans=[])
             return res
         with torch.cuda.device(self.device):
-            self._buffers()
             self._open_store(frames)
             if detections is None:
                 detections = self._detect()
@@ -771,7 +791,7 @@ class VideoScorer(_WindowScorer):
                 if len(detections) != len(frames):
                     raise ValueError("evaluator: detections for %d frames, %d frames" % (len(detections), len(frames)))
                 if self._resident:
-                    self._store_frames(range(len(frames)), 0)
+                    self.source.put(frames, 0)
             tracks = multiple_tracking(detections)
             spans = [(0, len(detections))] * len(tracks)
             if len(tracks) == 0:
@@ -780,8 +800,8 @@ class VideoScorer(_WindowScorer):
             def resident_tracks():
                 for (start, end), faces in zip(spans, tracks):
                     assert end - start == len(faces)
-                    recs = crop_records(self._shape, [(f[0], f[1], _NO_LM68, f[-1]) for f in faces])
-                    yield start, _FrameTrack([info for _, info in recs], range(start, end), self._shape)
+                    recs = crop_records(self.source.shape, [(f[0], f[1], _NO_LM68, f[-1]) for f in faces])
+                    yield start, _FrameTrack([info for _, info in recs], range(start, end), self.source.shape)
             res = self._score_tracks(resident_tracks(), threshold)
         res.update(detections=detections, tracks=tracks, spans=spans)
         self._frames = None                                        # the host frames are the caller's

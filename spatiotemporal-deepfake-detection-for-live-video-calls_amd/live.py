@@ -6,7 +6,7 @@ a track holds ``clip_size`` frames and ``stride`` frames have passed since its l
 the 32 host crops and ``infer_scores`` (:318-339).  ``LiveCall`` is that method behind the tracker: ``step`` copies the captured
 frame ONCE into a device ring of the last ``ring_frames`` frames, a track keeps no pixels - per frame only ``(frame index, crop
 rectangle, landmark record)`` - and all windows that close on a step are fitted on the host with the aligner's own arithmetic
-(``aligner.estimate_batch_transform``), warped in one launch out of rectangles of the resident frames
+(``aligner.fit_window``), warped in one launch out of rectangles of the resident frames
 (``af_warp_affine_window_rects_bgr_u8`` for frames as they are captured, B, G, R; csrc/af_align.hip) and scored by one replay of a
 HIP graph of ``forward_clips_u8`` at the batch size they pad to.  One score read-back per step is the only wait.
 
@@ -15,40 +15,23 @@ or FaceMesh's as in :420-432; the 68 points are zeros as in :448 - the aligner f
 (:403), the Laplacian quality weight (:439-442: a face the caller rejects is simply not handed in that step) and everything
 ``_flush_and_infer`` does with a score after it exists (:340-358).  There is no CPU fallback: without the HIP library the calls fail.
 """
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from .evaluator import _POOL_SLACK, VideoScorer, _FrameTrack, _is_crop, get_crop_box
+from ._staging import is_crop
+from .aligner import STD_POINTS_256
+from .evaluator import RECTS, RECTS_BGR, FrameStore, WindowWarp, _clip_buffers, _FrameTrack, _network_device, _padded, get_crop_box, partition
 
-_LAUNCH = {"rgb": "af_warp_affine_window_rects_u8", "bgr": "af_warp_affine_window_rects_bgr_u8"}
+_FORMS = {"rgb": RECTS, "bgr": RECTS_BGR}
 
 
-class _FrameRing(VideoScorer):
-    """``VideoScorer``'s frame store as a ring of the call's last frames: its staging slots, table ring, plan call and launch, with
-    ONE clip buffer (the static input of the replayed forwards) and the warp entry point of the frames' channel order"""
-
-    _CLIP_BUFFERS = 1
-
-    def __init__(self, network, clip_size: int, size: int, batch: int, ring_frames: int, shape, launch: str):
-        nbytes = int(shape[0]) * int(shape[1]) * 3
-        super().__init__(None, network, clip_size, size, batch, ring_frames * nbytes + _POOL_SLACK)     # 3 readable bytes behind the last slot
-        self._LAUNCH = launch
-        self._shape, self._frame_nbytes, self._capacity, self._resident = tuple(shape), nbytes, int(ring_frames), True
-        with torch.cuda.device(self.device), torch.inference_mode(False):
-            self._pool_dev = torch.empty(self.pool_bytes, dtype=torch.uint8, device=self.device)
-            self._buffers()
-
-    def put(self, frame: np.ndarray, slot: int):
-        """host frame -> a pinned staging slot -> ring slot `slot`, asynchronous on the current stream"""
-        self._frames = [frame]
-        self._store_frames((0,), slot)
-        self._frames = None
-
-    def view(self, slot: int) -> torch.Tensor:
-        h, w = self._shape[:2]
-        return self._pool_dev[slot * self._frame_nbytes:(slot + 1) * self._frame_nbytes].view(h, w, 3)
+class _DeviceSide(NamedTuple):
+    """what a call keeps on the device for one frame size"""
+    store: FrameStore             # the last ``ring_frames`` frames, used as a ring
+    warp: WindowWarp              # the warp of the call's channel order out of it,
+    clip: torch.Tensor            # into this: ``max_batch`` clips, the static input of the replayed forwards
 
 
 class _TrackState:
@@ -104,7 +87,7 @@ class LiveCall:
         self.clip_size, self.size, self.stride = int(clip_size), int(size), int(stride)
         self.crop_scale, self.ring_frames = float(crop_scale), int(ring_frames)
         self.max_batch, self.drop_after = int(max_batch), int(drop_after)
-        if channel_order not in _LAUNCH:
+        if channel_order not in _FORMS:
             raise ValueError("live: channel_order 'bgr' or 'rgb', not %r" % (channel_order,))
         self.channel_order = channel_order
         if self.clip_size < 1 or self.stride < 1 or self.drop_after < 1:
@@ -118,14 +101,14 @@ class LiveCall:
         self._tracks = {}                  # tid -> _TrackState
         self._shape = None
         self._first = 0                    # the oldest frame index the ring may hold (moved by a re-open)
-        self._ring: Optional[_FrameRing] = None
-        self._scorers = {}                 # clips per forward -> LiveScorer
+        self._ring: Optional[_DeviceSide] = None     # for the current frame size
+        self._scorers = {}                 # clips per forward -> LiveScorer on the front of the ring's clip buffer
         self._done = None                  # recorded behind the last launch of every step
         self._host = None
 
     # -- the host side: af_realtime.py:401-505 ---------------------------------------------------------
     def step(self, frame: np.ndarray, faces: Sequence[Tuple]) -> List[Tuple]:
-        if not _is_crop(frame) or not frame.flags.c_contiguous:
+        if not is_crop(frame) or not frame.flags.c_contiguous:
             raise AssertionError("live: a frame must be a C-contiguous HxWx3 uint8 numpy array")
         self.frame_idx += 1
         H, W = frame.shape[:2]
@@ -180,13 +163,13 @@ class LiveCall:
         if self._ring is None or not max(self._first, self.frame_idx - self.ring_frames + 1) <= k <= self.frame_idx:
             raise ValueError("live: frame %d is not resident (frames %d .. %d are)"
                              % (k, max(self._first, self.frame_idx - self.ring_frames + 1), self.frame_idx))
-        return self._ring.view(k % self.ring_frames)
+        return self._ring.store.view(k % self.ring_frames)
 
     # -- the device side ---------------------------------------------------------------------------------
     def _open_ring(self, shape):
         """a ring for frames of `shape`; the entries of all tracks name frames of the old one and are dropped"""
         if self._ring is not None:
-            torch.cuda.synchronize(self._ring.device)                                  # nothing still reads the old ring or clip buffer
+            torch.cuda.synchronize(self._ring.store.device)                            # nothing still reads the old ring or clip buffer
         self._ring, self._scorers = None, {}
         self._ring = self._new_ring(shape)
         self._shape, self._first = tuple(shape), self.frame_idx
@@ -194,40 +177,47 @@ class LiveCall:
             tr.entries = []
 
     def _new_ring(self, shape):
-        return _FrameRing(self.network, self.clip_size, self.size, self.max_batch, self.ring_frames, shape, _LAUNCH[self.channel_order])
+        dev = _network_device(self.network)
+        with torch.cuda.device(dev):
+            store = FrameStore(dev)
+            store.open(shape, self.ring_frames)
+            warp = WindowWarp(_FORMS[self.channel_order], store, self.clip_size, self.size, self.max_batch)
+            return _DeviceSide(store, warp, _clip_buffers(1, self.max_batch, self.clip_size, self.size, dev)[0])
 
     def _store_frame(self, frame: np.ndarray, slot: int):
-        ring = self._ring
+        """host frame -> a pinned staging slot -> ring slot `slot`, asynchronous on the current stream"""
+        ring = self._ring.store
         with torch.cuda.device(ring.device):
             cur = torch.cuda.current_stream(ring.device)
             if self._done is None:
                 self._done = torch.cuda.Event()
             else:
                 cur.wait_event(self._done)
-            ring.put(frame, slot)
+            ring.put([frame], slot)
             self._done.record(cur)
         self.uploaded_bytes += frame.nbytes
 
     def _scorer(self, run: int):
         from .classifier import LiveScorer
         if run not in self._scorers:
-            self._scorers[run] = LiveScorer(self.network, self.clip_size, self.size, batch=run, clip=self._ring._clips[0][:run])
+            self._scorers[run] = LiveScorer(self.network, self.clip_size, self.size, batch=run, clip=self._ring.clip[:run])
         return self._scorers[run]
 
     def _score(self, ready) -> np.ndarray:
         """``ready``: ``[(tid, [(frame index, record)] * clip_size)]`` -> their scores, float32: one fit per window, one launch and
         one replay per ``max_batch`` windows, one read-back"""
-        ring, T = self._ring, self.clip_size
+        ring, T = self._ring.store, self.clip_size
+        std_points = STD_POINTS_256 * self.size / 256.0
         entries = [e for _, win in ready for e in win]
         track = _FrameTrack([rec for _, rec in entries], [k % self.ring_frames for k, _ in entries], self._shape)
         windows = [list(range(w * T, (w + 1) * T)) for w in range(len(ready))]
         with torch.cuda.device(ring.device):
             cur = torch.cuda.current_stream(ring.device)
             parts = []
-            for first, n, run in ring.partition(len(windows)):
-                ids, fits = ring._padded(track, windows, first, n, run)
+            for first, n, run in partition(len(windows), self.max_batch):
+                ids, fits = _padded(track, windows, first, n, run, std_points)
                 scorer = self._scorer(run)
-                ring._warp(track, [windows[k] for k in ids], track.frame, 0, scorer.clip, fits)
+                self._ring.warp(track, [windows[k] for k in ids], track.frame, 0, scorer.clip, fits)
                 parts.append(scorer.replay()[:n].to(torch.float32, copy=True))     # the next replay of this size overwrites its scores
             if self._host is None or self._host.numel() < len(windows):
                 self._host = torch.empty(max(64, len(windows)), dtype=torch.float32, pin_memory=True)

@@ -154,3 +154,43 @@ def test_non_contiguous_crops_and_other_stream_push():
     got68, got = sal.align_last(32)                              # current stream != the stream the crops were uploaded on
     torch.cuda.synchronize()
     assert (got.cpu().numpy() == want).all()
+
+
+def test_pinned_ring_rewrites_a_slot_only_behind_its_last_reader():
+    """_staging.PinnedRing, 3 slots, on a side stream: seven fillings in a row (4 KiB and 1 KiB in turn, so the second slot grows
+    once), each a byte pattern of its own, copied to the slot's device twin and read there by a device copy into row k of the
+    result, with the event behind that reader.  After ONE synchronise every row holds its own pattern: no slot was rewritten or
+    replaced under a copy or a reader.  Then the same ring without twins, the pinned slot copied into the caller's buffer."""
+    from af_mi355x import _staging
+    dev = _staging.cuda_device()
+    sizes = [4096, 1024] * 3 + [4096]
+    ring = _staging.PinnedRing(slots=3, min_bytes=1024)
+    want = torch.zeros((7, 4096), dtype=torch.uint8)
+    for k, n in enumerate(sizes):
+        want[k, :n] = 11 + 17 * k
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        got = torch.zeros((7, 4096), dtype=torch.uint8, device=dev)
+        seen = []
+        for k, n in enumerate(sizes):
+            slot = ring.acquire(n, dev)
+            assert slot is ring.last and slot.host.is_pinned() and slot.dev.device == dev and slot.host.numel() >= n <= slot.dev.numel()
+            seen.append((id(slot), slot.host.numel()))
+            slot.host[:n].fill_(11 + 17 * k)
+            slot.dev[:n].copy_(slot.host[:n], non_blocking=True)
+            got[k, :n].copy_(slot.dev[:n], non_blocking=True)       # the slot's last reader
+            slot.record()
+        side.synchronize()
+        assert torch.equal(got.cpu(), want)
+        assert [s[0] for s in seen[:3]] == [s[0] for s in seen[3:6]] and seen[6][0] == seen[0][0] and len({s[0] for s in seen}) == 3
+        assert [s[1] for s in seen] == [4096, 1024, 4096, 4096, 4096, 4096, 4096] and ring.turn == 7      # one growth: slot 1 at turn 4
+        got = torch.zeros((7, 4096), dtype=torch.uint8, device=dev)
+        for k, n in enumerate(sizes):
+            slot = ring.acquire(n)                                   # no device: the slot's event goes behind the copy out of it
+            slot.host[:n].fill_(11 + 17 * k)
+            got[k, :n].copy_(slot.host[:n], non_blocking=True)
+            slot.record()
+        side.synchronize()
+        assert torch.equal(got.cpu(), want)
+    twinless = _staging.PinnedRing(slots=3, min_bytes=1024).acquire(100)
+    assert twinless.dev is None and twinless.host.numel() == 1024

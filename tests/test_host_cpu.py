@@ -512,10 +512,44 @@ def test_stage_rows_host_helper_matches_numpy():
     assert _lib.lib.af_stage_rows_u8(C.c_void_p(dst.ctypes.data), bad, 1) != 0
 
 
+def _row_cut(images, diff, tfm, size):
+    """the rectangle of the canvas the size x size destination can sample (bilinear taps, fixed-point rounding: 3 pixels of margin)
+    -> per frame the rows of the crop inside it (a rows x bytes view, no copy), their (h, w, 3) shape and the paste offset moved
+    accordingly: the aligner's per-frame planning as Python did it before af_align_plan_u8"""
+    import numpy as np
+    m = np.asarray(tfm, dtype=np.float64).reshape(2, 3)
+    det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    if not np.isfinite(det) or abs(det) < 1e-12:
+        return images, [im.shape for im in images], diff     # singular map: OpenCV's D = 0 path samples around one point; keep everything
+    s = float(size - 1)
+    corners = np.array([[0.0, 0.0], [s, 0.0], [0.0, s], [s, s]])
+    # dst = M [x y 1]^T  ->  src = M^-1 (dst - t)
+    dx, dy = corners[:, 0] - m[0, 2], corners[:, 1] - m[1, 2]
+    xs = (m[1, 1] * dx - m[0, 1] * dy) / det
+    ys = (-m[1, 0] * dx + m[0, 0] * dy) / det
+    if not (np.isfinite(xs).all() and np.isfinite(ys).all()):
+        return images, [im.shape for im in images], diff
+    ylo, yhi = int(np.floor(ys.min())) - 3, int(np.ceil(ys.max())) + 4
+    out_images, shapes, out_diff = [], [], np.array(diff, dtype=np.int64, copy=True)
+    for i, im in enumerate(images):
+        x0, y0 = int(out_diff[i][0]), int(out_diff[i][1])
+        r0, r1, c1 = max(0, ylo - y0), min(im.shape[0], yhi - y0), im.shape[1]
+        if r1 <= r0:                                          # the warp never reaches this crop: one pixel keeps the frame table valid
+            r0, r1, c1 = 0, 1, 1
+        rows = im[r0:r1]
+        if rows.flags.c_contiguous:
+            out_images.append(rows.reshape(r1 - r0, im.shape[1] * 3)[:, :c1 * 3])
+        else:
+            out_images.append(np.ascontiguousarray(rows[:, :c1]).reshape(r1 - r0, c1 * 3))
+        shapes.append((r1 - r0, c1, 3))
+        out_diff[i][0], out_diff[i][1] = x0, y0 + r0
+    return out_images, shapes, out_diff
+
+
 def test_align_plan_host_helper_matches_the_python_path():
     """af_align_plan_u8 is host code (round 4: the aligner's per-frame planning - canvas fit, row cut, staging table, frame table - as
-    one C call): same tables as the Python path it replaces (FasterCropAlignXRay._clip_rect + _layout + launch_warps' frame table)
-    for a random clip, for a singular transform (nothing is cut), and the reference's ValueError case (a crop that sticks out)."""
+    one C call): same tables as the Python path it replaced (_row_cut below + FasterCropAlignXRay._layout + launch_warps' frame
+    table) for a random clip, for a singular transform (nothing is cut), and the reference's ValueError case (a crop that sticks out)."""
     import ctypes as C
     import numpy as np
     from af_mi355x import _lib, aligner
@@ -527,10 +561,8 @@ def test_align_plan_host_helper_matches_the_python_path():
         images.append(rng.integers(0, 256, size=(ih, iw, 3), dtype=np.uint8))
         diff.append((int(rng.integers(0, W - iw)), int(rng.integers(0, H - ih))))
     diff = np.array(diff, dtype=np.int64)
-    al = aligner.FasterCropAlignXRay.__new__(aligner.FasterCropAlignXRay)
-    al.image_size = 224
     for tfm in (np.array([[0.9, 0.2, -30.0], [-0.2, 0.9, 10.0]]), np.array([[1.0, 2.0, 3.0], [2.0, 4.0, 5.0]])):   # regular, singular
-        cut, shapes, d2 = al._clip_rect(images, diff, tfm)
+        cut, shapes, d2 = _row_cut(images, diff, tfm, 224)
         offs, total = aligner.FasterCropAlignXRay._layout(cut)
         crops = (_lib.AlignCrop * n)(*[_lib.AlignCrop(im.ctypes.data, im.strides[0], im.shape[0], im.shape[1], int(diff[i][0]), int(diff[i][1]))
                                        for i, im in enumerate(images)])
@@ -551,6 +583,92 @@ def test_align_plan_host_helper_matches_the_python_path():
     crops[4].x = W - images[4].shape[1] + 1                                    # one pixel over the right edge of the canvas
     rc = _lib.lib.af_align_plan_u8(crops, n, H, W, m, 224, rects, frames, C.byref(tot), C.byref(bad))
     assert rc != 0 and bad.value == 4
+
+
+def _reference_fit(infos, std_points):
+    """faster_crop_align_xray.py:21-66 up to the transform, as FasterCropAlignXRay.__call__, StreamingCropAligner.align_last and the
+    evaluator's per-window fit each had it written out"""
+    import numpy as np
+    from af_mi355x import aligner
+    boxes = np.array([box for _, _, _, box in infos])
+    five = np.array([l5 for _, l5, _, _ in infos])
+    left_top = boxes[:, :2].min(0)
+    w, h = boxes[:, 2:].max(0) - left_top
+    diff = boxes[:, :2] - left_top[None]
+    tfm, trans = aligner.estimate_batch_transform(five + diff[:, None, :], std_points)
+    return tfm, trans, h, w, diff
+
+
+def test_fit_window_is_the_arithmetic_its_three_copies_had():
+    """aligner.fit_window against that arithmetic: the same float64 operations in the same order, so equality is exact"""
+    import numpy as np
+    from af_mi355x import aligner
+    std = aligner.STD_POINTS_256 * 224 / 256.0
+    clips = [aligner.synthetic_clip(8, seed=0)[0], aligner.synthetic_clip(8, seed=1, mirrored=True)[0], aligner.synthetic_clip(1, seed=2)[0]]
+    mirrored = []
+    for infos in clips:
+        want = _reference_fit(infos, std)
+        got = aligner.fit_window(np.array([i[3] for i in infos]), np.array([i[1] for i in infos]), std)
+        assert len(got) == 5
+        for g, w_ in zip(got, want):
+            assert np.asarray(g).dtype == np.asarray(w_).dtype and np.array_equal(g, w_)
+        assert got[0].dtype == got[1].dtype == np.float64 and got[0].shape == (2, 3) and got[4].shape == (len(infos), 2)
+        mirrored.append(bool(np.linalg.det(got[0][:, :2]) < 0))
+        # ... and the callers hand on what it gives: the landmarks through `trans`
+        t68 = aligner.FasterCropAlignXRay(224)(infos)
+        assert np.array_equal(t68, aligner._apply(want[1], np.array([i[2] for i in infos]) + want[4][:, None, :]))
+    assert mirrored == [False, True, False]                     # the second clip takes the reflective solution
+
+
+def test_stage_rects_and_crop_rect_against_numpy(monkeypatch):
+    """_staging.crop_rect + stage_rects into numpy memory: packed views are copied from where they are (a column slice keeps its
+    larger pitch), a channel-reversed view through a contiguous copy, a one-row crop with pitch = row bytes; once in a single
+    call and once with the size threshold down so that the two copy threads each take a part.  Every byte of every crop at its
+    offset, and no byte between the crops touched."""
+    import ctypes as C
+    import numpy as np
+    from af_mi355x import _lib, _staging
+    rng = np.random.default_rng(17)
+    wide = rng.integers(0, 256, size=(70, 140, 3), dtype=np.uint8)
+    crops = [rng.integers(0, 256, size=(60, 50, 3), dtype=np.uint8),
+             rng.integers(0, 256, size=(66, 58, 3), dtype=np.uint8)[:, :, ::-1],      # channel-reversed view
+             wide[:, 30:110],                                                          # packed pixels, larger pitch
+             rng.integers(0, 256, size=(90, 70, 3), dtype=np.uint8)[10:11],           # one row
+             rng.integers(0, 256, size=(90, 70, 3), dtype=np.uint8)]
+    assert [_staging.packed_rgb(c) for c in crops] == [True, False, True, True, True] and not crops[2].flags.c_contiguous
+    assert all(_staging.is_crop(c) for c in crops) and not _staging.is_crop(crops[0].astype(np.int8)) and not _staging.is_crop(crops[0][..., 0])
+    offs, total = [], 48                                         # gaps in front of, between and behind the crops
+    for c in crops:
+        offs.append(total)
+        total += (c.size + 15) // 16 * 16 + 32
+    rects, keep = (_lib.StageRect * len(crops))(), []
+    for i, (c, o) in enumerate(zip(crops, offs)):
+        (address, pitch, rows, row), kept = _staging.crop_rect(c)
+        assert (rows, row) == (c.shape[0], c.shape[1] * 3) and (kept is c) == _staging.packed_rgb(c)
+        assert pitch == (row if rows == 1 else kept.strides[0]) and address == kept.ctypes.data
+        keep.append(kept)
+        rects[i] = _lib.StageRect(address, o, pitch, rows, row)
+    assert rects[2].src_pitch == 140 * 3 and rects[2].src == wide.ctypes.data + 90 and rects[3].src_pitch == 70 * 3
+    assert sum(c.size for c in crops) < _staging._SPLIT_BYTES   # as it is: one call
+
+    def staged(expect_split):
+        parts = []
+        real = _lib.lib.af_stage_rows_u8
+        monkeypatch.setattr(_lib.lib, "af_stage_rows_u8", lambda base, r, n: parts.append(n) or real(base, r, n))
+        dst = np.full(total, 0xA5, dtype=np.uint8)
+        _staging.stage_rects(dst.ctypes.data, rects, len(crops), total)
+        monkeypatch.setattr(_lib.lib, "af_stage_rows_u8", real)
+        assert sorted(parts) == ([2, 3] if expect_split else [5])
+        untouched = np.ones(total, dtype=bool)
+        for c, o in zip(crops, offs):
+            assert np.array_equal(dst[o:o + c.size], np.ascontiguousarray(c).reshape(-1))
+            untouched[o:o + c.size] = False
+        assert (dst[untouched] == 0xA5).all() and untouched.sum() >= 48 + 32 * len(crops)
+
+    staged(False)
+    monkeypatch.setattr(_staging, "_SPLIT_BYTES", 1 << 10)
+    staged(True)
+    assert str(_staging.cuda_device("cpu")) == "cpu"            # only a CUDA device without an index is filled in
 
 
 def _kinds(text):

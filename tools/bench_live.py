@@ -152,16 +152,16 @@ def play(call, frames, script, tid_offset=0):
 def kernel_times(call, iters):
     """device-event ms of the BGR launch on the call's ring against the RGB launch of the same table on a reversed copy of it"""
     from af_mi355x import _lib
-    ring = call._ring
-    table = ring._tables[(ring._table_turn - 1) % len(ring._tables)][1]      # the table the last full batch left on the device
+    ring = call._ring.store
+    table = call._ring.warp.tables.last.dev                                      # the table the last full batch left on the device
     n = int(np.frombuffer(table[:4].cpu().numpy().tobytes(), dtype=np.int32)[0])
-    pix = call.ring_frames * ring._frame_nbytes
-    swapped = torch.cat([ring._pool_dev[:pix].view(-1, 3).flip(1).contiguous().view(-1), ring._pool_dev[pix:]])
+    pix = call.ring_frames * ring.frame_nbytes
+    swapped = torch.cat([ring.dev[:pix].view(-1, 3).flip(1).contiguous().view(-1), ring.dev[pix:]])
     out = [torch.empty((n, CLIP, SIZE, SIZE, 3), dtype=torch.uint8, device=ring.device) for _ in range(2)]
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     ms = {"bgr": [], "rgb": []}
     for it in range(iters + 2):
-        for name, fn, src, dst in (("bgr", "af_warp_affine_window_rects_bgr_u8", ring._pool_dev, out[0]),
+        for name, fn, src, dst in (("bgr", "af_warp_affine_window_rects_bgr_u8", ring.dev, out[0]),
                                    ("rgb", "af_warp_affine_window_rects_u8", swapped, out[1])):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -221,9 +221,9 @@ def main():
                 with phase("faces %d: %s, repetition %d" % (faces, name, rep), args.phase_seconds):
                     if name == "new":
                         before = call.uploaded_bytes
-                        turns = call._ring._table_turn
+                        turns = call._ring.warp.tables.turn
                         r = play(call, frames, script, tid_offset=1000 * (rep + 1))      # new tids: the tracks start empty
-                        sent = call.uploaded_bytes - before + (call._ring._table_turn - turns) * call._ring.table_bytes
+                        sent = call.uploaded_bytes - before + (call._ring.warp.tables.turn - turns) * call._ring.warp.table_bytes
                     else:
                         parent.reset()
                         before = parent.uploaded_bytes

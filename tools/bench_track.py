@@ -112,13 +112,13 @@ def main():
             for first, n, run in scorer.partition(len(windows)):
                 batch = windows[first:first + n]
                 t0 = time.perf_counter()
-                fits = [scorer._fit(track, idx) for idx in batch]
+                fits = [evaluator._fit(track, idx, scorer.std_points) for idx in batch]
                 st["fits_host_ms"] += (time.perf_counter() - t0) * 1e3
                 batch, fits = batch + [batch[-1]] * (run - n), fits + [fits[-1]] * (run - n)
                 e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                 t0 = time.perf_counter()
                 e[0].record()
-                scorer._warp(track, batch, offs, 0, scorer._clips[0][:run], fits)
+                scorer.warp(track, batch, offs, 0, scorer._clips[0][:run], fits)
                 e[1].record()
                 st["table_and_launch_host_ms"] += (time.perf_counter() - t0) * 1e3
                 net.forward_clips_u8(scorer._clips[0][:run], return_scores=True)
@@ -132,20 +132,20 @@ def main():
         if "kernel" not in out:                                   # the warp does not depend on the classifier's dtype
             n16 = windows[:16]
             last = max(max(w) for w in n16) + 1
-            fits = [scorer._fit(track, idx) for idx in n16]
+            fits = [evaluator._fit(track, idx, scorer.std_points) for idx in n16]
             buf_new, buf_old = scorer._clips[0], scorer._clips[1]
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            scorer._warp(track, n16, offs, 0, buf_new, fits)          # leaves the batch's table in the slot it used
-            table = scorer._tables[(scorer._table_turn - 1) % len(scorer._tables)][1].clone()
+            scorer.warp(track, n16, offs, 0, buf_new, fits)          # leaves the batch's table in the slot it used
+            table = scorer.warp.tables.last.dev.clone()
             sync()
 
             def launch_new():
-                _lib.check(_lib.lib.af_warp_affine_windows_u8(C.c_void_p(scorer._pool_dev.data_ptr()), C.c_void_p(table.data_ptr()), 16, 32, 224,
+                _lib.check(_lib.lib.af_warp_affine_windows_u8(C.c_void_p(scorer.source.dev.data_ptr()), C.c_void_p(table.data_ptr()), 16, 32, 224,
                                                               C.c_void_p(buf_new.data_ptr()), stream), "warp_affine_windows_u8")
 
             def launch_old():
                 for w, (idx, (tfm, h, wd, diff)) in enumerate(zip(n16, fits)):
-                    al.launch_warps(scorer._pool_dev, [int(offs[j]) for j in idx], [crops[j].shape for j in idx], diff, h, wd, tfm, buf_old[w])
+                    al.launch_warps(scorer.source.dev, [int(offs[j]) for j in idx], [crops[j].shape for j in idx], diff, h, wd, tfm, buf_old[w])
 
             def timed(fn):
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

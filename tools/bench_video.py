@@ -162,14 +162,14 @@ def main():
         for _ in range(args.kernel_iters):
             for name, sc, tr, offs in (("rects", vs, vtrack, voffs), ("pool", ts, ttrack, toffs)):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                slot = sc._tables[(sc._table_turn - 1) % 3]         # the table the last _warp left on the device: launch it again
+                table = sc.warp.tables.last.dev                     # the table the last warp left on the device: launch it again
                 stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
                 if _ == 0:
-                    sc._warp(tr, windows, offs, 0, got)
+                    sc.warp(tr, windows, offs, 0, got, [evaluator._fit(tr, idx, sc.std_points) for idx in windows])
                     torch.cuda.synchronize()
                     continue
                 e0.record()
-                _lib.check(getattr(_lib.lib, sc._LAUNCH)(C.c_void_p(sc._pool_dev.data_ptr()), C.c_void_p(slot[1].data_ptr()), 16, 32, 224,
+                _lib.check(getattr(_lib.lib, sc.warp.form.launch)(C.c_void_p(sc.source.dev.data_ptr()), C.c_void_p(table.data_ptr()), 16, 32, 224,
                                                          C.c_void_p(got.data_ptr()), stream), "launch")
                 e1.record()
                 torch.cuda.synchronize()
