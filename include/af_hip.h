@@ -457,6 +457,27 @@ int af_warp_affine_window_rects_u8(const void* store, const void* table, int n_w
  * reads; the exchange is a choice of which accumulated channel goes to which byte of the store.  (Added within ABI 6.) */
 int af_warp_affine_window_rects_bgr_u8(const void* store, const void* table, int n_windows, int clip_size, int size, void* out, void* stream);
 
+/* The quality gate's pixel part for every face of a frame in ONE launch, out of rectangles of resident frames: the reference's
+ *     small = cv2.resize(crop, (max(1, w // 2), max(1, h // 2)), interpolation=cv2.INTER_AREA)
+ *     lap   = cv2.Laplacian(cv2.cvtColor(small, cv2.COLOR_RGB2GRAY), cv2.CV_64F).var()
+ * (test/af_realtime.py:265-267, :191-192) as three exact integers per rectangle; the arithmetic is stated in csrc/af_quality.hip.
+ *   store / desc: the frame store as for the window warp (device pixels, host description); no slack bytes are asked for;
+ *   rects[i]: HOST array; frame, (rx, ry) and (ih, iw) name the rectangle, x / y / reserved are not read;
+ *   bgr: 0 - a pixel's bytes are R, G, B; non-zero - B, G, R;
+ *   sums: DEVICE array of n records: n_px = dw * dh, s1 = sum of the Laplacian, s2 = sum of its squares over the half-size grey
+ *     image (dw = max(1, iw / 2), dh = max(1, ih / 2)); the variance is (n_px * s2 - s1 * s1) / n_px^2.  Cleared and filled on
+ *     `stream`; integer sums, so identical from run to run whatever the order of the rectangles;
+ *   grey: null, or (tests) a DEVICE buffer of grey_bytes >= sum of dw * dh bytes that receives the grey images one behind the other.
+ * AF_ERR_ARG: more than AF_QUALITY_MAX_RECTS rectangles, a rectangle that leaves its frame or names a frame outside the store.
+ * (Added within ABI 6.) */
+#define AF_QUALITY_MAX_RECTS 64
+typedef struct af_quality_sums {
+    int64_t s1, s2;
+    int32_t n_px, reserved;
+} af_quality_sums;
+int af_face_quality_u8(const void* store, const af_frame_store* desc, const af_frame_rect* rects, int n, int bgr, af_quality_sums* sums,
+                       void* grey, int64_t grey_bytes, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,

@@ -9,7 +9,10 @@ def __getattr__(name):
     if name in ("VideoScorer", "TrackScorer"):
         from . import evaluator
         return getattr(evaluator, name)
-    if name == "LiveCall":
+    if name in ("LiveCall", "RealtimeCall", "FaceQuality"):
         from . import live
-        return live.LiveCall
+        return getattr(live, name)
+    if name == "ByteTracker":
+        from . import tracker
+        return tracker.ByteTracker
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -55,6 +55,13 @@ class FrameRect(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("frame", "rx", "ry", "ih", "iw", "x", "y", "reserved")]
 
 
+class QualitySums(C.Structure):
+    _fields_ = [("s1", C.c_int64), ("s2", C.c_int64), ("n_px", C.c_int32), ("reserved", C.c_int32)]
+
+
+QUALITY_MAX_RECTS = 64
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n", "t", "h", "w", "c", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw", "to", "ho", "wo", "dtype",
@@ -159,6 +166,8 @@ ABI = {
                                           C.c_void_p, C.c_void_p]),
     "af_warp_affine_window_rects_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "af_warp_affine_window_rects_bgr_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "af_face_quality_u8": (C.c_int, [C.c_void_p, C.POINTER(FrameStore), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p]),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6

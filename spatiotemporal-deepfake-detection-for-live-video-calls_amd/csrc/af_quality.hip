@@ -1,0 +1,215 @@
+// The quality gate's pixel part for every face of a frame in one launch: the reference's _frame_quality_weight (test/af_realtime.py
+// :265-267) with variance_of_laplacian (:191-192),
+//     small = cv2.resize(crop_rgb, (max(1, w // 2), max(1, h // 2)), interpolation=cv2.INTER_AREA)
+//     lap   = cv2.Laplacian(cv2.cvtColor(small, cv2.COLOR_RGB2GRAY), cv2.CV_64F).var()
+// over rectangles of frames that are resident on the device (af_hip.h: af_frame_store / af_frame_rect), so no crop is cut on the host.
+//
+// Arithmetic (a restatement of OpenCV 4.x - resize.cpp, color_rgb, deriv.cpp; like the warp of af_align.hip it cannot be pinned
+// against cv2 itself where this is built, only against tests/quality_ref.py and the hand-worked cases of tests/test_realtime_host.py):
+//   sizes      dw = max(1, w / 2), dh = max(1, h / 2)
+//   half size  per channel, to uint8:  w == 2 dw and h == 2 dh: (a + b + c + d + 2) >> 2;  both w / dw and h / dh whole: the integer
+//              box sum times fp32 1 / area, rounded half to even;  otherwise OpenCV's area table: cell bounds in fp64 (scale = w / dw;
+//              the first and last partial source pixel weigh overlap / cellWidth and count when the overlap exceeds 1e-3, whole
+//              pixels weigh 1 / cellWidth), weights cast to fp32, fp32 accumulation along x in table order, then over the rows with
+//              their weights, rounded half to even and saturated.  No contraction: __dmul_rn / __dadd_rn / __fmul_rn / __fadd_rn.
+//   grey       (R * 9798 + G * 19235 + B * 3735 + 16384) >> 15 on the resized bytes
+//   Laplacian  up + down + left + right - 4 * centre with BORDER_REFLECT_101 (-1 -> 1, n -> n - 2; a dimension of 1 -> 0): an integer in
+//              [-1020, 1020]
+//   sums       S1 = sum L, S2 = sum L^2 (64-bit), n_px = dw * dh; the host forms lap = (n_px * S2 - S1^2) / n_px^2.
+//
+// Shape: a workgroup of 256 threads takes one 8 x 32 tile of one rectangle's half-size image, builds the tile's grey bytes with a
+// halo of one (reflected) pixel in LDS, applies the stencil, reduces in the wave and adds the tile's two totals to the rectangle's
+// 64-bit accumulators with global integer atomics - integer addition commutes, so the sums do not depend on the order the tiles
+// finish in.  The accumulators are cleared by a hipMemsetAsync in front of the launch, on the same stream.  Rectangles are tens:
+// they and the prefix table of their tiles travel as kernel arguments.  Byte work on a few hundred KB; nothing here is tuned.
+#include "af_common.h"
+
+namespace af {
+
+constexpr int Q_TH = 8, Q_TW = 32;                  // the tile of half-size pixels one workgroup takes
+constexpr int Q_GH = Q_TH + 2, Q_GW = Q_TW + 2;     // with its halo
+
+struct QualityRect {
+    int32_t frame, x0, y0, w, h;
+    int32_t first_tile;                             // prefix sum of the tiles of the rectangles before this one
+    int32_t grey_offset;                            // prefix sum of their dw * dh (the debug image's place)
+    int32_t reserved;
+};
+
+struct QualityArgs {
+    const unsigned char* store;
+    af_quality_sums* sums;
+    unsigned char* grey;                            // null outside tests
+    long long frame_stride, row_pitch;
+    int n, total_tiles, bgr, reserved;
+    QualityRect r[AF_QUALITY_MAX_RECTS];
+};
+
+__device__ __forceinline__ int reflect101(int i, int n) { return n == 1 ? 0 : (i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i)); }
+
+__device__ __forceinline__ int round_sat_u8(float v) {          // saturate_cast<uchar>(float): cvRound (half to even), then clamp
+    const int r = (int)rintf(v);
+    return r < 0 ? 0 : (r > 255 ? 255 : r);
+}
+
+// One destination index of computeResizeAreaTab: the whole source pixels [s1, s2) at weight `mid`, the partial one s1 - 1 in front
+// at `first` and the partial one s2 behind at `last` (each only if `has_*`).
+struct AreaCell {
+    int s1, s2;
+    float first, mid, last;
+    bool has_first, has_last;
+};
+
+__device__ __forceinline__ AreaCell area_cell(int d, int ssize, int dsize) {
+    const double scale = (double)ssize / (double)dsize;
+    const double f1 = __dmul_rn((double)d, scale), f2 = __dadd_rn(f1, scale);
+    const double cell = fmin(scale, __dadd_rn((double)ssize, -f1));
+    int s1 = (int)ceil(f1), s2 = (int)floor(f2);
+    s2 = min(s2, ssize - 1);
+    s1 = min(s1, s2);
+    AreaCell c;
+    c.s1 = s1; c.s2 = s2;
+    const double lead = __dadd_rn((double)s1, -f1), tail = __dadd_rn(f2, -(double)s2);
+    c.has_first = lead > 1e-3;
+    c.has_last = tail > 1e-3;
+    c.first = (float)(lead / cell);
+    c.mid = (float)(1.0 / cell);
+    c.last = (float)(fmin(fmin(tail, 1.0), cell) / cell);
+    return c;
+}
+
+// the grey byte at (gx, gy) of the rectangle's half-size image; `src` is the rectangle's first byte
+__device__ int grey_at(const unsigned char* src, long long pitch, int w, int h, int dw, int dh, int gx, int gy, int bgr) {
+    int ch[3];
+    if (w == 2 * dw && h == 2 * dh) {
+        const unsigned char* p = src + (long long)(2 * gy) * pitch + (long long)(2 * gx) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ch[c] = (p[c] + p[3 + c] + p[pitch + c] + p[pitch + 3 + c] + 2) >> 2;
+    } else if (w % dw == 0 && h % dh == 0) {
+        const int kx = w / dw, ky = h / dh;
+        const float inv = (float)(1.0 / (double)(kx * ky));       // == 1.f / area: 53 bits round twice harmlessly for a quotient of small integers
+        int sum[3] = {0, 0, 0};
+        for (int y = 0; y < ky; ++y) {
+            const unsigned char* p = src + (long long)(gy * ky + y) * pitch + (long long)(gx * kx) * 3;
+            for (int x = 0; x < kx; ++x)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) sum[c] += p[x * 3 + c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ch[c] = round_sat_u8(__fmul_rn((float)sum[c], inv));
+    } else {
+        const AreaCell cx = area_cell(gx, w, dw), cy = area_cell(gy, h, dh);
+        float acc[3] = {0.f, 0.f, 0.f};
+        bool started = false;
+        for (int sy = cy.has_first ? cy.s1 - 1 : cy.s1; sy <= (cy.has_last ? cy.s2 : cy.s2 - 1); ++sy) {
+            const float beta = sy < cy.s1 ? cy.first : (sy < cy.s2 ? cy.mid : cy.last);
+            const unsigned char* p = src + (long long)sy * pitch;
+            float buf[3] = {0.f, 0.f, 0.f};
+            for (int sx = cx.has_first ? cx.s1 - 1 : cx.s1; sx <= (cx.has_last ? cx.s2 : cx.s2 - 1); ++sx) {
+                const float alpha = sx < cx.s1 ? cx.first : (sx < cx.s2 ? cx.mid : cx.last);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) buf[c] = __fadd_rn(buf[c], __fmul_rn((float)p[sx * 3 + c], alpha));
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] = started ? __fadd_rn(acc[c], __fmul_rn(beta, buf[c])) : __fmul_rn(beta, buf[c]);
+            started = true;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ch[c] = round_sat_u8(acc[c]);
+    }
+    const int r = bgr ? ch[2] : ch[0], b = bgr ? ch[0] : ch[2];
+    return (r * 9798 + ch[1] * 19235 + b * 3735 + 16384) >> 15;
+}
+
+__global__ __launch_bounds__(256) void face_quality_kernel(const QualityArgs a) {
+    __shared__ unsigned char g[Q_GH][Q_GW + 2];
+    __shared__ long long part[2][4];
+    const int tile = blockIdx.x;
+    if (tile >= a.total_tiles) return;
+    int k = 0;
+    while (k + 1 < a.n && a.r[k + 1].first_tile <= tile) ++k;     // tens of rectangles: a scan
+    const QualityRect r = a.r[k];
+    const int dw = max(1, r.w / 2), dh = max(1, r.h / 2);
+    const int tiles_x = (dw + Q_TW - 1) / Q_TW;
+    const int local = tile - r.first_tile;
+    const int ty0 = (local / tiles_x) * Q_TH, tx0 = (local % tiles_x) * Q_TW;
+    const unsigned char* src = a.store + (long long)r.frame * a.frame_stride + (long long)r.y0 * a.row_pitch + (long long)r.x0 * 3;
+
+    for (int i = threadIdx.x; i < Q_GH * Q_GW; i += 256) {
+        const int gr = i / Q_GW, gc = i - gr * Q_GW;
+        const int y = ty0 - 1 + gr, x = tx0 - 1 + gc;             // half-size coordinates before the border rule
+        int v = 0;
+        if (y <= dh && x <= dw) {                                 // beyond n nothing reads the cell
+            const int yy = reflect101(y, dh), xx = reflect101(x, dw);
+            v = grey_at(src, a.row_pitch, r.w, r.h, dw, dh, xx, yy, a.bgr);
+            if (a.grey && gr >= 1 && gr <= Q_TH && gc >= 1 && gc <= Q_TW && y < dh && x < dw)
+                a.grey[(long long)r.grey_offset + (long long)y * dw + x] = (unsigned char)v;
+        }
+        g[gr][gc] = (unsigned char)v;
+    }
+    __syncthreads();
+
+    const int ly = threadIdx.x / Q_TW, lx = threadIdx.x % Q_TW;
+    long long s1 = 0, s2 = 0;
+    if (ty0 + ly < dh && tx0 + lx < dw) {
+        const int L = (int)g[ly][lx + 1] + (int)g[ly + 2][lx + 1] + (int)g[ly + 1][lx] + (int)g[ly + 1][lx + 2] - 4 * (int)g[ly + 1][lx + 1];
+        s1 = L;
+        s2 = (long long)L * L;
+    }
+    for (int off = 32; off > 0; off >>= 1) {                      // wave64
+        s1 += __shfl_down(s1, off, 64);
+        s2 += __shfl_down(s2, off, 64);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { part[0][wave] = s1; part[1][wave] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const long long t1 = part[0][0] + part[0][1] + part[0][2] + part[0][3];
+        const long long t2 = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+        af_quality_sums* out = a.sums + k;
+        atomicAdd((unsigned long long*)&out->s1, (unsigned long long)t1);      // two's complement: the signed sum of the parts
+        atomicAdd((unsigned long long*)&out->s2, (unsigned long long)t2);
+        if (local == 0) out->n_px = dw * dh;
+    }
+}
+
+}  // namespace af
+
+extern "C" int af_face_quality_u8(const void* store, const af_frame_store* desc, const af_frame_rect* rects, int n, int bgr,
+                                  af_quality_sums* sums, void* grey, int64_t grey_bytes, void* stream) {
+    using namespace af;
+    AF_REQUIRE(store && desc && rects && sums, "face_quality: null argument");
+    AF_REQUIRE(n >= 0 && n <= AF_QUALITY_MAX_RECTS, "face_quality: %d rectangles (at most %d per launch)", n, AF_QUALITY_MAX_RECTS);
+    if (n == 0) return AF_OK;
+    const af_frame_store& s = *desc;
+    AF_REQUIRE(s.n_frames > 0 && s.height > 0 && s.width > 0 && s.height <= 32767 && s.width <= 32767, "face_quality: store of %d frames %dx%d",
+               s.n_frames, s.width, s.height);
+    const int64_t frame_span = (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3;
+    AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span,
+               "face_quality: row pitch %lld, frame stride %lld for frames of %dx%d", (long long)s.row_pitch, (long long)s.frame_stride, s.width, s.height);
+    AF_REQUIRE(s.store_bytes >= (int64_t)(s.n_frames - 1) * s.frame_stride + frame_span, "face_quality: %d frames do not fit a store of %lld bytes",
+               s.n_frames, (long long)s.store_bytes);
+    QualityArgs a;
+    a.store = (const unsigned char*)store; a.sums = sums; a.grey = (unsigned char*)grey;
+    a.frame_stride = s.frame_stride; a.row_pitch = s.row_pitch; a.n = n; a.bgr = bgr ? 1 : 0; a.reserved = 0;
+    int64_t tiles = 0, grey_total = 0;
+    for (int i = 0; i < n; ++i) {
+        const af_frame_rect& r = rects[i];
+        AF_REQUIRE(r.frame >= 0 && r.frame < s.n_frames && r.ih > 0 && r.iw > 0 && r.rx >= 0 && r.ry >= 0 &&
+                   (int64_t)r.rx + r.iw <= s.width && (int64_t)r.ry + r.ih <= s.height,
+                   "face_quality: rectangle %d: %dx%d at (%d,%d) of frame %d leaves the %d frames of %dx%d", i, r.iw, r.ih, r.rx, r.ry, r.frame,
+                   s.n_frames, s.width, s.height);
+        const int dw = r.iw / 2 > 1 ? r.iw / 2 : 1, dh = r.ih / 2 > 1 ? r.ih / 2 : 1;
+        a.r[i] = QualityRect{r.frame, r.rx, r.ry, r.iw, r.ih, (int32_t)tiles, (int32_t)grey_total, 0};
+        tiles += (int64_t)((dw + Q_TW - 1) / Q_TW) * ((dh + Q_TH - 1) / Q_TH);
+        grey_total += (int64_t)dw * dh;
+        AF_REQUIRE(tiles <= 0x7fffffff && grey_total <= 0x7fffffff, "face_quality: too many pixels");
+    }
+    AF_REQUIRE(!grey || grey_bytes >= grey_total, "face_quality: grey image buffer of %lld bytes, %lld needed", (long long)grey_bytes, (long long)grey_total);
+    a.total_tiles = (int)tiles;
+    hipError_t e = hipMemsetAsync(sums, 0, sizeof(af_quality_sums) * (size_t)n, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(AF_ERR_LAUNCH, "face_quality: hipMemsetAsync: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(face_quality_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    AF_CHECK_LAUNCH("face_quality_kernel");
+    return AF_OK;
+}

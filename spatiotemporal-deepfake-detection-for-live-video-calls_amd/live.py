@@ -13,7 +13,8 @@ HIP graph of ``forward_clips_u8`` at the batch size they pad to.  One score read
 What stays with the caller: the detector and the tracker (``faces`` carry their track ids), the five landmarks per face (YuNet's,
 or FaceMesh's as in :420-432; the 68 points are zeros as in :448 - the aligner fits on the five), the self-view exclusion
 (:403), the Laplacian quality weight (:439-442: a face the caller rejects is simply not handed in that step) and everything
-``_flush_and_infer`` does with a score after it exists (:340-358).  There is no CPU fallback: without the HIP library the calls fail.
+``_flush_and_infer`` does with a score after it exists (:340-358).  ``RealtimeCall`` further down is the caller that supplies all of
+these: the captured frame is its only input.  There is no CPU fallback: without the HIP library the calls fail.
 """
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
@@ -23,6 +24,7 @@ import torch
 from ._staging import is_crop
 from .aligner import STD_POINTS_256
 from .evaluator import RECTS, RECTS_BGR, FrameStore, WindowWarp, _clip_buffers, _FrameTrack, _network_device, _padded, get_crop_box, partition
+from .tracker import ByteTracker, STrack, iou_distance
 
 _FORMS = {"rgb": RECTS, "bgr": RECTS_BGR}
 
@@ -107,16 +109,31 @@ class LiveCall:
         self._host = None
 
     # -- the host side: af_realtime.py:401-505 ---------------------------------------------------------
-    def step(self, frame: np.ndarray, faces: Sequence[Tuple]) -> List[Tuple]:
+    def step(self, frame: np.ndarray, faces: Sequence[Tuple], alive: Sequence = ()) -> List[Tuple]:
+        self.admit(frame)
+        return self.advance(faces, alive)
+
+    def admit(self, frame: np.ndarray) -> int:
+        """the first half of ``step``: the captured frame goes into the ring, once (:373-376); returns its index.  Between
+        ``admit`` and ``advance`` a caller may read the frame where it now lies (``frame_view``): a detector, the quality gate."""
         if not is_crop(frame) or not frame.flags.c_contiguous:
             raise AssertionError("live: a frame must be a C-contiguous HxWx3 uint8 numpy array")
         self.frame_idx += 1
-        H, W = frame.shape[:2]
         if self._shape != frame.shape:
             self._open_ring(frame.shape)
         self._store_frame(frame, self.frame_idx % self.ring_frames)
+        return self.frame_idx
+
+    def advance(self, faces: Sequence[Tuple], alive: Sequence = ()) -> List[Tuple]:
+        """the second half of ``step``: the tracks move on by the faces of the admitted frame (:401-499).  ``alive``: tids that
+        were tracked on this frame but contribute no entry - no landmarks, or rejected by the quality gate (:407 against :431-442):
+        their ``missed`` count resets as for a face that was handed in, and nothing else happens to them."""
+        H, W = self._shape[:2]
         oldest = max(self._first, self.frame_idx - self.ring_frames + 1)
-        alive, ready = set(), []
+        alive, ready = set(alive), []
+        for tid in alive:                                                              # :409-411
+            if tid not in self._tracks:
+                self._tracks[tid] = _TrackState()
         for tid, tlbr, lm5 in faces:
             tlbr = np.asarray(tlbr, dtype=np.float32).reshape(4)
             alive.add(tid)                                                             # :407
@@ -225,3 +242,290 @@ class LiveCall:
             self._done.record(cur)
             cur.synchronize()
         return self._host[:len(windows)].numpy().copy()
+
+
+# ---- the quality gate: af_realtime.py:262-276 -------------------------------------------------------------------------------------
+
+def quality_weight(min_side: float, lap: float, q_weighting: bool = True, q_min_size_soft: int = 64, q_min_size_hard: int = 32,
+                   q_lap_soft: float = 20.0, q_lap_hard: float = 5.0) -> float:
+    """the weight ``_frame_quality_weight`` gives a crop whose shorter side is ``min_side`` and whose half-size Laplacian variance
+    is ``lap`` (:268-276): 0 under either hard limit, else 1 or the product of the two ramps between the hard and soft limits"""
+    if min_side < q_min_size_hard or lap < q_lap_hard:
+        return 0.0
+    if not q_weighting:
+        return 1.0
+    size_w = 1.0 if min_side >= q_min_size_soft else max(0.0, (min_side - q_min_size_hard) / max(1.0, (q_min_size_soft - q_min_size_hard)))
+    lap_w = 1.0 if lap >= q_lap_soft else max(0.0, (lap - q_lap_hard) / max(1e-6, (q_lap_soft - q_lap_hard)))
+    return float(size_w * lap_w)
+
+
+class FaceQuality:
+    """``FaceQuality(store, channel_order)(rects)`` -> ``[(min_side, lap), ...]``: the pixel part of the quality gate (:265-267,
+    :191-192) for every rectangle ``(slot, x0, y0, x1, y1)`` of the resident frames of ``store`` (an ``evaluator.FrameStore``) in
+    one launch of ``af_face_quality_u8`` (csrc/af_quality.hip) and one pinned read-back on the current stream - the only wait.  The
+    kernel returns three exact integers per rectangle; ``lap = (n_px * S2 - S1^2) / n_px^2`` is formed here from Python integers
+    with one fp64 division.  ``sums(rects, grey=True)`` also returns the half-size grey images (tests)."""
+
+    def __init__(self, store: FrameStore, channel_order: str = "bgr"):
+        from . import _lib                                        # fails loudly when libafhip.so is missing
+        if channel_order not in _FORMS:
+            raise ValueError("live: channel_order 'bgr' or 'rgb', not %r" % (channel_order,))
+        self.store, self.bgr = store, int(channel_order == "bgr")
+        self._fn = _lib.lib.af_face_quality_u8
+        self._dev = self._host = None
+
+    def sums(self, rects, grey: bool = False):
+        """-> ``[(n_px, S1, S2)]`` as Python integers (and, with ``grey``, the list of (dh, dw) uint8 grey images)"""
+        import ctypes as C
+        from . import _lib
+        from .evaluator import _RECT_DTYPE
+        n, store = len(rects), self.store
+        if n == 0:
+            return ([], []) if grey else []
+        items = np.zeros(n, dtype=_RECT_DTYPE)
+        for i, (slot, x0, y0, x1, y1) in enumerate(rects):
+            items[i] = (slot, x0, y0, y1 - y0, x1 - x0, 0, 0, 0)
+        halves = [(max(1, int(r["ih"]) // 2), max(1, int(r["iw"]) // 2)) for r in items]
+        rec = C.sizeof(_lib.QualitySums)
+        with torch.cuda.device(store.device):
+            cur = torch.cuda.current_stream(store.device)
+            if self._dev is None or self._dev.numel() < n * rec:
+                with torch.inference_mode(False):
+                    self._dev = torch.empty(max(n, _lib.QUALITY_MAX_RECTS) * rec, dtype=torch.uint8, device=store.device)
+                    self._host = torch.empty(self._dev.numel(), dtype=torch.uint8, pin_memory=True)
+            gbuf = torch.empty(sum(h * w for h, w in halves), dtype=torch.uint8, device=store.device) if grey else None
+            goff = 0
+            for lo in range(0, n, _lib.QUALITY_MAX_RECTS):                 # one launch for up to 64 faces
+                hi = min(n, lo + _lib.QUALITY_MAX_RECTS)
+                gn = sum(h * w for h, w in halves[lo:hi])
+                _lib.check(self._fn(C.c_void_p(store.dev.data_ptr()), store.plan_source(), C.c_void_p(items[lo:hi].ctypes.data), hi - lo, self.bgr,
+                                    C.c_void_p(self._dev.data_ptr() + lo * rec), C.c_void_p(gbuf.data_ptr() + goff if grey else None), gn,
+                                    C.c_void_p(cur.cuda_stream)), "face_quality_u8")
+                goff += gn
+            self._host[:n * rec].copy_(self._dev[:n * rec], non_blocking=True)
+            cur.synchronize()
+            raw = np.frombuffer(self._host.numpy()[:n * rec].tobytes(), dtype=np.dtype([("s1", "<i8"), ("s2", "<i8"), ("n_px", "<i4"), ("r", "<i4")]))
+            out = [(int(r["n_px"]), int(r["s1"]), int(r["s2"])) for r in raw]
+            if not grey:
+                return out
+            flat, images, off = gbuf.cpu().numpy(), [], 0
+            for h, w in halves:
+                images.append(flat[off:off + h * w].reshape(h, w).copy())
+                off += h * w
+            return out, images
+
+    def __call__(self, rects):
+        out = []
+        for (n_px, s1, s2), (_, x0, y0, x1, y1) in zip(self.sums(rects), rects):
+            out.append((float(min(y1 - y0, x1 - x0)), (n_px * s2 - s1 * s1) / (n_px * n_px)))
+        return out
+
+
+# ---- the whole live step: af_realtime.py:372-509 ----------------------------------------------------------------------------------
+
+class CallState:
+    """what ``track_faces`` keeps between frames: ``last_lm`` (:250) and ``_q_hist`` (:239)"""
+
+    def __init__(self):
+        import collections
+        self.last_lm = {}
+        self.q_hist = collections.defaultdict(lambda: collections.deque(maxlen=64))
+
+
+def in_exclude(box, H: int, W: int, exclude_rect) -> bool:
+    """the centre of ``box`` lies in the self-view rectangle, given in normalised coordinates (:311-315)"""
+    x1, y1, x2, y2 = box
+    cx, cy = 0.5 * (x1 + x2), 0.5 * (y1 + y2)
+    x1n, y1n, x2n, y2n = exclude_rect
+    return (x1n * W <= cx <= x2n * W) and (y1n * H <= cy <= y2n * H)
+
+
+def track_faces(state: CallState, frame_idx: int, shape, dets, online, quality, gate, mesh_every: int = 1, crop_scale: float = 0.6,
+                exclude_rect=(0.70, 0.70, 1.00, 1.00), landmarks=None, frame_view=None):
+    """The host part of ``RealtimeAF.step`` between the tracker and the window bookkeeping (:390-442), without a device call of
+    its own.  ``dets``: this frame's (N, 15) float32 YuNet rows, or None; ``online``: the tracker's tracks (``track_id``,
+    ``tlbr``); ``quality(rects)`` -> ``[(min_side, lap)]`` for rectangles ``(x0, y0, x1, y1)`` of this frame, called once with all
+    of them; ``gate(min_side, lap)`` -> the weight.  Returns ``(faces, alive, kept_boxes, rects)``: ``faces`` - ``(tid, tlbr
+    float32, lm5)`` of the tracks that go on to the windows; ``alive`` - the tids of the tracks that were kept past the self-view
+    exclusion but go no further (no landmarks, a degenerate crop box, or a weight of 0); ``kept_boxes`` as :407; ``rects`` as handed
+    to ``quality``.  The order of the skips is the reference's: an excluded track is not alive, a track skipped later is."""
+    H, W = int(shape[0]), int(shape[1])
+    det_tlbr = None
+    if dets is not None and len(dets) > 0:                                             # :391-396
+        dets = np.asarray(dets, dtype=np.float32)
+        det_tlbr = np.concatenate([dets[:, :2], dets[:, :2] + dets[:, 2:4]], axis=1).astype(np.float32)
+    kept_boxes, candidates, alive = {}, [], set()
+    for tr in online or []:                                                            # :401
+        if in_exclude(tr.tlbr, H, W, exclude_rect):                                    # :403
+            continue
+        tid = tr.track_id
+        tlbr = np.asarray(tr.tlbr).astype(np.float32).copy()
+        kept_boxes[tid] = tlbr                                                         # :407
+        alive.add(tid)
+        yunet_lm5 = None
+        if det_tlbr is not None:                                                       # :413-418
+            ious = 1.0 - iou_distance(np.array([tr.tlbr], dtype=np.float32), det_tlbr)[0]
+            k = int(np.argmax(ious))
+            if ious[k] >= 0.4:
+                yunet_lm5 = dets[k][5:15].reshape(5, 2)
+        fm = None
+        if (frame_idx % mesh_every) == 0 or (tid not in state.last_lm):                # :421-426
+            fm = landmarks(frame_view, tr.tlbr) if landmarks is not None else None
+            if fm is None and yunet_lm5 is not None:
+                fm = {"lm5": yunet_lm5, "lm68": None}
+            if fm is not None:
+                state.last_lm[tid] = {**fm, "frame_idx": frame_idx}
+        else:                                                                          # :427-430
+            cached = state.last_lm.get(tid)
+            if cached is not None:
+                fm = {"lm5": cached["lm5"], "lm68": cached["lm68"]}
+            elif yunet_lm5 is not None:
+                fm = {"lm5": yunet_lm5, "lm68": None}
+        if fm is None:                                                                 # :431-432
+            continue
+        x1, y1, x2, y2 = map(int, get_crop_box((H, W), tlbr, scale=crop_scale))        # :435-436, on the float32 box as LiveCall
+        if x2 <= x1 or y2 <= y1:                                                       # :437
+            continue
+        candidates.append((tid, tlbr, np.asarray(fm["lm5"], dtype=np.float32), (x1, y1, x2, y2)))
+    rects = [c[3] for c in candidates]
+    faces = []
+    for (tid, tlbr, lm5, _), (min_side, lap) in zip(candidates, quality(rects) if rects else []):
+        state.q_hist[tid].append((float(min_side), float(lap)))                        # :440
+        if gate(min_side, lap) <= 0.0:                                                 # :441-442
+            continue
+        faces.append((tid, tlbr, lm5))
+    return faces, alive - {f[0] for f in faces}, kept_boxes, rects
+
+
+class RealtimeCall:
+    """``RealtimeCall(network, detector).step(frame_bgr)`` -> ``[(tid, score), ...]``: the whole of ``RealtimeAF.step``
+    (test/af_realtime.py:372-509) with the captured frame as its only input, by composition over ``LiveCall``.
+
+    One host-to-device copy per frame: ``LiveCall.admit`` puts the frame into the ring, the detector reads it there
+    (``detector.detect(call.frame_view(k)[None])``), the quality gate is one ``FaceQuality`` launch over rectangles of the same
+    resident frame, and a window that closes is warped out of it.  A step waits for the device at most twice without a window
+    close (the detections, the quality sums) and three times with one (the scores).
+
+    ``detector``: a ``YuNet`` (``detector=None`` with ``modelPath`` builds one with ``conf``, 0.3, 5000 as :219) or any object with
+    ``detect(frames_u8) -> (rows, counts)`` device tensors.  The tracker is ``tracker.ByteTracker`` with ``track_thresh``,
+    ``track_buffer``, ``match_thresh`` at 30 fps.  ``landmarks``: an optional callable ``(frame_view, tlbr) -> {'lm5', 'lm68'} |
+    None`` where the reference has FaceMesh; without it the call behaves as the reference does when FaceMesh finds nothing: YuNet's
+    five points, with the ``last_lm`` cache.  Every other keyword is ``RealtimeAF``'s with its default, plus ``LiveCall``'s
+    ``ring_frames``, ``max_batch``, ``channel_order``, ``size``.  After the scores (:340-358, :501-505): ``score_is_real``,
+    ``running_scores``, ``clip_hist`` and ``state[tid]["fake"]`` (median of 5 with hysteresis 0.75 / 0.65), ``last_boxes`` and
+    ``pick_interlocutor_id``; the entries of purged tids are dropped (:489-499).  Not built: ``last_aligned``, the Win32 apps."""
+
+    def __init__(self, network, detector=None, modelPath=None, conf: float = 0.8, clip_size: int = 32, stride: int = 52,
+                 crop_scale: float = 0.6, drop_after: int = 90, detect_every: int = 1, mesh_every: int = 1, start_conf: float = 0.76,
+                 start_min_size: int = 80, q_weighting: bool = True, q_min_size_soft: int = 64, q_min_size_hard: int = 32,
+                 q_lap_soft: float = 20.0, q_lap_hard: float = 5.0, exclude_rect=(0.70, 0.70, 1.00, 1.00), score_is_real: bool = False,
+                 track_thresh: float = 0.8, track_buffer: int = 90, match_thresh: float = 0.8, landmarks=None, size: int = 224,
+                 ring_frames: int = 128, max_batch: int = 16, channel_order: str = "bgr"):
+        import collections
+        from types import SimpleNamespace
+        if detector is None:
+            if modelPath is None:
+                raise ValueError("realtime: a detector, or the modelPath of the YuNet file to build one from")
+            from .detector import YuNet
+            detector = YuNet(modelPath, confThreshold=conf, nmsThreshold=0.3, topK=5000)
+        self.detector, self.landmarks = detector, landmarks
+        self.call = LiveCall(network, clip_size=clip_size, size=size, stride=stride, crop_scale=crop_scale, ring_frames=ring_frames,
+                             max_batch=max_batch, drop_after=drop_after, channel_order=channel_order)
+        self.tracker = ByteTracker(SimpleNamespace(track_thresh=track_thresh, track_buffer=track_buffer, match_thresh=match_thresh,
+                                                   mot20=False), frame_rate=30.0)
+        self.detect_every, self.mesh_every = int(detect_every), int(mesh_every)
+        self.start_conf, self.start_min_size = float(start_conf), int(start_min_size)
+        self._gate = dict(q_weighting=bool(q_weighting), q_min_size_soft=int(q_min_size_soft), q_min_size_hard=int(q_min_size_hard),
+                          q_lap_soft=float(q_lap_soft), q_lap_hard=float(q_lap_hard))
+        self.exclude_rect, self.score_is_real = tuple(exclude_rect), bool(score_is_real)
+        self.drop_after, self.crop_scale = int(drop_after), float(crop_scale)
+        self.host = CallState()
+        self.running_scores = collections.defaultdict(list)
+        self.clip_hist = collections.defaultdict(lambda: collections.deque(maxlen=5))
+        self.state, self.last_boxes = {}, {}
+        self.detections = None                       # the rows the last detect frame handed the tracker's filter (N, 15) float32
+        self._quality = self._quality_ring = None
+        self._rows_host = None
+
+    frame_idx = property(lambda self: self.call.frame_idx)
+    uploaded_bytes = property(lambda self: self.call.uploaded_bytes)
+    purged = property(lambda self: self.call.purged)
+
+    def _detect(self, view) -> np.ndarray:
+        """the detector on the resident frame; counts and the first rows come back in one pinned copy (a second one only for more
+        than 64 faces)"""
+        rows, counts = self.detector.detect(view[None])
+        first = min(64, rows.shape[1])
+        with torch.cuda.device(rows.device):
+            if self._rows_host is None or self._rows_host.numel() < 1 + first * 15:
+                self._rows_host = torch.empty(1 + first * 15, dtype=torch.float32, pin_memory=True)
+            packed = torch.cat([counts[:1].to(torch.float32), rows[0, :first].reshape(-1)])
+            self._rows_host[:packed.numel()].copy_(packed, non_blocking=True)
+            torch.cuda.current_stream(rows.device).synchronize()
+            n = int(self._rows_host[0].item())
+            if n > first:
+                return rows[0, :n].cpu().numpy()
+            return self._rows_host[1:1 + n * 15].numpy().reshape(n, 15).copy()
+
+    def _frame_quality(self, rects):
+        ring = self.call._ring.store
+        if self._quality_ring is not ring:                                             # a new ring after a change of the frame size
+            self._quality, self._quality_ring = FaceQuality(ring, self.call.channel_order), ring
+        slot = self.call.frame_idx % self.call.ring_frames
+        return self._quality([(slot,) + tuple(r) for r in rects])
+
+    def step(self, frame: np.ndarray) -> List[Tuple]:
+        call = self.call
+        k = call.admit(frame)                                                          # :373-376, the one upload
+        H, W = frame.shape[:2]
+        dets = None
+        if k % max(1, self.detect_every) == 0:                                         # :378-380
+            dets = self.detections = self._detect(call.frame_view(k))
+        tracks_in = []
+        if dets is not None and len(dets) > 0:                                         # :382-386
+            for d in dets:
+                d = np.asarray(d, dtype=np.float32)
+                if d[4] >= self.start_conf and max(d[2], d[3]) >= self.start_min_size:
+                    tracks_in.append(STrack(d[:4], score=float(d[4])))
+        online = self.tracker.update(tracks_in, (H, W), (H, W))                        # :388
+        faces, alive, kept_boxes, _ = track_faces(
+            self.host, k, (H, W), dets, online, self._frame_quality, lambda m, l: quality_weight(m, l, **self._gate), self.mesh_every,
+            self.crop_scale, self.exclude_rect, self.landmarks, call.frame_view(k) if self.landmarks is not None else None)
+        results = call.advance(faces, alive)                                           # :445-499
+        return self._after(results, kept_boxes)
+
+    def _after(self, results, kept_boxes):
+        """what the reference does with a score once it exists (:340-358), the purge of a dropped tid's entries (:489-499) and the
+        last known boxes (:501-505)"""
+        out = []
+        for tid, s in results:
+            s = 1.0 - float(s) if self.score_is_real else float(s)                     # :340-341
+            self.running_scores[tid].append(s)
+            out.append((tid, s))
+            self.clip_hist[tid].append(s)
+            sm = float(np.median(self.clip_hist[tid]))
+            st = self.state.get(tid, {"fake": False})
+            if not st["fake"] and sm >= 0.75:
+                st["fake"] = True
+            elif st["fake"] and sm < 0.65:
+                st["fake"] = False
+            self.state[tid] = st
+        for tid in self.call.purged:
+            self.host.last_lm.pop(tid, None)
+            self.running_scores.pop(tid, None)
+            self.last_boxes.pop(tid, None)
+        tracks = self.call._tracks
+        persisting = {tid: box for tid, box in self.last_boxes.items() if tid not in tracks or tracks[tid].missed < self.drop_after}
+        persisting.update(kept_boxes)
+        self.last_boxes = persisting
+        return out
+
+    def pick_interlocutor_id(self, H: int, W: int):
+        """the largest face outside the self-view rectangle, or the largest of all when every face is inside it (:279-291)"""
+        if not self.last_boxes:
+            return None
+        area = lambda b: (b[2] - b[0]) * (b[3] - b[1])
+        cand = [(tid, area(b)) for tid, b in self.last_boxes.items() if not in_exclude(b, H, W, self.exclude_rect)]
+        if not cand:
+            cand = [(tid, area(b)) for tid, b in self.last_boxes.items()]
+        return max(cand, key=lambda t: t[1])[0]
