@@ -478,6 +478,33 @@ typedef struct af_quality_sums {
 int af_face_quality_u8(const void* store, const af_frame_store* desc, const af_frame_rect* rects, int n, int bgr, af_quality_sums* sums,
                        void* grey, int64_t grey_bytes, void* stream);
 
+/* ---- several frame stores in one launch (added within ABI 6) ------------------------------------------------------------------
+ * A server that steps many live calls keeps one frame store per call; these forms of the window warp and of the quality gate read
+ * from up to AF_MAX_STORES stores in one launch.  A store is named by its device base pointer, its description and its byte order
+ * (bgr: 0 - a pixel's bytes are R, G, B; non-zero - B, G, R); af_frame_rect.reserved is the index of a rectangle's store in `stores`
+ * (a HOST array).  The per-store checks are those of the single-store forms; a store index outside [0, n_stores) is AF_ERR_ARG.
+ *
+ * af_window_rects_plan_stores_u8 (host only) fills a table of af_window_rects_table_bytes(n_windows, clip_size) bytes whose items
+ * carry the absolute address of their rectangle's first pixel, its row pitch and its byte order; its `kind` differs from the pool
+ * and the single-store forms, so af_warp_affine_window_stores_u8 writes nothing for a table of another form, and the other
+ * launches write nothing for this one.  A refusal of one (window, frame) - canvas misfit, a rectangle that leaves its frame or its
+ * store, fewer than 3 readable bytes behind a rectangle that ends its store, a bad store index - sets *bad_window / *bad_frame.
+ * The output bytes of a window equal those of af_warp_affine_window_rects_u8 / _bgr_u8 on that window's store. */
+#define AF_MAX_STORES 64
+typedef struct af_store_ref {
+    const void* base;              /* device pointer of the store's first byte */
+    af_frame_store desc;
+    int32_t bgr, reserved;
+} af_store_ref;
+int af_window_rects_plan_stores_u8(const af_window_desc* windows, const af_frame_rect* rects, int n_windows, int clip_size, int size,
+                                   const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes, int32_t* bad_window,
+                                   int32_t* bad_frame);
+int af_warp_affine_window_stores_u8(const void* table, int n_windows, int clip_size, int size, void* out, void* stream);
+/* af_face_quality_u8 over rectangles of several stores: the same integer sums and grey bytes, rectangle i out of
+ * stores[rects[i].reserved].  At most AF_QUALITY_MAX_RECTS rectangles and AF_MAX_STORES stores per launch. */
+int af_face_quality_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
+                              void* grey, int64_t grey_bytes, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,
@@ -592,6 +619,15 @@ int af_yunet_detect(const af_yunet_desc* desc, const float* weights, const void*
                     float* out_rows, int32_t* out_count, float* raw, void* stream);
 int af_yunet_detect_timed(const af_yunet_desc* desc, const float* weights, const void* frames, void* workspace,
                           int64_t workspace_bytes, float* out_rows, int32_t* out_count, float* raw, void* stream, float* ms);
+
+/* af_yunet_detect on a LIST of frames: `frames` is a HOST array of desc->batch device pointers, one per frame; the frames have one
+ * size and one row_pitch, desc->frame_stride is not read, and desc->batch is at most AF_YUNET_MAX_LIST.  The pointers travel in the
+ * launch arguments of the first kernel (the only one that reads pixels): no copy of the list or of the frames.  Everything else,
+ * the outputs bit for bit, is af_yunet_detect on a contiguous copy of the same frames; the workspace is that of the same desc.
+ * (Added within ABI 6.) */
+#define AF_YUNET_MAX_LIST 64
+int af_yunet_detect_frames(const af_yunet_desc* desc, const float* weights, const void* const* frames, void* workspace,
+                           int64_t workspace_bytes, float* out_rows, int32_t* out_count, float* raw, void* stream);
 
 /* ---- RetinaFace detector (ABI 6) ---------------------------------------------------------
  * The offline evaluator's face detector: test_tools/ct/detection (RetinaFace(cfg_mnet, phase="test"),

@@ -9,7 +9,7 @@ def __getattr__(name):
     if name in ("VideoScorer", "TrackScorer"):
         from . import evaluator
         return getattr(evaluator, name)
-    if name in ("LiveCall", "RealtimeCall", "FaceQuality"):
+    if name in ("LiveCall", "RealtimeCall", "CallServer", "FaceQuality"):
         from . import live
         return getattr(live, name)
     if name == "ByteTracker":

@@ -62,6 +62,14 @@ class QualitySums(C.Structure):
 QUALITY_MAX_RECTS = 64
 
 
+class StoreRef(C.Structure):
+    """a frame store named for the several-stores launches: device base pointer, description, byte order"""
+    _fields_ = [("base", C.c_void_p), ("desc", FrameStore), ("bgr", C.c_int32), ("reserved", C.c_int32)]
+
+
+MAX_STORES = 64
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n", "t", "h", "w", "c", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw", "to", "ho", "wo", "dtype",
@@ -109,7 +117,7 @@ class YunetDesc(C.Structure):
                 ("frame_stride", C.c_int64), ("row_pitch", C.c_int64), ("conf_threshold", C.c_float), ("nms_threshold", C.c_float)]
 
 
-YUNET_MAX_TOPK, YUNET_MAX_SIDE, YUNET_LAUNCHES = 8192, 8192, 18
+YUNET_MAX_TOPK, YUNET_MAX_SIDE, YUNET_LAUNCHES, YUNET_MAX_LIST = 8192, 8192, 18, 64
 
 
 class RetinafaceDesc(C.Structure):
@@ -168,6 +176,10 @@ ABI = {
     "af_warp_affine_window_rects_bgr_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "af_face_quality_u8": (C.c_int, [C.c_void_p, C.POINTER(FrameStore), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p]),
+    "af_window_rects_plan_stores_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_void_p]),
+    "af_warp_affine_window_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "af_face_quality_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6
@@ -211,6 +223,7 @@ ABI = {
     "af_yunet_weight_floats": (C.c_int64, []),
     "af_yunet_workspace_bytes": (C.c_int64, [C.POINTER(YunetDesc)]),
     "af_yunet_detect": (C.c_int, [C.POINTER(YunetDesc)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4),
+    "af_yunet_detect_frames": (C.c_int, [C.POINTER(YunetDesc), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
     "af_yunet_detect_timed": (C.c_int, [C.POINTER(YunetDesc)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4
                               + [C.POINTER(C.c_float)]),
     "af_retinaface_weight_floats": (C.c_int64, []),

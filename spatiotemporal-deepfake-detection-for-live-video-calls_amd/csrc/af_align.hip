@@ -100,17 +100,30 @@ static void invert_affine_cv(const double* tfm, double* inv) {
 // The WindowRect form also comes for frames whose pixels are B, G, R in memory (what a capture API delivers): kBgr only chooses
 // which of the three accumulated channels goes to which byte of the R, G, B store - the reads and the arithmetic are the same.
 constexpr int WB_ROWS = 32, WB_THREADS = 256;
-constexpr int32_t WB_KIND_POOL = 0, WB_KIND_RECTS = 1;           // WindowTableHeader::kind
+constexpr int32_t WB_KIND_POOL = 0, WB_KIND_RECTS = 1, WB_KIND_STORES = 2;    // WindowTableHeader::kind
 struct WindowTableHeader { int32_t n_windows, clip_size, size, kind; };
 struct WindowXform { double m[6]; };                             // dst -> src map (already inverted)
 struct WindowRect { int64_t offset; int32_t ih, iw, x, y, pitch, reserved; };    // offset: the rectangle's first pixel in the store
+// A rectangle of one of several stores (af_window_rects_plan_stores_u8): the absolute device address of its first pixel instead
+// of an offset, and its store's byte order - the launch has no store pointer of its own and the R/B choice is per item.
+struct WindowStoreRect { const unsigned char* first; int32_t ih, iw, x, y, pitch, bgr; };
+static_assert(sizeof(WindowStoreRect) == sizeof(WindowRect), "one table size for both rectangle forms");
 
 // byte of pixel (row, col) of the work item's image, the one expression in which the two forms differ
 __device__ __forceinline__ long long wb_byte(const af_align_frame& f, int row, int col) { return ((long long)row * f.iw + col) * 3; }
 __device__ __forceinline__ long long wb_byte(const WindowRect& f, int row, int col) { return (long long)row * f.pitch + col * 3; }
+__device__ __forceinline__ long long wb_byte(const WindowStoreRect& f, int row, int col) { return (long long)row * f.pitch + col * 3; }
+// the work item's first byte, and whether its first and third byte are exchanged on the way out
+__device__ __forceinline__ const unsigned char* wb_first(const unsigned char* pool, const af_align_frame& f) { return pool + f.offset; }
+__device__ __forceinline__ const unsigned char* wb_first(const unsigned char* pool, const WindowRect& f) { return pool + f.offset; }
+__device__ __forceinline__ const unsigned char* wb_first(const unsigned char*, const WindowStoreRect& f) { return f.first; }
+template <bool kBgr> __device__ __forceinline__ bool wb_bgr(const af_align_frame&) { return kBgr; }
+template <bool kBgr> __device__ __forceinline__ bool wb_bgr(const WindowRect&) { return kBgr; }
+template <bool kBgr> __device__ __forceinline__ bool wb_bgr(const WindowStoreRect& f) { return f.bgr != 0; }
 template <typename Item> struct WbKind;
 template <> struct WbKind<af_align_frame> { static constexpr int32_t value = WB_KIND_POOL; };
 template <> struct WbKind<WindowRect> { static constexpr int32_t value = WB_KIND_RECTS; };
+template <> struct WbKind<WindowStoreRect> { static constexpr int32_t value = WB_KIND_STORES; };
 
 static inline int64_t window_table_bytes(int n_windows, int clip_size, size_t item = sizeof(af_align_frame)) {
     return (int64_t)sizeof(WindowTableHeader) + (int64_t)n_windows * sizeof(WindowXform) + (int64_t)n_windows * clip_size * (int64_t)item;
@@ -141,7 +154,8 @@ __global__ __launch_bounds__(WB_THREADS) void warp_affine_windows_kernel(const u
     }
     __syncthreads();
     const int rows = size - y0 < WB_ROWS ? size - y0 : WB_ROWS, quads = size >> 2;
-    const unsigned char* img = pool + f.offset;
+    const unsigned char* img = wb_first(pool, f);
+    const bool bgr = wb_bgr<kBgr>(f);                             // a constant of the kernel, except for WindowStoreRect
     unsigned char* dst = out + ((long long)k * size + y0) * (long long)size * 3;
     for (int i = threadIdx.x; i < rows * quads; i += WB_THREADS) {
         const int r = i / quads, q = i - r * quads;
@@ -175,7 +189,7 @@ __global__ __launch_bounds__(WB_THREADS) void warp_affine_windows_kernel(const u
             const int c1 = w00 * (int)((a4 >> 8) & 255) + w01 * (int)(a2 & 255) + w10 * (int)((b4 >> 8) & 255) + w11 * (int)(b2 & 255);
             const int c2 = w00 * (int)((a4 >> 16) & 255) + w01 * (int)(a2 >> 8) + w10 * (int)((b4 >> 16) & 255) + w11 * (int)(b2 >> 8);
             const int v0 = (c0 + (1 << 14)) >> 15, v1 = (c1 + (1 << 14)) >> 15, v2 = (c2 + (1 << 14)) >> 15;
-            const int vr = kBgr ? v2 : v0, vb = kBgr ? v0 : v2;            // source byte 0 is B in a BGR frame; the store is R, G, B
+            const int vr = bgr ? v2 : v0, vb = bgr ? v0 : v2;            // source byte 0 is B in a BGR frame; the store is R, G, B
             px[j] = (unsigned)(vr > 255 ? 255 : vr) | (unsigned)(v1 > 255 ? 255 : v1) << 8 | (unsigned)(vb > 255 ? 255 : vb) << 16;
         }
         uint3 o;                                                      // 4 x RGB = 3 dwords (size % 4 == 0: every quad is dword-aligned)
@@ -311,6 +325,82 @@ extern "C" int af_window_rects_plan_u8(const af_window_desc* windows, const af_f
     }
     hd->n_windows = n_windows; hd->clip_size = clip_size; hd->size = size; hd->kind = WB_KIND_RECTS;
     return AF_OK;
+}
+
+// ---- the same launch out of SEVERAL stores: af_frame_rect.reserved names the rectangle's store ----
+extern "C" int af_window_rects_plan_stores_u8(const af_window_desc* windows, const af_frame_rect* rects, int n_windows, int clip_size, int size,
+                                              const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes, int32_t* bad_window,
+                                              int32_t* bad_frame) {
+    using namespace af;
+    if (bad_window) *bad_window = -1;
+    if (bad_frame) *bad_frame = -1;
+    AF_REQUIRE(windows && rects && stores && table, "window_rects_plan_stores: null argument");
+    AF_REQUIRE(n_windows > 0 && n_windows <= AF_WINDOW_MAX_BATCH && clip_size > 0 && clip_size <= AF_ALIGN_MAX_FRAMES,
+               "window_rects_plan_stores: %d windows of %d frames (at most %d of %d)", n_windows, clip_size, AF_WINDOW_MAX_BATCH, AF_ALIGN_MAX_FRAMES);
+    AF_REQUIRE(size > 0 && size <= AF_WINDOW_MAX_SIZE && size % 4 == 0, "window_rects_plan_stores: size %d (a multiple of 4, at most %d)", size,
+               AF_WINDOW_MAX_SIZE);
+    AF_REQUIRE(n_stores > 0 && n_stores <= AF_MAX_STORES, "window_rects_plan_stores: %d stores (1 to %d)", n_stores, AF_MAX_STORES);
+    const int64_t need = window_table_bytes(n_windows, clip_size, sizeof(WindowStoreRect));
+    AF_REQUIRE(table_bytes >= need, "window_rects_plan_stores: table of %lld bytes, %lld needed", (long long)table_bytes, (long long)need);
+    for (int i = 0; i < n_stores; ++i) {
+        const af_frame_store& s = stores[i].desc;
+        AF_REQUIRE(stores[i].base, "window_rects_plan_stores: store %d: null base pointer", i);
+        AF_REQUIRE(s.n_frames > 0 && s.height > 0 && s.width > 0 && s.height <= 32767 && s.width <= 32767,
+                   "window_rects_plan_stores: store %d of %d frames %dx%d", i, s.n_frames, s.width, s.height);
+        const int64_t frame_span = (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3;
+        AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span,
+                   "window_rects_plan_stores: store %d: row pitch %lld, frame stride %lld for frames of %dx%d", i, (long long)s.row_pitch,
+                   (long long)s.frame_stride, s.width, s.height);
+        AF_REQUIRE(s.store_bytes >= (int64_t)(s.n_frames - 1) * s.frame_stride + frame_span,
+                   "window_rects_plan_stores: store %d: %d frames do not fit a store of %lld bytes", i, s.n_frames, (long long)s.store_bytes);
+    }
+    WindowTableHeader* hd = (WindowTableHeader*)table;
+    WindowXform* xf = (WindowXform*)(hd + 1);
+    WindowStoreRect* out = (WindowStoreRect*)(xf + n_windows);
+    hd->kind = -1;                                                  // a table that was refused half-way is no table
+    for (int w = 0; w < n_windows; ++w) {
+        const af_window_desc& d = windows[w];
+        AF_REQUIRE(d.canvas_h > 0 && d.canvas_w > 0 && d.canvas_h <= 32767 && d.canvas_w <= 32767,
+                   "window_rects_plan_stores: window %d: bad canvas %dx%d", w, d.canvas_w, d.canvas_h);
+        invert_affine_cv(d.tfm, xf[w].m);
+        for (int t = 0; t < clip_size; ++t) {
+            const af_frame_rect& r = rects[w * clip_size + t];
+            const char* why = nullptr;
+            int64_t offset = 0;
+            if (r.reserved < 0 || r.reserved >= n_stores) why = "names a store outside the list";
+            else {
+                const af_frame_store& s = stores[r.reserved].desc;
+                offset = (int64_t)r.frame * s.frame_stride + (int64_t)r.ry * s.row_pitch + (int64_t)r.rx * 3;
+                if (!(r.frame >= 0 && r.frame < s.n_frames && r.ih > 0 && r.iw > 0 && r.rx >= 0 && r.ry >= 0 &&
+                      (int64_t)r.rx + r.iw <= s.width && (int64_t)r.ry + r.ih <= s.height))
+                    why = "leaves its frame or the frames of its store";
+                // the 6-byte tap reads: only a rectangle that ends its store needs 3 readable bytes behind it
+                else if (offset + (int64_t)(r.ih - 1) * s.row_pitch + (int64_t)r.iw * 3 + 3 > s.store_bytes)
+                    why = "ends its store without 3 readable bytes behind it";
+            }
+            // the reference pastes with new_image[y:y+ih, x:x+iw] = image, which numpy refuses unless the crop fits the canvas
+            const bool misfit = !why && (r.x < 0 || r.y < 0 || (long long)r.x + r.iw > d.canvas_w || (long long)r.y + r.ih > d.canvas_h);
+            if (why || misfit) {
+                if (bad_window) *bad_window = w;
+                if (bad_frame) *bad_frame = t;
+                if (misfit)
+                    return set_error(AF_ERR_ARG, "aligner: window %d frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas", w, t, r.iw, r.ih, r.x,
+                                     r.y, d.canvas_w, d.canvas_h);
+                return set_error(AF_ERR_ARG, "window_rects_plan_stores: window %d frame %d: rectangle %dx%d at (%d,%d) of frame %d of store %d %s", w, t,
+                                 r.iw, r.ih, r.rx, r.ry, r.frame, r.reserved, why);
+            }
+            const af_store_ref& st = stores[r.reserved];
+            out[w * clip_size + t] = WindowStoreRect{(const unsigned char*)st.base + offset, r.ih, r.iw, r.x, r.y, (int32_t)st.desc.row_pitch,
+                                                     st.bgr ? 1 : 0};
+        }
+    }
+    hd->n_windows = n_windows; hd->clip_size = clip_size; hd->size = size; hd->kind = WB_KIND_STORES;
+    return AF_OK;
+}
+
+extern "C" int af_warp_affine_window_stores_u8(const void* table, int n_windows, int clip_size, int size, void* out, void* stream) {
+    // the items carry their own addresses: the launch's pool pointer is not read (the table stands in for the null check)
+    return af::launch_window_warp<af::WindowStoreRect>("warp_affine_window_stores", table, table, n_windows, clip_size, size, out, stream);
 }
 
 extern "C" int af_warp_affine_window_rects_u8(const void* store, const void* table, int n_windows, int clip_size, int size, void* out,

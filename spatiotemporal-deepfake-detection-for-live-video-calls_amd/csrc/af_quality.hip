@@ -45,6 +45,24 @@ struct QualityArgs {
     QualityRect r[AF_QUALITY_MAX_RECTS];
 };
 
+// The several-stores form (af_face_quality_stores_u8): a rectangle carries the absolute address of its first pixel, its store's row
+// pitch and byte order, so the launch needs no table of stores; 64 x 32 bytes + the header stay far under the 4 KB of arguments.
+struct QualityStoreRect {
+    const unsigned char* first;
+    int32_t pitch, w, h;
+    int32_t first_tile, grey_offset;
+    int32_t bgr;
+};
+static_assert(sizeof(QualityStoreRect) == 32, "argument budget");
+
+struct QualityStoresArgs {
+    af_quality_sums* sums;
+    unsigned char* grey;
+    int n, total_tiles;
+    QualityStoreRect r[AF_QUALITY_MAX_RECTS];
+};
+static_assert(sizeof(QualityStoresArgs) <= 4096, "kernel arguments");
+
 __device__ __forceinline__ int reflect101(int i, int n) { return n == 1 ? 0 : (i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i)); }
 
 __device__ __forceinline__ int round_sat_u8(float v) {          // saturate_cast<uchar>(float): cvRound (half to even), then clamp
@@ -121,19 +139,15 @@ __device__ int grey_at(const unsigned char* src, long long pitch, int w, int h, 
     return (r * 9798 + ch[1] * 19235 + b * 3735 + 16384) >> 15;
 }
 
-__global__ __launch_bounds__(256) void face_quality_kernel(const QualityArgs a) {
+// One tile of one rectangle: `src` the rectangle's first byte, rows `pitch` bytes apart, w x h pixels, tile `local` of it; the
+// tile's totals go to `out`, its grey bytes (tests) to `grey` (the rectangle's own image, or null).
+__device__ __forceinline__ void quality_tile(const unsigned char* src, long long pitch, int w, int h, int local, int bgr, af_quality_sums* out,
+                                             unsigned char* grey) {
     __shared__ unsigned char g[Q_GH][Q_GW + 2];
     __shared__ long long part[2][4];
-    const int tile = blockIdx.x;
-    if (tile >= a.total_tiles) return;
-    int k = 0;
-    while (k + 1 < a.n && a.r[k + 1].first_tile <= tile) ++k;     // tens of rectangles: a scan
-    const QualityRect r = a.r[k];
-    const int dw = max(1, r.w / 2), dh = max(1, r.h / 2);
+    const int dw = max(1, w / 2), dh = max(1, h / 2);
     const int tiles_x = (dw + Q_TW - 1) / Q_TW;
-    const int local = tile - r.first_tile;
     const int ty0 = (local / tiles_x) * Q_TH, tx0 = (local % tiles_x) * Q_TW;
-    const unsigned char* src = a.store + (long long)r.frame * a.frame_stride + (long long)r.y0 * a.row_pitch + (long long)r.x0 * 3;
 
     for (int i = threadIdx.x; i < Q_GH * Q_GW; i += 256) {
         const int gr = i / Q_GW, gc = i - gr * Q_GW;
@@ -141,9 +155,9 @@ __global__ __launch_bounds__(256) void face_quality_kernel(const QualityArgs a) 
         int v = 0;
         if (y <= dh && x <= dw) {                                 // beyond n nothing reads the cell
             const int yy = reflect101(y, dh), xx = reflect101(x, dw);
-            v = grey_at(src, a.row_pitch, r.w, r.h, dw, dh, xx, yy, a.bgr);
-            if (a.grey && gr >= 1 && gr <= Q_TH && gc >= 1 && gc <= Q_TW && y < dh && x < dw)
-                a.grey[(long long)r.grey_offset + (long long)y * dw + x] = (unsigned char)v;
+            v = grey_at(src, pitch, w, h, dw, dh, xx, yy, bgr);
+            if (grey && gr >= 1 && gr <= Q_TH && gc >= 1 && gc <= Q_TW && y < dh && x < dw)
+                grey[(long long)y * dw + x] = (unsigned char)v;
         }
         g[gr][gc] = (unsigned char)v;
     }
@@ -166,11 +180,29 @@ __global__ __launch_bounds__(256) void face_quality_kernel(const QualityArgs a) 
     if (threadIdx.x == 0) {
         const long long t1 = part[0][0] + part[0][1] + part[0][2] + part[0][3];
         const long long t2 = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-        af_quality_sums* out = a.sums + k;
         atomicAdd((unsigned long long*)&out->s1, (unsigned long long)t1);      // two's complement: the signed sum of the parts
         atomicAdd((unsigned long long*)&out->s2, (unsigned long long)t2);
         if (local == 0) out->n_px = dw * dh;
     }
+}
+
+__global__ __launch_bounds__(256) void face_quality_kernel(const QualityArgs a) {
+    const int tile = blockIdx.x;
+    if (tile >= a.total_tiles) return;
+    int k = 0;
+    while (k + 1 < a.n && a.r[k + 1].first_tile <= tile) ++k;     // tens of rectangles: a scan
+    const QualityRect r = a.r[k];
+    const unsigned char* src = a.store + (long long)r.frame * a.frame_stride + (long long)r.y0 * a.row_pitch + (long long)r.x0 * 3;
+    quality_tile(src, a.row_pitch, r.w, r.h, tile - r.first_tile, a.bgr, a.sums + k, a.grey ? a.grey + r.grey_offset : nullptr);
+}
+
+__global__ __launch_bounds__(256) void face_quality_stores_kernel(const QualityStoresArgs a) {
+    const int tile = blockIdx.x;
+    if (tile >= a.total_tiles) return;
+    int k = 0;
+    while (k + 1 < a.n && a.r[k + 1].first_tile <= tile) ++k;
+    const QualityStoreRect r = a.r[k];
+    quality_tile(r.first, r.pitch, r.w, r.h, tile - r.first_tile, r.bgr, a.sums + k, a.grey ? a.grey + r.grey_offset : nullptr);
 }
 
 }  // namespace af
@@ -211,5 +243,54 @@ extern "C" int af_face_quality_u8(const void* store, const af_frame_store* desc,
     if (e != hipSuccess) return set_error(AF_ERR_LAUNCH, "face_quality: hipMemsetAsync: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(face_quality_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
     AF_CHECK_LAUNCH("face_quality_kernel");
+    return AF_OK;
+}
+
+extern "C" int af_face_quality_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
+                                         void* grey, int64_t grey_bytes, void* stream) {
+    using namespace af;
+    AF_REQUIRE(stores && rects && sums, "face_quality_stores: null argument");
+    AF_REQUIRE(n >= 0 && n <= AF_QUALITY_MAX_RECTS, "face_quality_stores: %d rectangles (at most %d per launch)", n, AF_QUALITY_MAX_RECTS);
+    AF_REQUIRE(n_stores > 0 && n_stores <= AF_MAX_STORES, "face_quality_stores: %d stores (1 to %d per launch)", n_stores, AF_MAX_STORES);
+    if (n == 0) return AF_OK;
+    for (int i = 0; i < n_stores; ++i) {
+        const af_frame_store& s = stores[i].desc;
+        AF_REQUIRE(stores[i].base, "face_quality_stores: store %d: null base pointer", i);
+        AF_REQUIRE(s.n_frames > 0 && s.height > 0 && s.width > 0 && s.height <= 32767 && s.width <= 32767,
+                   "face_quality_stores: store %d of %d frames %dx%d", i, s.n_frames, s.width, s.height);
+        const int64_t frame_span = (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3;
+        AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span,
+                   "face_quality_stores: store %d: row pitch %lld, frame stride %lld for frames of %dx%d", i, (long long)s.row_pitch,
+                   (long long)s.frame_stride, s.width, s.height);
+        AF_REQUIRE(s.store_bytes >= (int64_t)(s.n_frames - 1) * s.frame_stride + frame_span,
+                   "face_quality_stores: store %d: %d frames do not fit a store of %lld bytes", i, s.n_frames, (long long)s.store_bytes);
+    }
+    QualityStoresArgs a;
+    a.sums = sums; a.grey = (unsigned char*)grey; a.n = n;
+    int64_t tiles = 0, grey_total = 0;
+    for (int i = 0; i < n; ++i) {
+        const af_frame_rect& r = rects[i];
+        AF_REQUIRE(r.reserved >= 0 && r.reserved < n_stores, "face_quality_stores: rectangle %d names store %d of %d", i, r.reserved, n_stores);
+        const af_store_ref& st = stores[r.reserved];
+        const af_frame_store& s = st.desc;
+        AF_REQUIRE(r.frame >= 0 && r.frame < s.n_frames && r.ih > 0 && r.iw > 0 && r.rx >= 0 && r.ry >= 0 &&
+                   (int64_t)r.rx + r.iw <= s.width && (int64_t)r.ry + r.ih <= s.height,
+                   "face_quality_stores: rectangle %d: %dx%d at (%d,%d) of frame %d leaves the %d frames of %dx%d of store %d", i, r.iw, r.ih, r.rx,
+                   r.ry, r.frame, s.n_frames, s.width, s.height, r.reserved);
+        const int dw = r.iw / 2 > 1 ? r.iw / 2 : 1, dh = r.ih / 2 > 1 ? r.ih / 2 : 1;
+        const int64_t offset = (int64_t)r.frame * s.frame_stride + (int64_t)r.ry * s.row_pitch + (int64_t)r.rx * 3;
+        a.r[i] = QualityStoreRect{(const unsigned char*)st.base + offset, (int32_t)s.row_pitch, r.iw, r.ih, (int32_t)tiles, (int32_t)grey_total,
+                                  st.bgr ? 1 : 0};
+        tiles += (int64_t)((dw + Q_TW - 1) / Q_TW) * ((dh + Q_TH - 1) / Q_TH);
+        grey_total += (int64_t)dw * dh;
+        AF_REQUIRE(tiles <= 0x7fffffff && grey_total <= 0x7fffffff, "face_quality_stores: too many pixels");
+    }
+    AF_REQUIRE(!grey || grey_bytes >= grey_total, "face_quality_stores: grey image buffer of %lld bytes, %lld needed", (long long)grey_bytes,
+               (long long)grey_total);
+    a.total_tiles = (int)tiles;
+    hipError_t e = hipMemsetAsync(sums, 0, sizeof(af_quality_sums) * (size_t)n, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(AF_ERR_LAUNCH, "face_quality_stores: hipMemsetAsync: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(face_quality_stores_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    AF_CHECK_LAUNCH("face_quality_stores_kernel");
     return AF_OK;
 }

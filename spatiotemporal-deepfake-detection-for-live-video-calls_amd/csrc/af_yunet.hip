@@ -198,12 +198,12 @@ __device__ __forceinline__ float4 max4(float4 a, float4 b, float4 c, float4 d) {
 
 // Stem (3x3/2 conv 3->16 + ReLU) + unit 0 (16->16 at stride 2) + MaxPool: one block = a 16x16 tile of the stride-4 output,
 // i.e. 32x32 stride-2 pixels + halo = 34x34x16 f32 (74 KB) in LDS.  Pixels of the padded frame beyond the real one read 0.
-__global__ __launch_bounds__(kThreads) void yunet_stem_unit0_pool(StemArgs a) {
+// `img`: the first byte of frame blockIdx.z - the one thing in which the two kernels below differ.
+__device__ __forceinline__ void stem_unit0_pool_tile(const StemArgs& a, const uint8_t* img) {
     extern __shared__ float mid[];   // [34 * 34][16]
     constexpr int L = 2 * kT + 2;
     const int b = blockIdx.z;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.counts[b] = 0;
-    const uint8_t* img = a.frames + (long long)b * a.frame_stride;
     const float* sw = a.wt;
     const float* sb = sw + 27 * 16;
     const float* pw = a.wt + kStemFloats;
@@ -259,6 +259,18 @@ __global__ __launch_bounds__(kThreads) void yunet_stem_unit0_pool(StemArgs a) {
         dw_quad(mid, L, 2 * qy, 2 * qx, c4, dw, db, c4 * 4, 16, o);
         *reinterpret_cast<float4*>(a.out + (((size_t)b * a.h4 + py) * a.w4 + px) * 16 + c4 * 4) = max4(o[0][0], o[0][1], o[1][0], o[1][1]);
     }
+}
+
+__global__ __launch_bounds__(kThreads) void yunet_stem_unit0_pool(StemArgs a) {
+    stem_unit0_pool_tile(a, a.frames + (long long)blockIdx.z * a.frame_stride);
+}
+
+// The same kernel for frames that lie anywhere (af_yunet_detect_frames): frame b starts at list.p[b].  The list travels by value
+// in the launch arguments (512 bytes), so the launch needs no copy of it; a.frames / a.frame_stride are not read.
+struct FrameList { const uint8_t* p[AF_YUNET_MAX_LIST]; };
+
+__global__ __launch_bounds__(kThreads) void yunet_stem_unit0_pool_frames(StemArgs a, FrameList list) {
+    stem_unit0_pool_tile(a, list.p[blockIdx.z]);
 }
 
 // One DP unit over a 16x16 output tile, 16 output channels at a time (a 18x18x16 f32 LDS tile, 20 KB): 1x1 conv into LDS, then
@@ -483,8 +495,9 @@ static void launch_unit(dim3 grid, hipStream_t s, const UnitArgs& ua) {
     hipLaunchKernelGGL((yunet_dp_unit<CIN, COUT>), grid, dim3(kThreads), 0, s, ua);
 }
 
+// `list`: null (frame b at frames + b * d->frame_stride), or d->batch frame pointers, checked by the caller (then `frames` is list[0])
 static int detect(const af_yunet_desc* d, const float* weights, const void* frames, void* workspace, int64_t workspace_bytes,
-                  float* out_rows, int32_t* out_count, float* raw, hipStream_t s, hipEvent_t* ev) {
+                  float* out_rows, int32_t* out_count, float* raw, hipStream_t s, hipEvent_t* ev, const void* const* list = nullptr) {
     int rc = check_desc(d);
     if (rc != AF_OK) return rc;
     AF_REQUIRE(weights && frames && workspace && out_rows && out_count, "yunet: null pointer");
@@ -504,7 +517,15 @@ static int detect(const af_yunet_desc* d, const float* weights, const void* fram
     AF_SET_MAX_LDS(yunet_stem_unit0_pool, kStemLds, "yunet_stem_unit0_pool");
     StemArgs sa{(const uint8_t*)frames, d->frame_stride, d->row_pitch, d->height, d->width, p.ph / 2, p.pw / 2, h4, w4,
                 weights, act + p.t189, counts};
-    hipLaunchKernelGGL(yunet_stem_unit0_pool, dim3((w4 + kT - 1) / kT, (h4 + kT - 1) / kT, p.B), dim3(kThreads), kStemLds, s, sa);
+    const dim3 stem_grid((w4 + kT - 1) / kT, (h4 + kT - 1) / kT, p.B);
+    if (list) {
+        FrameList fl{};
+        for (int b = 0; b < p.B; ++b) fl.p[b] = (const uint8_t*)list[b];
+        AF_SET_MAX_LDS(yunet_stem_unit0_pool_frames, kStemLds, "yunet_stem_unit0_pool_frames");
+        hipLaunchKernelGGL(yunet_stem_unit0_pool_frames, stem_grid, dim3(kThreads), kStemLds, s, sa, fl);
+    } else {
+        hipLaunchKernelGGL(yunet_stem_unit0_pool, stem_grid, dim3(kThreads), kStemLds, s, sa);
+    }
     AF_CHECK_LAUNCH("yunet_stem_unit0_pool");
     mark();
 
@@ -564,6 +585,17 @@ extern "C" int64_t af_yunet_workspace_bytes(const af_yunet_desc* d) {
 extern "C" int af_yunet_detect(const af_yunet_desc* d, const float* weights, const void* frames, void* workspace,
                                int64_t workspace_bytes, float* out_rows, int32_t* out_count, float* raw, void* stream) {
     return af::yunet::detect(d, weights, frames, workspace, workspace_bytes, out_rows, out_count, raw, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int af_yunet_detect_frames(const af_yunet_desc* d, const float* weights, const void* const* frames, void* workspace,
+                                      int64_t workspace_bytes, float* out_rows, int32_t* out_count, float* raw, void* stream) {
+    using namespace af;
+    AF_REQUIRE(d && frames, "yunet_detect_frames: null argument");
+    AF_REQUIRE(d->batch >= 1 && d->batch <= AF_YUNET_MAX_LIST, "yunet_detect_frames: %d frames (at most %d per call)", d->batch, AF_YUNET_MAX_LIST);
+    for (int b = 0; b < d->batch; ++b) AF_REQUIRE(frames[b], "yunet_detect_frames: frame %d is a null pointer", b);
+    af_yunet_desc one = *d;
+    one.frame_stride = d->row_pitch * d->height;            // not read by the kernel; keeps the shared layout check quiet
+    return yunet::detect(&one, weights, frames[0], workspace, workspace_bytes, out_rows, out_count, raw, (hipStream_t)stream, nullptr, frames);
 }
 
 extern "C" int af_yunet_detect_timed(const af_yunet_desc* d, const float* weights, const void* frames, void* workspace,

@@ -277,6 +277,44 @@ class YuNet(DeviceModel):
             self._call(self._detect_fn, args, timings)
         return (rows, counts, rawt) if raw else (rows, counts)
 
+    def detect_views(self, views, raw: bool = False, conf: Optional[float] = None, nms: Optional[float] = None,
+                     top_k: Optional[int] = None):
+        """``detect`` on frames that lie anywhere on one device: `views` a list of at most 64 (H, W, 3) uint8 device views of equal
+        shape and strides (slots of different frame rings, say).  One call of ``af_yunet_detect_frames``: the frame pointers
+        travel in the first kernel's launch arguments, no frame is copied.  Returns what ``detect`` returns on their stack."""
+        import torch
+        from . import _lib
+        views = list(views)
+        if not 1 <= len(views) <= _lib.YUNET_MAX_LIST:
+            raise ValueError("detect_views: %d frames (1 to %d per call)" % (len(views), _lib.YUNET_MAX_LIST))
+        v0 = views[0]
+        for v in views:
+            if not isinstance(v, torch.Tensor) or v.device.type != "cuda":
+                raise RuntimeError("YuNet.detect_views needs (H, W, 3) uint8 tensors on a HIP device (there is no CPU path)")
+            if v.dtype != torch.uint8 or v.dim() != 3 or v.shape[2] != 3:
+                raise ValueError("frames must be (H, W, 3) uint8, got %s %s" % (tuple(v.shape), v.dtype))
+            if v.stride(2) != 1 or v.stride(1) != 3:
+                raise ValueError("frames must have packed BGR pixels (strides (..., 3, 1))")
+            if v.shape != v0.shape or v.stride() != v0.stride() or v.device != v0.device:
+                raise ValueError("detect_views: the frames of one call have one shape, one row pitch and one device")
+        b, (h, w, _) = len(views), v0.shape
+        top_k = self._topK if top_k is None else int(top_k)
+        desc = self._desc(b, h, w, v0.stride(0) * h, v0.stride(0), self._confThreshold if conf is None else float(conf),
+                          self._nmsThreshold if nms is None else float(nms), top_k)
+        dev = v0.device
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            ws = self._workspace(dev, cur, desc)
+            wt = self._weights(dev)
+            rows = torch.empty(b, top_k, 15, dtype=torch.float32, device=dev)
+            counts = torch.empty(b, dtype=torch.int32, device=dev)
+            rawt = torch.empty(b, num_anchors(w, h), 16, dtype=torch.float32, device=dev) if raw else None
+            ptrs = (C.c_void_p * b)(*[v.data_ptr() for v in views])
+            self._call(("af_yunet_detect_frames", None),
+                       [C.byref(desc), C.c_void_p(wt.data_ptr()), ptrs, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(rows.data_ptr()),
+                        C.c_void_p(counts.data_ptr()), C.c_void_p(rawt.data_ptr() if raw else None), C.c_void_p(cur.cuda_stream)], None)
+        return (rows, counts, rawt) if raw else (rows, counts)
+
     def infer(self, image):
         """FaceDetectorYN.detect on one H x W x 3 uint8 BGR frame of the preset input size: (N, 15) float32, or
         np.empty((0, 5)) when there is no face (as the reference wrapper returns)."""

@@ -14,16 +14,18 @@ What stays with the caller: the detector and the tracker (``faces`` carry their 
 or FaceMesh's as in :420-432; the 68 points are zeros as in :448 - the aligner fits on the five), the self-view exclusion
 (:403), the Laplacian quality weight (:439-442: a face the caller rejects is simply not handed in that step) and everything
 ``_flush_and_infer`` does with a score after it exists (:340-358).  ``RealtimeCall`` further down is the caller that supplies all of
-these: the captured frame is its only input.  There is no CPU fallback: without the HIP library the calls fail.
+these: the captured frame is its only input.  ``CallServer`` at the end steps many such calls on launches they share (one YuNet
+call per frame size, one quality launch, one warp and one replay per batch of closed windows, whichever calls they belong to).
+There is no CPU fallback: without the HIP library the calls fail.
 """
-from typing import List, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ._staging import is_crop
 from .aligner import STD_POINTS_256
-from .evaluator import RECTS, RECTS_BGR, FrameStore, WindowWarp, _clip_buffers, _FrameTrack, _network_device, _padded, get_crop_box, partition
+from .evaluator import RECTS, RECTS_BGR, FrameStore, WindowWarp, _clip_buffers, _fit, _FrameTrack, _network_device, _padded, get_crop_box, partition
 from .tracker import ByteTracker, STrack, iou_distance
 
 _FORMS = {"rgb": RECTS, "bgr": RECTS_BGR}
@@ -128,6 +130,15 @@ class LiveCall:
         """the second half of ``step``: the tracks move on by the faces of the admitted frame (:401-499).  ``alive``: tids that
         were tracked on this frame but contribute no entry - no landmarks, or rejected by the quality gate (:407 against :431-442):
         their ``missed`` count resets as for a face that was handed in, and nothing else happens to them."""
+        ready = self.advance_host(faces, alive)
+        if not ready:
+            return []
+        scores = self._score(ready)                                                    # :472
+        return [(tid, float(s)) for (tid, _), s in zip(ready, scores)]
+
+    def advance_host(self, faces: Sequence[Tuple], alive: Sequence = ()) -> List[Tuple]:
+        """the books of ``advance`` without the scoring: returns the windows that closed on this frame, ``[(tid, [(frame index,
+        record)] * clip_size)]``.  ``advance`` scores them itself; ``CallServer`` scores the windows of many calls together."""
         H, W = self._shape[:2]
         oldest = max(self._first, self.frame_idx - self.ring_frames + 1)
         alive, ready = set(alive), []
@@ -168,10 +179,7 @@ class LiveCall:
                 if tr.missed >= self.drop_after:
                     del self._tracks[tid]
                     self.purged.append(tid)
-        if not ready:
-            return []
-        scores = self._score(ready)                                                    # :472
-        return [(tid, float(s)) for (tid, _), s in zip(ready, scores)]
+        return ready
 
     def frame_view(self, k: int) -> torch.Tensor:
         """the device (H, W, 3) uint8 view of frame ``k`` (``call.frame_idx`` is the last one), in the channel order it was captured
@@ -259,52 +267,46 @@ def quality_weight(min_side: float, lap: float, q_weighting: bool = True, q_min_
     return float(size_w * lap_w)
 
 
-class FaceQuality:
-    """``FaceQuality(store, channel_order)(rects)`` -> ``[(min_side, lap), ...]``: the pixel part of the quality gate (:265-267,
-    :191-192) for every rectangle ``(slot, x0, y0, x1, y1)`` of the resident frames of ``store`` (an ``evaluator.FrameStore``) in
-    one launch of ``af_face_quality_u8`` (csrc/af_quality.hip) and one pinned read-back on the current stream - the only wait.  The
-    kernel returns three exact integers per rectangle; ``lap = (n_px * S2 - S1^2) / n_px^2`` is formed here from Python integers
-    with one fp64 division.  ``sums(rects, grey=True)`` also returns the half-size grey images (tests)."""
+_SUMS_DTYPE = np.dtype([("s1", "<i8"), ("s2", "<i8"), ("n_px", "<i4"), ("r", "<i4")])          # af_quality_sums
 
-    def __init__(self, store: FrameStore, channel_order: str = "bgr"):
-        from . import _lib                                        # fails loudly when libafhip.so is missing
-        if channel_order not in _FORMS:
-            raise ValueError("live: channel_order 'bgr' or 'rgb', not %r" % (channel_order,))
-        self.store, self.bgr = store, int(channel_order == "bgr")
-        self._fn = _lib.lib.af_face_quality_u8
+
+class _QualitySums:
+    """what both forms of the quality launch share: the device and pinned records, one launch per 64 rectangles, one pinned
+    read-back on the current stream - the only wait - and the lap each rectangle's three integers give.  ``launches`` counts the
+    calls into the C function."""
+
+    def __init__(self, device):
+        self.device, self.launches = device, 0
         self._dev = self._host = None
 
-    def sums(self, rects, grey: bool = False):
-        """-> ``[(n_px, S1, S2)]`` as Python integers (and, with ``grey``, the list of (dh, dw) uint8 grey images)"""
+    def _sums(self, sizes, grey: bool, launch, what: str):
+        """``sizes``: (h, w) per rectangle; ``launch(lo, hi, sums, grey, grey_bytes, stream)`` calls the C function for rectangles
+        [lo, hi) -> ``[(n_px, S1, S2)]`` as Python integers (and, with ``grey``, the list of (dh, dw) uint8 grey images)"""
         import ctypes as C
         from . import _lib
-        from .evaluator import _RECT_DTYPE
-        n, store = len(rects), self.store
+        n = len(sizes)
         if n == 0:
             return ([], []) if grey else []
-        items = np.zeros(n, dtype=_RECT_DTYPE)
-        for i, (slot, x0, y0, x1, y1) in enumerate(rects):
-            items[i] = (slot, x0, y0, y1 - y0, x1 - x0, 0, 0, 0)
-        halves = [(max(1, int(r["ih"]) // 2), max(1, int(r["iw"]) // 2)) for r in items]
+        halves = [(max(1, h // 2), max(1, w // 2)) for h, w in sizes]
         rec = C.sizeof(_lib.QualitySums)
-        with torch.cuda.device(store.device):
-            cur = torch.cuda.current_stream(store.device)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
             if self._dev is None or self._dev.numel() < n * rec:
                 with torch.inference_mode(False):
-                    self._dev = torch.empty(max(n, _lib.QUALITY_MAX_RECTS) * rec, dtype=torch.uint8, device=store.device)
+                    self._dev = torch.empty(max(n, _lib.QUALITY_MAX_RECTS) * rec, dtype=torch.uint8, device=self.device)
                     self._host = torch.empty(self._dev.numel(), dtype=torch.uint8, pin_memory=True)
-            gbuf = torch.empty(sum(h * w for h, w in halves), dtype=torch.uint8, device=store.device) if grey else None
+            gbuf = torch.empty(sum(h * w for h, w in halves), dtype=torch.uint8, device=self.device) if grey else None
             goff = 0
             for lo in range(0, n, _lib.QUALITY_MAX_RECTS):                 # one launch for up to 64 faces
                 hi = min(n, lo + _lib.QUALITY_MAX_RECTS)
                 gn = sum(h * w for h, w in halves[lo:hi])
-                _lib.check(self._fn(C.c_void_p(store.dev.data_ptr()), store.plan_source(), C.c_void_p(items[lo:hi].ctypes.data), hi - lo, self.bgr,
-                                    C.c_void_p(self._dev.data_ptr() + lo * rec), C.c_void_p(gbuf.data_ptr() + goff if grey else None), gn,
-                                    C.c_void_p(cur.cuda_stream)), "face_quality_u8")
+                _lib.check(launch(lo, hi, C.c_void_p(self._dev.data_ptr() + lo * rec), C.c_void_p(gbuf.data_ptr() + goff if grey else None), gn,
+                                  C.c_void_p(cur.cuda_stream)), what)
+                self.launches += 1
                 goff += gn
             self._host[:n * rec].copy_(self._dev[:n * rec], non_blocking=True)
             cur.synchronize()
-            raw = np.frombuffer(self._host.numpy()[:n * rec].tobytes(), dtype=np.dtype([("s1", "<i8"), ("s2", "<i8"), ("n_px", "<i4"), ("r", "<i4")]))
+            raw = np.frombuffer(self._host.numpy()[:n * rec].tobytes(), dtype=_SUMS_DTYPE)
             out = [(int(r["n_px"]), int(r["s1"]), int(r["s2"])) for r in raw]
             if not grey:
                 return out
@@ -316,9 +318,39 @@ class FaceQuality:
 
     def __call__(self, rects):
         out = []
-        for (n_px, s1, s2), (_, x0, y0, x1, y1) in zip(self.sums(rects), rects):
+        for (n_px, s1, s2), (x0, y0, x1, y1) in zip(self.sums(rects), (r[-4:] for r in rects)):
             out.append((float(min(y1 - y0, x1 - x0)), (n_px * s2 - s1 * s1) / (n_px * n_px)))
         return out
+
+
+class FaceQuality(_QualitySums):
+    """``FaceQuality(store, channel_order)(rects)`` -> ``[(min_side, lap), ...]``: the pixel part of the quality gate (:265-267,
+    :191-192) for every rectangle ``(slot, x0, y0, x1, y1)`` of the resident frames of ``store`` (an ``evaluator.FrameStore``) in
+    one launch of ``af_face_quality_u8`` (csrc/af_quality.hip) and one pinned read-back on the current stream - the only wait.  The
+    kernel returns three exact integers per rectangle; ``lap = (n_px * S2 - S1^2) / n_px^2`` is formed here from Python integers
+    with one fp64 division.  ``sums(rects, grey=True)`` also returns the half-size grey images (tests)."""
+
+    def __init__(self, store: FrameStore, channel_order: str = "bgr"):
+        from . import _lib                                        # fails loudly when libafhip.so is missing
+        if channel_order not in _FORMS:
+            raise ValueError("live: channel_order 'bgr' or 'rgb', not %r" % (channel_order,))
+        super().__init__(store.device)
+        self.store, self.bgr = store, int(channel_order == "bgr")
+        self._fn = _lib.lib.af_face_quality_u8
+
+    def sums(self, rects, grey: bool = False):
+        """-> ``[(n_px, S1, S2)]`` as Python integers (and, with ``grey``, the list of (dh, dw) uint8 grey images)"""
+        import ctypes as C
+        from .evaluator import _RECT_DTYPE
+        store = self.store
+        items = np.zeros(len(rects), dtype=_RECT_DTYPE)
+        for i, (slot, x0, y0, x1, y1) in enumerate(rects):
+            items[i] = (slot, x0, y0, y1 - y0, x1 - x0, 0, 0, 0)
+
+        def launch(lo, hi, sums, gptr, gn, stream):
+            return self._fn(C.c_void_p(store.dev.data_ptr()), store.plan_source(), C.c_void_p(items[lo:hi].ctypes.data), hi - lo, self.bgr,
+                            sums, gptr, gn, stream)
+        return self._sums([(int(r["ih"]), int(r["iw"])) for r in items], grey, launch, "face_quality_u8")
 
 
 # ---- the whole live step: af_realtime.py:372-509 ----------------------------------------------------------------------------------
@@ -342,13 +374,21 @@ def in_exclude(box, H: int, W: int, exclude_rect) -> bool:
 
 def track_faces(state: CallState, frame_idx: int, shape, dets, online, quality, gate, mesh_every: int = 1, crop_scale: float = 0.6,
                 exclude_rect=(0.70, 0.70, 1.00, 1.00), landmarks=None, frame_view=None):
+    """``track_gate`` behind ``track_candidates``: see there.  ``quality(rects)`` -> ``[(min_side, lap)]`` for rectangles ``(x0,
+    y0, x1, y1)`` of this frame, called once with all of them (not at all without one); ``gate(min_side, lap)`` -> the weight."""
+    found = track_candidates(state, frame_idx, shape, dets, online, mesh_every, crop_scale, exclude_rect, landmarks, frame_view)
+    rects = found[0]
+    return track_gate(state, found, quality(rects) if rects else [], gate)
+
+
+def track_candidates(state: CallState, frame_idx: int, shape, dets, online, mesh_every: int = 1, crop_scale: float = 0.6,
+                     exclude_rect=(0.70, 0.70, 1.00, 1.00), landmarks=None, frame_view=None):
     """The host part of ``RealtimeAF.step`` between the tracker and the window bookkeeping (:390-442), without a device call of
-    its own.  ``dets``: this frame's (N, 15) float32 YuNet rows, or None; ``online``: the tracker's tracks (``track_id``,
-    ``tlbr``); ``quality(rects)`` -> ``[(min_side, lap)]`` for rectangles ``(x0, y0, x1, y1)`` of this frame, called once with all
-    of them; ``gate(min_side, lap)`` -> the weight.  Returns ``(faces, alive, kept_boxes, rects)``: ``faces`` - ``(tid, tlbr
-    float32, lm5)`` of the tracks that go on to the windows; ``alive`` - the tids of the tracks that were kept past the self-view
-    exclusion but go no further (no landmarks, a degenerate crop box, or a weight of 0); ``kept_boxes`` as :407; ``rects`` as handed
-    to ``quality``.  The order of the skips is the reference's: an excluded track is not alive, a track skipped later is."""
+    its own, in two halves around the quality measurement so that a server can measure the crops of many calls in one launch.
+    This half (:390-437): ``dets``: this frame's (N, 15) float32 YuNet rows, or None; ``online``: the tracker's tracks
+    (``track_id``, ``tlbr``).  Returns ``(rects, candidates, alive, kept_boxes)``, ``rects`` - the crop rectangles ``(x0, y0, x1,
+    y1)`` whose quality is wanted - first; the whole tuple goes to ``track_gate``.  The order of the skips is the reference's: an
+    excluded track is not alive, a track skipped later is."""
     H, W = int(shape[0]), int(shape[1])
     det_tlbr = None
     if dets is not None and len(dets) > 0:                                             # :391-396
@@ -387,9 +427,17 @@ def track_faces(state: CallState, frame_idx: int, shape, dets, online, quality, 
         if x2 <= x1 or y2 <= y1:                                                       # :437
             continue
         candidates.append((tid, tlbr, np.asarray(fm["lm5"], dtype=np.float32), (x1, y1, x2, y2)))
-    rects = [c[3] for c in candidates]
+    return [c[3] for c in candidates], candidates, alive, kept_boxes
+
+
+def track_gate(state: CallState, found, measured, gate):
+    """the second half (:438-442): ``found`` from ``track_candidates``, ``measured`` = ``[(min_side, lap)]`` of its rectangles,
+    ``gate(min_side, lap)`` -> the weight.  Returns ``(faces, alive, kept_boxes, rects)``: ``faces`` - ``(tid, tlbr float32, lm5)``
+    of the tracks that go on to the windows; ``alive`` - the tids of the tracks that were kept past the self-view exclusion but go
+    no further (no landmarks, a degenerate crop box, or a weight of 0); ``kept_boxes`` as :407; ``rects`` as they were measured."""
+    rects, candidates, alive, kept_boxes = found
     faces = []
-    for (tid, tlbr, lm5, _), (min_side, lap) in zip(candidates, quality(rects) if rects else []):
+    for (tid, tlbr, lm5, _), (min_side, lap) in zip(candidates, measured):
         state.q_hist[tid].append((float(min_side), float(lap)))                        # :440
         if gate(min_side, lap) <= 0.0:                                                 # :441-442
             continue
@@ -429,7 +477,7 @@ class RealtimeCall:
             from .detector import YuNet
             detector = YuNet(modelPath, confThreshold=conf, nmsThreshold=0.3, topK=5000)
         self.detector, self.landmarks = detector, landmarks
-        self.call = LiveCall(network, clip_size=clip_size, size=size, stride=stride, crop_scale=crop_scale, ring_frames=ring_frames,
+        self.call = self._ring_type(network, clip_size=clip_size, size=size, stride=stride, crop_scale=crop_scale, ring_frames=ring_frames,
                              max_batch=max_batch, drop_after=drop_after, channel_order=channel_order)
         self.tracker = ByteTracker(SimpleNamespace(track_thresh=track_thresh, track_buffer=track_buffer, match_thresh=match_thresh,
                                                    mot20=False), frame_rate=30.0)
@@ -447,6 +495,7 @@ class RealtimeCall:
         self._quality = self._quality_ring = None
         self._rows_host = None
 
+    _ring_type = LiveCall
     frame_idx = property(lambda self: self.call.frame_idx)
     uploaded_bytes = property(lambda self: self.call.uploaded_bytes)
     purged = property(lambda self: self.call.purged)
@@ -529,3 +578,350 @@ class RealtimeCall:
         if not cand:
             cand = [(tid, area(b)) for tid, b in self.last_boxes.items()]
         return max(cand, key=lambda t: t[1])[0]
+
+
+# ---- many calls per device: the launches of one step shared by every call ---------------------------------------------------------
+
+class _ServedRing(LiveCall):
+    """the books and the frame ring of one call of a ``CallServer``: no warp, clip buffer or event of its own - the server's
+    launches read the ring, and the server orders the steps"""
+
+    def _new_ring(self, shape):
+        dev = _network_device(self.network)
+        with torch.cuda.device(dev):
+            store = FrameStore(dev)
+            store.open(shape, self.ring_frames)
+        return _DeviceSide(store, None, None)
+
+    def _store_frame(self, frame: np.ndarray, slot: int):
+        ring = self._ring.store
+        with torch.cuda.device(ring.device):
+            ring.put([frame], slot)
+        self.uploaded_bytes += frame.nbytes
+
+    def _score(self, ready):
+        raise RuntimeError("live: a served call is scored by its CallServer")
+
+
+class _ServedCall(RealtimeCall):
+    """a call's state inside a ``CallServer``: ``RealtimeCall``'s attributes, stepped only by the server"""
+    _ring_type = _ServedRing
+
+    def step(self, frame):
+        raise RuntimeError("live: a served call is stepped by its CallServer (server.step({cid: frame}))")
+
+
+def _store_ref(store: FrameStore, channel_order: str):
+    from . import _lib
+    h, w = store.shape[:2]
+    return _lib.StoreRef(store.dev.data_ptr(), _lib.FrameStore(store.dev.numel(), store.frame_nbytes, w * 3, store.capacity, h, w, 0),
+                         int(channel_order == "bgr"), 0)
+
+
+class StoresQuality(_QualitySums):
+    """``FaceQuality`` over rectangles of several frame stores: ``rects = [(store, channel_order, slot, x0, y0, x1, y1)]`` in one
+    launch of ``af_face_quality_stores_u8`` per 64 rectangles, whatever their stores, and one read-back"""
+
+    def __init__(self, device):
+        from . import _lib                                        # fails loudly when libafhip.so is missing
+        super().__init__(device)
+        self._fn = _lib.lib.af_face_quality_stores_u8
+
+    def sums(self, rects, grey: bool = False):
+        import ctypes as C
+        from . import _lib
+        from .evaluator import _RECT_DTYPE
+
+        def launch(lo, hi, sums, gptr, gn, stream):
+            index, refs = {}, []                                           # the stores of this launch, in order of first use
+            items = np.zeros(hi - lo, dtype=_RECT_DTYPE)
+            for i, (store, order, slot, x0, y0, x1, y1) in enumerate(rects[lo:hi]):
+                if id(store) not in index:
+                    index[id(store)] = len(refs)
+                    refs.append(_store_ref(store, order))
+                items[i] = (slot, x0, y0, y1 - y0, x1 - x0, 0, 0, index[id(store)])
+            return self._fn((_lib.StoreRef * len(refs))(*refs), len(refs), C.c_void_p(items.ctypes.data), hi - lo, sums, gptr, gn, stream)
+        return self._sums([(r[6] - r[4], r[5] - r[3]) for r in rects], grey, launch, "face_quality_stores_u8")
+
+
+class StoresWarp:
+    """the window-batch warp out of several frame stores (``af_window_rects_plan_stores_u8`` /
+    ``af_warp_affine_window_stores_u8``): ``warp(windows, out)`` with ``windows = [(store, channel_order, slots, track, fit)]`` -
+    ``track`` an ``evaluator._FrameTrack`` of the window's ``clip_size`` frames, which sit in ``slots`` of ``store`` - plans one
+    table, sends it through a ring of pinned slots and launches once.  ``launches`` counts the launches."""
+
+    def __init__(self, device, clip_size: int, size: int, batch: int):
+        from . import _lib                                        # fails loudly when libafhip.so is missing
+        from ._staging import PinnedRing
+        self.device, self.clip_size, self.size, self.batch, self.launches = device, int(clip_size), int(size), int(batch), 0
+        if not (1 <= self.batch <= _lib.WINDOW_MAX_BATCH and 1 <= self.clip_size <= _lib.ALIGN_MAX_FRAMES):
+            raise ValueError("live: max_batch 1..%d, clip_size 1..%d" % (_lib.WINDOW_MAX_BATCH, _lib.ALIGN_MAX_FRAMES))
+        if self.size % 4 or not 0 < self.size <= _lib.WINDOW_MAX_SIZE:
+            raise ValueError("live: size must be a multiple of 4, at most %d" % _lib.WINDOW_MAX_SIZE)
+        self.table_bytes = int(_lib.lib.af_window_rects_table_bytes(self.batch, self.clip_size))
+        self.tables = PinnedRing(min_bytes=self.table_bytes)
+
+    def __call__(self, windows, out: torch.Tensor):
+        import ctypes as C
+        from . import _lib
+        from .aligner import canvas_misfit
+        from .evaluator import _RECT_DTYPE, _WINDOW_DTYPE
+        n, T = len(windows), self.clip_size
+        desc = np.zeros(n, dtype=_WINDOW_DTYPE)
+        items = np.zeros((n, T), dtype=_RECT_DTYPE)
+        index, refs = {}, []
+        for w, (store, order, slots, track, (tfm, h, wd, diff)) in enumerate(windows):
+            if id(store) not in index:
+                index[id(store)] = len(refs)
+                refs.append(_store_ref(store, order))
+            desc[w] = (np.asarray(tfm, dtype=np.float64).reshape(6), h, wd)
+            items["frame"][w], items["rx"][w], items["ry"][w] = slots, track.rx, track.ry
+            items["ih"][w], items["iw"][w] = track.ih, track.iw
+            items["x"][w], items["y"][w] = diff[:, 0], diff[:, 1]
+            items["reserved"][w] = index[id(store)]
+        with torch.cuda.device(self.device):
+            slot = self.tables.acquire(self.table_bytes, self.device)
+            bad_w, bad_f = C.c_int32(-1), C.c_int32(-1)
+            rc = _lib.lib.af_window_rects_plan_stores_u8(desc.ctypes.data, items.ctypes.data, n, T, self.size, (_lib.StoreRef * len(refs))(*refs),
+                                                         len(refs), slot.host.data_ptr(), self.table_bytes, C.byref(bad_w), C.byref(bad_f))
+            if rc != 0 and bad_w.value >= 0:
+                f, d = items[bad_w.value, bad_f.value], desc[bad_w.value]
+                if f["x"] < 0 or f["y"] < 0 or f["x"] + f["iw"] > d["canvas_w"] or f["y"] + f["ih"] > d["canvas_h"]:
+                    canvas_misfit(bad_f.value, f["iw"], f["ih"], f["x"], f["y"], d["canvas_w"], d["canvas_h"], window=bad_w.value)
+            _lib.check(rc, "window_rects_plan_stores_u8")
+            used = int(_lib.lib.af_window_rects_table_bytes(n, T))
+            slot.dev[:used].copy_(slot.host[:used], non_blocking=True)
+            slot.record()                                           # behind the copy: the host rewrites only the pinned table
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(_lib.lib.af_warp_affine_window_stores_u8(C.c_void_p(slot.dev.data_ptr()), n, T, self.size, C.c_void_p(out.data_ptr()), stream),
+                       "warp_affine_window_stores_u8")
+            self.launches += 1
+
+
+class ServerStats:
+    """what a ``CallServer`` enqueued and waited for: ``last`` for the last step, ``total`` since the server was made, each with
+    ``detect`` (calls of ``af_yunet_detect_frames``, or of a detector's ``detect_views``), ``quality``, ``warp`` (launches),
+    ``replay`` (graph replays) and ``wait`` (host waits for the device)"""
+    KEYS = ("detect", "quality", "warp", "replay", "wait")
+
+    def __init__(self):
+        self.steps = 0
+        self.last = dict.fromkeys(self.KEYS, 0)
+        self.total = dict.fromkeys(self.KEYS, 0)
+
+    def begin(self):
+        self.steps += 1
+        self.last = dict.fromkeys(self.KEYS, 0)
+
+    def count(self, key: str, n: int = 1):
+        self.last[key] += n
+        self.total[key] += n
+
+
+class CallServer:
+    """Many live calls on one device: ``server.step({cid: frame, ...})`` -> ``{cid: [(tid, score), ...]}`` does for every call in
+    the mapping what ``RealtimeCall.step`` does for one, on launches that all of them share.
+
+        server = CallServer(network, modelPath="face_detection_yunet_2023mar.onnx")
+        a, b = server.open(), server.open(channel_order="rgb", detect_every=2)
+        results = server.step({a: frame_a, b: frame_b})          # a call that is not in the mapping does not advance
+        server.call(a).running_scores, server.call(a).state      # a call's state: ``RealtimeCall``'s attributes
+        server.close(b)
+
+    ``clip_size``, ``size`` and ``max_batch`` belong to the server (one network, one clip buffer); every other keyword of
+    ``RealtimeCall`` is a call's own - ``call_defaults`` here, overridden per call in ``open`` - as are its frame size, tracker,
+    ``CallState`` and frame ring.  ``detector``: a ``YuNet`` (or ``modelPath`` to build one with ``conf``), or any object with
+    ``detect_views(views) -> (rows, counts)``.
+
+    One step, whatever the number of calls: every frame is admitted into its call's ring (one upload per frame); the calls that
+    detect on this frame are grouped by frame shape and each group goes through ``detect_views`` 64 frames at a time, all counts
+    and first rows coming back in one pinned copy; per call the tracker and ``track_candidates``; one ``af_face_quality_stores_u8``
+    launch per 64 crop rectangles of all calls and one read-back; per call ``track_gate`` and ``advance_host``; the windows that
+    closed - ordered as the mapping iterates, then as each call orders its own - go ``max_batch`` at a time through one plan and
+    one warp out of all the rings into the server's clip buffer and one replay at the next of 1, 2, 4 ... ``max_batch`` clips (a
+    short batch repeats its last window), with one read-back of the scores; per call ``RealtimeCall._after``.  That is at most
+    three host waits per step (four when one frame has more than 64 faces).  The scores are ``forward_clips_u8(...,
+    return_scores=True)``'s at that batch size, bit for bit; every other result is a lone ``RealtimeCall``'s on the same frames.
+
+    Streams: a step waits, on the stream it is called on, for the event the step before recorded behind its last launch, as
+    ``LiveCall`` does; the rings are read and written only here; ``close`` and a change of a call's frame size (which re-opens
+    that call's ring, as in ``LiveCall``) wait for the device first.  ``stats``: ``ServerStats``."""
+
+    def __init__(self, network, detector=None, modelPath=None, max_batch: int = 16, clip_size: int = 32, size: int = 224, conf: float = 0.8,
+                 **call_defaults):
+        self.network = getattr(network, "network", network)
+        if detector is None:
+            if modelPath is None:
+                raise ValueError("server: a detector, or the modelPath of the YuNet file to build one from")
+            from .detector import YuNet
+            detector = YuNet(modelPath, confThreshold=conf, nmsThreshold=0.3, topK=5000)
+        self.detector = detector
+        self.clip_size, self.size, self.max_batch = int(clip_size), int(size), int(max_batch)
+        for name in ("network", "detector", "modelPath", "clip_size", "size", "max_batch"):
+            if name in call_defaults:
+                raise TypeError("server: %s belongs to the server, not to a call" % name)
+        self.call_defaults = dict(call_defaults)
+        self.device = _network_device(self.network)
+        self.stats = ServerStats()
+        self.uploaded_bytes = 0
+        self._calls: Dict[int, _ServedCall] = {}
+        self._next = 0
+        self._quality = StoresQuality(self.device)
+        self._warp = StoresWarp(self.device, self.clip_size, self.size, self.max_batch)
+        self._clip = None                  # ``max_batch`` clips, the static input of the replayed forwards
+        self._scorers = {}                 # clips per forward -> LiveScorer on the front of the clip buffer
+        self._done = None                  # recorded behind the last launch of every step
+        self._rows_host = self._scores_host = None
+
+    # -- calls ---------------------------------------------------------------------------------------------
+    def open(self, **overrides) -> int:
+        """a new call with the server's defaults and these ``RealtimeCall`` keywords; returns its id"""
+        for name in ("network", "detector", "modelPath", "clip_size", "size", "max_batch"):
+            if name in overrides:
+                raise TypeError("server: %s belongs to the server, not to a call" % name)
+        args = dict(self.call_defaults)
+        args.update(overrides)
+        cid, self._next = self._next, self._next + 1
+        self._calls[cid] = _ServedCall(self.network, detector=self.detector, clip_size=self.clip_size, size=self.size,
+                                       max_batch=self.max_batch, **args)
+        return cid
+
+    def close(self, cid: int) -> None:
+        """ends a call: waits for the device, then frees the call's ring and state"""
+        self._calls[cid]                                             # KeyError for an unknown call
+        torch.cuda.synchronize(self.device)
+        del self._calls[cid]
+
+    def call(self, cid: int) -> RealtimeCall:
+        return self._calls[cid]
+
+    def __len__(self):
+        return len(self._calls)
+
+    # -- the step ------------------------------------------------------------------------------------------
+    def step(self, frames: Mapping[int, np.ndarray]) -> Dict[int, List[Tuple]]:
+        calls = [(cid, self._calls[cid], frame) for cid, frame in frames.items()]          # KeyError before anything moves
+        self.stats.begin()
+        if not calls:
+            return {}
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            if self._done is None:
+                self._done = torch.cuda.Event()
+            else:
+                cur.wait_event(self._done)
+            try:
+                return self._step(calls, cur)
+            finally:
+                self._done.record(cur)
+
+    def _step(self, calls, cur):
+        ticks = []
+        for cid, c, frame in calls:                                                        # 1. the uploads
+            ticks.append(c.call.admit(frame))
+            self.uploaded_bytes += frame.nbytes
+        detecting = [i for i, (_, c, _) in enumerate(calls) if ticks[i] % max(1, c.detect_every) == 0]
+        dets = dict(zip(detecting, self._detect([calls[i][1].call.frame_view(ticks[i]) for i in detecting])))      # 2.
+        found, wanted = [], []
+        for i, (cid, c, frame) in enumerate(calls):                                        # 3. trackers, candidates
+            H, W = frame.shape[:2]
+            d = dets.get(i)
+            if d is not None:
+                c.detections = d
+            tracks_in = []
+            if d is not None and len(d) > 0:
+                for row in d:
+                    row = np.asarray(row, dtype=np.float32)
+                    if row[4] >= c.start_conf and max(row[2], row[3]) >= c.start_min_size:
+                        tracks_in.append(STrack(row[:4], score=float(row[4])))
+            online = c.tracker.update(tracks_in, (H, W), (H, W))
+            f = track_candidates(c.host, ticks[i], (H, W), d, online, c.mesh_every, c.crop_scale, c.exclude_rect, c.landmarks,
+                                 c.call.frame_view(ticks[i]) if c.landmarks is not None else None)
+            found.append(f)
+            ring, slot = c.call._ring.store, ticks[i] % c.call.ring_frames
+            wanted += [(ring, c.call.channel_order, slot) + tuple(r) for r in f[0]]
+        launched = self._quality.launches                                                  # 4. one gate for all
+        measured = self._quality(wanted) if wanted else []
+        self.stats.count("quality", self._quality.launches - launched)
+        self.stats.count("wait", 1 if wanted else 0)
+        ready, kept, at = [], [], 0
+        for (cid, c, frame), f in zip(calls, found):                                       # 5. the books
+            faces, alive, kept_boxes, _ = track_gate(c.host, f, measured[at:at + len(f[0])], lambda m, l, g=c._gate: quality_weight(m, l, **g))
+            at += len(f[0])
+            kept.append(kept_boxes)
+            ready.append(c.call.advance_host(faces, alive))
+        scores = self._score([(c.call, win) for (_, c, _), wins in zip(calls, ready) for _, win in wins])
+        out, at = {}, 0
+        for (cid, c, _), wins, kept_boxes in zip(calls, ready, kept):                      # 6.
+            results = [(tid, float(s)) for (tid, _), s in zip(wins, scores[at:at + len(wins)])]
+            at += len(wins)
+            out[cid] = c._after(results, kept_boxes)
+        return out
+
+    def _detect(self, views) -> List[np.ndarray]:
+        """the rows of every view, in order: the views grouped by shape, one ``detect_views`` per 64 of a group, the counts and
+        the first 64 rows of every frame back in one pinned copy and one wait (one more only for a frame with more faces)"""
+        if not views:
+            return []
+        from . import _lib
+        groups = {}
+        for i, v in enumerate(views):
+            groups.setdefault(tuple(v.shape), []).append(i)
+        chunks, packed, at = [], [], 0
+        for members in groups.values():
+            for lo in range(0, len(members), _lib.YUNET_MAX_LIST):
+                chunk = members[lo:lo + _lib.YUNET_MAX_LIST]
+                rows, counts = self.detector.detect_views([views[i] for i in chunk])
+                self.stats.count("detect")
+                first = min(64, rows.shape[1])
+                packed += [counts.to(torch.float32), rows[:, :first].reshape(-1)]
+                chunks.append((chunk, rows, first, at))
+                at += len(chunk) * (1 + first * 15)
+        if self._rows_host is None or self._rows_host.numel() < at:
+            self._rows_host = torch.empty(max(at, 16 * (1 + 64 * 15)), dtype=torch.float32, pin_memory=True)
+        self._rows_host[:at].copy_(torch.cat(packed), non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        self.stats.count("wait")
+        host, out = self._rows_host.numpy(), [None] * len(views)
+        for chunk, rows, first, at in chunks:                                              # a chunk: its counts, then its first rows
+            for b, i in enumerate(chunk):
+                n = int(host[at + b])
+                if n > first:
+                    out[i] = rows[b, :n].cpu().numpy()
+                    self.stats.count("wait")
+                else:
+                    lo = at + len(chunk) + b * first * 15
+                    out[i] = host[lo:lo + n * 15].reshape(n, 15).copy()
+        return out
+
+    def _scorer(self, run: int):
+        from .classifier import LiveScorer
+        if self._clip is None:
+            self._clip = _clip_buffers(1, self.max_batch, self.clip_size, self.size, self.device)[0]
+        if run not in self._scorers:
+            self._scorers[run] = LiveScorer(self.network, self.clip_size, self.size, batch=run, clip=self._clip[:run])
+        return self._scorers[run]
+
+    def _score(self, closed) -> np.ndarray:
+        """``closed``: ``[(the call's ``_ServedRing``, [(frame index, record)] * clip_size)]`` in the server's order -> their scores, float32:
+        one fit per window, one plan, one warp and one replay per ``max_batch`` windows, one read-back"""
+        if not closed:
+            return np.zeros(0, dtype=np.float32)
+        std_points = STD_POINTS_256 * self.size / 256.0
+        windows, idx = [], list(range(self.clip_size))
+        for books, win in closed:
+            track = _FrameTrack([rec for _, rec in win], [k % books.ring_frames for k, _ in win], books._shape)
+            windows.append((books._ring.store, books.channel_order, track.frame, track, _fit(track, idx, std_points)))
+        cur, parts = torch.cuda.current_stream(self.device), []
+        for first, n, run in partition(len(windows), self.max_batch):
+            scorer = self._scorer(run)
+            self._warp(windows[first:first + n] + [windows[first + n - 1]] * (run - n), scorer.clip)
+            self.stats.count("warp")
+            parts.append(scorer.replay()[:n].to(torch.float32, copy=True))             # the next replay of this size overwrites its scores
+            self.stats.count("replay")
+        if self._scores_host is None or self._scores_host.numel() < len(windows):
+            self._scores_host = torch.empty(max(64, len(windows)), dtype=torch.float32, pin_memory=True)
+        self._scores_host[:len(windows)].copy_(parts[0] if len(parts) == 1 else torch.cat(parts), non_blocking=True)
+        cur.synchronize()
+        self.stats.count("wait")
+        return self._scores_host[:len(windows)].numpy().copy()
