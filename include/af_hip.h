@@ -505,6 +505,48 @@ int af_warp_affine_window_stores_u8(const void* table, int n_windows, int clip_s
 int af_face_quality_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
                               void* grey, int64_t grey_bytes, void* stream);
 
+/* ---- YUV 4:2:0 frames into frame stores (added within ABI 6) ---------------------------------------------------------------------
+ * What a WebRTC stack (I420), a hardware decoder (NV12) or ffmpeg (yuv420p) hands over, converted on the device straight into slots
+ * of frame stores: one launch converts up to AF_YUV_MAX_FRAMES frames that may differ in size, format, destination store and byte
+ * order.  Arithmetic: OpenCV's cvtColor(..., COLOR_YUV2BGR_NV12 / _I420) - fixed-point BT.601, limited range, integer only, one
+ * (U, V) per 2 x 2 block of Y without interpolation; stated in csrc/af_yuv.hip and equal, byte for byte, to the numpy restatement
+ * tests/yuv_ref.py (unpinned against cv2 itself, absent where this is built).  Not built: full range, BT.709, 4:2:2 / 4:4:4, 10-bit.
+ *
+ * af_yuv_frame (host description of one frame): y - DEVICE pointer of the Y plane, h rows of w bytes y_pitch apart; u - the first
+ * chroma plane: the interleaved plane (h / 2 rows of w bytes) when `interleaved`, else the first of two planes of h / 2 rows of
+ * w / 2 bytes, v the second; c_pitch - the row pitch of the chroma plane(s); swap_uv - the first chroma byte / plane is V (NV21,
+ * YV12 in memory order); (store, slot) - the destination: slot `slot` of stores[store], whose height and width must be h and w.
+ * af_yuv420_plan_u8 (host only, no device work) fills items[0 .. n) and refuses with AF_ERR_ARG: odd or non-positive h or w, a pitch
+ * shorter than its row, a store index outside [0, n_stores), a store of another frame size, a slot that does not lie wholly inside
+ * its store (store_bytes is checked), n above AF_YUV_MAX_FRAMES.  An item carries the absolute address of its destination's first
+ * byte, the pitches, the flags (bgr: the store's byte order) and first_tile, the prefix sum of the tiles of the items before it.
+ * af_yuv420_to_rgb_u8 takes a HOST table the planner filled (it travels to the kernel by value), checks sizes, pitches and the
+ * first_tile prefix again and trusts the pointers.  The kernel reads no byte outside [plane, plane + pitch * (rows - 1) + row bytes)
+ * and writes exactly the h * w * 3 bytes of each destination frame, whatever the alignment of planes, pitches and destination rows;
+ * the planes must be ready on `stream` and stay unchanged until the launch has run. */
+#define AF_YUV_MAX_FRAMES 64
+typedef struct af_yuv_frame {
+    const void* y;
+    const void* u;
+    const void* v;
+    int64_t y_pitch, c_pitch;
+    int32_t h, w;
+    int32_t interleaved, swap_uv;
+    int32_t store, slot;
+} af_yuv_frame;
+typedef struct af_yuv_item {
+    const void* y;
+    const void* c0;
+    const void* c1;
+    void* dst;
+    int32_t y_pitch, c_pitch, dst_pitch;
+    int32_t first_tile;
+    uint16_t h, w;
+    uint8_t interleaved, swap_uv, bgr, reserved;
+} af_yuv_item;
+int af_yuv420_plan_u8(const af_yuv_frame* frames, int n, const af_store_ref* stores, int n_stores, af_yuv_item* items);
+int af_yuv420_to_rgb_u8(const af_yuv_item* items, int n, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,

@@ -12,6 +12,9 @@ def __getattr__(name):
     if name in ("LiveCall", "RealtimeCall", "CallServer", "FaceQuality"):
         from . import live
         return getattr(live, name)
+    if name == "YuvFrame":
+        from . import frames
+        return frames.YuvFrame
     if name == "ByteTracker":
         from . import tracker
         return tracker.ByteTracker

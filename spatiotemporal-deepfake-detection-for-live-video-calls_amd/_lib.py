@@ -70,6 +70,23 @@ class StoreRef(C.Structure):
 MAX_STORES = 64
 
 
+class YuvFrameDesc(C.Structure):
+    """af_yuv_frame: one 4:2:0 frame on the device and the store slot it is converted into"""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_pitch", C.c_int64), ("c_pitch", C.c_int64),
+                ("h", C.c_int32), ("w", C.c_int32), ("interleaved", C.c_int32), ("swap_uv", C.c_int32), ("store", C.c_int32),
+                ("slot", C.c_int32)]
+
+
+class YuvItem(C.Structure):
+    """af_yuv_item: what af_yuv420_plan_u8 fills and af_yuv420_to_rgb_u8 launches over"""
+    _fields_ = [("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p), ("dst", C.c_void_p), ("y_pitch", C.c_int32),
+                ("c_pitch", C.c_int32), ("dst_pitch", C.c_int32), ("first_tile", C.c_int32), ("h", C.c_uint16), ("w", C.c_uint16),
+                ("interleaved", C.c_uint8), ("swap_uv", C.c_uint8), ("bgr", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+YUV_MAX_FRAMES, YUV_RUN, YUV_TILE = 64, 8, 256
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n", "t", "h", "w", "c", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw", "to", "ho", "wo", "dtype",
@@ -180,6 +197,8 @@ ABI = {
                                                  C.c_void_p, C.c_void_p]),
     "af_warp_affine_window_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "af_face_quality_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "af_yuv420_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "af_yuv420_to_rgb_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6

@@ -31,6 +31,7 @@ import torch
 
 from ._staging import _COPY_THREADS, _SPLIT_BYTES, PinnedRing, _pool, crop_rect, cuda_device, is_crop, packed_rgb, stage_rects
 from .aligner import STD_POINTS_256, canvas_misfit, fit_window
+from .frames import YuvConverter, YuvFrame
 
 _FRAME_DTYPE = np.dtype([("offset", "<i8"), ("ih", "<i4"), ("iw", "<i4"), ("x", "<i4"), ("y", "<i4")])       # af_align_frame
 _RECT_DTYPE = np.dtype([(n, "<i4") for n in ("frame", "rx", "ry", "ih", "iw", "x", "y", "reserved")])            # af_frame_rect
@@ -370,11 +371,14 @@ class CropPool(_Resident):
 
 class FrameStore(_Resident):
     """`capacity` decoded frames of one `shape`, packed, slot after slot in one device buffer: a whole video, a window through
-    which a longer one passes, or a ring of a call's last frames"""
+    which a longer one passes, or a ring of a call's last frames.  ``channel_order``: the byte order of a pixel in the store,
+    which only a conversion into the store needs to know (``YuvFrame``s); numpy frames are stored as they come."""
 
-    def __init__(self, device):
+    def __init__(self, device, channel_order: str = "rgb"):
         super().__init__(device)
         self.shape, self.frame_nbytes, self.capacity = None, 0, 0
+        self.channel_order = channel_order
+        self._yuv = None
 
     def open(self, shape, capacity: int):
         self.shape, self.capacity = tuple(shape), int(capacity)
@@ -385,8 +389,14 @@ class FrameStore(_Resident):
     def put(self, frames, first_slot: int):
         """host frames -> consecutive slots of the store from `first_slot`: pinned slots in turn, each filled by the copy threads
         in bands of rows, one asynchronous copy per slot.  A frame whose pixels are not packed RGB bytes (a channel-reversed
-        view) costs a strided host pass here instead of a memcpy per band."""
+        view) costs a strided host pass here instead of a memcpy per band.
+
+        A list of ``YuvFrame`` (a list is all numpy or all ``YuvFrame``) is converted on the way: host planes go tightly into
+        a pinned slot (1.5 bytes per pixel), one copy moves them to the slot's device twin and one ``af_yuv420_to_rgb_u8`` launch
+        per staging slot writes the store's slots in its ``channel_order``; device-resident planes are read where they are."""
         from . import _lib
+        if any(isinstance(f, YuvFrame) for f in frames):
+            return self._put_yuv(list(frames), first_slot)
         h, w = self.shape[:2]
         fb, row = self.frame_nbytes, w * 3
         per_slot = max(1, _STAGE_BYTES // fb)
@@ -414,6 +424,24 @@ class FrameStore(_Resident):
             elif strided:
                 np.copyto(*strided[0])
             self._send(slot, used, (first_slot + i) * fb)
+
+    def _put_yuv(self, frames, first_slot: int):
+        """``put`` for ``YuvFrame``s: chunks of at most ``_STAGE_BYTES`` of host planes and ``AF_YUV_MAX_FRAMES`` frames, each one
+        fill, one copy and one launch"""
+        from . import _lib
+        if not all(isinstance(f, YuvFrame) for f in frames):
+            raise ValueError("evaluator: a list of frames is all numpy arrays or all YuvFrame")
+        if self._yuv is None:
+            self._yuv = YuvConverter(self.device, self._stage)
+        i = 0
+        while i < len(frames):
+            j, used = i, 0
+            while j < len(frames) and j - i < _lib.YUV_MAX_FRAMES and (j == i or used + frames[j].upload_bytes <= _STAGE_BYTES):
+                used += frames[j].upload_bytes
+                j += 1
+            self._yuv.convert([(f, self, self.channel_order, first_slot + k) for k, f in enumerate(frames[i:j], i)])
+            self.uploaded_bytes += used
+            i = j
 
     def view(self, slot: int, n: Optional[int] = None) -> torch.Tensor:
         """the device (H, W, 3) view of slot `slot`, or the (n, H, W, 3) view of the `n` slots from it on"""
@@ -707,10 +735,14 @@ class VideoScorer(_WindowScorer):
     # -- the frame store -----------------------------------------------------------------------------
     def _open_store(self, frames):
         """checks the frames and sizes the store for them: all of them when ``frame_bytes`` allows, else as many as it holds"""
-        shape = frames[0].shape
-        for im in frames:
-            if not is_crop(im) or im.shape != shape:
-                raise AssertionError("evaluator: frames must be HxWx3 uint8 numpy arrays of one size")
+        shape = tuple(frames[0].shape)
+        if any(isinstance(im, YuvFrame) for im in frames):
+            if not all(isinstance(im, YuvFrame) and im.shape == shape for im in frames):
+                raise ValueError("evaluator: a list of frames is all numpy arrays or all YuvFrame, of one size")
+        else:
+            for im in frames:
+                if not is_crop(im) or im.shape != shape:
+                    raise AssertionError("evaluator: frames must be HxWx3 uint8 numpy arrays of one size")
         nbytes = shape[0] * shape[1] * 3
         capacity = min(len(frames), (self.pool_bytes - _POOL_SLACK) // nbytes)
         self._frames, self._resident = frames, capacity == len(frames)

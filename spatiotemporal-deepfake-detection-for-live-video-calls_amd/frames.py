@@ -1,0 +1,258 @@
+"""YUV 4:2:0 frames as a caller has them - what a WebRTC stack (I420), a hardware decoder (NV12) or ffmpeg / PyAV (yuv420p) hands over -
+and their way into the frame stores: ``YuvFrame`` names the planes, ``YuvConverter`` stages host planes through one pinned slot and
+one copy and converts every frame of a call to it, whatever its size, format, store and byte order, in one launch of
+``af_yuv420_to_rgb_u8`` per ``AF_YUV_MAX_FRAMES`` frames (csrc/af_yuv.hip).
+
+The conversion is OpenCV's ``cvtColor(..., COLOR_YUV2BGR_NV12 / _I420)``: fixed-point BT.601, limited range, one (U, V) per 2 x 2
+block of Y.  It equals the numpy restatement of OpenCV's code (tests/yuv_ref.py) byte for byte and is unpinned against cv2 itself,
+which is absent where this is built.  Not built: full-range and BT.709 matrices, 4:2:2 / 4:4:4, 10-bit formats.  There is no CPU
+fallback: without the HIP library the conversion fails."""
+import ctypes as C
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from ._staging import _COPY_THREADS, _SPLIT_BYTES, PinnedRing, stage_rects
+
+# format -> (chroma is one interleaved plane, the first chroma byte / plane in memory is V)
+FORMATS = {"nv12": (True, False), "nv21": (True, True), "i420": (False, False), "yv12": (False, True)}
+_FRAME_ALIGN = 16         # a frame's planes start on a 16-byte boundary of the staging slot: aligned vector loads for the usual widths
+
+
+def _plane(name: str, p):
+    """checks one plane; returns (is a device tensor, rows, row bytes, pitch)"""
+    if isinstance(p, np.ndarray):
+        dev, dtype_ok, strides = False, p.dtype == np.uint8, p.strides
+    elif isinstance(p, torch.Tensor):
+        if not p.is_cuda:
+            raise ValueError("yuv: plane %s is a CPU tensor: planes are numpy arrays or CUDA tensors" % name)
+        dev, dtype_ok, strides = True, p.dtype == torch.uint8, tuple(p.stride())
+    else:
+        raise ValueError("yuv: plane %s is a %s: planes are numpy arrays or CUDA tensors" % (name, type(p).__name__))
+    if not dtype_ok or p.ndim != 2:
+        raise ValueError("yuv: plane %s must be a 2-D uint8 array" % name)
+    rows, row = int(p.shape[0]), int(p.shape[1])
+    if rows < 1 or row < 1:
+        raise ValueError("yuv: plane %s is empty (%d x %d)" % (name, rows, row))
+    if row > 1 and strides[1] != 1:
+        raise ValueError("yuv: plane %s has element stride %d: the bytes of a row must be contiguous" % (name, strides[1]))
+    pitch = int(strides[0]) if rows > 1 else row
+    if pitch < row:
+        raise ValueError("yuv: plane %s has row pitch %d, shorter than its row of %d bytes" % (name, pitch, row))
+    return dev, rows, row, pitch
+
+
+class YuvFrame:
+    """One YUV 4:2:0 frame: ``YuvFrame(fmt, y, u=None, v=None, uv=None)``.
+
+    ``fmt``: ``"nv12"`` / ``"nv21"`` (``y`` and one interleaved plane ``uv`` of (h / 2, w) bytes: U, V, U, V ... - V first for nv21) or
+    ``"i420"`` / ``"yv12"`` (``y``, ``u`` and ``v`` of (h / 2, w / 2) bytes each; the two differ only in the order of the planes in
+    a packed buffer, which ``from_packed`` knows).  Planes are 2-D uint8 with unit element stride and a row stride of at least the
+    row; ``h`` and ``w`` are even, as OpenCV asks.  Either all planes are numpy arrays, or all are CUDA ``torch`` tensors on the
+    device of the store they go to.  ``shape`` is ``(h, w, 3)``, the shape of the converted frame.
+
+    Host planes are copied (into a pinned slot) before the call that takes the frame returns.  Device planes are read where they
+    are, on the stream that is current when the frame is handed in: the caller guarantees they are ready on that stream and stay
+    unchanged until the work the call enqueued has run."""
+
+    __slots__ = ("fmt", "y", "u", "v", "uv", "shape", "on_device", "interleaved", "swap_uv", "_planes")
+
+    def __init__(self, fmt: str, y, u=None, v=None, uv=None):
+        if fmt not in FORMATS:
+            raise ValueError("yuv: format %r is not one of %s" % (fmt, ", ".join(sorted(FORMATS))))
+        self.fmt, self.y, self.u, self.v, self.uv = fmt, y, u, v, uv
+        self.interleaved, self.swap_uv = FORMATS[fmt]
+        if self.interleaved:
+            if uv is None or u is not None or v is not None:
+                raise ValueError("yuv: %s takes y and uv (one interleaved chroma plane)" % fmt)
+            named = [("y", y), ("uv", uv)]
+        else:
+            if u is None or v is None or uv is not None:
+                raise ValueError("yuv: %s takes y, u and v" % fmt)
+            named = [("y", y), ("u", u), ("v", v)]
+            self.swap_uv = False                                  # the planes are named: their order in memory does not matter
+        checked = [_plane(n, p) for n, p in named]
+        if len({c[0] for c in checked}) != 1:
+            raise ValueError("yuv: planes are all numpy arrays or all CUDA tensors, not mixed")
+        self.on_device = checked[0][0]
+        if self.on_device and len({p.device for _, p in named}) != 1:
+            raise ValueError("yuv: the planes are on different devices")
+        h, w = checked[0][1], checked[0][2]
+        if h % 2 or w % 2:
+            raise ValueError("yuv: a 4:2:0 frame has even height and width, not %d x %d" % (h, w))
+        want = (h // 2, w) if self.interleaved else (h // 2, w // 2)
+        for (n, _), c in zip(named[1:], checked[1:]):
+            if (c[1], c[2]) != want:
+                raise ValueError("yuv: plane %s is %d x %d, %d x %d for a %s frame of %d x %d" % (n, c[1], c[2], want[0], want[1], fmt, h, w))
+        if not self.interleaved and checked[1][3] != checked[2][3]:
+            raise ValueError("yuv: planes u and v have row pitches %d and %d: one chroma pitch per frame" % (checked[1][3], checked[2][3]))
+        self.shape = (h, w, 3)
+        self._planes = [(p, c[1], c[2], c[3]) for (_, p), c in zip(named, checked)]
+
+    @classmethod
+    def from_packed(cls, buf, h: int, w: int, fmt: str) -> "YuvFrame":
+        """the ``(h * 3 / 2, w)`` uint8 array OpenCV and most decoders use for a 4:2:0 frame (numpy or a CUDA tensor): h rows of Y,
+        then the chroma as `fmt` lays it out.  Views of `buf`, no copies.  The planar formats need `buf` contiguous (a chroma row is
+        half a row of `buf`); nv12 / nv21 take any row pitch."""
+        if fmt not in FORMATS:
+            raise ValueError("yuv: format %r is not one of %s" % (fmt, ", ".join(sorted(FORMATS))))
+        h, w = int(h), int(w)
+        if h < 2 or w < 2 or h % 2 or w % 2:
+            raise ValueError("yuv: a 4:2:0 frame has even height and width, not %d x %d" % (h, w))
+        if buf.ndim != 2 or tuple(buf.shape) != (h * 3 // 2, w):
+            raise ValueError("yuv: a packed %d x %d frame is a (%d, %d) array, not %s" % (h, w, h * 3 // 2, w, tuple(buf.shape)))
+        if FORMATS[fmt][0]:
+            return cls(fmt, buf[:h], uv=buf[h:])
+        contiguous = buf.flags.c_contiguous if isinstance(buf, np.ndarray) else buf.is_contiguous()
+        if not contiguous:
+            raise ValueError("yuv: a packed %s frame must be contiguous" % fmt)
+        flat = buf.reshape(-1)
+        q = h * w // 4
+        first, second = (flat[h * w + k * q:h * w + (k + 1) * q].reshape(h // 2, w // 2) for k in (0, 1))
+        return cls(fmt, buf[:h], u=second if FORMATS[fmt][1] else first, v=first if FORMATS[fmt][1] else second)
+
+    @property
+    def nbytes(self) -> int:
+        """the bytes of the frame's planes: 1.5 per pixel"""
+        return self.shape[0] * self.shape[1] * 3 // 2
+
+    @property
+    def upload_bytes(self) -> int:
+        """what admitting the frame sends to the device: its planes, or nothing when they are already there"""
+        return 0 if self.on_device else self.nbytes
+
+    @property
+    def device(self) -> Optional[torch.device]:
+        return self.y.device if self.on_device else None
+
+    def planes(self):
+        """``[(plane, rows, row bytes, pitch)]`` in staging order: Y, then the chroma plane(s) (U before V)"""
+        return self._planes
+
+
+def upload_bytes(frame) -> int:
+    """the bytes a frame sends to the device when it is admitted: a numpy frame's own, a ``YuvFrame``'s planes if they are on the host"""
+    return frame.upload_bytes if isinstance(frame, YuvFrame) else frame.nbytes
+
+
+def store_ref(store, channel_order: str):
+    """the ``af_store_ref`` of a ``FrameStore`` whose pixels are in `channel_order`"""
+    from . import _lib
+    h, w = store.shape[:2]
+    return _lib.StoreRef(store.dev.data_ptr(), _lib.FrameStore(store.dev.numel(), store.frame_nbytes, w * 3, store.capacity, h, w, 0),
+                         int(channel_order == "bgr"), 0)
+
+
+def _address(p) -> int:
+    return p.__array_interface__["data"][0] if isinstance(p, np.ndarray) else p.data_ptr()
+
+
+def staged_offsets(frames: Sequence[YuvFrame]) -> Tuple[List[int], int]:
+    """where each host frame's planes start in a staging slot (device-resident frames: -1), and the bytes used"""
+    offs, used = [], 0
+    for f in frames:
+        if f.on_device:
+            offs.append(-1)
+        else:
+            used = -(-used // _FRAME_ALIGN) * _FRAME_ALIGN
+            offs.append(used)
+            used += f.nbytes
+    return offs, used
+
+
+def stage_planes(base: int, frames: Sequence[YuvFrame], offs: Sequence[int], nbytes: int) -> None:
+    """the planes of the host frames -> memory at address `base`, frame i from ``offs[i]`` on as tight Y rows, then tight chroma rows
+    (U before V): ``af_stage_rows_u8``, one memcpy per plane whose pitch equals its row, else one per row.  From 1 MiB on every plane
+    goes as an upper and a lower band of rows, the upper bands on one copy thread and the lower ones on the other."""
+    from . import _lib
+    bands = _COPY_THREADS if nbytes >= _SPLIT_BYTES else 1
+    rects = []
+    for t in range(bands):
+        for f, off in zip(frames, offs):
+            if off < 0:
+                continue
+            for p, rows, row, pitch in f.planes():
+                r0, r1 = rows * t // bands, rows * (t + 1) // bands
+                if r1 > r0:
+                    rects.append(_lib.StageRect(_address(p) + r0 * pitch, off + r0 * row, pitch, r1 - r0, row))
+                off += rows * row
+    if rects:
+        stage_rects(base, (_lib.StageRect * len(rects))(*rects), len(rects), nbytes)
+
+
+class YuvConverter:
+    """``convert([(YuvFrame, FrameStore, channel_order, slot), ...])``: every frame into its slot of its store, converted on the
+    device.  The host planes of all frames go tightly into ONE pinned slot and cross in ONE asynchronous copy; one launch per
+    ``AF_YUV_MAX_FRAMES`` frames follows on the current stream and reads host frames from the slot's device twin, device-resident
+    ones where they are.  The slot's event is recorded behind the last launch, the last reader of both buffers; nothing waits.
+    ``launches`` and ``copies`` count what was enqueued."""
+
+    def __init__(self, device, stage: Optional[PinnedRing] = None):
+        from . import _lib                                        # fails loudly when libafhip.so is missing
+        self.device = device
+        self._stage = stage if stage is not None else PinnedRing(min_bytes=1 << 20, headroom=True)
+        self._launch = _lib.lib.af_yuv420_to_rgb_u8
+        self.launches = self.copies = 0
+
+    @staticmethod
+    def table(frames: Sequence[YuvFrame], addresses: Sequence[int], stores, slots: Sequence[int]):
+        """the planner's part, host only: ``frames[i]`` whose planes start at device address ``addresses[i]`` (tight Y, then tight
+        chroma; None: the frame's own device planes) into slot ``slots[i]`` of ``stores[i]`` (an ``_lib.StoreRef`` each) -> the
+        ``YuvItem`` array of one launch"""
+        from . import _lib
+        refs, index, descs = [], {}, (_lib.YuvFrameDesc * max(1, len(frames)))()
+        for i, (f, base, ref, slot) in enumerate(zip(frames, addresses, stores, slots)):
+            if id(ref) not in index:
+                index[id(ref)] = len(refs)
+                refs.append(ref)
+            h, w = f.shape[:2]
+            if base is None:
+                ptrs = [_address(p) for p, _, _, _ in f.planes()]
+                y_pitch, c_pitch = f.planes()[0][3], f.planes()[1][3]
+            else:
+                ptrs, y_pitch, c_pitch = [base, base + h * w], w, (w if f.interleaved else w // 2)
+                if not f.interleaved:
+                    ptrs.append(base + h * w + h * w // 4)
+            descs[i] = _lib.YuvFrameDesc(ptrs[0], ptrs[1], None if f.interleaved else ptrs[2], y_pitch, c_pitch, h, w,
+                                         int(f.interleaved), int(f.swap_uv), index[id(ref)], int(slot))
+        items = (_lib.YuvItem * max(1, len(frames)))()
+        store_arr = (_lib.StoreRef * max(1, len(refs)))(*refs)
+        _lib.check(_lib.lib.af_yuv420_plan_u8(C.byref(descs), len(frames), C.byref(store_arr), len(refs), C.byref(items)), "yuv420_plan_u8")
+        return items
+
+    def convert(self, jobs) -> None:
+        from . import _lib
+        jobs = list(jobs)
+        if not jobs:
+            return
+        frames = [j[0] for j in jobs]
+        for f, store, order, slot in jobs:
+            if not isinstance(f, YuvFrame):
+                raise ValueError("yuv: a list of frames is all numpy arrays or all YuvFrame")
+            if tuple(f.shape) != tuple(store.shape):
+                raise ValueError("yuv: a frame of %s for a store of %s" % (f.shape, tuple(store.shape)))
+            if f.on_device and f.device != store.device:
+                raise ValueError("yuv: the planes are on %s, the frame store on %s" % (f.device, store.device))
+        refs = {}
+        for _, store, order, _ in jobs:
+            if (id(store), order) not in refs:
+                refs[(id(store), order)] = store_ref(store, order)
+        with torch.cuda.device(self.device):
+            offs, used = staged_offsets(frames)
+            slot, dev_base = None, 0
+            if used:
+                slot = self._stage.acquire(used, self.device)
+                stage_planes(slot.host.data_ptr(), frames, offs, used)
+                slot.dev[:used].copy_(slot.host[:used], non_blocking=True)
+                self.copies += 1
+                dev_base = slot.dev.data_ptr()
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            for lo in range(0, len(jobs), _lib.YUV_MAX_FRAMES):
+                part = jobs[lo:lo + _lib.YUV_MAX_FRAMES]
+                items = self.table([j[0] for j in part], [None if o < 0 else dev_base + o for o in offs[lo:lo + len(part)]],
+                                   [refs[(id(j[1]), j[2])] for j in part], [j[3] for j in part])
+                _lib.check(self._launch(C.byref(items), len(part), stream), "yuv420_to_rgb_u8")
+                self.launches += 1
+            if slot is not None:
+                slot.record()          # behind the last launch: it reads the device twin, which the next copy into this slot rewrites

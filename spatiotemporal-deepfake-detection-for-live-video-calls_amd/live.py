@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from ._staging import is_crop
+from .frames import YuvConverter, YuvFrame, store_ref, upload_bytes
 from .aligner import STD_POINTS_256
 from .evaluator import RECTS, RECTS_BGR, FrameStore, WindowWarp, _clip_buffers, _fit, _FrameTrack, _network_device, _padded, get_crop_box, partition
 from .tracker import ByteTracker, STrack, iou_distance
@@ -118,12 +119,19 @@ class LiveCall:
     def admit(self, frame: np.ndarray) -> int:
         """the first half of ``step``: the captured frame goes into the ring, once (:373-376); returns its index.  Between
         ``admit`` and ``advance`` a caller may read the frame where it now lies (``frame_view``): a detector, the quality gate."""
-        if not is_crop(frame) or not frame.flags.c_contiguous:
+        k = self.admit_books(frame)
+        self._store_frame(frame, k % self.ring_frames)
+        return k
+
+    def admit_books(self, frame) -> int:
+        """``admit`` without the pixels: checks the frame, counts it and re-opens the ring when its size has changed; returns its
+        index.  The caller then moves the pixels into ring slot ``index % ring_frames`` (``CallServer`` does, for all its calls'
+        ``YuvFrame``s at once)."""
+        if not isinstance(frame, YuvFrame) and (not is_crop(frame) or not frame.flags.c_contiguous):
             raise AssertionError("live: a frame must be a C-contiguous HxWx3 uint8 numpy array")
         self.frame_idx += 1
-        if self._shape != frame.shape:
+        if self._shape != tuple(frame.shape):
             self._open_ring(frame.shape)
-        self._store_frame(frame, self.frame_idx % self.ring_frames)
         return self.frame_idx
 
     def advance(self, faces: Sequence[Tuple], alive: Sequence = ()) -> List[Tuple]:
@@ -204,7 +212,7 @@ class LiveCall:
     def _new_ring(self, shape):
         dev = _network_device(self.network)
         with torch.cuda.device(dev):
-            store = FrameStore(dev)
+            store = FrameStore(dev, self.channel_order)
             store.open(shape, self.ring_frames)
             warp = WindowWarp(_FORMS[self.channel_order], store, self.clip_size, self.size, self.max_batch)
             return _DeviceSide(store, warp, _clip_buffers(1, self.max_batch, self.clip_size, self.size, dev)[0])
@@ -220,7 +228,7 @@ class LiveCall:
                 cur.wait_event(self._done)
             ring.put([frame], slot)
             self._done.record(cur)
-        self.uploaded_bytes += frame.nbytes
+        self.uploaded_bytes += upload_bytes(frame)
 
     def _scorer(self, run: int):
         from .classifier import LiveScorer
@@ -589,7 +597,7 @@ class _ServedRing(LiveCall):
     def _new_ring(self, shape):
         dev = _network_device(self.network)
         with torch.cuda.device(dev):
-            store = FrameStore(dev)
+            store = FrameStore(dev, self.channel_order)
             store.open(shape, self.ring_frames)
         return _DeviceSide(store, None, None)
 
@@ -597,7 +605,7 @@ class _ServedRing(LiveCall):
         ring = self._ring.store
         with torch.cuda.device(ring.device):
             ring.put([frame], slot)
-        self.uploaded_bytes += frame.nbytes
+        self.uploaded_bytes += upload_bytes(frame)
 
     def _score(self, ready):
         raise RuntimeError("live: a served call is scored by its CallServer")
@@ -611,11 +619,7 @@ class _ServedCall(RealtimeCall):
         raise RuntimeError("live: a served call is stepped by its CallServer (server.step({cid: frame}))")
 
 
-def _store_ref(store: FrameStore, channel_order: str):
-    from . import _lib
-    h, w = store.shape[:2]
-    return _lib.StoreRef(store.dev.data_ptr(), _lib.FrameStore(store.dev.numel(), store.frame_nbytes, w * 3, store.capacity, h, w, 0),
-                         int(channel_order == "bgr"), 0)
+_store_ref = store_ref
 
 
 class StoresQuality(_QualitySums):
@@ -701,17 +705,25 @@ class StoresWarp:
 class ServerStats:
     """what a ``CallServer`` enqueued and waited for: ``last`` for the last step, ``total`` since the server was made, each with
     ``detect`` (calls of ``af_yunet_detect_frames``, or of a detector's ``detect_views``), ``quality``, ``warp`` (launches),
-    ``replay`` (graph replays) and ``wait`` (host waits for the device)"""
+    ``replay`` (graph replays), ``wait`` (host waits for the device), ``convert`` (launches of ``af_yuv420_to_rgb_u8``) and
+    ``yuv_copies`` (host-to-device copies of staged YUV planes)"""
     KEYS = ("detect", "quality", "warp", "replay", "wait")
+    YUV_KEYS = ("convert", "yuv_copies")       # appear in ``last`` / ``total`` once a step has YUV frames; read as 0 before
+
+    class _Counts(dict):
+        def __missing__(self, key):
+            if key in ServerStats.YUV_KEYS:
+                return 0
+            raise KeyError(key)
 
     def __init__(self):
         self.steps = 0
-        self.last = dict.fromkeys(self.KEYS, 0)
-        self.total = dict.fromkeys(self.KEYS, 0)
+        self.last = self._Counts.fromkeys(self.KEYS, 0)
+        self.total = self._Counts.fromkeys(self.KEYS, 0)
 
     def begin(self):
         self.steps += 1
-        self.last = dict.fromkeys(self.KEYS, 0)
+        self.last = self._Counts.fromkeys(self.KEYS, 0)
 
     def count(self, key: str, n: int = 1):
         self.last[key] += n
@@ -732,6 +744,11 @@ class CallServer:
     ``RealtimeCall`` is a call's own - ``call_defaults`` here, overridden per call in ``open`` - as are its frame size, tracker,
     ``CallState`` and frame ring.  ``detector``: a ``YuNet`` (or ``modelPath`` to build one with ``conf``), or any object with
     ``detect_views(views) -> (rows, counts)``.
+
+    A frame is a numpy array or a ``YuvFrame`` (the mapping may mix them).  The ``YuvFrame``s of a step are admitted together: the
+    host planes of all calls fill one pinned slot and cross in one copy, and one ``af_yuv420_to_rgb_u8`` launch per 64 frames
+    converts them - and the device-resident ones where they lie - into the calls' own ring slots, each in its call's
+    ``channel_order``.  The conversion needs no wait.
 
     One step, whatever the number of calls: every frame is admitted into its call's ring (one upload per frame); the calls that
     detect on this frame are grouped by frame shape and each group goes through ``detect_views`` 64 frames at a time, all counts
@@ -768,6 +785,7 @@ class CallServer:
         self._next = 0
         self._quality = StoresQuality(self.device)
         self._warp = StoresWarp(self.device, self.clip_size, self.size, self.max_batch)
+        self._yuv = YuvConverter(self.device)     # its own pinned ring: the YUV planes of all calls of a step share one slot
         self._clip = None                  # ``max_batch`` clips, the static input of the replayed forwards
         self._scorers = {}                 # clips per forward -> LiveScorer on the front of the clip buffer
         self._done = None                  # recorded behind the last launch of every step
@@ -817,9 +835,20 @@ class CallServer:
 
     def _step(self, calls, cur):
         ticks = []
+        yuv = []
         for cid, c, frame in calls:                                                        # 1. the uploads
-            ticks.append(c.call.admit(frame))
-            self.uploaded_bytes += frame.nbytes
+            if isinstance(frame, YuvFrame):                                                # the books now, the pixels of all of them below
+                ticks.append(c.call.admit_books(frame))
+                c.call.uploaded_bytes += frame.upload_bytes
+                yuv.append((frame, c.call._ring.store, c.call.channel_order, ticks[-1] % c.call.ring_frames))
+            else:
+                ticks.append(c.call.admit(frame))
+            self.uploaded_bytes += upload_bytes(frame)
+        if yuv:                                                                            # one fill, one copy, one launch per 64
+            launched, copied = self._yuv.launches, self._yuv.copies
+            self._yuv.convert(yuv)
+            self.stats.count("convert", self._yuv.launches - launched)
+            self.stats.count("yuv_copies", self._yuv.copies - copied)
         detecting = [i for i, (_, c, _) in enumerate(calls) if ticks[i] % max(1, c.detect_every) == 0]
         dets = dict(zip(detecting, self._detect([calls[i][1].call.frame_view(ticks[i]) for i in detecting])))      # 2.
         found, wanted = [], []
