@@ -434,7 +434,10 @@ int af_warp_affine_windows_u8(const void* pool, const void* table, int n_windows
  * frame of the store.  The kernel reads tap pairs as 6 bytes from an address clamped into the rectangle and gives a tap outside the
  * rectangle weight 0: the pixels next to a rectangle never reach the result.
  * The launch trusts the table as af_warp_affine_windows_u8 does, compares the header (a table of the pool form is a mismatch too)
- * and writes nothing on a mismatch.  (Added within ABI 6, like the pool form.) */
+ * and writes nothing on a mismatch.  (Added within ABI 6, like the pool form.)
+ * Widened since, with af_window_rects_plan_stores_u8, whose planner this now shares: EVERY refusal of one (window, frame) - not the
+ * canvas misfit alone - sets *bad_window / *bad_frame, and a refused table's header is stamped so that no launch takes it; a caller
+ * that read bad_window >= 0 as "canvas misfit" must look at the named rectangle, or at af_last_error, first. */
 typedef struct af_frame_store {
     int64_t store_bytes;
     int64_t frame_stride, row_pitch;

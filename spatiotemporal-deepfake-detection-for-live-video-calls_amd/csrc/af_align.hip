@@ -274,128 +274,85 @@ extern "C" int64_t af_window_rects_table_bytes(int n_windows, int clip_size) {
     return af::window_table_bytes(n_windows, clip_size, sizeof(af::WindowRect));
 }
 
-extern "C" int af_window_rects_plan_u8(const af_window_desc* windows, const af_frame_rect* rects, int n_windows, int clip_size, int size,
-                                       const af_frame_store* store, void* table, int64_t table_bytes, int32_t* bad_window, int32_t* bad_frame) {
-    using namespace af;
+namespace af {
+// what a checked rectangle becomes in the table: the one place the two rectangle forms differ on the host
+static inline void window_item(WindowRect* out, const af_store_ref& st, int64_t offset, const af_frame_rect& r) {
+    *out = WindowRect{offset, r.ih, r.iw, r.x, r.y, (int32_t)st.desc.row_pitch, 0};
+}
+static inline void window_item(WindowStoreRect* out, const af_store_ref& st, int64_t offset, const af_frame_rect& r) {
+    *out = WindowStoreRect{(const unsigned char*)st.base + offset, r.ih, r.iw, r.x, r.y, (int32_t)st.desc.row_pitch, st.bgr ? 1 : 0};
+}
+
+// The planner of both rectangle forms.  WindowStoreRect: af_frame_rect.reserved names the rectangle's store in `stores`.
+// WindowRect: one store, which every rectangle is of (reserved is not read) and whose base the launch is handed.
+// A refusal of one (window, frame) sets *bad_window / *bad_frame, whatever its reason, and a refused table is no table.
+template <typename Item>
+static int plan_window_rects(const char* who, const af_window_desc* windows, const af_frame_rect* rects, int n_windows, int clip_size, int size,
+                             const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes, int32_t* bad_window, int32_t* bad_frame) {
+    constexpr bool kListed = WbKind<Item>::value == WB_KIND_STORES;
     if (bad_window) *bad_window = -1;
     if (bad_frame) *bad_frame = -1;
-    AF_REQUIRE(windows && rects && store && table, "window_rects_plan: null argument");
+    AF_REQUIRE(windows && rects && stores && table, "%s: null argument", who);
     AF_REQUIRE(n_windows > 0 && n_windows <= AF_WINDOW_MAX_BATCH && clip_size > 0 && clip_size <= AF_ALIGN_MAX_FRAMES,
-               "window_rects_plan: %d windows of %d frames (at most %d of %d)", n_windows, clip_size, AF_WINDOW_MAX_BATCH, AF_ALIGN_MAX_FRAMES);
-    AF_REQUIRE(size > 0 && size <= AF_WINDOW_MAX_SIZE && size % 4 == 0, "window_rects_plan: size %d (a multiple of 4, at most %d)", size, AF_WINDOW_MAX_SIZE);
-    const int64_t need = window_table_bytes(n_windows, clip_size, sizeof(WindowRect));
-    AF_REQUIRE(table_bytes >= need, "window_rects_plan: table of %lld bytes, %lld needed", (long long)table_bytes, (long long)need);
-    const af_frame_store& s = *store;
-    AF_REQUIRE(s.n_frames > 0 && s.height > 0 && s.width > 0 && s.height <= 32767 && s.width <= 32767, "window_rects_plan: store of %d frames %dx%d",
-               s.n_frames, s.width, s.height);
-    const int64_t frame_span = (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3;      // first to last byte of one frame
-    AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span,
-               "window_rects_plan: row pitch %lld, frame stride %lld for frames of %dx%d", (long long)s.row_pitch, (long long)s.frame_stride, s.width, s.height);
-    AF_REQUIRE(s.store_bytes >= (int64_t)(s.n_frames - 1) * s.frame_stride + frame_span, "window_rects_plan: %d frames do not fit a store of %lld bytes",
-               s.n_frames, (long long)s.store_bytes);
+               "%s: %d windows of %d frames (at most %d of %d)", who, n_windows, clip_size, AF_WINDOW_MAX_BATCH, AF_ALIGN_MAX_FRAMES);
+    AF_REQUIRE(size > 0 && size <= AF_WINDOW_MAX_SIZE && size % 4 == 0, "%s: size %d (a multiple of 4, at most %d)", who, size, AF_WINDOW_MAX_SIZE);
+    AF_REQUIRE(n_stores > 0 && n_stores <= AF_MAX_STORES, "%s: %d stores (1 to %d)", who, n_stores, AF_MAX_STORES);
+    const int64_t need = window_table_bytes(n_windows, clip_size, sizeof(Item));
+    AF_REQUIRE(table_bytes >= need, "%s: table of %lld bytes, %lld needed", who, (long long)table_bytes, (long long)need);
+    for (int i = 0; i < n_stores; ++i) {
+        AF_REQUIRE(!kListed || stores[i].base, "%s: store %d: null base pointer", who, i);
+        const int rc = check_frame_store(who, kListed ? i : -1, stores[i].desc);
+        if (rc != AF_OK) return rc;
+    }
     WindowTableHeader* hd = (WindowTableHeader*)table;
     WindowXform* xf = (WindowXform*)(hd + 1);
-    WindowRect* out = (WindowRect*)(xf + n_windows);
+    Item* out = (Item*)(xf + n_windows);
+    hd->kind = -1;                                                  // a table that was refused half-way is no table
     for (int w = 0; w < n_windows; ++w) {
         const af_window_desc& d = windows[w];
-        AF_REQUIRE(d.canvas_h > 0 && d.canvas_w > 0 && d.canvas_h <= 32767 && d.canvas_w <= 32767, "window_rects_plan: window %d: bad canvas %dx%d",
-                   w, d.canvas_w, d.canvas_h);
+        AF_REQUIRE(d.canvas_h > 0 && d.canvas_w > 0 && d.canvas_h <= 32767 && d.canvas_w <= 32767, "%s: window %d: bad canvas %dx%d", who, w,
+                   d.canvas_w, d.canvas_h);
         invert_affine_cv(d.tfm, xf[w].m);
         for (int t = 0; t < clip_size; ++t) {
             const af_frame_rect& r = rects[w * clip_size + t];
-            AF_REQUIRE(r.frame >= 0 && r.frame < s.n_frames && r.ih > 0 && r.iw > 0 && r.rx >= 0 && r.ry >= 0 &&
-                       (int64_t)r.rx + r.iw <= s.width && (int64_t)r.ry + r.ih <= s.height,
-                       "window_rects_plan: window %d frame %d: rectangle %dx%d at (%d,%d) of frame %d leaves the %d frames of %dx%d", w, t, r.iw, r.ih,
-                       r.rx, r.ry, r.frame, s.n_frames, s.width, s.height);
-            const int64_t offset = (int64_t)r.frame * s.frame_stride + (int64_t)r.ry * s.row_pitch + (int64_t)r.rx * 3;
-            // the kernel reads the two taps of a row as 6 bytes: inside a frame the 3 bytes behind a rectangle's last pixel are the
-            // frame's next pixels, so only a rectangle that ends with the store needs them to be there
-            AF_REQUIRE(offset + (int64_t)(r.ih - 1) * s.row_pitch + (int64_t)r.iw * 3 + 3 <= s.store_bytes,
-                       "window_rects_plan: window %d frame %d: 3 readable bytes must follow the rectangle that ends the store of %lld bytes", w, t,
-                       (long long)s.store_bytes);
+            const int store = kListed ? r.reserved : 0;
+            const bool listed = store >= 0 && store < n_stores;
+            int64_t offset = 0;
+            // the kernel reads the two taps of a row as 6 bytes: 3 readable bytes behind a rectangle that ends its store
+            const int fault = listed ? frame_rect_fault(stores[store].desc, r, 3, &offset) : 0;
             // the reference pastes with new_image[y:y+ih, x:x+iw] = image, which numpy refuses unless the crop fits the canvas
-            if (r.x < 0 || r.y < 0 || (long long)r.x + r.iw > d.canvas_w || (long long)r.y + r.ih > d.canvas_h) {
+            const bool misfit = r.x < 0 || r.y < 0 || (long long)r.x + r.iw > d.canvas_w || (long long)r.y + r.ih > d.canvas_h;
+            if (!listed || fault || misfit) {
                 if (bad_window) *bad_window = w;
                 if (bad_frame) *bad_frame = t;
-                return set_error(AF_ERR_ARG, "aligner: window %d frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas", w, t, r.iw, r.ih, r.x, r.y,
-                                 d.canvas_w, d.canvas_h);
+                char item[48];
+                snprintf(item, sizeof item, "window %d frame %d", w, t);
+                if (!listed) return set_error(AF_ERR_ARG, "%s: %s: the rectangle names store %d of %d", who, item, store, n_stores);
+                if (fault) return refuse_frame_rect(who, item, kListed ? store : -1, stores[store].desc, r, fault);
+                return set_error(AF_ERR_ARG, "aligner: %s (%dx%d at %d,%d) does not fit the %dx%d canvas", item, r.iw, r.ih, r.x, r.y, d.canvas_w,
+                                 d.canvas_h);
             }
-            out[w * clip_size + t] = WindowRect{offset, r.ih, r.iw, r.x, r.y, (int32_t)s.row_pitch, 0};
+            window_item(&out[w * clip_size + t], stores[store], offset, r);
         }
     }
-    hd->n_windows = n_windows; hd->clip_size = clip_size; hd->size = size; hd->kind = WB_KIND_RECTS;
+    hd->n_windows = n_windows; hd->clip_size = clip_size; hd->size = size; hd->kind = WbKind<Item>::value;
     return AF_OK;
+}
+}  // namespace af
+
+extern "C" int af_window_rects_plan_u8(const af_window_desc* windows, const af_frame_rect* rects, int n_windows, int clip_size, int size,
+                                       const af_frame_store* store, void* table, int64_t table_bytes, int32_t* bad_window, int32_t* bad_frame) {
+    const af_store_ref one{nullptr, store ? *store : af_frame_store{}, 0, 0};      // the launch is handed the base; the items hold offsets
+    return af::plan_window_rects<af::WindowRect>("window_rects_plan", windows, rects, n_windows, clip_size, size, store ? &one : nullptr, 1, table,
+                                                 table_bytes, bad_window, bad_frame);
 }
 
 // ---- the same launch out of SEVERAL stores: af_frame_rect.reserved names the rectangle's store ----
 extern "C" int af_window_rects_plan_stores_u8(const af_window_desc* windows, const af_frame_rect* rects, int n_windows, int clip_size, int size,
                                               const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes, int32_t* bad_window,
                                               int32_t* bad_frame) {
-    using namespace af;
-    if (bad_window) *bad_window = -1;
-    if (bad_frame) *bad_frame = -1;
-    AF_REQUIRE(windows && rects && stores && table, "window_rects_plan_stores: null argument");
-    AF_REQUIRE(n_windows > 0 && n_windows <= AF_WINDOW_MAX_BATCH && clip_size > 0 && clip_size <= AF_ALIGN_MAX_FRAMES,
-               "window_rects_plan_stores: %d windows of %d frames (at most %d of %d)", n_windows, clip_size, AF_WINDOW_MAX_BATCH, AF_ALIGN_MAX_FRAMES);
-    AF_REQUIRE(size > 0 && size <= AF_WINDOW_MAX_SIZE && size % 4 == 0, "window_rects_plan_stores: size %d (a multiple of 4, at most %d)", size,
-               AF_WINDOW_MAX_SIZE);
-    AF_REQUIRE(n_stores > 0 && n_stores <= AF_MAX_STORES, "window_rects_plan_stores: %d stores (1 to %d)", n_stores, AF_MAX_STORES);
-    const int64_t need = window_table_bytes(n_windows, clip_size, sizeof(WindowStoreRect));
-    AF_REQUIRE(table_bytes >= need, "window_rects_plan_stores: table of %lld bytes, %lld needed", (long long)table_bytes, (long long)need);
-    for (int i = 0; i < n_stores; ++i) {
-        const af_frame_store& s = stores[i].desc;
-        AF_REQUIRE(stores[i].base, "window_rects_plan_stores: store %d: null base pointer", i);
-        AF_REQUIRE(s.n_frames > 0 && s.height > 0 && s.width > 0 && s.height <= 32767 && s.width <= 32767,
-                   "window_rects_plan_stores: store %d of %d frames %dx%d", i, s.n_frames, s.width, s.height);
-        const int64_t frame_span = (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3;
-        AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span,
-                   "window_rects_plan_stores: store %d: row pitch %lld, frame stride %lld for frames of %dx%d", i, (long long)s.row_pitch,
-                   (long long)s.frame_stride, s.width, s.height);
-        AF_REQUIRE(s.store_bytes >= (int64_t)(s.n_frames - 1) * s.frame_stride + frame_span,
-                   "window_rects_plan_stores: store %d: %d frames do not fit a store of %lld bytes", i, s.n_frames, (long long)s.store_bytes);
-    }
-    WindowTableHeader* hd = (WindowTableHeader*)table;
-    WindowXform* xf = (WindowXform*)(hd + 1);
-    WindowStoreRect* out = (WindowStoreRect*)(xf + n_windows);
-    hd->kind = -1;                                                  // a table that was refused half-way is no table
-    for (int w = 0; w < n_windows; ++w) {
-        const af_window_desc& d = windows[w];
-        AF_REQUIRE(d.canvas_h > 0 && d.canvas_w > 0 && d.canvas_h <= 32767 && d.canvas_w <= 32767,
-                   "window_rects_plan_stores: window %d: bad canvas %dx%d", w, d.canvas_w, d.canvas_h);
-        invert_affine_cv(d.tfm, xf[w].m);
-        for (int t = 0; t < clip_size; ++t) {
-            const af_frame_rect& r = rects[w * clip_size + t];
-            const char* why = nullptr;
-            int64_t offset = 0;
-            if (r.reserved < 0 || r.reserved >= n_stores) why = "names a store outside the list";
-            else {
-                const af_frame_store& s = stores[r.reserved].desc;
-                offset = (int64_t)r.frame * s.frame_stride + (int64_t)r.ry * s.row_pitch + (int64_t)r.rx * 3;
-                if (!(r.frame >= 0 && r.frame < s.n_frames && r.ih > 0 && r.iw > 0 && r.rx >= 0 && r.ry >= 0 &&
-                      (int64_t)r.rx + r.iw <= s.width && (int64_t)r.ry + r.ih <= s.height))
-                    why = "leaves its frame or the frames of its store";
-                // the 6-byte tap reads: only a rectangle that ends its store needs 3 readable bytes behind it
-                else if (offset + (int64_t)(r.ih - 1) * s.row_pitch + (int64_t)r.iw * 3 + 3 > s.store_bytes)
-                    why = "ends its store without 3 readable bytes behind it";
-            }
-            // the reference pastes with new_image[y:y+ih, x:x+iw] = image, which numpy refuses unless the crop fits the canvas
-            const bool misfit = !why && (r.x < 0 || r.y < 0 || (long long)r.x + r.iw > d.canvas_w || (long long)r.y + r.ih > d.canvas_h);
-            if (why || misfit) {
-                if (bad_window) *bad_window = w;
-                if (bad_frame) *bad_frame = t;
-                if (misfit)
-                    return set_error(AF_ERR_ARG, "aligner: window %d frame %d (%dx%d at %d,%d) does not fit the %dx%d canvas", w, t, r.iw, r.ih, r.x,
-                                     r.y, d.canvas_w, d.canvas_h);
-                return set_error(AF_ERR_ARG, "window_rects_plan_stores: window %d frame %d: rectangle %dx%d at (%d,%d) of frame %d of store %d %s", w, t,
-                                 r.iw, r.ih, r.rx, r.ry, r.frame, r.reserved, why);
-            }
-            const af_store_ref& st = stores[r.reserved];
-            out[w * clip_size + t] = WindowStoreRect{(const unsigned char*)st.base + offset, r.ih, r.iw, r.x, r.y, (int32_t)st.desc.row_pitch,
-                                                     st.bgr ? 1 : 0};
-        }
-    }
-    hd->n_windows = n_windows; hd->clip_size = clip_size; hd->size = size; hd->kind = WB_KIND_STORES;
-    return AF_OK;
+    return af::plan_window_rects<af::WindowStoreRect>("window_rects_plan_stores", windows, rects, n_windows, clip_size, size, stores, n_stores, table,
+                                                      table_bytes, bad_window, bad_frame);
 }
 
 extern "C" int af_warp_affine_window_stores_u8(const void* table, int n_windows, int clip_size, int size, void* out, void* stream) {

@@ -264,6 +264,44 @@ int device_cus();
             return af::set_error(AF_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e__)); \
     } while (0)
 
+// ---- frame stores (af_hip.h: af_frame_store / af_frame_rect): the host checks of every entry point that is handed one ----
+static inline int64_t frame_span(const af_frame_store& s) { return (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3; }   // first to last byte of one frame
+struct StoreName {                                                // "store 3", or "the store" for index -1; made only for a message
+    char text[24];
+    explicit StoreName(int index) { index < 0 ? snprintf(text, sizeof text, "the store") : snprintf(text, sizeof text, "store %d", index); }
+};
+// Is this store sane?  `who`: the entry point, for the message.  `whole`: all n_frames frames must lie inside store_bytes (every
+// reader of rectangles); the YUV planner writes one slot, checks that slot's bytes itself and passes false.
+static inline int check_frame_store(const char* who, int index, const af_frame_store& s, bool whole = true) {
+    AF_REQUIRE(s.n_frames > 0 && s.height > 0 && s.width > 0 && s.height <= 32767 && s.width <= 32767, "%s: %s of %d frames %dx%d", who,
+               StoreName(index).text, s.n_frames, s.width, s.height);
+    AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span(s),
+               "%s: %s: row pitch %lld, frame stride %lld for frames of %dx%d", who, StoreName(index).text, (long long)s.row_pitch,
+               (long long)s.frame_stride, s.width, s.height);
+    AF_REQUIRE(!whole || s.store_bytes >= (int64_t)(s.n_frames - 1) * s.frame_stride + frame_span(s), "%s: %s: %d frames do not fit a store of %lld bytes",
+               who, StoreName(index).text, s.n_frames, (long long)s.store_bytes);
+    return AF_OK;
+}
+// Is this rectangle inside its frame, and the frame in the (checked) store?  Yields the byte offset of its first pixel and returns
+// 0, or what is wrong with it for refuse_frame_rect.  `slack`: readable bytes wanted behind the rectangle's last pixel (3 for the
+// warp's 6-byte tap reads).  Inside a frame those are the frame's next pixels: only a rectangle that ends the store can lack them.
+static inline int frame_rect_fault(const af_frame_store& s, const af_frame_rect& r, int slack, int64_t* offset) {
+    if (!(r.frame >= 0 && r.frame < s.n_frames && r.ih > 0 && r.iw > 0 && r.rx >= 0 && r.ry >= 0 && (int64_t)r.rx + r.iw <= s.width &&
+          (int64_t)r.ry + r.ih <= s.height))
+        return 1;
+    *offset = (int64_t)r.frame * s.frame_stride + (int64_t)r.ry * s.row_pitch + (int64_t)r.rx * 3;
+    return *offset + (int64_t)(r.ih - 1) * s.row_pitch + (int64_t)r.iw * 3 + slack > s.store_bytes ? 2 : 0;
+}
+// ... and the refusal in words; `item` is the caller's name for the rectangle ("window 1 frame 2", "rectangle 3")
+static inline int refuse_frame_rect(const char* who, const char* item, int index, const af_frame_store& s, const af_frame_rect& r, int fault) {
+    const StoreName name(index);
+    if (fault == 1)
+        return set_error(AF_ERR_ARG, "%s: %s: %dx%d at (%d,%d) of frame %d leaves the %d frames of %dx%d of %s", who, item, r.iw, r.ih, r.rx, r.ry,
+                         r.frame, s.n_frames, s.width, s.height, name.text);
+    return set_error(AF_ERR_ARG, "%s: %s: 3 readable bytes must follow the rectangle that ends %s of %lld bytes", who, item, name.text,
+                     (long long)s.store_bytes);
+}
+
 // the event marks of a launch sequence: the i-th call records ev[i] on s, so mark() before launch 0 and after every
 // launch gives launch i the span between ev[i] and ev[i + 1].  Does nothing when ev is null (an untimed run).
 struct Marks {

@@ -29,24 +29,9 @@ namespace af {
 constexpr int Q_TH = 8, Q_TW = 32;                  // the tile of half-size pixels one workgroup takes
 constexpr int Q_GH = Q_TH + 2, Q_GW = Q_TW + 2;     // with its halo
 
-struct QualityRect {
-    int32_t frame, x0, y0, w, h;
-    int32_t first_tile;                             // prefix sum of the tiles of the rectangles before this one
-    int32_t grey_offset;                            // prefix sum of their dw * dh (the debug image's place)
-    int32_t reserved;
-};
-
-struct QualityArgs {
-    const unsigned char* store;
-    af_quality_sums* sums;
-    unsigned char* grey;                            // null outside tests
-    long long frame_stride, row_pitch;
-    int n, total_tiles, bgr, reserved;
-    QualityRect r[AF_QUALITY_MAX_RECTS];
-};
-
-// The several-stores form (af_face_quality_stores_u8): a rectangle carries the absolute address of its first pixel, its store's row
-// pitch and byte order, so the launch needs no table of stores; 64 x 32 bytes + the header stay far under the 4 KB of arguments.
+// A rectangle carries the absolute address of its first pixel, its store's row pitch and byte order, so the launch needs no table of
+// stores - one (af_face_quality_u8) or several (af_face_quality_stores_u8); 64 x 32 bytes + the header stay far under the 4 KB of
+// arguments.
 struct QualityStoreRect {
     const unsigned char* first;
     int32_t pitch, w, h;
@@ -186,111 +171,67 @@ __device__ __forceinline__ void quality_tile(const unsigned char* src, long long
     }
 }
 
-__global__ __launch_bounds__(256) void face_quality_kernel(const QualityArgs a) {
-    const int tile = blockIdx.x;
-    if (tile >= a.total_tiles) return;
-    int k = 0;
-    while (k + 1 < a.n && a.r[k + 1].first_tile <= tile) ++k;     // tens of rectangles: a scan
-    const QualityRect r = a.r[k];
-    const unsigned char* src = a.store + (long long)r.frame * a.frame_stride + (long long)r.y0 * a.row_pitch + (long long)r.x0 * 3;
-    quality_tile(src, a.row_pitch, r.w, r.h, tile - r.first_tile, a.bgr, a.sums + k, a.grey ? a.grey + r.grey_offset : nullptr);
-}
-
 __global__ __launch_bounds__(256) void face_quality_stores_kernel(const QualityStoresArgs a) {
     const int tile = blockIdx.x;
     if (tile >= a.total_tiles) return;
     int k = 0;
-    while (k + 1 < a.n && a.r[k + 1].first_tile <= tile) ++k;
+    while (k + 1 < a.n && a.r[k + 1].first_tile <= tile) ++k;     // tens of rectangles: a scan
     const QualityStoreRect r = a.r[k];
     quality_tile(r.first, r.pitch, r.w, r.h, tile - r.first_tile, r.bgr, a.sums + k, a.grey ? a.grey + r.grey_offset : nullptr);
 }
 
-}  // namespace af
-
-extern "C" int af_face_quality_u8(const void* store, const af_frame_store* desc, const af_frame_rect* rects, int n, int bgr,
-                                  af_quality_sums* sums, void* grey, int64_t grey_bytes, void* stream) {
-    using namespace af;
-    AF_REQUIRE(store && desc && rects && sums, "face_quality: null argument");
-    AF_REQUIRE(n >= 0 && n <= AF_QUALITY_MAX_RECTS, "face_quality: %d rectangles (at most %d per launch)", n, AF_QUALITY_MAX_RECTS);
-    if (n == 0) return AF_OK;
-    const af_frame_store& s = *desc;
-    AF_REQUIRE(s.n_frames > 0 && s.height > 0 && s.width > 0 && s.height <= 32767 && s.width <= 32767, "face_quality: store of %d frames %dx%d",
-               s.n_frames, s.width, s.height);
-    const int64_t frame_span = (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3;
-    AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span,
-               "face_quality: row pitch %lld, frame stride %lld for frames of %dx%d", (long long)s.row_pitch, (long long)s.frame_stride, s.width, s.height);
-    AF_REQUIRE(s.store_bytes >= (int64_t)(s.n_frames - 1) * s.frame_stride + frame_span, "face_quality: %d frames do not fit a store of %lld bytes",
-               s.n_frames, (long long)s.store_bytes);
-    QualityArgs a;
-    a.store = (const unsigned char*)store; a.sums = sums; a.grey = (unsigned char*)grey;
-    a.frame_stride = s.frame_stride; a.row_pitch = s.row_pitch; a.n = n; a.bgr = bgr ? 1 : 0; a.reserved = 0;
-    int64_t tiles = 0, grey_total = 0;
-    for (int i = 0; i < n; ++i) {
-        const af_frame_rect& r = rects[i];
-        AF_REQUIRE(r.frame >= 0 && r.frame < s.n_frames && r.ih > 0 && r.iw > 0 && r.rx >= 0 && r.ry >= 0 &&
-                   (int64_t)r.rx + r.iw <= s.width && (int64_t)r.ry + r.ih <= s.height,
-                   "face_quality: rectangle %d: %dx%d at (%d,%d) of frame %d leaves the %d frames of %dx%d", i, r.iw, r.ih, r.rx, r.ry, r.frame,
-                   s.n_frames, s.width, s.height);
-        const int dw = r.iw / 2 > 1 ? r.iw / 2 : 1, dh = r.ih / 2 > 1 ? r.ih / 2 : 1;
-        a.r[i] = QualityRect{r.frame, r.rx, r.ry, r.iw, r.ih, (int32_t)tiles, (int32_t)grey_total, 0};
-        tiles += (int64_t)((dw + Q_TW - 1) / Q_TW) * ((dh + Q_TH - 1) / Q_TH);
-        grey_total += (int64_t)dw * dh;
-        AF_REQUIRE(tiles <= 0x7fffffff && grey_total <= 0x7fffffff, "face_quality: too many pixels");
-    }
-    AF_REQUIRE(!grey || grey_bytes >= grey_total, "face_quality: grey image buffer of %lld bytes, %lld needed", (long long)grey_bytes, (long long)grey_total);
-    a.total_tiles = (int)tiles;
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(af_quality_sums) * (size_t)n, (hipStream_t)stream);
-    if (e != hipSuccess) return set_error(AF_ERR_LAUNCH, "face_quality: hipMemsetAsync: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(face_quality_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
-    AF_CHECK_LAUNCH("face_quality_kernel");
-    return AF_OK;
-}
-
-extern "C" int af_face_quality_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
-                                         void* grey, int64_t grey_bytes, void* stream) {
-    using namespace af;
-    AF_REQUIRE(stores && rects && sums, "face_quality_stores: null argument");
-    AF_REQUIRE(n >= 0 && n <= AF_QUALITY_MAX_RECTS, "face_quality_stores: %d rectangles (at most %d per launch)", n, AF_QUALITY_MAX_RECTS);
-    AF_REQUIRE(n_stores > 0 && n_stores <= AF_MAX_STORES, "face_quality_stores: %d stores (1 to %d per launch)", n_stores, AF_MAX_STORES);
+// The host side of both entry points: the stores and the rectangles checked, one memset and one launch.  `listed`: a rectangle
+// names its store in af_frame_rect.reserved; otherwise every rectangle is of the one store and reserved is not read.
+static int face_quality(const char* who, const af_store_ref* stores, int n_stores, bool listed, const af_frame_rect* rects, int n,
+                        af_quality_sums* sums, void* grey, int64_t grey_bytes, void* stream) {
+    AF_REQUIRE(stores && rects && sums, "%s: null argument", who);
+    AF_REQUIRE(n >= 0 && n <= AF_QUALITY_MAX_RECTS, "%s: %d rectangles (at most %d per launch)", who, n, AF_QUALITY_MAX_RECTS);
+    AF_REQUIRE(n_stores > 0 && n_stores <= AF_MAX_STORES, "%s: %d stores (1 to %d per launch)", who, n_stores, AF_MAX_STORES);
     if (n == 0) return AF_OK;
     for (int i = 0; i < n_stores; ++i) {
-        const af_frame_store& s = stores[i].desc;
-        AF_REQUIRE(stores[i].base, "face_quality_stores: store %d: null base pointer", i);
-        AF_REQUIRE(s.n_frames > 0 && s.height > 0 && s.width > 0 && s.height <= 32767 && s.width <= 32767,
-                   "face_quality_stores: store %d of %d frames %dx%d", i, s.n_frames, s.width, s.height);
-        const int64_t frame_span = (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3;
-        AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span,
-                   "face_quality_stores: store %d: row pitch %lld, frame stride %lld for frames of %dx%d", i, (long long)s.row_pitch,
-                   (long long)s.frame_stride, s.width, s.height);
-        AF_REQUIRE(s.store_bytes >= (int64_t)(s.n_frames - 1) * s.frame_stride + frame_span,
-                   "face_quality_stores: store %d: %d frames do not fit a store of %lld bytes", i, s.n_frames, (long long)s.store_bytes);
+        AF_REQUIRE(stores[i].base, "%s: store %d: null base pointer", who, i);
+        const int rc = check_frame_store(who, listed ? i : -1, stores[i].desc);
+        if (rc != AF_OK) return rc;
     }
     QualityStoresArgs a;
     a.sums = sums; a.grey = (unsigned char*)grey; a.n = n;
     int64_t tiles = 0, grey_total = 0;
     for (int i = 0; i < n; ++i) {
         const af_frame_rect& r = rects[i];
-        AF_REQUIRE(r.reserved >= 0 && r.reserved < n_stores, "face_quality_stores: rectangle %d names store %d of %d", i, r.reserved, n_stores);
-        const af_store_ref& st = stores[r.reserved];
-        const af_frame_store& s = st.desc;
-        AF_REQUIRE(r.frame >= 0 && r.frame < s.n_frames && r.ih > 0 && r.iw > 0 && r.rx >= 0 && r.ry >= 0 &&
-                   (int64_t)r.rx + r.iw <= s.width && (int64_t)r.ry + r.ih <= s.height,
-                   "face_quality_stores: rectangle %d: %dx%d at (%d,%d) of frame %d leaves the %d frames of %dx%d of store %d", i, r.iw, r.ih, r.rx,
-                   r.ry, r.frame, s.n_frames, s.width, s.height, r.reserved);
+        const int store = listed ? r.reserved : 0;
+        AF_REQUIRE(store >= 0 && store < n_stores, "%s: rectangle %d names store %d of %d", who, i, store, n_stores);
+        const af_store_ref& st = stores[store];
+        int64_t offset = 0;
+        if (const int fault = frame_rect_fault(st.desc, r, 0, &offset)) {
+            char item[32];
+            snprintf(item, sizeof item, "rectangle %d", i);
+            return refuse_frame_rect(who, item, listed ? store : -1, st.desc, r, fault);
+        }
         const int dw = r.iw / 2 > 1 ? r.iw / 2 : 1, dh = r.ih / 2 > 1 ? r.ih / 2 : 1;
-        const int64_t offset = (int64_t)r.frame * s.frame_stride + (int64_t)r.ry * s.row_pitch + (int64_t)r.rx * 3;
-        a.r[i] = QualityStoreRect{(const unsigned char*)st.base + offset, (int32_t)s.row_pitch, r.iw, r.ih, (int32_t)tiles, (int32_t)grey_total,
+        a.r[i] = QualityStoreRect{(const unsigned char*)st.base + offset, (int32_t)st.desc.row_pitch, r.iw, r.ih, (int32_t)tiles, (int32_t)grey_total,
                                   st.bgr ? 1 : 0};
         tiles += (int64_t)((dw + Q_TW - 1) / Q_TW) * ((dh + Q_TH - 1) / Q_TH);
         grey_total += (int64_t)dw * dh;
-        AF_REQUIRE(tiles <= 0x7fffffff && grey_total <= 0x7fffffff, "face_quality_stores: too many pixels");
+        AF_REQUIRE(tiles <= 0x7fffffff && grey_total <= 0x7fffffff, "%s: too many pixels", who);
     }
-    AF_REQUIRE(!grey || grey_bytes >= grey_total, "face_quality_stores: grey image buffer of %lld bytes, %lld needed", (long long)grey_bytes,
-               (long long)grey_total);
+    AF_REQUIRE(!grey || grey_bytes >= grey_total, "%s: grey image buffer of %lld bytes, %lld needed", who, (long long)grey_bytes, (long long)grey_total);
     a.total_tiles = (int)tiles;
     hipError_t e = hipMemsetAsync(sums, 0, sizeof(af_quality_sums) * (size_t)n, (hipStream_t)stream);
-    if (e != hipSuccess) return set_error(AF_ERR_LAUNCH, "face_quality_stores: hipMemsetAsync: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return set_error(AF_ERR_LAUNCH, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
     hipLaunchKernelGGL(face_quality_stores_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
     AF_CHECK_LAUNCH("face_quality_stores_kernel");
     return AF_OK;
+}
+
+}  // namespace af
+
+extern "C" int af_face_quality_u8(const void* store, const af_frame_store* desc, const af_frame_rect* rects, int n, int bgr,
+                                  af_quality_sums* sums, void* grey, int64_t grey_bytes, void* stream) {
+    const af_store_ref one{store, desc ? *desc : af_frame_store{}, bgr, 0};
+    return af::face_quality("face_quality", store && desc ? &one : nullptr, 1, false, rects, n, sums, grey, grey_bytes, stream);
+}
+
+extern "C" int af_face_quality_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
+                                         void* grey, int64_t grey_bytes, void* stream) {
+    return af::face_quality("face_quality_stores", stores, n_stores, true, rects, n, sums, grey, grey_bytes, stream);
 }

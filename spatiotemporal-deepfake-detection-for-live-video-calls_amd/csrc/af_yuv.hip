@@ -221,11 +221,9 @@ extern "C" int af_yuv420_plan_u8(const af_yuv_frame* frames, int n, const af_sto
         AF_REQUIRE(st.base, "yuv420_plan: store %d: null base pointer", f.store);
         AF_REQUIRE(s.n_frames > 0 && s.height == f.h && s.width == f.w, "yuv420_plan: frame %d of %dx%d does not fit store %d of %d frames of %dx%d", i,
                    f.w, f.h, f.store, s.n_frames, s.width, s.height);
-        const int64_t frame_span = (int64_t)(s.height - 1) * s.row_pitch + (int64_t)s.width * 3;
-        AF_REQUIRE(s.row_pitch >= (int64_t)s.width * 3 && s.row_pitch <= 0x7fffffff && s.frame_stride >= frame_span,
-                   "yuv420_plan: store %d: row pitch %lld, frame stride %lld for frames of %dx%d", f.store, (long long)s.row_pitch,
-                   (long long)s.frame_stride, s.width, s.height);
-        AF_REQUIRE(f.slot >= 0 && f.slot < s.n_frames && (int64_t)f.slot * s.frame_stride + frame_span <= s.store_bytes,
+        const int rc = check_frame_store("yuv420_plan", f.store, s, false);     // one slot is written: its own bytes are checked next
+        if (rc != AF_OK) return rc;
+        AF_REQUIRE(f.slot >= 0 && f.slot < s.n_frames && (int64_t)f.slot * s.frame_stride + frame_span(s) <= s.store_bytes,
                    "yuv420_plan: frame %d: slot %d leaves store %d of %d frames, %lld bytes", i, f.slot, f.store, s.n_frames, (long long)s.store_bytes);
         af_yuv_item& it = items[i];
         it.y = f.y; it.c0 = f.u; it.c1 = f.interleaved ? nullptr : f.v;

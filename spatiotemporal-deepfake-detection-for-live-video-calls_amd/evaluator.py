@@ -31,7 +31,7 @@ import torch
 
 from ._staging import _COPY_THREADS, _SPLIT_BYTES, PinnedRing, _pool, crop_rect, cuda_device, is_crop, packed_rgb, stage_rects
 from .aligner import STD_POINTS_256, canvas_misfit, fit_window
-from .frames import YuvConverter, YuvFrame
+from .frames import YuvConverter, YuvFrame, StoreTable
 
 _FRAME_DTYPE = np.dtype([("offset", "<i8"), ("ih", "<i4"), ("iw", "<i4"), ("x", "<i4"), ("y", "<i4")])       # af_align_frame
 _RECT_DTYPE = np.dtype([(n, "<i4") for n in ("frame", "rx", "ry", "ih", "iw", "x", "y", "reserved")])            # af_frame_rect
@@ -264,6 +264,7 @@ class _WarpForm(NamedTuple):
 POOL = _WarpForm(_FRAME_DTYPE, ("offset",), "af_window_batch_table_bytes", "af_window_batch_plan_u8", "af_warp_affine_windows_u8")
 RECTS = _WarpForm(_RECT_DTYPE, ("frame", "rx", "ry"), "af_window_rects_table_bytes", "af_window_rects_plan_u8", "af_warp_affine_window_rects_u8")
 RECTS_BGR = RECTS._replace(launch="af_warp_affine_window_rects_bgr_u8")     # the same rectangles of frames whose bytes are B, G, R
+STORES = RECTS._replace(plan="af_window_rects_plan_stores_u8", launch="af_warp_affine_window_stores_u8")      # ... of several stores
 
 
 def partition(n_windows: int, batch: int):
@@ -460,48 +461,88 @@ class WindowWarp:
     """One form of the window-batch warp over the device pixels of `source`: fills the planner's records for a batch of windows,
     has the planner write the batch's table into a slot of its ring of tables, sends the table and launches."""
 
-    def __init__(self, form: _WarpForm, source: _Resident, clip_size: int = 32, size: int = 224, batch: int = 16):
+    def __init__(self, form: _WarpForm, source: Optional[_Resident], clip_size: int = 32, size: int = 224, batch: int = 16, device=None):
         from . import _lib                                        # fails loudly when libafhip.so is missing
-        self.form, self.source = form, source
+        self.form, self.source, self.device = form, source, source.device if device is None else device
         self.clip_size, self.size, self.batch = int(clip_size), int(size), int(batch)
         if not (1 <= self.batch <= _lib.WINDOW_MAX_BATCH and 1 <= self.clip_size <= _lib.ALIGN_MAX_FRAMES):
             raise ValueError("evaluator: batch 1..%d, clip_size 1..%d" % (_lib.WINDOW_MAX_BATCH, _lib.ALIGN_MAX_FRAMES))
         if self.size % 4 or not 0 < self.size <= _lib.WINDOW_MAX_SIZE:
             raise ValueError("evaluator: size must be a multiple of 4, at most %d" % _lib.WINDOW_MAX_SIZE)
-        self._table_bytes, self._plan, self._launch = (getattr(_lib.lib, name) for name in (form.table_bytes, form.plan, form.launch))
+        self._table_bytes, self._plan_fn, self._launch = (getattr(_lib.lib, name) for name in (form.table_bytes, form.plan, form.launch))
         self.table_bytes = int(self._table_bytes(self.batch, self.clip_size))
         self.tables = PinnedRing(min_bytes=self.table_bytes)      # three slots: the host runs up to two batches ahead of the device
+
+    def _records(self, n: int):
+        return np.zeros(n, dtype=_WINDOW_DTYPE), np.zeros((n, self.clip_size), dtype=self.form.item)
+
+    @staticmethod
+    def _fill(desc, items, w: int, fit, ih, iw):
+        """what every form's records of window `w` hold: the transform, the canvas, the crops' sizes and paste offsets"""
+        tfm, h, wd, diff = fit
+        desc[w] = (np.asarray(tfm, dtype=np.float64).reshape(6), h, wd)
+        items["ih"][w], items["iw"][w] = ih, iw
+        items["x"][w], items["y"][w] = diff[:, 0], diff[:, 1]
 
     def __call__(self, track, windows, offs: np.ndarray, first_frame: int, out: torch.Tensor, fits):
         """windows (index lists into the track, whose frame j sits at ``offs[j - first_frame]`` of the source) with their `fits`
         -> table -> pinned slot -> device; one launch into `out`"""
-        from . import _lib
-        n, src = len(windows), self.source
-        desc = np.zeros(n, dtype=_WINDOW_DTYPE)
-        items = np.zeros((n, self.clip_size), dtype=self.form.item)
-        for w, (idx, (tfm, h, wd, diff)) in enumerate(zip(windows, fits)):
-            desc[w] = (np.asarray(tfm, dtype=np.float64).reshape(6), h, wd)
+        desc, items = self._records(len(windows))
+        for w, (idx, fit) in enumerate(zip(windows, fits)):
             ii = np.asarray(idx)
+            self._fill(desc, items, w, fit, track.ih[ii], track.iw[ii])
             for name, values in zip(self.form.source, track.source(ii, offs[ii - first_frame])):
                 items[name][w] = values
-            items["ih"][w], items["iw"][w] = track.ih[ii], track.iw[ii]
-            items["x"][w], items["y"][w] = diff[:, 0], diff[:, 1]
-        slot = self.tables.acquire(self.table_bytes, src.device)
+        self._send(desc, items, (self.source.plan_source(),), (C.c_void_p(self.source.dev.data_ptr()),), out)
+
+    def _plan(self, desc, items, where: tuple, table: int):
+        """the filled records -> the batch's table at host address `table` (host only).  The planner names the (window, frame) it
+        refuses, whatever its reason: the aligner's canvas-misfit ``ValueError`` only if that one really misfits its canvas."""
+        from . import _lib
         bad_w, bad_f = C.c_int32(-1), C.c_int32(-1)
-        rc = self._plan(desc.ctypes.data, items.ctypes.data, n, self.clip_size, self.size, src.plan_source(), slot.host.data_ptr(),
-                        self.table_bytes, C.byref(bad_w), C.byref(bad_f))
+        rc = self._plan_fn(desc.ctypes.data, items.ctypes.data, len(desc), self.clip_size, self.size, *where, table, self.table_bytes,
+                           C.byref(bad_w), C.byref(bad_f))
         if rc != 0 and bad_w.value >= 0:
             f, d = items[bad_w.value, bad_f.value], desc[bad_w.value]
-            canvas_misfit(bad_f.value, f["iw"], f["ih"], f["x"], f["y"], d["canvas_w"], d["canvas_h"], window=bad_w.value)
+            if f["x"] < 0 or f["y"] < 0 or f["x"] + f["iw"] > d["canvas_w"] or f["y"] + f["ih"] > d["canvas_h"]:
+                canvas_misfit(bad_f.value, f["iw"], f["ih"], f["x"], f["y"], d["canvas_w"], d["canvas_h"], window=bad_w.value)
         _lib.check(rc, self.form.plan[3:])
-        used = int(self._table_bytes(n, self.clip_size))
+
+    def _send(self, desc, items, where: tuple, pixels: tuple, out: torch.Tensor):
+        """everything behind the filled records, for every form: table slot, plan, copy, launch.  `where` / `pixels`: what the
+        form's planner takes for the place of the pixels, and what its launch takes in front of the table"""
+        from . import _lib
+        slot = self.tables.acquire(self.table_bytes, self.device)
+        self._plan(desc, items, where, slot.host.data_ptr())
+        used = int(self._table_bytes(len(desc), self.clip_size))
         slot.dev[:used].copy_(slot.host[:used], non_blocking=True)
         # behind the copy, not the launch: the host rewrites only the pinned table; its twin is next written by the copy of three
         # batches later, which the stream orders behind this launch
         slot.record()
-        stream = C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
-        _lib.check(self._launch(C.c_void_p(src.dev.data_ptr()), C.c_void_p(slot.dev.data_ptr()), n, self.clip_size, self.size,
-                                C.c_void_p(out.data_ptr()), stream), self.form.launch[3:])
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._launch(*pixels, C.c_void_p(slot.dev.data_ptr()), len(desc), self.clip_size, self.size, C.c_void_p(out.data_ptr()), stream),
+                   self.form.launch[3:])
+
+
+class StoresWarp(WindowWarp):
+    """the window-batch warp out of several frame stores (``af_window_rects_plan_stores_u8`` /
+    ``af_warp_affine_window_stores_u8``): ``warp(windows, out)`` with ``windows = [(store, channel_order, slots, track, fit)]`` -
+    ``track`` a ``_FrameTrack`` of the window's ``clip_size`` frames, which sit in ``slots`` of ``store`` - plans one table, sends
+    it through a ring of pinned slots and launches once.  ``launches`` counts the launches."""
+
+    def __init__(self, device, clip_size: int, size: int, batch: int):
+        super().__init__(STORES, None, clip_size, size, batch, device)
+        self.launches = 0
+
+    def __call__(self, windows, out: torch.Tensor):
+        desc, items = self._records(len(windows))
+        table = StoreTable()
+        for w, (store, order, slots, track, fit) in enumerate(windows):
+            self._fill(desc, items, w, fit, track.ih, track.iw)
+            items["frame"][w], items["rx"][w], items["ry"][w], items["reserved"][w] = slots, track.rx, track.ry, table.index(store, order)
+        with torch.cuda.device(self.device):
+            self._send(desc, items, (table.array(), len(table.refs)), (), out)
+        self.launches += 1
 
 
 class _WindowScorer:

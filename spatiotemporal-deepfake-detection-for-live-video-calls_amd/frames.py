@@ -144,6 +144,25 @@ def store_ref(store, channel_order: str):
                          int(channel_order == "bgr"), 0)
 
 
+class StoreTable:
+    """the stores of one launch: ``index(store, channel_order)`` -> the pair's index in this launch; ``refs``: the ``af_store_ref``s
+    in order of first use.  Asked once per item, inside the loop that fills the items."""
+
+    def __init__(self):
+        self._at, self.refs = {}, []
+
+    def index(self, store, order: str) -> int:
+        at = self._at.get((id(store), order))
+        if at is None:
+            at = self._at[(id(store), order)] = len(self.refs)
+            self.refs.append(store_ref(store, order))
+        return at
+
+    def array(self):
+        from . import _lib
+        return (_lib.StoreRef * len(self.refs))(*self.refs)
+
+
 def _address(p) -> int:
     return p.__array_interface__["data"][0] if isinstance(p, np.ndarray) else p.data_ptr()
 
@@ -234,10 +253,8 @@ class YuvConverter:
                 raise ValueError("yuv: a frame of %s for a store of %s" % (f.shape, tuple(store.shape)))
             if f.on_device and f.device != store.device:
                 raise ValueError("yuv: the planes are on %s, the frame store on %s" % (f.device, store.device))
-        refs = {}
-        for _, store, order, _ in jobs:
-            if (id(store), order) not in refs:
-                refs[(id(store), order)] = store_ref(store, order)
+        table = StoreTable()
+        refs = [table.refs[table.index(j[1], j[2])] for j in jobs]
         with torch.cuda.device(self.device):
             offs, used = staged_offsets(frames)
             slot, dev_base = None, 0
@@ -251,7 +268,7 @@ class YuvConverter:
             for lo in range(0, len(jobs), _lib.YUV_MAX_FRAMES):
                 part = jobs[lo:lo + _lib.YUV_MAX_FRAMES]
                 items = self.table([j[0] for j in part], [None if o < 0 else dev_base + o for o in offs[lo:lo + len(part)]],
-                                   [refs[(id(j[1]), j[2])] for j in part], [j[3] for j in part])
+                                   refs[lo:lo + len(part)], [j[3] for j in part])
                 _lib.check(self._launch(C.byref(items), len(part), stream), "yuv420_to_rgb_u8")
                 self.launches += 1
             if slot is not None:

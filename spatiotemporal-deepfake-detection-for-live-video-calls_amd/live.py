@@ -24,19 +24,64 @@ import numpy as np
 import torch
 
 from ._staging import is_crop
-from .frames import YuvConverter, YuvFrame, store_ref, upload_bytes
+from .frames import YuvConverter, YuvFrame, StoreTable, upload_bytes
 from .aligner import STD_POINTS_256
-from .evaluator import RECTS, RECTS_BGR, FrameStore, WindowWarp, _clip_buffers, _fit, _FrameTrack, _network_device, _padded, get_crop_box, partition
+from .evaluator import (RECTS, RECTS_BGR, FrameStore, StoresWarp, WindowWarp, _clip_buffers, _fit, _FrameTrack, _network_device, _padded, get_crop_box,
+                        partition)
 from .tracker import ByteTracker, STrack, iou_distance
 
 _FORMS = {"rgb": RECTS, "bgr": RECTS_BGR}
 
 
+def _known_order(channel_order: str) -> str:
+    if channel_order not in _FORMS:
+        raise ValueError("live: channel_order 'bgr' or 'rgb', not %r" % (channel_order,))
+    return channel_order
+
+
+class _ClosedWindows:
+    """The scoring loop of the windows that closed on a step, a call's own or a server's: ``max_batch`` clips - the static input
+    of the replayed forwards -, the ``LiveScorer`` per batch size on the front of them (``scorers``, made on first use) and the
+    pinned score buffer."""
+
+    def __init__(self, network, clip_size: int, size: int, max_batch: int, device):
+        self.network, self.clip_size, self.size, self.max_batch, self.device = network, clip_size, size, max_batch, device
+        self.clip = _clip_buffers(1, max_batch, clip_size, size, device)[0]
+        self.scorers = {}
+        self._host = None
+
+    def scorer(self, run: int):
+        from .classifier import LiveScorer
+        if run not in self.scorers:
+            self.scorers[run] = LiveScorer(self.network, self.clip_size, self.size, batch=run, clip=self.clip[:run])
+        return self.scorers[run]
+
+    def __call__(self, n_windows: int, warp, before_wait=None, count=lambda key: None) -> np.ndarray:
+        """the scores of `n_windows` windows, float32: per ``max_batch`` of them ``warp(first, n, run, clip)`` - which warps windows
+        [first, first + n), the last one repeated up to `run`, into `clip` - and one replay; one read-back and one wait, in
+        front of which ``before_wait(stream)`` is called.  ``count``: ``ServerStats.count``."""
+        cur, parts = torch.cuda.current_stream(self.device), []
+        for first, n, run in partition(n_windows, self.max_batch):
+            scorer = self.scorer(run)
+            warp(first, n, run, scorer.clip)
+            count("warp")
+            parts.append(scorer.replay()[:n].to(torch.float32, copy=True))         # the next replay of this size overwrites its scores
+            count("replay")
+        if self._host is None or self._host.numel() < n_windows:
+            self._host = torch.empty(max(64, n_windows), dtype=torch.float32, pin_memory=True)
+        self._host[:n_windows].copy_(parts[0] if len(parts) == 1 else torch.cat(parts), non_blocking=True)
+        if before_wait is not None:
+            before_wait(cur)
+        cur.synchronize()
+        count("wait")
+        return self._host[:n_windows].numpy().copy()
+
+
 class _DeviceSide(NamedTuple):
     """what a call keeps on the device for one frame size"""
-    store: FrameStore             # the last ``ring_frames`` frames, used as a ring
-    warp: WindowWarp              # the warp of the call's channel order out of it,
-    clip: torch.Tensor            # into this: ``max_batch`` clips, the static input of the replayed forwards
+    store: FrameStore                        # the last ``ring_frames`` frames, used as a ring
+    warp: Optional[WindowWarp]               # the warp of the call's channel order out of it,
+    scoring: Optional[_ClosedWindows]        # into the clip buffer of this (a served call has neither: its server has them)
 
 
 class _TrackState:
@@ -92,9 +137,7 @@ class LiveCall:
         self.clip_size, self.size, self.stride = int(clip_size), int(size), int(stride)
         self.crop_scale, self.ring_frames = float(crop_scale), int(ring_frames)
         self.max_batch, self.drop_after = int(max_batch), int(drop_after)
-        if channel_order not in _FORMS:
-            raise ValueError("live: channel_order 'bgr' or 'rgb', not %r" % (channel_order,))
-        self.channel_order = channel_order
+        self.channel_order = _known_order(channel_order)
         if self.clip_size < 1 or self.stride < 1 or self.drop_after < 1:
             raise ValueError("live: clip_size, stride and drop_after are at least 1")
         if self.ring_frames < self.clip_size + self.drop_after:
@@ -107,9 +150,10 @@ class LiveCall:
         self._shape = None
         self._first = 0                    # the oldest frame index the ring may hold (moved by a re-open)
         self._ring: Optional[_DeviceSide] = None     # for the current frame size
-        self._scorers = {}                 # clips per forward -> LiveScorer on the front of the ring's clip buffer
         self._done = None                  # recorded behind the last launch of every step
-        self._host = None
+
+    # clips per forward -> LiveScorer on the front of the ring's clip buffer
+    _scorers = property(lambda self: self._ring.scoring.scorers if self._ring is not None and self._ring.scoring is not None else {})
 
     # -- the host side: af_realtime.py:401-505 ---------------------------------------------------------
     def step(self, frame: np.ndarray, faces: Sequence[Tuple], alive: Sequence = ()) -> List[Tuple]:
@@ -148,7 +192,7 @@ class LiveCall:
         """the books of ``advance`` without the scoring: returns the windows that closed on this frame, ``[(tid, [(frame index,
         record)] * clip_size)]``.  ``advance`` scores them itself; ``CallServer`` scores the windows of many calls together."""
         H, W = self._shape[:2]
-        oldest = max(self._first, self.frame_idx - self.ring_frames + 1)
+        oldest = self._oldest()
         alive, ready = set(alive), []
         for tid in alive:                                                              # :409-411
             if tid not in self._tracks:
@@ -193,17 +237,20 @@ class LiveCall:
         """the device (H, W, 3) uint8 view of frame ``k`` (``call.frame_idx`` is the last one), in the channel order it was captured
         in; valid on the stream ``step`` was called on until ``ring_frames`` more frames have arrived"""
         k = int(k)
-        if self._ring is None or not max(self._first, self.frame_idx - self.ring_frames + 1) <= k <= self.frame_idx:
-            raise ValueError("live: frame %d is not resident (frames %d .. %d are)"
-                             % (k, max(self._first, self.frame_idx - self.ring_frames + 1), self.frame_idx))
+        if self._ring is None or not self._oldest() <= k <= self.frame_idx:
+            raise ValueError("live: frame %d is not resident (frames %d .. %d are)" % (k, self._oldest(), self.frame_idx))
         return self._ring.store.view(k % self.ring_frames)
+
+    def _oldest(self) -> int:
+        """the oldest frame index the ring still holds"""
+        return max(self._first, self.frame_idx - self.ring_frames + 1)
 
     # -- the device side ---------------------------------------------------------------------------------
     def _open_ring(self, shape):
         """a ring for frames of `shape`; the entries of all tracks name frames of the old one and are dropped"""
         if self._ring is not None:
             torch.cuda.synchronize(self._ring.store.device)                            # nothing still reads the old ring or clip buffer
-        self._ring, self._scorers = None, {}
+        self._ring = None                                                              # the old buffers go before the new ones come
         self._ring = self._new_ring(shape)
         self._shape, self._first = tuple(shape), self.frame_idx
         for tr in self._tracks.values():
@@ -215,7 +262,7 @@ class LiveCall:
             store = FrameStore(dev, self.channel_order)
             store.open(shape, self.ring_frames)
             warp = WindowWarp(_FORMS[self.channel_order], store, self.clip_size, self.size, self.max_batch)
-            return _DeviceSide(store, warp, _clip_buffers(1, self.max_batch, self.clip_size, self.size, dev)[0])
+            return _DeviceSide(store, warp, _ClosedWindows(self.network, self.clip_size, self.size, self.max_batch, dev))
 
     def _store_frame(self, frame: np.ndarray, slot: int):
         """host frame -> a pinned staging slot -> ring slot `slot`, asynchronous on the current stream"""
@@ -230,34 +277,20 @@ class LiveCall:
             self._done.record(cur)
         self.uploaded_bytes += upload_bytes(frame)
 
-    def _scorer(self, run: int):
-        from .classifier import LiveScorer
-        if run not in self._scorers:
-            self._scorers[run] = LiveScorer(self.network, self.clip_size, self.size, batch=run, clip=self._ring.clip[:run])
-        return self._scorers[run]
-
     def _score(self, ready) -> np.ndarray:
         """``ready``: ``[(tid, [(frame index, record)] * clip_size)]`` -> their scores, float32: one fit per window, one launch and
         one replay per ``max_batch`` windows, one read-back"""
-        ring, T = self._ring.store, self.clip_size
+        ring, T = self._ring, self.clip_size
         std_points = STD_POINTS_256 * self.size / 256.0
         entries = [e for _, win in ready for e in win]
         track = _FrameTrack([rec for _, rec in entries], [k % self.ring_frames for k, _ in entries], self._shape)
         windows = [list(range(w * T, (w + 1) * T)) for w in range(len(ready))]
-        with torch.cuda.device(ring.device):
-            cur = torch.cuda.current_stream(ring.device)
-            parts = []
-            for first, n, run in partition(len(windows), self.max_batch):
-                ids, fits = _padded(track, windows, first, n, run, std_points)
-                scorer = self._scorer(run)
-                self._ring.warp(track, [windows[k] for k in ids], track.frame, 0, scorer.clip, fits)
-                parts.append(scorer.replay()[:n].to(torch.float32, copy=True))     # the next replay of this size overwrites its scores
-            if self._host is None or self._host.numel() < len(windows):
-                self._host = torch.empty(max(64, len(windows)), dtype=torch.float32, pin_memory=True)
-            self._host[:len(windows)].copy_(parts[0] if len(parts) == 1 else torch.cat(parts), non_blocking=True)
-            self._done.record(cur)
-            cur.synchronize()
-        return self._host[:len(windows)].numpy().copy()
+
+        def warp(first, n, run, clip):
+            ids, fits = _padded(track, windows, first, n, run, std_points)
+            ring.warp(track, [windows[k] for k in ids], track.frame, 0, clip, fits)
+        with torch.cuda.device(ring.store.device):
+            return ring.scoring(len(windows), warp, before_wait=self._done.record)
 
 
 # ---- the quality gate: af_realtime.py:262-276 -------------------------------------------------------------------------------------
@@ -340,10 +373,8 @@ class FaceQuality(_QualitySums):
 
     def __init__(self, store: FrameStore, channel_order: str = "bgr"):
         from . import _lib                                        # fails loudly when libafhip.so is missing
-        if channel_order not in _FORMS:
-            raise ValueError("live: channel_order 'bgr' or 'rgb', not %r" % (channel_order,))
         super().__init__(store.device)
-        self.store, self.bgr = store, int(channel_order == "bgr")
+        self.store, self.bgr = store, int(_known_order(channel_order) == "bgr")
         self._fn = _lib.lib.af_face_quality_u8
 
     def sums(self, rects, grey: bool = False):
@@ -453,6 +484,39 @@ def track_gate(state: CallState, found, measured, gate):
     return faces, alive - {f[0] for f in faces}, kept_boxes, rects
 
 
+class _Detections:
+    """the read-back of a step's detector results: ``read([(rows, counts), ...])`` - device tensors, (B, N, 15) and (B,) - -> the
+    (n, 15) float32 numpy rows of every frame, in order.  The counts and the first 64 rows of every frame come back in one pinned
+    copy and one wait; one more copy and wait only for a frame with more rows.  ``count``: ``ServerStats.count``."""
+
+    def __init__(self):
+        self._host = None
+
+    def read(self, results, device, count=lambda key: None) -> List[np.ndarray]:
+        packed, places, at = [], [], 0
+        for rows, counts in results:                                                   # a result: its counts, then its first rows
+            b, first = rows.shape[0], min(64, rows.shape[1])
+            packed += [counts[:b].to(torch.float32), rows[:, :first].reshape(-1)]
+            places.append((rows, first, at))
+            at += b * (1 + first * 15)
+        if self._host is None or self._host.numel() < at:
+            self._host = torch.empty(max(at, 16 * (1 + 64 * 15)), dtype=torch.float32, pin_memory=True)
+        self._host[:at].copy_(torch.cat(packed), non_blocking=True)
+        torch.cuda.current_stream(device).synchronize()
+        count("wait")
+        host, out = self._host.numpy(), []
+        for rows, first, at in places:
+            for b in range(rows.shape[0]):
+                n = int(host[at + b])
+                if n > first:
+                    out.append(rows[b, :n].cpu().numpy())
+                    count("wait")
+                else:
+                    lo = at + rows.shape[0] + b * first * 15
+                    out.append(host[lo:lo + n * 15].reshape(n, 15).copy())
+        return out
+
+
 class RealtimeCall:
     """``RealtimeCall(network, detector).step(frame_bgr)`` -> ``[(tid, score), ...]``: the whole of ``RealtimeAF.step``
     (test/af_realtime.py:372-509) with the captured frame as its only input, by composition over ``LiveCall``.
@@ -501,7 +565,7 @@ class RealtimeCall:
         self.state, self.last_boxes = {}, {}
         self.detections = None                       # the rows the last detect frame handed the tracker's filter (N, 15) float32
         self._quality = self._quality_ring = None
-        self._rows_host = None
+        self._detections = _Detections()
 
     _ring_type = LiveCall
     frame_idx = property(lambda self: self.call.frame_idx)
@@ -509,20 +573,28 @@ class RealtimeCall:
     purged = property(lambda self: self.call.purged)
 
     def _detect(self, view) -> np.ndarray:
-        """the detector on the resident frame; counts and the first rows come back in one pinned copy (a second one only for more
-        than 64 faces)"""
+        """the detector on the resident frame and the one read-back of its rows"""
         rows, counts = self.detector.detect(view[None])
-        first = min(64, rows.shape[1])
         with torch.cuda.device(rows.device):
-            if self._rows_host is None or self._rows_host.numel() < 1 + first * 15:
-                self._rows_host = torch.empty(1 + first * 15, dtype=torch.float32, pin_memory=True)
-            packed = torch.cat([counts[:1].to(torch.float32), rows[0, :first].reshape(-1)])
-            self._rows_host[:packed.numel()].copy_(packed, non_blocking=True)
-            torch.cuda.current_stream(rows.device).synchronize()
-            n = int(self._rows_host[0].item())
-            if n > first:
-                return rows[0, :n].cpu().numpy()
-            return self._rows_host[1:1 + n * 15].numpy().reshape(n, 15).copy()
+            return self._detections.read([(rows, counts)], rows.device)[0]
+
+    def _track(self, k: int, shape, dets):
+        """:382-437 for frame `k`, whose detections are `dets` (None when the detector did not run on it): they are kept in
+        ``detections``, filtered into the tracker, and the tracks go through ``track_candidates``, whose result this returns"""
+        H, W = shape[:2]
+        tracks_in = []
+        if dets is not None:
+            self.detections = dets
+            for d in dets:                                                             # :382-386
+                d = np.asarray(d, dtype=np.float32)
+                if d[4] >= self.start_conf and max(d[2], d[3]) >= self.start_min_size:
+                    tracks_in.append(STrack(d[:4], score=float(d[4])))
+        online = self.tracker.update(tracks_in, (H, W), (H, W))                        # :388
+        return track_candidates(self.host, k, (H, W), dets, online, self.mesh_every, self.crop_scale, self.exclude_rect, self.landmarks,
+                                self.call.frame_view(k) if self.landmarks is not None else None)
+
+    def _weight(self, min_side: float, lap: float) -> float:
+        return quality_weight(min_side, lap, **self._gate)
 
     def _frame_quality(self, rects):
         ring = self.call._ring.store
@@ -534,20 +606,9 @@ class RealtimeCall:
     def step(self, frame: np.ndarray) -> List[Tuple]:
         call = self.call
         k = call.admit(frame)                                                          # :373-376, the one upload
-        H, W = frame.shape[:2]
-        dets = None
-        if k % max(1, self.detect_every) == 0:                                         # :378-380
-            dets = self.detections = self._detect(call.frame_view(k))
-        tracks_in = []
-        if dets is not None and len(dets) > 0:                                         # :382-386
-            for d in dets:
-                d = np.asarray(d, dtype=np.float32)
-                if d[4] >= self.start_conf and max(d[2], d[3]) >= self.start_min_size:
-                    tracks_in.append(STrack(d[:4], score=float(d[4])))
-        online = self.tracker.update(tracks_in, (H, W), (H, W))                        # :388
-        faces, alive, kept_boxes, _ = track_faces(
-            self.host, k, (H, W), dets, online, self._frame_quality, lambda m, l: quality_weight(m, l, **self._gate), self.mesh_every,
-            self.crop_scale, self.exclude_rect, self.landmarks, call.frame_view(k) if self.landmarks is not None else None)
+        dets = self._detect(call.frame_view(k)) if k % max(1, self.detect_every) == 0 else None      # :378-380
+        found = self._track(k, frame.shape, dets)
+        faces, alive, kept_boxes, _ = track_gate(self.host, found, self._frame_quality(found[0]) if found[0] else [], self._weight)
         results = call.advance(faces, alive)                                           # :445-499
         return self._after(results, kept_boxes)
 
@@ -619,9 +680,6 @@ class _ServedCall(RealtimeCall):
         raise RuntimeError("live: a served call is stepped by its CallServer (server.step({cid: frame}))")
 
 
-_store_ref = store_ref
-
-
 class StoresQuality(_QualitySums):
     """``FaceQuality`` over rectangles of several frame stores: ``rects = [(store, channel_order, slot, x0, y0, x1, y1)]`` in one
     launch of ``af_face_quality_stores_u8`` per 64 rectangles, whatever their stores, and one read-back"""
@@ -633,73 +691,15 @@ class StoresQuality(_QualitySums):
 
     def sums(self, rects, grey: bool = False):
         import ctypes as C
-        from . import _lib
         from .evaluator import _RECT_DTYPE
 
         def launch(lo, hi, sums, gptr, gn, stream):
-            index, refs = {}, []                                           # the stores of this launch, in order of first use
+            table = StoreTable()                                           # the stores of this launch
             items = np.zeros(hi - lo, dtype=_RECT_DTYPE)
             for i, (store, order, slot, x0, y0, x1, y1) in enumerate(rects[lo:hi]):
-                if id(store) not in index:
-                    index[id(store)] = len(refs)
-                    refs.append(_store_ref(store, order))
-                items[i] = (slot, x0, y0, y1 - y0, x1 - x0, 0, 0, index[id(store)])
-            return self._fn((_lib.StoreRef * len(refs))(*refs), len(refs), C.c_void_p(items.ctypes.data), hi - lo, sums, gptr, gn, stream)
+                items[i] = (slot, x0, y0, y1 - y0, x1 - x0, 0, 0, table.index(store, order))
+            return self._fn(table.array(), len(table.refs), C.c_void_p(items.ctypes.data), hi - lo, sums, gptr, gn, stream)
         return self._sums([(r[6] - r[4], r[5] - r[3]) for r in rects], grey, launch, "face_quality_stores_u8")
-
-
-class StoresWarp:
-    """the window-batch warp out of several frame stores (``af_window_rects_plan_stores_u8`` /
-    ``af_warp_affine_window_stores_u8``): ``warp(windows, out)`` with ``windows = [(store, channel_order, slots, track, fit)]`` -
-    ``track`` an ``evaluator._FrameTrack`` of the window's ``clip_size`` frames, which sit in ``slots`` of ``store`` - plans one
-    table, sends it through a ring of pinned slots and launches once.  ``launches`` counts the launches."""
-
-    def __init__(self, device, clip_size: int, size: int, batch: int):
-        from . import _lib                                        # fails loudly when libafhip.so is missing
-        from ._staging import PinnedRing
-        self.device, self.clip_size, self.size, self.batch, self.launches = device, int(clip_size), int(size), int(batch), 0
-        if not (1 <= self.batch <= _lib.WINDOW_MAX_BATCH and 1 <= self.clip_size <= _lib.ALIGN_MAX_FRAMES):
-            raise ValueError("live: max_batch 1..%d, clip_size 1..%d" % (_lib.WINDOW_MAX_BATCH, _lib.ALIGN_MAX_FRAMES))
-        if self.size % 4 or not 0 < self.size <= _lib.WINDOW_MAX_SIZE:
-            raise ValueError("live: size must be a multiple of 4, at most %d" % _lib.WINDOW_MAX_SIZE)
-        self.table_bytes = int(_lib.lib.af_window_rects_table_bytes(self.batch, self.clip_size))
-        self.tables = PinnedRing(min_bytes=self.table_bytes)
-
-    def __call__(self, windows, out: torch.Tensor):
-        import ctypes as C
-        from . import _lib
-        from .aligner import canvas_misfit
-        from .evaluator import _RECT_DTYPE, _WINDOW_DTYPE
-        n, T = len(windows), self.clip_size
-        desc = np.zeros(n, dtype=_WINDOW_DTYPE)
-        items = np.zeros((n, T), dtype=_RECT_DTYPE)
-        index, refs = {}, []
-        for w, (store, order, slots, track, (tfm, h, wd, diff)) in enumerate(windows):
-            if id(store) not in index:
-                index[id(store)] = len(refs)
-                refs.append(_store_ref(store, order))
-            desc[w] = (np.asarray(tfm, dtype=np.float64).reshape(6), h, wd)
-            items["frame"][w], items["rx"][w], items["ry"][w] = slots, track.rx, track.ry
-            items["ih"][w], items["iw"][w] = track.ih, track.iw
-            items["x"][w], items["y"][w] = diff[:, 0], diff[:, 1]
-            items["reserved"][w] = index[id(store)]
-        with torch.cuda.device(self.device):
-            slot = self.tables.acquire(self.table_bytes, self.device)
-            bad_w, bad_f = C.c_int32(-1), C.c_int32(-1)
-            rc = _lib.lib.af_window_rects_plan_stores_u8(desc.ctypes.data, items.ctypes.data, n, T, self.size, (_lib.StoreRef * len(refs))(*refs),
-                                                         len(refs), slot.host.data_ptr(), self.table_bytes, C.byref(bad_w), C.byref(bad_f))
-            if rc != 0 and bad_w.value >= 0:
-                f, d = items[bad_w.value, bad_f.value], desc[bad_w.value]
-                if f["x"] < 0 or f["y"] < 0 or f["x"] + f["iw"] > d["canvas_w"] or f["y"] + f["ih"] > d["canvas_h"]:
-                    canvas_misfit(bad_f.value, f["iw"], f["ih"], f["x"], f["y"], d["canvas_w"], d["canvas_h"], window=bad_w.value)
-            _lib.check(rc, "window_rects_plan_stores_u8")
-            used = int(_lib.lib.af_window_rects_table_bytes(n, T))
-            slot.dev[:used].copy_(slot.host[:used], non_blocking=True)
-            slot.record()                                           # behind the copy: the host rewrites only the pinned table
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(_lib.lib.af_warp_affine_window_stores_u8(C.c_void_p(slot.dev.data_ptr()), n, T, self.size, C.c_void_p(out.data_ptr()), stream),
-                       "warp_affine_window_stores_u8")
-            self.launches += 1
 
 
 class ServerStats:
@@ -774,10 +774,7 @@ class CallServer:
             detector = YuNet(modelPath, confThreshold=conf, nmsThreshold=0.3, topK=5000)
         self.detector = detector
         self.clip_size, self.size, self.max_batch = int(clip_size), int(size), int(max_batch)
-        for name in ("network", "detector", "modelPath", "clip_size", "size", "max_batch"):
-            if name in call_defaults:
-                raise TypeError("server: %s belongs to the server, not to a call" % name)
-        self.call_defaults = dict(call_defaults)
+        self.call_defaults = self._a_calls_own(call_defaults)
         self.device = _network_device(self.network)
         self.stats = ServerStats()
         self.uploaded_bytes = 0
@@ -786,19 +783,23 @@ class CallServer:
         self._quality = StoresQuality(self.device)
         self._warp = StoresWarp(self.device, self.clip_size, self.size, self.max_batch)
         self._yuv = YuvConverter(self.device)     # its own pinned ring: the YUV planes of all calls of a step share one slot
-        self._clip = None                  # ``max_batch`` clips, the static input of the replayed forwards
-        self._scorers = {}                 # clips per forward -> LiveScorer on the front of the clip buffer
+        self._scoring: Optional[_ClosedWindows] = None      # the clip buffer and the scorers, made when the first window closes
         self._done = None                  # recorded behind the last launch of every step
-        self._rows_host = self._scores_host = None
+        self._detections = _Detections()
+
+    _scorers = property(lambda self: self._scoring.scorers if self._scoring is not None else {})
+
+    @staticmethod
+    def _a_calls_own(keywords) -> dict:
+        for name in ("network", "detector", "modelPath", "clip_size", "size", "max_batch"):
+            if name in keywords:
+                raise TypeError("server: %s belongs to the server, not to a call" % name)
+        return dict(keywords)
 
     # -- calls ---------------------------------------------------------------------------------------------
     def open(self, **overrides) -> int:
         """a new call with the server's defaults and these ``RealtimeCall`` keywords; returns its id"""
-        for name in ("network", "detector", "modelPath", "clip_size", "size", "max_batch"):
-            if name in overrides:
-                raise TypeError("server: %s belongs to the server, not to a call" % name)
-        args = dict(self.call_defaults)
-        args.update(overrides)
+        args = dict(self.call_defaults, **CallServer._a_calls_own(overrides))
         cid, self._next = self._next, self._next + 1
         self._calls[cid] = _ServedCall(self.network, detector=self.detector, clip_size=self.clip_size, size=self.size,
                                        max_batch=self.max_batch, **args)
@@ -853,19 +854,7 @@ class CallServer:
         dets = dict(zip(detecting, self._detect([calls[i][1].call.frame_view(ticks[i]) for i in detecting])))      # 2.
         found, wanted = [], []
         for i, (cid, c, frame) in enumerate(calls):                                        # 3. trackers, candidates
-            H, W = frame.shape[:2]
-            d = dets.get(i)
-            if d is not None:
-                c.detections = d
-            tracks_in = []
-            if d is not None and len(d) > 0:
-                for row in d:
-                    row = np.asarray(row, dtype=np.float32)
-                    if row[4] >= c.start_conf and max(row[2], row[3]) >= c.start_min_size:
-                        tracks_in.append(STrack(row[:4], score=float(row[4])))
-            online = c.tracker.update(tracks_in, (H, W), (H, W))
-            f = track_candidates(c.host, ticks[i], (H, W), d, online, c.mesh_every, c.crop_scale, c.exclude_rect, c.landmarks,
-                                 c.call.frame_view(ticks[i]) if c.landmarks is not None else None)
+            f = c._track(ticks[i], frame.shape, dets.get(i))
             found.append(f)
             ring, slot = c.call._ring.store, ticks[i] % c.call.ring_frames
             wanted += [(ring, c.call.channel_order, slot) + tuple(r) for r in f[0]]
@@ -875,7 +864,7 @@ class CallServer:
         self.stats.count("wait", 1 if wanted else 0)
         ready, kept, at = [], [], 0
         for (cid, c, frame), f in zip(calls, found):                                       # 5. the books
-            faces, alive, kept_boxes, _ = track_gate(c.host, f, measured[at:at + len(f[0])], lambda m, l, g=c._gate: quality_weight(m, l, **g))
+            faces, alive, kept_boxes, _ = track_gate(c.host, f, measured[at:at + len(f[0])], c._weight)
             at += len(f[0])
             kept.append(kept_boxes)
             ready.append(c.call.advance_host(faces, alive))
@@ -888,69 +877,37 @@ class CallServer:
         return out
 
     def _detect(self, views) -> List[np.ndarray]:
-        """the rows of every view, in order: the views grouped by shape, one ``detect_views`` per 64 of a group, the counts and
-        the first 64 rows of every frame back in one pinned copy and one wait (one more only for a frame with more faces)"""
+        """the rows of every view, in order: the views grouped by shape, one ``detect_views`` per 64 of a group, and the one
+        read-back of all their rows (``_Detections``)"""
         if not views:
             return []
         from . import _lib
         groups = {}
         for i, v in enumerate(views):
             groups.setdefault(tuple(v.shape), []).append(i)
-        chunks, packed, at = [], [], 0
+        order, results = [], []
         for members in groups.values():
             for lo in range(0, len(members), _lib.YUNET_MAX_LIST):
                 chunk = members[lo:lo + _lib.YUNET_MAX_LIST]
-                rows, counts = self.detector.detect_views([views[i] for i in chunk])
+                results.append(self.detector.detect_views([views[i] for i in chunk]))
                 self.stats.count("detect")
-                first = min(64, rows.shape[1])
-                packed += [counts.to(torch.float32), rows[:, :first].reshape(-1)]
-                chunks.append((chunk, rows, first, at))
-                at += len(chunk) * (1 + first * 15)
-        if self._rows_host is None or self._rows_host.numel() < at:
-            self._rows_host = torch.empty(max(at, 16 * (1 + 64 * 15)), dtype=torch.float32, pin_memory=True)
-        self._rows_host[:at].copy_(torch.cat(packed), non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        self.stats.count("wait")
-        host, out = self._rows_host.numpy(), [None] * len(views)
-        for chunk, rows, first, at in chunks:                                              # a chunk: its counts, then its first rows
-            for b, i in enumerate(chunk):
-                n = int(host[at + b])
-                if n > first:
-                    out[i] = rows[b, :n].cpu().numpy()
-                    self.stats.count("wait")
-                else:
-                    lo = at + len(chunk) + b * first * 15
-                    out[i] = host[lo:lo + n * 15].reshape(n, 15).copy()
+                order += chunk
+        out = [None] * len(views)
+        for i, rows in zip(order, self._detections.read(results, self.device, self.stats.count)):
+            out[i] = rows
         return out
-
-    def _scorer(self, run: int):
-        from .classifier import LiveScorer
-        if self._clip is None:
-            self._clip = _clip_buffers(1, self.max_batch, self.clip_size, self.size, self.device)[0]
-        if run not in self._scorers:
-            self._scorers[run] = LiveScorer(self.network, self.clip_size, self.size, batch=run, clip=self._clip[:run])
-        return self._scorers[run]
 
     def _score(self, closed) -> np.ndarray:
         """``closed``: ``[(the call's ``_ServedRing``, [(frame index, record)] * clip_size)]`` in the server's order -> their scores, float32:
         one fit per window, one plan, one warp and one replay per ``max_batch`` windows, one read-back"""
         if not closed:
             return np.zeros(0, dtype=np.float32)
+        if self._scoring is None:
+            self._scoring = _ClosedWindows(self.network, self.clip_size, self.size, self.max_batch, self.device)
         std_points = STD_POINTS_256 * self.size / 256.0
         windows, idx = [], list(range(self.clip_size))
         for books, win in closed:
             track = _FrameTrack([rec for _, rec in win], [k % books.ring_frames for k, _ in win], books._shape)
             windows.append((books._ring.store, books.channel_order, track.frame, track, _fit(track, idx, std_points)))
-        cur, parts = torch.cuda.current_stream(self.device), []
-        for first, n, run in partition(len(windows), self.max_batch):
-            scorer = self._scorer(run)
-            self._warp(windows[first:first + n] + [windows[first + n - 1]] * (run - n), scorer.clip)
-            self.stats.count("warp")
-            parts.append(scorer.replay()[:n].to(torch.float32, copy=True))             # the next replay of this size overwrites its scores
-            self.stats.count("replay")
-        if self._scores_host is None or self._scores_host.numel() < len(windows):
-            self._scores_host = torch.empty(max(64, len(windows)), dtype=torch.float32, pin_memory=True)
-        self._scores_host[:len(windows)].copy_(parts[0] if len(parts) == 1 else torch.cat(parts), non_blocking=True)
-        cur.synchronize()
-        self.stats.count("wait")
-        return self._scores_host[:len(windows)].numpy().copy()
+        return self._scoring(len(windows), lambda first, n, run, clip: self._warp(windows[first:first + n] + [windows[first + n - 1]] * (run - n), clip),
+                             count=self.stats.count)

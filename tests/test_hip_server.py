@@ -282,3 +282,37 @@ def test_three_calls_share_one_real_yunet_launch():
             total += len(want)
         assert server.uploaded_bytes == (tick + 1) * 3 * h * w * 3
     assert total >= 1
+
+
+class _ManyRows:
+    """a detector that answers, for the frame whose first byte is k, with k rows (no kernel of the library is involved)"""
+
+    def __init__(self, capacity=80):
+        rng = np.random.default_rng(9)
+        self.rows = rng.uniform(1.0, 60.0, (capacity, 15)).astype(np.float32)
+        self.rows[:, 4] = 0.5                                     # under start_conf: the rows reach ``detections`` and no tracker
+
+    def detect_views(self, views):
+        counts = torch.stack([v[0, 0, 0] for v in views]).to(torch.int32)
+        return torch.from_numpy(self.rows).to(views[0].device)[None].repeat(len(views), 1, 1), counts
+
+    def detect(self, frames_u8):
+        return self.detect_views([frames_u8[0]])
+
+
+def test_a_frame_with_more_than_64_rows_costs_one_more_wait_and_loses_none():
+    """the second copy of the detection read-back, in both of its callers: a 64 x 64 frame for which the detector reports 65 rows"""
+    net, det = torch.nn.Linear(1, 1).cuda(), _ManyRows()          # the network only names the device: no window closes here
+    frame = lambda k: np.full((64, 64, 3), k, dtype=np.uint8)    # noqa: E731
+    lone = af_mi355x.RealtimeCall(net, detector=det, clip_size=CLIP, size=SIZE, **_args("bgr"))
+    for k in (64, 65, 3):
+        assert lone.step(frame(k)) == [] and np.array_equal(lone.detections, det.rows[:k]) and lone.detections.shape == (k, 15)
+    server = af_mi355x.CallServer(net, detector=det, clip_size=CLIP, size=SIZE, **_args("bgr"))
+    a, b = server.open(), server.open()
+    waits = []
+    for ka, kb in ((64, 7), (65, 7), (7, 65), (65, 65)):
+        assert server.step({a: frame(ka), b: frame(kb)}) == {a: [], b: []}
+        assert np.array_equal(server.call(a).detections, det.rows[:ka]) and np.array_equal(server.call(b).detections, det.rows[:kb])
+        assert server.stats.last["detect"] == 1 and server.stats.last["quality"] == 0
+        waits.append(server.stats.last["wait"])
+    assert waits == [1, 2, 2, 3]                                  # the read-back, and one more per frame with more than 64 rows

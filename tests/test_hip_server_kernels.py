@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from af_mi355x import _lib, evaluator, live
+from af_mi355x import _lib, evaluator, frames, live
 from test_hip_yunet import MODEL, frames as yunet_frames
 
 pytestmark = pytest.mark.gpu
@@ -94,7 +94,7 @@ def stores():
 
 
 def _refs(stores, order):
-    return (_lib.StoreRef * 2)(*[live._store_ref(stores[i], ORDERS[i]) for i in order])
+    return (_lib.StoreRef * 2)(*[frames.store_ref(stores[i], ORDERS[i]) for i in order])
 
 
 # ---- the warp ----------------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,10 @@
   refusals    a store index out of range; a rectangle that leaves its frame in store 1 only; 3 bytes of slack missing behind store
               1 only - AF_ERR_ARG with the window and frame named
   arguments   af_yunet_detect_frames, af_face_quality_stores_u8 and the stores warp refuse bad arguments before any device call
+  one planner the single-store and the several-stores planner write the same table for the same rectangles of store 0, refuse the
+              same cases with the same code and the same (window, frame), and stamp a refused table as no table; the shared tail
+              of WindowWarp / StoresWarp raises the aligner's canvas-misfit ValueError only for a rectangle that misfits its canvas
+  one check   a table of broken stores, refused by all five entry points that take a store, each under its own name
 """
 import ctypes as C
 import types
@@ -17,7 +21,7 @@ import pytest
 
 import test_live_host as LH
 import test_realtime_host as RH
-from af_mi355x import _lib, live
+from af_mi355x import _lib, evaluator, frames, live
 
 L = _lib.lib
 
@@ -250,6 +254,164 @@ def test_stores_plan_and_launch_refuse_bad_arguments_without_a_device():
     for n, clip, size in ((0, 3, 8), (65, 3, 8), (2, 0, 8), (2, 65, 8), (2, 3, 6), (2, 3, 1028)):
         assert L.af_warp_affine_window_stores_u8(one, n, clip, size, one, None) == -1, (n, clip, size)
     assert L.af_warp_affine_window_stores_u8(one, 2, 3, 8, C.c_void_p(table.ctypes.data + 2), None) == -1
+
+
+# ---- one planner behind both entry points ------------------------------------------------------------------------------------------
+
+SINGLE_ITEM = np.dtype([("offset", "<i8"), ("ih", "<i4"), ("iw", "<i4"), ("x", "<i4"), ("y", "<i4"), ("pitch", "<i4"), ("reserved", "<i4")])
+
+
+def _plan_single(desc, rects, size, slack=3):
+    n, clip = rects.shape
+    h, w, frames = SHAPES[0]
+    st = _lib.FrameStore(frames * h * w * 3 + slack, h * w * 3, w * 3, frames, h, w, 0)
+    table = np.zeros(L.af_window_rects_table_bytes(n, clip) // 8, dtype=np.int64)
+    bw, bf = C.c_int32(-7), C.c_int32(-7)
+    rc = L.af_window_rects_plan_u8(desc.ctypes.data, rects.ctypes.data, n, clip, size, C.byref(st), table.ctypes.data, table.nbytes,
+                                   C.byref(bw), C.byref(bf))
+    return rc, bw.value, bf.value, table
+
+
+def _store0_case(seed):
+    desc, rects = _case(np.random.default_rng(seed), 3, 4, [0, 0, 0])
+    desc["canvas_w"], desc["canvas_h"] = 400, 400
+    return desc, rects
+
+
+def test_both_planners_write_the_same_table_for_one_store():
+    desc, rects = _store0_case(21)
+    h, w, n = SHAPES[0]
+    rects[2, 3] = (n - 1, w - 2, h - 1, 1, 2, 0, 0, 0)           # the last two pixels of the store
+    rc, bw, bf, single = _plan_single(desc, rects, 8)
+    assert rc == 0 and (bw, bf) == (-1, -1), L.af_last_error()
+    rc, bw, bf, listed = _plan(desc, rects, 8, _stores(_ref(0)))
+    assert rc == 0 and (bw, bf) == (-1, -1), L.af_last_error()
+    a, b = single.view(np.uint8), listed.view(np.uint8)
+    assert a[:16].view("<i4").tolist() == [3, 4, 8, 1] and b[:16].view("<i4").tolist() == [3, 4, 8, 2]      # the header apart from kind
+    assert np.array_equal(a[16:16 + 3 * 48], b[16:16 + 3 * 48])                                           # the transforms
+    items = slice(16 + 3 * 48, 16 + 3 * 48 + 12 * 32)
+    one, many = a[items].view(SINGLE_ITEM), b[items].view(ITEM)
+    np.testing.assert_array_equal(many["first"].astype(np.int64), BASES[0] + one["offset"])
+    for k in ("ih", "iw", "x", "y", "pitch"):
+        np.testing.assert_array_equal(one[k], many[k])
+    flat = rects.reshape(-1)
+    np.testing.assert_array_equal(one["offset"], flat["frame"].astype(np.int64) * (h * w * 3) + flat["ry"].astype(np.int64) * (w * 3) + flat["rx"] * 3)
+    assert (one["reserved"] == 0).all() and (many["bgr"] == 1).all() and _ref(0).bgr == 1
+    assert (one["pitch"] == w * 3).all()
+
+
+def test_both_planners_refuse_alike():
+    h, w, n = SHAPES[0]
+
+    def leaves(desc, rects):
+        rects[1, 2] = (0, w - 10, 5, 20, 11, 0, 0, 0)            # one pixel over the right edge of its frame
+        return 3
+
+    def ends_the_store(desc, rects):
+        rects[1, 2] = (n - 1, w - 1, h - 1, 1, 1, 0, 0, 0)       # the last pixel of a store with 2 bytes behind it
+        return 2
+
+    def misfit(desc, rects):
+        rects["x"][1, 2] = 400 - rects["iw"][1, 2] + 1
+        return 3
+
+    def bad_canvas(desc, rects):
+        desc["canvas_h"][1] = 0
+        return 3
+
+    for case in (leaves, ends_the_store, misfit, bad_canvas):
+        desc, rects = _store0_case(22)
+        slack = case(desc, rects)
+        rc1, bw1, bf1, single = _plan_single(desc, rects, 8, slack=slack)
+        said1 = L.af_last_error().decode()
+        rc2, bw2, bf2, listed = _plan(desc, rects, 8, _stores(_ref(0, slack=slack)))
+        said2 = L.af_last_error().decode()
+        assert rc1 == rc2 == -1, case.__name__
+        assert said1.startswith("aligner: " if case is misfit else "window_rects_plan: ") and \
+            said2.startswith("aligner: " if case is misfit else "window_rects_plan_stores: "), (said1, said2)
+        assert ("does not fit" in said1) == ("does not fit" in said2) == (case is misfit), (said1, said2)
+        if case is bad_canvas:
+            assert "bad canvas" in said1 and "bad canvas" in said2
+            continue
+        assert (bw1, bf1) == (bw2, bf2) == (1, 2), case.__name__
+        assert "window 1 frame 2" in said1 and "window 1 frame 2" in said2
+        for table in (single, listed):
+            assert table.view(np.uint8)[:16].view("<i4")[3] not in (0, 1, 2), case.__name__      # a refused table is no table
+        assert ("leaves" in said1) == ("leaves" in said2) == (case is leaves)
+        assert ("3 readable bytes" in said1) == ("3 readable bytes" in said2) == (case is ends_the_store)
+
+
+def test_the_warps_shared_tail_calls_only_a_canvas_misfit_a_canvas_misfit():
+    """WindowWarp._plan, the host part of the tail every form of the warp shares, over a 64 x 64 store of 4 frames that lives in
+    host memory (the planner reads no pixel): the planner names the (window, frame) of every refusal, and only a rectangle that
+    really misfits its canvas becomes the aligner's ValueError"""
+    store = evaluator.FrameStore(None, "bgr")
+    store.open((64, 64, 3), 4)
+    fit = (np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), 40, 40, np.zeros((2, 2), dtype=np.int64))
+
+    def records(warp, rx):
+        desc, items = warp._records(1)
+        warp._fill(desc, items, 0, fit, [20, 20], [20, 20])
+        items["frame"][0], items["rx"][0], items["ry"][0] = [0, 3], [10, rx], [10, 10]
+        return desc, items
+
+    single = evaluator.WindowWarp(evaluator.RECTS_BGR, store, clip_size=2, size=8, batch=2)
+    listed = evaluator.StoresWarp("cpu", clip_size=2, size=8, batch=2)               # the device is the launch's: not touched here
+    table = np.zeros(single.table_bytes // 8, dtype=np.int64)
+    forms = ((single, lambda: (store.plan_source(),)), (listed, lambda: ((_lib.StoreRef * 1)(frames.store_ref(store, "bgr")), 1)))
+    for warp, where in forms:
+        warp._plan(*records(warp, 44), where(), table.ctypes.data)                     # 44 + 20 = 64: the rectangle ends with its frame
+        assert table.view(np.uint8)[:16].view("<i4").tolist()[:3] == [1, 2, 8]
+        with pytest.raises(_lib.AfError, match="window 0 frame 1.*leaves") as refused:
+            warp._plan(*records(warp, 45), where(), table.ctypes.data)
+        assert "does not fit" not in str(refused.value)
+        desc, items = records(warp, 44)
+        items["x"][0, 1] = 21                                                          # 21 + 20 > 40
+        with pytest.raises(ValueError, match=r"window 0 frame 1 \(20x20 at 21,0\) does not fit the 40x40 canvas"):
+            warp._plan(desc, items, where(), table.ctypes.data)
+
+
+# ---- one store check behind five entry points --------------------------------------------------------------------------------------
+
+def _broken_stores():
+    """store 1 (80 x 112, 9 frames; even, so that a YUV frame of its size exists) with one field wrong at a time"""
+    h, w, n = SHAPES[1]
+    return {"pitch": dict(row_pitch=w * 3 - 1), "stride": dict(frame_stride=(h - 1) * w * 3 + w * 3 - 1), "bytes": dict(store_bytes=n * h * w * 3 - 1),
+            "no frames": dict(n_frames=0), "width": dict(width=32768, row_pitch=32768 * 3, frame_stride=h * 32768 * 3, store_bytes=1 << 40)}
+
+
+def _broken(fields):
+    ref = _ref(1, slack=0)
+    for k, v in fields.items():
+        setattr(ref.desc, k, v)
+    return ref
+
+
+@pytest.mark.parametrize("what", list(_broken_stores()))
+def test_a_broken_store_is_refused_by_every_entry_point_under_its_own_name(what):
+    ref = _broken(_broken_stores()[what])
+    h, w, n = SHAPES[1]
+    desc, rects = np.zeros(1, dtype=WINDOW), np.zeros((1, 2), dtype=RECT)
+    desc[0] = ([1.0, 0.0, 0.0, 0.0, 1.0, 0.0], 40, 40)
+    rects["ih"], rects["iw"] = 10, 12
+    table = np.zeros(L.af_window_rects_table_bytes(1, 2) // 8, dtype=np.int64)
+    sums = np.zeros(64 * 3, dtype=np.int64)
+    pixels = C.c_void_p(BASES[1])                                 # an address only: every refusal comes before the first device call
+    plan = [desc.ctypes.data, rects.ctypes.data, 1, 2, 8]
+    calls = {"window_rects_plan": lambda: L.af_window_rects_plan_u8(*plan, C.byref(ref.desc), table.ctypes.data, table.nbytes, None, None),
+             "window_rects_plan_stores": lambda: L.af_window_rects_plan_stores_u8(*plan, _stores(ref), 1, table.ctypes.data, table.nbytes, None, None),
+             "face_quality": lambda: L.af_face_quality_u8(pixels, C.byref(ref.desc), rects.ctypes.data, 2, 1, C.c_void_p(sums.ctypes.data), None, 0, None),
+             "face_quality_stores": lambda: L.af_face_quality_stores_u8(_stores(ref), 1, rects.ctypes.data, 2, C.c_void_p(sums.ctypes.data), None, 0, None)}
+    if what != "width":                                           # a YUV frame of 32768 columns is refused before its store is looked at
+        frame = (_lib.YuvFrameDesc * 1)(_lib.YuvFrameDesc(0x1000, 0x2000, None, w, w, h, w, 1, 0, 0, n - 1))      # nv12 into the last slot
+        items = (_lib.YuvItem * 1)()
+        calls["yuv420_plan"] = lambda: L.af_yuv420_plan_u8(C.byref(frame), 1, C.byref(_stores(ref)), 1, C.byref(items))
+    for name, call in calls.items():
+        assert call() == -1, (what, name)
+        assert L.af_last_error().decode().startswith(name + ": "), (what, name, L.af_last_error())
+    good = _ref(1, slack=0)                                        # and the store as it should be passes all five (no rectangle ends it)
+    ref.desc = good.desc
+    assert all(call() == 0 for name, call in calls.items() if "quality" not in name), L.af_last_error()
 
 
 # ---- the other two entry points: every refusal comes before the first device call ---------------------------------------------------

@@ -209,7 +209,7 @@ def test_rect_plan_refuses_a_rectangle_that_leaves_its_frame():
     d = desc.copy()
     d["canvas_w"], d["canvas_h"] = 400, 400
     rc, bw, bf, _ = _plan(d, r, 8, _store())
-    assert rc == -1 and (bw, bf) == (-1, -1) and b"leaves" in _lib.lib.af_last_error()
+    assert rc == -1 and (bw, bf) == (2, 0) and b"leaves" in _lib.lib.af_last_error()
     r[2, 0] = (0, 5, H - 10, 11, 20, 0, 0, 0)
     assert _plan(d, r, 8, _store())[0] == -1 and b"leaves" in _lib.lib.af_last_error()
     r[2, 0] = (0, 5, H - 10, 10, 20, 0, 0, 0)
