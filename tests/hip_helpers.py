@@ -184,22 +184,24 @@ def conv_cpa(b_ndhwc, wc_oidhw, bn_c, res_ndhwc, wa_oidhw, bn_a, dtype, x_sub):
     return x, a_out
 
 
-def conv_dual(x_ndhwc, w_oidhw, bn, x2_ndhwc, w2_oidhw, bn2, stride2, dtype):
-    """relu(bn(conv1x1x1(x)) + bn2(conv1x1x1_strided(x2))) as one af_conv3d_dual_bn_act launch."""
+def conv_dual(x_ndhwc, w_oidhw, bn, x2_ndhwc, w2_oidhw, bn2, stride2, dtype, out=None, out_ld=0, tpool=0):
+    """relu(bn(conv1x1x1(x)) + bn2(conv1x1x1_strided(x2))) as one af_conv3d_dual_bn_act launch; ``out`` / ``out_ld``: rows of a
+    wider caller-owned buffer, ``tpool`` = 1: the frame-pair max fused behind the ReLU."""
     L = lib()
     (scale, shift), (scale2, shift2) = bn, bn2
     n, t, h, w, cin = x_ndhwc.shape
     cout = w_oidhw.shape[0]
-    d = _desc(x_ndhwc.shape, cout, (1, 1, 1), dtype)
+    d = _desc(x_ndhwc.shape, cout, (1, 1, 1), dtype, tpool=tpool)
     d2 = _desc(x2_ndhwc.shape, cout, (1, 1, 1), dtype, stride=stride2, dout=(t, h, w))
-    out = torch.empty((n, t, h, w, cout), dtype=TORCH_DT[dtype], device="cuda")
+    if out is None:
+        out = torch.empty((n, t // 2 if int(tpool) == 1 else t, h, w, cout), dtype=TORCH_DT[dtype], device="cuda")
     ones = torch.ones(L.lib.af_padded_channels(cout), device="cuda")
     # keep every device buffer referenced until the launch has been enqueued (the caching allocator would
     # otherwise hand the first packed weight's memory to the second)
     pw, pw2, shift_sum = _pack(w_oidhw, dtype, scale), _pack(w2_oidhw, dtype, scale2), (shift + shift2).contiguous()
     conv_dual.last_variant = L.lib.af_conv_variant(C.byref(d), C.byref(d2))
     L.check(L.lib.af_conv3d_dual_bn_act(C.byref(d), _p(x_ndhwc), _p(pw), C.byref(d2), _p(x2_ndhwc), _p(pw2), _p(ones),
-                                        _p(shift_sum), _p(out), 0, _stream()), "conv3d_dual_bn_act")
+                                        _p(shift_sum), _p(out), out_ld, _stream()), "conv3d_dual_bn_act")
     torch.cuda.current_stream().synchronize()
     return out
 

@@ -259,9 +259,17 @@ CONV_CASES = [
     ("t311g_192to256_T16_ragged", 192, 256, (3, 1, 1), (1, 1, 1), (1, 0, 0), (1, 16, 53, 51), True, False),
     ("t311g_64to128_T16_ragged", 64, 128, (3, 1, 1), (1, 1, 1), (1, 0, 0), (1, 16, 74, 73), True, False),
     ("t311g_128to128_T32_norelu", 128, 128, (3, 1, 1), (1, 1, 1), (1, 0, 0), (1, 32, 52, 52), False, False),
+    # 16-bit layers that pick_variant itself gives the 128x256 tile (12 K-steps at 73 workgroups: too few for 256x256; the asm K
+    # loop; two clips of 6 frames, 36.7 row tiles), the 64x256 tile (64 channels, 6 K-steps, T = 10: not the time-tiled kernel) and
+    # the 128x128 tile with the 2-slot ring (128 channels, 8 K-steps); fp32 takes 128x256 for the first and the third, split 3 ways
+    ("tile0_3x1x1_256to256", 256, 256, (3, 1, 1), (1, 1, 1), (1, 0, 0), (2, 6, 27, 29), True, False),
+    ("tile1_3x1x1_128to64", 128, 64, (3, 1, 1), (1, 1, 1), (1, 0, 0), (2, 10, 29, 30), True, False),
+    ("tile5_1x1x1_512to128", 512, 128, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 8, 33, 32), True, False),
 ]
 EXPECT_VARIANT = {"c64_1x3x3_56x56": {"f16": 4, "bf16": 4}, "c64_1x3x3_30x27": {"f16": 4, "bf16": 4},
-                  "c64_1x3x3_56x56_many": {"f16": 4, "bf16": 4}, "c64_1x3x3_54x50_many": {"f16": 4, "bf16": 4}, "1x3x3": {"f16": 3, "bf16": 3},
+                  "c64_1x3x3_56x56_many": {"f32": 1, "f16": 4, "bf16": 4}, "c64_1x3x3_54x50_many": {"f32": 1, "f16": 4, "bf16": 4},
+                  "1x3x3": {"f16": 3, "bf16": 3},
+                  "tile0_3x1x1_256to256": 0, "tile1_3x1x1_128to64": 1, "tile5_1x1x1_512to128": {"f32": 0, "f16": 5, "bf16": 5},
                   "tile256_1x3x3_res": 6, "tile256_ragged_m": 6, "tile224_1x3x3_res": 12, "tile224_ragged_m": 12,
                   "tile224_3x1x1_1024to256": {"f16": 12, "bf16": 12}, "tile224_1x1x1_1024to256_res": {"f16": 12, "bf16": 12}, "tile512_1x3x3_res": 7, "tile512_ragged_m": 7,
                   "t311_64to64_T32": 8, "t311_256to64_T16": 8, "t311_256to64_T32_many": 8,
@@ -270,14 +278,15 @@ EXPECT_VARIANT = {"c64_1x3x3_56x56": {"f16": 4, "bf16": 4}, "c64_1x3x3_30x27": {
                   "stream111_128to512_res_ragged": {"f32": 5, "f16": 10, "bf16": 10},
                   "stream111_256to1024_res_ragged": {"f32": 5, "f16": 10, "bf16": 10},
                   "stream111_64to768_three_columns": {"f32": 2, "f16": 10, "bf16": 10},
-                  "stream111_128to256_nores_ragged": {"f16": 10, "bf16": 10}, "stream111_256to512_nores_ragged": {"f16": 10, "bf16": 10},
+                  "stream111_128to256_nores_ragged": {"f32": 0, "f16": 10, "bf16": 10},
+                  "stream111_256to512_nores_ragged": {"f32": 5, "f16": 10, "bf16": 10},
                   "halo133_64to256_14x14": {"f32": 12, "f16": 11, "bf16": 11}, "halo133_192to256_13x14": {"f32": None, "f16": 11, "bf16": 11},
                   "halo133_128to128_28x28": {"f32": 7, "f16": 11, "bf16": 11},
                   "halo133_256to128_27x26_norelu": {"f32": 7, "f16": 11, "bf16": 11},
-                  "halo333_64to64_56x56": {"f16": 11, "bf16": 11}, "halo333_64to64_50x53_norelu": {"f16": 11, "bf16": 11},
+                  "halo333_64to64_56x56": {"f32": 1, "f16": 11, "bf16": 11}, "halo333_64to64_50x53_norelu": {"f32": 1, "f16": 11, "bf16": 11},
                   "halo333_64to128_28x28": {"f16": 11, "bf16": 11}, "halo333_128to256_14x14": {"f16": 11, "bf16": 11},
                   "t311g_128to256_T16": {"f16": 13, "bf16": 13}, "t311g_192to256_T16_ragged": {"f16": 13, "bf16": 13},
-                  "t311g_64to128_T16_ragged": {"f16": 13, "bf16": 13}, "t311g_128to128_T32_norelu": {"f16": 13, "bf16": 13}}
+                  "t311g_64to128_T16_ragged": {"f32": 5, "f16": 13, "bf16": 13}, "t311g_128to128_T32_norelu": {"f32": 0, "f16": 13, "bf16": 13}}
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -316,9 +325,11 @@ def test_conv_vs_oracle(case, dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("cin,cout,dims", [(64, 256, (2, 6, 9, 7)), (64, 64, (1, 4, 5, 5)),
-                                           (64, 256, (2, 16, 63, 65))])     # persistent stream: 1024 tiles, ragged 64-pixel chunks
+                                           (64, 256, (2, 16, 63, 65)),      # persistent stream: 1024 tiles, ragged 64-pixel chunks
+                                           (64, 256, (1, 4, 47, 49))])      # the 128x128 tile (where a small batch ships it), 71.97 row tiles
 def test_conv_with_fused_temporal_maxpool(dtype, cin, cout, dims):
-    """s2's last 1x1x1 (+ residual + ReLU) with pathway0_pool = MaxPool3d([2,1,1]) fused into its epilogue."""
+    """s2's last 1x1x1 (+ residual + ReLU) with pathway0_pool = MaxPool3d([2,1,1]) fused into its epilogue: on the 64x128 tile
+    (the two small cases), the persistent stream (fp32: the 128x128 tile) and the 128x128 tile."""
     seed = 4242 + cout
     lay = [("w.weight", (cout, cin, 1, 1, 1), "float32"), ("bn.weight", (cout,), "float32"), ("bn.bias", (cout,), "float32"),
            ("bn.running_mean", (cout,), "float32"), ("bn.running_var", (cout,), "float32")]
@@ -332,8 +343,8 @@ def test_conv_with_fused_temporal_maxpool(dtype, cin, cout, dims):
     want = F.max_pool3d(F.relu(y + res.double()), (2, 1, 1), (2, 1, 1))
     got = hh.conv_bn_act(hh.to_ndhwc(x, dtype), sd["w.weight"], *hh.fold_bn(sd, "bn"), (1, 1, 1), (0, 0, 0), True, dtype,
                          residual=hh.to_ndhwc(res, dtype), tpool=True)
-    if dims[2] * dims[3] > 4000 and dtype != "f32":
-        assert hh.conv_bn_act.last_variant == 10, hh.conv_bn_act.last_variant
+    want_variant = {(2, 6, 9, 7): 3, (1, 4, 5, 5): 3, (2, 16, 63, 65): 2 if dtype == "f32" else 10, (1, 4, 47, 49): 2}[dims]
+    assert hh.conv_bn_act.last_variant == want_variant, hh.conv_bn_act.last_variant
     got = hh.to_ncdhw(got).double()
     assert got.shape == want.shape
     tol = {"f32": 2e-6, "f16": 1.5e-3, "bf16": 1.2e-2}[dtype]
@@ -392,9 +403,11 @@ def test_projection_shortcut_256_tile(dtype, rows, monkeypatch):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("cin,cout,dims,relu", [(128, 128, (2, 3, 8, 10), True),       # pooled `b` conv (64x128 tile: 4 pooled rows per patch)
-                                                (256, 512, (1, 4, 12, 6), False),      # pooled projection shortcut
-                                                (64, 256, (1, 16, 56, 56), True)])     # 256x256 tile
+@pytest.mark.parametrize("cin,cout,dims,relu", [
+    (128, 128, (2, 3, 8, 10), True),       # pooled `b` conv (64x128 tile: 4 pooled rows per patch)
+    (256, 512, (1, 4, 12, 6), False),      # pooled projection shortcut (64x128 tile)
+    (64, 256, (1, 16, 56, 56), True),      # 128x128 tile (1 - 2 K-steps: too short for the pooled 256x256 form)
+    (256, 256, (1, 16, 56, 56), True)])    # 256x256 tile (4 - 8 K-steps)
 def test_conv_with_fused_2x2_maxpool(dtype, cin, cout, dims, relu):
     """FTCN-TT: conv -> BN -> MaxPool3d((1,2,2)) [-> ReLU] (i3d_temporal_var_fix_dropout_tt_cfg.py:207-288) in one launch."""
     seed = 777 + cout
@@ -410,6 +423,7 @@ def test_conv_with_fused_2x2_maxpool(dtype, cin, cout, dims, relu):
     if relu:
         want = F.relu(want)
     got = hh.conv_bn_act(hh.to_ndhwc(x, dtype), sd["w.weight"], *hh.fold_bn(sd, "bn"), (1, 1, 1), (0, 0, 0), relu, dtype, tpool=2)
+    assert hh.conv_bn_act.last_variant == {(128, 128): 3, (256, 512): 3, (64, 256): 2, (256, 256): 6}[(cin, cout)], hh.conv_bn_act.last_variant
     got = hh.to_ncdhw(got).double()
     assert got.shape == want.shape
     tol = {"f32": 2e-6, "f16": 1.5e-3, "bf16": 1.2e-2}[dtype]

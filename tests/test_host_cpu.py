@@ -728,3 +728,46 @@ def test_conv_paths_and_fusion_answers_equal_the_recorded_ones():
         assert got[key]["convs"] == want[key]["convs"], key
         assert got[key]["fusable"] == want[key]["fusable"], key
         assert len(want[key]["convs"]) >= 40 and len(want[key]["fusable"]) >= 10, key
+
+
+def test_conv_matrix_covers_what_ships(monkeypatch):
+    """every (conv_igemm tile, dtype, epilogue form, K-step class) that the three networks launch at batch 1..32 is a case of
+    tests/test_hip_conv_matrix.py (which runs it against fp64 on the GPU): a new layer shape or pick_variant threshold that ships
+    an untested pair fails here.  The plans are built with the fusions off, as tools/gen_conv_paths_golden.py builds them; form =
+    (two inputs, residual, tpool, out_ld != cout, split-K); K-steps S class as S up to 6 and as S mod 6 beyond."""
+    import ctypes as C
+    import importlib.util
+    from af_mi355x import engine
+    from af_mi355x._lib import lib
+    spec_ = importlib.util.spec_from_file_location("test_hip_conv_matrix", os.path.join(ROOT, "tests", "test_hip_conv_matrix.py"))
+    matrix = importlib.util.module_from_spec(spec_)
+    spec_.loader.exec_module(matrix)
+    covered = {matrix.case_key(c, dt) for dt in matrix.DTYPES for c in matrix.CASES if not c.nonfinite}
+    for name in ("AF_FUSE_BC", "AF_FUSE_CA", "AF_FUSE_CPA", "AF_FUSE_ABC"):
+        monkeypatch.setenv(name, "0")
+    monkeypatch.delenv("AF_FORCE_VAR", raising=False)
+    specs = {"i3d_r50": arch.i3d_r50_spec(), "slowfast_r50": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
+    rgb3 = {"i3d_r50": {specs["i3d_r50"].stem.conv}, "slowfast_r50": {specs["slowfast_r50"].stems[0].conv}, "ftcn_tt": set()}
+    shipped = {}
+    for net, spec in specs.items():
+        for dtype in ("f32", "bf16", "f16"):
+            bk = 32 if dtype == "f32" else 64
+            for batch in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32):
+                p = engine.plan_network(spec, dtype, batch, (spec.num_frames, spec.crop, spec.crop), rgb3[net] if dtype != "f32" else set())
+                for e in p.entries:
+                    if e["kind"] not in ("conv", "dual"):
+                        continue
+                    cv, dual, tpool = e["cv"], e["kind"] == "dual", int(e.get("tpool") or 0)
+                    d = p.desc(cv, e["din"], e["dout"], tpool)
+                    d2 = p.desc(e["cv2"], e["din2"], e["dout"]) if dual else None
+                    tile = lib.af_conv_variant(C.byref(d), C.byref(d2) if dual else None)
+                    if tile not in matrix.TILES:
+                        continue                                # a specialised kernel: its own tests pin the variant
+                    s = cv.kernel[0] * cv.kernel[1] * cv.kernel[2] * -(-cv.cin // bk) + (-(-e["cv2"].cin // bk) if dual else 0)
+                    split = not dual and lib.af_conv_workspace_bytes(C.byref(d)) > 0
+                    form = (dual, e.get("res") is not None, tpool, e.get("ld", cv.cout) != cv.cout, split)
+                    shipped.setdefault((tile, dtype, form, s if s <= 6 else ("big", s % 6)), "%s batch %d: %d -> %d %s, S = %d" % (
+                        net, batch, cv.cin, cv.cout, tuple(cv.kernel), s))
+    assert len(shipped) >= 200, len(shipped)
+    missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
+    assert not missing, "%d shipped tile x form pairs without a matrix case:\n%s" % (len(missing), "\n".join(missing))
