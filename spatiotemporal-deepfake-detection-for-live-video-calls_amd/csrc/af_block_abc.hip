@@ -304,11 +304,11 @@ static bool abc_geometry(const af_conv_desc* da, const af_conv_desc* db, const a
     }
     if ((long long)da->h * da->w * 8 * inner >= (1LL << 31)) return false;
     // patch rows: the phases of a frame are short dependent chains (LDS read -> MFMA -> BN -> LDS write, a barrier between them),
-    // so what pays is latency hiding, not the smaller halo of a taller patch.  Measured on SlowFast's Fast pathway (B = 16, bf16;
-    // AF_ABC_PH sweeps it): s2 (inner 8) 14 / 10 / 7 / 5 / 4 / 3 rows -> 0.097 / 0.098 / 0.080 / 0.082 / 0.099 / 0.104 ms per
+    // so what pays is latency hiding, not the smaller halo of a taller patch.  Measured on SlowFast's Fast pathway (B = 16, bf16,
+    // sweeping the start value below): s2 (inner 8) 14 / 10 / 7 / 5 / 4 / 3 rows -> 0.097 / 0.098 / 0.080 / 0.082 / 0.099 / 0.104 ms per
     // block (7 rows = 58 KB of LDS: two workgroups per CU, 8 even bands of a 56-row frame); s3 (inner 16) 10 / 7 / 5 / 4 / 3 rows ->
     // 0.070 / 0.053 / 0.081 / 0.054 / 0.082 ms.
-    int p = env_int("AF_ABC_PH", 7);
+    int p = 7;
     if (p > da->h) p = da->h;
     if (p < 1) p = 1;
     while (p > 1 && abc_lds_bytes(inner, cin, p, da->kt) > 160 * 1024) --p;

@@ -14,19 +14,39 @@ namespace af {
 
 int set_error(int code, const char* fmt, ...);
 
-// an integer knob from the environment (A/B runs, experiments, tests); `dflt` when it is not set
+// An integer knob from the environment; `dflt` when it is not set.  The shipped library reads exactly three names, all in host-side
+// selection code and all flipped in-process by tests: AF_FORCE_VAR and AF_IGEMM_224 (af_conv.hip, pick_variant) and AF_ABC_INNER32
+// (af_block_abc.hip); tests/test_host_cpu.py pins that set.  They are read per call on purpose: a cached value would not see the
+// tests' changes, and a setter in the C ABI would be more machinery than three knobs deserve.  A kernel FORM is not chosen here: two
+// forms are compared as two libraries (tools/ab_lib.sh).  The diagnostic build's knobs are all below, under AF_STAMPS.
 inline int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) : dflt;
 }
 
-// Diagnostic build (-DAF_STAMPS) only: the stamp buffer of AF_STAMP_PTR and the kernel's timing-ablation knob into its arguments
+// Diagnostic build (-DAF_STAMPS; never the shipped library) only - every environment name it reads is read here.
+// fill_dbg: a kernel's timing-ablation knob (AF_G_DBG, AF_C64_DBG, AF_CA_DBG) into its arguments; fill_stamps: that and the stamp
+// buffer of AF_STAMP_PTR; stamps_unit_per_workgroup: should conv133g give every unit a workgroup of its own instead of persisting?
+template <class Args>
+inline void fill_dbg(Args& a, const char* dbg_knob) {
+#ifdef AF_STAMPS
+    a.dbg = env_int(dbg_knob, 0);
+#endif
+}
 template <class Args>
 inline void fill_stamps(Args& a, const char* dbg_knob) {
 #ifdef AF_STAMPS
     const char* ep = getenv("AF_STAMP_PTR");
     a.stamps = ep ? (unsigned long long*)strtoull(ep, nullptr, 0) : nullptr;
-    a.dbg = env_int(dbg_knob, 0);
+#endif
+    fill_dbg(a, dbg_knob);
+}
+inline bool stamps_unit_per_workgroup() {
+#ifdef AF_STAMPS
+    static const int persist = env_int("AF_G_PERSIST", 1);   // 0: the stamp slots are per unit (tools/r04_collect.sh)
+    return !persist;
+#else
+    return false;
 #endif
 }
 // ... and its device side: shader-clock stamps around the phases of a tile / unit, kept in registers and written behind the last

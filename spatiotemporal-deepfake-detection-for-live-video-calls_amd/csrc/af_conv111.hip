@@ -53,18 +53,16 @@ __device__ __forceinline__ void wait_counted(int nl, int ns) {
     }
 }
 
-// WC = output channels per wave: 64 (4 channel groups x 2 position halves) or, for K = 256 where 64 channels of
-// weights would not fit the registers next to two residual sets, 32 (8 channel groups, every wave all 128 positions).
+// Every wave has WC = 64 output channels (4 channel groups x 2 position halves).
 // BM = positions per tile, NSLOT = slots of the activation ring = residual register sets: tile q + NSLOT - 1 is fetched while
 // tile q is multiplied (NSLOT = 2: one tile ahead, the original pipeline; deeper for the short tiles of K = 256).
-template <int DT, int KS1, int KS2, bool TPOOL, bool RES, int WC, int BM = 128, int NSLOT = 2>
+template <int DT, int KS1, int KS2, bool TPOOL, bool RES, int BM = 128, int NSLOT = 2>
 __global__ __launch_bounds__(512, 1) void conv111_kernel(const C111Args a) {
     typedef Elem<DT> E;
     constexpr int EPC = E::EPC, ES = 16 / EPC;
     static_assert(EPC == 8, "16-bit storage types only");
-    static_assert(WC == 64 || (WC == 32 && !TPOOL), "wave columns of 64 or 32 channels; the pooled tile order assumes 64");
     static_assert((BM == 128 || (BM == 64 && !TPOOL)) && NSLOT >= 2 && NSLOT <= 4, "tiles of 128 or 64 positions; the pooled row order assumes 128");
-    constexpr int KS = KS1 + KS2, TN = WC / 16, D = NSLOT - 1;
+    constexpr int WC = 64, KS = KS1 + KS2, TN = WC / 16, D = NSLOT - 1;
     constexpr int NWN = 256 / WC, NWM = 8 / NWN, WPOS = BM / NWM, MT = WPOS / 16;   // wave grid; positions, m-tiles per wave
     constexpr int SLAB = BM * 128, STAGE = KS * SLAB;  // bytes: one 64-channel K slab of the tile; one ring slot
     constexpr int PROW = WC + 4;                       // patch row stride in floats (pad: conflict-free b128 writes)
@@ -108,22 +106,15 @@ __global__ __launch_bounds__(512, 1) void conv111_kernel(const C111Args a) {
             wreg[i][2 * KS1 + k] = *reinterpret_cast<const uint4*>(a.w2 + (ch * a.Cin2 + k * 32 + fg * 8) * ES);
     }
 
-    // ---- epilogue geometry: lane = (row rr of RPI, 8 channels at cc) of a 16-row patch.
-    // REGEPI (round 4, the 32-channel wave columns of K = 256): no patch - the packed halves of the wave's two channel tiles trade
-    // places between lane rows (v_permlane16_swap, swap_pair16), so lane (position frow, group fg) holds 8 consecutive channels:
-    // row rr = frow, channels (fg & 1) * 16 + (fg >> 1) * 8 .. + 7 - the same 64-byte row segments per wave instruction as the
-    // patch form wrote, without four LDS round trips per tile on an in-order wave; the residual rows arrive in that layout and are
-    // traded back into tile order for the fp32 sum.  Measured: a tie with the patch form (59.1 against 58.5 us for s4's c conv): the
-    // launch is bound by its 64-byte memory segments (4.6 TB/s with the compute switched off), not by the transposition.
-    constexpr bool REGEPI = WC == 32;
-    const int rr = REGEPI ? frow : lane / LPR, cc = REGEPI ? (fg & 1) * 16 + (fg >> 1) * 8 : (lane % LPR) * 8;
+    // ---- epilogue geometry: lane = (row rr of RPI, 8 channels at cc) of a 16-row patch
+    const int rr = lane / LPR, cc = (lane % LPR) * 8;
     const int ch0 = col * 256 + wn * WC + cc;
-    // BN scale / shift: of this lane's 8 channels in row order, or (REGEPI) of its 4 channels of tile 0 and of tile 1: registers
+    // BN scale / shift of this lane's 8 channels in row order: registers
     // (read from LDS per use they were a third of the kernel's LDS traffic; the two-pass accumulators left the room)
     f32x4 sc[2], sf[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-        const int chp = REGEPI ? col * 256 + wn * WC + e * 16 + fg * 4 : ch0 + 4 * e;
+        const int chp = ch0 + 4 * e;
         sc[e] = *reinterpret_cast<const f32x4*>(a.scale + chp);
         sf[e] = *reinterpret_cast<const f32x4*>(a.shift + chp);
     }
@@ -257,31 +248,6 @@ __global__ __launch_bounds__(512, 1) void conv111_kernel(const C111Args a) {
                     for (int jl = 0; jl < 2; ++jl) Mma<DT>::run(wreg[i][k], bf[jl], acc[i][jl]);
             }
 
-            if constexpr (REGEPI) {
-                // ---- epilogue in registers: BN in tile order, + the residual traded back into tile order, ReLU, the one rounding,
-                // then the packed halves of the two tiles trade lane rows: 16 bytes = 8 consecutive channels per lane
-                const float lo = a.relu ? 0.f : -__builtin_inff();
-#pragma unroll
-                for (int jl = 0; jl < 2; ++jl) {
-                    const int j = 2 * h + jl, row = wm * WPOS + j * 16 + rr;
-                    f32x4 v0 = acc[0][jl] * sc[0] + sf[0], v1 = acc[1][jl] * sc[1] + sf[1];
-                    if (RES) {
-                        const u32x4 x = rcur[j];
-                        const u32x2 s0 = __builtin_amdgcn_permlane16_swap(x[0], x[2], false, false);
-                        const u32x2 s1 = __builtin_amdgcn_permlane16_swap(x[1], x[3], false, false);
-                        const u32x2 ra = u32x2{s0[0], s1[0]}, rb = u32x2{s0[1], s1[1]};
-                        v0 += Vec4<DT>::load(&ra); v1 += Vec4<DT>::load(&rb);
-                    }
-                    v0[0] = max_nan(v0[0], lo); v0[1] = max_nan(v0[1], lo); v0[2] = max_nan(v0[2], lo); v0[3] = max_nan(v0[3], lo);
-                    v1[0] = max_nan(v1[0], lo); v1[1] = max_nan(v1[1], lo); v1[2] = max_nan(v1[2], lo); v1[3] = max_nan(v1[3], lo);
-                    u32x2 p0, p1;
-                    Vec4<DT>::store(&p0, v0); Vec4<DT>::store(&p1, v1);
-                    const u32x4 o = swap_pair16(p0, p1);
-                    if (row_live(row, live))
-                        __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(obase + out_soff(j) + out_lane));
-                }
-                continue;
-            }
             // ---- epilogue: 16 positions at a time through the wave's patch
             float keep[ITS][8];                          // tpool: frame 0 of the pixel rows, waiting for frame 1
 #pragma unroll
@@ -337,11 +303,11 @@ __global__ __launch_bounds__(512, 1) void conv111_kernel(const C111Args a) {
     }
 }
 
-template <int DT, int KS1, int KS2, bool TPOOL, bool RES, int WC = 64, int BM = 128, int NSLOT = 2>
+template <int DT, int KS1, int KS2, bool TPOOL, bool RES, int BM = 128, int NSLOT = 2>
 static int launch111(const C111Args& a, int blocks, hipStream_t stream) {
-    const int lds = NSLOT * (KS1 + KS2) * BM * 128 + 8 * 16 * (WC + 4) * 4;
-    AF_SET_MAX_LDS((&conv111_kernel<DT, KS1, KS2, TPOOL, RES, WC, BM, NSLOT>), lds, "conv111");
-    hipLaunchKernelGGL((conv111_kernel<DT, KS1, KS2, TPOOL, RES, WC, BM, NSLOT>), dim3(blocks), dim3(512), lds, stream, a);
+    const int lds = NSLOT * (KS1 + KS2) * BM * 128 + 8 * 16 * (64 + 4) * 4;        // ring + the waves' epilogue patches
+    AF_SET_MAX_LDS((&conv111_kernel<DT, KS1, KS2, TPOOL, RES, BM, NSLOT>), lds, "conv111");
+    hipLaunchKernelGGL((conv111_kernel<DT, KS1, KS2, TPOOL, RES, BM, NSLOT>), dim3(blocks), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("conv111_kernel");
     return AF_OK;
 }
@@ -392,19 +358,13 @@ int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, con
         if (d2) return launch111<dt, 1, 1, false, false>(a, blocks, stream);
         if (d->tpool) return residual ? launch111<dt, 1, 0, true, true>(a, blocks, stream) : launch111<dt, 1, 0, true, false>(a, blocks, stream);
         if (d->cin == 64) return residual ? launch111<dt, 1, 0, false, true>(a, blocks, stream) : launch111<dt, 1, 0, false, false>(a, blocks, stream);
-        // K = 256 (s4 `c`).  Round 4, late: 64-channel wave columns - 128-byte row segments for the residual rows and the output instead of
-        // 64 - with a TWO-slot ring.  128 weight registers next to the three residual sets of the 4-slot ring spilled 11 registers (and a
-        // scratch reload's vmcnt(0) is poison in this loop), which is why rounds 2-4 ran this layer on 32-channel columns; with ONE residual
-        // set (one tile ahead) it is 242 registers, and one tile of look-ahead on full lines beats three tiles of it on half lines:
-        // 58.6 -> 49.9 us (tools/exp_c111_wc64.py, interleaved on one box).  AF_C111_WC64=0: the 32-channel form, for A/B runs.
-        // (A three-slot ring with the BN parameters moved to LDS - 256 registers, no spills - measured the same as two slots: 49.0 us.)
-        if (d->cin == 256) {
-            if (env_int("AF_C111_WC64", 1) != 0)
-                return residual ? launch111<dt, 4, 0, false, true, 64, 64, 2>(a, blocks, stream) : launch111<dt, 4, 0, false, false, 64, 64, 2>(a, blocks, stream);
-            return residual ? launch111<dt, 4, 0, false, true, 32, 64, 4>(a, blocks, stream) : launch111<dt, 4, 0, false, false, 32, 64, 4>(a, blocks, stream);
-        }
+        // K = 256 (s4 `c`): a TWO-slot ring.  128 weight registers next to the three residual sets of a 4-slot ring spilled 11
+        // registers (a scratch reload's vmcnt(0) is poison in this loop); with ONE residual set (one tile ahead) it is 242 registers.
+        // (Measured against 32-channel wave columns on a 4-slot ring, the form of rounds 2-4: 58.6 -> 49.9 us)
+        if (d->cin == 256)
+            return residual ? launch111<dt, 4, 0, false, true, 64, 2>(a, blocks, stream) : launch111<dt, 4, 0, false, false, 64, 2>(a, blocks, stream);
         // K = 128: tiles of 64 positions as well (16-KB stages), three tiles ahead
-        return residual ? launch111<dt, 2, 0, false, true, 64, 64, 4>(a, blocks, stream) : launch111<dt, 2, 0, false, false, 64, 64, 4>(a, blocks, stream);
+        return residual ? launch111<dt, 2, 0, false, true, 64, 4>(a, blocks, stream) : launch111<dt, 2, 0, false, false, 64, 4>(a, blocks, stream);
     });
 }
 

@@ -4,23 +4,21 @@
 // The generic implicit GEMM streams every activation row through LDS once PER TAP (9x) and re-reads the
 // weight tile from LDS for every 32 positions; at Cin = Cout = 64 that makes the layer ingest / LDS bound
 // (~0.37 PFLOP/s).  This kernel is shaped around what is small here:
-//   * the whole weight tensor (64 x 9 x 64) lives in REGISTERS: 4 waves, ONE per SIMD, each with all 64 output
-//     channels: 72 MFMA A-fragments (9 taps x 2 k-halves x 4 channel tiles = 288 registers, VGPRs + AGPRs - a wave
-//     alone on its SIMD has all 512) for the life of the workgroup; the A operand never touches LDS, a B fragment
-//     feeds 4 MFMAs, and the fragments of the next (tap, k-half) step are read while this one multiplies (with two
-//     waves per SIMD and 32 channels each, the loop was a chain of LDS latencies: read, wait, 2 MFMAs);
+//   * the weights stay with the waves for the life of the workgroup: EIGHT waves, two per SIMD, wave = (channel half,
+//     m-tile group), 32 output channels x 4 m-tiles each; the MFMA A-fragments of taps 0-6 (7 taps x 2 k-halves x 2 channel
+//     tiles = 112 registers) live in REGISTERS and those of the last two taps wait in LDS in fragment order (all nine taps in
+//     registers spilled); a B fragment feeds 2 MFMAs and is read a whole (tap, k-half) step ahead of its use;
 //   * a workgroup walks a contiguous run of image strips (R = 4 output rows); each strip's input patch
 //     ((R+2) rows, zero halo columns included) is brought in ONCE by LDS-DMA (buffer loads; out-of-range lanes = zeros), double-buffered under the MFMAs
 //     of the previous strip, and all 9 taps read it: with the rows stored at a padded pitch WP = W + 2 a tap
 //     (dh,dw) is the constant row offset dh*WP + dw, so every B fragment is a plain swizzled ds_read_b128;
 //   * positions are the padded strip (R x WP, two halo columns per row computed and discarded: 3.4 % waste).
-// Persistent: one workgroup per CU, two barriers per strip (~4 600 MFMA cycles per wave between them).  Results leave
-// through an LDS output tile ([position][64 channels], swizzled like the patches): the workgroup stores whole 128-byte
-// rows, and does so under the MFMAs of the NEXT strip.
+// Persistent: one workgroup per CU, two barriers per strip.  Results leave through an LDS output tile ([position][64
+// channels], swizzled like the patches): the workgroup stores whole 128-byte rows, and does so under the MFMAs of the
+// NEXT strip.
 #include "af_common.h"
 
 namespace af {
-
 
 struct C133Args {
     const char* in;
@@ -56,180 +54,10 @@ struct C133Args {
 #define C64_FLUSH do {} while (0)
 #endif
 
-
-template <int DT, int R>
-__global__ __launch_bounds__(256, 1) void conv133_c64_kernel(const C133Args a) {
-    typedef Elem<DT> E;
-    static_assert(E::EPC == 8, "16-bit operands only");
-    constexpr int MT = 4;                              // m-tiles per wave (up to 16 per strip)
-    constexpr int OTROWS = 16 * 16;                    // rows of the output tile (16 m-tiles of 16 positions)
-
-    extern __shared__ uint4 smem[];
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int mg = wave;                               // m-tile group: tiles mg, mg + 4, ... (all 64 channels per wave)
-    constexpr int NT4 = 4;                             // channel tiles per wave
-    const int frow = lane & 15, fg = lane >> 4;
-    const int WP = a.W + 2;
-    const int NP = a.rows_alloc >> 3;                  // DMA pieces per patch
-    const int buf_bytes = a.rows_alloc * 128;
-    // output tile of a strip: [position][64 channels] in the output type, 128-byte rows with the same XOR swizzle as the
-    // patches; every wave drops its 32 channels x 64 positions in, then the whole workgroup streams full rows out
-    char* otile = reinterpret_cast<char*>(smem) + 2 * buf_bytes;
-
-    // ---- weights -> registers (A operand: lane = (channel row, k-group))
-    // 288 registers of weights do not fit the 256 VGPRs next to the accumulators and fragments; left to itself hipcc parks
-    // the overflow in AGPRs and copies it back with one v_accvgpr_read PER REGISTER PER USE (282 copies for the 288 MFMAs of a
-    // strip: with one wave per SIMD every one of them is an issue slot the MFMA stream loses).  An MFMA can take its A
-    // operand straight from an AGPR: the empty asm below pins the first AGPR_FRAGS fragments there for the life of the
-    // workgroup, the rest stay in VGPRs, and the loop has no copies at all.
-    constexpr int AGPR_FRAGS = 44;
-    u32x4 wreg[9][2][NT4];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < NT4; ++i) {
-                const int ch = i * 16 + frow;
-                wreg[tap][kk][i] = *reinterpret_cast<const u32x4*>(a.w + ((ch * 9 + tap) * 64 + kk * 32 + fg * 8) * 2);
-                if ((tap * 2 + kk) * NT4 + i < AGPR_FRAGS) asm volatile("" : "+a"(wreg[tap][kk][i]));
-                else asm volatile("" : "+v"(wreg[tap][kk][i]));
-            }
-    // BN scale / shift wait in LDS (the weights take 144 VGPRs; a spill would put scratch loads - and their
-    // vmcnt(0), which also waits for the patch DMA in flight - into the strip loop)
-    float* bn_lds = reinterpret_cast<float*>(otile + OTROWS * 128);
-    if (tid < 64) { bn_lds[tid] = a.scale[tid]; bn_lds[64 + tid] = a.shift[tid]; }
-
-    // ---- patch producer.  LDS row j of a patch <-> padded pixel q = j - 1 : (r, c') = (q / WP, q % WP), input pixel
-    // (h0 + r - 1, c' - 1).  The (r, c') split and the source offset of every (piece, lane) are the same for every
-    // strip, so they are worked out once into an LDS table (entry = r << 24 | byte offset from pixel (h0 - 1, 0);
-    // all ones = halo column / beyond the patch); per strip a piece costs one table read, the row test and the DMA.
-    // Out-of-image lanes get an offset outside the buffer descriptor's range and the hardware writes zeros.
-    unsigned* dma_tab = reinterpret_cast<unsigned*>(bn_lds + 128);
-    const int dma_row = lane >> 3, dma_chunk = (lane & 7) ^ dma_row;      // LDS row inside a piece; source chunk
-    for (int g = wave; g < NP; g += 4) {
-        const int q = g * 8 + dma_row - 1;
-        const int r = q / WP, c = q - r * WP;
-        const bool ok = q >= 0 && r < R + 2 && c >= 1 && c <= a.W;
-        dma_tab[g * 64 + lane] = ok ? ((unsigned)r << 24) | (unsigned)((r * a.W + (c - 1)) * 128 + dma_chunk * 16) : 0xffffffffu;
-    }
-    __syncthreads();                                   // table + BN parameters visible to every wave
-    auto issue_patch = [&](int strip, int buf) {
-        const int frame = strip / a.strips_per_frame;
-        const int h0 = (strip - frame * a.strips_per_frame) * R;
-        // origin = pixel (h0 - 1, 0) of the frame (one row above the image for the first strip: those lanes are masked)
-        const i32x4 desc = make_desc(a.in + ((long long)frame * a.H + h0 - 1) * a.W * 128);
-        for (int g = wave; g < NP; g += 4) {
-            const unsigned e = dma_tab[g * 64 + lane];
-            const bool ok = e != 0xffffffffu && (unsigned)(h0 - 1 + (int)(e >> 24)) < (unsigned)a.H;
-            blds16(ok ? (e & 0xffffffu) : kOutOfRange, desc, 0, __builtin_amdgcn_readfirstlane(lds0 + buf * buf_bytes + g * 1024));
-        }
-    };
-
-    // output side: thread -> (row = position in the padded strip, 16-byte chunk) for each of its 4 row stores
-    int out_off[OTROWS * 8 / 256], out_row[OTROWS * 8 / 256];
-#pragma unroll
-    for (int j = 0; j < OTROWS * 8 / 256; ++j) {
-        const int p = (tid + 256 * j) >> 3, r = p / WP, c = p - r * WP;
-        const bool ok = r < R && c >= 1 && c <= a.W;                // halo columns / rows beyond the strip are not stored
-        out_row[j] = r;
-        out_off[j] = ok ? (r * a.W + (c - 1)) * 128 + (tid & 7) * 16 : -1;
-    }
-
-    // contiguous run of strips for this workgroup
-    const int G = gridDim.x, b = blockIdx.x;
-    const int s0 = (int)((long long)a.total_strips * b / G), s1 = (int)((long long)a.total_strips * (b + 1) / G);
-    if (s0 < s1) issue_patch(s0, 0);
-
-    // the workgroup streams the output tile of strip `sp` out as whole 128-byte rows, 16 bytes per lane
-    auto store_tile = [&](int sp) {
-        const int frame = sp / a.strips_per_frame;
-        const int h0 = (sp - frame * a.strips_per_frame) * R;
-        char* obase = a.out + ((long long)frame * a.H + h0) * a.W * 128;
-#pragma unroll
-        for (int j = 0; j < OTROWS * 8 / 256; ++j) {
-            if (out_off[j] >= 0 && h0 + out_row[j] < a.H) {
-                const int row = (tid + 256 * j) >> 3, chunk = tid & 7;
-                const u32x4 o = *reinterpret_cast<const u32x4*>(otile + row * 128 + ((chunk ^ (row & 7)) << 4));
-                __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(obase + out_off[j]));
-            }
-        }
-    };
-
-    for (int s = s0; s < s1; ++s) {
-        const int buf = (s - s0) & 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's pieces of strip s have landed
-        __builtin_amdgcn_s_barrier();                             // ... everybody's; and buffer buf^1 is no longer read
-        if (s + 1 < s1) issue_patch(s + 1, buf ^ 1);
-
-        const char* xb = reinterpret_cast<const char*>(smem) + buf * buf_bytes;
-        f32x4 acc[NT4][MT];
-#pragma unroll
-        for (int i = 0; i < NT4; ++i)
-#pragma unroll
-            for (int k = 0; k < MT; ++k) acc[i][k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // 18 (tap, k-half) steps of 16 MFMAs (4 channel tiles x 4 m-tiles); the 4 B fragments of step i+1 are read while
-        // step i multiplies.  One wave per SIMD: nothing else hides the LDS latency, but the whole register file is this
-        // wave's (288 weight registers + 64 accumulators + two fragment sets).  All MT m-tiles are multiplied
-        // unconditionally (a tile index beyond NT reads rows of the other buffer / the output tile - still inside this
-        // workgroup's LDS - and is never stored).
-        uint4 bf[2][MT];
-        auto read_step = [&](int step, uint4 (&b)[MT]) {
-            const int tap = step >> 1, kk = step & 1;
-            const int row = frow + (tap / 3) * WP + (tap % 3);    // + 16 * m-tile: does not change row & 7
-            const char* base = xb + row * 128 + (((kk * 4 + fg) ^ (row & 7)) << 4);
-#pragma unroll
-            for (int k = 0; k < MT; ++k) b[k] = *reinterpret_cast<const uint4*>(base + (mg + 4 * k) * (16 * 128));
-        };
-        read_step(0, bf[0]);
-#pragma unroll
-        for (int step = 0; step < 18; ++step) {
-            if (step + 1 < 18) read_step(step + 1, bf[(step + 1) & 1]);
-            if (step == 6 && s > s0) store_tile(s - 1);           // the previous strip's tile leaves under the MFMAs
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < MT; ++k)
-#pragma unroll
-                for (int i = 0; i < NT4; ++i) Mma<DT>::run(__builtin_bit_cast(uint4, wreg[step >> 1][step & 1][i]), bf[step & 1][k], acc[i][k]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-
-        // ---- epilogue: BN + ReLU + rounding in registers -> the strip's output tile in LDS (8 bytes per lane); the tile is
-        // stored to HBM during the NEXT strip's MFMA loop (store_tile above).  Which (row, chunk) a thread stores and
-        // where it lands relative to the strip never changes: worked out once (out_off / out_row).
-        f32x4 sc[NT4], sf[NT4];
-#pragma unroll
-        for (int i = 0; i < NT4; ++i) {
-            sc[i] = *reinterpret_cast<const f32x4*>(bn_lds + i * 16 + fg * 4);
-            sf[i] = *reinterpret_cast<const f32x4*>(bn_lds + 64 + i * 16 + fg * 4);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                  // every wave has read the previous tile out
-        __builtin_amdgcn_s_barrier();                                       // (raw barrier: the patch DMA stays in flight)
-#pragma unroll
-        for (int k = 0; k < MT; ++k) {
-            const int row = (mg + 4 * k) * 16 + frow;                       // position inside the padded strip
-#pragma unroll
-            for (int i = 0; i < NT4; ++i) {
-                f32x4 v = acc[i][k] * sc[i] + sf[i];
-                v[0] = relu_f(v[0]); v[1] = relu_f(v[1]); v[2] = relu_f(v[2]); v[3] = relu_f(v[3]);
-                const int ch = i * 16 + fg * 4;                             // 4 channels = 8 bytes: half a 16-byte chunk
-                Vec4<DT>::store(otile + row * 128 + (((ch >> 3) ^ (row & 7)) << 4) + (ch & 4) * 2, v);
-            }
-        }
-    }
-    if (s0 < s1) {                                                          // the last strip's tile
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        store_tile(s1 - 1);
-    }
-}
-
-// Round 3: the same strip walk on EIGHT waves, two per SIMD: wave = (channel half ng = wave >> 2, m-tile group mg = wave & 3),
-// 32 output channels x 4 m-tiles each: 144 weight registers (9 taps x 2 k-halves x 2 channel tiles), 32 accumulators, two
-// fragment sets - ~210 VGPRs, so two waves fit a SIMD.  With one wave per SIMD every non-MFMA instruction of the strip (patch DMA
-// issue: 26 us per launch, tile stores: 16, epilogue: 14, of 145) sat in the MFMA stream's way; with two, one wave's DMA issue /
+// The strip walk on EIGHT waves, two per SIMD: wave = (channel half ng = wave >> 2, m-tile group mg = wave & 3), 32 output
+// channels x 4 m-tiles each.  Rounds 1-2 ran FOUR waves, one per SIMD, each with all 64 channels (288 weight registers, VGPRs +
+// AGPRs): every non-MFMA instruction of the strip (patch DMA issue: 26 us per launch, tile stores: 16, epilogue: 14, of 145)
+// sat in the MFMA stream's way; with two waves per SIMD, one wave's DMA issue /
 // epilogue / stores run under the other's MFMAs.  The price: every B fragment is read by both channel halves (2x the LDS
 // fragment reads: ~125 B/clk of the CU's 256) and feeds 2 MFMAs instead of 4 - which is why the fragments of step s + 1 are read
 // a whole step (8 MFMAs) ahead of their use (round 1's 8-wave form read them right in front: a chain of LDS latencies, 58 %).
@@ -438,7 +266,7 @@ static Geom133 geom133(const af_conv_desc* d) {
     g.ok = true; g.strips_per_frame = (d->h + kStripRows - 1) / kStripRows;
     g.total_strips = d->n * d->t * g.strips_per_frame;
     g.rows_alloc = (((kStripRows + 2) * (d->w + 2) + 2 + 16) + 7) & ~7;
-    g.lds = 2 * g.rows_alloc * 128 + 16 * 16 * 128 + 128 * 4 + 2 * 512 * 16 + (g.rows_alloc / 8) * 64 * 4;   // (+ the last two taps' fragments: 8-wave form)
+    g.lds = 2 * g.rows_alloc * 128 + 16 * 16 * 128 + 128 * 4 + 2 * 512 * 16 + (g.rows_alloc / 8) * 64 * 4;   // (2 * 512 * 16: the last two taps' fragments)
     return g;
 }
 
@@ -446,14 +274,8 @@ template <int DT>
 static int launch_c133(const C133Args& a, int lds, hipStream_t stream) {
     const int g_num_cus = device_cus();
     const int grid = a.total_strips < g_num_cus ? a.total_strips : g_num_cus;
-    // AF_C64_WAVES=4: the round-1 / 2 form (one wave per SIMD, all 64 channels per wave) for A/B runs
-    if (env_int("AF_C64_WAVES", 8) == 4) {
-        AF_SET_MAX_LDS((&conv133_c64_kernel<DT, kStripRows>), kLdsBudget, "conv133");
-        hipLaunchKernelGGL((conv133_c64_kernel<DT, kStripRows>), dim3(grid), dim3(256), lds, stream, a);
-    } else {
-        AF_SET_MAX_LDS((&conv133_c64x2_kernel<DT, kStripRows>), kLdsBudget, "conv133");
-        hipLaunchKernelGGL((conv133_c64x2_kernel<DT, kStripRows>), dim3(grid), dim3(512), lds, stream, a);
-    }
+    AF_SET_MAX_LDS((&conv133_c64x2_kernel<DT, kStripRows>), kLdsBudget, "conv133");
+    hipLaunchKernelGGL((conv133_c64x2_kernel<DT, kStripRows>), dim3(grid), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("conv133_c64_kernel");
     return AF_OK;
 }

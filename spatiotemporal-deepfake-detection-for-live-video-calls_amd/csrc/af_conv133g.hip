@@ -43,7 +43,6 @@ struct C133GArgs {
     const float* shift2;
     const char* res;     // [frames][H][W][Cout2] or null
     int Cout2, relu2;
-    int stagger;         // waves 4-7 take the K loop's barrier half an MFMA group late (AF_G_STAGGER=0 for A/B runs)
 #ifdef AF_STAMPS
     unsigned long long* stamps;   // diagnostic build only (tools/stamps_lib.sh): [unit][wave][8] shader-clock / wall-clock stamps
     int dbg;                      // timing-only ablations of the K loop (AF_G_DBG; outputs are then garbage, addresses unchanged):
@@ -251,7 +250,7 @@ __global__ __launch_bounds__(512, 2) void conv133g_kernel(const C133GArgs a) {
         });
     };
 
-    const bool late = a.stagger && wave >= 4;
+    const bool late = wave >= 4;                       // waves 4-7 take the K loop's barrier half an MFMA group late
     constexpr bool PERSIST = !FUSEC;
     int epi_frame = 0, epi_h0 = 0;
     bool epi_more = false;
@@ -568,8 +567,7 @@ static int launch133g_n(const C133GArgs& a, hipStream_t stream) {
     AF_SET_MAX_LDS((&conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), kLdsBudget, "conv133g");
     // persistent workgroups (one per CU: the kernel uses all of LDS): unit blockIdx.x, + gridDim.x, ...
     const int units = a.frames * a.upf, cus = device_cus();
-    static const int persist = env_int("AF_G_PERSIST", 1);   // 0: one unit per workgroup (A/B runs)
-    const int grid = (FUSEC || !persist || units <= cus || cus <= 0) ? units : cus;
+    const int grid = (FUSEC || stamps_unit_per_workgroup() || units <= cus || cus <= 0) ? units : cus;
     hipLaunchKernelGGL((conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), dim3(grid), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("conv133g_kernel");
     return AF_OK;
@@ -641,8 +639,7 @@ static Geom133g geom311g(const af_conv_desc* d) {
 }
 
 bool conv311g_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    static const int enabled = env_int("AF_T311G", 1);
-    return enabled && !residual && (out_ld == 0 || out_ld % 8 == 0) && geom311g(d).ok;
+    return !residual && (out_ld == 0 || out_ld % 8 == 0) && geom311g(d).ok;
 }
 
 // the kernel's arguments for layer `d` cut into units as `g` says, without a fused c conv
@@ -655,7 +652,6 @@ static void fill133g(C133GArgs& a, const Geom133g& g, const af_conv_desc* d, con
     a.kslabs = d->cin / 64; a.relu = d->relu;
     a.inv_wp = 1.0f / (float)a.WP;
     a.w2 = nullptr; a.scale2 = a.shift2 = nullptr; a.res = nullptr; a.Cout2 = 0; a.relu2 = 0;
-    a.stagger = env_int("AF_G_STAGGER", 1);
     fill_stamps(a, "AF_G_DBG");
     a.out = (char*)out; a.out_ld = out_ld;
 }

@@ -458,13 +458,11 @@ int conv_ca_run(const af_conv_desc* dc, const void* inb, const void* wc, const v
     a.T = dc->t; a.HW = dc->h * dc->w; a.C = dc->cout; a.kslabs = dc->cout / 64;
     const GeomCA g = geom_ca(dc, in1 != nullptr);
     a.P = g.P; a.chunks = g.chunks; a.tiles = g.tiles;
-#ifdef AF_STAMPS
-    a.dbg = env_int("AF_CA_DBG", 0);
-#endif
+    fill_dbg(a, "AF_CA_DBG");
     const int cus = device_cus();
     const int blocks = a.tiles < cus ? a.tiles : cus;
     if (in1) return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, true, false>(a, blocks, stream); });
-    if (g.cwl && env_int("AF_CA_CWL", 1) != 0)                           // (AF_CA_CWL=0: the fragment loads, for A/B runs)
+    if (g.cwl)
         return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, false, true>(a, blocks, stream); });
     return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, false, false>(a, blocks, stream); });
 }

@@ -488,6 +488,22 @@ def test_asm_statement_mfmas_and_lds_reads_are_not_crowded_by_compiler_code():
     assert n_mfma >= 1000 and n_reads >= 500, (n_mfma, n_reads)     # the lint saw the loops it is meant for
 
 
+def test_kernel_sources_read_exactly_the_three_product_knobs():
+    """The shipped library reads three environment names, all in host-side selection code and all flipped by tests: AF_FORCE_VAR,
+    AF_IGEMM_224, AF_ABC_INNER32.  A kernel form is not chosen through the environment (two forms are compared as two libraries),
+    and the diagnostic build's knobs live in af_common.h under AF_STAMPS - so a new env_int / getenv of an AF_ name in a kernel
+    source is a decision to take here, not an accident.  Source text only: no compiler."""
+    csrc = os.path.join(ROOT, "spatiotemporal-deepfake-detection-for-live-video-calls_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert len(files) >= 20, files
+    names = {}
+    for f in files:
+        with open(os.path.join(csrc, f)) as fh:
+            for m in re.finditer(r'\b(?:env_int|getenv)\s*\(\s*"(AF_\w+)"', fh.read()):
+                names.setdefault(m.group(1), []).append(f)
+    assert set(names) == {"AF_FORCE_VAR", "AF_IGEMM_224", "AF_ABC_INNER32"}, names
+
+
 def test_stage_rows_host_helper_matches_numpy():
     """af_stage_rows_u8 is host code (the aligner's copy of the sampled crop rows into its pinned staging buffer): contiguous and
     strided rectangles against numpy, a refused rectangle (pitch smaller than the row)."""

@@ -1,6 +1,6 @@
-"""Run ON THE GPU BOX: device time of the frame-resident 1x3x3 `b` convs (s3 / s4 shapes, B = 16) through the C ABI, with the
-K loop's barrier stagger off / on (AF_G_STAGGER), 200 back-to-back launches each (a sustained-load figure: inside the model
-these launches alternate with memory-bound ones and run a few percent faster)."""
+"""Run ON THE GPU BOX: device time of the frame-resident 1x3x3 `b` convs (s3 / s4 shapes, B = 16) through the C ABI, four times
+200 back-to-back launches each (a sustained-load figure: inside the model these launches alternate with memory-bound ones and
+run a few percent faster)."""
 import os, sys, ctypes as C
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,8 +19,7 @@ for dt in ("bf16", "f16"):
         run = layer(d)
         flop = 2.0 * d.n * d.to * d.ho * d.wo * d.cout * d.cin * 9
         line = "%-22s %s" % (name, dt)
-        for stg in ("0", "1", "0", "1"):
-            os.environ["AF_G_STAGGER"] = stg
+        for _ in range(4):
             us = timeit(run, 200)
-            line += " | stagger=%s %6.1f us %5.0f TF" % (stg, us, flop / us * 1e-6)
+            line += " | %6.1f us %5.0f TF" % (us, flop / us * 1e-6)
         print(line, flush=True)

@@ -17,8 +17,7 @@ for name, d, units in CASES:
     run = layer(d)
     buf = torch.zeros(units * 8 * 8, dtype=torch.int64, device="cuda")
     os.environ["AF_STAMP_PTR"] = hex(buf.data_ptr())
-    for stg, dbg in (("0", 0), ("1", 0), ("1", 1), ("1", 2), ("1", 4), ("1", 20), ("1", 23), ("0", 23)):
-        os.environ["AF_G_STAGGER"] = stg
+    for dbg in (0, 1, 2, 4, 20, 23):
         os.environ["AF_G_DBG"] = str(dbg)
         us = timeit(run, 300)
         torch.cuda.synchronize()
@@ -27,5 +26,5 @@ for name, d, units in CASES:
         clk = tot / (s[:, :, 7] - s[:, :, 6]) * 0.1        # GHz: s_memrealtime ticks at 100 MHz
         med = lambda t, w: t[:, w].median().item()
         span = (s[:, :, 3].max() - s[:, :, 0].min()).item()
-        print("%s stagger=%s dbg=%-2d launch %.1f us | cycles (median over units) wave0: prologue %.0f loop %.0f epilogue %.0f total %.0f | wave4: %.0f %.0f %.0f %.0f | clock %.2f GHz | first start -> last end %.0f cycles"
-              % (name, stg, dbg, us, med(pro, 0), med(loop, 0), med(epi, 0), med(tot, 0), med(pro, 4), med(loop, 4), med(epi, 4), med(tot, 4), clk.median().item(), span), flush=True)
+        print("%s dbg=%-2d launch %.1f us | cycles (median over units) wave0: prologue %.0f loop %.0f epilogue %.0f total %.0f | wave4: %.0f %.0f %.0f %.0f | clock %.2f GHz | first start -> last end %.0f cycles"
+              % (name, dbg, us, med(pro, 0), med(loop, 0), med(epi, 0), med(tot, 0), med(pro, 4), med(loop, 4), med(epi, 4), med(tot, 4), clk.median().item(), span), flush=True)

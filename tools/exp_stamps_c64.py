@@ -16,12 +16,11 @@ units = 256
 buf = torch.zeros(units * 8 * 8, dtype=torch.int64, device="cuda")
 os.environ["AF_STAMP_PTR"] = hex(buf.data_ptr())
 names = ["prologue", "vmcnt", "barrier1", "issue", "mfma", "barrier2", "epilogue", "tail"]
-for form, dbg in (("8", 0), ("8", 0), ("8", 1), ("8", 2), ("8", 4), ("8", 7)):
+for dbg in (0, 0, 1, 2, 4, 7):
     os.environ["AF_C64_DBG"] = str(dbg)
-    os.environ["AF_C64_WAVES"] = form
     us = timeit(run, 200)
     torch.cuda.synchronize()
     s = buf.cpu().view(units, 8, 8).double()
     for w in (0, 4):
-        print("form=" + form + " dbg=%d launch %.1f us wave %d: " % (dbg, us, w) + "  ".join("%s %.0f" % (n, s[:, w, i].median().item()) for i, n in enumerate(names))
+        print("dbg=%d launch %.1f us wave %d: " % (dbg, us, w) + "  ".join("%s %.0f" % (n, s[:, w, i].median().item()) for i, n in enumerate(names))
               + "  | total %.0f cycles" % s[:, w, :].sum(dim=1).median().item(), flush=True)

@@ -21,7 +21,6 @@ if [ "$PART" = "kernels" ]; then
   AF_HIP_LIB=$ROOT/$PKG/libafhip_stamps.so timeout -k 10 400 python3 tools/exp_stamps_igemm.py > $OUT/stamps_igemm.log 2>&1; echo "stamps igemm rc=$?"
   AF_HIP_LIB=$ROOT/$PKG/libafhip_stamps.so timeout -k 10 300 python3 tools/exp_stamps_c64.py > $OUT/stamps_c64.log 2>&1; echo "stamps c64 rc=$?"
   AF_HIP_LIB=$ROOT/$PKG/libafhip_stamps.so timeout -k 10 300 python3 tools/exp_ca_dbg.py > $OUT/ca_ablations.log 2>&1; echo "ca ablations rc=$?"
-  timeout -k 10 300 python3 tools/exp_ca_ab.py > $OUT/ca_cwl_ab.log 2>&1; echo "ca cwl a/b rc=$?"
   timeout -k 10 300 python3 tools/exp_b133g.py > $OUT/b133g_new.log 2>&1
   # (the A/B against the round-3 library - tools/ab_lib.sh with libafhip_prev.so - was run in the first half of the round; that library
   #  speaks ABI 3 and no longer loads beside the ABI-4 host code)
