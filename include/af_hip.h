@@ -249,6 +249,15 @@ int af_conv3d_cpa_bn_act(const af_conv_desc* dc, const void* in_b, const void* w
 int af_conv_variant(const af_conv_desc* d, const af_conv_desc* d2);
 const char* af_conv_variant_name(int variant);
 
+/* what that launch is cut into: *units = the work units of the layer (strips of conv133, tiles of conv311 / conv111 / a conv_igemm
+ * tile, units of conv133g / conv311g), *workgroups = the grid the launch has on the current device (256 CUs assumed where there is
+ * none).  The specialised kernels are persistent - workgroup b walks units b, b + workgroups, ... (conv133: a contiguous range) - so
+ * units / workgroups is how many units a workgroup runs one behind the other; a conv_igemm tile launches one workgroup per tile
+ * (times the K ranges of a split, which depend on the caller's workspace and are not counted).  Both numbers come from the
+ * launchers' own geometry: a test sizes its input from them instead of restating it.  Returns af_conv_variant(d, d2), or < 0
+ * (the narrow-layer path is not cut into units). */
+int af_conv_work_units(const af_conv_desc* d, const af_conv_desc* d2, int64_t* units, int* workgroups);
+
 /* nn.MaxPool3d on NDHWC (stem_helper.py:168-170 [1,3,3]/[1,2,2]/[0,1,1];
  * video_model_builder.py:474-480 [2,1,1]/[2,1,1]); padding behaves as -inf. */
 int af_maxpool3d(const af_pool_desc* d, const void* in, void* out, void* stream);

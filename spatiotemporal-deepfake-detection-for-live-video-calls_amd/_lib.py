@@ -211,6 +211,7 @@ ABI = {
                             + [C.POINTER(ConvDesc), C.c_void_p] + [C.c_void_p, C.c_int, C.c_void_p]),
     "af_conv_variant": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
     "af_conv_variant_name": (C.c_char_p, [C.c_int]),
+    "af_conv_work_units": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "af_maxpool3d": (C.c_int, [C.POINTER(PoolDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "af_avgpool_fc": (C.c_int, [C.POINTER(PoolDesc)] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
     "af_avgpool_fc_scores": (C.c_int, [C.POINTER(PoolDesc)] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4),

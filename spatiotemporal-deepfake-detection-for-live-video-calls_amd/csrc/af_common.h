@@ -246,6 +246,13 @@ int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, con
                 const void* w2_packed, const float* scale, const float* shift, const void* residual, void* out, int out_ld,
                 hipStream_t stream);
 
+// af_conv_work_units: the work units (strips, tiles, units) of a layer that takes the path and the grid its *_run function launches
+void conv133_work(const af_conv_desc* d, long long* units, int* workgroups);
+void conv133g_work(const af_conv_desc* d, long long* units, int* workgroups);
+void conv311g_work(const af_conv_desc* d, long long* units, int* workgroups);
+void conv311_work(const af_conv_desc* d, long long* units, int* workgroups);
+void conv111_work(const af_conv_desc* d, const af_conv_desc* d2, long long* units, int* workgroups);
+
 // One-time PER-DEVICE setup.  hipFuncSetAttribute and the CU count belong to a device, and one process may drive several
 // (one engine per device): every "done once" flag is therefore indexed by the current device ordinal.
 constexpr int kMaxDevices = 64;

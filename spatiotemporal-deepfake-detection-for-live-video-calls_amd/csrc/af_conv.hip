@@ -717,10 +717,12 @@ __global__ __launch_bounds__(WN * WM * KS * 64, MINW) void conv_igemm_kernel(con
     conv_igemm_tile<DT, BN, BM, WN, WM, KS, NSTAGE, MINW, DUAL, SPLITK, BMR>(a, blockIdx.x, gridDim.x);
 }
 
+// tiles of a conv_igemm launch = its grid's x extent (y: the K ranges of a split): row tiles of `bmr` positions x channel tiles
+static long long igemm_tiles(long long M, int bmr, int tiles_n) { return (M + bmr - 1) / bmr * tiles_n; }
+
 template <int DT, int BN, int BM, int WN, int WM, int KS, int MINW, bool DUAL, int NSTAGE = 3, bool SPLITK = false, int BMR = BM>
 static int launch(const ConvArgs& a, hipStream_t stream) {
-    const long long tiles_m = (a.M + BMR - 1) / BMR;
-    const long long blocks = tiles_m * a.tiles_n;
+    const long long blocks = igemm_tiles(a.M, BMR, a.tiles_n);
     if (blocks <= 0 || blocks > 0x7fffffffLL) return set_error(AF_ERR_ARG, "conv: grid of %lld workgroups", blocks);
     // LDS actually needed: the ring slots this layer's K loop touches, or the epilogue patches
     constexpr int TMv = BMR / WM / 16;
@@ -900,6 +902,31 @@ static int dispatch(ConvArgs& a, const ConvPad& p, int v, hipStream_t stream) {
 extern "C" int af_conv_variant(const af_conv_desc* d, const af_conv_desc* d2) {
     AF_REQUIRE(d && d->cout > 0 && d->cin > 0 && af::dtype_ok(d->dtype), "conv_variant: bad descriptor");
     return af::conv_path(d, d2, nullptr, 0, af::conv_pad(d, d2));
+}
+
+extern "C" int af_conv_work_units(const af_conv_desc* d, const af_conv_desc* d2, int64_t* units, int* workgroups) {
+    using namespace af;
+    AF_REQUIRE(d && units && workgroups && d->cout > 0 && d->cin > 0 && dtype_ok(d->dtype), "conv_work_units: bad argument");
+    AF_REQUIRE(d->n > 0 && d->to > 0 && d->ho > 0 && d->wo > 0, "conv_work_units: bad dims");
+    const ConvPad p = conv_pad(d, d2);
+    const int v = conv_path(d, d2, nullptr, 0, p);
+    long long u = 0;
+    int g = 0;
+    switch (v) {
+        case VAR_C133: conv133_work(d, &u, &g); break;
+        case VAR_C133G: conv133g_work(d, &u, &g); break;
+        case VAR_C311G: conv311g_work(d, &u, &g); break;
+        case VAR_C311: conv311_work(d, &u, &g); break;
+        case VAR_C111: conv111_work(d, d2, &u, &g); break;
+        case VAR_SMALL: return set_error(AF_ERR_ARG, "conv_work_units: the narrow-layer path is not cut into units");
+        default: {
+            u = igemm_tiles(p.M, variant_bm(v), p.coutp / variant_bn(v));
+            AF_REQUIRE(u > 0 && u <= 0x7fffffffLL, "conv_work_units: grid of %lld workgroups", u);
+            g = (int)u;
+        }
+    }
+    *units = u; *workgroups = g;
+    return v;
 }
 
 extern "C" const char* af_conv_variant_name(int variant) {

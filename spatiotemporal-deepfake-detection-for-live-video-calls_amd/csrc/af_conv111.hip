@@ -337,6 +337,17 @@ static Geom111 geom111(const af_conv_desc* d, const af_conv_desc* d2) {
     return g;
 }
 
+// persistent grid: device_cus() / ncol streams of tiles (at most one per tile), each ncol workgroups wide
+static int grid111(const Geom111& g) {
+    int streams = device_cus() / g.ncol;
+    if (streams > g.tiles) streams = g.tiles;
+    return streams * g.ncol;
+}
+void conv111_work(const af_conv_desc* d, const af_conv_desc* d2, long long* units, int* workgroups) {
+    const Geom111 g = geom111(d, d2);
+    *units = g.tiles; *workgroups = grid111(g);
+}
+
 bool conv111_applies(const af_conv_desc* d, const af_conv_desc* d2, const void* residual, int out_ld) {
     if (d2 && residual) return false;
     return geom111(d, d2).ok;
@@ -351,9 +362,7 @@ int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, con
     a.Cin = d->cin; a.Cin2 = d2 ? d2->cin : 0; a.Cout = d->cout; a.out_ld = out_ld; a.relu = d->relu;
     const Geom111 g = geom111(d, d2);
     a.ncol = g.ncol; a.T = d->t; a.HW = g.HW; a.chunks = g.chunks; a.M = g.M; a.tiles = g.tiles;
-    int streams = device_cus() / a.ncol;
-    if (streams > a.tiles) streams = a.tiles;
-    const int blocks = streams * a.ncol;
+    const int blocks = grid111(g);
     return with_dtype16(d->dtype, [&](auto dt) {
         if (d2) return launch111<dt, 1, 1, false, false>(a, blocks, stream);
         if (d->tpool) return residual ? launch111<dt, 1, 0, true, true>(a, blocks, stream) : launch111<dt, 1, 0, true, false>(a, blocks, stream);

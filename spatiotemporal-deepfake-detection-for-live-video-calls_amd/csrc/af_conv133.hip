@@ -270,10 +270,19 @@ static Geom133 geom133(const af_conv_desc* d) {
     return g;
 }
 
+// persistent grid: one workgroup per CU, each a contiguous range of strips
+static int grid_c133(int total_strips) {
+    const int g_num_cus = device_cus();
+    return total_strips < g_num_cus ? total_strips : g_num_cus;
+}
+void conv133_work(const af_conv_desc* d, long long* units, int* workgroups) {
+    const Geom133 g = geom133(d);
+    *units = g.total_strips; *workgroups = grid_c133(g.total_strips);
+}
+
 template <int DT>
 static int launch_c133(const C133Args& a, int lds, hipStream_t stream) {
-    const int g_num_cus = device_cus();
-    const int grid = a.total_strips < g_num_cus ? a.total_strips : g_num_cus;
+    const int grid = grid_c133(a.total_strips);
     AF_SET_MAX_LDS((&conv133_c64x2_kernel<DT, kStripRows>), kLdsBudget, "conv133");
     hipLaunchKernelGGL((conv133_c64x2_kernel<DT, kStripRows>), dim3(grid), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("conv133_c64_kernel");

@@ -555,6 +555,13 @@ struct Geom133g {
     int slots;           // weight ring slots: 3 where the two patches leave room for them (s4: 2 x 31 KB + 3 x 32 KB), else 2
 };
 
+// persistent workgroups (one per CU: the kernel uses all of LDS): unit blockIdx.x, + gridDim.x, ...; the fused form and the
+// diagnostic build's per-unit stamps give every unit a workgroup of its own
+static int grid133g(int units, bool fusec) {
+    const int cus = device_cus();
+    return (fusec || stamps_unit_per_workgroup() || units <= cus || cus <= 0) ? units : cus;
+}
+
 template <int DT, int WN, int WM, bool FUSEC, int MT, int MAXP, int NSLOT, bool TEMPORAL = false>
 static int launch133g_n(const C133GArgs& a, hipStream_t stream) {
     if (a.prows > kPieceRows * MAXP) return set_error(AF_ERR_ARG, "conv133g: %d patch rows for %d pieces per wave", a.prows, MAXP);
@@ -565,9 +572,7 @@ static int launch133g_n(const C133GArgs& a, hipStream_t stream) {
     if (lds < lds_e) lds = lds_e;
     if (lds > kLdsBudget) return set_error(AF_ERR_ARG, "conv133g: %d bytes of LDS needed", lds);
     AF_SET_MAX_LDS((&conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), kLdsBudget, "conv133g");
-    // persistent workgroups (one per CU: the kernel uses all of LDS): unit blockIdx.x, + gridDim.x, ...
-    const int units = a.frames * a.upf, cus = device_cus();
-    const int grid = (FUSEC || stamps_unit_per_workgroup() || units <= cus || cus <= 0) ? units : cus;
+    const int grid = grid133g(a.frames * a.upf, FUSEC);
     hipLaunchKernelGGL((conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), dim3(grid), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("conv133g_kernel");
     return AF_OK;
@@ -615,6 +620,13 @@ bool conv133g_applies(const af_conv_desc* d, const void* residual, int out_ld) {
     return !residual && (out_ld == 0 || out_ld % 8 == 0) && geom133g(d).ok;
 }
 
+// units and workgroups of the launch `g` describes (af_conv_work_units)
+static void work133g(const Geom133g& g, long long* units, int* workgroups) {
+    *units = (long long)g.frames * g.upf;
+    *workgroups = grid133g(g.frames * g.upf, false);
+}
+void conv133g_work(const af_conv_desc* d, long long* units, int* workgroups) { work133g(geom133g(d), units, workgroups); }
+
 // ---- TEMPORAL mode: 3x1x1 / stride 1 / pad (1,0,0) convs into 128 / 256 channels (the `a` convs of s3 / s4) on the same kernel.
 // P = pixels per unit so that T x P is the kernel's position count (224 for 256 channels, 448 for 128)
 static Geom133g geom311g(const af_conv_desc* d) {
@@ -641,6 +653,8 @@ static Geom133g geom311g(const af_conv_desc* d) {
 bool conv311g_applies(const af_conv_desc* d, const void* residual, int out_ld) {
     return !residual && (out_ld == 0 || out_ld % 8 == 0) && geom311g(d).ok;
 }
+
+void conv311g_work(const af_conv_desc* d, long long* units, int* workgroups) { work133g(geom311g(d), units, workgroups); }
 
 // the kernel's arguments for layer `d` cut into units as `g` says, without a fused c conv
 static void fill133g(C133GArgs& a, const Geom133g& g, const af_conv_desc* d, const void* in, const void* w_packed, const float* scale,

@@ -199,6 +199,16 @@ static Geom311 geom311(const af_conv_desc* d) {
     return g;
 }
 
+// persistent grid: one workgroup per CU, tile blockIdx.x, + gridDim.x, ...
+static int grid311(int tiles) {
+    const int cus = device_cus();
+    return tiles < cus ? tiles : cus;
+}
+void conv311_work(const af_conv_desc* d, long long* units, int* workgroups) {
+    const Geom311 g = geom311(d);
+    *units = g.tiles; *workgroups = grid311(g.tiles);
+}
+
 // true iff this layer takes the time-tiled path (also used by af_conv_variant)
 bool conv311_applies(const af_conv_desc* d, const void* residual, int out_ld) {
     return !residual && geom311(d).ok;
@@ -212,8 +222,7 @@ int conv311_run(const af_conv_desc* d, const void* in, const void* w_packed, con
     a.T = d->t; a.HW = d->h * d->w; a.Cin = d->cin; a.kpt = g.kpt;
     a.P = g.P; a.chunks = g.chunks; a.tiles = g.tiles;
     a.relu = d->relu; a.out_ld = out_ld;
-    const int cus = device_cus();                        // persistent grid: one workgroup per CU
-    const int blocks = a.tiles < cus ? a.tiles : cus;
+    const int blocks = grid311(a.tiles);
     if (d->cout == 128) return with_dtype16(d->dtype, [&](auto dt) { return launch311<dt, 128>(a, blocks, stream); });
     return with_dtype(d->dtype, [&](auto dt) { return launch311<dt, 64>(a, blocks, stream); });
 }

@@ -91,6 +91,31 @@ def conv_bn_act(x_ndhwc, w_oidhw, scale, shift, stride, pad, relu, dtype, residu
     return out
 
 
+def conv_work_units(shape_ndhwc, cout, kernel, dtype, pad=(0, 0, 0), relu=True):
+    """(variant, work units, workgroups) of the af_conv3d_bn_act launch of this layer (stride 1) over an input of shape (N,T,H,W,C):
+    the library's own answer (af_conv_work_units), no tensor needed"""
+    L = lib()
+    d = _desc(shape_ndhwc, cout, kernel, dtype, pad=pad, relu=relu)
+    units, groups = C.c_int64(0), C.c_int(0)
+    v = L.lib.af_conv_work_units(C.byref(d), None, C.byref(units), C.byref(groups))
+    L.check(min(v, 0), "conv_work_units")
+    assert v == L.lib.af_conv_variant(C.byref(d), None)
+    return v, units.value, groups.value
+
+
+def compare(got, want, tol, what):
+    """NaN masks equal, infinities equal, the finite rest within tol * max|finite want|"""
+    nan_w = torch.isnan(want)
+    assert torch.equal(torch.isnan(got), nan_w), "%s: %d NaN in the output, %d in the reference" % (what, int(torch.isnan(got).sum()), int(nan_w.sum()))
+    inf_w = torch.isinf(want)
+    assert torch.equal(torch.isinf(got), inf_w) and torch.equal(got[inf_w], want[inf_w]), "%s: infinities differ" % what
+    fin = ~(nan_w | inf_w)
+    ref = want[fin].abs().max().item() + 1e-9
+    err = (got[fin] - want[fin]).abs().max().item()
+    print("%s: max|d| / max|want| = %.3e (tolerance %.3e)" % (what, err / ref, tol))
+    assert err <= tol * ref, "%s: max|d|=%.3e vs max|ref|=%.3e, tolerance %.3e" % (what, err, ref, tol)
+
+
 def conv_bc(x_ndhwc, wb_oidhw, bn_b, wc_oidhw, bn_c, residual, dtype):
     """relu(bn_c(conv1x1x1(relu(bn_b(conv1x3x3(x))))) + residual) as one af_conv3d_bc_bn_act launch; None if the library
     does not fuse this pair (af_conv_bc_fusable)."""

@@ -204,17 +204,7 @@ def _bn_layout(prefix, ch):
     return [(prefix + s, (ch,), "float32") for s in (".weight", ".bias", ".running_mean", ".running_var")]
 
 
-def _compare(got, want, tol, what):
-    """NaN masks equal, infinities equal, the finite rest within tol * max|finite want|"""
-    nan_w = torch.isnan(want)
-    assert torch.equal(torch.isnan(got), nan_w), "%s: %d NaN in the output, %d in the reference" % (what, int(torch.isnan(got).sum()), int(nan_w.sum()))
-    inf_w = torch.isinf(want)
-    assert torch.equal(torch.isinf(got), inf_w) and torch.equal(got[inf_w], want[inf_w]), "%s: infinities differ" % what
-    fin = ~(nan_w | inf_w)
-    ref = want[fin].abs().max().item() + 1e-9
-    err = (got[fin] - want[fin]).abs().max().item()
-    print("%s: max|d| / max|want| = %.3e (tolerance %.3e)" % (what, err / ref, tol))
-    assert err <= tol * ref, "%s: max|d|=%.3e vs max|ref|=%.3e, tolerance %.3e" % (what, err, ref, tol)
+_compare = hh.compare          # NaN masks equal, infinities equal, the finite rest within tol * max|finite want|
 
 
 def _cases_for(dtype):

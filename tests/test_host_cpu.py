@@ -787,3 +787,51 @@ def test_conv_matrix_covers_what_ships(monkeypatch):
     assert len(shipped) >= 200, len(shipped)
     missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
     assert not missing, "%d shipped tile x form pairs without a matrix case:\n%s" % (len(missing), "\n".join(missing))
+
+
+def test_persist_matrix_covers_what_ships(monkeypatch):
+    """every conv the three networks launch on a persistent specialised kernel (conv311, conv133g, conv311g: variants 8, 11, 13) at
+    batch 1..32 - default fusions, and the four fusion switches off - is a case of tests/test_hip_conv_persist.py, which runs it
+    against fp64 on the GPU at the same number of rounds of units per workgroup: key = (variant, dtype, cout, kernel, K slabs, T of
+    the temporal kernels or (h, w) of the spatial ones, rounds class).  (units, workgroups) come from af_conv_work_units, which
+    answers for 256 CUs where there is no device."""
+    import ctypes as C
+    import importlib.util
+    from af_mi355x import engine
+    from af_mi355x._lib import lib
+    spec_ = importlib.util.spec_from_file_location("test_hip_conv_persist", os.path.join(ROOT, "tests", "test_hip_conv_persist.py"))
+    matrix = importlib.util.module_from_spec(spec_)
+    spec_.loader.exec_module(matrix)
+    covered = {matrix.case_key(c, dt) for c in matrix.CASES for dt in c.dtypes if c.form != "nonfinite"}
+    monkeypatch.delenv("AF_FORCE_VAR", raising=False)
+    specs = {"i3d_r50": arch.i3d_r50_spec(), "slowfast_r50": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
+    rgb3 = {"i3d_r50": {specs["i3d_r50"].stem.conv}, "slowfast_r50": {specs["slowfast_r50"].stems[0].conv}, "ftcn_tt": set()}
+    shipped = {}
+    for fusions in (True, False):
+        for name in ("AF_FUSE_BC", "AF_FUSE_CA", "AF_FUSE_CPA", "AF_FUSE_ABC"):
+            if fusions:
+                monkeypatch.delenv(name, raising=False)
+            else:
+                monkeypatch.setenv(name, "0")
+        for net, spec in specs.items():
+            for dtype in ("f32", "bf16", "f16"):
+                for batch in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32):
+                    p = engine.plan_network(spec, dtype, batch, (spec.num_frames, spec.crop, spec.crop), rgb3[net] if dtype != "f32" else set())
+                    for e in p.entries:
+                        if e["kind"] != "conv":
+                            continue
+                        cv = e["cv"]
+                        d = p.desc(cv, e["din"], e["dout"], int(e.get("tpool") or 0))
+                        v = lib.af_conv_variant(C.byref(d), None)
+                        if v not in (8, 11, 13):
+                            continue
+                        units, groups = C.c_int64(0), C.c_int(0)
+                        assert lib.af_conv_work_units(C.byref(d), None, C.byref(units), C.byref(groups)) == v
+                        assert 0 < groups.value <= 256 and groups.value == min(units.value, 256)
+                        key = (v, dtype, cv.cout, tuple(cv.kernel), matrix.kslabs(cv.cin, dtype), d.t if cv.kernel[1] == 1 else (d.h, d.w),
+                               matrix.rounds_class(units.value, groups.value))
+                        shipped.setdefault(key, "%s batch %d%s: %d -> %d %s, %d units on %d workgroups" % (
+                            net, batch, "" if fusions else " unfused", cv.cin, cv.cout, tuple(cv.kernel), units.value, groups.value))
+    assert len(shipped) >= 60, len(shipped)
+    missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
+    assert not missing, "%d shipped persistent-kernel launches without a case:\n%s" % (len(missing), "\n".join(missing))
