@@ -559,6 +559,60 @@ typedef struct af_yuv_item {
 int af_yuv420_plan_u8(const af_yuv_frame* frames, int n, const af_store_ref* stores, int n_stores, af_yuv_item* items);
 int af_yuv420_to_rgb_u8(const af_yuv_item* items, int n, void* stream);
 
+/* ---- cv2.resize of resident frames (added within ABI 6) -----------------------------------------------------------------------
+ * cv2.resize(frame, (dw, dh)) with the default INTER_LINEAR on frames that sit in frame stores: one launch resizes up to
+ * AF_RESIZE_MAX_FRAMES frames that may differ in store, size, destination and destination size - the step in front of a detector
+ * that runs on downscaled frames (FaceDetector.scale_detect, demo2.py's yunet_res).  Arithmetic: the plain C++ path of OpenCV 4.x
+ * resize.cpp for 8-bit images - a copy at equal size, (a + b + c + d + 2) >> 2 at exactly 2x in both axes, else the 11-bit
+ * fixed-point bilinear form - stated in csrc/af_resize.hip and equal, byte for byte, to the numpy restatement tests/resize_ref.py
+ * (unpinned against cv2 itself, absent where this is built; an IPP-enabled OpenCV may differ from the plain path).  Channels are
+ * treated alike: a store's byte order passes through.
+ *
+ * af_resize_job (host): frame `frame` of stores[store] -> dh rows of dw pixels at the DEVICE pointer dst, rows dst_pitch bytes apart.
+ * af_resize_table_bytes: an upper bound of the table's size for these jobs (-1: n or a size out of range).
+ * af_resize_plan_u8 (host only, no device work) fills `table`, a caller-owned HOST buffer (pinned, for an asynchronous copy), 8-byte
+ * aligned, and sets *used_bytes, the bytes to copy to the device.  Layout: af_resize_header; n af_resize_item (absolute addresses,
+ * pitches, sizes, mode, byte offsets of the coefficient tables from the table's start, so the table may be copied anywhere); then
+ * one af_resize_coef table per distinct (w -> dw) and per distinct (h -> dh) of the bilinear jobs, shared by the jobs of one
+ * geometry.  The coefficients are computed here, on the host, in the fp64 / fp32 steps OpenCV takes.
+ * AF_ERR_ARG: more than AF_RESIZE_MAX_FRAMES jobs, a store or frame index out of range, a bad store, dw or dh outside
+ * [1, AF_RESIZE_MAX_SIDE], a destination pitch below 3 * dw, a null pointer, a table buffer that is too small.  A refused table's
+ * header is stamped (kind = -1) so that no launch takes it.
+ * af_resize_frames_u8 launches over a DEVICE copy of the table.  It trusts the table as the window launches trust theirs; the
+ * kernel compares the header with n and writes nothing on a mismatch (the call still returns AF_OK).  Reads stay inside
+ * [frame, frame + row_pitch * (h - 1) + 3 * w); writes are exactly dh rows of 3 * dw bytes, nothing in the pitch padding. */
+#define AF_RESIZE_MAX_FRAMES 64
+#define AF_RESIZE_MAX_SIDE 8192
+#define AF_RESIZE_KIND 0x315a5352              /* "RSZ1" */
+enum af_resize_mode { AF_RESIZE_COPY = 0, AF_RESIZE_AREA2 = 1, AF_RESIZE_LINEAR = 2 };
+typedef struct af_resize_job {
+    int32_t store, frame;
+    void* dst;
+    int64_t dst_pitch;
+    int32_t dh, dw;
+} af_resize_job;
+typedef struct af_resize_header {
+    int32_t kind, n, total_tiles, used_bytes;
+    int32_t first_tile[AF_RESIZE_MAX_FRAMES + 1];      /* prefix sum of the jobs' tiles; [n ..] = total_tiles */
+    int32_t reserved[3];
+} af_resize_header;
+typedef struct af_resize_item {
+    const void* src;                                   /* first byte of the source frame */
+    void* dst;
+    int32_t src_pitch, dst_pitch;
+    int32_t h, w, dh, dw;
+    int32_t mode, runs_x;                              /* af_resize_mode; runs of 4 pixels per destination row */
+    int32_t xtab, ytab;                                /* bilinear: byte offsets of the dw- and dh-entry coefficient tables */
+} af_resize_item;
+typedef struct af_resize_coef {
+    int32_t idx;                                       /* first tap: column (clamped to [0, w - 1]) or row (-1 .. h - 1, clipped by the kernel) */
+    int16_t a0, a1;                                    /* weights of the first and second tap, 11 fractional bits */
+} af_resize_coef;
+int64_t af_resize_table_bytes(const af_resize_job* jobs, int n);
+int af_resize_plan_u8(const af_resize_job* jobs, int n, const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes,
+                      int64_t* used_bytes);
+int af_resize_frames_u8(const void* table_dev, int n, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,

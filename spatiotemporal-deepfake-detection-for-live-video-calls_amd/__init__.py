@@ -12,9 +12,9 @@ def __getattr__(name):
     if name in ("LiveCall", "RealtimeCall", "CallServer", "FaceQuality"):
         from . import live
         return getattr(live, name)
-    if name == "YuvFrame":
+    if name in ("YuvFrame", "FrameResizer"):
         from . import frames
-        return frames.YuvFrame
+        return getattr(frames, name)
     if name == "ByteTracker":
         from . import tracker
         return tracker.ByteTracker

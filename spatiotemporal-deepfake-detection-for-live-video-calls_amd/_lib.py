@@ -87,6 +87,32 @@ class YuvItem(C.Structure):
 YUV_MAX_FRAMES, YUV_RUN, YUV_TILE = 64, 8, 256
 
 
+class ResizeJob(C.Structure):
+    """af_resize_job: frame `frame` of store `store` -> dh rows of dw pixels at the device pointer dst"""
+    _fields_ = [("store", C.c_int32), ("frame", C.c_int32), ("dst", C.c_void_p), ("dst_pitch", C.c_int64), ("dh", C.c_int32), ("dw", C.c_int32)]
+
+
+RESIZE_MAX_FRAMES, RESIZE_MAX_SIDE, RESIZE_KIND = 64, 8192, 0x315a5352
+RESIZE_COPY, RESIZE_AREA2, RESIZE_LINEAR = 0, 1, 2
+
+
+class ResizeHeader(C.Structure):
+    """af_resize_header: the first bytes of the table af_resize_plan_u8 fills"""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("total_tiles", C.c_int32), ("used_bytes", C.c_int32),
+                ("first_tile", C.c_int32 * (RESIZE_MAX_FRAMES + 1)), ("reserved", C.c_int32 * 3)]
+
+
+class ResizeItem(C.Structure):
+    """af_resize_item: one job as the kernel reads it"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_pitch", C.c_int32), ("dst_pitch", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("dh", C.c_int32), ("dw", C.c_int32), ("mode", C.c_int32), ("runs_x", C.c_int32), ("xtab", C.c_int32), ("ytab", C.c_int32)]
+
+
+class ResizeCoef(C.Structure):
+    """af_resize_coef: first tap and the two 11-bit weights of one destination column or row"""
+    _fields_ = [("idx", C.c_int32), ("a0", C.c_int16), ("a1", C.c_int16)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n", "t", "h", "w", "c", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw", "to", "ho", "wo", "dtype",
@@ -199,6 +225,9 @@ ABI = {
     "af_face_quality_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "af_yuv420_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "af_yuv420_to_rgb_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "af_resize_table_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
+    "af_resize_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "af_resize_frames_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6

@@ -315,6 +315,60 @@ class YuNet(DeviceModel):
                         C.c_void_p(counts.data_ptr()), C.c_void_p(rawt.data_ptr() if raw else None), C.c_void_p(cur.cuda_stream)], None)
         return (rows, counts, rawt) if raw else (rows, counts)
 
+    # ---- detection on downscaled frames
+    @staticmethod
+    def scale_rows(rows, sx: float, sy: float) -> np.ndarray:
+        """(n, 15) rows found on a resized frame -> the full frame's, as demo2.py:196-208 scales them: float64; x, w and the
+        landmark x's times `sx`, y, h and the landmark y's times `sy`, the score untouched"""
+        return np.asarray(rows, dtype=np.float64).reshape(-1, 15) * np.array([sx, sy] * 7 + [1.0], dtype=np.float64)
+
+    def _resizer(self, device):
+        from .frames import FrameResizer
+        resizers = self.__dict__.setdefault("_resizers", {})
+        if device not in resizers:
+            resizers[device] = FrameResizer(device)
+        return resizers[device]
+
+    def detect_resized(self, frames, size, conf: Optional[float] = None, nms: Optional[float] = None, top_k: Optional[int] = None):
+        """``detect`` on frames resized on the device to ``size`` = (dw, dh) with cv2.resize's arithmetic (``frames.FrameResizer``),
+        the rows scaled back to each frame's own size: what demo2.py does with ``--yunet_res``.  `frames`: a (B, H, W, 3) uint8
+        device tensor, or a list of (H, W, 3) device views / ``(FrameStore, slot)`` pairs that may differ in size - they share one
+        resize launch and one detector call per 64.  Returns a list of (n, 15) **float64** numpy arrays, one per frame
+        (``scale_rows`` with sx = W / dw, sy = H / dh, on the host); this call waits for the device once."""
+        import torch
+        if isinstance(frames, torch.Tensor):
+            if frames.dim() != 4:
+                raise ValueError("frames must be (B, H, W, 3) uint8, got %s" % (tuple(frames.shape),))
+            dev, shapes = frames.device, [tuple(frames.shape[1:3])] * frames.shape[0]
+        else:
+            frames = list(frames)
+            if not frames:
+                return []
+            first = frames[0] if isinstance(frames[0], torch.Tensor) else frames[0][0]
+            dev = first.device
+            shapes = [tuple(f.shape[:2]) if isinstance(f, torch.Tensor) else tuple(f[0].shape[:2]) for f in frames]
+        dw, dh = int(size[0]), int(size[1])
+        out = []
+        with torch.cuda.device(dev):
+            small = self._resizer(dev).resize(frames, (dw, dh))
+            for lo in range(0, small.shape[0], 64):
+                rows, counts = self.detect(small[lo:lo + 64], conf=conf, nms=nms, top_k=top_k)
+                rows, counts = rows.cpu().numpy(), counts.cpu().numpy()
+                out += [rows[b, :int(counts[b])] for b in range(rows.shape[0])]
+        return [self.scale_rows(r, w / dw, h / dh) for r, (h, w) in zip(out, shapes)]
+
+    def infer_resized(self, image, size):
+        """``infer`` as demo2.py:194-196 calls it: one H x W x 3 uint8 BGR frame of any size, resized on the device to ``size`` =
+        (dw, dh) and detected there (the preset input size is not consulted).  Returns the (N, 15) rows scaled back to the frame,
+        **float64**, or np.empty((0, 5)) when there is no face."""
+        image = np.asarray(image)
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("infer_resized needs an H x W x 3 uint8 BGR image, got %s %s" % (image.shape, image.dtype))
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        rows = self.detect_resized(torch.from_numpy(np.ascontiguousarray(image)).to(dev).unsqueeze(0), size)[0]
+        return rows if len(rows) else np.empty(shape=(0, 5))
+
     def infer(self, image):
         """FaceDetectorYN.detect on one H x W x 3 uint8 BGR frame of the preset input size: (N, 15) float32, or
         np.empty((0, 5)) when there is no face (as the reference wrapper returns)."""

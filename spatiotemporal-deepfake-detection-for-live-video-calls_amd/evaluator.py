@@ -762,13 +762,21 @@ class VideoScorer(_WindowScorer):
     wait.  Everything is enqueued on the stream that is current when ``score`` is called.  (Refilling a pinned slot waits for the
     copy that last left it, as every staging ring does.)
 
+    ``scale_detect=True`` detects as the reference's ``FaceDetector.scale_detect`` does: every detector batch is resized out of the
+    store to ``retinaface.scale_detect_size`` (half size up to 1920 on the long side) in one launch (``frames.FrameResizer``),
+    detected there with ``min_score=0.5`` and no cap on the boxes, and on the host the rows are scaled back and filtered
+    (``post_detect`` / ``check_valid``) before the first 10 are kept - on score-sorted rows that is ``get_valid_faces`` behind
+    ``scale_detect``.  Tracks, warps (out of the full-size store) and scores are untouched by it.
+
     ``frame_bytes`` bounds the frame store.  A video that does not fit is detected batch by batch through the store and then
     scored track by track in frame segments that overlap by ``clip_size - 1`` and are uploaded again from the host frames; the
     scores do not depend on where the cuts fall.  ``uploaded_bytes`` is what the last call sent to the device."""
 
-    def __init__(self, detector, network, clip_size: int = 32, size: int = 224, batch: int = 16, frame_bytes: int = 4 << 30):
+    def __init__(self, detector, network, clip_size: int = 32, size: int = 224, batch: int = 16, frame_bytes: int = 4 << 30,
+                 scale_detect: bool = False):
         super().__init__(network, RECTS, FrameStore(_network_device(getattr(network, "network", network))), clip_size, size, batch, frame_bytes)
         self.detector = detector
+        self.scale_detect, self._resizer = bool(scale_detect), None
         if detector is not None and torch.device(detector.device) != self.device:
             raise ValueError("evaluator: the detector is on %s, the network on %s" % (detector.device, self.device))
         self._frames, self._resident = None, False
@@ -811,6 +819,8 @@ class VideoScorer(_WindowScorer):
         per batch, bit for bit"""
         if self.detector is None:
             raise ValueError("evaluator: no detector and no detections")
+        if self.scale_detect:
+            return self._detect_scaled()
         n, store = len(self._frames), self.source
         found = []
         for lo in range(0, n, DETECT_BATCH):
@@ -824,6 +834,32 @@ class VideoScorer(_WindowScorer):
         rows = np.ascontiguousarray(back[:, :-1]).view(np.float32).reshape(n, -1, 15)
         return [[(rows[b, i, :4].astype(np.float64), rows[b, i, 5:15].reshape(5, 2).astype(np.float64), rows[b, i, 4])
                  for i in range(int(counts[b]))] for b in range(n)]
+
+    def _detect_scaled(self):
+        """``_detect`` on frames resized to ``scale_detect_size``: ``get_valid_faces(detector.scale_detect(batch))`` per batch.  The
+        device cuts at score 0.5 and caps nothing (a cap of 10 in front of ``check_valid`` could drop a face the reference keeps);
+        the counts come back first, then the rows up to the largest count."""
+        from .frames import FrameResizer
+        from .retinaface import post_detect, scale_detect_scale, scale_detect_size
+        n, store = len(self._frames), self.source
+        h, w = store.shape[:2]
+        dw, dh = scale_detect_size(h, w)
+        if dw < 1 or dh < 1:
+            raise ValueError("evaluator: scale_detect would detect frames of %dx%d at %dx%d" % (w, h, dw, dh))
+        if self._resizer is None:
+            self._resizer = FrameResizer(self.device)
+        found = []
+        for lo in range(0, n, DETECT_BATCH):
+            hi = min(lo + DETECT_BATCH, n)
+            first = lo if self._resident else 0
+            store.put(self._frames[lo:hi], first)
+            small = self._resizer.resize(store.view(first, hi - lo), (dw, dh))
+            found.append(self.detector.detect_device(small, min_score=0.5))
+        counts = torch.cat([c for _, c in found]).cpu().numpy()    # the first wait
+        most = max(1, int(counts.max()))
+        rows = torch.cat([r[:, :most] for r, _ in found]).cpu().numpy()
+        faces = [[(rows[b, i, :4].copy(), rows[b, i, 5:15].reshape(5, 2).copy(), rows[b, i, 4]) for i in range(int(counts[b]))] for b in range(n)]
+        return get_valid_faces(post_detect(faces, scale_detect_scale(h, w), w, h), max_count=10, thres=0.5)
 
     # -- public ------------------------------------------------------------------------------------
     def aligned_windows(self, frames, frame_ids, infos, windows, rects=None) -> torch.Tensor:

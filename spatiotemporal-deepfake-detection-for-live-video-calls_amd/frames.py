@@ -1,4 +1,6 @@
-"""YUV 4:2:0 frames as a caller has them - what a WebRTC stack (I420), a hardware decoder (NV12) or ffmpeg / PyAV (yuv420p) hands over -
+"""Frames on their way into and out of the frame stores: YUV 4:2:0 frames in, downscaled detector batches out.
+
+YUV 4:2:0 frames as a caller has them - what a WebRTC stack (I420), a hardware decoder (NV12) or ffmpeg / PyAV (yuv420p) hands over -
 and their way into the frame stores: ``YuvFrame`` names the planes, ``YuvConverter`` stages host planes through one pinned slot and
 one copy and converts every frame of a call to it, whatever its size, format, store and byte order, in one launch of
 ``af_yuv420_to_rgb_u8`` per ``AF_YUV_MAX_FRAMES`` frames (csrc/af_yuv.hip).
@@ -6,14 +8,19 @@ one copy and converts every frame of a call to it, whatever its size, format, st
 The conversion is OpenCV's ``cvtColor(..., COLOR_YUV2BGR_NV12 / _I420)``: fixed-point BT.601, limited range, one (U, V) per 2 x 2
 block of Y.  It equals the numpy restatement of OpenCV's code (tests/yuv_ref.py) byte for byte and is unpinned against cv2 itself,
 which is absent where this is built.  Not built: full-range and BT.709 matrices, 4:2:2 / 4:4:4, 10-bit formats.  There is no CPU
-fallback: without the HIP library the conversion fails."""
+fallback: without the HIP library the conversion fails.
+
+``FrameResizer`` is the other direction: ``cv2.resize(frame, (dw, dh))`` (the default ``INTER_LINEAR``) of frames that already sit on
+the device - slots of frame stores, views, a batch - into one detector batch, in one launch of ``af_resize_frames_u8`` per
+``AF_RESIZE_MAX_FRAMES`` frames (csrc/af_resize.hip).  It equals tests/resize_ref.py, the numpy restatement of OpenCV's plain C++
+path, byte for byte; that restatement is unpinned against cv2 itself, and an IPP-enabled OpenCV may differ from it."""
 import ctypes as C
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from ._staging import _COPY_THREADS, _SPLIT_BYTES, PinnedRing, stage_rects
+from ._staging import _COPY_THREADS, _SPLIT_BYTES, PinnedRing, cuda_device, stage_rects
 
 # format -> (chroma is one interleaved plane, the first chroma byte / plane in memory is V)
 FORMATS = {"nv12": (True, False), "nv21": (True, True), "i420": (False, False), "yv12": (False, True)}
@@ -273,3 +280,122 @@ class YuvConverter:
                 self.launches += 1
             if slot is not None:
                 slot.record()          # behind the last launch: it reads the device twin, which the next copy into this slot rewrites
+
+
+def _tensor_ref(t: torch.Tensor):
+    """the ``af_store_ref`` of a (B, H, W, 3) or (H, W, 3) uint8 device tensor with packed pixels: B frames (or one) of a store"""
+    from . import _lib
+    if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3:
+        raise ValueError("resize: frames must be (H, W, 3) or (B, H, W, 3) uint8, got %s %s" % (tuple(t.shape), t.dtype))
+    if t.stride(-1) != 1 or t.stride(-2) != 3:
+        raise ValueError("resize: frames must have packed pixels (strides (..., 3, 1))")
+    b = t.shape[0] if t.dim() == 4 else 1
+    h, w = int(t.shape[-3]), int(t.shape[-2])
+    if b < 1 or h < 1 or w < 1:
+        raise ValueError("resize: empty frames %s" % (tuple(t.shape),))
+    pitch = max(int(t.stride(-3)), 3 * w) if h > 1 else 3 * w
+    span = (h - 1) * pitch + 3 * w
+    stride = max(int(t.stride(0)), span) if t.dim() == 4 and b > 1 else span
+    if (h > 1 and t.stride(-3) < 3 * w) or (t.dim() == 4 and b > 1 and t.stride(0) < span):
+        raise ValueError("resize: rows or frames overlap (strides %s)" % (tuple(t.stride()),))
+    return _lib.StoreRef(t.data_ptr(), _lib.FrameStore((b - 1) * stride + span, stride, pitch, b, h, w, 0), 0, 0), b
+
+
+class FrameResizer:
+    """``cv2.resize(frame, (dw, dh))`` of frames that are on `device`, into a detector batch: ``resize(frames, (dw, dh))`` ->
+    a (B, dh, dw, 3) uint8 device tensor, enqueued on the current stream without a host synchronisation.
+
+    ``frames``: a (B, H, W, 3) uint8 device tensor, or a list whose entries are (H, W, 3) device views (pixels packed, rows may be
+    pitched) or ``(FrameStore, slot)`` pairs; the entries may differ in size and come from different stores
+    (``resize_views`` is the list form under the name the servers use).  All entries of one call go out in ONE launch per
+    ``AF_RESIZE_MAX_FRAMES`` frames.  Channels are treated alike: the byte order of the source is the byte order of the result.
+
+    The resizer owns a ring of pinned tables (the planner's output crosses in one asynchronous copy per launch) and one output
+    buffer per (B, size), RE-USED: the tensor a call returns is overwritten by the next call with the same B and size, so consume
+    it (on the same stream) before then, or clone it.  ``launches`` counts the launches enqueued."""
+
+    def __init__(self, device=None):
+        from . import _lib                                        # fails loudly when libafhip.so is missing
+        self.device = cuda_device(device)
+        self._tables = PinnedRing(slots=4, min_bytes=1 << 16, headroom=True)
+        self._out = {}
+        self._launch = _lib.lib.af_resize_frames_u8
+        self.launches = 0
+
+    @staticmethod
+    def plan(jobs, refs, table_address: int, table_bytes: int) -> int:
+        """the planner's part, host only: ``jobs`` = [(index into refs, frame, destination address, destination pitch, dw, dh)] and
+        ``refs`` = [``_lib.StoreRef``] -> the launch's table at host address `table_address`; returns the bytes used"""
+        from . import _lib
+        arr = (_lib.ResizeJob * max(1, len(jobs)))(*[_lib.ResizeJob(int(r), int(f), int(d), int(p), int(dh), int(dw)) for r, f, d, p, dw, dh in jobs])
+        store_arr = (_lib.StoreRef * max(1, len(refs)))(*refs)
+        used = C.c_int64(0)
+        _lib.check(_lib.lib.af_resize_plan_u8(C.byref(arr), len(jobs), C.byref(store_arr), len(refs), C.c_void_p(table_address), table_bytes,
+                                              C.byref(used)), "resize_plan_u8")
+        return used.value
+
+    @staticmethod
+    def table_bytes(sizes) -> int:
+        """an upper bound of the table's bytes for destinations of ``sizes`` = [(dw, dh)]"""
+        from . import _lib
+        arr = (_lib.ResizeJob * max(1, len(sizes)))(*[_lib.ResizeJob(0, 0, None, 0, int(dh), int(dw)) for dw, dh in sizes])
+        n = _lib.lib.af_resize_table_bytes(C.byref(arr), len(sizes))
+        if n < 0:
+            raise ValueError("resize: %d destinations of %s: at most %d per launch, each 1 to %d in both directions"
+                             % (len(sizes), sorted(set(sizes)), _lib.RESIZE_MAX_FRAMES, _lib.RESIZE_MAX_SIDE))
+        return n
+
+    def _sources(self, frames):
+        """-> ([StoreRef], [(index into them, frame)])"""
+        table, extra, src = StoreTable(), [], []
+        if isinstance(frames, torch.Tensor):
+            frames = [frames]
+        for f in frames:
+            if isinstance(f, torch.Tensor):
+                if f.device != self.device:
+                    raise ValueError("resize: a frame on %s, the resizer on %s" % (f.device, self.device))
+                ref, b = _tensor_ref(f)
+                extra.append(ref)
+                src += [(-len(extra), k) for k in range(b)]      # negative: an index into `extra`, resolved below
+            else:
+                store, slot = f
+                if store.device != self.device:
+                    raise ValueError("resize: a frame store on %s, the resizer on %s" % (store.device, self.device))
+                if not 0 <= int(slot) < store.capacity:
+                    raise ValueError("resize: slot %d of a frame store of %d" % (slot, store.capacity))
+                src.append((table.index(store, "rgb"), int(slot)))
+        refs = table.refs + extra
+        return refs, [(r if r >= 0 else len(table.refs) - r - 1, k) for r, k in src]
+
+    def resize(self, frames, size: Tuple[int, int]) -> torch.Tensor:
+        from . import _lib
+        dw, dh = int(size[0]), int(size[1])
+        if not (1 <= dw <= _lib.RESIZE_MAX_SIDE and 1 <= dh <= _lib.RESIZE_MAX_SIDE):
+            raise ValueError("resize: a destination of %dx%d (1 to %d in both directions)" % (dw, dh, _lib.RESIZE_MAX_SIDE))
+        refs, src = self._sources(frames)
+        if not src:
+            raise ValueError("resize: no frames")
+        b = len(src)
+        with torch.cuda.device(self.device):
+            out = self._out.get((b, dw, dh))
+            if out is None:
+                with torch.inference_mode(False):
+                    out = self._out[(b, dw, dh)] = torch.empty((b, dh, dw, 3), dtype=torch.uint8, device=self.device)
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            for lo in range(0, b, _lib.RESIZE_MAX_FRAMES):
+                part = src[lo:lo + _lib.RESIZE_MAX_FRAMES]
+                used_refs = sorted({r for r, _ in part})
+                at = {r: i for i, r in enumerate(used_refs)}
+                jobs = [(at[r], k, out.data_ptr() + (lo + i) * dh * dw * 3, dw * 3, dw, dh) for i, (r, k) in enumerate(part)]
+                need = self.table_bytes([(dw, dh)] * len(part))
+                slot = self._tables.acquire(need, self.device)
+                used = self.plan(jobs, [refs[r] for r in used_refs], slot.host.data_ptr(), slot.host.numel())
+                slot.dev[:used].copy_(slot.host[:used], non_blocking=True)
+                _lib.check(self._launch(C.c_void_p(slot.dev.data_ptr()), len(part), stream), "resize_frames_u8")
+                slot.record()                                     # behind the launch, the last reader of both buffers
+                self.launches += 1
+        return out
+
+    def resize_views(self, views, size: Tuple[int, int]) -> torch.Tensor:
+        """``resize`` on a list of (H, W, 3) device views out of several stores, of any sizes: what a server's detecting tick has"""
+        return self.resize(list(views), size)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ._staging import is_crop
-from .frames import YuvConverter, YuvFrame, StoreTable, upload_bytes
+from .frames import FrameResizer, YuvConverter, YuvFrame, StoreTable, upload_bytes
 from .aligner import STD_POINTS_256
 from .evaluator import (RECTS, RECTS_BGR, FrameStore, StoresWarp, WindowWarp, _clip_buffers, _fit, _FrameTrack, _network_device, _padded, get_crop_box,
                         partition)
@@ -484,6 +484,22 @@ def track_gate(state: CallState, found, measured, gate):
     return faces, alive - {f[0] for f in faces}, kept_boxes, rects
 
 
+def _detect_size(size):
+    """``detect_size`` as a call keeps it: None, or (dw, dh) as two positive ints"""
+    if size is None:
+        return None
+    dw, dh = (int(v) for v in size)
+    if dw < 1 or dh < 1:
+        raise ValueError("realtime: detect_size %r: two positive numbers (dw, dh), or None" % (size,))
+    return dw, dh
+
+
+def _scale_back(rows: np.ndarray, shape, size) -> np.ndarray:
+    """(n, 15) YuNet rows found on a frame of `shape` resized to `size` = (dw, dh) -> the frame's own, float64"""
+    from .detector import YuNet
+    return YuNet.scale_rows(rows, shape[1] / size[0], shape[0] / size[1])
+
+
 class _Detections:
     """the read-back of a step's detector results: ``read([(rows, counts), ...])`` - device tensors, (B, N, 15) and (B,) - -> the
     (n, 15) float32 numpy rows of every frame, in order.  The counts and the first 64 rows of every frame come back in one pinned
@@ -533,16 +549,22 @@ class RealtimeCall:
     five points, with the ``last_lm`` cache.  Every other keyword is ``RealtimeAF``'s with its default, plus ``LiveCall``'s
     ``ring_frames``, ``max_batch``, ``channel_order``, ``size``.  After the scores (:340-358, :501-505): ``score_is_real``,
     ``running_scores``, ``clip_hist`` and ``state[tid]["fake"]`` (median of 5 with hysteresis 0.75 / 0.65), ``last_boxes`` and
-    ``pick_interlocutor_id``; the entries of purged tids are dropped (:489-499).  Not built: ``last_aligned``, the Win32 apps."""
+    ``pick_interlocutor_id``; the entries of purged tids are dropped (:489-499).  Not built: ``last_aligned``, the Win32 apps.
+
+    ``detect_size=(dw, dh)``: a detecting tick resizes the resident frame to dw x dh on the device (``frames.FrameResizer``,
+    cv2.resize's arithmetic), runs the detector there and hands the tracker the rows scaled back to the frame (float64, YuNet's
+    row layout: ``YuNet.scale_rows`` with W / dw and H / dh, as demo2.py does).  ``None`` (the default) detects at full size."""
 
     def __init__(self, network, detector=None, modelPath=None, conf: float = 0.8, clip_size: int = 32, stride: int = 52,
                  crop_scale: float = 0.6, drop_after: int = 90, detect_every: int = 1, mesh_every: int = 1, start_conf: float = 0.76,
                  start_min_size: int = 80, q_weighting: bool = True, q_min_size_soft: int = 64, q_min_size_hard: int = 32,
                  q_lap_soft: float = 20.0, q_lap_hard: float = 5.0, exclude_rect=(0.70, 0.70, 1.00, 1.00), score_is_real: bool = False,
                  track_thresh: float = 0.8, track_buffer: int = 90, match_thresh: float = 0.8, landmarks=None, size: int = 224,
-                 ring_frames: int = 128, max_batch: int = 16, channel_order: str = "bgr"):
+                 ring_frames: int = 128, max_batch: int = 16, channel_order: str = "bgr", detect_size=None):
         import collections
         from types import SimpleNamespace
+        self.detect_size = _detect_size(detect_size)
+        self._resizer = None
         if detector is None:
             if modelPath is None:
                 raise ValueError("realtime: a detector, or the modelPath of the YuNet file to build one from")
@@ -574,9 +596,17 @@ class RealtimeCall:
 
     def _detect(self, view) -> np.ndarray:
         """the detector on the resident frame and the one read-back of its rows"""
-        rows, counts = self.detector.detect(view[None])
+        if self.detect_size is not None:
+            if self._resizer is None:
+                self._resizer = FrameResizer(view.device)
+            with torch.cuda.device(view.device):
+                small = self._resizer.resize([view], self.detect_size)
+            rows, counts = self.detector.detect(small)
+        else:
+            rows, counts = self.detector.detect(view[None])
         with torch.cuda.device(rows.device):
-            return self._detections.read([(rows, counts)], rows.device)[0]
+            found = self._detections.read([(rows, counts)], rows.device)[0]
+        return found if self.detect_size is None else _scale_back(found, view.shape, self.detect_size)
 
     def _track(self, k: int, shape, dets):
         """:382-437 for frame `k`, whose detections are `dets` (None when the detector did not run on it): they are kept in
@@ -705,14 +735,15 @@ class StoresQuality(_QualitySums):
 class ServerStats:
     """what a ``CallServer`` enqueued and waited for: ``last`` for the last step, ``total`` since the server was made, each with
     ``detect`` (calls of ``af_yunet_detect_frames``, or of a detector's ``detect_views``), ``quality``, ``warp`` (launches),
-    ``replay`` (graph replays), ``wait`` (host waits for the device), ``convert`` (launches of ``af_yuv420_to_rgb_u8``) and
-    ``yuv_copies`` (host-to-device copies of staged YUV planes)"""
+    ``replay`` (graph replays), ``wait`` (host waits for the device), ``convert`` (launches of ``af_yuv420_to_rgb_u8``),
+    ``yuv_copies`` (host-to-device copies of staged YUV planes) and ``resize`` (launches of ``af_resize_frames_u8``)"""
     KEYS = ("detect", "quality", "warp", "replay", "wait")
     YUV_KEYS = ("convert", "yuv_copies")       # appear in ``last`` / ``total`` once a step has YUV frames; read as 0 before
+    RESIZE_KEYS = ("resize",)                  # likewise once a call with a ``detect_size`` has detected
 
     class _Counts(dict):
         def __missing__(self, key):
-            if key in ServerStats.YUV_KEYS:
+            if key in ServerStats.YUV_KEYS or key in ServerStats.RESIZE_KEYS:
                 return 0
             raise KeyError(key)
 
@@ -743,7 +774,9 @@ class CallServer:
     ``clip_size``, ``size`` and ``max_batch`` belong to the server (one network, one clip buffer); every other keyword of
     ``RealtimeCall`` is a call's own - ``call_defaults`` here, overridden per call in ``open`` - as are its frame size, tracker,
     ``CallState`` and frame ring.  ``detector``: a ``YuNet`` (or ``modelPath`` to build one with ``conf``), or any object with
-    ``detect_views(views) -> (rows, counts)``.
+    ``detect_views(views) -> (rows, counts)``.  ``detect_size=(dw, dh)`` (a call's own, ``None`` by default) detects that call's
+    frames resized to dw x dh, as ``RealtimeCall`` does: calls of any frame sizes that share a detect size share one resize launch
+    and one ``detect_views``.
 
     A frame is a numpy array or a ``YuvFrame`` (the mapping may mix them).  The ``YuvFrame``s of a step are admitted together: the
     host planes of all calls fill one pinned slot and cross in one copy, and one ``af_yuv420_to_rgb_u8`` launch per 64 frames
@@ -782,6 +815,7 @@ class CallServer:
         self._next = 0
         self._quality = StoresQuality(self.device)
         self._warp = StoresWarp(self.device, self.clip_size, self.size, self.max_batch)
+        self._resizer: Optional[FrameResizer] = None        # made when the first call with a ``detect_size`` detects
         self._yuv = YuvConverter(self.device)     # its own pinned ring: the YUV planes of all calls of a step share one slot
         self._scoring: Optional[_ClosedWindows] = None      # the clip buffer and the scorers, made when the first window closes
         self._done = None                  # recorded behind the last launch of every step
@@ -851,7 +885,8 @@ class CallServer:
             self.stats.count("convert", self._yuv.launches - launched)
             self.stats.count("yuv_copies", self._yuv.copies - copied)
         detecting = [i for i, (_, c, _) in enumerate(calls) if ticks[i] % max(1, c.detect_every) == 0]
-        dets = dict(zip(detecting, self._detect([calls[i][1].call.frame_view(ticks[i]) for i in detecting])))      # 2.
+        dets = dict(zip(detecting, self._detect([calls[i][1].call.frame_view(ticks[i]) for i in detecting],
+                                                [calls[i][1].detect_size for i in detecting])))                    # 2.
         found, wanted = [], []
         for i, (cid, c, frame) in enumerate(calls):                                        # 3. trackers, candidates
             f = c._track(ticks[i], frame.shape, dets.get(i))
@@ -876,15 +911,29 @@ class CallServer:
             out[cid] = c._after(results, kept_boxes)
         return out
 
-    def _detect(self, views) -> List[np.ndarray]:
-        """the rows of every view, in order: the views grouped by shape, one ``detect_views`` per 64 of a group, and the one
-        read-back of all their rows (``_Detections``)"""
+    def _detect(self, views, sizes=None) -> List[np.ndarray]:
+        """the rows of every view, in order: the views grouped by detect size where their call has one (``sizes[i]``) and by shape
+        otherwise, one ``detect_views`` per 64 of a group, and the one read-back of all their rows (``_Detections``).  The views
+        of one detect size, whatever their own sizes, are resized in one launch per 64 and detected where they land; their rows
+        are scaled back per view."""
         if not views:
             return []
         from . import _lib
-        groups = {}
+        sizes = list(sizes) if sizes is not None else [None] * len(views)
+        full, views, groups, by_size = list(views), list(views), {}, {}
+        for i, size in enumerate(sizes):
+            if size is not None:
+                by_size.setdefault(size, []).append(i)
+        if by_size and self._resizer is None:
+            self._resizer = FrameResizer(self.device)
+        for size, members in by_size.items():
+            launched = self._resizer.launches
+            small = self._resizer.resize_views([full[i] for i in members], size)
+            self.stats.count("resize", self._resizer.launches - launched)
+            for at, i in enumerate(members):
+                views[i] = small[at]
         for i, v in enumerate(views):
-            groups.setdefault(tuple(v.shape), []).append(i)
+            groups.setdefault(("resized",) + sizes[i] if sizes[i] is not None else tuple(v.shape), []).append(i)
         order, results = [], []
         for members in groups.values():
             for lo in range(0, len(members), _lib.YUNET_MAX_LIST):
@@ -894,7 +943,7 @@ class CallServer:
                 order += chunk
         out = [None] * len(views)
         for i, rows in zip(order, self._detections.read(results, self.device, self.stats.count)):
-            out[i] = rows
+            out[i] = rows if sizes[i] is None else _scale_back(rows, full[i].shape, sizes[i])
         return out
 
     def _score(self, closed) -> np.ndarray:

@@ -167,6 +167,42 @@ def _split_rows(rows: np.ndarray, n: int):
     return [(rows[i, :4].copy(), rows[i, 5:15].reshape(5, 2).copy(), rows[i, 4]) for i in range(n)]
 
 
+# ---- FaceDetector.scale_detect's host steps (test_tools/ct/detection/__init__.py:10-51), restated
+
+SCALE_DETECT_MAX_RES = 1920
+
+
+def scale_detect_scale(h: int, w: int):
+    """``resize_scale`` for frames of h x w: the int 2 up to 1920 on the long side, ``2 * max(h, w) / 1920`` (a float) above"""
+    return 2 * (max(h, w) / SCALE_DETECT_MAX_RES if max(h, w) > SCALE_DETECT_MAX_RES else 1)
+
+
+def scale_detect_size(h: int, w: int) -> Tuple[int, int]:
+    """``(resize_w, resize_h)``: the size scale_detect detects frames of h x w at; (0, 0) for a 1 x 1 frame"""
+    s = scale_detect_scale(h, w)
+    return int(w / s), int(h / s)
+
+
+def check_valid(face, w, h) -> bool:
+    """a face (box, landmarks, score) whose box is ordered and lies, with every landmark, in [0, w) x [0, h)"""
+    box, pts = face[0], face[1]
+    if box[0] > box[2] or box[1] > box[3]:
+        return False
+    if not (0 <= box[0] < w and 0 <= box[1] < h and 0 <= box[2] < w and 0 <= box[3] < h):
+        return False
+    return all(0 <= p[0] < w and 0 <= p[1] < h for p in pts)
+
+
+def post_detect(detect_results, scale, w, h):
+    """boxes and landmarks of every frame's faces times `scale` (float32 products, as numpy gives ``float32 array * python
+    number``), faces that fail ``check_valid`` on the w x h frame dropped; scores untouched"""
+    out = []
+    for faces in detect_results:
+        scaled = [(box * scale, ldm * scale, score) for box, ldm, score in faces]
+        out.append([f for f in scaled if check_valid(f, w=w, h=h)])
+    return out
+
+
 class FaceDetector(DeviceModel):
     """Drop-in for test_tools/ct/detection.FaceDetector (RetinaFace, mobilenet0.25) on HIP device `gpu_id`."""
 
@@ -321,6 +357,40 @@ class FaceDetector(DeviceModel):
         rows, counts = self.detect_device(t.to(dev, non_blocking=False))
         rows, counts = rows.cpu().numpy(), counts.cpu().numpy()
         out = [_split_rows(rows[b], int(counts[b])) for b in range(rows.shape[0])]
+        return out[0] if single else out
+
+    def scale_detect_device(self, frames_u8, keep_top_k: int = KEEP_TOP_K, max_count: int = 0, min_score: float = 0.0, timings=None):
+        """``detect_device`` on `frames_u8` (B, H, W, 3) resized on the device to ``scale_detect_size(H, W)`` with cv2.resize's
+        arithmetic (``frames.FrameResizer``).  Returns ``(rows, counts, scale)``: rows and counts as ``detect_device`` returns
+        them, in the coordinates of the RESIZED frames; multiply boxes and landmarks by `scale` (``scale_detect_scale``) and apply
+        ``check_valid`` against (W, H) to get what ``scale_detect`` returns.  No host synchronisation."""
+        from .frames import FrameResizer
+        if frames_u8.dim() != 4:
+            raise ValueError("frames must be (B, H, W, 3), got %s" % (tuple(frames_u8.shape),))
+        h, w = int(frames_u8.shape[1]), int(frames_u8.shape[2])
+        dw, dh = scale_detect_size(h, w)
+        if dw < 1 or dh < 1:
+            raise ValueError("scale_detect: frames of %dx%d would be detected at %dx%d (cv2.resize fails there in the reference)" % (w, h, dw, dh))
+        resizers = self.__dict__.setdefault("_resizers", {})
+        rs = resizers.get(frames_u8.device)
+        if rs is None:
+            rs = resizers[frames_u8.device] = FrameResizer(frames_u8.device)
+        small = rs.resize(frames_u8, (dw, dh))
+        rows, counts = self.detect_device(small, keep_top_k, max_count, min_score, timings=timings)
+        return rows, counts, scale_detect_scale(h, w)
+
+    def scale_detect(self, images):
+        """the reference's ``scale_detect``: frames up to 1920 on the long side are detected at half size, larger ones at 960 on
+        the long side, and the boxes and landmarks are scaled back (``post_detect``: faces that leave the frame are dropped).
+        The frames are uploaded as ``detect`` uploads them and resized on the device.  Returns what ``detect`` returns."""
+        t, single = self._as_batch(images)
+        h, w = int(t.shape[1]), int(t.shape[2])
+        dw, dh = scale_detect_size(h, w)
+        if dw < 1 or dh < 1:
+            raise ValueError("scale_detect: frames of %dx%d would be detected at %dx%d (cv2.resize fails there in the reference)" % (w, h, dw, dh))
+        rows, counts, scale = self.scale_detect_device(t.to(self.device, non_blocking=False))
+        rows, counts = rows.cpu().numpy(), counts.cpu().numpy()
+        out = post_detect([_split_rows(rows[b], int(counts[b])) for b in range(rows.shape[0])], scale, w, h)
         return out[0] if single else out
 
     def __call__(self, images):
