@@ -235,7 +235,7 @@ int af_conv3d_ca_bn_act(const af_conv_desc* dc, const void* in_b, const void* wc
  *     x     = relu( bn_c(conv1x1x1_c(b)) + residual )                   [n][32][h][w][C]  (never stored)
  *     xp    = max(x[2t'], x[2t'+1])                                     -> out_x
  *     a_out = relu( bn_a(conv3x1x1_a(xp)) )                             -> out_a [n][16][h][w][128]
- * dc: 64 -> C (C % 64 == 0, C <= 256), tpool = 1, t = 32, h even, w % 4 == 0; da: C -> 128, kernel [3,1,1], pad [1,0,0], t = 16.
+ * dc: 64 -> C (C % 64 == 0; run against fp64 up to C = 512), tpool = 1, t = 32, h even, w % 4 == 0; da: C -> 128, kernel [3,1,1], pad [1,0,0], t = 16.
  * x_sub = 1: out_x is the whole pooled trunk [n][16][h][w][C]; x_sub = 2: only its even (h, w) positions, packed as
  * [n][16][h/2][w/2][C] - all that a 1x1x1 convolution of stride (1,2,2) (the stage's projection shortcut, resnet_helper.py:
  * 411-431) reads; its caller then runs that convolution with stride 1 over the packed tensor.  (ABI 3) */
@@ -257,6 +257,24 @@ const char* af_conv_variant_name(int variant);
  * launchers' own geometry: a test sizes its input from them instead of restating it.  Returns af_conv_variant(d, d2), or < 0
  * (the narrow-layer path is not cut into units). */
 int af_conv_work_units(const af_conv_desc* d, const af_conv_desc* d2, int64_t* units, int* workgroups);
+
+/* ... and how the fused launches are cut, from their launchers' own geometry, with no launch (256 CUs assumed where there is no
+ * device).  Each takes the descriptors of its *_fusable predicate and returns that predicate's answer; the outputs are written only
+ * when it is 1 (< 0: a NULL output pointer).
+ *   af_conv3d_ca_bn_act:  *tiles of all T frames x *pixels pixels (256 / T) on *workgroups persistent workgroups - workgroup b walks
+ *                         tiles b, b + workgroups, ... -, *form = the kernel instantiation: AF_CA_PLAIN, AF_CA_PLAIN_CWL (the c
+ *                         weights as an LDS image) or AF_CA_PROJECTION (d1 != NULL);
+ *   af_conv3d_cpa_bn_act: *tiles of 2 rows x 4 columns x all frames on *workgroups persistent workgroups;
+ *   af_block_abc_bn_act:  one workgroup per unit = (clip, band of *patch_rows rows, 14 columns, one of *time_segments ranges of
+ *                         frames). */
+#define AF_CA_PLAIN 0
+#define AF_CA_PLAIN_CWL 1
+#define AF_CA_PROJECTION 2
+int af_conv_ca_work_units(const af_conv_desc* dc, const af_conv_desc* d1, const af_conv_desc* da, int64_t* tiles, int* workgroups,
+                          int* form, int* pixels);
+int af_conv_cpa_work_units(const af_conv_desc* dc, const af_conv_desc* da, int x_sub, int64_t* tiles, int* workgroups);
+int af_block_abc_work_units(const af_conv_desc* da, const af_conv_desc* db, const af_conv_desc* dc, const af_conv_desc* d1,
+                            int* patch_rows, int* time_segments, int64_t* units);
 
 /* nn.MaxPool3d on NDHWC (stem_helper.py:168-170 [1,3,3]/[1,2,2]/[0,1,1];
  * video_model_builder.py:474-480 [2,1,1]/[2,1,1]); padding behaves as -inf. */

@@ -277,6 +277,11 @@ __global__ __launch_bounds__(512, 2) void block_abc_kernel(const ABCArgs a) {
     if (t1 > t0) store_frame(t1 - 1);
 }
 
+// workgroups of a launch: one per (clip, band of `ph` rows, 14 columns, time segment)
+static long long abc_units(const af_conv_desc* da, int ph, int ts_n) {
+    return (long long)da->n * ((da->h + ph - 1) / ph) * ((da->w + 13) / 14) * ts_n;
+}
+
 // patch rows / time segments for a layer; false: the block does not take this path.  d1 != null: block 0 of a stage with a
 // 1x1x1 stride-1 projection shortcut over the block's input (cin = d1->cin channels)
 static bool abc_geometry(const af_conv_desc* da, const af_conv_desc* db, const af_conv_desc* dc, const af_conv_desc* d1, int* ph, int* ts_n) {
@@ -314,7 +319,7 @@ static bool abc_geometry(const af_conv_desc* da, const af_conv_desc* db, const a
     while (p > 1 && abc_lds_bytes(inner, cin, p, da->kt) > 160 * 1024) --p;
     p = (da->h + (da->h + p - 1) / p - 1) / ((da->h + p - 1) / p);                  // even bands
     if (abc_lds_bytes(inner, cin, p, da->kt) > 160 * 1024 || ((p + 2) * 16 * (cin / 8) + 63) / 64 > 24) return false;   // <= 6 DMA pieces per producer wave and frame
-    const long long units = (long long)da->n * ((da->h + p - 1) / p) * ((da->w + 13) / 14);
+    const long long units = abc_units(da, p, 1);
     int s = 1;
     while (units * s < 256 && da->t / (2 * s) >= 4) s *= 2;           // time segments of >= 4 frames until the chip is covered
     if (units * s > 0x7fffffffLL) return false;
@@ -335,6 +340,15 @@ static int launch_abc(const ABCArgs& a, int units, int lds, hipStream_t stream) 
 extern "C" int af_block_abc_fusable(const af_conv_desc* da, const af_conv_desc* db, const af_conv_desc* dc, const af_conv_desc* d1) {
     int ph, ts;
     return af::abc_geometry(da, db, dc, d1, &ph, &ts) ? 1 : 0;
+}
+
+extern "C" int af_block_abc_work_units(const af_conv_desc* da, const af_conv_desc* db, const af_conv_desc* dc, const af_conv_desc* d1,
+                                       int* patch_rows, int* time_segments, int64_t* units) {
+    AF_REQUIRE(patch_rows && time_segments && units, "block_abc_work_units: null argument");
+    int ph = 0, ts = 0;
+    if (!af::abc_geometry(da, db, dc, d1, &ph, &ts)) return 0;
+    *patch_rows = ph; *time_segments = ts; *units = af::abc_units(da, ph, ts);
+    return 1;
 }
 
 extern "C" int af_block_abc_bn_act(const af_conv_desc* da, const void* x, const void* wa_packed, const float* scale_a, const float* shift_a,
@@ -359,7 +373,7 @@ extern "C" int af_block_abc_bn_act(const af_conv_desc* da, const void* x, const 
     a.y = (char*)out; a.T = da->t; a.H = da->h; a.W = da->w; a.kta = da->kt; a.PH = ph;
     a.py_n = (da->h + ph - 1) / ph; a.px_n = (da->w + 13) / 14; a.ts_n = ts_n; a.TS = (da->t + ts_n - 1) / ts_n;
     a.out_ld = out_ld;
-    const int units = da->n * a.py_n * a.px_n * a.ts_n;
+    const int units = (int)abc_units(da, ph, ts_n);
     const int lds = abc_lds_bytes(da->cout, da->cin, ph, da->kt);
     hipStream_t s = (hipStream_t)stream;
     const bool bf = da->dtype == AF_BF16;

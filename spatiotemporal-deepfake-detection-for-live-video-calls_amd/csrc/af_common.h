@@ -252,6 +252,10 @@ void conv133g_work(const af_conv_desc* d, long long* units, int* workgroups);
 void conv311g_work(const af_conv_desc* d, long long* units, int* workgroups);
 void conv311_work(const af_conv_desc* d, long long* units, int* workgroups);
 void conv111_work(const af_conv_desc* d, const af_conv_desc* d2, long long* units, int* workgroups);
+// af_conv_ca_work_units / af_conv_cpa_work_units: the tiles of a fused pair and the grid its *_run function launches; false: not fused
+bool conv_ca_work(const af_conv_desc* dc, const af_conv_desc* d1, const af_conv_desc* da, long long* tiles, int* workgroups, int* form,
+                  int* pixels);
+bool conv_cpa_work(const af_conv_desc* dc, const af_conv_desc* da, int x_sub, long long* tiles, int* workgroups);
 
 // One-time PER-DEVICE setup.  hipFuncSetAttribute and the CU count belong to a device, and one process may drive several
 // (one engine per device): every "done once" flag is therefore indexed by the current device ordinal.

@@ -1036,6 +1036,15 @@ extern "C" int af_conv_ca_fusable(const af_conv_desc* dc, const af_conv_desc* d1
     return af::conv_ca_applies(dc, d1, da) ? 1 : 0;
 }
 
+extern "C" int af_conv_ca_work_units(const af_conv_desc* dc, const af_conv_desc* d1, const af_conv_desc* da, int64_t* tiles,
+                                     int* workgroups, int* form, int* pixels) {
+    AF_REQUIRE(tiles && workgroups && form && pixels, "conv_ca_work_units: null argument");
+    long long u = 0;
+    if (!af::conv_ca_work(dc, d1, da, &u, workgroups, form, pixels)) return 0;
+    *tiles = u;
+    return 1;
+}
+
 extern "C" int af_conv3d_ca_bn_act(const af_conv_desc* dc, const void* in_b, const void* wc_packed, const af_conv_desc* d1,
                                    const void* in1, const void* w1_packed, const float* scale_c, const float* shift_c,
                                    const void* residual, void* out_x, const af_conv_desc* da, const void* wa_packed,

@@ -417,7 +417,7 @@ static GeomCA geom_ca(const af_conv_desc* dc, bool dual) {
     const long long hw = (long long)dc->h * dc->w;
     if ((long long)dc->t * hw * dc->cout * 2 >= (1LL << 31)) return g;     // 32-bit offsets inside a clip
     const int p = 256 / dc->t;
-    // the launch must fit LDS (wide trunks: the plain form with T = 16 and C >= 512, the projection form with C >= 512 do not):
+    // the launch must fit LDS (wide trunks: the plain form with T = 16 and C = 1024, the projection form with C > 256 do not):
     // such a pair keeps its two launches instead of failing in launch_ca
     if (conv_ca_lds_bytes(dual, p, dc->cout) > kLdsBudget) return g;
     // whole tiles only: the kernel's counted s_waitcnt vmcnt assume that every wave issues every store of an iteration; a
@@ -435,6 +435,7 @@ static GeomCA geom_ca(const af_conv_desc* dc, bool dual) {
 // dc: the 1x1x1 `c` conv (64 -> C, with residual + ReLU), da: the 3x1x1 `a` conv of the next block (C -> 64) over its output
 // d1 (optional): the projection shortcut of block 0 - a 1x1x1 stride-1 conv from 64 channels onto the same positions
 bool conv_ca_applies(const af_conv_desc* dc, const af_conv_desc* d1, const af_conv_desc* da) {
+    if (!dc || !da) return false;
     if (d1) {
         if (d1->dtype != dc->dtype || d1->tpool || d1->kt != 1 || d1->kh != 1 || d1->kw != 1 || d1->st != 1 || d1->sh != 1 || d1->sw != 1) return false;
         if (d1->pt || d1->ph || d1->pw || d1->cin != 64 || d1->cout != dc->cout) return false;
@@ -448,6 +449,22 @@ bool conv_ca_applies(const af_conv_desc* dc, const af_conv_desc* d1, const af_co
     return geom_ca(dc, d1 != nullptr).ok;
 }
 
+// persistent grid: one workgroup per CU (at most one per tile), workgroup b walks tiles b, b + grid, ...
+static int grid_ca(const GeomCA& g) {
+    const int cus = device_cus();
+    return g.tiles < cus ? g.tiles : cus;
+}
+
+// af_conv_ca_work_units: how conv_ca_run cuts the pair and which instantiation it launches (false: the pair is not fused)
+bool conv_ca_work(const af_conv_desc* dc, const af_conv_desc* d1, const af_conv_desc* da, long long* tiles, int* workgroups, int* form,
+                  int* pixels) {
+    if (!conv_ca_applies(dc, d1, da)) return false;
+    const GeomCA g = geom_ca(dc, d1 != nullptr);
+    *tiles = g.tiles; *workgroups = grid_ca(g); *pixels = g.P;
+    *form = d1 ? AF_CA_PROJECTION : g.cwl ? AF_CA_PLAIN_CWL : AF_CA_PLAIN;
+    return true;
+}
+
 int conv_ca_run(const af_conv_desc* dc, const void* inb, const void* wc, const void* in1, const void* w1, const float* scale_c,
                 const float* shift_c, const void* residual, void* outx, const af_conv_desc* da, const void* wa, const float* scale_a,
                 const float* shift_a, void* outa, hipStream_t stream) {
@@ -459,8 +476,7 @@ int conv_ca_run(const af_conv_desc* dc, const void* inb, const void* wc, const v
     const GeomCA g = geom_ca(dc, in1 != nullptr);
     a.P = g.P; a.chunks = g.chunks; a.tiles = g.tiles;
     fill_dbg(a, "AF_CA_DBG");
-    const int cus = device_cus();
-    const int blocks = a.tiles < cus ? a.tiles : cus;
+    const int blocks = grid_ca(g);
     if (in1) return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, true, false>(a, blocks, stream); });
     if (g.cwl)
         return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, false, true>(a, blocks, stream); });

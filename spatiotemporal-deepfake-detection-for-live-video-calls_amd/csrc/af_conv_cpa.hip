@@ -377,6 +377,20 @@ bool conv_cpa_applies(const af_conv_desc* dc, const af_conv_desc* da, int x_sub)
     return geom_cpa(dc).ok;
 }
 
+// persistent grid: one workgroup per CU (at most one per tile), workgroup b walks tiles b, b + grid, ...
+static int grid_cpa(const GeomCPA& g) {
+    const int cus = device_cus();
+    return g.tiles < cus ? g.tiles : cus;
+}
+
+// af_conv_cpa_work_units: how conv_cpa_run cuts the pair (false: the pair is not fused)
+bool conv_cpa_work(const af_conv_desc* dc, const af_conv_desc* da, int x_sub, long long* tiles, int* workgroups) {
+    if (!conv_cpa_applies(dc, da, x_sub)) return false;
+    const GeomCPA g = geom_cpa(dc);
+    *tiles = g.tiles; *workgroups = grid_cpa(g);
+    return true;
+}
+
 int conv_cpa_run(const af_conv_desc* dc, const void* inb, const void* wc, const float* scale_c, const float* shift_c,
                  const void* residual, void* outx, int x_sub, const af_conv_desc* da, const void* wa, const float* scale_a,
                  const float* shift_a, void* outa, hipStream_t stream) {
@@ -387,8 +401,7 @@ int conv_cpa_run(const af_conv_desc* dc, const void* inb, const void* wc, const 
     const GeomCPA g = geom_cpa(dc);
     a.wq = g.wq; a.per_clip = g.per_clip; a.tiles = g.tiles;
     a.sub = x_sub == 2;
-    const int cus = device_cus();
-    const int blocks = a.tiles < cus ? a.tiles : cus;
+    const int blocks = grid_cpa(g);
     return with_dtype16(dc->dtype, [&](auto dt) { return launch_cpa<dt>(a, blocks, stream); });
 }
 
@@ -396,6 +409,14 @@ int conv_cpa_run(const af_conv_desc* dc, const void* inb, const void* wc, const 
 
 extern "C" int af_conv_cpa_fusable(const af_conv_desc* dc, const af_conv_desc* da, int x_sub) {
     return af::conv_cpa_applies(dc, da, x_sub) ? 1 : 0;
+}
+
+extern "C" int af_conv_cpa_work_units(const af_conv_desc* dc, const af_conv_desc* da, int x_sub, int64_t* tiles, int* workgroups) {
+    AF_REQUIRE(tiles && workgroups, "conv_cpa_work_units: null argument");
+    long long u = 0;
+    if (!af::conv_cpa_work(dc, da, x_sub, &u, workgroups)) return 0;
+    *tiles = u;
+    return 1;
 }
 
 extern "C" int af_conv3d_cpa_bn_act(const af_conv_desc* dc, const void* in_b, const void* wc_packed, const float* scale_c,

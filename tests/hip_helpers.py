@@ -116,34 +116,60 @@ def compare(got, want, tol, what):
     assert err <= tol * ref, "%s: max|d|=%.3e vs max|ref|=%.3e, tolerance %.3e" % (what, err, ref, tol)
 
 
-def conv_bc(x_ndhwc, wb_oidhw, bn_b, wc_oidhw, bn_c, residual, dtype):
+def bc_descs(shape_ndhwc, cmid, cout, dtype):
+    """(db, dc) of a fused b (1x3x3) + c (1x1x1) pair over an input of shape (N,T,H,W,C)"""
+    n, t, h, w, cin = shape_ndhwc
+    return _desc(shape_ndhwc, cmid, (1, 3, 3), dtype, pad=(0, 1, 1)), _desc((n, t, h, w, cmid), cout, (1, 1, 1), dtype)
+
+
+def conv_bc(x_ndhwc, wb_oidhw, bn_b, wc_oidhw, bn_c, residual, dtype, out=None, out_ld=0):
     """relu(bn_c(conv1x1x1(relu(bn_b(conv1x3x3(x))))) + residual) as one af_conv3d_bc_bn_act launch; None if the library
-    does not fuse this pair (af_conv_bc_fusable)."""
+    does not fuse this pair (af_conv_bc_fusable).  ``out`` / ``out_ld``: rows of a wider caller-owned buffer."""
     L = lib()
     n, t, h, w, cin = x_ndhwc.shape
     cmid, cout = wb_oidhw.shape[0], wc_oidhw.shape[0]
-    db = _desc(x_ndhwc.shape, cmid, (1, 3, 3), dtype, pad=(0, 1, 1))
-    dc = _desc((n, t, h, w, cmid), cout, (1, 1, 1), dtype)
+    db, dc = bc_descs(x_ndhwc.shape, cmid, cout, dtype)
     if not L.lib.af_conv_bc_fusable(C.byref(db), C.byref(dc)):
         return None
     pb, pc = _pack(wb_oidhw, dtype), _pack(wc_oidhw, dtype)
-    out = torch.empty((n, t, h, w, cout), dtype=TORCH_DT[dtype], device="cuda")
+    if out is None:
+        out = torch.empty((n, t, h, w, cout), dtype=TORCH_DT[dtype], device="cuda")
     L.check(L.lib.af_conv3d_bc_bn_act(C.byref(db), _p(x_ndhwc), _p(pb), _p(bn_b[0]), _p(bn_b[1]), C.byref(dc), _p(pc), _p(bn_c[0]),
-                                      _p(bn_c[1]), _p(residual), _p(out), 0, _stream()), "conv3d_bc_bn_act")
+                                      _p(bn_c[1]), _p(residual), _p(out), out_ld, _stream()), "conv3d_bc_bn_act")
     torch.cuda.current_stream().synchronize()
     return out
 
 
-def block_abc(x_ndhwc, wa_oidhw, bn_a, wb_oidhw, bn_b, wc_oidhw, bn_c, dtype, out_ld=0, w1_oidhw=None, bn_1=None):
+def abc_descs(shape_ndhwc, inner, kta, cout, dtype):
+    """(da, db, dc, d1) of a bottleneck block (a: kT x 1 x 1, b: 1x3x3, c: 1x1x1, d1: its 1x1x1 projection shortcut) over an input
+    of shape (N,T,H,W,C)"""
+    n, t, h, w, cin = shape_ndhwc
+    return tuple(_desc((n, t, h, w, ci), co, k, dtype, pad=p, dout=(t, h, w)) for ci, co, k, p in (
+        (cin, inner, (kta, 1, 1), (kta // 2, 0, 0)), (inner, inner, (1, 3, 3), (0, 1, 1)),
+        (inner, cout, (1, 1, 1), (0, 0, 0)), (cin, cout, (1, 1, 1), (0, 0, 0))))
+
+
+def abc_work_units(shape_ndhwc, inner, kta, cout, dtype, proj=False):
+    """(patch rows, time segments, units = workgroups) of the af_block_abc_bn_act launch of this block - the library's own answer
+    (af_block_abc_work_units), no tensor needed; None if the library does not fuse the block"""
+    L = lib()
+    da, db, dc, d1 = abc_descs(shape_ndhwc, inner, kta, cout, dtype)
+    ph, ts, units = C.c_int(0), C.c_int(0), C.c_int64(0)
+    rc = L.lib.af_block_abc_work_units(C.byref(da), C.byref(db), C.byref(dc), C.byref(d1) if proj else None, C.byref(ph), C.byref(ts),
+                                       C.byref(units))
+    L.check(min(rc, 0), "block_abc_work_units")
+    assert rc == L.lib.af_block_abc_fusable(C.byref(da), C.byref(db), C.byref(dc), C.byref(d1) if proj else None)
+    return (ph.value, ts.value, units.value) if rc else None
+
+
+def block_abc(x_ndhwc, wa_oidhw, bn_a, wb_oidhw, bn_b, wc_oidhw, bn_c, dtype, out_ld=0, w1_oidhw=None, bn_1=None, out=None):
     """relu(shortcut(x) + bn_c(c(relu(bn_b(b(relu(bn_a(a(x)))))))))  as one af_block_abc_bn_act launch (a: kT x 1 x 1, b: 1x3x3,
     c: 1x1x1; shortcut = x, or bn_1(conv1x1x1_1(x)) with w1 / bn_1: the projection form with folded weights); None if the
-    library does not fuse this block (af_block_abc_fusable)."""
+    library does not fuse this block (af_block_abc_fusable).  ``out``: rows of a caller-owned buffer (with ``out_ld``)."""
     L = lib()
     n, t, h, w, cin = x_ndhwc.shape
     inner, kta, cout = wa_oidhw.shape[0], wa_oidhw.shape[2], wc_oidhw.shape[0]
-    da, db, dc, d1 = (_desc((n, t, h, w, ci), co, k, dtype, pad=p, dout=(t, h, w)) for ci, co, k, p in (
-        (cin, inner, (kta, 1, 1), (kta // 2, 0, 0)), (inner, inner, (1, 3, 3), (0, 1, 1)),
-        (inner, cout, (1, 1, 1), (0, 0, 0)), (cin, cout, (1, 1, 1), (0, 0, 0))))
+    da, db, dc, d1 = abc_descs(x_ndhwc.shape, inner, kta, cout, dtype)
     proj = w1_oidhw is not None
     if not L.lib.af_block_abc_fusable(C.byref(da), C.byref(db), C.byref(dc), C.byref(d1) if proj else None):
         return None
@@ -154,7 +180,8 @@ def block_abc(x_ndhwc, wa_oidhw, bn_a, wb_oidhw, bn_b, wc_oidhw, bn_c, dtype, ou
     else:
         pc, p1, sc3, sh3 = _pack(wc_oidhw, dtype), None, bn_c[0], bn_c[1]
     ld = out_ld or cout
-    out = torch.full((n, t, h, w, ld), 7.0, dtype=TORCH_DT[dtype], device="cuda")
+    if out is None:
+        out = torch.full((n, t, h, w, ld), 7.0, dtype=TORCH_DT[dtype], device="cuda")
     L.check(L.lib.af_block_abc_bn_act(C.byref(da), _p(x_ndhwc), _p(pa), _p(bn_a[0]), _p(bn_a[1]), C.byref(db), _p(pb), _p(bn_b[0]),
                                       _p(bn_b[1]), C.byref(dc), _p(pc), _p(sc3), _p(sh3), C.byref(d1) if proj else None, _p(p1),
                                       _p(out), out_ld, _stream()), "block_abc_bn_act")
@@ -162,21 +189,63 @@ def block_abc(x_ndhwc, wa_oidhw, bn_a, wb_oidhw, bn_b, wc_oidhw, bn_c, dtype, ou
     return out
 
 
-def conv_ca(b_ndhwc, wc_oidhw, bn_c, res_ndhwc, wa_oidhw, bn_a, dtype, x0_ndhwc=None, w1_oidhw=None, bn_1=None):
+CA_FORMS = ("plain", "plain-CWL", "projection")          # AF_CA_PLAIN, AF_CA_PLAIN_CWL, AF_CA_PROJECTION
+
+
+def ca_descs(dims, ctrunk, dtype, proj=False, cmid=64, cout_a=64, cin1=64):
+    """(dc, d1 or None, da) of a fused c (1x1x1, cmid -> ctrunk) + a (3x1x1, ctrunk -> cout_a) pair over dims = (n, t, h, w);
+    proj: with the 1x1x1 projection shortcut d1 (cin1 -> ctrunk)"""
+    n, t, h, w = dims
+    dc = _desc((n, t, h, w, cmid), ctrunk, (1, 1, 1), dtype)
+    da = _desc((n, t, h, w, ctrunk), cout_a, (3, 1, 1), dtype, pad=(1, 0, 0))
+    return dc, (_desc((n, t, h, w, cin1), ctrunk, (1, 1, 1), dtype) if proj else None), da
+
+
+def ca_work_units(dims, ctrunk, dtype, proj=False):
+    """(tiles, workgroups, form, pixels per tile) of the af_conv3d_ca_bn_act launch of this pair - the library's own answer
+    (af_conv_ca_work_units), no tensor needed; None if the library does not fuse the pair.  form: one of CA_FORMS"""
+    L = lib()
+    dc, d1, da = ca_descs(dims, ctrunk, dtype, proj)
+    p1 = None if d1 is None else C.byref(d1)
+    tiles, groups, form, pix = C.c_int64(0), C.c_int(0), C.c_int(-1), C.c_int(0)
+    rc = L.lib.af_conv_ca_work_units(C.byref(dc), p1, C.byref(da), C.byref(tiles), C.byref(groups), C.byref(form), C.byref(pix))
+    L.check(min(rc, 0), "conv_ca_work_units")
+    assert rc == L.lib.af_conv_ca_fusable(C.byref(dc), p1, C.byref(da))
+    return (tiles.value, groups.value, CA_FORMS[form.value], pix.value) if rc else None
+
+
+def cpa_descs(dims, ctrunk, dtype, cmid=64, cout_a=128):
+    """(dc, da) of the fused stage boundary: c (1x1x1, cmid -> ctrunk, the frame-pair max behind it) over dims = (n, t, h, w) and a
+    (3x1x1, ctrunk -> cout_a) over the pooled tensor"""
+    n, t, h, w = dims
+    return (_desc((n, t, h, w, cmid), ctrunk, (1, 1, 1), dtype, tpool=1),
+            _desc((n, t // 2, h, w, ctrunk), cout_a, (3, 1, 1), dtype, pad=(1, 0, 0)))
+
+
+def cpa_work_units(dims, ctrunk, dtype, x_sub):
+    """(tiles, workgroups) of the af_conv3d_cpa_bn_act launch of this pair (af_conv_cpa_work_units); None if it is not fused"""
+    L = lib()
+    dc, da = cpa_descs(dims, ctrunk, dtype)
+    tiles, groups = C.c_int64(0), C.c_int(0)
+    rc = L.lib.af_conv_cpa_work_units(C.byref(dc), C.byref(da), x_sub, C.byref(tiles), C.byref(groups))
+    L.check(min(rc, 0), "conv_cpa_work_units")
+    assert rc == L.lib.af_conv_cpa_fusable(C.byref(dc), C.byref(da), x_sub)
+    return (tiles.value, groups.value) if rc else None
+
+
+def conv_ca(b_ndhwc, wc_oidhw, bn_c, res_ndhwc, wa_oidhw, bn_a, dtype, x0_ndhwc=None, w1_oidhw=None, bn_1=None, out_x=None, out_a=None):
     """x = relu(bn_c(conv1x1x1(b)) + res), a_out = relu(bn_a(conv3x1x1(x))) as one af_conv3d_ca_bn_act launch -> (x, a_out);
     with x0 / w1 / bn_1 (a projection block) x = relu(bn_c(c(b)) + bn_1(conv1x1x1_1(x0))) and res must be None.
-    None if the library does not fuse this pair (af_conv_ca_fusable)."""
+    None if the library does not fuse this pair (af_conv_ca_fusable).  ``out_x`` / ``out_a``: caller-owned contiguous outputs."""
     L = lib()
     n, t, h, w, cmid = b_ndhwc.shape
     ctrunk, cout_a = wc_oidhw.shape[0], wa_oidhw.shape[0]
-    dc = _desc(b_ndhwc.shape, ctrunk, (1, 1, 1), dtype)
-    da = _desc((n, t, h, w, ctrunk), cout_a, (3, 1, 1), dtype, pad=(1, 0, 0))
-    d1 = None if x0_ndhwc is None else _desc((n, t, h, w, x0_ndhwc.shape[-1]), ctrunk, (1, 1, 1), dtype)
+    dc, d1, da = ca_descs((n, t, h, w), ctrunk, dtype, x0_ndhwc is not None, cmid, cout_a, 0 if x0_ndhwc is None else x0_ndhwc.shape[-1])
     if not L.lib.af_conv_ca_fusable(C.byref(dc), None if d1 is None else C.byref(d1), C.byref(da)):
         return None
     pa = _pack(wa_oidhw, dtype)
-    x = torch.empty((n, t, h, w, ctrunk), dtype=TORCH_DT[dtype], device="cuda")
-    a_out = torch.empty((n, t, h, w, cout_a), dtype=TORCH_DT[dtype], device="cuda")
+    x = torch.empty((n, t, h, w, ctrunk), dtype=TORCH_DT[dtype], device="cuda") if out_x is None else out_x
+    a_out = torch.empty((n, t, h, w, cout_a), dtype=TORCH_DT[dtype], device="cuda") if out_a is None else out_a
     if d1 is None:
         pc, p1, sc, sf = _pack(wc_oidhw, dtype), None, bn_c[0], bn_c[1]
     else:           # both weight sets carry their BN scale, scale = ones, shift = the summed shifts (as the engine does)
@@ -189,20 +258,20 @@ def conv_ca(b_ndhwc, wc_oidhw, bn_c, res_ndhwc, wa_oidhw, bn_a, dtype, x0_ndhwc=
     return x, a_out
 
 
-def conv_cpa(b_ndhwc, wc_oidhw, bn_c, res_ndhwc, wa_oidhw, bn_a, dtype, x_sub):
+def conv_cpa(b_ndhwc, wc_oidhw, bn_c, res_ndhwc, wa_oidhw, bn_a, dtype, x_sub, out_x=None, out_a=None):
     """x = relu(bn_c(conv1x1x1(b)) + res), xp = max over frame pairs, a_out = relu(bn_a(conv3x1x1(xp))) as one
-    af_conv3d_cpa_bn_act launch -> (xp or its even (h, w) positions, a_out); None if the library does not fuse this pair."""
+    af_conv3d_cpa_bn_act launch -> (xp or its even (h, w) positions, a_out); None if the library does not fuse this pair.
+    ``out_x`` / ``out_a``: caller-owned contiguous outputs."""
     L = lib()
     n, t, h, w, cmid = b_ndhwc.shape
     ctrunk, cout_a = wc_oidhw.shape[0], wa_oidhw.shape[0]
-    dc = _desc(b_ndhwc.shape, ctrunk, (1, 1, 1), dtype, tpool=1)
-    da = _desc((n, t // 2, h, w, ctrunk), cout_a, (3, 1, 1), dtype, pad=(1, 0, 0))
+    dc, da = cpa_descs((n, t, h, w), ctrunk, dtype, cmid, cout_a)
     if not L.lib.af_conv_cpa_fusable(C.byref(dc), C.byref(da), x_sub):
         return None
     pc, pa = _pack(wc_oidhw, dtype), _pack(wa_oidhw, dtype)
     xs = (n, t // 2, h // 2, w // 2, ctrunk) if x_sub == 2 else (n, t // 2, h, w, ctrunk)
-    x = torch.full(xs, 7.0, dtype=TORCH_DT[dtype], device="cuda")
-    a_out = torch.full((n, t // 2, h, w, cout_a), 7.0, dtype=TORCH_DT[dtype], device="cuda")
+    x = torch.full(xs, 7.0, dtype=TORCH_DT[dtype], device="cuda") if out_x is None else out_x
+    a_out = torch.full((n, t // 2, h, w, cout_a), 7.0, dtype=TORCH_DT[dtype], device="cuda") if out_a is None else out_a
     L.check(L.lib.af_conv3d_cpa_bn_act(C.byref(dc), _p(b_ndhwc), _p(pc), _p(bn_c[0]), _p(bn_c[1]), _p(res_ndhwc), _p(x), x_sub,
                                        C.byref(da), _p(pa), _p(bn_a[0]), _p(bn_a[1]), _p(a_out), _stream()), "conv3d_cpa_bn_act")
     torch.cuda.current_stream().synchronize()

@@ -835,3 +835,79 @@ def test_persist_matrix_covers_what_ships(monkeypatch):
     assert len(shipped) >= 60, len(shipped)
     missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
     assert not missing, "%d shipped persistent-kernel launches without a case:\n%s" % (len(missing), "\n".join(missing))
+
+
+def test_fused_matrix_covers_what_ships(monkeypatch):
+    """every fused conv launch of the three networks at batch 1..32 - kind `ca`, `abc` with the default switches, `cpa` under
+    AF_FUSE_CPA=1, `bc` under AF_FUSE_BC=1 - is a case of tests/test_hip_conv_fused.py, which runs it against fp64 on the GPU in the
+    same kernel form, at the same K-slab count and in the same class of tiles per workgroup (conv_ca, conv_cpa) or with the same
+    patch rows and time segments (block_abc); the keys are that file's case_key().  How a launch is cut comes from
+    af_conv_ca_work_units / af_conv_cpa_work_units / af_block_abc_work_units, which answer for 256 CUs where there is no device."""
+    import collections
+    import ctypes as C
+    import importlib.util
+    import sys
+    from af_mi355x import engine
+    from af_mi355x._lib import lib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hip_helpers as hh
+    spec_ = importlib.util.spec_from_file_location("test_hip_conv_fused", os.path.join(ROOT, "tests", "test_hip_conv_fused.py"))
+    matrix = importlib.util.module_from_spec(spec_)
+    spec_.loader.exec_module(matrix)
+    covered = {matrix.case_key(c, dt) for c in matrix.CASES for dt in c.dtypes}
+    for name in ("AF_FORCE_VAR", "AF_ABC_INNER32"):
+        monkeypatch.delenv(name, raising=False)
+    specs = {"i3d_r50": arch.i3d_r50_spec(), "slowfast_r50": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
+    rgb3 = {"i3d_r50": {specs["i3d_r50"].stem.conv}, "slowfast_r50": {specs["slowfast_r50"].stems[0].conv}, "ftcn_tt": set()}
+    ref = lambda d: None if d is None else C.byref(d)
+    shipped, kinds = {}, collections.Counter()
+    for switch in (None, "AF_FUSE_CPA", "AF_FUSE_BC"):
+        for name in ("AF_FUSE_BC", "AF_FUSE_CA", "AF_FUSE_CPA", "AF_FUSE_ABC"):
+            monkeypatch.delenv(name, raising=False)
+        if switch:
+            monkeypatch.setenv(switch, "1")
+        for net, spec in specs.items():
+            for dtype in ("bf16", "f16"):
+                for batch in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32):
+                    p = engine.plan_network(spec, dtype, batch, (spec.num_frames, spec.crop, spec.crop), rgb3[net])
+                    for e in p.entries:
+                        kind = e["kind"]
+                        if kind not in ("ca", "cpa", "abc", "bc"):
+                            continue
+                        cv, cv2 = e["cv"], e["cv2"]
+                        if kind == "ca":
+                            cv1 = e.get("cv3")
+                            dc, da = p.desc(cv, e["din"], e["dout"]), p.desc(cv2, e["dout"], cv2.out_dims(*e["dout"]))
+                            d1 = None if cv1 is None else p.desc(cv1, e["din3"], e["dout"])
+                            tiles, groups, form, pix = C.c_int64(0), C.c_int(0), C.c_int(-1), C.c_int(0)
+                            assert lib.af_conv_ca_work_units(ref(dc), ref(d1), ref(da), ref(tiles), ref(groups), ref(form), ref(pix)) == 1
+                            assert groups.value == 256 and pix.value * dc.t == 256 and (form.value == 2) == (cv1 is not None)
+                            key = ("ca", hh.CA_FORMS[form.value], dtype, dc.t, cv.cout // 64, matrix.rounds_class(tiles.value, groups.value))
+                            what = "%d -> %d -> %d, %d tiles on %d workgroups" % (cv.cin, cv.cout, cv2.cout, tiles.value, groups.value)
+                        elif kind == "cpa":
+                            dp = (e["dout"][0] // 2,) + tuple(e["dout"][1:])
+                            dc, da = p.desc(cv, e["din"], e["dout"], 1), p.desc(cv2, dp, cv2.out_dims(*dp))
+                            tiles, groups = C.c_int64(0), C.c_int(0)
+                            assert lib.af_conv_cpa_work_units(ref(dc), ref(da), e["x_sub"], ref(tiles), ref(groups)) == 1
+                            assert groups.value == 256
+                            key = ("cpa", dtype, cv.cout // 64, e["x_sub"], matrix.rounds_class(tiles.value, groups.value))
+                            what = "%d -> %d -> %d, %d tiles on %d workgroups" % (cv.cin, cv.cout, cv2.cout, tiles.value, groups.value)
+                        elif kind == "abc":
+                            d, cv3, cv4 = e["din"], e["cv3"], e.get("cv4")
+                            ds = [p.desc(c_, d, d) for c_ in (cv, cv2, cv3)] + [None if cv4 is None else p.desc(cv4, d, d)]
+                            rows, seg, units = C.c_int(0), C.c_int(0), C.c_int64(0)
+                            assert lib.af_block_abc_work_units(*(ref(x) for x in ds), ref(rows), ref(seg), ref(units)) == 1
+                            assert units.value == batch * -(-d[1] // rows.value) * -(-d[2] // 14) * seg.value
+                            key = ("abc", cv.cout, cv.kernel[0], cv4 is not None, dtype, rows.value, seg.value)
+                            what = "%d -> %d, %s frames of %d x %d, %d units" % (cv.cin, cv3.cout, d[0], d[1], d[2], units.value)
+                        else:
+                            db, dc = p.desc(cv, e["din"], e["dmid"]), p.desc(cv2, e["dmid"], e["dout"])
+                            assert lib.af_conv_bc_fusable(ref(db), ref(dc)) == 1
+                            key = ("bc", dtype, cv.cin, cv.cout, cv2.cout, (db.h, db.w))
+                            what = "%d -> %d -> %d" % (cv.cin, cv.cout, cv2.cout)
+                        kinds[kind] += 1
+                        shipped.setdefault(key, "%s batch %d%s: %s" % (net, batch, " with %s=1" % switch if switch else "", what))
+    # today 40 keys: 8 ca (plain-CWL and projection, T = 32, 4 slabs, classes "4-5" and ">5"), 4 cpa, 24 abc, 4 bc
+    assert len(shipped) >= 40 and all(kinds[k] for k in ("ca", "cpa", "abc", "bc")), (len(shipped), kinds)
+    missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
+    assert not missing, "%d shipped fused launches without a case:\n%s" % (len(missing), "\n".join(missing))
