@@ -534,6 +534,12 @@ int af_warp_affine_window_stores_u8(const void* table, int n_windows, int clip_s
  * stores[rects[i].reserved].  At most AF_QUALITY_MAX_RECTS rectangles and AF_MAX_STORES stores per launch. */
 int af_face_quality_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
                               void* grey, int64_t grey_bytes, void* stream);
+/* The same kernel in its full-size mode: the Laplacian sums of every rectangle AS IT IS, without the INTER_AREA half-size stage -
+ * the second measurement the dataset evaluator takes of a crop (altfreezing/TEST2.py:296-299: variance_of_laplacian(crop_rgb) into
+ * _qstat).  dw = iw, dh = ih, n_px = iw * ih; grey, Laplacian, sums, grey bytes (sum of iw * ih) and every refusal are those of
+ * af_face_quality_stores_u8.  (Added within ABI 6.) */
+int af_face_laplacian_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
+                                void* grey, int64_t grey_bytes, void* stream);
 
 /* ---- YUV 4:2:0 frames into frame stores (added within ABI 6) ---------------------------------------------------------------------
  * What a WebRTC stack (I420), a hardware decoder (NV12) or ffmpeg (yuv420p) hands over, converted on the device straight into slots

@@ -12,6 +12,9 @@ def __getattr__(name):
     if name in ("LiveCall", "RealtimeCall", "CallServer", "FaceQuality"):
         from . import live
         return getattr(live, name)
+    if name == "VideoRunner":
+        from . import runner
+        return runner.VideoRunner
     if name in ("YuvFrame", "FrameResizer"):
         from . import frames
         return getattr(frames, name)

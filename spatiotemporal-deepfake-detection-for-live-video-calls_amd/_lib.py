@@ -223,7 +223,8 @@ ABI = {
                                                  C.c_void_p, C.c_void_p]),
     "af_warp_affine_window_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "af_face_quality_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "af_yuv420_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "af_face_laplacian_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "af_yuv420_plan_u8":(C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "af_yuv420_to_rgb_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "af_resize_table_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
     "af_resize_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),

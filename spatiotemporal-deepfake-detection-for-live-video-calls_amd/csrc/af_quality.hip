@@ -81,10 +81,16 @@ __device__ __forceinline__ AreaCell area_cell(int d, int ssize, int dsize) {
     return c;
 }
 
-// the grey byte at (gx, gy) of the rectangle's half-size image; `src` is the rectangle's first byte
+// the grey byte at (gx, gy) of the rectangle's half-size image - FULL: of the rectangle as it is, no resize stage -; `src` is the
+// rectangle's first byte
+template <bool FULL>
 __device__ int grey_at(const unsigned char* src, long long pitch, int w, int h, int dw, int dh, int gx, int gy, int bgr) {
     int ch[3];
-    if (w == 2 * dw && h == 2 * dh) {
+    if (FULL) {
+        const unsigned char* p = src + (long long)gy * pitch + (long long)gx * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ch[c] = p[c];
+    } else if (w == 2 * dw && h == 2 * dh) {
         const unsigned char* p = src + (long long)(2 * gy) * pitch + (long long)(2 * gx) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) ch[c] = (p[c] + p[3 + c] + p[pitch + c] + p[pitch + 3 + c] + 2) >> 2;
@@ -125,12 +131,14 @@ __device__ int grey_at(const unsigned char* src, long long pitch, int w, int h, 
 }
 
 // One tile of one rectangle: `src` the rectangle's first byte, rows `pitch` bytes apart, w x h pixels, tile `local` of it; the
-// tile's totals go to `out`, its grey bytes (tests) to `grey` (the rectangle's own image, or null).
+// tile's totals go to `out`, its grey bytes (tests) to `grey` (the rectangle's own image, or null).  FULL: the measured image is
+// the rectangle itself (dw = w, dh = h), the reference's second, full-size variance_of_laplacian (TEST2.py:296-299).
+template <bool FULL>
 __device__ __forceinline__ void quality_tile(const unsigned char* src, long long pitch, int w, int h, int local, int bgr, af_quality_sums* out,
                                              unsigned char* grey) {
     __shared__ unsigned char g[Q_GH][Q_GW + 2];
     __shared__ long long part[2][4];
-    const int dw = max(1, w / 2), dh = max(1, h / 2);
+    const int dw = FULL ? w : max(1, w / 2), dh = FULL ? h : max(1, h / 2);
     const int tiles_x = (dw + Q_TW - 1) / Q_TW;
     const int ty0 = (local / tiles_x) * Q_TH, tx0 = (local % tiles_x) * Q_TW;
 
@@ -140,7 +148,7 @@ __device__ __forceinline__ void quality_tile(const unsigned char* src, long long
         int v = 0;
         if (y <= dh && x <= dw) {                                 // beyond n nothing reads the cell
             const int yy = reflect101(y, dh), xx = reflect101(x, dw);
-            v = grey_at(src, pitch, w, h, dw, dh, xx, yy, bgr);
+            v = grey_at<FULL>(src, pitch, w, h, dw, dh, xx, yy, bgr);
             if (grey && gr >= 1 && gr <= Q_TH && gc >= 1 && gc <= Q_TW && y < dh && x < dw)
                 grey[(long long)y * dw + x] = (unsigned char)v;
         }
@@ -171,18 +179,20 @@ __device__ __forceinline__ void quality_tile(const unsigned char* src, long long
     }
 }
 
+template <bool FULL>
 __global__ __launch_bounds__(256) void face_quality_stores_kernel(const QualityStoresArgs a) {
     const int tile = blockIdx.x;
     if (tile >= a.total_tiles) return;
     int k = 0;
     while (k + 1 < a.n && a.r[k + 1].first_tile <= tile) ++k;     // tens of rectangles: a scan
     const QualityStoreRect r = a.r[k];
-    quality_tile(r.first, r.pitch, r.w, r.h, tile - r.first_tile, r.bgr, a.sums + k, a.grey ? a.grey + r.grey_offset : nullptr);
+    quality_tile<FULL>(r.first, r.pitch, r.w, r.h, tile - r.first_tile, r.bgr, a.sums + k, a.grey ? a.grey + r.grey_offset : nullptr);
 }
 
 // The host side of both entry points: the stores and the rectangles checked, one memset and one launch.  `listed`: a rectangle
-// names its store in af_frame_rect.reserved; otherwise every rectangle is of the one store and reserved is not read.
-static int face_quality(const char* who, const af_store_ref* stores, int n_stores, bool listed, const af_frame_rect* rects, int n,
+// names its store in af_frame_rect.reserved; otherwise every rectangle is of the one store and reserved is not read.  `full`: the
+// kernel's full-size mode.
+static int face_quality(const char* who, const af_store_ref* stores, int n_stores, bool listed, bool full, const af_frame_rect* rects, int n,
                         af_quality_sums* sums, void* grey, int64_t grey_bytes, void* stream) {
     AF_REQUIRE(stores && rects && sums, "%s: null argument", who);
     AF_REQUIRE(n >= 0 && n <= AF_QUALITY_MAX_RECTS, "%s: %d rectangles (at most %d per launch)", who, n, AF_QUALITY_MAX_RECTS);
@@ -207,7 +217,7 @@ static int face_quality(const char* who, const af_store_ref* stores, int n_store
             snprintf(item, sizeof item, "rectangle %d", i);
             return refuse_frame_rect(who, item, listed ? store : -1, st.desc, r, fault);
         }
-        const int dw = r.iw / 2 > 1 ? r.iw / 2 : 1, dh = r.ih / 2 > 1 ? r.ih / 2 : 1;
+        const int dw = full ? r.iw : (r.iw / 2 > 1 ? r.iw / 2 : 1), dh = full ? r.ih : (r.ih / 2 > 1 ? r.ih / 2 : 1);
         a.r[i] = QualityStoreRect{(const unsigned char*)st.base + offset, (int32_t)st.desc.row_pitch, r.iw, r.ih, (int32_t)tiles, (int32_t)grey_total,
                                   st.bgr ? 1 : 0};
         tiles += (int64_t)((dw + Q_TW - 1) / Q_TW) * ((dh + Q_TH - 1) / Q_TH);
@@ -218,7 +228,10 @@ static int face_quality(const char* who, const af_store_ref* stores, int n_store
     a.total_tiles = (int)tiles;
     hipError_t e = hipMemsetAsync(sums, 0, sizeof(af_quality_sums) * (size_t)n, (hipStream_t)stream);
     if (e != hipSuccess) return set_error(AF_ERR_LAUNCH, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
-    hipLaunchKernelGGL(face_quality_stores_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    if (full)
+        hipLaunchKernelGGL(face_quality_stores_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(face_quality_stores_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
     AF_CHECK_LAUNCH("face_quality_stores_kernel");
     return AF_OK;
 }
@@ -228,10 +241,15 @@ static int face_quality(const char* who, const af_store_ref* stores, int n_store
 extern "C" int af_face_quality_u8(const void* store, const af_frame_store* desc, const af_frame_rect* rects, int n, int bgr,
                                   af_quality_sums* sums, void* grey, int64_t grey_bytes, void* stream) {
     const af_store_ref one{store, desc ? *desc : af_frame_store{}, bgr, 0};
-    return af::face_quality("face_quality", store && desc ? &one : nullptr, 1, false, rects, n, sums, grey, grey_bytes, stream);
+    return af::face_quality("face_quality", store && desc ? &one : nullptr, 1, false, false, rects, n, sums, grey, grey_bytes, stream);
 }
 
 extern "C" int af_face_quality_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
                                          void* grey, int64_t grey_bytes, void* stream) {
-    return af::face_quality("face_quality_stores", stores, n_stores, true, rects, n, sums, grey, grey_bytes, stream);
+    return af::face_quality("face_quality_stores", stores, n_stores, true, false, rects, n, sums, grey, grey_bytes, stream);
+}
+
+extern "C" int af_face_laplacian_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
+                                           void* grey, int64_t grey_bytes, void* stream) {
+    return af::face_quality("face_laplacian_stores", stores, n_stores, true, true, rects, n, sums, grey, grey_bytes, stream);
 }

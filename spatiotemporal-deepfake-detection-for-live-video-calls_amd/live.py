@@ -320,35 +320,41 @@ class _QualitySums:
         self.device, self.launches = device, 0
         self._dev = self._host = None
 
-    def _sums(self, sizes, grey: bool, launch, what: str):
-        """``sizes``: (h, w) per rectangle; ``launch(lo, hi, sums, grey, grey_bytes, stream)`` calls the C function for rectangles
-        [lo, hi) -> ``[(n_px, S1, S2)]`` as Python integers (and, with ``grey``, the list of (dh, dw) uint8 grey images)"""
+    def _sums(self, sizes, grey: bool, launch, what: str, full: bool = False, both: bool = False):
+        """``sizes``: (h, w) per rectangle; ``launch(lo, hi, sums, grey, grey_bytes, stream, full)`` calls the C function for
+        rectangles [lo, hi) -> ``[(n_px, S1, S2)]`` as Python integers (and, with ``grey``, the list of (dh, dw) uint8 grey images;
+        ``full``: the measured images are the rectangles themselves, (h, w)).  ``both`` (without ``grey``): the half-size launches,
+        then the full-size ones, and ONE read-back -> the two lists."""
         import ctypes as C
         from . import _lib
         n = len(sizes)
         if n == 0:
-            return ([], []) if grey else []
-        halves = [(max(1, h // 2), max(1, w // 2)) for h, w in sizes]
-        rec = C.sizeof(_lib.QualitySums)
+            return ([], []) if grey or both else []
+        passes = (False, True) if both else (bool(full),)
+        halves = [(h, w) if full else (max(1, h // 2), max(1, w // 2)) for h, w in sizes]
+        rec, total = C.sizeof(_lib.QualitySums), n * len(passes)
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
-            if self._dev is None or self._dev.numel() < n * rec:
+            if self._dev is None or self._dev.numel() < total * rec:
                 with torch.inference_mode(False):
-                    self._dev = torch.empty(max(n, _lib.QUALITY_MAX_RECTS) * rec, dtype=torch.uint8, device=self.device)
+                    self._dev = torch.empty(max(total, _lib.QUALITY_MAX_RECTS) * rec, dtype=torch.uint8, device=self.device)
                     self._host = torch.empty(self._dev.numel(), dtype=torch.uint8, pin_memory=True)
             gbuf = torch.empty(sum(h * w for h, w in halves), dtype=torch.uint8, device=self.device) if grey else None
             goff = 0
-            for lo in range(0, n, _lib.QUALITY_MAX_RECTS):                 # one launch for up to 64 faces
-                hi = min(n, lo + _lib.QUALITY_MAX_RECTS)
-                gn = sum(h * w for h, w in halves[lo:hi])
-                _lib.check(launch(lo, hi, C.c_void_p(self._dev.data_ptr() + lo * rec), C.c_void_p(gbuf.data_ptr() + goff if grey else None), gn,
-                                  C.c_void_p(cur.cuda_stream)), what)
-                self.launches += 1
-                goff += gn
-            self._host[:n * rec].copy_(self._dev[:n * rec], non_blocking=True)
+            for p, mode in enumerate(passes):
+                for lo in range(0, n, _lib.QUALITY_MAX_RECTS):             # one launch for up to 64 faces
+                    hi = min(n, lo + _lib.QUALITY_MAX_RECTS)
+                    gn = sum(h * w for h, w in halves[lo:hi]) if grey else 0
+                    _lib.check(launch(lo, hi, C.c_void_p(self._dev.data_ptr() + (p * n + lo) * rec),
+                                      C.c_void_p(gbuf.data_ptr() + goff if grey else None), gn, C.c_void_p(cur.cuda_stream), mode), what)
+                    self.launches += 1
+                    goff += gn
+            self._host[:total * rec].copy_(self._dev[:total * rec], non_blocking=True)
             cur.synchronize()
-            raw = np.frombuffer(self._host.numpy()[:n * rec].tobytes(), dtype=_SUMS_DTYPE)
+            raw = np.frombuffer(self._host.numpy()[:total * rec].tobytes(), dtype=_SUMS_DTYPE)
             out = [(int(r["n_px"]), int(r["s1"]), int(r["s2"])) for r in raw]
+            if both:
+                return out[:n], out[n:]
             if not grey:
                 return out
             flat, images, off = gbuf.cpu().numpy(), [], 0
@@ -360,6 +366,15 @@ class _QualitySums:
     def __call__(self, rects):
         out = []
         for (n_px, s1, s2), (x0, y0, x1, y1) in zip(self.sums(rects), (r[-4:] for r in rects)):
+            out.append((float(min(y1 - y0, x1 - x0)), (n_px * s2 - s1 * s1) / (n_px * n_px)))
+        return out
+
+    def full_size(self, rects):
+        """``[(min_side, lap)]`` of the same rectangles measured as they are, without the half-size stage: the evaluator's
+        ``variance_of_laplacian(crop_rgb)`` (altfreezing/TEST2.py:296-299).  One launch of ``af_face_laplacian_stores_u8`` per 64
+        rectangles (counted in ``launches``) and one read-back."""
+        out = []
+        for (n_px, s1, s2), (x0, y0, x1, y1) in zip(self.full_sums(rects), (r[-4:] for r in rects)):
             out.append((float(min(y1 - y0, x1 - x0)), (n_px * s2 - s1 * s1) / (n_px * n_px)))
         return out
 
@@ -386,10 +401,22 @@ class FaceQuality(_QualitySums):
         for i, (slot, x0, y0, x1, y1) in enumerate(rects):
             items[i] = (slot, x0, y0, y1 - y0, x1 - x0, 0, 0, 0)
 
-        def launch(lo, hi, sums, gptr, gn, stream):
+        def launch(lo, hi, sums, gptr, gn, stream, full=False):
             return self._fn(C.c_void_p(store.dev.data_ptr()), store.plan_source(), C.c_void_p(items[lo:hi].ctypes.data), hi - lo, self.bgr,
                             sums, gptr, gn, stream)
         return self._sums([(int(r["ih"]), int(r["iw"])) for r in items], grey, launch, "face_quality_u8")
+
+    def full_sums(self, rects, grey: bool = False):
+        """``sums`` of the rectangles at full size (the (h, w) grey images with ``grey``): the one store through the several-store
+        entry point, which is the only one the full-size mode has"""
+        if getattr(self, "_stores", None) is None:
+            self._stores = StoresQuality(self.device)
+        order = "bgr" if self.bgr else "rgb"
+        launched = self._stores.launches
+        try:
+            return self._stores.full_sums([(self.store, order) + tuple(r) for r in rects], grey)
+        finally:
+            self.launches += self._stores.launches - launched
 
 
 # ---- the whole live step: af_realtime.py:372-509 ----------------------------------------------------------------------------------
@@ -718,18 +745,33 @@ class StoresQuality(_QualitySums):
         from . import _lib                                        # fails loudly when libafhip.so is missing
         super().__init__(device)
         self._fn = _lib.lib.af_face_quality_stores_u8
+        self._full_fn = _lib.lib.af_face_laplacian_stores_u8
 
-    def sums(self, rects, grey: bool = False):
+    def sums(self, rects, grey: bool = False, full: bool = False, both: bool = False):
         import ctypes as C
         from .evaluator import _RECT_DTYPE
 
-        def launch(lo, hi, sums, gptr, gn, stream):
+        def launch(lo, hi, sums, gptr, gn, stream, full=False):
             table = StoreTable()                                           # the stores of this launch
             items = np.zeros(hi - lo, dtype=_RECT_DTYPE)
             for i, (store, order, slot, x0, y0, x1, y1) in enumerate(rects[lo:hi]):
                 items[i] = (slot, x0, y0, y1 - y0, x1 - x0, 0, 0, table.index(store, order))
-            return self._fn(table.array(), len(table.refs), C.c_void_p(items.ctypes.data), hi - lo, sums, gptr, gn, stream)
-        return self._sums([(r[6] - r[4], r[5] - r[3]) for r in rects], grey, launch, "face_quality_stores_u8")
+            fn = self._full_fn if full else self._fn
+            return fn(table.array(), len(table.refs), C.c_void_p(items.ctypes.data), hi - lo, sums, gptr, gn, stream)
+        return self._sums([(r[6] - r[4], r[5] - r[3]) for r in rects], grey, launch,
+                          "face_quality_stores_u8 / face_laplacian_stores_u8" if both else "face_laplacian_stores_u8" if full else "face_quality_stores_u8",
+                          full, both)
+
+    def full_sums(self, rects, grey: bool = False):
+        """``sums`` of the rectangles at full size: ``af_face_laplacian_stores_u8``; with ``grey`` the (h, w) grey images"""
+        return self.sums(rects, grey, full=True)
+
+    def half_and_full(self, rects):
+        """``[(min_side, half-size lap, full-size lap)]``: both modes of the kernel on the same rectangles - one launch of each per
+        64 rectangles - behind ONE read-back: what the evaluator's gate measures of a crop while ``_qstat`` is short"""
+        half, full = self.sums(rects, both=True)
+        lap = lambda t: (t[0] * t[2] - t[1] * t[1]) / (t[0] * t[0])
+        return [(float(min(r[6] - r[4], r[5] - r[3])), lap(h), lap(f)) for r, h, f in zip(rects, half, full)]
 
 
 class ServerStats:
