@@ -637,6 +637,75 @@ int af_resize_plan_u8(const af_resize_job* jobs, int n, const af_store_ref* stor
                       int64_t* used_bytes);
 int af_resize_frames_u8(const void* table_dev, int n, void* stream);
 
+/* ---- captured bitmaps into frame stores (added within ABI 6) --------------------------------------------------------------------
+ * What a screen or window capture hands over - a BGRA (or RGBA, BGR, RGB) bitmap - into slots of frame stores in one launch that
+ * does the three things the reference's capture code does on the host (test/win_capture.py:37, :110-115; test/capture_tile.py:190,
+ * :199-201): the alpha byte is dropped, the client rectangle is cut out, and the rectangle is reduced with cv2.resize(...,
+ * interpolation=cv2.INTER_AREA).  One launch takes up to AF_CAPTURE_MAX_FRAMES frames that may differ in size, format, mode, store
+ * and byte order.  Arithmetic: OpenCV 4.x resize.cpp for 8-bit images, per channel, after the alpha drop (alpha never enters a
+ * result), stated in csrc/af_capture.hip and equal, byte for byte, to the numpy restatement tests/capture_ref.py (unpinned against
+ * cv2 itself, absent where this is built):
+ *     COPY    dw == w and dh == h                     the three bytes
+ *     AREA2   w == 2 dw and h == 2 dh                 (a + b + c + d + 2) >> 2
+ *     BOX     w % dw == 0 and h % dh == 0 otherwise   fp32(integer box sum) * fp32(1 / (kx ky)), rounded half to even, saturated
+ *     TABLE   everything else                         computeResizeAreaTab on both axes, fp32 accumulation in table order
+ * Not built: upscaling (dw > w or dh > h is refused), bottom-up bitmaps, 16-bit and float captures.
+ *
+ * af_capture_frame (host description of one frame): src - DEVICE pointer of the first byte of the RECTANGLE, h rows of w pixels of
+ * `channels` (3 or 4) bytes, rows `pitch` bytes apart; src_bgr - non-zero: the bytes of a pixel are B, G, R[, x], zero: R, G, B[, x];
+ * (store, slot) - the destination; (dh, dw) - the destination size, which must be the frame size of stores[store].
+ * af_capture_table_bytes: an upper bound of the table's size for these frames (-1: n or a size out of range).
+ * af_capture_plan_u8 (host only, no device work) fills `table`, a caller-owned HOST buffer (pinned, for an asynchronous copy), 8-byte
+ * aligned, and sets *used_bytes.  Layout: af_capture_header; n af_capture_item (absolute addresses, pitches, sizes, mode, swap - the
+ * store's bgr differs from src_bgr - and byte offsets of the area tables from the table's start, so the table may be copied
+ * anywhere); then one area table per distinct (w -> dw) and per distinct (h -> dh) of the TABLE jobs, shared by the jobs of one
+ * geometry: int32 first[d + 1] (the taps of destination index i are [first[i], first[i + 1])), padded to 8 bytes, then the
+ * af_capture_tap list in OpenCV's table order.  Cell bounds are fp64 and weights are cast to fp32, here on the host.
+ * AF_ERR_ARG: more than AF_CAPTURE_MAX_FRAMES frames, a side outside [1, AF_CAPTURE_MAX_SIDE], dw > w or dh > h, a pitch below
+ * w * channels, channels not 3 or 4, a bad store or slot, a store of another frame size, a null pointer, a table buffer that is too
+ * small.  A refused table's header is stamped (kind = -1) so that no launch takes it.
+ * af_capture_to_stores_u8 launches over a DEVICE copy of the table.  It trusts the table as the resize launch trusts its own; the
+ * kernel compares the header with n and writes nothing on a mismatch (the call still returns AF_OK).  Whatever the alignment of
+ * source, pitch and destination rows, reads stay inside [src, src + pitch * (h - 1) + w * channels) and writes are exactly dh rows
+ * of 3 * dw bytes.  The source must be ready on `stream` and stay unchanged until the launch has run. */
+#define AF_CAPTURE_MAX_FRAMES 64
+#define AF_CAPTURE_MAX_SIDE 8192
+#define AF_CAPTURE_KIND 0x31504143             /* "CAP1" */
+enum af_capture_mode { AF_CAPTURE_COPY = 0, AF_CAPTURE_AREA2 = 1, AF_CAPTURE_BOX = 2, AF_CAPTURE_TABLE = 3 };
+typedef struct af_capture_frame {
+    const void* src;
+    int64_t pitch;
+    int32_t h, w;
+    int32_t channels, src_bgr;
+    int32_t store, slot;
+    int32_t dh, dw;
+} af_capture_frame;
+typedef struct af_capture_header {
+    int32_t kind, n, total_tiles, used_bytes;
+    int32_t first_tile[AF_CAPTURE_MAX_FRAMES + 1];     /* prefix sum of the items' tiles; [n ..] = total_tiles */
+    int32_t reserved[3];
+} af_capture_header;
+typedef struct af_capture_item {
+    const void* src;                                   /* first byte of the rectangle */
+    void* dst;                                         /* first byte of the store's slot */
+    int32_t src_pitch, dst_pitch;
+    int32_t h, w, dh, dw;
+    int32_t mode, runs_x;                              /* af_capture_mode; runs of 4 pixels per destination row */
+    int32_t xtab, ytab;                                /* TABLE: byte offsets of the two area tables */
+    int32_t kx, ky;                                    /* BOX: w / dw and h / dh */
+    float inv_area;                                    /* BOX: fp32(1) / fp32(kx * ky) */
+    uint8_t channels, swap, dword, xk;                 /* dword: 4 channels, source address and pitch 4-byte aligned; xk - TABLE: the
+                                                          most taps one destination column has (255: that many or more) */
+} af_capture_item;
+typedef struct af_capture_tap {
+    int32_t idx;                                       /* source column or row, 0 .. size - 1 */
+    float weight;
+} af_capture_tap;
+int64_t af_capture_table_bytes(const af_capture_frame* frames, int n);
+int af_capture_plan_u8(const af_capture_frame* frames, int n, const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes,
+                       int64_t* used_bytes);
+int af_capture_to_stores_u8(const void* table_dev, int n, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,

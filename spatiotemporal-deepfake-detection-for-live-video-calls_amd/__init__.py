@@ -15,7 +15,7 @@ def __getattr__(name):
     if name == "VideoRunner":
         from . import runner
         return runner.VideoRunner
-    if name in ("YuvFrame", "FrameResizer"):
+    if name in ("YuvFrame", "CapturedFrame", "FrameResizer"):
         from . import frames
         return getattr(frames, name)
     if name == "ByteTracker":

@@ -113,6 +113,36 @@ class ResizeCoef(C.Structure):
     _fields_ = [("idx", C.c_int32), ("a0", C.c_int16), ("a1", C.c_int16)]
 
 
+class CaptureFrame(C.Structure):
+    """af_capture_frame: the rectangle of one captured bitmap on the device and the store slot it goes into"""
+    _fields_ = [("src", C.c_void_p), ("pitch", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("channels", C.c_int32), ("src_bgr", C.c_int32),
+                ("store", C.c_int32), ("slot", C.c_int32), ("dh", C.c_int32), ("dw", C.c_int32)]
+
+
+CAPTURE_MAX_FRAMES, CAPTURE_MAX_SIDE, CAPTURE_KIND = 64, 8192, 0x31504143
+CAPTURE_COPY, CAPTURE_AREA2, CAPTURE_BOX, CAPTURE_TABLE = 0, 1, 2, 3
+CAPTURE_RUN, CAPTURE_TILE = 4, 256
+
+
+class CaptureHeader(C.Structure):
+    """af_capture_header: the first bytes of the table af_capture_plan_u8 fills"""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("total_tiles", C.c_int32), ("used_bytes", C.c_int32),
+                ("first_tile", C.c_int32 * (CAPTURE_MAX_FRAMES + 1)), ("reserved", C.c_int32 * 3)]
+
+
+class CaptureItem(C.Structure):
+    """af_capture_item: one frame as the kernel reads it"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_pitch", C.c_int32), ("dst_pitch", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("dh", C.c_int32), ("dw", C.c_int32), ("mode", C.c_int32), ("runs_x", C.c_int32), ("xtab", C.c_int32), ("ytab", C.c_int32),
+                ("kx", C.c_int32), ("ky", C.c_int32), ("inv_area", C.c_float), ("channels", C.c_uint8), ("swap", C.c_uint8),
+                ("dword", C.c_uint8), ("xk", C.c_uint8)]
+
+
+class CaptureTap(C.Structure):
+    """af_capture_tap: one entry of an area table: source index and fp32 weight"""
+    _fields_ = [("idx", C.c_int32), ("weight", C.c_float)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n", "t", "h", "w", "c", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw", "to", "ho", "wo", "dtype",
@@ -229,6 +259,9 @@ ABI = {
     "af_resize_table_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
     "af_resize_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "af_resize_frames_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "af_capture_table_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
+    "af_capture_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "af_capture_to_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6

@@ -31,7 +31,7 @@ import torch
 
 from ._staging import _COPY_THREADS, _SPLIT_BYTES, PinnedRing, _pool, crop_rect, cuda_device, is_crop, packed_rgb, stage_rects
 from .aligner import STD_POINTS_256, canvas_misfit, fit_window
-from .frames import YuvConverter, YuvFrame, StoreTable
+from .frames import CaptureConverter, ConvertedFrame, YuvConverter, YuvFrame, StoreTable
 
 _FRAME_DTYPE = np.dtype([("offset", "<i8"), ("ih", "<i4"), ("iw", "<i4"), ("x", "<i4"), ("y", "<i4")])       # af_align_frame
 _RECT_DTYPE = np.dtype([(n, "<i4") for n in ("frame", "rx", "ry", "ih", "iw", "x", "y", "reserved")])            # af_frame_rect
@@ -373,13 +373,13 @@ class CropPool(_Resident):
 class FrameStore(_Resident):
     """`capacity` decoded frames of one `shape`, packed, slot after slot in one device buffer: a whole video, a window through
     which a longer one passes, or a ring of a call's last frames.  ``channel_order``: the byte order of a pixel in the store,
-    which only a conversion into the store needs to know (``YuvFrame``s); numpy frames are stored as they come."""
+    which only a conversion into the store needs to know (``YuvFrame``s, ``CapturedFrame``s); numpy frames are stored as they come."""
 
     def __init__(self, device, channel_order: str = "rgb"):
         super().__init__(device)
         self.shape, self.frame_nbytes, self.capacity = None, 0, 0
         self.channel_order = channel_order
-        self._yuv = None
+        self._yuv = self._capture = None
 
     def open(self, shape, capacity: int):
         self.shape, self.capacity = tuple(shape), int(capacity)
@@ -394,10 +394,11 @@ class FrameStore(_Resident):
 
         A list of ``YuvFrame`` (a list is all numpy or all ``YuvFrame``) is converted on the way: host planes go tightly into
         a pinned slot (1.5 bytes per pixel), one copy moves them to the slot's device twin and one ``af_yuv420_to_rgb_u8`` launch
-        per staging slot writes the store's slots in its ``channel_order``; device-resident planes are read where they are."""
+        per staging slot writes the store's slots in its ``channel_order``; device-resident planes are read where they are.
+        A list of ``CapturedFrame`` goes the same way through ``af_capture_to_stores_u8``: only each frame's rectangle is staged."""
         from . import _lib
-        if any(isinstance(f, YuvFrame) for f in frames):
-            return self._put_yuv(list(frames), first_slot)
+        if any(isinstance(f, ConvertedFrame) for f in frames):
+            return self._put_converted(list(frames), first_slot)
         h, w = self.shape[:2]
         fb, row = self.frame_nbytes, w * 3
         per_slot = max(1, _STAGE_BYTES // fb)
@@ -426,21 +427,23 @@ class FrameStore(_Resident):
                 np.copyto(*strided[0])
             self._send(slot, used, (first_slot + i) * fb)
 
-    def _put_yuv(self, frames, first_slot: int):
-        """``put`` for ``YuvFrame``s: chunks of at most ``_STAGE_BYTES`` of host planes and ``AF_YUV_MAX_FRAMES`` frames, each one
-        fill, one copy and one launch"""
-        from . import _lib
-        if not all(isinstance(f, YuvFrame) for f in frames):
-            raise ValueError("evaluator: a list of frames is all numpy arrays or all YuvFrame")
-        if self._yuv is None:
-            self._yuv = YuvConverter(self.device, self._stage)
+    def _put_converted(self, frames, first_slot: int):
+        """``put`` for ``YuvFrame``s or ``CapturedFrame``s: chunks of at most ``_STAGE_BYTES`` of host bytes and one launch's frames,
+        each one fill, one copy and one launch"""
+        kind = type(frames[0])
+        if not issubclass(kind, ConvertedFrame) or not all(type(f) is kind for f in frames):
+            raise ValueError("evaluator: a list of frames is all numpy arrays or all YuvFrame or all CapturedFrame")
+        if kind is YuvFrame:
+            converter = self._yuv = self._yuv if self._yuv is not None else YuvConverter(self.device, self._stage)
+        else:
+            converter = self._capture = self._capture if self._capture is not None else CaptureConverter(self.device, self._stage)
         i = 0
         while i < len(frames):
             j, used = i, 0
-            while j < len(frames) and j - i < _lib.YUV_MAX_FRAMES and (j == i or used + frames[j].upload_bytes <= _STAGE_BYTES):
+            while j < len(frames) and j - i < converter.max_frames and (j == i or used + frames[j].upload_bytes <= _STAGE_BYTES):
                 used += frames[j].upload_bytes
                 j += 1
-            self._yuv.convert([(f, self, self.channel_order, first_slot + k) for k, f in enumerate(frames[i:j], i)])
+            converter.convert([(f, self, self.channel_order, first_slot + k) for k, f in enumerate(frames[i:j], i)])
             self.uploaded_bytes += used
             i = j
 

@@ -13,7 +13,15 @@ fallback: without the HIP library the conversion fails.
 ``FrameResizer`` is the other direction: ``cv2.resize(frame, (dw, dh))`` (the default ``INTER_LINEAR``) of frames that already sit on
 the device - slots of frame stores, views, a batch - into one detector batch, in one launch of ``af_resize_frames_u8`` per
 ``AF_RESIZE_MAX_FRAMES`` frames (csrc/af_resize.hip).  It equals tests/resize_ref.py, the numpy restatement of OpenCV's plain C++
-path, byte for byte; that restatement is unpinned against cv2 itself, and an IPP-enabled OpenCV may differ from it."""
+path, byte for byte; that restatement is unpinned against cv2 itself, and an IPP-enabled OpenCV may differ from it.
+
+``CapturedFrame`` is the entry for what a screen or window capture hands over: a BGRA (RGBA, BGR, RGB) bitmap, its client rectangle
+and the reference's ``max_w`` rule.  ``CaptureConverter`` puts every such frame of a call into its store slot in one launch of
+``af_capture_to_stores_u8`` per ``AF_CAPTURE_MAX_FRAMES`` frames (csrc/af_capture.hip), which drops the alpha byte, cuts the
+rectangle, orders the bytes as the store has them and reduces with ``cv2.INTER_AREA``'s arithmetic (OpenCV 4.x resize.cpp).  It equals
+tests/capture_ref.py byte for byte; that statement is pinned by hand-worked anchors and by its tie to tests/quality_ref.py's
+``half_size``, not against cv2 itself.  Not built: upscaling, ``INTER_AREA`` inside ``FrameResizer``, bottom-up bitmaps, 16-bit and
+float captures.  There is no CPU fallback here either."""
 import ctypes as C
 from typing import List, Optional, Sequence, Tuple
 
@@ -50,7 +58,21 @@ def _plane(name: str, p):
     return dev, rows, row, pitch
 
 
-class YuvFrame:
+class ConvertedFrame:
+    """A frame that is converted on its way into a frame store (``YuvFrame``, ``CapturedFrame``) instead of being copied as it is:
+    ``shape`` is the (h, w, 3) of the stored frame, ``on_device`` / ``device`` say where its bytes are, ``nbytes`` is what staging
+    a host frame copies, ``planes()`` lists those bytes as ``[(array, rows, row bytes, pitch)]`` in staging order, and ``converter``
+    is the class whose ``convert`` takes it.  What admits frames tests for this class, not for its kinds."""
+    __slots__ = ()
+    converter = None
+
+    @property
+    def upload_bytes(self) -> int:
+        """what admitting the frame sends to the device: its bytes, or nothing when they are already there"""
+        return 0 if self.on_device else self.nbytes
+
+
+class YuvFrame(ConvertedFrame):
     """One YUV 4:2:0 frame: ``YuvFrame(fmt, y, u=None, v=None, uv=None)``.
 
     ``fmt``: ``"nv12"`` / ``"nv21"`` (``y`` and one interleaved plane ``uv`` of (h / 2, w) bytes: U, V, U, V ... - V first for nv21) or
@@ -125,11 +147,6 @@ class YuvFrame:
         return self.shape[0] * self.shape[1] * 3 // 2
 
     @property
-    def upload_bytes(self) -> int:
-        """what admitting the frame sends to the device: its planes, or nothing when they are already there"""
-        return 0 if self.on_device else self.nbytes
-
-    @property
     def device(self) -> Optional[torch.device]:
         return self.y.device if self.on_device else None
 
@@ -138,9 +155,95 @@ class YuvFrame:
         return self._planes
 
 
+# format -> (bytes per pixel, the first byte of a pixel is B)
+CAPTURE_FORMATS = {"bgra": (4, True), "rgba": (4, False), "bgr": (3, True), "rgb": (3, False)}
+
+
+def capture_size(h: int, w: int, max_w: int) -> Tuple[int, int]:
+    """``(dw, dh)`` a captured h x w frame is stored at (test/capture_tile.py:199-201): down to `max_w` columns when it has more,
+    the height by the same ratio in Python floats, truncated; unchanged otherwise"""
+    if max_w > 0 and w > max_w:
+        return int(max_w), int(h * (max_w / w))
+    return int(w), int(h)
+
+
+class CapturedFrame(ConvertedFrame):
+    """One captured bitmap: ``CapturedFrame(pixels, fmt="bgra", rect=None, max_w=0, size=None)``.
+
+    ``pixels``: (H, W, 4) uint8 for ``"bgra"`` / ``"rgba"`` or (H, W, 3) for ``"bgr"`` / ``"rgb"`` - a numpy array, or a CUDA tensor
+    on the device of the store it goes to - with unit element stride, a pixel stride of its channels and any row pitch of at least
+    the row; top-down.  The fourth byte never reaches a result.  ``rect = (x0, y0, x1, y1)``: the client area, inside the frame
+    (default: all of it).  The stored size: ``capture_size(rh, rw, max_w)`` of the rectangle - the reference's rule - or
+    ``size = (dw, dh)``, which must not exceed the rectangle (upscaling is not built); a smaller size is reached with
+    ``cv2.INTER_AREA``'s arithmetic on the device.  ``shape`` is the STORED ``(dh, dw, 3)``: rings, stores and trackers downstream
+    see the downscaled frame, as the reference's loop does.
+
+    Of a host frame only the rectangle is copied (rh tight rows of rw * channels bytes into a pinned slot) before the call that
+    takes the frame returns.  A device frame is read where it lies, under ``YuvFrame``'s stream contract: ready on the stream that
+    is current when the frame is handed in, unchanged until the work that call enqueued has run."""
+
+    __slots__ = ("fmt", "pixels", "rect", "shape", "on_device", "channels", "src_bgr", "pitch", "rect_shape", "_view")
+
+    def __init__(self, pixels, fmt: str = "bgra", rect=None, max_w: int = 0, size=None):
+        if fmt not in CAPTURE_FORMATS:
+            raise ValueError("capture: format %r is not one of %s" % (fmt, ", ".join(sorted(CAPTURE_FORMATS))))
+        ch, self.src_bgr = CAPTURE_FORMATS[fmt]
+        if isinstance(pixels, np.ndarray):
+            dev, dtype_ok, strides = False, pixels.dtype == np.uint8, pixels.strides
+        elif isinstance(pixels, torch.Tensor):
+            if not pixels.is_cuda:
+                raise ValueError("capture: the pixels are a CPU tensor: a numpy array or a CUDA tensor")
+            dev, dtype_ok, strides = True, pixels.dtype == torch.uint8, tuple(pixels.stride())
+        else:
+            raise ValueError("capture: the pixels are a %s: a numpy array or a CUDA tensor" % type(pixels).__name__)
+        if not dtype_ok or pixels.ndim != 3:
+            raise ValueError("capture: the pixels must be a 3-D uint8 array")
+        H, W = int(pixels.shape[0]), int(pixels.shape[1])
+        if int(pixels.shape[2]) != ch:
+            raise ValueError("capture: %s pixels have %d channels, the array has %d" % (fmt, ch, int(pixels.shape[2])))
+        if H < 1 or W < 1:
+            raise ValueError("capture: the frame is empty (%d x %d)" % (H, W))
+        if strides[2] != 1:
+            raise ValueError("capture: element stride %d: the bytes of a pixel must be contiguous" % strides[2])
+        if W > 1 and strides[1] != ch:
+            raise ValueError("capture: pixel stride %d, not the %d bytes of a %s pixel" % (strides[1], ch, fmt))
+        pitch = int(strides[0]) if H > 1 else W * ch
+        if pitch < W * ch:
+            raise ValueError("capture: row pitch %d, shorter than a row of %d bytes" % (pitch, W * ch))
+        x0, y0, x1, y1 = (0, 0, W, H) if rect is None else (int(v) for v in rect)
+        if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+            raise ValueError("capture: rect (%d, %d, %d, %d) leaves the frame of %d x %d" % (x0, y0, x1, y1, W, H))
+        rh, rw = y1 - y0, x1 - x0
+        if size is not None:
+            dw, dh = int(size[0]), int(size[1])
+            if dw > rw or dh > rh:
+                raise ValueError("capture: size %d x %d exceeds the rectangle of %d x %d: upscaling is not built" % (dw, dh, rw, rh))
+        else:
+            dw, dh = capture_size(rh, rw, int(max_w))
+        if dw < 1 or dh < 1:
+            raise ValueError("capture: a stored size of %d x %d" % (dw, dh))
+        self.fmt, self.pixels, self.rect, self.channels, self.pitch, self.on_device = fmt, pixels, (x0, y0, x1, y1), ch, pitch, dev
+        self.rect_shape, self.shape = (rh, rw), (dh, dw, 3)
+        self._view = pixels[y0:y1, x0:x1]
+
+    @property
+    def nbytes(self) -> int:
+        """the bytes of the rectangle: what staging a host frame copies"""
+        return self.rect_shape[0] * self.rect_shape[1] * self.channels
+
+    @property
+    def device(self) -> Optional[torch.device]:
+        return self.pixels.device if self.on_device else None
+
+    def planes(self):
+        """``[(the rectangle, rows, row bytes, pitch)]``: one plane"""
+        rh, rw = self.rect_shape
+        return [(self._view, rh, rw * self.channels, self.pitch)]
+
+
 def upload_bytes(frame) -> int:
-    """the bytes a frame sends to the device when it is admitted: a numpy frame's own, a ``YuvFrame``'s planes if they are on the host"""
-    return frame.upload_bytes if isinstance(frame, YuvFrame) else frame.nbytes
+    """the bytes a frame sends to the device when it is admitted: a numpy frame's own, a ``ConvertedFrame``'s if they are on the host"""
+    return frame.upload_bytes if isinstance(frame, ConvertedFrame) else frame.nbytes
 
 
 def store_ref(store, channel_order: str):
@@ -207,19 +310,82 @@ def stage_planes(base: int, frames: Sequence[YuvFrame], offs: Sequence[int], nby
         stage_rects(base, (_lib.StageRect * len(rects))(*rects), len(rects), nbytes)
 
 
-class YuvConverter:
-    """``convert([(YuvFrame, FrameStore, channel_order, slot), ...])``: every frame into its slot of its store, converted on the
-    device.  The host planes of all frames go tightly into ONE pinned slot and cross in ONE asynchronous copy; one launch per
-    ``AF_YUV_MAX_FRAMES`` frames follows on the current stream and reads host frames from the slot's device twin, device-resident
-    ones where they are.  The slot's event is recorded behind the last launch, the last reader of both buffers; nothing waits.
-    ``launches`` and ``copies`` count what was enqueued."""
+class _Converter:
+    """``convert([(frame, FrameStore, channel_order, slot), ...])`` for one kind of ``ConvertedFrame``: every frame into its slot of
+    its store, converted on the device.  The host bytes of all frames go tightly into ONE pinned slot - behind them, for a kind
+    whose launch reads its table from device memory, the tables of the launches - and cross in ONE asynchronous copy; one launch per
+    ``max_frames`` frames follows on the current stream and reads host frames from the slot's device twin, device-resident ones
+    where they are.  The slot's event is recorded behind the last launch, the last reader of both buffers; nothing waits.
+    ``launches`` and ``copies`` count what was enqueued.  A kind says: ``frame_type``, ``what`` (its word in messages),
+    ``max_frames``, ``stat_keys`` (a server's counters of its launches and copies), ``_room`` and ``_plan``."""
+    frame_type, what, holds, max_frames, stat_keys = None, "", "bytes", 0, (None, None)
 
     def __init__(self, device, stage: Optional[PinnedRing] = None):
         from . import _lib                                        # fails loudly when libafhip.so is missing
         self.device = device
         self._stage = stage if stage is not None else PinnedRing(min_bytes=1 << 20, headroom=True)
-        self._launch = _lib.lib.af_yuv420_to_rgb_u8
         self.launches = self.copies = 0
+
+    def _room(self, frames) -> int:
+        """the bytes the table of one launch over `frames` may need in the staging slot (0: the table travels by value)"""
+        return 0
+
+    def _plan(self, frames, addresses, refs, slots, table_host: int, table_dev: int, room: int):
+        """plans one launch -> (the bytes of the table written at `table_host`, ``launch(stream)``)"""
+        raise NotImplementedError
+
+    def convert(self, jobs) -> None:
+        jobs = list(jobs)
+        if not jobs:
+            return
+        frames = [j[0] for j in jobs]
+        for f, store, order, slot in jobs:
+            if not isinstance(f, self.frame_type):
+                raise ValueError("%s: a list of frames is all numpy arrays or all YuvFrame or all CapturedFrame" % self.what)
+            if tuple(f.shape) != tuple(store.shape):
+                raise ValueError("%s: a frame of %s for a store of %s" % (self.what, f.shape, tuple(store.shape)))
+            if f.on_device and f.device != store.device:
+                raise ValueError("%s: the %s are on %s, the frame store on %s" % (self.what, self.holds, f.device, store.device))
+        table = StoreTable()
+        refs = [table.refs[table.index(j[1], j[2])] for j in jobs]
+        with torch.cuda.device(self.device):
+            offs, used = staged_offsets(frames)
+            parts, total = [], used
+            for lo in range(0, len(jobs), self.max_frames):
+                hi = min(lo + self.max_frames, len(jobs))
+                room = self._room(frames[lo:hi])
+                if room:
+                    total = -(-total // _FRAME_ALIGN) * _FRAME_ALIGN
+                parts.append((lo, hi, total, room))
+                total += room
+            slot, host_base, dev_base = None, 0, 0
+            if total:
+                slot = self._stage.acquire(total, self.device)
+                host_base, dev_base = slot.host.data_ptr(), slot.dev.data_ptr()
+            if used:
+                stage_planes(host_base, frames, offs, used)
+            end, launches = used, []
+            for lo, hi, at, room in parts:
+                wrote, launch = self._plan(frames[lo:hi], [None if o < 0 else dev_base + o for o in offs[lo:hi]], refs[lo:hi],
+                                           [j[3] for j in jobs[lo:hi]], host_base + at, dev_base + at, room)
+                if wrote:
+                    end = at + wrote
+                launches.append(launch)
+            if end:
+                slot.dev[:end].copy_(slot.host[:end], non_blocking=True)
+                self.copies += 1
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            for launch in launches:
+                launch(stream)
+                self.launches += 1
+            if slot is not None:
+                slot.record()          # behind the last launch: it reads the device twin, which the next copy into this slot rewrites
+
+
+class YuvConverter(_Converter):
+    """``_Converter`` for ``YuvFrame``s: one launch of ``af_yuv420_to_rgb_u8`` per ``AF_YUV_MAX_FRAMES`` frames; its table travels
+    to the kernel by value, so ``copies`` counts the copies of staged host planes alone"""
+    frame_type, what, holds, max_frames, stat_keys = YuvFrame, "yuv", "planes", 64, ("convert", "yuv_copies")
 
     @staticmethod
     def table(frames: Sequence[YuvFrame], addresses: Sequence[int], stores, slots: Sequence[int]):
@@ -247,39 +413,68 @@ class YuvConverter:
         _lib.check(_lib.lib.af_yuv420_plan_u8(C.byref(descs), len(frames), C.byref(store_arr), len(refs), C.byref(items)), "yuv420_plan_u8")
         return items
 
-    def convert(self, jobs) -> None:
+    def _plan(self, frames, addresses, refs, slots, table_host, table_dev, room):
         from . import _lib
-        jobs = list(jobs)
-        if not jobs:
-            return
-        frames = [j[0] for j in jobs]
-        for f, store, order, slot in jobs:
-            if not isinstance(f, YuvFrame):
-                raise ValueError("yuv: a list of frames is all numpy arrays or all YuvFrame")
-            if tuple(f.shape) != tuple(store.shape):
-                raise ValueError("yuv: a frame of %s for a store of %s" % (f.shape, tuple(store.shape)))
-            if f.on_device and f.device != store.device:
-                raise ValueError("yuv: the planes are on %s, the frame store on %s" % (f.device, store.device))
-        table = StoreTable()
-        refs = [table.refs[table.index(j[1], j[2])] for j in jobs]
-        with torch.cuda.device(self.device):
-            offs, used = staged_offsets(frames)
-            slot, dev_base = None, 0
-            if used:
-                slot = self._stage.acquire(used, self.device)
-                stage_planes(slot.host.data_ptr(), frames, offs, used)
-                slot.dev[:used].copy_(slot.host[:used], non_blocking=True)
-                self.copies += 1
-                dev_base = slot.dev.data_ptr()
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            for lo in range(0, len(jobs), _lib.YUV_MAX_FRAMES):
-                part = jobs[lo:lo + _lib.YUV_MAX_FRAMES]
-                items = self.table([j[0] for j in part], [None if o < 0 else dev_base + o for o in offs[lo:lo + len(part)]],
-                                   refs[lo:lo + len(part)], [j[3] for j in part])
-                _lib.check(self._launch(C.byref(items), len(part), stream), "yuv420_to_rgb_u8")
-                self.launches += 1
-            if slot is not None:
-                slot.record()          # behind the last launch: it reads the device twin, which the next copy into this slot rewrites
+        items, n = self.table(frames, addresses, refs, slots), len(frames)
+        return 0, lambda stream: _lib.check(_lib.lib.af_yuv420_to_rgb_u8(C.byref(items), n, stream), "yuv420_to_rgb_u8")
+
+
+class CaptureConverter(_Converter):
+    """``_Converter`` for ``CapturedFrame``s: ``CaptureConverter(device, stage=None).convert([(frame, store, channel_order, slot),
+    ...])`` - one pinned fill, one copy and one launch of ``af_capture_to_stores_u8`` per ``AF_CAPTURE_MAX_FRAMES`` frames, which may
+    differ in size, format, rectangle, mode, store and byte order.  The launch reads its table (it holds the area tables) from
+    device memory: the tables lie behind the pixels in the same pinned slot and cross in the same copy, so ``copies`` is one per
+    ``convert`` - also for device-resident frames, whose table still has to cross."""
+    frame_type, what, holds, max_frames, stat_keys = CapturedFrame, "capture", "pixels", 64, ("capture", None)
+
+    @staticmethod
+    def descs(frames: Sequence[CapturedFrame], addresses: Sequence[Optional[int]], stores, slots: Sequence[int]):
+        """``frames[i]`` whose rectangle lies tight at device address ``addresses[i]`` (None: where the frame's own device pixels
+        are, at their pitch) into slot ``slots[i]`` of ``stores[i]`` (an ``_lib.StoreRef`` each) -> (the ``af_capture_frame`` array,
+        the ``af_store_ref`` array, its length)"""
+        from . import _lib
+        refs, index, descs = [], {}, (_lib.CaptureFrame * max(1, len(frames)))()
+        for i, (f, base, ref, slot) in enumerate(zip(frames, addresses, stores, slots)):
+            if id(ref) not in index:
+                index[id(ref)] = len(refs)
+                refs.append(ref)
+            (rh, rw), (dh, dw, _) = f.rect_shape, f.shape
+            src, pitch = (_address(f._view), f.pitch) if base is None else (base, rw * f.channels)
+            descs[i] = _lib.CaptureFrame(src, pitch, rh, rw, f.channels, int(f.src_bgr), index[id(ref)], int(slot), dh, dw)
+        return descs, (_lib.StoreRef * max(1, len(refs)))(*refs), len(refs)
+
+    @staticmethod
+    def table_bytes(frames: Sequence[CapturedFrame]) -> int:
+        """an upper bound of the bytes of the table of one launch over `frames`"""
+        from . import _lib
+        descs = (_lib.CaptureFrame * max(1, len(frames)))(*[_lib.CaptureFrame(None, 0, f.rect_shape[0], f.rect_shape[1], f.channels, 0, 0, 0,
+                                                                                 f.shape[0], f.shape[1]) for f in frames])
+        n = _lib.lib.af_capture_table_bytes(C.byref(descs), len(frames))
+        if n < 0:
+            raise ValueError("capture: %d frames of %s: at most %d per launch, every side 1 to %d, no upscaling"
+                             % (len(frames), sorted({f.rect_shape + f.shape[:2] for f in frames}), _lib.CAPTURE_MAX_FRAMES, _lib.CAPTURE_MAX_SIDE))
+        return n
+
+    @staticmethod
+    def table(frames, addresses, stores, slots, table_address: int, table_bytes: int) -> int:
+        """the planner's part, host only: the table of one launch at host address `table_address`; returns the bytes used"""
+        from . import _lib
+        descs, store_arr, n_stores = CaptureConverter.descs(frames, addresses, stores, slots)
+        used = C.c_int64(0)
+        _lib.check(_lib.lib.af_capture_plan_u8(C.byref(descs), len(frames), C.byref(store_arr), n_stores, C.c_void_p(table_address), table_bytes,
+                                               C.byref(used)), "capture_plan_u8")
+        return used.value
+
+    def _room(self, frames) -> int:
+        return self.table_bytes(frames)
+
+    def _plan(self, frames, addresses, refs, slots, table_host, table_dev, room):
+        from . import _lib
+        used, n = self.table(frames, addresses, refs, slots, table_host, room), len(frames)
+        return used, lambda stream: _lib.check(_lib.lib.af_capture_to_stores_u8(C.c_void_p(table_dev), n, stream), "capture_to_stores_u8")
+
+
+CapturedFrame.converter, YuvFrame.converter = CaptureConverter, YuvConverter
 
 
 def _tensor_ref(t: torch.Tensor):

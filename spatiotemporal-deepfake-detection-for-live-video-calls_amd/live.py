@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ._staging import is_crop
-from .frames import FrameResizer, YuvConverter, YuvFrame, StoreTable, upload_bytes
+from .frames import ConvertedFrame, FrameResizer, StoreTable, upload_bytes
 from .aligner import STD_POINTS_256
 from .evaluator import (RECTS, RECTS_BGR, FrameStore, StoresWarp, WindowWarp, _clip_buffers, _fit, _FrameTrack, _network_device, _padded, get_crop_box,
                         partition)
@@ -170,9 +170,9 @@ class LiveCall:
     def admit_books(self, frame) -> int:
         """``admit`` without the pixels: checks the frame, counts it and re-opens the ring when its size has changed; returns its
         index.  The caller then moves the pixels into ring slot ``index % ring_frames`` (``CallServer`` does, for all its calls'
-        ``YuvFrame``s at once)."""
-        if not isinstance(frame, YuvFrame) and (not is_crop(frame) or not frame.flags.c_contiguous):
-            raise AssertionError("live: a frame must be a C-contiguous HxWx3 uint8 numpy array")
+        converted frames - ``YuvFrame``s, ``CapturedFrame``s - at once)."""
+        if not isinstance(frame, ConvertedFrame) and (not is_crop(frame) or not frame.flags.c_contiguous):
+            raise AssertionError("live: a frame must be a C-contiguous HxWx3 uint8 numpy array, a YuvFrame or a CapturedFrame")
         self.frame_idx += 1
         if self._shape != tuple(frame.shape):
             self._open_ring(frame.shape)
@@ -778,14 +778,16 @@ class ServerStats:
     """what a ``CallServer`` enqueued and waited for: ``last`` for the last step, ``total`` since the server was made, each with
     ``detect`` (calls of ``af_yunet_detect_frames``, or of a detector's ``detect_views``), ``quality``, ``warp`` (launches),
     ``replay`` (graph replays), ``wait`` (host waits for the device), ``convert`` (launches of ``af_yuv420_to_rgb_u8``),
-    ``yuv_copies`` (host-to-device copies of staged YUV planes) and ``resize`` (launches of ``af_resize_frames_u8``)"""
+    ``yuv_copies`` (host-to-device copies of staged YUV planes), ``capture`` (launches of ``af_capture_to_stores_u8``) and ``resize``
+    (launches of ``af_resize_frames_u8``)"""
     KEYS = ("detect", "quality", "warp", "replay", "wait")
     YUV_KEYS = ("convert", "yuv_copies")       # appear in ``last`` / ``total`` once a step has YUV frames; read as 0 before
+    CAPTURE_KEYS = ("capture",)                # likewise once a step has captured frames
     RESIZE_KEYS = ("resize",)                  # likewise once a call with a ``detect_size`` has detected
 
     class _Counts(dict):
         def __missing__(self, key):
-            if key in ServerStats.YUV_KEYS or key in ServerStats.RESIZE_KEYS:
+            if key in ServerStats.YUV_KEYS or key in ServerStats.CAPTURE_KEYS or key in ServerStats.RESIZE_KEYS:
                 return 0
             raise KeyError(key)
 
@@ -820,7 +822,8 @@ class CallServer:
     frames resized to dw x dh, as ``RealtimeCall`` does: calls of any frame sizes that share a detect size share one resize launch
     and one ``detect_views``.
 
-    A frame is a numpy array or a ``YuvFrame`` (the mapping may mix them).  The ``YuvFrame``s of a step are admitted together: the
+    A frame is a numpy array, a ``YuvFrame`` or a ``CapturedFrame`` (the mapping may mix them).  The ``CapturedFrame``s of a step are
+    admitted together - one fill, one copy, one ``af_capture_to_stores_u8`` launch per 64 - as are its ``YuvFrame``s: the
     host planes of all calls fill one pinned slot and cross in one copy, and one ``af_yuv420_to_rgb_u8`` launch per 64 frames
     converts them - and the device-resident ones where they lie - into the calls' own ring slots, each in its call's
     ``channel_order``.  The conversion needs no wait.
@@ -858,7 +861,7 @@ class CallServer:
         self._quality = StoresQuality(self.device)
         self._warp = StoresWarp(self.device, self.clip_size, self.size, self.max_batch)
         self._resizer: Optional[FrameResizer] = None        # made when the first call with a ``detect_size`` detects
-        self._yuv = YuvConverter(self.device)     # its own pinned ring: the YUV planes of all calls of a step share one slot
+        self._converters = {}                     # converter class -> one with its own pinned ring: the frames of a kind of all calls of a step share one slot
         self._scoring: Optional[_ClosedWindows] = None      # the clip buffer and the scorers, made when the first window closes
         self._done = None                  # recorded behind the last launch of every step
         self._detections = _Detections()
@@ -912,20 +915,24 @@ class CallServer:
 
     def _step(self, calls, cur):
         ticks = []
-        yuv = []
+        converted = {}
         for cid, c, frame in calls:                                                        # 1. the uploads
-            if isinstance(frame, YuvFrame):                                                # the books now, the pixels of all of them below
+            if isinstance(frame, ConvertedFrame):                                          # the books now, the pixels of all of them below
                 ticks.append(c.call.admit_books(frame))
                 c.call.uploaded_bytes += frame.upload_bytes
-                yuv.append((frame, c.call._ring.store, c.call.channel_order, ticks[-1] % c.call.ring_frames))
+                converted.setdefault(frame.converter, []).append((frame, c.call._ring.store, c.call.channel_order, ticks[-1] % c.call.ring_frames))
             else:
                 ticks.append(c.call.admit(frame))
             self.uploaded_bytes += upload_bytes(frame)
-        if yuv:                                                                            # one fill, one copy, one launch per 64
-            launched, copied = self._yuv.launches, self._yuv.copies
-            self._yuv.convert(yuv)
-            self.stats.count("convert", self._yuv.launches - launched)
-            self.stats.count("yuv_copies", self._yuv.copies - copied)
+        for kind, jobs in converted.items():                                               # per kind one fill, one copy, one launch per 64
+            conv = self._converters.get(kind)
+            if conv is None:
+                conv = self._converters[kind] = kind(self.device)
+            launched, copied = conv.launches, conv.copies
+            conv.convert(jobs)
+            for key, n in zip(conv.stat_keys, (conv.launches - launched, conv.copies - copied)):
+                if key is not None:
+                    self.stats.count(key, n)
         detecting = [i for i, (_, c, _) in enumerate(calls) if ticks[i] % max(1, c.detect_every) == 0]
         dets = dict(zip(detecting, self._detect([calls[i][1].call.frame_view(ticks[i]) for i in detecting],
                                                 [calls[i][1].detect_size for i in detecting])))                    # 2.
