@@ -29,38 +29,23 @@
 // with their neighbours once inlined, so every product and sum here is cp_mul / cp_add, written below a file-scope
 // `#pragma clang fp contract(off)`; the build's ISA holds no fused multiply-add for this kernel.
 //
-// Shape: a memory stream, as af_resize.hip.  A lane owns a run of 4 adjacent pixels of one destination row (12 bytes, three dwords);
-// the runs of an item are numbered row by row, a workgroup of 256 lanes takes 256 consecutive runs (a tile), and the tiles of all
-// items form one flat list with a first_tile prefix in the table's header.  The table lies in device memory (it holds the area
-// tables), so the launch cannot know the tile count: a fixed grid strides over the tiles.  A 4-channel pixel is one dword load when
-// the rectangle's address and pitch are 4-byte aligned (four of them one 16-byte load where the address allows), byte loads otherwise.
+// Shape: a memory stream; the runs, tiles and fixed grid of af_frame_runs.h, which also holds the argument for the writes.  A
+// 4-channel pixel is one dword load when the rectangle's address and pitch are 4-byte aligned (four of them one 16-byte load where
+// the address allows), byte loads otherwise.
 //
-// No stray access.  Reads: a pixel (row, col) with 0 <= row < h, 0 <= col < w is read as the 3 bytes row * pitch + col * channels +
+// No stray access, reads: a pixel (row, col) with 0 <= row < h, 0 <= col < w is read as the 3 bytes row * pitch + col * channels +
 // {0, 1, 2}, or - 4 channels, aligned - as the dword of its 4 bytes; nothing is rounded down or widened past a pixel, so reads stay
 // inside [src, src + pitch * (h - 1) + w * channels).  COPY: row dy < h, columns x0 + i < dw = w.  AREA2: rows 2 dy + 1 < h, columns
 // 2 (x0 + i) + 1 < w.  BOX: rows ky dy + j < h, columns kx (x0 + i) + k < w.  TABLE: the planner refuses a tap outside [0, size).
-// Writes: a full run writes the 12 bytes [12 j, 12 j + 12) of its destination row, as three dwords when the address is 4-byte
-// aligned and as bytes otherwise; the last run of a row with dw % 4 != 0 writes its 3, 6 or 9 bytes as bytes.  Exactly dh rows of
-// 3 dw bytes; nothing goes into the pitch padding, between slots or behind the last row.
 #include <cmath>
-#include <cstring>
-#include <vector>
 
-#include "af_common.h"
+#include "af_frame_runs.h"
 
 namespace af {
-
-constexpr int CP_RUN = 4;                           // pixels of a row one lane produces
-constexpr int CP_TILE = 256;                        // runs per workgroup
-constexpr int CP_GRID = 2048;                       // workgroups of a launch: 8 per CU, each strides over the tiles
 
 static_assert(sizeof(af_capture_header) % 8 == 0 && sizeof(af_capture_item) == 72 && sizeof(af_capture_tap) == 8 && sizeof(af_capture_frame) == 48,
               "table layout");
 
-static inline int64_t capture_tiles(int dh, int dw) {
-    const int64_t runs = (int64_t)dh * ((dw + CP_RUN - 1) / CP_RUN);
-    return (runs + CP_TILE - 1) / CP_TILE;
-}
 static inline int64_t pad8(int64_t v) { return (v + 7) & ~(int64_t)7; }
 
 #pragma clang fp contract(off)                      // from here to the end of the file: a product and a sum stay two roundings
@@ -88,18 +73,11 @@ __device__ __forceinline__ unsigned cp_ch(unsigned px, int c) { return (px >> (8
 __device__ __forceinline__ unsigned cp_area2(unsigned a, unsigned b, unsigned c, unsigned d) {
     unsigned out = 0;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) out |= ((cp_ch(a, k) + cp_ch(b, k) + cp_ch(c, k) + cp_ch(d, k) + 2u) >> 2) << (8 * k);
+    for (int k = 0; k < 3; ++k) out |= area2(cp_ch(a, k), cp_ch(b, k), cp_ch(c, k), cp_ch(d, k)) << (8 * k);
     return out;
 }
 // cvRound and saturate_cast<uchar>: half to even, then clamped
 __device__ __forceinline__ unsigned cp_round(float v) { return (unsigned)min(max(__float2int_rn(v), 0), 255); }
-
-// four pixels (24 bits each) -> the 12 bytes of a run
-__device__ __forceinline__ void cp_pack(const unsigned (&px)[4], unsigned (&out)[3]) {
-    out[0] = px[0] | (px[1] << 24);
-    out[1] = (px[1] >> 8) | (px[2] << 16);
-    out[2] = (px[2] >> 16) | (px[3] << 8);
-}
 
 // TABLE mode of one run whose destination columns have at most K taps each: the x taps of the 4 pixels are read once, every source
 // row then issues its 4 K pixel loads together.  A slot past a pixel's taps repeats the run's first tap (a valid column) with weight
@@ -138,30 +116,19 @@ __device__ __forceinline__ void cp_table_run(const unsigned char* src, int pitch
     }
 }
 
-__global__ __launch_bounds__(CP_TILE) void capture_frames_kernel(const unsigned char* __restrict__ table, int n) {
-    const af_capture_header* hd = (const af_capture_header*)table;
-    if (hd->kind != AF_CAPTURE_KIND || hd->n != n) return;          // not this launch's table (or a refused one): write nothing
-    const af_capture_item* items = (const af_capture_item*)(table + sizeof(af_capture_header));
-    const int total = hd->total_tiles;
-    for (int tile = blockIdx.x; tile < total; tile += gridDim.x) {
-        int k = 0, hi = n - 1;                                       // the last item whose first tile is <= tile
-        while (k < hi) {
-            const int mid = (k + hi + 1) >> 1;
-            if (hd->first_tile[mid] <= tile) k = mid; else hi = mid - 1;
-        }
-        const af_capture_item it = items[k];
-        const int run = (tile - hd->first_tile[k]) * CP_TILE + (int)threadIdx.x;
-        if (run >= it.dh * it.runs_x) continue;
-        const int dy = run / it.runs_x, j = run - dy * it.runs_x;
-        const int x0 = j * CP_RUN, npx = min(CP_RUN, it.dw - x0);
+__global__ __launch_bounds__(RUN_TILE) void capture_frames_kernel(const unsigned char* __restrict__ table, int n) {
+    for (int tile = blockIdx.x, total = launch_tiles<AF_CAPTURE_KIND, af_capture_header>(table, n); tile < total; tile += gridDim.x) {
+        const TileRun<af_capture_item> r = tile_run<af_capture_header, af_capture_item>(table, n, tile);
+        if (!r.npx) continue;
+        const af_capture_item& it = r.it;
+        const int dy = r.dy, x0 = r.x0, npx = r.npx;
         const unsigned char* src = (const unsigned char*)it.src;
         const int ch = it.channels;
         const bool dword = it.dword != 0;
         unsigned px[4] = {0, 0, 0, 0}, out[3];
-
         if (it.mode == AF_CAPTURE_COPY) {
             const unsigned char* row = src + (long long)dy * it.src_pitch;
-            if (npx == CP_RUN) {
+            if (npx == RUN_PX) {
                 cp_px4(row, x0, ch, dword, px);                      // x0 + 4 <= dw = w
             } else {
                 for (int i = 0; i < npx; ++i) px[i] = cp_px(row, x0 + i, ch, dword);
@@ -169,7 +136,7 @@ __global__ __launch_bounds__(CP_TILE) void capture_frames_kernel(const unsigned 
         } else if (it.mode == AF_CAPTURE_AREA2) {
             const unsigned char* r0 = src + (long long)(2 * dy) * it.src_pitch;      // rows 2 dy, 2 dy + 1 < h = 2 dh
             const unsigned char* r1 = r0 + it.src_pitch;
-            if (npx == CP_RUN) {
+            if (npx == RUN_PX) {
                 unsigned a[8], b[8];                                 // source pixels 2 x0 .. 2 x0 + 7 <= 2 dw - 1 = w - 1
                 cp_px4(r0, 2 * x0, ch, dword, a); cp_px4(r0, 2 * x0 + 4, ch, dword, a + 4);
                 cp_px4(r1, 2 * x0, ch, dword, b); cp_px4(r1, 2 * x0 + 4, ch, dword, b + 4);
@@ -243,13 +210,8 @@ __global__ __launch_bounds__(CP_TILE) void capture_frames_kernel(const unsigned 
 #pragma unroll
             for (int i = 0; i < 4; ++i) px[i] = (px[i] & 0xff00u) | (px[i] >> 16) | ((px[i] & 0xffu) << 16);
         }
-        cp_pack(px, out);
-        unsigned char* d = (unsigned char*)it.dst + (long long)dy * it.dst_pitch + 3 * x0;
-        if (npx == CP_RUN && ((unsigned)(uintptr_t)d & 3) == 0) {
-            ((unsigned*)d)[0] = out[0]; ((unsigned*)d)[1] = out[1]; ((unsigned*)d)[2] = out[2];
-        } else {
-            for (int i = 0; i < 3 * npx; ++i) d[i] = (unsigned char)(out[i >> 2] >> (8 * (i & 3)));
-        }
+        pack_run(px, out);
+        store_run12(run_dst(r), out, npx);
     }
 }
 
@@ -266,44 +228,30 @@ struct AreaTable {
     int32_t offset;
     std::vector<int32_t> first;
     std::vector<af_capture_tap> taps;
-    int64_t bytes() const { return pad8((int64_t)first.size() * 4) + (int64_t)taps.size() * (int64_t)sizeof(af_capture_tap); }
     int most_taps() const {
         int most = 0;
         for (size_t d = 0; d + 1 < first.size(); ++d) most = first[d + 1] - first[d] > most ? first[d + 1] - first[d] : most;
         return most;
     }
-};
-
-static void area_table(int ssize, int dsize, AreaTable* out) {
+    int64_t prepare() {                                              // fills first and taps; the bytes they take in the table
 #pragma clang fp contract(off)
-    const double scale = (double)ssize / (double)dsize;
-    out->first.clear(); out->taps.clear();
-    for (int dx = 0; dx < dsize; ++dx) {
-        out->first.push_back((int32_t)out->taps.size());
-        const double fsx1 = dx * scale;
-        const double fsx2 = fsx1 + scale;
-        const double cell = std::fmin(scale, ssize - fsx1);
-        int sx1 = (int)std::ceil(fsx1), sx2 = (int)std::floor(fsx2);
-        sx2 = sx2 < ssize - 1 ? sx2 : ssize - 1;
-        sx1 = sx1 < sx2 ? sx1 : sx2;
-        if (sx1 - fsx1 > 1e-3) out->taps.push_back(af_capture_tap{sx1 - 1, (float)((sx1 - fsx1) / cell)});
-        for (int sx = sx1; sx < sx2; ++sx) out->taps.push_back(af_capture_tap{sx, (float)(1.0 / cell)});
-        if (fsx2 - sx2 > 1e-3) out->taps.push_back(af_capture_tap{sx2, (float)(std::fmin(std::fmin(fsx2 - sx2, 1.0), cell) / cell)});
+        const double scale = (double)src / (double)dst;
+        for (int dx = 0; dx < dst; ++dx) {
+            first.push_back((int32_t)taps.size());
+            const double fsx1 = dx * scale;
+            const double fsx2 = fsx1 + scale;
+            const double cell = std::fmin(scale, src - fsx1);
+            int sx1 = (int)std::ceil(fsx1), sx2 = (int)std::floor(fsx2);
+            sx2 = sx2 < src - 1 ? sx2 : src - 1;
+            sx1 = sx1 < sx2 ? sx1 : sx2;
+            if (sx1 - fsx1 > 1e-3) taps.push_back(af_capture_tap{sx1 - 1, (float)((sx1 - fsx1) / cell)});
+            for (int sx = sx1; sx < sx2; ++sx) taps.push_back(af_capture_tap{sx, (float)(1.0 / cell)});
+            if (fsx2 - sx2 > 1e-3) taps.push_back(af_capture_tap{sx2, (float)(std::fmin(std::fmin(fsx2 - sx2, 1.0), cell) / cell)});
+        }
+        first.push_back((int32_t)taps.size());
+        return pad8((int64_t)first.size() * 4) + (int64_t)taps.size() * (int64_t)sizeof(af_capture_tap);
     }
-    out->first.push_back((int32_t)out->taps.size());
-}
-
-// the table of (src -> dst) among `known`, or a new one at *used
-static int32_t area_table_at(std::vector<AreaTable>& known, int src, int dst, int64_t* used) {
-    for (const AreaTable& g : known)
-        if (g.src == src && g.dst == dst) return g.offset;
-    known.emplace_back();
-    AreaTable& g = known.back();
-    g.src = src; g.dst = dst; g.offset = (int32_t)*used;
-    area_table(src, dst, &g);
-    *used += g.bytes();
-    return g.offset;
-}
+};
 
 static int check_area_table(const AreaTable& g) {
     for (int d = 0; d < g.dst; ++d)
@@ -317,12 +265,10 @@ static inline bool capture_side(int v) { return v >= 1 && v <= AF_CAPTURE_MAX_SI
 
 static int capture_plan(const af_capture_frame* frames, int n, const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes,
                         int64_t* used_bytes) {
-    AF_REQUIRE(n >= 0 && n <= AF_CAPTURE_MAX_FRAMES, "capture_plan: %d frames (at most %d per launch)", n, AF_CAPTURE_MAX_FRAMES);
-    AF_REQUIRE(n_stores > 0 && n_stores <= AF_MAX_STORES, "capture_plan: %d stores (1 to %d per launch)", n_stores, AF_MAX_STORES);
-    af_capture_header hd = {};
-    std::vector<af_capture_item> items((size_t)n);
+    RunPlan<af_capture_header, af_capture_item> plan;
+    int rc = plan.begin("capture_plan", n, n_stores);
+    if (rc != AF_OK) return rc;
     std::vector<AreaTable> xs, ys;
-    int64_t used = (int64_t)sizeof(af_capture_header) + (int64_t)n * sizeof(af_capture_item), tiles = 0;
     for (int i = 0; i < n; ++i) {
         const af_capture_frame& f = frames[i];
         AF_REQUIRE(f.src, "capture_plan: frame %d: null source", i);
@@ -332,51 +278,43 @@ static int capture_plan(const af_capture_frame* frames, int n, const af_store_re
         AF_REQUIRE(f.dw <= f.w && f.dh <= f.h, "capture_plan: frame %d: %dx%d -> %dx%d is upscaling", i, f.w, f.h, f.dw, f.dh);
         AF_REQUIRE(f.pitch >= (int64_t)f.w * f.channels && f.pitch <= 0x7fffffff, "capture_plan: frame %d: pitch %lld is shorter than a row of %d bytes",
                    i, (long long)f.pitch, f.w * f.channels);
-        AF_REQUIRE(f.store >= 0 && f.store < n_stores, "capture_plan: frame %d names store %d of %d", i, f.store, n_stores);
-        const af_store_ref& st = stores[f.store];
-        const af_frame_store& s = st.desc;
-        AF_REQUIRE(st.base, "capture_plan: store %d: null base pointer", f.store);
-        const int rc = check_frame_store("capture_plan", f.store, s);
+        const af_store_ref* st;
+        unsigned char* dst;
+        rc = store_frame("capture_plan", "frame", i, stores, n_stores, f.store, f.slot, true, true, &st, &dst);
         if (rc != AF_OK) return rc;
+        const af_frame_store& s = st->desc;
         AF_REQUIRE(s.height == f.dh && s.width == f.dw, "capture_plan: frame %d: a destination of %dx%d does not fit store %d of %dx%d", i, f.dw, f.dh,
                    f.store, s.width, s.height);
-        AF_REQUIRE(f.slot >= 0 && f.slot < s.n_frames, "capture_plan: frame %d: slot %d leaves store %d of %d frames", i, f.slot, f.store, s.n_frames);
-        af_capture_item& it = items[i];
-        memset(&it, 0, sizeof it);
+        af_capture_item& it = plan.items[i];
         it.src = f.src;
-        it.dst = (unsigned char*)st.base + (int64_t)f.slot * s.frame_stride;
+        it.dst = dst;
         it.src_pitch = (int32_t)f.pitch; it.dst_pitch = (int32_t)s.row_pitch;
         it.h = f.h; it.w = f.w; it.dh = f.dh; it.dw = f.dw;
-        it.runs_x = (f.dw + CP_RUN - 1) / CP_RUN;
+        it.runs_x = row_runs(f.dw);
         it.mode = capture_mode(f.h, f.w, f.dh, f.dw);
         it.kx = it.ky = 1; it.inv_area = 1.f;
         if (it.mode == AF_CAPTURE_BOX) {
             it.kx = f.w / f.dw; it.ky = f.h / f.dh;
             it.inv_area = 1.f / (float)(it.kx * it.ky);              // one fp32 division, as the statement's
         } else if (it.mode == AF_CAPTURE_TABLE) {
-            it.xtab = area_table_at(xs, f.w, f.dw, &used);
-            it.ytab = area_table_at(ys, f.h, f.dh, &used);
-            for (const AreaTable& g : xs)
-                if (g.offset == it.xtab) it.xk = (uint8_t)(g.most_taps() < 255 ? g.most_taps() : 255);
+            const AreaTable& x = axis_table_at(xs, f.w, f.dw, &plan.used);
+            it.xtab = x.offset;
+            it.xk = (uint8_t)(x.most_taps() < 255 ? x.most_taps() : 255);
+            it.ytab = axis_table_at(ys, f.h, f.dh, &plan.used).offset;
         }
         it.channels = (uint8_t)f.channels;
-        it.swap = (uint8_t)((st.bgr != 0) != (f.src_bgr != 0));
+        it.swap = (uint8_t)((st->bgr != 0) != (f.src_bgr != 0));
         it.dword = (uint8_t)(f.channels == 4 && ((uintptr_t)f.src & 3) == 0 && (f.pitch & 3) == 0);
-        hd.first_tile[i] = (int32_t)tiles;
-        tiles += capture_tiles(f.dh, f.dw);
+        plan.add_tiles(i, f.dh, f.dw);
     }
-    for (int i = n; i <= AF_CAPTURE_MAX_FRAMES; ++i) hd.first_tile[i] = (int32_t)tiles;
     for (const std::vector<AreaTable>* axis : {&xs, &ys})
         for (const AreaTable& g : *axis) {
-            const int rc = check_area_table(g);
+            rc = check_area_table(g);
             if (rc != AF_OK) return rc;
         }
-    AF_REQUIRE(table_bytes >= used, "capture_plan: the table needs %lld bytes, the buffer has %lld", (long long)used, (long long)table_bytes);
-    AF_REQUIRE(used <= 0x7fffffff && tiles <= 0x7fffffff, "capture_plan: a table of %lld bytes and %lld tiles", (long long)used, (long long)tiles);
-    hd.kind = AF_CAPTURE_KIND; hd.n = n; hd.total_tiles = (int32_t)tiles; hd.used_bytes = (int32_t)used;
+    rc = plan.finish("capture_plan", AF_CAPTURE_KIND, table, table_bytes, used_bytes);
+    if (rc != AF_OK) return rc;
     unsigned char* t = (unsigned char*)table;
-    memcpy(t, &hd, sizeof hd);
-    if (n) memcpy(t + sizeof hd, items.data(), (size_t)n * sizeof(af_capture_item));
     for (const std::vector<AreaTable>* axis : {&xs, &ys})
         for (const AreaTable& g : *axis) {
             const int64_t head = pad8((int64_t)g.first.size() * 4);
@@ -384,7 +322,6 @@ static int capture_plan(const af_capture_frame* frames, int n, const af_store_re
             memcpy(t + g.offset, g.first.data(), g.first.size() * 4);
             memcpy(t + g.offset + head, g.taps.data(), g.taps.size() * sizeof(af_capture_tap));
         }
-    *used_bytes = used;
     return AF_OK;
 }
 
@@ -408,25 +345,11 @@ extern "C" int64_t af_capture_table_bytes(const af_capture_frame* frames, int n)
 extern "C" int af_capture_plan_u8(const af_capture_frame* frames, int n, const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes,
                                   int64_t* used_bytes) {
     using namespace af;
-    AF_REQUIRE(table && used_bytes, "capture_plan: null argument");
-    AF_REQUIRE(((uintptr_t)table & 7) == 0, "capture_plan: the table buffer must be 8-byte aligned");
-    AF_REQUIRE(table_bytes >= (int64_t)sizeof(af_capture_header), "capture_plan: the table needs %lld bytes for its header alone, the buffer has %lld",
-               (long long)sizeof(af_capture_header), (long long)table_bytes);
-    *used_bytes = 0;
-    int rc;
-    if (!frames || !stores) rc = set_error(AF_ERR_ARG, "capture_plan: null argument");
-    else rc = capture_plan(frames, n, stores, n_stores, table, table_bytes, used_bytes);
-    if (rc != AF_OK) ((af_capture_header*)table)->kind = -1;         // a refused table is no table: no launch takes it
-    return rc;
+    return plan_into<af_capture_header>("capture_plan", table, table_bytes, used_bytes, [&] {      // null frames or stores: stamped too
+        return frames && stores ? capture_plan(frames, n, stores, n_stores, table, table_bytes, used_bytes) : set_error(AF_ERR_ARG, "capture_plan: null argument");
+    });
 }
 
 extern "C" int af_capture_to_stores_u8(const void* table_dev, int n, void* stream) {
-    using namespace af;
-    AF_REQUIRE(table_dev, "capture_to_stores: null table");
-    AF_REQUIRE(((uintptr_t)table_dev & 7) == 0, "capture_to_stores: the table must be 8-byte aligned");
-    AF_REQUIRE(n >= 0 && n <= AF_CAPTURE_MAX_FRAMES, "capture_to_stores: %d frames (at most %d per launch)", n, AF_CAPTURE_MAX_FRAMES);
-    if (n == 0) return AF_OK;
-    hipLaunchKernelGGL(capture_frames_kernel, dim3(CP_GRID), dim3(CP_TILE), 0, (hipStream_t)stream, (const unsigned char*)table_dev, n);
-    AF_CHECK_LAUNCH("capture_frames_kernel");
-    return AF_OK;
+    return af::launch_runs("capture_to_stores", "capture_frames_kernel", af::capture_frames_kernel, table_dev, n, AF_CAPTURE_MAX_FRAMES, stream);
 }

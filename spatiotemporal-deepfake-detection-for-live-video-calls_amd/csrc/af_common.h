@@ -313,6 +313,22 @@ static inline int check_frame_store(const char* who, int index, const af_frame_s
                who, StoreName(index).text, s.n_frames, (long long)s.store_bytes);
     return AF_OK;
 }
+// Frame k of stores[index], for item i of a planner (`item`: its word for one, "job" or "frame"): the index in range, a base
+// pointer, a sane store, k in range - said as a slot that is written (`slot`) or a frame that is read.  Yields the store and the
+// frame's first byte.
+static inline int store_frame(const char* who, const char* item, int i, const af_store_ref* stores, int n_stores, int index, int k, bool slot, bool whole,
+                              const af_store_ref** store, unsigned char** frame) {
+    AF_REQUIRE(index >= 0 && index < n_stores, "%s: %s %d names store %d of %d", who, item, i, index, n_stores);
+    const af_store_ref& st = stores[index];
+    AF_REQUIRE(st.base, "%s: store %d: null base pointer", who, index);
+    const int rc = check_frame_store(who, index, st.desc, whole);
+    if (rc != AF_OK) return rc;
+    AF_REQUIRE(k >= 0 && k < st.desc.n_frames, slot ? "%s: %s %d: slot %d leaves store %d of %d frames" : "%s: %s %d names frame %d of store %d of %d frames",
+               who, item, i, k, index, st.desc.n_frames);
+    *store = &st;
+    *frame = (unsigned char*)st.base + (int64_t)k * st.desc.frame_stride;
+    return AF_OK;
+}
 // Is this rectangle inside its frame, and the frame in the (checked) store?  Yields the byte offset of its first pixel and returns
 // 0, or what is wrong with it for refuse_frame_rect.  `slack`: readable bytes wanted behind the rectangle's last pixel (3 for the
 // warp's 6-byte tap reads).  Inside a frame those are the frame's next pixels: only a rectangle that ends the store can lack them.

@@ -19,35 +19,17 @@
 // hipcc would fuse (dx + 0.5) * scale_x - 0.5 into an fma and change bits.  The device does integer arithmetic only.  Channels are
 // treated alike, so the byte order of a store passes through unchanged.
 //
-// Shape: memory-bound.  A lane owns a run of 4 adjacent pixels of one destination row (12 bytes, three dwords); the runs of a job
-// are numbered row by row, a workgroup of 256 lanes takes 256 consecutive runs (a tile), and the tiles of all jobs form one flat
-// list with a first_tile prefix in the table's header, as af_yuv420_to_rgb_u8 flattens its items.  The table lies in device memory
-// (it holds the coefficient tables), so the launch cannot know the tile count: a fixed grid strides over the tiles.
+// Shape: memory-bound; the runs, tiles and fixed grid of af_frame_runs.h, which also holds the argument for the writes.
 //
-// No stray access.  Reads: every source byte address is row * pitch + 3 * col + c with 0 <= row < h, 0 <= col < w, c < 3, or a
-// dword that covers 4 such bytes of one row at a 4-byte aligned address, never rounded down or widened past them.  Writes: a full
-// run writes the 12 bytes [12 j, 12 j + 12) of its destination row, as three dwords when the address is 4-byte aligned and as
-// bytes otherwise; the last run of a row with dw % 4 != 0 writes its 3, 6 or 9 bytes as bytes.  Nothing goes into the pitch
-// padding or behind the last row.
+// No stray access, reads: every source byte address is row * pitch + 3 * col + c with 0 <= row < h, 0 <= col < w, c < 3, or a
+// dword that covers 4 such bytes of one row at a 4-byte aligned address, never rounded down or widened past them.
 #include <cfloat>
 #include <cmath>
-#include <cstring>
-#include <vector>
-
-#include "af_common.h"
+#include "af_frame_runs.h"
 
 namespace af {
 
-constexpr int RS_RUN = 4;                           // pixels of a row one lane produces
-constexpr int RS_TILE = 256;                        // runs per workgroup
-constexpr int RS_GRID = 2048;                       // workgroups of a launch: 8 per CU, each strides over the tiles
-
 static_assert(sizeof(af_resize_header) % 8 == 0 && sizeof(af_resize_item) % 8 == 0 && sizeof(af_resize_coef) == 8, "table layout");
-
-static inline int64_t resize_tiles(int dh, int dw) {
-    const int64_t runs = (int64_t)dh * ((dw + RS_RUN - 1) / RS_RUN);
-    return (runs + RS_TILE - 1) / RS_TILE;
-}
 
 // N bytes (a multiple of 4) from p as little-endian dwords: dword loads when p is 4-byte aligned, else byte loads.  Reads [p, p + N).
 template <int N>
@@ -64,52 +46,32 @@ __device__ __forceinline__ void rs_load(const unsigned char* p, unsigned (&d)[N 
 template <int N>
 __device__ __forceinline__ unsigned rs_byte(const unsigned (&d)[N], int k) { return (d[k >> 2] >> (8 * (k & 3))) & 255u; }
 
-// four pixels (24 bits each) -> the 12 bytes of a run
-__device__ __forceinline__ void rs_pack(const unsigned (&px)[4], unsigned (&out)[3]) {
-    out[0] = px[0] | (px[1] << 24);
-    out[1] = (px[1] >> 8) | (px[2] << 16);
-    out[2] = (px[2] >> 16) | (px[3] << 8);
-}
-
-__device__ __forceinline__ unsigned rs_area2(unsigned a, unsigned b, unsigned c, unsigned d) { return (a + b + c + d + 2u) >> 2; }
-
 // one channel of one pixel: the horizontal pass of both rows, then the vertical one
 __device__ __forceinline__ unsigned rs_linear(int s00, int s01, int s10, int s11, int a0, int a1, int b0, int b1) {
     const int h0 = s00 * a0 + s01 * a1, h1 = s10 * a0 + s11 * a1;
     return (unsigned)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
 }
 
-__global__ __launch_bounds__(RS_TILE) void resize_frames_kernel(const unsigned char* __restrict__ table, int n) {
-    const af_resize_header* hd = (const af_resize_header*)table;
-    if (hd->kind != AF_RESIZE_KIND || hd->n != n) return;           // not this launch's table (or a refused one): write nothing
-    const af_resize_item* items = (const af_resize_item*)(table + sizeof(af_resize_header));
-    const int total = hd->total_tiles;
-    for (int tile = blockIdx.x; tile < total; tile += gridDim.x) {
-        int k = 0, hi = n - 1;                                       // the last job whose first tile is <= tile
-        while (k < hi) {
-            const int mid = (k + hi + 1) >> 1;
-            if (hd->first_tile[mid] <= tile) k = mid; else hi = mid - 1;
-        }
-        const af_resize_item it = items[k];
-        const int run = (tile - hd->first_tile[k]) * RS_TILE + (int)threadIdx.x;
-        if (run >= it.dh * it.runs_x) continue;
-        const int dy = run / it.runs_x, j = run - dy * it.runs_x;
-        const int x0 = j * RS_RUN, npx = min(RS_RUN, it.dw - x0);
+__global__ __launch_bounds__(RUN_TILE) void resize_frames_kernel(const unsigned char* __restrict__ table, int n) {
+    for (int tile = blockIdx.x, total = launch_tiles<AF_RESIZE_KIND, af_resize_header>(table, n); tile < total; tile += gridDim.x) {
+        const TileRun<af_resize_item> r = tile_run<af_resize_header, af_resize_item>(table, n, tile);
+        if (!r.npx) continue;
+        const af_resize_item& it = r.it;
+        const int dy = r.dy, x0 = r.x0, npx = r.npx;
         const unsigned char* src = (const unsigned char*)it.src;
         unsigned px[4] = {0, 0, 0, 0}, out[3];
-
         if (it.mode == AF_RESIZE_COPY) {
             const unsigned char* s = src + (long long)dy * it.src_pitch + 3 * x0;
-            if (npx == RS_RUN) {
+            if (npx == RUN_PX) {
                 rs_load<12>(s, out);                                 // x0 + 4 <= dw = w: the 12 bytes lie inside the row
             } else {
                 for (int i = 0; i < npx; ++i) px[i] = (unsigned)s[3 * i] | ((unsigned)s[3 * i + 1] << 8) | ((unsigned)s[3 * i + 2] << 16);
-                rs_pack(px, out);
+                pack_run(px, out);
             }
         } else if (it.mode == AF_RESIZE_AREA2) {
             const unsigned char* s0 = src + (long long)(2 * dy) * it.src_pitch + 6 * x0;     // rows 2 dy, 2 dy + 1 < h = 2 dh
             const unsigned char* s1 = s0 + it.src_pitch;
-            if (npx == RS_RUN) {
+            if (npx == RUN_PX) {
                 unsigned r0[6], r1[6];                               // source pixels 2 x0 .. 2 x0 + 7 <= 2 dw - 1 = w - 1
                 rs_load<24>(s0, r0);
                 rs_load<24>(s1, r1);
@@ -117,13 +79,13 @@ __global__ __launch_bounds__(RS_TILE) void resize_frames_kernel(const unsigned c
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int c = 0; c < 3; ++c)
-                        px[i] |= rs_area2(rs_byte(r0, 6 * i + c), rs_byte(r0, 6 * i + 3 + c), rs_byte(r1, 6 * i + c), rs_byte(r1, 6 * i + 3 + c)) << (8 * c);
+                        px[i] |= area2(rs_byte(r0, 6 * i + c), rs_byte(r0, 6 * i + 3 + c), rs_byte(r1, 6 * i + c), rs_byte(r1, 6 * i + 3 + c)) << (8 * c);
             } else {
                 for (int i = 0; i < npx; ++i)
                     for (int c = 0; c < 3; ++c)
-                        px[i] |= rs_area2(s0[6 * i + c], s0[6 * i + 3 + c], s1[6 * i + c], s1[6 * i + 3 + c]) << (8 * c);
+                        px[i] |= area2(s0[6 * i + c], s0[6 * i + 3 + c], s1[6 * i + c], s1[6 * i + 3 + c]) << (8 * c);
             }
-            rs_pack(px, out);
+            pack_run(px, out);
         } else {
             const af_resize_coef yc = ((const af_resize_coef*)(table + it.ytab))[dy];
             const int ra = min(max(yc.idx, 0), it.h - 1), rb = min(max(yc.idx + 1, 0), it.h - 1);
@@ -140,15 +102,9 @@ __global__ __launch_bounds__(RS_TILE) void resize_frames_kernel(const unsigned c
                         px[i] |= rs_linear(s0[o0 + c], s0[o1 + c], s1[o0 + c], s1[o1 + c], xc.a0, xc.a1, yc.a0, yc.a1) << (8 * c);
                 }
             }
-            rs_pack(px, out);
+            pack_run(px, out);
         }
-
-        unsigned char* d = (unsigned char*)it.dst + (long long)dy * it.dst_pitch + 3 * x0;
-        if (npx == RS_RUN && ((unsigned)(uintptr_t)d & 3) == 0) {
-            ((unsigned*)d)[0] = out[0]; ((unsigned*)d)[1] = out[1]; ((unsigned*)d)[2] = out[2];
-        } else {
-            for (int i = 0; i < 3 * npx; ++i) d[i] = (unsigned char)(out[i >> 2] >> (8 * (i & 3)));
-        }
+        store_run12(run_dst(r), out, npx);
     }
 }
 
@@ -177,45 +133,32 @@ static void resize_coefs(int src, int dst, bool clamp_x, af_resize_coef* out) {
     }
 }
 
-struct ResizeGeom { int src, dst; int32_t offset; };
-
-// the table of (src -> dst) among `known`, or a new one at *used
-static int32_t resize_table_at(std::vector<ResizeGeom>& known, int src, int dst, int64_t* used) {
-    for (const ResizeGeom& g : known)
-        if (g.src == src && g.dst == dst) return g.offset;
-    known.push_back(ResizeGeom{src, dst, (int32_t)*used});
-    *used += (int64_t)dst * sizeof(af_resize_coef);
-    return known.back().offset;
-}
+// one axis' table, src -> dst: dst coefficients at `offset`
+struct ResizeGeom { int src, dst; int32_t offset; int64_t prepare() const { return (int64_t)dst * sizeof(af_resize_coef); } };
 
 static int resize_plan(const af_resize_job* jobs, int n, const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes, int64_t* used_bytes) {
-    AF_REQUIRE(n >= 0 && n <= AF_RESIZE_MAX_FRAMES, "resize_plan: %d frames (at most %d per launch)", n, AF_RESIZE_MAX_FRAMES);
-    AF_REQUIRE(n_stores > 0 && n_stores <= AF_MAX_STORES, "resize_plan: %d stores (1 to %d per launch)", n_stores, AF_MAX_STORES);
-    af_resize_header hd = {};
-    std::vector<af_resize_item> items((size_t)n);
+    RunPlan<af_resize_header, af_resize_item> plan;
+    int rc = plan.begin("resize_plan", n, n_stores);
+    if (rc != AF_OK) return rc;
     std::vector<ResizeGeom> xs, ys;
-    int64_t used = (int64_t)sizeof(af_resize_header) + (int64_t)n * sizeof(af_resize_item), tiles = 0;
     for (int i = 0; i < n; ++i) {
         const af_resize_job& j = jobs[i];
-        AF_REQUIRE(j.store >= 0 && j.store < n_stores, "resize_plan: job %d names store %d of %d", i, j.store, n_stores);
-        const af_store_ref& st = stores[j.store];
-        const af_frame_store& s = st.desc;
-        AF_REQUIRE(st.base, "resize_plan: store %d: null base pointer", j.store);
-        const int rc = check_frame_store("resize_plan", j.store, s);
+        const af_store_ref* st;
+        unsigned char* src;
+        rc = store_frame("resize_plan", "job", i, stores, n_stores, j.store, j.frame, false, true, &st, &src);
         if (rc != AF_OK) return rc;
-        AF_REQUIRE(j.frame >= 0 && j.frame < s.n_frames, "resize_plan: job %d names frame %d of store %d of %d frames", i, j.frame, j.store, s.n_frames);
+        const af_frame_store& s = st->desc;
         AF_REQUIRE(j.dst, "resize_plan: job %d: null destination", i);
         AF_REQUIRE(j.dw >= 1 && j.dh >= 1 && j.dw <= AF_RESIZE_MAX_SIDE && j.dh <= AF_RESIZE_MAX_SIDE,
                    "resize_plan: job %d: a destination of %dx%d (1 to %d in both directions)", i, j.dw, j.dh, AF_RESIZE_MAX_SIDE);
         AF_REQUIRE(j.dst_pitch >= 3 * (int64_t)j.dw && j.dst_pitch <= 0x7fffffff, "resize_plan: job %d: destination pitch %lld is shorter than a row of %d bytes",
                    i, (long long)j.dst_pitch, 3 * j.dw);
-        af_resize_item& it = items[i];
-        it.src = (const unsigned char*)st.base + (int64_t)j.frame * s.frame_stride;
+        af_resize_item& it = plan.items[i];
+        it.src = src;
         it.dst = j.dst;
         it.src_pitch = (int32_t)s.row_pitch; it.dst_pitch = (int32_t)j.dst_pitch;
         it.h = s.height; it.w = s.width; it.dh = j.dh; it.dw = j.dw;
-        it.runs_x = (j.dw + RS_RUN - 1) / RS_RUN;
-        it.xtab = it.ytab = 0;
+        it.runs_x = row_runs(j.dw);
         if (j.dw == s.width && j.dh == s.height) {
             it.mode = AF_RESIZE_COPY;
         } else if (std::fabs(resize_scale(s.width, j.dw) - 2.0) < DBL_EPSILON && std::fabs(resize_scale(s.height, j.dh) - 2.0) < DBL_EPSILON &&
@@ -223,21 +166,16 @@ static int resize_plan(const af_resize_job* jobs, int n, const af_store_ref* sto
             it.mode = AF_RESIZE_AREA2;
         } else {
             it.mode = AF_RESIZE_LINEAR;
-            it.xtab = resize_table_at(xs, s.width, j.dw, &used);
-            it.ytab = resize_table_at(ys, s.height, j.dh, &used);
+            it.xtab = axis_table_at(xs, s.width, j.dw, &plan.used).offset;
+            it.ytab = axis_table_at(ys, s.height, j.dh, &plan.used).offset;
         }
-        hd.first_tile[i] = (int32_t)tiles;
-        tiles += resize_tiles(j.dh, j.dw);
+        plan.add_tiles(i, j.dh, j.dw);
     }
-    for (int i = n; i <= AF_RESIZE_MAX_FRAMES; ++i) hd.first_tile[i] = (int32_t)tiles;
-    AF_REQUIRE(table_bytes >= used, "resize_plan: the table needs %lld bytes, the buffer has %lld", (long long)used, (long long)table_bytes);
-    hd.kind = AF_RESIZE_KIND; hd.n = n; hd.total_tiles = (int32_t)tiles; hd.used_bytes = (int32_t)used;
+    rc = plan.finish("resize_plan", AF_RESIZE_KIND, table, table_bytes, used_bytes);
+    if (rc != AF_OK) return rc;
     unsigned char* t = (unsigned char*)table;
-    memcpy(t, &hd, sizeof hd);
-    if (n) memcpy(t + sizeof hd, items.data(), (size_t)n * sizeof(af_resize_item));
     for (const ResizeGeom& g : xs) resize_coefs(g.src, g.dst, true, (af_resize_coef*)(t + g.offset));
     for (const ResizeGeom& g : ys) resize_coefs(g.src, g.dst, false, (af_resize_coef*)(t + g.offset));
-    *used_bytes = used;
     return AF_OK;
 }
 
@@ -256,23 +194,11 @@ extern "C" int64_t af_resize_table_bytes(const af_resize_job* jobs, int n) {
 extern "C" int af_resize_plan_u8(const af_resize_job* jobs, int n, const af_store_ref* stores, int n_stores, void* table, int64_t table_bytes,
                                  int64_t* used_bytes) {
     using namespace af;
-    AF_REQUIRE(jobs && stores && table && used_bytes, "resize_plan: null argument");
-    AF_REQUIRE(((uintptr_t)table & 7) == 0, "resize_plan: the table buffer must be 8-byte aligned");
-    AF_REQUIRE(table_bytes >= (int64_t)sizeof(af_resize_header), "resize_plan: the table needs %lld bytes for its header alone, the buffer has %lld",
-               (long long)sizeof(af_resize_header), (long long)table_bytes);
-    *used_bytes = 0;
-    const int rc = resize_plan(jobs, n, stores, n_stores, table, table_bytes, used_bytes);
-    if (rc != AF_OK) ((af_resize_header*)table)->kind = -1;          // a refused table is no table: no launch takes it
-    return rc;
+    AF_REQUIRE(jobs && stores, "resize_plan: null argument");
+    return plan_into<af_resize_header>("resize_plan", table, table_bytes, used_bytes,
+                                       [&] { return resize_plan(jobs, n, stores, n_stores, table, table_bytes, used_bytes); });
 }
 
 extern "C" int af_resize_frames_u8(const void* table_dev, int n, void* stream) {
-    using namespace af;
-    AF_REQUIRE(table_dev, "resize_frames: null table");
-    AF_REQUIRE(((uintptr_t)table_dev & 7) == 0, "resize_frames: the table must be 8-byte aligned");
-    AF_REQUIRE(n >= 0 && n <= AF_RESIZE_MAX_FRAMES, "resize_frames: %d frames (at most %d per launch)", n, AF_RESIZE_MAX_FRAMES);
-    if (n == 0) return AF_OK;
-    hipLaunchKernelGGL(resize_frames_kernel, dim3(RS_GRID), dim3(RS_TILE), 0, (hipStream_t)stream, (const unsigned char*)table_dev, n);
-    AF_CHECK_LAUNCH("resize_frames_kernel");
-    return AF_OK;
+    return af::launch_runs("resize_frames", "resize_frames_kernel", af::resize_frames_kernel, table_dev, n, AF_RESIZE_MAX_FRAMES, stream);
 }

@@ -215,19 +215,20 @@ extern "C" int af_yuv420_plan_u8(const af_yuv_frame* frames, int n, const af_sto
         const int crow = f.interleaved ? f.w : f.w / 2;
         AF_REQUIRE(f.c_pitch >= crow && f.c_pitch <= 0x7fffffff, "yuv420_plan: frame %d: chroma pitch %lld is shorter than a row of %d bytes", i,
                    (long long)f.c_pitch, crow);
-        AF_REQUIRE(f.store >= 0 && f.store < n_stores, "yuv420_plan: frame %d names store %d of %d", i, f.store, n_stores);
-        const af_store_ref& st = stores[f.store];
-        const af_frame_store& s = st.desc;
-        AF_REQUIRE(st.base, "yuv420_plan: store %d: null base pointer", f.store);
-        AF_REQUIRE(s.n_frames > 0 && s.height == f.h && s.width == f.w, "yuv420_plan: frame %d of %dx%d does not fit store %d of %d frames of %dx%d", i,
-                   f.w, f.h, f.store, s.n_frames, s.width, s.height);
-        const int rc = check_frame_store("yuv420_plan", f.store, s, false);     // one slot is written: its own bytes are checked next
+        const af_store_ref* ref;
+        unsigned char* dst;
+        // one slot is written, so the store need not hold all its frames (whole = false): the slot's own bytes are checked below
+        const int rc = store_frame("yuv420_plan", "frame", i, stores, n_stores, f.store, f.slot, true, false, &ref, &dst);
         if (rc != AF_OK) return rc;
-        AF_REQUIRE(f.slot >= 0 && f.slot < s.n_frames && (int64_t)f.slot * s.frame_stride + frame_span(s) <= s.store_bytes,
-                   "yuv420_plan: frame %d: slot %d leaves store %d of %d frames, %lld bytes", i, f.slot, f.store, s.n_frames, (long long)s.store_bytes);
+        const af_store_ref& st = *ref;
+        const af_frame_store& s = st.desc;
+        AF_REQUIRE(s.height == f.h && s.width == f.w, "yuv420_plan: frame %d of %dx%d does not fit store %d of %d frames of %dx%d", i, f.w, f.h, f.store,
+                   s.n_frames, s.width, s.height);
+        AF_REQUIRE((int64_t)f.slot * s.frame_stride + frame_span(s) <= s.store_bytes, "yuv420_plan: frame %d: slot %d leaves store %d of %d frames, %lld bytes", i,
+                   f.slot, f.store, s.n_frames, (long long)s.store_bytes);
         af_yuv_item& it = items[i];
         it.y = f.y; it.c0 = f.u; it.c1 = f.interleaved ? nullptr : f.v;
-        it.dst = (unsigned char*)st.base + (int64_t)f.slot * s.frame_stride;
+        it.dst = dst;
         it.y_pitch = (int32_t)f.y_pitch; it.c_pitch = (int32_t)f.c_pitch; it.dst_pitch = (int32_t)s.row_pitch;
         it.first_tile = (int32_t)tiles;
         it.h = (uint16_t)f.h; it.w = (uint16_t)f.w;

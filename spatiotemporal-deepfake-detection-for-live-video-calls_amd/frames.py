@@ -273,6 +273,18 @@ class StoreTable:
         return (_lib.StoreRef * len(self.refs))(*self.refs)
 
 
+def launch_stores(refs):
+    """the ``af_store_ref`` of every item of one launch -> (the array of the distinct ones in order of first use, its length, every
+    item's index into it).  Distinct by identity: ``_Converter.convert`` hands each (store, order) pair's one ``StoreTable`` ref."""
+    from . import _lib
+    distinct, at = [], {}
+    for ref in refs:
+        if id(ref) not in at:
+            at[id(ref)] = len(distinct)
+            distinct.append(ref)
+    return (_lib.StoreRef * max(1, len(distinct)))(*distinct), len(distinct), [at[id(ref)] for ref in refs]
+
+
 def _address(p) -> int:
     return p.__array_interface__["data"][0] if isinstance(p, np.ndarray) else p.data_ptr()
 
@@ -393,11 +405,9 @@ class YuvConverter(_Converter):
         chroma; None: the frame's own device planes) into slot ``slots[i]`` of ``stores[i]`` (an ``_lib.StoreRef`` each) -> the
         ``YuvItem`` array of one launch"""
         from . import _lib
-        refs, index, descs = [], {}, (_lib.YuvFrameDesc * max(1, len(frames)))()
-        for i, (f, base, ref, slot) in enumerate(zip(frames, addresses, stores, slots)):
-            if id(ref) not in index:
-                index[id(ref)] = len(refs)
-                refs.append(ref)
+        descs = (_lib.YuvFrameDesc * max(1, len(frames)))()
+        store_arr, n_stores, index = launch_stores(stores)
+        for i, (f, base, slot) in enumerate(zip(frames, addresses, slots)):
             h, w = f.shape[:2]
             if base is None:
                 ptrs = [_address(p) for p, _, _, _ in f.planes()]
@@ -407,10 +417,9 @@ class YuvConverter(_Converter):
                 if not f.interleaved:
                     ptrs.append(base + h * w + h * w // 4)
             descs[i] = _lib.YuvFrameDesc(ptrs[0], ptrs[1], None if f.interleaved else ptrs[2], y_pitch, c_pitch, h, w,
-                                         int(f.interleaved), int(f.swap_uv), index[id(ref)], int(slot))
+                                         int(f.interleaved), int(f.swap_uv), index[i], int(slot))
         items = (_lib.YuvItem * max(1, len(frames)))()
-        store_arr = (_lib.StoreRef * max(1, len(refs)))(*refs)
-        _lib.check(_lib.lib.af_yuv420_plan_u8(C.byref(descs), len(frames), C.byref(store_arr), len(refs), C.byref(items)), "yuv420_plan_u8")
+        _lib.check(_lib.lib.af_yuv420_plan_u8(C.byref(descs), len(frames), C.byref(store_arr), n_stores, C.byref(items)), "yuv420_plan_u8")
         return items
 
     def _plan(self, frames, addresses, refs, slots, table_host, table_dev, room):
@@ -433,15 +442,13 @@ class CaptureConverter(_Converter):
         are, at their pitch) into slot ``slots[i]`` of ``stores[i]`` (an ``_lib.StoreRef`` each) -> (the ``af_capture_frame`` array,
         the ``af_store_ref`` array, its length)"""
         from . import _lib
-        refs, index, descs = [], {}, (_lib.CaptureFrame * max(1, len(frames)))()
-        for i, (f, base, ref, slot) in enumerate(zip(frames, addresses, stores, slots)):
-            if id(ref) not in index:
-                index[id(ref)] = len(refs)
-                refs.append(ref)
+        descs = (_lib.CaptureFrame * max(1, len(frames)))()
+        store_arr, n_stores, index = launch_stores(stores)
+        for i, (f, base, slot) in enumerate(zip(frames, addresses, slots)):
             (rh, rw), (dh, dw, _) = f.rect_shape, f.shape
             src, pitch = (_address(f._view), f.pitch) if base is None else (base, rw * f.channels)
-            descs[i] = _lib.CaptureFrame(src, pitch, rh, rw, f.channels, int(f.src_bgr), index[id(ref)], int(slot), dh, dw)
-        return descs, (_lib.StoreRef * max(1, len(refs)))(*refs), len(refs)
+            descs[i] = _lib.CaptureFrame(src, pitch, rh, rw, f.channels, int(f.src_bgr), index[i], int(slot), dh, dw)
+        return descs, store_arr, n_stores
 
     @staticmethod
     def table_bytes(frames: Sequence[CapturedFrame]) -> int:

@@ -20,6 +20,7 @@ import torch
 
 import capture_ref as R
 import quality_ref as Q
+import resize_ref as RS
 from af_mi355x import _lib, frames as F
 
 L = _lib.lib
@@ -92,6 +93,17 @@ def test_the_statement_at_half_size_is_the_pinned_half_size():
             modes.add(R.mode(h, w, dh, dw))
             assert np.array_equal(R.area_resize(c, dw, dh), Q.half_size(c)), (h, w)
     assert modes == {"copy", "area2", "box", "table"}
+
+
+def test_the_two_statements_of_the_2x2_mean_agree():
+    """capture_ref's AREA2 and resize_ref's fast area path state one piece of device code (area2 in csrc/af_frame_runs.h)"""
+    rng = np.random.default_rng(3)
+    for (h, w), (dh, dw) in (((6, 10), (3, 5)), ((2, 2), (1, 1)), ((16, 24), (8, 12))):
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        assert R.mode(h, w, dh, dw) == "area2" and RS.is_area2(w, h, dw, dh)
+        assert np.array_equal(R.area_resize(img, dw, dh), RS.resize_linear(img, dw, dh)), (h, w)
+    img = rng.integers(0, 256, (3, 5, 3), dtype=np.uint8)
+    assert np.array_equal(R.area_resize(img, 5, 3), img) and np.array_equal(RS.resize_linear(img, 5, 3), img)
 
 
 def test_capture_size_is_the_references_formula():

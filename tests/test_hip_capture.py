@@ -14,7 +14,8 @@ tests/test_hip_live.py (f16, 8 frames of 64 x 64).
                 forms of the kernel's table loop (at most 4 taps per column, unrolled; any number, a loop), 3 x 11 -> 2 x 2 (6 taps)
                 and 2 x 37 -> 1 x 3 (13 taps, and a sum that lands on 105.5 exactly: one fused multiply-add turns the byte into
                 105) next to the cases above (at most 4)
-  several       64 frames of mixed size, mode, format, store, order and residence in one launch; 65 make two
+  several       64 frames of mixed size, mode, format, store, order and residence in one launch; 65 make two; 64 frames of 33 tiles
+                each, more tiles than the launch's grid of 2048 workgroups
   put           FrameStore.put of captured frames equals put of the statement's arrays
   LiveCall      bgra bitmaps with a rect and a max_w that lands in TABLE mode against a twin stepped with the statement's frames:
                 frame bytes, results and books, across the ring's wrap; bgr, rgb, and on a side stream
@@ -24,6 +25,8 @@ tests/test_hip_live.py (f16, 8 frames of 64 x 64).
 
 Each equality test first asserts, on the twin alone, that the script produced its cases.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -186,6 +189,34 @@ def test_mixed_frames_share_launches(n, launches):
     for (dh, dw, _), store in stores.items():
         fb = dh * dw * 3
         assert bool((store.dev[:fb] == SENTINEL).all()) and bool((store.dev[(store.capacity - 1) * fb:] == SENTINEL).all())
+
+
+BIG = [(66, 512), (132, 1024), (198, 1024), (100, 700)]          # h x w -> 66 x 512: COPY, AREA2, BOX (kx 2, ky 3), TABLE
+
+
+def test_a_launch_of_more_tiles_than_workgroups():
+    """64 frames of 128 runs x 66 rows = 33 tiles each into the 64 slots of one store: 2112 tiles for a grid of 2048 workgroups, so
+    the first 64 workgroups take a second tile (the last two frames: BOX and TABLE)"""
+    assert [R.mode(h, w, 66, 512) for h, w in BIG] == ["copy", "area2", "box", "table"] and (1024 // 512, 198 // 66) == (2, 3)
+    store = _store(66, 512, "bgr", capacity=_lib.CAPTURE_MAX_FRAMES)
+    jobs, wants = [], []
+    for k in range(_lib.CAPTURE_MAX_FRAMES):
+        (h, w), fmt, seed = BIG[k % 4], ("bgra", "rgb")[(k // 4) % 2], (k // 8) % 2
+        jobs.append((_frame(h, w, 66, 512, fmt, "tight", seed=seed), store, "bgr", k))
+        wants.append(_want(h, w, 66, 512, fmt, "bgr", seed=seed))
+    frames = [j[0] for j in jobs]
+    table = np.zeros(F.CaptureConverter.table_bytes(frames) // 8 + 1, np.int64)       # the planner alone, for the header it writes
+    F.CaptureConverter.table(frames, [0x1000] * len(frames), [F.store_ref(store, "bgr")] * len(frames), list(range(len(frames))),
+                             table.ctypes.data, table.nbytes)
+    header = _lib.CaptureHeader.from_buffer_copy(table.tobytes()[:C.sizeof(_lib.CaptureHeader)])
+    assert header.total_tiles == 64 * 33 > 2048                                      # the launch's grid, which _lib does not export
+    conv = F.CaptureConverter(_dev())
+    conv.convert(jobs)
+    torch.cuda.synchronize()
+    assert (conv.launches, conv.copies) == (1, 1)
+    want = np.concatenate([np.stack(wants).reshape(-1), np.full(16, SENTINEL, np.uint8)])
+    bad = np.flatnonzero(store.dev.cpu().numpy() != want)
+    assert bad.size == 0, "%d bytes differ, the first at %d of slots of %d" % (bad.size, bad[0], 66 * 512 * 3)
 
 
 def test_put_of_captured_frames_equals_put_of_the_statements_arrays(monkeypatch):

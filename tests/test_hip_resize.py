@@ -5,7 +5,7 @@
                 byte outside the dh rows of 3 dw bytes - pitch padding, the guards around every job and around the buffer - keeps
                 its value.  One launch of 64 jobs of mixed geometries out of three stores (one of them B, G, R): every job equals
                 the restatement and its own single-job launch; two runs are bitwise equal; a launch whose n differs from the
-                table's writes nothing
+                table's writes nothing; one launch of 2112 tiles, more than its grid of 2048 workgroups
   FrameResizer  a batch tensor, pitched views of several sizes and (FrameStore, slot) pairs, in one launch each
   scale_detect  FaceDetector.scale_detect on 359 x 641 and 240 x 320 frames equals post_detect(detect(resize_ref frames)), row for row
   YuNet         detect_resized equals detect on the host-resized frame followed by the float64 scaling; infer_resized likewise
@@ -63,8 +63,9 @@ def _layout(sizes, aligned):
     return places, at
 
 
-def _launch(refs, jobs, aligned, out=None, n_launch=None):
-    """jobs = [(store, frame, dw, dh)] in ONE launch -> (the whole destination buffer as numpy, the layout)"""
+def _launch(refs, jobs, aligned, out=None, n_launch=None, header=None):
+    """jobs = [(store, frame, dw, dh)] in ONE launch -> (the whole destination buffer as numpy, the layout); a list handed in as
+    `header` receives the planned table's af_resize_header"""
     places, total = _layout([(dw, dh) for _, _, dw, dh in jobs], aligned)
     if out is None:
         out = torch.full((total,), FILL, dtype=torch.uint8, device="cuda")
@@ -74,6 +75,8 @@ def _launch(refs, jobs, aligned, out=None, n_launch=None):
     table = torch.zeros(need // 8 + 1, dtype=torch.int64)
     used = C.c_int64(0)
     _lib.check(L.af_resize_plan_u8(C.byref(arr), len(jobs), C.byref(stores), len(refs), C.c_void_p(table.data_ptr()), need, C.byref(used)), "plan")
+    if header is not None:
+        header.append(_lib.ResizeHeader.from_buffer_copy(table.numpy().tobytes()[:C.sizeof(_lib.ResizeHeader)]))
     table_dev = table.cuda()
     _lib.check(L.af_resize_frames_u8(C.c_void_p(table_dev.data_ptr()), len(jobs) if n_launch is None else n_launch,
                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), "launch")
@@ -143,6 +146,24 @@ def test_sixty_four_mixed_jobs_out_of_three_stores_in_one_launch():
             for i, (s, f, dw, dh) in enumerate(jobs):                            # each job alone: the same bytes
                 alone, place = _launch(refs, [(s, f, dw, dh)], aligned)
                 assert np.array_equal(_rows(alone, place[0], dw, dh), _rows(got, places[i], dw, dh)), i
+
+
+BIG = [(66, 512), (132, 1024), (100, 700)]           # h x w -> 66 x 512: a copy, the 2 x 2 path, bilinear
+
+
+@pytest.mark.parametrize("aligned", [True, False], ids=["aligned", "odd"])
+def test_a_launch_of_more_tiles_than_workgroups(aligned):
+    """64 jobs of 128 runs x 66 rows = 33 tiles each: 2112 tiles for a grid of 2048 workgroups, so the first 64 workgroups take a
+    second tile (the last two jobs: a copy and the 2 x 2 path when aligned, bilinear and a copy when not)"""
+    assert not R.is_area2(512, 66, 512, 66) and R.is_area2(1024, 132, 512, 66) and not R.is_area2(700, 100, 512, 66)
+    held = [_store(_case(h, w, 66, 512)[0]) for h, w in BIG]
+    jobs = [((i + int(aligned)) % 3, (i // 3) % 2, 512, 66) for i in range(64)]
+    want = [_case(*BIG[s], 66, 512)[1][f] for s, f, _, _ in jobs]
+    header = []
+    got, places = _launch([r for _, r in held], jobs, aligned, header=header)
+    assert header[0].total_tiles == 64 * 33 > 2048                               # the launch's grid, which _lib does not export
+    bad = np.flatnonzero(got != _expected(got.size, places, want))
+    assert bad.size == 0, "%d bytes differ, the first at %d (rows at %s)" % (bad.size, bad[0], places[:3])
 
 
 def test_a_launch_whose_n_differs_from_the_tables_writes_nothing():
