@@ -368,6 +368,80 @@ int af_mlp_head(const float* z, const float* weights, int clips, int n, int hidd
 int af_gated_moe(const float* z_rgb, const float* z_dual, const float* weights, int hidden, int n, float* z, float* gate,
                  void* stream);
 
+/* ---- dualrun at video level: raw landmark / AU tracks -> clip features, clip logits -> track and video verdicts ---- */
+
+/* One face track on the device: lmk = n rows of P >= 467 (x, y) fp32 points, a row every lmk_pitch >= 934 floats; au = n rows of
+ * K fp32 action units (columns in the reference's sorted-key order), a row every au_pitch >= K floats. */
+typedef struct af_dualv_track {
+    const float* lmk;
+    const float* au;
+    int64_t lmk_pitch;
+    int32_t au_pitch;
+    int32_t n;
+} af_dualv_track;
+
+/* One clip: frames first .. first + len - 1 of track `track`, 1 <= len <= 16. */
+typedef struct af_dualv_clip {
+    int32_t track, first, len, reserved;
+} af_dualv_clip;
+
+#define AF_DUALV_MAX_T 16
+#define AF_DUALV_LMK_DIM 132
+#define AF_DUALV_MIN_POINTS 467      /* the key set reaches index 466 (make_lmk_features.py:52 computes it; its comment says 309) */
+#define AF_DUALV_ZSCORE_NONE 0
+#define AF_DUALV_ZSCORE_CLIP 1
+#define AF_DUALV_ZSCORE_GLOBAL 2
+#define AF_DUALV_APPLY_BOTH 0
+#define AF_DUALV_APPLY_AU 1
+#define AF_DUALV_APPLY_LMK 2
+
+typedef struct af_dualv_opts {
+    int32_t frames;                 /* T: rows per clip handed to the encoder, 1..16            */
+    int32_t au_k;                   /* K raw action units per frame                             */
+    int32_t zscore_mode;            /* AF_DUALV_ZSCORE_*                                        */
+    int32_t zscore_apply;           /* AF_DUALV_APPLY_*                                         */
+    int32_t use_delta, use_delta2;  /* append diff(X) / diff(diff(X)): F_au = K * (1 + d + d2)  */
+    const float* au_mean;           /* [F_au], [F_au], [132], [132] device vectors: all four in */
+    const float* au_std;            /* global mode, ignored otherwise                           */
+    const float* lmk_mean;
+    const float* lmk_std;
+} af_dualv_opts;
+
+/* dualrun's feature path per clip, ONE launch (grid = clips): make_lmk_features._seq_to_features (the 66 key points centred on
+ * the nose, divided by ||mouth left - mouth right|| + 1e-6; a frame whose scale is not finite or < 1e-8 is dropped and the rest
+ * compacted), make_au_features.seq_au_to_features (X | diff | diff of diff, each with its first row prepended), fixT per modality
+ * (centre crop / repeat the last row) and fusion.normalize_features (clip: mean and unbiased std over the T rows, clamp 1e-6;
+ * global: the given vectors, std floored at 1e-6; nan_to_num in both; none: untouched).  tracks [n_tracks] and clips [n_clips]
+ * are DEVICE tables.  A [n_clips][T][F_au], L [n_clips][T][132], nvalid [n_clips] = landmark frames that survived; a clip
+ * with none (or a clip record that leaves its track) gets nvalid 0 and zeros.  Arithmetic and its order: tests/dualvideo_ref.py. */
+int af_dual_clip_features(const af_dualv_track* tracks, int n_tracks, const af_dualv_clip* clips, int n_clips,
+                          const af_dualv_opts* opts, float* A, float* L, int32_t* nvalid, void* stream);
+
+#define AF_DUALV_FAMILY_FUSION 0    /* fusion.track_reduce / agg_video on logits                 */
+#define AF_DUALV_FAMILY_BEST 1      /* best.aggregate_video_predictions on sigmoid(logit)        */
+#define AF_DUALV_TRACK_MEDIAN 0     /* fusion family: torch.median (the lower middle value)      */
+#define AF_DUALV_TRACK_MEAN 1
+#define AF_DUALV_VIDEO_MAX 0
+#define AF_DUALV_VIDEO_MEDIAN 1
+#define AF_DUALV_VIDEO_MEAN 2
+#define AF_DUALV_BEST_TRACK_MEAN 0  /* best family: track_mode                                   */
+#define AF_DUALV_BEST_TRACK_MEDIAN 1 /* np.median: the midpoint on an even count, fp64           */
+#define AF_DUALV_BEST_TRACK_MAJORITY 2
+
+/* Clip logits -> track and video verdicts, ONE launch (grid = videos).  video_tracks [videos + 1]: video v owns tracks
+ * video_tracks[v] .. video_tracks[v + 1] - 1; track_clips [tracks + 1]: track t owns clip_index[track_clips[t] ..
+ * track_clips[t + 1] - 1], clip numbers < clips in input order.  Clips with nvalid == 0 are skipped, a track left with none is
+ * skipped (track_count 0), a video left with none gets NaN (fusion) or score 0, pred 0 (best).  sigmoid = fp32(1 / (1 + exp(-x)))
+ * evaluated in fp64.  Fusion family writes track_logit, track_prob [tracks], video_logit, video_prob [videos]; best family
+ * writes clip_prob [clips] (sigmoid of every clip the CSR names: best.py's y_score_clip), track_score [tracks] (fp64), track_pred
+ * [tracks], video_score [videos] (fp64), video_pred [videos]; both write
+ * track_count [tracks] = clips used.  Means are sequential sums in input order (fp32 for fusion, fp64 for best). */
+int af_dual_video_reduce(const float* logits, const int32_t* nvalid, int clips, const int32_t* video_tracks, int videos,
+                         const int32_t* track_clips, int tracks, const int32_t* clip_index, int family, int track_mode,
+                         int video_mode, double prob_thresh, float* track_logit, float* track_prob, float* video_logit,
+                         float* video_prob, float* clip_prob, double* track_score, int32_t* track_pred, double* video_score,
+                         int32_t* video_pred, int32_t* track_count, void* stream);
+
 /* ---- clip aligner --------------------------------------------------- */
 
 /* Replaces the per-frame loop of FasterCropAlignXRay.__call__ / process_single

@@ -18,6 +18,9 @@ def __getattr__(name):
     if name in ("YuvFrame", "CapturedFrame", "FrameResizer"):
         from . import frames
         return getattr(frames, name)
+    if name in ("DualVideoScorer", "DualTrack"):
+        from . import dual_video
+        return getattr(dual_video, name)
     if name == "ByteTracker":
         from . import tracker
         return tracker.ByteTracker

@@ -143,6 +143,32 @@ class CaptureTap(C.Structure):
     _fields_ = [("idx", C.c_int32), ("weight", C.c_float)]
 
 
+class DualvTrack(C.Structure):
+    """af_dualv_track: one face track's raw landmark and AU rows on the device"""
+    _fields_ = [("lmk", C.c_void_p), ("au", C.c_void_p), ("lmk_pitch", C.c_int64), ("au_pitch", C.c_int32), ("n", C.c_int32)]
+
+
+class DualvClip(C.Structure):
+    """af_dualv_clip: frames first .. first + len - 1 of a track"""
+    _fields_ = [("track", C.c_int32), ("first", C.c_int32), ("len", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DualvOpts(C.Structure):
+    """af_dualv_opts"""
+    _fields_ = [("frames", C.c_int32), ("au_k", C.c_int32), ("zscore_mode", C.c_int32), ("zscore_apply", C.c_int32),
+                ("use_delta", C.c_int32), ("use_delta2", C.c_int32), ("au_mean", C.c_void_p), ("au_std", C.c_void_p),
+                ("lmk_mean", C.c_void_p), ("lmk_std", C.c_void_p)]
+
+
+DUALV_MAX_T, DUALV_LMK_DIM, DUALV_MIN_POINTS = 16, 132, 467
+DUALV_ZSCORE = {"none": 0, "clip": 1, "global": 2}
+DUALV_APPLY = {"both": 0, "au": 1, "lmk": 2}
+DUALV_FAMILY_FUSION, DUALV_FAMILY_BEST = 0, 1
+DUALV_TRACK = {"median": 0, "mean": 1}
+DUALV_VIDEO = {"max": 0, "median": 1, "mean": 2}
+DUALV_BEST = {"track_mean": 0, "track_median": 1, "track_majority": 2}
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n", "t", "h", "w", "c", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw", "to", "ho", "wo", "dtype",
@@ -301,6 +327,9 @@ ABI = {
     "af_dual_branch_encoders": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p,
                                            C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "af_gated_moe": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "af_dual_clip_features": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(DualvOpts)] + [C.c_void_p] * 4),
+    "af_dual_video_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 11),
     "af_warp_affine_clip_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int,
                                          C.c_void_p, C.c_void_p]),
     "af_dual_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
