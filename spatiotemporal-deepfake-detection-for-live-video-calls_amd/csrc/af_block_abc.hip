@@ -21,7 +21,7 @@
 // PROJ form (block 0 of the Fast pathway's s2: 8 -> 32 channels, stride 1): the input has CIN channels instead of C, the shortcut
 // is the 1x1x1 projection `branch1` (resnet_helper.py:411-436) accumulated into c's tile like af_conv3d_dual_bn_act does - both
 // weight sets carry their BN scale (folded in fp32 by the caller), shift = shift_c + shift_1 - and no residual is added.
-#include "af_common.h"
+#include "af_conv_paths.h"
 
 namespace af {
 
@@ -294,18 +294,18 @@ static bool abc_geometry(const af_conv_desc* da, const af_conv_desc* db, const a
     if ((inner != 8 && inner != 16 && inner != 32) || db->cin != inner || db->cout != inner || dc->cin != inner || dc->cout != 4 * inner) return false;
     if (d1) {   // projection form: instantiated for the Fast pathway's s2 (8 -> 8 -> 8 -> 32)
         if (inner != 8 || cin != 8 || d1->dtype != da->dtype || d1->cin != cin || d1->cout != dc->cout) return false;
-        if (d1->kt != 1 || d1->kh != 1 || d1->kw != 1 || d1->st != 1 || d1->sh != 1 || d1->sw != 1 || d1->pt || d1->ph || d1->pw || d1->tpool) return false;
-        if (d1->n != da->n || d1->t != da->t || d1->h != da->h || d1->w != da->w) return false;
+        if (!pointwise(d1) || d1->tpool) return false;
+        if (!same_input(d1, da)) return false;
     } else if (cin != 4 * inner) {
         return false;
     }
-    if ((da->kt != 1 && da->kt != 3) || da->kh != 1 || da->kw != 1 || da->pt != da->kt / 2 || da->ph || da->pw) return false;
-    if (db->kt != 1 || db->kh != 3 || db->kw != 3 || db->pt || db->ph != 1 || db->pw != 1) return false;
-    if (dc->kt != 1 || dc->kh != 1 || dc->kw != 1 || dc->pt || dc->ph || dc->pw) return false;
+    if ((!kernel_is(da, 1, 1, 1) && !kernel_is(da, 3, 1, 1)) || !pad_is(da, da->kt / 2, 0, 0)) return false;
+    if (!kernel_is(db, 1, 3, 3) || !pad_is(db, 0, 1, 1)) return false;
+    if (!kernel_is(dc, 1, 1, 1) || !pad_is(dc, 0, 0, 0)) return false;
     const af_conv_desc* all[3] = {da, db, dc};
     for (const af_conv_desc* d : all) {
-        if (d->st != 1 || d->sh != 1 || d->sw != 1 || d->tpool || !d->relu) return false;
-        if (d->n != da->n || d->t != da->t || d->h != da->h || d->w != da->w || d->to != da->t || d->ho != da->h || d->wo != da->w) return false;
+        if (!unit_stride(d) || d->tpool || !d->relu) return false;
+        if (!same_input(d, da) || !keeps_size(d)) return false;
     }
     if ((long long)da->h * da->w * 8 * inner >= (1LL << 31)) return false;
     // patch rows: the phases of a frame are short dependent chains (LDS read -> MFMA -> BN -> LDS write, a barrier between them),
@@ -316,23 +316,15 @@ static bool abc_geometry(const af_conv_desc* da, const af_conv_desc* db, const a
     int p = 7;
     if (p > da->h) p = da->h;
     if (p < 1) p = 1;
-    while (p > 1 && abc_lds_bytes(inner, cin, p, da->kt) > 160 * 1024) --p;
+    while (p > 1 && abc_lds_bytes(inner, cin, p, da->kt) > kLdsBudget) --p;
     p = (da->h + (da->h + p - 1) / p - 1) / ((da->h + p - 1) / p);                  // even bands
-    if (abc_lds_bytes(inner, cin, p, da->kt) > 160 * 1024 || ((p + 2) * 16 * (cin / 8) + 63) / 64 > 24) return false;   // <= 6 DMA pieces per producer wave and frame
+    if (abc_lds_bytes(inner, cin, p, da->kt) > kLdsBudget || ((p + 2) * 16 * (cin / 8) + 63) / 64 > 24) return false;   // <= 6 DMA pieces per producer wave and frame
     const long long units = abc_units(da, p, 1);
     int s = 1;
     while (units * s < 256 && da->t / (2 * s) >= 4) s *= 2;           // time segments of >= 4 frames until the chip is covered
     if (units * s > 0x7fffffffLL) return false;
     *ph = p; *ts_n = s;
     return true;
-}
-
-template <int DT, int INNER, int CIN>
-static int launch_abc(const ABCArgs& a, int units, int lds, hipStream_t stream) {
-    AF_SET_MAX_LDS((&block_abc_kernel<DT, INNER, CIN>), 160 * 1024, "block_abc");
-    hipLaunchKernelGGL((block_abc_kernel<DT, INNER, CIN>), dim3(units), dim3(512), lds, stream, a);
-    AF_CHECK_LAUNCH("block_abc_kernel");
-    return AF_OK;
 }
 
 }  // namespace af
@@ -356,11 +348,9 @@ extern "C" int af_block_abc_bn_act(const af_conv_desc* da, const void* x, const 
                                    const af_conv_desc* dc, const void* wc_packed, const float* scale_c, const float* shift_c,
                                    const af_conv_desc* d1, const void* w1_packed, void* out, int out_ld, void* stream) {
     using namespace af;
-    AF_REQUIRE(da && db && dc && x && wa_packed && wb_packed && wc_packed && scale_a && shift_a && scale_b && shift_b && scale_c && shift_c && out,
-               "block_abc: null argument");
+    AF_REQUIRE(none_null(da, db, dc, x, wa_packed, wb_packed, wc_packed, scale_a, shift_a, scale_b, shift_b, scale_c, shift_c, out), "block_abc: null argument");
     AF_REQUIRE((d1 != nullptr) == (w1_packed != nullptr), "block_abc: the projection shortcut needs both its descriptor and its weight");
-    AF_REQUIRE(aligned16(x) && aligned16(wa_packed) && aligned16(wb_packed) && aligned16(wc_packed) && aligned16(w1_packed) && aligned16(scale_a) &&
-                   aligned16(shift_a) && aligned16(scale_b) && aligned16(shift_b) && aligned16(scale_c) && aligned16(shift_c) && aligned16(out),
+    AF_REQUIRE(all_aligned16(x, wa_packed, wb_packed, wc_packed, w1_packed, scale_a, shift_a, scale_b, shift_b, scale_c, shift_c, out),
                "block_abc: buffers must be 16-byte aligned");
     int ph = 0, ts_n = 0;
     AF_REQUIRE(abc_geometry(da, db, dc, d1, &ph, &ts_n), "block_abc: this block does not take the fused path (ask af_block_abc_fusable first)");
@@ -376,9 +366,11 @@ extern "C" int af_block_abc_bn_act(const af_conv_desc* da, const void* x, const 
     const int units = (int)abc_units(da, ph, ts_n);
     const int lds = abc_lds_bytes(da->cout, da->cin, ph, da->kt);
     hipStream_t s = (hipStream_t)stream;
-    const bool bf = da->dtype == AF_BF16;
-    if (d1) return bf ? launch_abc<AF_BF16, 8, 8>(a, units, lds, s) : launch_abc<AF_F16, 8, 8>(a, units, lds, s);
-    if (da->cout == 8) return bf ? launch_abc<AF_BF16, 8, 32>(a, units, lds, s) : launch_abc<AF_F16, 8, 32>(a, units, lds, s);
-    if (da->cout == 32) return bf ? launch_abc<AF_BF16, 32, 128>(a, units, lds, s) : launch_abc<AF_F16, 32, 128>(a, units, lds, s);
-    return bf ? launch_abc<AF_BF16, 16, 64>(a, units, lds, s) : launch_abc<AF_F16, 16, 64>(a, units, lds, s);
+    auto launch = [&](auto inner, auto cin) {
+        return with_dtype16(da->dtype, [&](auto dt) { return launch_lds<&block_abc_kernel<dt, inner, cin>>("block_abc", units, lds, s, a); });
+    };
+    if (d1) return launch(IC<8>{}, IC<8>{});
+    if (da->cout == 8) return launch(IC<8>{}, IC<32>{});
+    if (da->cout == 32) return launch(IC<32>{}, IC<128>{});
+    return launch(IC<16>{}, IC<64>{});
 }

@@ -203,60 +203,6 @@ template <int N, int I = 0, class F> __device__ __forceinline__ void static_for(
 template <class F> inline auto with_dtype16(int dtype, F&& f) { return dtype == AF_BF16 ? f(IC<AF_BF16>{}) : f(IC<AF_F16>{}); }
 template <class F> inline auto with_dtype(int dtype, F&& f) { return dtype == AF_F32 ? f(IC<AF_F32>{}) : with_dtype16(dtype, f); }
 
-// af_conv133.hip: register-resident-weights 1x3x3 64->64 kernel (s2 `b` convs), 16-bit dtypes
-bool conv133_applies(const af_conv_desc* d, const void* residual, int out_ld);
-int conv133_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
-                void* out, hipStream_t stream);
-// af_conv133g.hip: frame / band resident 1x3x3 kernel for 128 / 256 output channels (s3 / s4 `b` convs), 16-bit dtypes
-bool conv133g_applies(const af_conv_desc* d, const void* residual, int out_ld);
-int conv133g_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
-                 void* out, int out_ld, hipStream_t stream);
-// ... and its TEMPORAL mode: 3x1x1 convs into 128 / 256 channels (s3 / s4 `a` convs): (T + 2) x P patch, three taps share it
-bool conv311g_applies(const af_conv_desc* d, const void* residual, int out_ld);
-int conv311g_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
-                 void* out, int out_ld, hipStream_t stream);
-bool conv133g_fused_applies(const af_conv_desc* db, const af_conv_desc* dc, int out_ld);
-int conv133g_fused_run(const af_conv_desc* db, const void* in, const void* wb, const float* scale_b, const float* shift_b,
-                       const af_conv_desc* dc, const void* wc, const float* scale_c, const float* shift_c, const void* residual,
-                       void* out, int out_ld, hipStream_t stream);
-// af_conv_cpa.hip: the s2 -> s3 boundary - c + residual + ReLU, the temporal max-pool and the next stage's 3x1x1 a conv in one launch
-bool conv_cpa_applies(const af_conv_desc* dc, const af_conv_desc* da, int x_sub);
-int conv_cpa_run(const af_conv_desc* dc, const void* inb, const void* wc, const float* scale_c, const float* shift_c,
-                 const void* residual, void* outx, int x_sub, const af_conv_desc* da, const void* wa, const float* scale_a,
-                 const float* shift_a, void* outa, hipStream_t stream);
-// af_conv_ca.hip: c(i) -> a(i+1) across a block boundary of s2 in the time-tiled layout (the trunk slab is produced in LDS)
-bool conv_ca_applies(const af_conv_desc* dc, const af_conv_desc* d1, const af_conv_desc* da);
-int conv_ca_run(const af_conv_desc* dc, const void* inb, const void* wc, const void* in1, const void* w1, const float* scale_c,
-                const float* shift_c, const void* residual, void* outx, const af_conv_desc* da, const void* wa, const float* scale_a,
-                const float* shift_a, void* outa, hipStream_t stream);
-// af_conv_small.hip: direct-gather MFMA path for narrow layers (<= 16 output channels, <= 32 K chunks): SlowFast's Fast pathway
-bool conv_small_applies(const af_conv_desc* d, const af_conv_desc* d2, const void* residual, int out_ld);
-int conv_small_run(const af_conv_desc* d, const void* in, const void* w_packed, const af_conv_desc* d2, const void* in2,
-                   const void* w2_packed, const float* scale, const float* shift, const void* residual, void* out, int out_ld,
-                   hipStream_t stream);
-// af_conv311.hip: time-tiled 3x1x1 -> 64 channels kernel (s2 `a` convs): the three taps share one LDS image
-bool conv311_applies(const af_conv_desc* d, const void* residual, int out_ld);
-int conv311_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
-                void* out, int out_ld, hipStream_t stream);
-
-// af_conv111.hip: persistent weights-in-registers 1x1x1 stream (short-K `c` convs of s2 / s3, with the projection
-// shortcut, the residual and the temporal pool), 16-bit dtypes
-bool conv111_applies(const af_conv_desc* d, const af_conv_desc* d2, const void* residual, int out_ld);
-int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, const af_conv_desc* d2, const void* in2,
-                const void* w2_packed, const float* scale, const float* shift, const void* residual, void* out, int out_ld,
-                hipStream_t stream);
-
-// af_conv_work_units: the work units (strips, tiles, units) of a layer that takes the path and the grid its *_run function launches
-void conv133_work(const af_conv_desc* d, long long* units, int* workgroups);
-void conv133g_work(const af_conv_desc* d, long long* units, int* workgroups);
-void conv311g_work(const af_conv_desc* d, long long* units, int* workgroups);
-void conv311_work(const af_conv_desc* d, long long* units, int* workgroups);
-void conv111_work(const af_conv_desc* d, const af_conv_desc* d2, long long* units, int* workgroups);
-// af_conv_ca_work_units / af_conv_cpa_work_units: the tiles of a fused pair and the grid its *_run function launches; false: not fused
-bool conv_ca_work(const af_conv_desc* dc, const af_conv_desc* d1, const af_conv_desc* da, long long* tiles, int* workgroups, int* form,
-                  int* pixels);
-bool conv_cpa_work(const af_conv_desc* dc, const af_conv_desc* da, int x_sub, long long* tiles, int* workgroups);
-
 // One-time PER-DEVICE setup.  hipFuncSetAttribute and the CU count belong to a device, and one process may drive several
 // (one engine per device): every "done once" flag is therefore indexed by the current device ordinal.
 constexpr int kMaxDevices = 64;

@@ -21,7 +21,7 @@
 //     hardware returns zeros (per-row validity bit per tap, computed once); no halo in HBM, no branch.
 //   * pipeline: 3-slot LDS ring, K-steps s+1 and s+2 in flight while step s is multiplied; one raw
 //     s_barrier per K-step; explicit counted s_waitcnt vmcnt (hipcc does not see the DMA loads).
-#include "af_common.h"
+#include "af_conv_paths.h"
 
 namespace af {
 
@@ -743,9 +743,7 @@ static int launch(const ConvArgs& a, hipStream_t stream) {
 // MFMA-bound: biggest tile.  Short-K layers (<= 3 K-steps) are HBM-bound streams of input, residual and
 // output: half-height tiles with a trimmed ring so several workgroups share a CU and overlap each
 // other's load / store phases.
-enum { VAR_128x256 = 0, VAR_64x256 = 1, VAR_128x128 = 2, VAR_64x128 = 3, VAR_C133 = 4, VAR_128x128_R2 = 5, VAR_256x256 = 6,
-       VAR_128x512 = 7, VAR_C311 = 8, VAR_SMALL = 9, VAR_C111 = 10, VAR_C133G = 11, VAR_256x224 = 12, VAR_C311G = 13, VAR_COUNT = 14 };
-
+// (the VAR_* ids: af_conv_paths.h)
 // What there is to know about a variant id, written once.  A conv_igemm tile (bn != 0): its template tuple - BMR < BM: see above -,
 // the LDS ring slots its lean K loop uses and whether its projection-block (DUAL) form is compiled; a specialised path: its name.
 struct Variant { const char* name; int bn, bm, wn, wm, ks, minw, nstage, bmr, ring; bool dual; };
@@ -855,16 +853,13 @@ static ConvPad conv_pad(const af_conv_desc* d, const af_conv_desc* d2) {
 }
 static int pick_variant(const af_conv_desc* d, const ConvPad& p) { return pick_variant(p.coutp, p.cinp, p.taps, d->dtype, p.M, p.cin2p, d->tpool); }
 
-// The path a layer takes, as a VAR_* value; the specialised kernels in their order of precedence, then the generic tile.
-// af_conv_variant reports it (the engine plans from that) and conv_common runs it.
-static int conv_path(const af_conv_desc* d, const af_conv_desc* d2, const void* residual, int out_ld, const ConvPad& p) {
-    if (conv_small_applies(d, d2, residual, out_ld)) return VAR_SMALL;
-    if (!d2 && conv133_applies(d, residual, out_ld)) return VAR_C133;
-    if (!d2 && conv133g_applies(d, residual, out_ld)) return VAR_C133G;
-    if (!d2 && conv311g_applies(d, residual, out_ld)) return VAR_C311G;
-    if (!d2 && conv311_applies(d, residual, out_ld)) return VAR_C311;
-    if (conv111_applies(d, d2, residual, out_ld)) return VAR_C111;
-    return pick_variant(d, p);
+// The specialised paths in their order of precedence; a layer none of them takes runs the generic tile pick_variant chooses.
+// af_conv_variant and af_conv_work_units report from this table (the engine plans from that) and conv_common runs from it.
+static const ConvPath* conv_path(const ConvCall& c) {
+    static const ConvPath* const paths[] = {&conv_small_path(), &conv133_path(), &conv133g_path(), &conv311g_path(), &conv311_path(), &conv111_path()};
+    for (const ConvPath* path : paths)
+        if (path->applies(c)) return path;
+    return nullptr;
 }
 
 // launches tile `v` in one of the three forms of the kernel: plain, DUAL (second K segment) or SPLITK.  An id without a tile of its
@@ -901,29 +896,29 @@ static int dispatch(ConvArgs& a, const ConvPad& p, int v, hipStream_t stream) {
 
 extern "C" int af_conv_variant(const af_conv_desc* d, const af_conv_desc* d2) {
     AF_REQUIRE(d && d->cout > 0 && d->cin > 0 && af::dtype_ok(d->dtype), "conv_variant: bad descriptor");
-    return af::conv_path(d, d2, nullptr, 0, af::conv_pad(d, d2));
+    const af::ConvCall question = {d, d2};
+    const af::ConvPath* path = af::conv_path(question);
+    return path ? path->variant : af::pick_variant(d, af::conv_pad(d, d2));
 }
 
 extern "C" int af_conv_work_units(const af_conv_desc* d, const af_conv_desc* d2, int64_t* units, int* workgroups) {
     using namespace af;
     AF_REQUIRE(d && units && workgroups && d->cout > 0 && d->cin > 0 && dtype_ok(d->dtype), "conv_work_units: bad argument");
     AF_REQUIRE(d->n > 0 && d->to > 0 && d->ho > 0 && d->wo > 0, "conv_work_units: bad dims");
-    const ConvPad p = conv_pad(d, d2);
-    const int v = conv_path(d, d2, nullptr, 0, p);
+    const ConvCall question = {d, d2};
+    const ConvPath* path = conv_path(question);
     long long u = 0;
-    int g = 0;
-    switch (v) {
-        case VAR_C133: conv133_work(d, &u, &g); break;
-        case VAR_C133G: conv133g_work(d, &u, &g); break;
-        case VAR_C311G: conv311g_work(d, &u, &g); break;
-        case VAR_C311: conv311_work(d, &u, &g); break;
-        case VAR_C111: conv111_work(d, d2, &u, &g); break;
-        case VAR_SMALL: return set_error(AF_ERR_ARG, "conv_work_units: the narrow-layer path is not cut into units");
-        default: {
-            u = igemm_tiles(p.M, variant_bm(v), p.coutp / variant_bn(v));
-            AF_REQUIRE(u > 0 && u <= 0x7fffffffLL, "conv_work_units: grid of %lld workgroups", u);
-            g = (int)u;
-        }
+    int g = 0, v;
+    if (path) {
+        AF_REQUIRE(path->variant != VAR_SMALL, "conv_work_units: the narrow-layer path is not cut into units");
+        path->work(question, &u, &g);
+        v = path->variant;
+    } else {
+        const ConvPad p = conv_pad(d, d2);
+        v = pick_variant(d, p);
+        u = igemm_tiles(p.M, variant_bm(v), p.coutp / variant_bn(v));
+        AF_REQUIRE(u > 0 && u <= 0x7fffffffLL, "conv_work_units: grid of %lld workgroups", u);
+        g = (int)u;
     }
     *units = u; *workgroups = g;
     return v;
@@ -945,7 +940,7 @@ static int conv_common(const af_conv_desc* d, const void* in, const void* w_pack
                        const void* in2, const void* w2_packed, const float* scale, const float* shift,
                        const void* residual, void* out, int out_ld, void* workspace, int64_t workspace_bytes, void* stream) {
     using namespace af;
-    AF_REQUIRE(d && in && w_packed && scale && shift && out, "conv: null argument");
+    AF_REQUIRE(none_null(d, in, w_packed, scale, shift, out), "conv: null argument");
     AF_REQUIRE(dtype_ok(d->dtype), "conv: bad dtype %d", d->dtype);
     AF_REQUIRE(d->n > 0 && d->t > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0, "conv: bad dims");
     AF_REQUIRE(d->kt > 0 && d->kh > 0 && d->kw > 0 && d->st > 0 && d->sh > 0 && d->sw > 0, "conv: bad kernel/stride");
@@ -959,8 +954,7 @@ static int conv_common(const af_conv_desc* d, const void* in, const void* w_pack
     AF_REQUIRE(d->cout % epc == 0, "conv: cout=%d must be a multiple of %d for this dtype", d->cout, epc);
     if (out_ld == 0) out_ld = d->cout;
     AF_REQUIRE(out_ld >= d->cout && out_ld % 8 == 0, "conv: bad out_ld %d", out_ld);
-    AF_REQUIRE(aligned16(in) && aligned16(w_packed) && aligned16(scale) && aligned16(shift) && aligned16(out) &&
-                   aligned16(residual), "conv: buffers must be 16-byte aligned");
+    AF_REQUIRE(all_aligned16(in, w_packed, scale, shift, out, residual), "conv: buffers must be 16-byte aligned");
     AF_REQUIRE((long long)(d->cout + 63) * d->kt * d->kh * d->kw * (d->cin + bk) < (1LL << 31), "conv: weight too large");
     AF_REQUIRE(d->kt * d->kh * d->kw <= 31, "conv: at most 31 kernel taps (got %d)", d->kt * d->kh * d->kw);
     AF_REQUIRE((long long)d->kt * d->h * d->w * d->cin * dtype_size(d->dtype) < (1LL << 31), "conv: tap offset overflows");
@@ -970,15 +964,10 @@ static int conv_common(const af_conv_desc* d, const void* in, const void* w_pack
     AF_REQUIRE((256 / ((long long)to * ho * wo) + 3) * d->t * d->h * d->w * d->cin * dtype_size(d->dtype) < (1LL << 31),
                "conv: one clip of input is too large for 32-bit tile offsets");
 
-    const ConvPad p = conv_pad(d, d2);
-    const int path = conv_path(d, d2, residual, out_ld, p);
-    switch (path) {
-        case VAR_C133: return conv133_run(d, in, w_packed, scale, shift, out, (hipStream_t)stream);
-        case VAR_C133G: return conv133g_run(d, in, w_packed, scale, shift, out, out_ld, (hipStream_t)stream);
-        case VAR_C311G: return conv311g_run(d, in, w_packed, scale, shift, out, out_ld, (hipStream_t)stream);
-        case VAR_C311: return conv311_run(d, in, w_packed, scale, shift, out, out_ld, (hipStream_t)stream);
-        default: break;   // the other paths take a second segment or a residual: their checks come first
-    }
+    const ConvCall call = {d, d2, in, w_packed, in2, w2_packed, scale, shift, residual, out, out_ld, (hipStream_t)stream};
+    const ConvPath* path = conv_path(call);
+    if (path && path->before_segment_checks) return path->run(call);
+    // (the other paths take a second segment or a residual: their checks come first)
     ConvArgs a;
     a.in = (const char*)in; a.w = (const char*)w_packed; a.scale = scale; a.shift = shift;
     a.res = (const char*)residual; a.out = (char*)out;
@@ -1019,11 +1008,10 @@ static int conv_common(const af_conv_desc* d, const void* in, const void* w_pack
         a.in2 = (const char*)in2; a.w2 = (const char*)w2_packed;
         a.T2 = d2->t; a.H2 = d2->h; a.W2 = d2->w; a.Cin2 = d2->cin; a.st2 = d2->st; a.sh2 = d2->sh; a.sw2 = d2->sw;
     }
-    if (path == VAR_SMALL)
-        return conv_small_run(d, in, w_packed, d2, in2, w2_packed, scale, shift, residual, out, out_ld, (hipStream_t)stream);
-    if (path == VAR_C111)
-        return conv111_run(d, in, w_packed, d2, in2, w2_packed, scale, shift, residual, out, out_ld, (hipStream_t)stream);
-    return with_dtype(d->dtype, [&](auto dt) { return dispatch<dt>(a, p, path, (hipStream_t)stream); });
+    if (path) return path->run(call);
+    const ConvPad p = conv_pad(d, d2);
+    const int tile = pick_variant(d, p);
+    return with_dtype(d->dtype, [&](auto dt) { return dispatch<dt>(a, p, tile, (hipStream_t)stream); });
 }
 
 extern "C" int af_conv3d_bn_act(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale,
@@ -1050,14 +1038,12 @@ extern "C" int af_conv3d_ca_bn_act(const af_conv_desc* dc, const void* in_b, con
                                    const void* residual, void* out_x, const af_conv_desc* da, const void* wa_packed,
                                    const float* scale_a, const float* shift_a, void* out_a, void* stream) {
     using namespace af;
-    AF_REQUIRE(dc && da && in_b && wc_packed && scale_c && shift_c && out_x && wa_packed && scale_a && shift_a && out_a, "conv_ca: null argument");
+    AF_REQUIRE(none_null(dc, da, in_b, wc_packed, scale_c, shift_c, out_x, wa_packed, scale_a, shift_a, out_a), "conv_ca: null argument");
     AF_REQUIRE((d1 != nullptr) == (in1 != nullptr) && (d1 != nullptr) == (w1_packed != nullptr) && (d1 != nullptr) != (residual != nullptr),
                "conv_ca: either a residual (plain block) or the projection shortcut (d1, in1, w1: block 0), not both");
-    AF_REQUIRE(aligned16(in_b) && aligned16(wc_packed) && aligned16(in1) && aligned16(w1_packed) && aligned16(scale_c) && aligned16(shift_c) &&
-                   aligned16(residual) && aligned16(out_x) && aligned16(wa_packed) && aligned16(scale_a) && aligned16(shift_a) && aligned16(out_a),
+    AF_REQUIRE(all_aligned16(in_b, wc_packed, in1, w1_packed, scale_c, shift_c, residual, out_x, wa_packed, scale_a, shift_a, out_a),
                "conv_ca: buffers must be 16-byte aligned");
-    AF_REQUIRE(dc->to == dc->t && dc->ho == dc->h && dc->wo == dc->w && da->to == da->t && da->ho == da->h && da->wo == da->w,
-               "conv_ca: both convolutions keep the tensor size");
+    AF_REQUIRE(keeps_size(dc) && keeps_size(da), "conv_ca: both convolutions keep the tensor size");
     AF_REQUIRE(conv_ca_applies(dc, d1, da), "conv_ca: this (1x1x1 c, 3x1x1 a) pair does not take the fused path (ask af_conv_ca_fusable first)");
     return conv_ca_run(dc, in_b, wc_packed, in1, w1_packed, scale_c, shift_c, residual, out_x, da, wa_packed, scale_a, shift_a, out_a,
                        (hipStream_t)stream);
@@ -1071,11 +1057,9 @@ extern "C" int af_conv3d_bc_bn_act(const af_conv_desc* db, const void* in, const
                                    const float* shift_b, const af_conv_desc* dc, const void* wc_packed, const float* scale_c,
                                    const float* shift_c, const void* residual, void* out, int out_ld, void* stream) {
     using namespace af;
-    AF_REQUIRE(db && dc && in && wb_packed && scale_b && shift_b && wc_packed && scale_c && shift_c && out, "conv_bc: null argument");
-    AF_REQUIRE(aligned16(in) && aligned16(wb_packed) && aligned16(wc_packed) && aligned16(scale_b) && aligned16(shift_b) &&
-                   aligned16(scale_c) && aligned16(shift_c) && aligned16(residual) && aligned16(out), "conv_bc: buffers must be 16-byte aligned");
-    AF_REQUIRE(db->to == db->t && db->ho == db->h && db->wo == db->w && dc->to == dc->t && dc->ho == dc->h && dc->wo == dc->w,
-               "conv_bc: both convolutions keep the spatial size");
+    AF_REQUIRE(none_null(db, dc, in, wb_packed, scale_b, shift_b, wc_packed, scale_c, shift_c, out), "conv_bc: null argument");
+    AF_REQUIRE(all_aligned16(in, wb_packed, wc_packed, scale_b, shift_b, scale_c, shift_c, residual, out), "conv_bc: buffers must be 16-byte aligned");
+    AF_REQUIRE(keeps_size(db) && keeps_size(dc), "conv_bc: both convolutions keep the spatial size");
     AF_REQUIRE(conv133g_fused_applies(db, dc, out_ld),
                "conv_bc: this (1x3x3, 1x1x1) pair does not take the fused path (ask af_conv_bc_fusable first)");
     return conv133g_fused_run(db, in, wb_packed, scale_b, shift_b, dc, wc_packed, scale_c, shift_c, residual, out, out_ld,

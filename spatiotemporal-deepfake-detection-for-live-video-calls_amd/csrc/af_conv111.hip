@@ -21,7 +21,7 @@
 //
 // Temporal pool (tpool): tile = (clip, frame pair, 64 pixels).  Rows are ordered so that the two frames of a pixel
 // are accumulator tiles j and j + 2 of the SAME lane: the pair max needs no exchange at all.
-#include "af_common.h"
+#include "af_conv_paths.h"
 
 namespace af {
 
@@ -306,10 +306,7 @@ __global__ __launch_bounds__(512, 1) void conv111_kernel(const C111Args a) {
 template <int DT, int KS1, int KS2, bool TPOOL, bool RES, int BM = 128, int NSLOT = 2>
 static int launch111(const C111Args& a, int blocks, hipStream_t stream) {
     const int lds = NSLOT * (KS1 + KS2) * BM * 128 + 8 * 16 * (64 + 4) * 4;        // ring + the waves' epilogue patches
-    AF_SET_MAX_LDS((&conv111_kernel<DT, KS1, KS2, TPOOL, RES, BM, NSLOT>), lds, "conv111");
-    hipLaunchKernelGGL((conv111_kernel<DT, KS1, KS2, TPOOL, RES, BM, NSLOT>), dim3(blocks), dim3(512), lds, stream, a);
-    AF_CHECK_LAUNCH("conv111_kernel");
-    return AF_OK;
+    return launch_lds<&conv111_kernel<DT, KS1, KS2, TPOOL, RES, BM, NSLOT>>("conv111", blocks, lds, stream, a);
 }
 
 // How a layer runs on the persistent stream: position tiles over columns of 256 channels (ok == false: not this path)
@@ -317,11 +314,11 @@ struct Geom111 { bool ok; int ncol, HW, chunks, tiles; long long M; };
 static Geom111 geom111(const af_conv_desc* d, const af_conv_desc* d2) {
     Geom111 g = {};
     if (d->dtype == AF_F32) return g;
-    if (d->kt != 1 || d->kh != 1 || d->kw != 1 || d->st != 1 || d->sh != 1 || d->sw != 1 || d->pt || d->ph || d->pw) return g;
+    if (!pointwise(d)) return g;
     if (d->cout % 256 != 0 || (d->tpool != 0 && d->tpool != 1)) return g;
     if (d2) {
         if (d->cin != 64 || d2->cin != 64 || d->tpool) return g;
-        if (d2->st != 1 || d2->sh != 1 || d2->sw != 1 || d2->t != d->t || d2->h != d->h || d2->w != d->w) return g;
+        if (!unit_stride(d2) || !same_frames(d2, d)) return g;
     } else if (d->cin != 64 && d->cin != 128 && d->cin != 256) return g;
     if (d->tpool && (d->cin != 64 || d->t % 2 != 0)) return g;
     const long long hw = (long long)d->h * d->w, chunks = (hw + 63) / 64;
@@ -332,7 +329,7 @@ static Geom111 geom111(const af_conv_desc* d, const af_conv_desc* d2) {
     const long long tiles = d->tpool ? (long long)d->n * (d->t / 2) * chunks : (M + bm - 1) / bm;
     if (tiles >= (1LL << 30)) return g;
     // persistent streams only pay with several tiles per workgroup (one clip of the deep stages stays on the generic path)
-    if (tiles * bm / 128 * (d->cout / 256) < 4LL * device_cus()) return g;                // (counted in 128-position tiles)
+    if (!fills_chip(tiles * bm / 128 * (d->cout / 256))) return g;                // (counted in 128-position tiles)
     g.ok = true; g.ncol = d->cout / 256; g.HW = (int)hw; g.chunks = (int)chunks; g.tiles = (int)tiles; g.M = M;
     return g;
 }
@@ -343,23 +340,24 @@ static int grid111(const Geom111& g) {
     if (streams > g.tiles) streams = g.tiles;
     return streams * g.ncol;
 }
-void conv111_work(const af_conv_desc* d, const af_conv_desc* d2, long long* units, int* workgroups) {
-    const Geom111 g = geom111(d, d2);
+static void c111_work(const ConvCall& c, long long* units, int* workgroups) {
+    const Geom111 g = geom111(c.d, c.d2);
     *units = g.tiles; *workgroups = grid111(g);
 }
 
-bool conv111_applies(const af_conv_desc* d, const af_conv_desc* d2, const void* residual, int out_ld) {
-    if (d2 && residual) return false;
-    return geom111(d, d2).ok;
+static bool c111_applies(const ConvCall& c) {
+    if (c.d2 && c.residual) return false;
+    return geom111(c.d, c.d2).ok;
 }
 
-int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, const af_conv_desc* d2, const void* in2,
-                const void* w2_packed, const float* scale, const float* shift, const void* residual, void* out, int out_ld,
-                hipStream_t stream) {
+static int c111_run(const ConvCall& c) {
+    const af_conv_desc *d = c.d, *d2 = c.d2;
+    const void* residual = c.residual;
+    hipStream_t stream = c.stream;
     C111Args a;
-    a.in = (const char*)in; a.in2 = (const char*)in2; a.w = (const char*)w_packed; a.w2 = (const char*)w2_packed;
-    a.scale = scale; a.shift = shift; a.res = (const char*)residual; a.out = (char*)out;
-    a.Cin = d->cin; a.Cin2 = d2 ? d2->cin : 0; a.Cout = d->cout; a.out_ld = out_ld; a.relu = d->relu;
+    a.in = (const char*)c.in; a.in2 = (const char*)c.in2; a.w = (const char*)c.w; a.w2 = (const char*)c.w2;
+    a.scale = c.scale; a.shift = c.shift; a.res = (const char*)residual; a.out = (char*)c.out;
+    a.Cin = d->cin; a.Cin2 = d2 ? d2->cin : 0; a.Cout = d->cout; a.out_ld = c.out_ld; a.relu = d->relu;
     const Geom111 g = geom111(d, d2);
     a.ncol = g.ncol; a.T = d->t; a.HW = g.HW; a.chunks = g.chunks; a.M = g.M; a.tiles = g.tiles;
     const int blocks = grid111(g);
@@ -375,6 +373,12 @@ int conv111_run(const af_conv_desc* d, const void* in, const void* w_packed, con
         // K = 128: tiles of 64 positions as well (16-KB stages), three tiles ahead
         return residual ? launch111<dt, 2, 0, false, true, 64, 4>(a, blocks, stream) : launch111<dt, 2, 0, false, false, 64, 4>(a, blocks, stream);
     });
+}
+
+// (with the projection shortcut, the residual and the temporal pool)
+const ConvPath& conv111_path() {
+    static const ConvPath path = {VAR_C111, c111_applies, c111_work, c111_run, false};
+    return path;
 }
 
 }  // namespace af

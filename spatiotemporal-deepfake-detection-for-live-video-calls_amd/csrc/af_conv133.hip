@@ -16,7 +16,7 @@
 // Persistent: one workgroup per CU, two barriers per strip.  Results leave through an LDS output tile ([position][64
 // channels], swizzled like the patches): the workgroup stores whole 128-byte rows, and does so under the MFMAs of the
 // NEXT strip.
-#include "af_common.h"
+#include "af_conv_paths.h"
 
 namespace af {
 
@@ -259,8 +259,8 @@ struct Geom133 { bool ok; int strips_per_frame, total_strips, rows_alloc, lds; }
 static Geom133 geom133(const af_conv_desc* d) {
     Geom133 g = {};
     const int positions = kStripRows * (d->w + 2);           // of the 256 every workgroup multiplies
-    if (d->dtype == AF_F32 || d->cin != 64 || d->cout != 64 || d->kt != 1 || d->kh != 3 || d->kw != 3 || d->st != 1 || d->sh != 1 ||
-        d->sw != 1 || d->pt != 0 || d->ph != 1 || d->pw != 1 || !d->relu || d->tpool || positions > 256) return g;
+    if (d->dtype == AF_F32 || d->cin != 64 || d->cout != 64 || !kernel_is(d, 1, 3, 3) || !unit_stride(d) || !pad_is(d, 0, 1, 1) ||
+        !d->relu || d->tpool || positions > 256) return g;
     // narrow frames (SlowFast's Fast pathway in s5: 7 x 7) would run at 14 % and took 2.4x the generic kernel's time
     if (positions < 112) return g;
     g.ok = true; g.strips_per_frame = (d->h + kStripRows - 1) / kStripRows;
@@ -270,39 +270,33 @@ static Geom133 geom133(const af_conv_desc* d) {
     return g;
 }
 
-// persistent grid: one workgroup per CU, each a contiguous range of strips
-static int grid_c133(int total_strips) {
-    const int g_num_cus = device_cus();
-    return total_strips < g_num_cus ? total_strips : g_num_cus;
-}
-void conv133_work(const af_conv_desc* d, long long* units, int* workgroups) {
-    const Geom133 g = geom133(d);
-    *units = g.total_strips; *workgroups = grid_c133(g.total_strips);
+// true iff this layer takes the register-resident-weights path
+static bool c133_applies(const ConvCall& c) {
+    return !c.d2 && c.residual == nullptr && (c.out_ld == 0 || c.out_ld == 64) && geom133(c.d).ok;
 }
 
-template <int DT>
-static int launch_c133(const C133Args& a, int lds, hipStream_t stream) {
-    const int grid = grid_c133(a.total_strips);
-    AF_SET_MAX_LDS((&conv133_c64x2_kernel<DT, kStripRows>), kLdsBudget, "conv133");
-    hipLaunchKernelGGL((conv133_c64x2_kernel<DT, kStripRows>), dim3(grid), dim3(512), lds, stream, a);
-    AF_CHECK_LAUNCH("conv133_c64_kernel");
-    return AF_OK;
+// persistent grid: each workgroup a contiguous range of strips
+static void c133_work(const ConvCall& c, long long* units, int* workgroups) {
+    const Geom133 g = geom133(c.d);
+    *units = g.total_strips; *workgroups = persistent_grid(g.total_strips);
 }
 
-// true iff this layer takes the register-resident-weights path (also used by af_conv_variant)
-bool conv133_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    return residual == nullptr && (out_ld == 0 || out_ld == 64) && geom133(d).ok;
-}
-
-int conv133_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
-                void* out, hipStream_t stream) {
+static int c133_run(const ConvCall& c) {
+    const af_conv_desc* d = c.d;
     C133Args a;
-    a.in = (const char*)in; a.w = (const char*)w_packed; a.scale = scale; a.shift = shift; a.out = (char*)out;
+    a.in = (const char*)c.in; a.w = (const char*)c.w; a.scale = c.scale; a.shift = c.shift; a.out = (char*)c.out;
     const Geom133 g = geom133(d);
     a.H = d->h; a.W = d->w; a.frames = d->n * d->t;
     a.strips_per_frame = g.strips_per_frame; a.total_strips = g.total_strips; a.rows_alloc = g.rows_alloc;
     fill_stamps(a, "AF_C64_DBG");
-    return with_dtype16(d->dtype, [&](auto dt) { return launch_c133<dt>(a, g.lds, stream); });
+    return with_dtype16(d->dtype, [&](auto dt) {
+        return launch_lds<&conv133_c64x2_kernel<dt, kStripRows>>("conv133", persistent_grid(a.total_strips), g.lds, c.stream, a);
+    });
+}
+
+const ConvPath& conv133_path() {
+    static const ConvPath path = {VAR_C133, c133_applies, c133_work, c133_run, true};
+    return path;
 }
 
 }  // namespace af

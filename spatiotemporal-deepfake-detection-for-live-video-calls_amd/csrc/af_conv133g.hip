@@ -19,7 +19,7 @@
 //     W = 14, 6.7 % at W = 28), 8 waves = WN channel groups of 64 x WM position groups of 7 m-tiles (28 accumulator
 //     tiles per wave); the K loop is software-pipelined by k-halves like the generic kernel's 2-slot variant;
 //   * at B = 16 the 256 frames of s4 are exactly one unit per CU, the 512 half-frames of s3 exactly two rounds.
-#include "af_common.h"
+#include "af_conv_paths.h"
 
 namespace af {
 
@@ -570,12 +570,7 @@ static int launch133g_n(const C133GArgs& a, hipStream_t stream) {
     if (FUSEC && lds_c > lds) lds = lds_c;
     const int lds_e = 8 * 16 * (64 + 8) * 2;                                   // the epilogue's per-wave patches
     if (lds < lds_e) lds = lds_e;
-    if (lds > kLdsBudget) return set_error(AF_ERR_ARG, "conv133g: %d bytes of LDS needed", lds);
-    AF_SET_MAX_LDS((&conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), kLdsBudget, "conv133g");
-    const int grid = grid133g(a.frames * a.upf, FUSEC);
-    hipLaunchKernelGGL((conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>), dim3(grid), dim3(512), lds, stream, a);
-    AF_CHECK_LAUNCH("conv133g_kernel");
-    return AF_OK;
+    return launch_lds<&conv133g_kernel<DT, WN, WM, MT, FUSEC, MAXP, NSLOT, TEMPORAL>>("conv133g", grid133g(a.frames * a.upf, FUSEC), lds, stream, a);
 }
 
 // the ring depth of the geometry (the fused form has two slots only)
@@ -589,8 +584,7 @@ static int launch133g(const C133GArgs& a, const Geom133g& g, hipStream_t stream)
 static Geom133g geom133g(const af_conv_desc* d, bool fused = false) {
     Geom133g g = {};
     if (d->dtype == AF_F32 || d->tpool) return g;
-    if ((d->kt != 1 && d->kt != 3) || d->kh != 3 || d->kw != 3 || d->st != 1 || d->sh != 1 || d->sw != 1) return g;
-    if (d->pt != d->kt / 2 || d->ph != 1 || d->pw != 1) return g;
+    if ((!kernel_is(d, 1, 3, 3) && !kernel_is(d, 3, 3, 3)) || !unit_stride(d) || !pad_is(d, d->kt / 2, 1, 1)) return g;
     // 64 output channels only for the 3x3x3 case (the 1x3x3 64 -> 64 layers of s2 keep their weights-in-registers kernel)
     if (d->cin % 64 != 0 || (d->cout != 128 && d->cout != 256 && !(d->cout == 64 && d->kt == 3))) return g;
     const int mpad = d->cout == 256 ? 224 : d->cout == 128 ? 448 : 512;   // positions of a unit: WM x MT m-tiles
@@ -616,24 +610,23 @@ static Geom133g geom133g(const af_conv_desc* d, bool fused = false) {
     return g;
 }
 
-bool conv133g_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    return !residual && (out_ld == 0 || out_ld % 8 == 0) && geom133g(d).ok;
-}
+// neither mode takes a second segment or a residual; a question comes with out_ld 0
+static bool takes_plain_layer(const ConvCall& c) { return !c.d2 && !c.residual && (c.out_ld == 0 || c.out_ld % 8 == 0); }
+static bool c133g_applies(const ConvCall& c) { return takes_plain_layer(c) && geom133g(c.d).ok; }
 
 // units and workgroups of the launch `g` describes (af_conv_work_units)
 static void work133g(const Geom133g& g, long long* units, int* workgroups) {
     *units = (long long)g.frames * g.upf;
     *workgroups = grid133g(g.frames * g.upf, false);
 }
-void conv133g_work(const af_conv_desc* d, long long* units, int* workgroups) { work133g(geom133g(d), units, workgroups); }
+static void c133g_work(const ConvCall& c, long long* units, int* workgroups) { work133g(geom133g(c.d), units, workgroups); }
 
 // ---- TEMPORAL mode: 3x1x1 / stride 1 / pad (1,0,0) convs into 128 / 256 channels (the `a` convs of s3 / s4) on the same kernel.
 // P = pixels per unit so that T x P is the kernel's position count (224 for 256 channels, 448 for 128)
 static Geom133g geom311g(const af_conv_desc* d) {
     Geom133g g = {};
     if (d->dtype == AF_F32 || d->tpool) return g;
-    if (d->kt != 3 || d->kh != 1 || d->kw != 1 || d->st != 1 || d->sh != 1 || d->sw != 1) return g;
-    if (d->pt != 1 || d->ph != 0 || d->pw != 0) return g;
+    if (!temporal3(d)) return g;
     if (d->cin % 64 != 0 || (d->cout != 128 && d->cout != 256)) return g;
     const int mpad = d->cout == 256 ? 224 : 448;
     if (d->t < 4 || mpad % d->t != 0) return g;
@@ -650,11 +643,8 @@ static Geom133g geom311g(const af_conv_desc* d) {
     return g;
 }
 
-bool conv311g_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    return !residual && (out_ld == 0 || out_ld % 8 == 0) && geom311g(d).ok;
-}
-
-void conv311g_work(const af_conv_desc* d, long long* units, int* workgroups) { work133g(geom311g(d), units, workgroups); }
+static bool c311g_applies(const ConvCall& c) { return takes_plain_layer(c) && geom311g(c.d).ok; }
+static void c311g_work(const ConvCall& c, long long* units, int* workgroups) { work133g(geom311g(c.d), units, workgroups); }
 
 // the kernel's arguments for layer `d` cut into units as `g` says, without a fused c conv
 static void fill133g(C133GArgs& a, const Geom133g& g, const af_conv_desc* d, const void* in, const void* w_packed, const float* scale,
@@ -670,24 +660,27 @@ static void fill133g(C133GArgs& a, const Geom133g& g, const af_conv_desc* d, con
     a.out = (char*)out; a.out_ld = out_ld;
 }
 
-int conv311g_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
-                 void* out, int out_ld, hipStream_t stream) {
+static int c311g_run(const ConvCall& c) {
+    const af_conv_desc* d = c.d;
     const Geom133g g = geom311g(d);
     C133GArgs a;
-    fill133g(a, g, d, in, w_packed, scale, shift, out, out_ld ? out_ld : d->cout);
+    fill133g(a, g, d, c.in, c.w, c.scale, c.shift, c.out, c.out_ld ? c.out_ld : d->cout);
     return with_dtype16(d->dtype, [&](auto dt) {
         if (d->cout == 256 && a.prows > kPieceRows * g.maxp) return set_error(AF_ERR_ARG, "conv311g: %d patch rows", a.prows);
-        if (d->cout == 256) return launch133g<dt, 4, 2, false, 7, 5, true>(a, g, stream);
-        return launch133g<dt, 2, 4, false, 7, 9, true>(a, g, stream);
+        if (d->cout == 256) return launch133g<dt, 4, 2, false, 7, 5, true>(a, g, c.stream);
+        return launch133g<dt, 2, 4, false, 7, 9, true>(a, g, c.stream);
     });
+}
+const ConvPath& conv311g_path() {
+    static const ConvPath path = {VAR_C311G, c311g_applies, c311g_work, c311g_run, true};
+    return path;
 }
 
 // b (1x3x3) + c (1x1x1, + residual, + ReLU) of a bottleneck as one launch: true iff `db` takes the frame-resident path and
 // `dc` is a plain 1x1x1 convolution over db's output whose channel count is a multiple of db's
 bool conv133g_fused_applies(const af_conv_desc* db, const af_conv_desc* dc, int out_ld) {
-    if (!db || !dc || !conv133g_applies(db, nullptr, 0) || db->kt != 1 || db->cout == 64) return false;
-    if (dc->dtype != db->dtype || dc->tpool || dc->kt != 1 || dc->kh != 1 || dc->kw != 1) return false;
-    if (dc->st != 1 || dc->sh != 1 || dc->sw != 1 || dc->pt || dc->ph || dc->pw) return false;
+    if (!db || !dc || !geom133g(db).ok || db->kt != 1 || db->cout == 64) return false;
+    if (dc->dtype != db->dtype || dc->tpool || !pointwise(dc)) return false;
     if (dc->n != db->n || dc->t != db->to || dc->h != db->ho || dc->w != db->wo || dc->cin != db->cout) return false;
     if (dc->cout % db->cout != 0) return false;
     return out_ld == 0 || (out_ld >= dc->cout && out_ld % 8 == 0);
@@ -706,17 +699,21 @@ int conv133g_fused_run(const af_conv_desc* db, const void* in, const void* wb, c
     });
 }
 
-int conv133g_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
-                 void* out, int out_ld, hipStream_t stream) {
+static int c133g_run(const ConvCall& c) {
+    const af_conv_desc* d = c.d;
     const Geom133g g = geom133g(d);
     C133GArgs a;
-    fill133g(a, g, d, in, w_packed, scale, shift, out, out_ld ? out_ld : d->cout);
+    fill133g(a, g, d, c.in, c.w, c.scale, c.shift, c.out, c.out_ld ? c.out_ld : d->cout);
     return with_dtype16(d->dtype, [&](auto dt) {
-        if (d->cout == 256) return launch133g<dt, 4, 2, false, 7, 5>(a, g, stream);
-        if (d->cout == 64) return launch133g<dt, 1, 8, false, 4, 9>(a, g, stream);
-        if (g.maxp == 8) return launch133g<dt, 2, 4, false, 7, 8>(a, g, stream);
-        return launch133g<dt, 2, 4, false, 7, 9>(a, g, stream);
+        if (d->cout == 256) return launch133g<dt, 4, 2, false, 7, 5>(a, g, c.stream);
+        if (d->cout == 64) return launch133g<dt, 1, 8, false, 4, 9>(a, g, c.stream);
+        if (g.maxp == 8) return launch133g<dt, 2, 4, false, 7, 8>(a, g, c.stream);
+        return launch133g<dt, 2, 4, false, 7, 9>(a, g, c.stream);
     });
+}
+const ConvPath& conv133g_path() {
+    static const ConvPath path = {VAR_C133G, c133g_applies, c133g_work, c133g_run, true};
+    return path;
 }
 
 }  // namespace af

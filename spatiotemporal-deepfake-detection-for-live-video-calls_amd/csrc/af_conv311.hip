@@ -15,7 +15,7 @@
 // workgroup is persistent: the stage stream runs on across tile boundaries, so the first slab of the next tile
 // is in flight while the epilogue of this one (BN + ReLU, transposed through a per-wave patch in the output type,
 // 16-byte row stores) runs.  8 waves, each 64 channels x 32 rows: BN = 64 -> 256-row tiles, BN = 128 -> 128-row tiles.
-#include "af_common.h"
+#include "af_conv_paths.h"
 
 namespace af {
 
@@ -169,14 +169,11 @@ __global__ __launch_bounds__(512, 2) void conv311_kernel(const C311Args a) {
     }
 }
 
+// dynamic LDS of conv311_kernel<DT, BN> on tiles of P pixels
 template <int DT, int BN>
-static int launch311(const C311Args& a, int blocks, hipStream_t stream) {
+static int lds311(int P) {
     constexpr int BM = 256 / (BN / 64), EPC = Elem<DT>::EPC;
-    const int lds = 2 * (3 * BN + BM + 2 * a.P) * 128 + 8 * 16 * (64 + EPC) * (16 / EPC);
-    AF_SET_MAX_LDS((&conv311_kernel<DT, BN>), kLdsBudget, "conv311");
-    hipLaunchKernelGGL((conv311_kernel<DT, BN>), dim3(blocks), dim3(512), lds, stream, a);
-    AF_CHECK_LAUNCH("conv311_kernel");
-    return AF_OK;
+    return 2 * (3 * BN + BM + 2 * P) * 128 + 8 * 16 * (64 + EPC) * (16 / EPC);
 }
 
 // How a layer runs on the time-tiled path: tiles of all T frames x P pixels (ok == false: it does not take the path)
@@ -184,8 +181,7 @@ struct Geom311 { bool ok; int P, chunks, tiles, kpt; };
 static Geom311 geom311(const af_conv_desc* d) {
     Geom311 g = {};
     if (d->tpool) return g;
-    if (d->kt != 3 || d->kh != 1 || d->kw != 1 || d->st != 1 || d->sh != 1 || d->sw != 1) return g;
-    if (d->pt != 1 || d->ph != 0 || d->pw != 0) return g;
+    if (!temporal3(d)) return g;
     const int bke = d->dtype == AF_F32 ? 32 : 64;
     if (d->cin % bke != 0) return g;
     int bm = 0;
@@ -199,32 +195,32 @@ static Geom311 geom311(const af_conv_desc* d) {
     return g;
 }
 
-// persistent grid: one workgroup per CU, tile blockIdx.x, + gridDim.x, ...
-static int grid311(int tiles) {
-    const int cus = device_cus();
-    return tiles < cus ? tiles : cus;
-}
-void conv311_work(const af_conv_desc* d, long long* units, int* workgroups) {
-    const Geom311 g = geom311(d);
-    *units = g.tiles; *workgroups = grid311(g.tiles);
+// true iff this layer takes the time-tiled path
+static bool c311_applies(const ConvCall& c) { return !c.d2 && !c.residual && geom311(c.d).ok; }
+
+// persistent grid: tile blockIdx.x, + gridDim.x, ...
+static void c311_work(const ConvCall& c, long long* units, int* workgroups) {
+    const Geom311 g = geom311(c.d);
+    *units = g.tiles; *workgroups = persistent_grid(g.tiles);
 }
 
-// true iff this layer takes the time-tiled path (also used by af_conv_variant)
-bool conv311_applies(const af_conv_desc* d, const void* residual, int out_ld) {
-    return !residual && geom311(d).ok;
-}
-
-int conv311_run(const af_conv_desc* d, const void* in, const void* w_packed, const float* scale, const float* shift,
-                void* out, int out_ld, hipStream_t stream) {
+static int c311_run(const ConvCall& c) {
+    const af_conv_desc* d = c.d;
     C311Args a;
-    a.in = (const char*)in; a.w = (const char*)w_packed; a.scale = scale; a.shift = shift; a.out = (char*)out;
+    a.in = (const char*)c.in; a.w = (const char*)c.w; a.scale = c.scale; a.shift = c.shift; a.out = (char*)c.out;
     const Geom311 g = geom311(d);
     a.T = d->t; a.HW = d->h * d->w; a.Cin = d->cin; a.kpt = g.kpt;
     a.P = g.P; a.chunks = g.chunks; a.tiles = g.tiles;
-    a.relu = d->relu; a.out_ld = out_ld;
-    const int blocks = grid311(a.tiles);
-    if (d->cout == 128) return with_dtype16(d->dtype, [&](auto dt) { return launch311<dt, 128>(a, blocks, stream); });
-    return with_dtype(d->dtype, [&](auto dt) { return launch311<dt, 64>(a, blocks, stream); });
+    a.relu = d->relu; a.out_ld = c.out_ld;
+    const int blocks = persistent_grid(a.tiles);
+    if (d->cout == 128)
+        return with_dtype16(d->dtype, [&](auto dt) { return launch_lds<&conv311_kernel<dt, 128>>("conv311", blocks, lds311<dt, 128>(a.P), c.stream, a); });
+    return with_dtype(d->dtype, [&](auto dt) { return launch_lds<&conv311_kernel<dt, 64>>("conv311", blocks, lds311<dt, 64>(a.P), c.stream, a); });
+}
+
+const ConvPath& conv311_path() {
+    static const ConvPath path = {VAR_C311, c311_applies, c311_work, c311_run, true};
+    return path;
 }
 
 }  // namespace af

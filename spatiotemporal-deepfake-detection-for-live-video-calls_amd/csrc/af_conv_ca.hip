@@ -15,7 +15,7 @@
 // residual slab fetched TWO stages ahead (Little's law: one 56-KB stage in flight per CU gave 4.1 TB/s), the c weights and
 // the b fragments (K = 64: four 16-byte fragments per lane and tile) go global -> registers a stage / a tile ahead; BN
 // parameters sit in LDS (a plain global load between the DMA issue and its use would make hipcc wait for the DMA in flight).
-#include "af_common.h"
+#include "af_conv_paths.h"
 
 namespace af {
 
@@ -399,16 +399,6 @@ static long long conv_ca_lds_bytes(bool dual, int P, int C, bool cwl = false) {
     return 2LL * 3 * 64 * 128 + (dual ? (256LL + 2 * P) * 128 + 2LL * C * 128 : (3LL * (256 + P) + P) * 128 + (cwl ? 64 * 128 : 0)) + (2LL * C + 128) * 4;
 }
 
-template <int DT, bool DUAL, bool CWL>
-static int launch_ca(const CAArgs& a, int blocks, hipStream_t stream) {
-    const int lds = (int)conv_ca_lds_bytes(DUAL, a.P, a.C, CWL);
-    if (lds > kLdsBudget) return set_error(AF_ERR_ARG, "conv_ca: %d bytes of LDS needed", lds);
-    AF_SET_MAX_LDS((&conv_ca_kernel<DT, DUAL, CWL>), kLdsBudget, "conv_ca");
-    hipLaunchKernelGGL((conv_ca_kernel<DT, DUAL, CWL>), dim3(blocks), dim3(512), lds, stream, a);
-    AF_CHECK_LAUNCH("conv_ca_kernel");
-    return AF_OK;
-}
-
 // How the pair runs: tiles of all T frames x P pixels (ok == false: not on this path).  `dual`: with the projection shortcut
 struct GeomCA { bool ok; int P, chunks, tiles; bool cwl; };
 static GeomCA geom_ca(const af_conv_desc* dc, bool dual) {
@@ -418,14 +408,14 @@ static GeomCA geom_ca(const af_conv_desc* dc, bool dual) {
     if ((long long)dc->t * hw * dc->cout * 2 >= (1LL << 31)) return g;     // 32-bit offsets inside a clip
     const int p = 256 / dc->t;
     // the launch must fit LDS (wide trunks: the plain form with T = 16 and C = 1024, the projection form with C > 256 do not):
-    // such a pair keeps its two launches instead of failing in launch_ca
+    // such a pair keeps its two launches instead of failing at the launch
     if (conv_ca_lds_bytes(dual, p, dc->cout) > kLdsBudget) return g;
     // whole tiles only: the kernel's counted s_waitcnt vmcnt assume that every wave issues every store of an iteration; a
     // ragged last chunk could mask ALL lanes of a wave's store, hipcc would branch around it and the count would be off
     if (hw % p != 0) return g;
     const long long tiles = (long long)dc->n * (hw / p);
     // persistent stream: pays with several tiles per workgroup (small batches keep the two launches)
-    if (tiles < 4LL * device_cus() || tiles >= (1LL << 31)) return g;
+    if (!fills_chip(tiles) || tiles >= (1LL << 31)) return g;
     g.ok = true; g.P = p; g.chunks = (int)(hw / p); g.tiles = (int)tiles;
     // the stage's c weights as an LDS image where its 8 KB fit (T = 32 with a 256-channel trunk)
     g.cwl = !dual && conv_ca_lds_bytes(false, p, dc->cout, true) <= kLdsBudget;
@@ -437,22 +427,16 @@ static GeomCA geom_ca(const af_conv_desc* dc, bool dual) {
 bool conv_ca_applies(const af_conv_desc* dc, const af_conv_desc* d1, const af_conv_desc* da) {
     if (!dc || !da) return false;
     if (d1) {
-        if (d1->dtype != dc->dtype || d1->tpool || d1->kt != 1 || d1->kh != 1 || d1->kw != 1 || d1->st != 1 || d1->sh != 1 || d1->sw != 1) return false;
-        if (d1->pt || d1->ph || d1->pw || d1->cin != 64 || d1->cout != dc->cout) return false;
-        if (d1->n != dc->n || d1->t != dc->t || d1->h != dc->h || d1->w != dc->w) return false;
+        if (d1->dtype != dc->dtype || d1->tpool || !pointwise(d1)) return false;
+        if (d1->cin != 64 || d1->cout != dc->cout) return false;
+        if (!same_input(d1, dc)) return false;
     }
     if (!dc || !da || dc->dtype == AF_F32 || da->dtype != dc->dtype || dc->tpool || da->tpool) return false;
-    if (dc->kt != 1 || dc->kh != 1 || dc->kw != 1 || dc->st != 1 || dc->sh != 1 || dc->sw != 1 || dc->pt || dc->ph || dc->pw) return false;
-    if (da->kt != 3 || da->kh != 1 || da->kw != 1 || da->st != 1 || da->sh != 1 || da->sw != 1 || da->pt != 1 || da->ph || da->pw) return false;
+    if (!pointwise(dc)) return false;
+    if (!temporal3(da)) return false;
     if (dc->cin != 64 || da->cout != 64 || dc->cout != da->cin || dc->cout % 64 != 0 || dc->cout > 1024 || !dc->relu || !da->relu) return false;
-    if (dc->n != da->n || dc->t != da->t || dc->h != da->h || dc->w != da->w) return false;
+    if (!same_input(dc, da)) return false;
     return geom_ca(dc, d1 != nullptr).ok;
-}
-
-// persistent grid: one workgroup per CU (at most one per tile), workgroup b walks tiles b, b + grid, ...
-static int grid_ca(const GeomCA& g) {
-    const int cus = device_cus();
-    return g.tiles < cus ? g.tiles : cus;
 }
 
 // af_conv_ca_work_units: how conv_ca_run cuts the pair and which instantiation it launches (false: the pair is not fused)
@@ -460,7 +444,7 @@ bool conv_ca_work(const af_conv_desc* dc, const af_conv_desc* d1, const af_conv_
                   int* pixels) {
     if (!conv_ca_applies(dc, d1, da)) return false;
     const GeomCA g = geom_ca(dc, d1 != nullptr);
-    *tiles = g.tiles; *workgroups = grid_ca(g); *pixels = g.P;
+    *tiles = g.tiles; *workgroups = persistent_grid(g.tiles); *pixels = g.P;
     *form = d1 ? AF_CA_PROJECTION : g.cwl ? AF_CA_PLAIN_CWL : AF_CA_PLAIN;
     return true;
 }
@@ -476,11 +460,10 @@ int conv_ca_run(const af_conv_desc* dc, const void* inb, const void* wc, const v
     const GeomCA g = geom_ca(dc, in1 != nullptr);
     a.P = g.P; a.chunks = g.chunks; a.tiles = g.tiles;
     fill_dbg(a, "AF_CA_DBG");
-    const int blocks = grid_ca(g);
-    if (in1) return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, true, false>(a, blocks, stream); });
-    if (g.cwl)
-        return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, false, true>(a, blocks, stream); });
-    return with_dtype16(dc->dtype, [&](auto dt) { return launch_ca<dt, false, false>(a, blocks, stream); });
+    const int blocks = persistent_grid(g.tiles), lds = (int)conv_ca_lds_bytes(in1 != nullptr, a.P, a.C, g.cwl);
+    if (in1) return with_dtype16(dc->dtype, [&](auto dt) { return launch_lds<&conv_ca_kernel<dt, true, false>>("conv_ca", blocks, lds, stream, a); });
+    if (g.cwl) return with_dtype16(dc->dtype, [&](auto dt) { return launch_lds<&conv_ca_kernel<dt, false, true>>("conv_ca", blocks, lds, stream, a); });
+    return with_dtype16(dc->dtype, [&](auto dt) { return launch_lds<&conv_ca_kernel<dt, false, false>>("conv_ca", blocks, lds, stream, a); });
 }
 
 }  // namespace af

@@ -26,7 +26,7 @@
 // at conv_ca's rate); weight or residual DMA lanes out of range -0.02 / -0.03 ms (not ingest-bound).  A stage here has 50 KB
 // of HBM traffic against conv_ca's 80 KB but more instructions (SQ counters: 523 vector + 263 scalar per wave and stage against
 // 356 + 206) and five barriers: the stage is bound by its own critical path, not by HBM.
-#include "af_common.h"
+#include "af_conv_paths.h"
 
 namespace af {
 
@@ -341,16 +341,6 @@ __global__ __launch_bounds__(512) void conv_cpa_kernel(const CPAArgs a) {
     }
 }
 
-template <int DT>
-static int launch_cpa(const CPAArgs& a, int blocks, hipStream_t stream) {
-    const int lds = (int)conv_cpa_lds_bytes(a.C);
-    if (lds > kLdsBudget) return set_error(AF_ERR_ARG, "conv_cpa: %d bytes of LDS needed", lds);
-    AF_SET_MAX_LDS((&conv_cpa_kernel<DT>), kLdsBudget, "conv_cpa");
-    hipLaunchKernelGGL((conv_cpa_kernel<DT>), dim3(blocks), dim3(512), lds, stream, a);
-    AF_CHECK_LAUNCH("conv_cpa_kernel");
-    return AF_OK;
-}
-
 // How the pair runs: tiles of 2 rows x 4 columns of a clip, all frames (ok == false: not on this path)
 struct GeomCPA { bool ok; int wq, per_clip, tiles; };
 static GeomCPA geom_cpa(const af_conv_desc* dc) {
@@ -359,39 +349,33 @@ static GeomCPA geom_cpa(const af_conv_desc* dc) {
     if ((long long)dc->t * dc->h * dc->w * dc->cout * 2 >= (1LL << 31)) return g;     // 32-bit offsets inside a clip
     if (conv_cpa_lds_bytes(dc->cout) > kLdsBudget) return g;
     const long long tiles = (long long)dc->n * (dc->h / 2) * (dc->w / 4);
-    if (tiles < 4LL * device_cus() || tiles >= (1LL << 31)) return g;   // persistent stream: several tiles per workgroup
+    if (!fills_chip(tiles) || tiles >= (1LL << 31)) return g;   // persistent stream: several tiles per workgroup
     g.ok = true; g.wq = dc->w / 4; g.per_clip = (dc->h / 2) * g.wq; g.tiles = (int)tiles;
     return g;
 }
 
 // dc: the 1x1x1 `c` conv (64 -> C, residual + ReLU) with the temporal pool behind it (tpool = 1);
 // da: the 3x1x1 conv (C -> 128) over the pooled tensor; x_sub: 1 = store the whole pooled trunk, 2 = its even (h, w) positions
-bool conv_cpa_applies(const af_conv_desc* dc, const af_conv_desc* da, int x_sub) {
+static bool conv_cpa_applies(const af_conv_desc* dc, const af_conv_desc* da, int x_sub) {
     if (!dc || !da || (x_sub != 1 && x_sub != 2)) return false;
     if (dc->dtype == AF_F32 || da->dtype != dc->dtype || dc->tpool != 1 || da->tpool) return false;
-    if (dc->kt != 1 || dc->kh != 1 || dc->kw != 1 || dc->st != 1 || dc->sh != 1 || dc->sw != 1 || dc->pt || dc->ph || dc->pw) return false;
-    if (da->kt != 3 || da->kh != 1 || da->kw != 1 || da->st != 1 || da->sh != 1 || da->sw != 1 || da->pt != 1 || da->ph || da->pw) return false;
+    if (!pointwise(dc)) return false;
+    if (!temporal3(da)) return false;
     if (dc->cin != 64 || da->cout != 128 || dc->cout != da->cin || dc->cout % 64 != 0 || !dc->relu || !da->relu) return false;
     if (dc->t != 32 || da->t != 16 || dc->n != da->n || dc->h != da->h || dc->w != da->w) return false;
-    if (dc->to != dc->t || dc->ho != dc->h || dc->wo != dc->w || da->to != da->t || da->ho != da->h || da->wo != da->w) return false;
+    if (!keeps_size(dc) || !keeps_size(da)) return false;
     return geom_cpa(dc).ok;
 }
 
-// persistent grid: one workgroup per CU (at most one per tile), workgroup b walks tiles b, b + grid, ...
-static int grid_cpa(const GeomCPA& g) {
-    const int cus = device_cus();
-    return g.tiles < cus ? g.tiles : cus;
-}
-
 // af_conv_cpa_work_units: how conv_cpa_run cuts the pair (false: the pair is not fused)
-bool conv_cpa_work(const af_conv_desc* dc, const af_conv_desc* da, int x_sub, long long* tiles, int* workgroups) {
+static bool conv_cpa_work(const af_conv_desc* dc, const af_conv_desc* da, int x_sub, long long* tiles, int* workgroups) {
     if (!conv_cpa_applies(dc, da, x_sub)) return false;
     const GeomCPA g = geom_cpa(dc);
-    *tiles = g.tiles; *workgroups = grid_cpa(g);
+    *tiles = g.tiles; *workgroups = persistent_grid(g.tiles);
     return true;
 }
 
-int conv_cpa_run(const af_conv_desc* dc, const void* inb, const void* wc, const float* scale_c, const float* shift_c,
+static int conv_cpa_run(const af_conv_desc* dc, const void* inb, const void* wc, const float* scale_c, const float* shift_c,
                  const void* residual, void* outx, int x_sub, const af_conv_desc* da, const void* wa, const float* scale_a,
                  const float* shift_a, void* outa, hipStream_t stream) {
     CPAArgs a;
@@ -401,8 +385,9 @@ int conv_cpa_run(const af_conv_desc* dc, const void* inb, const void* wc, const 
     const GeomCPA g = geom_cpa(dc);
     a.wq = g.wq; a.per_clip = g.per_clip; a.tiles = g.tiles;
     a.sub = x_sub == 2;
-    const int blocks = grid_cpa(g);
-    return with_dtype16(dc->dtype, [&](auto dt) { return launch_cpa<dt>(a, blocks, stream); });
+    return with_dtype16(dc->dtype, [&](auto dt) {
+        return launch_lds<&conv_cpa_kernel<dt>>("conv_cpa", persistent_grid(g.tiles), (int)conv_cpa_lds_bytes(a.C), stream, a);
+    });
 }
 
 }  // namespace af
@@ -423,10 +408,8 @@ extern "C" int af_conv3d_cpa_bn_act(const af_conv_desc* dc, const void* in_b, co
                                     const float* shift_c, const void* residual, void* out_x, int x_sub, const af_conv_desc* da,
                                     const void* wa_packed, const float* scale_a, const float* shift_a, void* out_a, void* stream) {
     using namespace af;
-    AF_REQUIRE(dc && da && in_b && wc_packed && scale_c && shift_c && residual && out_x && wa_packed && scale_a && shift_a && out_a,
-               "conv_cpa: null argument");
-    AF_REQUIRE(aligned16(in_b) && aligned16(wc_packed) && aligned16(scale_c) && aligned16(shift_c) && aligned16(residual) &&
-                   aligned16(out_x) && aligned16(wa_packed) && aligned16(scale_a) && aligned16(shift_a) && aligned16(out_a),
+    AF_REQUIRE(none_null(dc, da, in_b, wc_packed, scale_c, shift_c, residual, out_x, wa_packed, scale_a, shift_a, out_a), "conv_cpa: null argument");
+    AF_REQUIRE(all_aligned16(in_b, wc_packed, scale_c, shift_c, residual, out_x, wa_packed, scale_a, shift_a, out_a),
                "conv_cpa: buffers must be 16-byte aligned");
     AF_REQUIRE(conv_cpa_applies(dc, da, x_sub),
                "conv_cpa: this (1x1x1 c + temporal pool, 3x1x1 a) pair does not take the fused path (ask af_conv_cpa_fusable first)");

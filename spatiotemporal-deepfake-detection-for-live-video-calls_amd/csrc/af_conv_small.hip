@@ -12,7 +12,7 @@
 //     generic kernel's packed layout ([cout_pad64][tap][cin_pad64]: no second packer);
 //   * a wave owns 64 positions (4 MFMA tiles) per step, all their gathers in flight together; the epilogue applies
 //     scale / shift (+ residual) (+ ReLU) per lane - 4 consecutive channels - and stores 8 bytes.
-#include "af_common.h"
+#include "af_conv_paths.h"
 
 namespace af {
 
@@ -136,8 +136,9 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallArgs a) {
     }
 }
 
-// true iff this layer takes the narrow-layer path (also used by af_conv_variant)
-bool conv_small_applies(const af_conv_desc* d, const af_conv_desc* d2, const void* residual, int out_ld) {
+// true iff this layer takes the narrow-layer path
+static bool small_applies(const ConvCall& c) {
+    const af_conv_desc *d = c.d, *d2 = c.d2;
     if (d->dtype == AF_F32 || d->tpool) return false;
     // (measured: at 32 output channels - the Fast pathway's `c` convs - the generic 64-wide tile with its 16-byte row
     // stores is faster than this kernel's 8-byte per-lane stores)
@@ -154,12 +155,11 @@ bool conv_small_applies(const af_conv_desc* d, const af_conv_desc* d2, const voi
     return true;
 }
 
-int conv_small_run(const af_conv_desc* d, const void* in, const void* w_packed, const af_conv_desc* d2, const void* in2,
-                   const void* w2_packed, const float* scale, const float* shift, const void* residual, void* out, int out_ld,
-                   hipStream_t stream) {
+static int small_run(const ConvCall& c) {
+    const af_conv_desc *d = c.d, *d2 = c.d2;
     SmallArgs a;
-    a.in = (const char*)in; a.w = (const char*)w_packed; a.in2 = (const char*)in2; a.w2 = (const char*)w2_packed;
-    a.scale = scale; a.shift = shift; a.res = (const char*)residual; a.out = (char*)out;
+    a.in = (const char*)c.in; a.w = (const char*)c.w; a.in2 = (const char*)c.in2; a.w2 = (const char*)c.w2;
+    a.scale = c.scale; a.shift = c.shift; a.res = (const char*)c.residual; a.out = (char*)c.out;
     a.T = d->t; a.H = d->h; a.W = d->w; a.Cin = d->cin; a.kt = d->kt; a.kh = d->kh; a.kw = d->kw;
     a.st = d->st; a.sh = d->sh; a.sw = d->sw; a.pt = d->pt; a.ph = d->ph; a.pw = d->pw;
     a.To = d->to; a.Ho = d->ho; a.Wo = d->wo; a.Cout = d->cout;
@@ -171,14 +171,19 @@ int conv_small_run(const af_conv_desc* d, const void* in, const void* w_packed, 
         a.T2 = d2->t; a.H2 = d2->h; a.W2 = d2->w; a.Cin2 = d2->cin; a.st2 = d2->st; a.sh2 = d2->sh; a.sw2 = d2->sw;
         a.Cin2P = (d2->cin + 63) / 64 * 64; a.nch2 = d2->cin / 8;
     }
-    a.relu = d->relu; a.out_ld = out_ld;
+    a.relu = d->relu; a.out_ld = c.out_ld;
     a.M = (long long)d->n * d->to * d->ho * d->wo;
     long long blocks = (a.M + 255) / 256;                       // one 64-position step per wave, then grid-stride
     if (blocks > 256 * 32) blocks = 256 * 32;
-    if (d->dtype == AF_BF16) hipLaunchKernelGGL((conv_small_kernel<AF_BF16, 1>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((conv_small_kernel<AF_F16, 1>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    with_dtype16(d->dtype, [&](auto dt) { hipLaunchKernelGGL((conv_small_kernel<dt, 1>), dim3((unsigned)blocks), dim3(256), 0, c.stream, a); });
     AF_CHECK_LAUNCH("conv_small_kernel");
     return AF_OK;
+}
+
+// (no LDS and no persistent grid: not cut into units; it takes a second segment and a residual)
+const ConvPath& conv_small_path() {
+    static const ConvPath path = {VAR_SMALL, small_applies, nullptr, small_run, false};
+    return path;
 }
 
 }  // namespace af

@@ -301,7 +301,7 @@ def test_rgb3_stem_sizes():
 
 
 def test_conv_ca_is_not_offered_where_its_lds_does_not_fit():
-    """af_conv_ca_fusable must agree with what launch_ca can run: the fused c -> a pair needs 2 a-weight slots + 3 image
+    """af_conv_ca_fusable must agree with what conv_ca_run can launch: the fused c -> a pair needs 2 a-weight slots + 3 image
     slots (plain) or 1 image slot + both c-side weight sets (projection); with a 512-wide trunk that is > 160 KB and the
     engine has to keep the two launches (it used to plan the fused op and fail every forward with AF_ERR_ARG)."""
     import ctypes as C
@@ -733,17 +733,32 @@ def test_plans_need_no_device_and_keep_their_launch_kinds(monkeypatch):
 def test_conv_paths_and_fusion_answers_equal_the_recorded_ones():
     """for every conv of the three networks (f32 / bf16 / f16, batch 1 / 8 / 16) af_conv_variant gives the recorded id, the id has the
     recorded name and af_conv_workspace_bytes the recorded size; the engine's bc / ca / cpa / abc fusion questions get the recorded
-    answers in the recorded order (fixture: tests/golden/conv_paths.json, written by tools/gen_conv_paths_golden.py)"""
+    answers in the recorded order (fixture: tests/golden/conv_paths.json, written by tools/gen_conv_paths_golden.py).  How the
+    launches are cut is recorded as well (tests/golden/conv_work_units.json, same tool): per conv what af_conv_work_units returns
+    - variant, units, workgroups, or its refusal in words -, per fusion answered yes what the pair's *_work_units function says."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("gen_conv_paths_golden", os.path.join(ROOT, "tools", "gen_conv_paths_golden.py"))
     gen = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(gen)
-    want, got = load_json("conv_paths.json"), gen.collect()
+    got_work = {}
+    want, got, want_work = load_json("conv_paths.json"), gen.collect(got_work), load_json("conv_work_units.json")
     assert sorted(got) == sorted(want) and len(want) == 3 * 3 * 3
+    assert sorted(got_work) == sorted(want) and sorted(want_work) == sorted(want)
     for key in sorted(want):
         assert got[key]["convs"] == want[key]["convs"], key
         assert got[key]["fusable"] == want[key]["fusable"], key
         assert len(want[key]["convs"]) >= 40 and len(want[key]["fusable"]) >= 10, key
+        assert got_work[key]["convs"] == want_work[key]["convs"], key
+        assert got_work[key]["fused"] == want_work[key]["fused"], key
+        assert len(want_work[key]["convs"]) == len(want[key]["convs"]), key
+        assert len(want_work[key]["fused"]) == sum(yes for _, yes in want[key]["fusable"]), key
+        # the recorded variant of a launch that is cut into units is the one af_conv_variant gave
+        assert all(w[0] == c[1] for w, c in zip(want_work[key]["convs"], want[key]["convs"]) if w[0] >= 0), key
+    assert sum(len(v["fused"]) for v in want_work.values()) >= 60
+    for key in sorted(want_work):                     # the narrow-layer path's refusal: SlowFast's Fast pathway at 16 bits, nowhere else
+        refused = [w for w in want_work[key]["convs"] if w[0] < 0]
+        assert bool(refused) == (key.startswith("slowfast_r50/") and "/f32/" not in key), key
+        assert all("not cut into units" in w[1] for w in refused), key
 
 
 def test_conv_matrix_covers_what_ships(monkeypatch):
