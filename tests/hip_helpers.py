@@ -91,16 +91,28 @@ def conv_bn_act(x_ndhwc, w_oidhw, scale, shift, stride, pad, relu, dtype, residu
     return out
 
 
-def conv_work_units(shape_ndhwc, cout, kernel, dtype, pad=(0, 0, 0), relu=True):
+def conv_work_units(shape_ndhwc, cout, kernel, dtype, pad=(0, 0, 0), relu=True, tpool=0, shape2_ndhwc=None, stride2=(1, 1, 1)):
     """(variant, work units, workgroups) of the af_conv3d_bn_act launch of this layer (stride 1) over an input of shape (N,T,H,W,C):
-    the library's own answer (af_conv_work_units), no tensor needed"""
+    the library's own answer (af_conv_work_units), no tensor needed.  ``tpool``: the fused pool of the descriptor;
+    ``shape2_ndhwc`` / ``stride2``: the second input of an af_conv3d_dual_bn_act launch (a 1x1x1 at that stride onto the same output)"""
     L = lib()
-    d = _desc(shape_ndhwc, cout, kernel, dtype, pad=pad, relu=relu)
+    d = _desc(shape_ndhwc, cout, kernel, dtype, pad=pad, relu=relu, tpool=tpool)
+    d2 = None if shape2_ndhwc is None else _desc(shape2_ndhwc, cout, (1, 1, 1), dtype, stride=stride2, dout=(d.to, d.ho, d.wo))
+    p2 = None if d2 is None else C.byref(d2)
     units, groups = C.c_int64(0), C.c_int(0)
-    v = L.lib.af_conv_work_units(C.byref(d), None, C.byref(units), C.byref(groups))
+    v = L.lib.af_conv_work_units(C.byref(d), p2, C.byref(units), C.byref(groups))
     L.check(min(v, 0), "conv_work_units")
-    assert v == L.lib.af_conv_variant(C.byref(d), None)
+    assert v == L.lib.af_conv_variant(C.byref(d), p2)
     return v, units.value, groups.value
+
+
+def conv_variant(shape_ndhwc, cout, kernel, dtype, stride=(1, 1, 1), pad=(0, 0, 0), shape2_ndhwc=None, stride2=(1, 1, 1)):
+    """the kernel the library picks for this layer (af_conv_variant), no tensor needed; also for the paths that are not cut into
+    units, which af_conv_work_units refuses"""
+    L = lib()
+    d = _desc(shape_ndhwc, cout, kernel, dtype, stride=stride, pad=pad)
+    d2 = None if shape2_ndhwc is None else _desc(shape2_ndhwc, cout, (1, 1, 1), dtype, stride=stride2, dout=(d.to, d.ho, d.wo))
+    return L.lib.af_conv_variant(C.byref(d), None if d2 is None else C.byref(d2))
 
 
 def compare(got, want, tol, what):

@@ -3,7 +3,8 @@ workgroup, against the oracle in fp64.  A workgroup of these kernels walks units
 its next unit under the epilogue of the current one (conv133g: `has_next` - the second patch buffer, a counted wait over the DMA
 that is in flight; conv311: the stage stream runs on across the tile boundary, into the other ring slot).  The layer tests
 (tests/test_hip_layers.py) run these kernels at no more units than a 256-CU device has workgroups, i.e. one unit each; the networks
-ship them at up to 49 rounds.
+ship them at up to 49 rounds.  The fifth persistent kernel, the 1x1x1 stream conv111 (variant 10), has its own file:
+tests/test_hip_conv111.py, over the tiles per workgroup and the residues of its unrolled tile loop that ship.
 
 Sizing at run time.  af_conv_work_units (the launchers' own geometry and grid expression) answers (units, workgroups) for a layer;
 a case names a ROUNDS CLASS and the frame / clip count is computed from W = workgroups on this device (and the units per frame or

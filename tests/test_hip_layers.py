@@ -269,6 +269,7 @@ CONV_CASES = [
 EXPECT_VARIANT = {"c64_1x3x3_56x56": {"f16": 4, "bf16": 4}, "c64_1x3x3_30x27": {"f16": 4, "bf16": 4},
                   "c64_1x3x3_56x56_many": {"f32": 1, "f16": 4, "bf16": 4}, "c64_1x3x3_54x50_many": {"f32": 1, "f16": 4, "bf16": 4},
                   "1x3x3": {"f16": 3, "bf16": 3},
+                  "sf_fast_8to8_3x1x1": {"f16": 9, "bf16": 9}, "sf_fast_16_1x3x3_s2": {"f16": 9, "bf16": 9},
                   "tile0_3x1x1_256to256": 0, "tile1_3x1x1_128to64": 1, "tile5_1x1x1_512to128": {"f32": 0, "f16": 5, "bf16": 5},
                   "tile256_1x3x3_res": 6, "tile256_ragged_m": 6, "tile224_1x3x3_res": 12, "tile224_ragged_m": 12,
                   "tile224_3x1x1_1024to256": {"f16": 12, "bf16": 12}, "tile224_1x1x1_1024to256_res": {"f16": 12, "bf16": 12}, "tile512_1x3x3_res": 7, "tile512_ragged_m": 7,

@@ -926,3 +926,74 @@ def test_fused_matrix_covers_what_ships(monkeypatch):
     assert len(shipped) >= 40 and all(kinds[k] for k in ("ca", "cpa", "abc", "bc")), (len(shipped), kinds)
     missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
     assert not missing, "%d shipped fused launches without a case:\n%s" % (len(missing), "\n".join(missing))
+
+
+def test_conv111_and_small_matrices_cover_what_ships(monkeypatch):
+    """every `conv` and `dual` launch of the three networks at batch 1..32 - default fusions, and the four fusion switches off -
+    that runs on the persistent 1x1x1 stream (conv111, variant 10) is a case of tests/test_hip_conv111.py, and every one on the
+    narrow-layer path (conv_small, variant 9) a case of tests/test_hip_conv_small.py; both files run their cases against fp64 on
+    the GPU.  conv111: key = (dtype, cin, cin2 or 0, cout, tpool, residual, out_ld != cout, my_tiles % NSLOT), one key per residue
+    that occurs among the launch's workgroups - (tiles, workgroups) come from af_conv_work_units for (d, d2), which answers for
+    256 CUs where there is no device.  conv_small: key = (dtype, cin, cout, kernel, stride, second segment, residual,
+    out_ld != cout, M > 2 097 152: the grid-stride loop runs twice)."""
+    import ctypes as C
+    import importlib.util
+    from af_mi355x import engine
+    from af_mi355x._lib import lib
+
+    def load(name):
+        spec_ = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
+        module = importlib.util.module_from_spec(spec_)
+        spec_.loader.exec_module(module)
+        return module
+
+    m111, msmall = load("test_hip_conv111"), load("test_hip_conv_small")
+    covered111 = set().union(*(m111.case_keys(c, dt) for c in m111.CASES for dt in m111.DT16 if c.form != "nonfinite"))
+    covered_small = {msmall.case_key(c, dt) for c in msmall.CASES for dt in msmall.DT16 if c.form != "nonfinite" and c.variant == 9}
+    monkeypatch.delenv("AF_FORCE_VAR", raising=False)
+    specs = {"i3d_r50": arch.i3d_r50_spec(), "slowfast_r50": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
+    rgb3 = {"i3d_r50": {specs["i3d_r50"].stem.conv}, "slowfast_r50": {specs["slowfast_r50"].stems[0].conv}, "ftcn_tt": set()}
+    shipped111, shipped_small = {}, {}
+    for fusions in (True, False):
+        for name in ("AF_FUSE_BC", "AF_FUSE_CA", "AF_FUSE_CPA", "AF_FUSE_ABC"):
+            if fusions:
+                monkeypatch.delenv(name, raising=False)
+            else:
+                monkeypatch.setenv(name, "0")
+        for net, spec in specs.items():
+            for dtype in ("f32", "bf16", "f16"):
+                for batch in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32):
+                    p = engine.plan_network(spec, dtype, batch, (spec.num_frames, spec.crop, spec.crop), rgb3[net] if dtype != "f32" else set())
+                    for e in p.entries:
+                        if e["kind"] not in ("conv", "dual"):
+                            continue
+                        cv, dual, tpool = e["cv"], e["kind"] == "dual", int(e.get("tpool") or 0)
+                        d = p.desc(cv, e["din"], e["dout"], tpool)
+                        d2 = C.byref(p.desc(e["cv2"], e["din2"], e["dout"])) if dual else None
+                        v = lib.af_conv_variant(C.byref(d), d2)
+                        if v not in (9, 10):
+                            continue
+                        assert dtype != "f32"
+                        cin2, res, ld = e["cv2"].cin if dual else 0, e.get("res") is not None, e.get("ld", cv.cout) != cv.cout
+                        where = "%s batch %d%s: %d%s -> %d %s" % (net, batch, "" if fusions else " unfused", cv.cin, " + %d" % cin2 if dual else "",
+                                                                   cv.cout, tuple(cv.kernel))
+                        if v == 9:
+                            m = d.n * d.to * d.ho * d.wo
+                            key = msmall.shipped_key(dtype, cv.cin, cv.cout, cv.kernel, cv.stride, dual, res, ld, m)
+                            shipped_small.setdefault(key, "%s stride %s, %d positions" % (where, tuple(cv.stride), m))
+                            continue
+                        tiles, groups = C.c_int64(0), C.c_int(0)
+                        assert lib.af_conv_work_units(C.byref(d), d2, C.byref(tiles), C.byref(groups)) == 10
+                        ncol = cv.cout // 256
+                        assert 0 < groups.value <= 256 and groups.value == 256 // ncol * ncol and tiles.value >= 4 * groups.value // ncol
+                        for residue in m111.residues_of(tiles.value, groups.value, cv.cin, cv.cout):
+                            key = m111.shipped_key(dtype, cv.cin, cin2, cv.cout, tpool, res, ld, residue)
+                            shipped111.setdefault(key, "%s, %d tiles on %d workgroups" % (where, tiles.value, groups.value))
+    # today 34 conv111 keys (17 per dtype: K = 128 with all four residues, and three of them with out_ld) and 24 conv_small keys (the
+    # eight shapes, four of them also beyond the launch cap)
+    assert len(shipped111) >= 34 and len(shipped_small) >= 24, (len(shipped111), len(shipped_small))
+    assert any(k[-1] for k in shipped_small) and {k[-1] for k in shipped111 if k[1] == 128} == {0, 1, 2, 3}
+    missing = sorted("%s (%s)" % (k, v) for k, v in shipped111.items() if k not in covered111)
+    assert not missing, "%d shipped conv111 launches without a case in test_hip_conv111.py:\n%s" % (len(missing), "\n".join(missing))
+    missing = sorted("%s (%s)" % (k, v) for k, v in shipped_small.items() if k not in covered_small)
+    assert not missing, "%d shipped conv_small launches without a case in test_hip_conv_small.py:\n%s" % (len(missing), "\n".join(missing))
