@@ -780,6 +780,68 @@ int af_capture_plan_u8(const af_capture_frame* frames, int n, const af_store_ref
                        int64_t* used_bytes);
 int af_capture_to_stores_u8(const void* table_dev, int n, void* stream);
 
+/* ---- the speaker tile of a captured call grid (added within ABI 6) ---------------------------------------------------------------
+ * LargestTilePicker's pixel work (test/capture_tile.py:55-95) on a frame that is resident on the device; the arithmetic is stated
+ * in csrc/af_tile.hip and equals tests/tile_ref.py byte for byte (a numpy restatement of OpenCV 4.x's plain C++ path, unpinned
+ * against cv2 itself, absent where this is built).
+ *
+ * af_tile_source: DEVICE pointer of the first byte of h rows of w packed 3-byte pixels, rows `pitch` bytes apart; bgr - non-zero:
+ * B, G, R, zero: R, G, B.  A frame of an af_store_ref is base + frame * frame_stride with the store's row_pitch and bgr.  Both sides
+ * are AF_TILE_MIN_SIDE .. AF_TILE_MAX_SIDE (the blur's reflected halo of 4 pixels needs 8).
+ * `workspace`: DEVICE memory of af_tile_workspace_bytes(h, w) bytes, 256-byte aligned, owned by the caller and by one call at a
+ * time.  Its first sizeof(af_tile_result) bytes are the call's answer, written on `stream`; the caller copies them back (the one
+ * read-back of a sequence).  Nothing waits on the host.
+ *
+ * af_tile_candidates_u8: grey, GaussianBlur 5 x 5, Canny(50, 150) with the hysteresis as a labelling of the candidates, dilate
+ * 3 x 3, the 8-connected components of the result with their boxes, the external ones (findContours RETR_EXTERNAL), _valid with
+ * `params`, and for each of the at most AF_TILE_MAX_BOXES survivors the exact sums S1, S2 of the blurred grey over the inset roi
+ * of n_px pixels, by ascending root (a component's smallest pixel index y * w + x): result.count, result.box[].  More survivors:
+ * result.overflow != 0.  The host decides n_px == 0 or n_px * S2 - S1^2 < 50 n_px^2 and sorts.
+ * af_tile_motion_u8: the unblurred grey into `grey` (h * w bytes), |grey - prev_grey| > 16, medianBlur 5, two 5 x 5 dilations,
+ * the components of the result and the union x1, y1, x2, y2 of the boxes with w * h >= area_min (union_count of them; none: w, h,
+ * 0, 0).  prev_grey null: only the grey is written (the reference's first frame).
+ * af_tile_components_u8: the stage both end in, on any h x w mask (non-zero = set; `g`, h * w bytes or null, feeds the sums;
+ * params null: no selection).  result.components counts the components.
+ * af_tile_outputs (null, or any member null): tight h x w copies of the stages for tests - g (motion: the grey), cls (0 none, 1
+ * candidate, 2 strong; motion: the threshold 0 / 1), edges (0 / 255; motion: the median 0 / 1), mask (0 / 255), labels (int32: the
+ * root, -1 background), boxes (int32 x 4 per pixel, minx, miny, maxx, maxy at a root, w, h, -1, -1 elsewhere), external (bytes, 1 at
+ * the root of an external component).
+ * Every device loop is bounded by the pixel count; a bound that is hit sets bits in result.error (1: a find, 2: a union) instead of
+ * spinning.  A caller treats error != 0 or overflow != 0 as a failure, never as an answer. */
+#define AF_TILE_MAX_BOXES 64
+#define AF_TILE_MIN_SIDE 8
+#define AF_TILE_MAX_SIDE 8192
+typedef struct af_tile_source {
+    const void* pixels;
+    int64_t pitch;
+    int32_t h, w;
+    int32_t bgr, reserved;
+} af_tile_source;
+typedef struct af_tile_params {                        /* LargestTilePicker._valid: ww >= min_w, hh >= min_h, ar_lo <= ww / hh <= ar_hi */
+    int32_t min_w, min_h;                              /* in fp64, ww * hh >= area_min (the host's 0.10 * W * H) */
+    double ar_lo, ar_hi, area_min;
+} af_tile_params;
+typedef struct af_tile_box {
+    int32_t root, x, y, w, h, n_px;
+    int64_t s1, s2;
+} af_tile_box;
+typedef struct af_tile_result {
+    int32_t error, count, overflow, components;
+    int32_t x1, y1, x2, y2;                            /* motion: the union */
+    int32_t union_count, reserved[3];
+    af_tile_box box[AF_TILE_MAX_BOXES];
+} af_tile_result;
+typedef struct af_tile_outputs {
+    void *g, *cls, *edges, *mask, *labels, *boxes, *external;
+} af_tile_outputs;
+int64_t af_tile_workspace_bytes(int h, int w);
+int af_tile_candidates_u8(const af_tile_source* src, const af_tile_params* params, void* workspace, int64_t workspace_bytes,
+                          const af_tile_outputs* out, void* stream);
+int af_tile_motion_u8(const af_tile_source* src, const void* prev_grey, void* grey, double area_min, void* workspace,
+                      int64_t workspace_bytes, const af_tile_outputs* out, void* stream);
+int af_tile_components_u8(const void* mask, int64_t pitch, int h, int w, const void* g, const af_tile_params* params, void* workspace,
+                          int64_t workspace_bytes, const af_tile_outputs* out, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,

@@ -18,6 +18,9 @@ def __getattr__(name):
     if name in ("YuvFrame", "CapturedFrame", "FrameResizer"):
         from . import frames
         return getattr(frames, name)
+    if name == "TilePicker":
+        from . import tile_picker
+        return tile_picker.TilePicker
     if name in ("DualVideoScorer", "DualTrack"):
         from . import dual_video
         return getattr(dual_video, name)

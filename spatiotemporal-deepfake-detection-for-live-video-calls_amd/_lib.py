@@ -143,6 +143,34 @@ class CaptureTap(C.Structure):
     _fields_ = [("idx", C.c_int32), ("weight", C.c_float)]
 
 
+class TileSource(C.Structure):
+    """af_tile_source: h rows of w packed 3-byte pixels on the device"""
+    _fields_ = [("pixels", C.c_void_p), ("pitch", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("bgr", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TileParams(C.Structure):
+    """af_tile_params: LargestTilePicker._valid's constants; area_min is the host's own 0.10 * W * H"""
+    _fields_ = [("min_w", C.c_int32), ("min_h", C.c_int32), ("ar_lo", C.c_double), ("ar_hi", C.c_double), ("area_min", C.c_double)]
+
+
+TILE_MAX_BOXES, TILE_MIN_SIDE, TILE_MAX_SIDE = 64, 8, 8192
+
+
+class TileBox(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("root", "x", "y", "w", "h", "n_px")] + [("s1", C.c_int64), ("s2", C.c_int64)]
+
+
+class TileResult(C.Structure):
+    """af_tile_result: the first bytes of the workspace after a call"""
+    _fields_ = [(n, C.c_int32) for n in ("error", "count", "overflow", "components", "x1", "y1", "x2", "y2", "union_count")] + [
+        ("reserved", C.c_int32 * 3), ("box", TileBox * TILE_MAX_BOXES)]
+
+
+class TileOutputs(C.Structure):
+    """af_tile_outputs: optional tight copies of the stages"""
+    _fields_ = [(n, C.c_void_p) for n in ("g", "cls", "edges", "mask", "labels", "boxes", "external")]
+
+
 class DualvTrack(C.Structure):
     """af_dualv_track: one face track's raw landmark and AU rows on the device"""
     _fields_ = [("lmk", C.c_void_p), ("au", C.c_void_p), ("lmk_pitch", C.c_int64), ("au_pitch", C.c_int32), ("n", C.c_int32)]
@@ -288,6 +316,12 @@ ABI = {
     "af_capture_table_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
     "af_capture_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "af_capture_to_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "af_tile_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "af_tile_candidates_u8": (C.c_int, [C.POINTER(TileSource), C.POINTER(TileParams), C.c_void_p, C.c_int64, C.POINTER(TileOutputs), C.c_void_p]),
+    "af_tile_motion_u8": (C.c_int, [C.POINTER(TileSource), C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.POINTER(TileOutputs),
+                                    C.c_void_p]),
+    "af_tile_components_u8": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(TileParams), C.c_void_p, C.c_int64,
+                                        C.POINTER(TileOutputs), C.c_void_p]),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6
