@@ -6,6 +6,7 @@ What this orchestrates is the reference's ``ResNet.forward`` / ``SlowFast.forwar
 pool -> s3 -> ... -> head, with every Conv3d+BatchNorm3d(+add)(+ReLU)(+pool) group collapsed into one kernel
 launch.  PyTorch is used only to own device memory and the stream.
 """
+import collections
 import ctypes as C
 import dataclasses
 import os
@@ -161,10 +162,6 @@ class PackedWeights:
                 self.shift_sum[c.conv].data_ptr())
 
 
-def _conv_desc(batch, code, cv: ConvSpec, din, dout, relu=True, tpool=0):
-    return _lib.conv_desc(batch, din, cv.cin, cv.cout, cv.kernel, cv.stride, cv.pad, relu, code, dout, tpool)
-
-
 # The plan's switches (A/B runs and tests): name -> on by default.  Read whenever a plan is built; "1" is on, anything else off.
 SWITCHES = {"AF_FUSE_BC": False, "AF_FUSE_CA": True, "AF_FUSE_CPA": False, "AF_FUSE_ABC": True, "AF_FUSE_TSTEM_POOL": True,
             "AF_SLOWFAST_STEM3": True}
@@ -174,187 +171,227 @@ def _read_switches():
     return {name: os.environ.get(name, "1" if on else "0") == "1" for name, on in SWITCHES.items()}
 
 
+# The convs of a fused launch by role, in the parameter order of the library entry point it goes to (a lone conv's role: "conv").
+_ROLES = {"dual": ("c", "branch1"), "ca": ("c", "branch1", "a_next"), "cpa": ("c", "a_next"), "abc": ("a", "b", "c", "branch1"),
+          "bc": ("b", "c")}
+# The fused kinds the library is asked about: kind -> (switch, its predicate over the launch's descriptors).
+#   bc   a bottleneck's b (1x3x3) and c (1x1x1 + residual) convs (af_conv3d_bc_bn_act).  OFF unless AF_FUSE_BC=1: measured slower
+#        than the two launches, whose MFMA-bound b and HBM-bound c overlap across workgroups
+#   ca   a block's c conv (+ residual or projection shortcut, + ReLU) and the NEXT block's a conv (af_conv3d_ca_bn_act)
+#   cpa  a stage's last c conv (+ residual + ReLU), the temporal max-pool behind the stage and the NEXT stage's first a conv
+#        (af_conv3d_cpa_bn_act; the predicate also takes x_sub).  OFF unless AF_FUSE_CPA=1
+#   abc  a whole block, a, b, c + identity or stride-1 projection shortcut + ReLU (af_block_abc_bn_act: SlowFast's Fast pathway)
+_QUESTIONS = {"bc": ("AF_FUSE_BC", lib.af_conv_bc_fusable), "ca": ("AF_FUSE_CA", lib.af_conv_ca_fusable),
+              "cpa": ("AF_FUSE_CPA", lib.af_conv_cpa_fusable), "abc": ("AF_FUSE_ABC", lib.af_block_abc_fusable)}
+
+
+@dataclasses.dataclass
+class Launch:
+    """One launch of a plan.  ``convs``: its ConvSpecs by role (_ROLES; None for a conv this launch does not have); ``descs``: their
+    af_conv_desc in the same order, built once, by the planner: the library's *_fusable predicate is asked with them, the op is
+    filled from them, tools and tests read them.  A lone conv's carries its own ReLU, the convs of a fused launch relu = 1."""
+    kind: str
+    convs: Dict[str, Optional[ConvSpec]] = dataclasses.field(default_factory=dict)
+    descs: tuple = ()
+    src: Optional[str] = None            # input
+    src2: Optional[str] = None           # what the projection shortcut reads (dual, ca)
+    res: Optional[str] = None            # residual
+    dst: Optional[str] = None            # output
+    dst_a: Optional[str] = None          # output of the a conv behind a c conv (ca, cpa)
+    ld: int = 0                          # row stride of the output, in channels
+    ch_off: int = 0                      # first channel written in those rows
+    x_sub: int = 0                       # cpa: 2 = the pooled trunk is stored at its even (h, w) only, else 1
+    pool: Optional[_lib.PoolDesc] = None # the pooling launches (and the token pool of tt_head)
+
+    @property
+    def tpool(self) -> int:              # of the conv that writes the output: 1 = the temporal max-pool rides in its epilogue, 2 = a 1x2x2
+        return self.descs[0].tpool if self.descs else 0
+
+    def refs(self):                      # ``descs`` as the library takes them
+        return [None if d is None else C.byref(d) for d in self.descs]
+
+    def macs(self) -> int:
+        return sum(cv.macs(d.t, d.h, d.w) for cv, d in zip(self.convs.values(), self.descs) if cv is not None)
+
+
+# What a block hands the next (a stage's last: the next stage's first): the launch of its c conv already ran that block's a conv;
+# it stored the trunk only where a stride-(1,2,2) projection shortcut reads it.
+_Handoff = collections.namedtuple("_Handoff", "a_done sub", defaults=(False, False))
+
+
 class _Plan:
-    """Accumulates plan entries (dicts) and the element count every named activation buffer must hold; the network planners add
-    what the engine needs besides: ``inputs`` [(stem-input buffer, dims, temporal stride)], ``rgb3`` (the single input feeds a
-    K-packed stem), ``rgb3_inputs`` (SlowFast: the inputs that do), ``head_dims`` and ``head_width``."""
+    """Accumulates ``launches`` and the element count every named activation buffer must hold (``sizes``), and keeps what the
+    library was ``asked``: (switch, answer, candidate Launch) per question, in order.  The network planners add what the engine
+    needs besides: ``inputs`` [(stem-input buffer, dims, temporal stride)], ``rgb3`` (the single input feeds a K-packed stem),
+    ``rgb3_inputs`` (SlowFast: the inputs that do), ``head_dims`` and ``head_width``."""
 
     def __init__(self, batch, dtype):
         self.batch, self.dtype, self.code = batch, dtype, _lib.DTYPE_CODES[dtype]
-        self.entries, self.sizes, self.switch = [], {}, _read_switches()
-        self.boundary = None                 # set by a stage whose last launch already ran the next stage's first a conv
+        self.launches, self.asked, self.sizes, self.switch = [], [], {}, _read_switches()
+        self.handoff = _Handoff()            # of the block planned last
         self.inputs, self.rgb3, self.rgb3_inputs, self.head_dims, self.head_width = [], False, set(), None, None
 
     def need(self, buf, dims, width):
         self.sizes[buf] = max(self.sizes.get(buf, 0), self.batch * dims[0] * dims[1] * dims[2] * width)
 
-    def add(self, **e):
-        self.entries.append(e)
+    def make(self, kind, convs, **where) -> Launch:
+        """A launch of ``kind`` over ``convs``: (role, ConvSpec or None, din, dout[, tpool]) each, in the order of _ROLES.  ``ld``
+        defaults to the channels of the conv that writes the output."""
+        assert tuple(c[0] for c in convs) == _ROLES.get(kind, ("conv",)), (kind, convs)
+        # lone: a, b, stems and laterals carry their own ReLU; c (final_bn) takes the block's add + ReLU; the projection shortcut
+        # has neither (resnet_helper.py:311-326, 438-444; video_model_builder.py:136-143)
+        descs = tuple(cv and _lib.conv_desc(self.batch, din, cv.cin, cv.cout, cv.kernel, cv.stride, cv.pad,
+                                            len(convs) > 1 or cv.relu or cv.final_bn, self.code, dout, *tpool)
+                      for _, cv, din, dout, *tpool in convs)
+        specs = {c[0]: c[1] for c in convs}
+        where.setdefault("ld", (specs.get("c") or specs.get("conv")).cout)
+        return Launch(kind, specs, descs, **where)
 
-    def desc(self, cv: ConvSpec, din, dout, tpool=0):
-        return _conv_desc(self.batch, self.code, cv, din, dout, True, tpool)
+    def conv(self, cv: ConvSpec, din, dout, src, dst, kind="conv", tpool=0, **where):
+        """a conv (or stem) launch of its own"""
+        self.launches.append(self.make(kind, [("conv", cv, din, dout, tpool)], src=src, dst=dst, **where))
 
-    def _fusable(self, switch, ask, convs, *more) -> bool:
-        """the shared body of the *_fusable questions: the switch, then the library's own predicate over the descriptors of
-        ``convs``: (ConvSpec, din, dout[, tpool]) each, or None for a conv the launch does not have"""
+    def pool(self, kind, p, ch, din, dout, src, **where):
+        """a pooling launch: ``p`` a PoolSpec, or the kernel alone (stride 1, no padding); ``ld`` goes into its descriptor"""
+        kernel, stride, pad = (p.kernel, p.stride, p.pad) if isinstance(p, PoolSpec) else (p, (1, 1, 1), (0, 0, 0))
+        desc = _lib.pool_desc(self.batch, din, ch, kernel, stride, pad, self.code, dout, where.pop("ld", 0))
+        self.launches.append(Launch(kind, src=src, pool=desc, **where))
+
+    def ask(self, cand: Launch) -> Optional[Launch]:
+        """The candidate, if its switch is on (else no question reaches the library) and the library runs its descriptors as one launch."""
+        switch, question = _QUESTIONS[cand.kind]
         if not self.switch[switch]:
-            return False
-        return bool(ask(*(None if c is None else C.byref(self.desc(*c)) for c in convs), *more))
+            return None
+        yes = bool(question(*cand.refs(), *((cand.x_sub,) if cand.kind == "cpa" else ())))
+        self.asked.append((switch, yes, cand))
+        return cand if yes else None
 
-    def bc_fusable(self, b: ConvSpec, c: ConvSpec, da, db, dc) -> bool:
-        """does the library run this bottleneck's b (1x3x3) and c (1x1x1 + residual) convs as one launch (af_conv3d_bc_bn_act)?
-        OFF unless AF_FUSE_BC=1: measured slower (B=16, bf16: s3 0.205 ms against 0.068 + 0.080 ms for the two launches, s4
-        0.134 against 0.056 + 0.070) - the b conv is MFMA-bound, the c conv with its residual an HBM stream, and inside one
-        workgroup the two phases run back to back on every CU at the same time instead of overlapping."""
-        return self._fusable("AF_FUSE_BC", lib.af_conv_bc_fusable, [(b, da, db), (c, db, dc)])
+    def stage(self, stage, d, cur, nxt, a_buf, b_buf, last_ld=None, tpool_last=False, next_stage=None):
+        """One pathway's ResStage.  ``last_ld``: row stride of the stage's final output (room for the lateral's channels);
+        ``next_stage`` (with ``tpool_last``): the stage behind the temporal pool, whose first a conv may ride in this stage's last launch.
+        Returns (dims, channels, buffer holding the output, the other trunk buffer, whether the temporal pool rode in the last launch)."""
+        c, tpooled = None, False
+        for bi, blk in enumerate(stage.blocks):
+            last = bi == len(stage.blocks) - 1
+            nxa = None if last else stage.blocks[bi + 1].a
+            ld = last_ld if (last and last_ld) else blk.c.cout
+            tpool_here = tpool_last and last
+            hand, self.handoff = self.handoff, _Handoff()
+            dout = None if (hand.a_done or tpool_here) else self._whole_block(blk, d, cur, nxt, ld)
+            if dout is None:
+                da = blk.a.out_dims(*d)
+                if not hand.a_done:
+                    self.conv(blk.a, d, da, cur, a_buf)
+                self.need(a_buf, da, blk.a.cout)
+                dout, c_src = self._b_side(blk, da, cur, nxt, a_buf, b_buf, ld, with_c=not tpool_here)
+                if c_src is not None:
+                    res = cur
+                    if blk.branch1 is not None and blk.branch1.pool_after_bn is not None:
+                        # pooled projection shortcut: conv + BN, pool, then it is the residual of the c conv
+                        _, res = self._conv_maxpool(blk.branch1, d, cur, "R1", "R0", "R1")
+                    dout, self.handoff, tpooled = self._c_side(blk, nxa, d, dout, c_src, res, cur, nxt, a_buf, ld, hand.sub, tpool_here,
+                                                               next_stage)
+            d, cur, nxt, c = dout, nxt, cur, blk.c.cout
+        return d, c, cur, nxt, tpooled
 
-    def ca_fusable(self, c: ConvSpec, a_next: ConvSpec, db, dc, branch1: ConvSpec = None, d_in=None) -> bool:
-        """does the library run this block's c conv (+ residual or projection shortcut, + ReLU) and the NEXT block's a conv as one
-        launch (af_conv3d_ca_bn_act)?  AF_FUSE_CA=0 switches it off (A/B runs)."""
-        return self._fusable("AF_FUSE_CA", lib.af_conv_ca_fusable,
-                             [(c, db, dc), branch1 and (branch1, d_in, dc), (a_next, dc, a_next.out_dims(*dc))])
-
-    def cpa_fusable(self, c: ConvSpec, a_next: ConvSpec, db, dc, x_sub) -> bool:
-        """does the library run the stage's last c conv (+ residual + ReLU), the temporal max-pool behind the stage and the NEXT
-        stage's first a conv as one launch (af_conv3d_cpa_bn_act)?  OFF unless AF_FUSE_CPA=1."""
-        dp = (dc[0] // 2,) + tuple(dc[1:])
-        return self._fusable("AF_FUSE_CPA", lib.af_conv_cpa_fusable, [(c, db, dc, 1), (a_next, dp, a_next.out_dims(*dp))], x_sub)
-
-    def _boundary_fusable(self, c: ConvSpec, next_stage, db, dc) -> int:
-        """0, or the x_sub of the fused stage-boundary launch: 2 when the next stage's block 0 reads the pooled trunk only through
-        a 1x1x1 projection shortcut of stride (1,2,2) (and its a conv, which runs inside the launch), else 1."""
-        nb = next_stage.blocks[0]
-        if nb.a.pool_after_bn is not None or dc[0] % 2:
-            return 0
-        b1 = nb.branch1
-        sub = 2 if (b1 is not None and b1.pool_after_bn is None and tuple(b1.kernel) == (1, 1, 1) and tuple(b1.stride) == (1, 2, 2)
-                    and tuple(b1.pad) == (0, 0, 0) and dc[1] % 2 == 0 and dc[2] % 2 == 0) else 1
-        if b1 is None:
-            return 0                       # an identity shortcut would need the whole trunk AND block 0's residual add: not this launch
-        return sub if self.cpa_fusable(c, nb.a, db, dc, sub) else 0
-
-    def abc_fusable(self, blk, d) -> bool:
-        """does the library run this whole block (a, b, c + identity or stride-1 projection shortcut + ReLU) as one launch
-        (af_block_abc_bn_act: the narrow blocks of SlowFast's Fast pathway)?  AF_FUSE_ABC=0 switches it off (A/B runs)."""
-        if any(cv is not None and cv.pool_after_bn is not None for cv in (blk.a, blk.b, blk.c, blk.branch1)):
-            return False
+    def _whole_block(self, blk, d, cur, nxt, ld):
+        """The whole block as one launch (narrow pathway): trunk in, trunk out, a and b stay on the CU.  Returns the output dims,
+        or None where the library does not run it so."""
         da = blk.a.out_dims(*d)
         db = blk.b.out_dims(*da)
         dc = blk.c.out_dims(*db)
-        if blk.branch1 is not None and blk.branch1.out_dims(*d) != dc:
-            return False
-        return self._fusable("AF_FUSE_ABC", lib.af_block_abc_fusable,
-                             [(blk.a, d, da), (blk.b, da, db), (blk.c, db, dc), blk.branch1 and (blk.branch1, d, dc)])
+        if (any(cv is not None and cv.pool_after_bn is not None for cv in (blk.a, blk.b, blk.c, blk.branch1))
+                or (blk.branch1 is not None and blk.branch1.out_dims(*d) != dc)):
+            return None
+        launch = self.ask(self.make("abc", [("a", blk.a, d, da), ("b", blk.b, da, db), ("c", blk.c, db, dc), ("branch1", blk.branch1, d, dc)],
+                                    src=cur, dst=nxt, ld=ld))
+        if launch is not None:
+            self.launches.append(launch); self.need(nxt, dc, ld)
+            return dc
 
-    def stage(self, stage, d, cur, nxt, a_buf, b_buf, last_ld=None, tpool_last=False, next_stage=None):
-        """One pathway's ResStage.  ``last_ld``: row stride of the stage's final output (room for the lateral's
-        channels); ``next_stage`` (with ``tpool_last``): the stage behind the temporal pool, whose first a conv may ride in this
-        stage's last launch.  Returns (dims, channels, buffer holding the output, the other trunk buffer)."""
-        c = None
-        nblk = len(stage.blocks)
-        # this block's a conv was run by the previous block's fused c -> a launch (or, block 0, by the previous STAGE's last one)
-        bnd, self.boundary = self.boundary, None
-        a_done = bnd is not None
-        sub_first = bool(bnd and bnd.get("sub"))
-        for bi, blk in enumerate(stage.blocks):
-            last = bi == nblk - 1
-            if not a_done and not (tpool_last and last) and self.abc_fusable(blk, d):
-                # the whole block in one launch (narrow pathway): trunk in, trunk out, a and b stay on the CU
-                ld = last_ld if (last and last_ld) else blk.c.cout
-                self.add(kind="abc", cv=blk.a, cv2=blk.b, cv3=blk.c, cv4=blk.branch1, din=d, dout=d, src=cur, dst=nxt, ld=ld)
-                self.need(nxt, d, ld)
-                cur, nxt = nxt, cur
-                c = blk.c.cout
-                continue
-            da = blk.a.out_dims(*d)
-            if not a_done:
-                self.add(kind="conv", cv=blk.a, din=d, dout=da, src=cur, dst=a_buf)
-            self.need(a_buf, da, blk.a.cout)
-            a_done = False
-            db = blk.b.out_dims(*da)
-            c_src, res_src = b_buf, cur
-            pb = blk.b.pool_after_bn
-            if pb is not None and _is_pool(pb, (1, 2, 2), (1, 2, 2), (0, 0, 0)) and db[1] % 2 == 0 and db[2] % 2 == 0:
-                # FTCN: conv -> BN -> MaxPool3d((1,2,2)) -> ReLU in one launch (max and ReLU commute): the conv's tile
-                # rows are ordered so that a 2x2 window is 4 adjacent rows and the epilogue stores their max
-                dbp = _pool_out(db, pb)
-                self.add(kind="conv", cv=blk.b, din=da, dout=db, src=a_buf, dst=b_buf, tpool=2); self.need(b_buf, dbp, blk.b.cout)
-                db = dbp
-            elif (pb is None and blk.branch1 is None and not (tpool_last and bi == nblk - 1) and
-                  self.bc_fusable(blk.b, blk.c, da, db, blk.c.out_dims(*db))):
-                # b + c + residual + ReLU in one launch: the b output of a frame stays in LDS (s3 / s4 at bench batch sizes)
-                dc = blk.c.out_dims(*db)
-                ld = last_ld if (bi == nblk - 1 and last_ld) else blk.c.cout
-                self.add(kind="bc", cv=blk.b, cv2=blk.c, din=da, dmid=db, dout=dc, src=a_buf, dst=nxt, res=cur, ld=ld)
-                self.need(nxt, dc, ld)
-                cur, nxt = nxt, cur
-                d, c = dc, blk.c.cout
-                continue
-            else:
-                self.add(kind="conv", cv=blk.b, din=da, dout=db, src=a_buf, dst=b_buf); self.need(b_buf, db, blk.b.cout)
-                if pb is not None:       # odd sizes / other pool shapes: the pool as its own launch into the free a buffer
-                    dbp = _pool_out(db, pb)
-                    self.add(kind="pool", pool=pb, ch=blk.b.cout, din=db, dout=dbp, src=b_buf, dst=a_buf)
-                    self.need(a_buf, dbp, blk.b.cout)
-                    db, c_src = dbp, a_buf
-            if blk.branch1 is not None and blk.branch1.pool_after_bn is not None:
-                # pooled projection shortcut: conv + BN, pool, then it is the residual of the c conv
-                p1 = blk.branch1.pool_after_bn
-                d1 = blk.branch1.out_dims(*d)
-                d1p = _pool_out(d1, p1)
-                if _is_pool(p1, (1, 2, 2), (1, 2, 2), (0, 0, 0)) and d1[1] % 2 == 0 and d1[2] % 2 == 0:
-                    self.add(kind="conv", cv=blk.branch1, din=d, dout=d1, src=cur, dst="R1", tpool=2)
-                else:
-                    self.add(kind="conv", cv=blk.branch1, din=d, dout=d1, src=cur, dst="R0"); self.need("R0", d1, blk.branch1.cout)
-                    self.add(kind="pool", pool=p1, ch=blk.branch1.cout, din=d1, dout=d1p, src="R0", dst="R1")
-                self.need("R1", d1p, blk.branch1.cout)
-                res_src = "R1"
+    def _b_side(self, blk, da, cur, nxt, a_buf, b_buf, ld, with_c):
+        """The b conv.  Returns (dims, buffer) of what the c conv reads; or, where b, c, the residual add and the ReLU went as one
+        launch (``with_c`` allows it), (the block's output dims, None)."""
+        if blk.b.pool_after_bn is not None:
+            return self._conv_maxpool(blk.b, da, a_buf, b_buf, b_buf, a_buf)       # the pool of its own goes into the free a buffer
+        db = blk.b.out_dims(*da)
+        if blk.branch1 is None and with_c:
+            # b + c + residual + ReLU in one launch: the b output of a frame stays in LDS (s3 / s4 at bench batch sizes)
             dc = blk.c.out_dims(*db)
-            ld = last_ld if (last and last_ld) else blk.c.cout
-            # the temporal max-pool after s2 rides in the epilogue of s2's last conv when it can
-            tp = tpool_last and last and blk.branch1 is None and dc[0] % 2 == 0
-            dstore = (dc[0] // 2,) + tuple(dc[1:]) if tp else dc
-            if blk.branch1 is not None and blk.branch1.pool_after_bn is None and bi == 0 and sub_first:
-                # the previous stage's last launch stored the trunk only where this stride-(1,2,2) shortcut reads it, packed:
-                # the same weights as a stride-1 convolution over that tensor
-                b1 = dataclasses.replace(blk.branch1, stride=(1, 1, 1))
-                dsub = (d[0], d[1] // 2, d[2] // 2)
-                assert b1.out_dims(*dsub) == dc
-                self.add(kind="dual", cv=blk.c, cv2=b1, din=db, din2=dsub, dout=dc, src=c_src, src2=cur, dst=nxt, ld=ld)
-            elif blk.branch1 is not None and blk.branch1.pool_after_bn is None:
-                # c conv + projection shortcut in one launch; no shortcut tensor
-                assert blk.branch1.out_dims(*d) == dc
-                if (not last and ld == blk.c.cout and stage.blocks[bi + 1].a.pool_after_bn is None
-                        and self.ca_fusable(blk.c, stage.blocks[bi + 1].a, db, dc, blk.branch1, d)):
-                    # ... and the next block's a conv behind them (s2): the trunk slab never comes back from HBM
-                    nxa = stage.blocks[bi + 1].a
-                    self.add(kind="ca", cv=blk.c, cv2=nxa, cv3=blk.branch1, din=db, din3=d, dout=dc, src=c_src, src3=cur, dst=nxt, dst2=a_buf)
-                    self.need(a_buf, nxa.out_dims(*dc), nxa.cout)
-                    a_done = True
-                else:
-                    self.add(kind="dual", cv=blk.c, cv2=blk.branch1, din=db, din2=d, dout=dc, src=c_src, src2=cur, dst=nxt, ld=ld)
-            elif (not last and not tp and res_src == cur and ld == blk.c.cout and stage.blocks[bi + 1].a.pool_after_bn is None
-                  and self.ca_fusable(blk.c, stage.blocks[bi + 1].a, db, dc)):
-                # c + residual + ReLU of this block and the a conv of the next one in one launch (s2): the trunk slab is
-                # produced in LDS, stored once, and multiplied by the temporal taps without being read back
-                nxa = stage.blocks[bi + 1].a
-                self.add(kind="ca", cv=blk.c, cv2=nxa, din=db, dout=dc, src=c_src, res=res_src, dst=nxt, dst2=a_buf)
-                self.need(a_buf, nxa.out_dims(*dc), nxa.cout)
-                a_done = True
-            elif tp and next_stage is not None and res_src == cur and ld == blk.c.cout and (
-                    sub := self._boundary_fusable(blk.c, next_stage, db, dc)):
-                # s2 -> s3: c + residual + ReLU, the temporal pool and the next stage's first a conv in one launch; the pooled trunk
-                # is stored only where the next stage's projection shortcut reads it
-                nb = next_stage.blocks[0]
-                self.add(kind="cpa", cv=blk.c, cv2=nb.a, din=db, dout=dc, src=c_src, res=res_src, dst=nxt, dst2=a_buf, x_sub=sub, tpool=True)
-                self.need(a_buf, nb.a.out_dims(*dstore), nb.a.cout)
-                self.boundary = {"sub": sub == 2}
-            else:
-                self.add(kind="conv", cv=blk.c, din=db, dout=dc, src=c_src, dst=nxt, res=res_src, ld=ld, tpool=tp)
-            self.need(nxt, dstore, ld)
-            cur, nxt = nxt, cur
-            d, c = dstore, blk.c.cout
-        return d, c, cur, nxt
+            launch = self.ask(self.make("bc", [("b", blk.b, da, db), ("c", blk.c, db, dc)], src=a_buf, res=cur, dst=nxt, ld=ld))
+            if launch is not None:
+                self.launches.append(launch); self.need(nxt, dc, ld)
+                return dc, None
+        self.conv(blk.b, da, db, a_buf, b_buf); self.need(b_buf, db, blk.b.cout)
+        return db, b_buf
+
+    def _conv_maxpool(self, cv: ConvSpec, din, src, fused_dst, conv_dst, pool_dst):
+        """FTCN's conv -> BN -> MaxPool3d -> ReLU.  A 1x2x2 pool over even sizes rides in the conv's launch, into ``fused_dst`` (max
+        and ReLU commute: the tile rows are ordered so that a 2x2 window is 4 adjacent rows and the epilogue stores their max); else
+        the conv goes into ``conv_dst`` and the pool, a launch of its own, into ``pool_dst``.  Returns (pooled dims, their buffer)."""
+        p, dout = cv.pool_after_bn, cv.out_dims(*din)
+        dp = _pool_out(dout, p)
+        if _is_pool(p, (1, 2, 2), (1, 2, 2), (0, 0, 0)) and dout[1] % 2 == 0 and dout[2] % 2 == 0:
+            self.conv(cv, din, dout, src, fused_dst, tpool=2); self.need(fused_dst, dp, cv.cout)
+            return dp, fused_dst
+        self.conv(cv, din, dout, src, conv_dst); self.need(conv_dst, dout, cv.cout)
+        self.pool("pool", p, cv.cout, dout, dp, conv_dst, dst=pool_dst); self.need(pool_dst, dp, cv.cout)
+        return dp, pool_dst
+
+    def _c_side(self, blk, nxa, d, db, c_src, res, cur, nxt, a_buf, ld, sub, tpool_here, next_stage):
+        """The c conv with the block's shortcut, add and ReLU, as the first of these that applies: dual on a subsampled trunk (``sub``:
+        a cpa launch with x_sub = 2 stored ``cur``), ca with projection, dual, ca, cpa, conv.  ``nxa``: the next block's a conv, None
+        behind the last block.  Returns (the dims stored, what the next block is handed, whether the temporal pool rode along)."""
+        dc = blk.c.out_dims(*db)
+        proj = blk.branch1 if (blk.branch1 is not None and blk.branch1.pool_after_bn is None) else None
+        # the temporal max-pool after s2 rides in the epilogue of s2's last conv when it can
+        tp = bool(tpool_here and blk.branch1 is None and dc[0] % 2 == 0)
+        c = ("c", blk.c, db, dc)
+        a_next = lambda: ("a_next", nxa, dc, nxa.out_dims(*dc))
+        may_ca = nxa is not None and ld == blk.c.cout and nxa.pool_after_bn is None
+        launch = None
+        if proj is not None and sub:
+            # the previous stage's last launch stored the trunk only where this stride-(1,2,2) shortcut reads it, packed:
+            # the same weights as a stride-1 convolution over that tensor
+            b1 = dataclasses.replace(proj, stride=(1, 1, 1))
+            dsub = (d[0], d[1] // 2, d[2] // 2)
+            assert b1.out_dims(*dsub) == dc
+            launch = self.make("dual", [c, ("branch1", b1, dsub, dc)], src=c_src, src2=cur, dst=nxt, ld=ld)
+        elif proj is not None:
+            # c conv + projection shortcut in one launch, no shortcut tensor; and the next block's a conv behind them (s2) where
+            # the library takes it: the trunk slab never comes back from HBM
+            assert proj.out_dims(*d) == dc
+            b1 = ("branch1", proj, d, dc)
+            launch = may_ca and self.ask(self.make("ca", [c, b1, a_next()], src=c_src, src2=cur, dst=nxt, dst_a=a_buf))
+            launch = launch or self.make("dual", [c, b1], src=c_src, src2=cur, dst=nxt, ld=ld)
+        elif may_ca and not tp and res == cur:
+            # c + residual + ReLU of this block and the a conv of the next one in one launch (s2): the trunk slab is
+            # produced in LDS, stored once, and multiplied by the temporal taps without being read back
+            launch = self.ask(self.make("ca", [c, ("branch1", None, d, dc), a_next()], src=c_src, res=res, dst=nxt, dst_a=a_buf))
+        elif tp and next_stage is not None and res == cur and ld == blk.c.cout:
+            # s2 -> s3: c + residual + ReLU, the temporal pool and the next stage's first a conv in one launch; the pooled trunk
+            # is stored only where the next stage's projection shortcut reads it
+            launch = self._boundary(blk.c, next_stage.blocks[0], db, dc, c_src, res, nxt, a_buf)
+        launch = launch or self.make("conv", [("conv", blk.c, db, dc, int(tp))], src=c_src, res=res, dst=nxt, ld=ld)
+        self.launches.append(launch)
+        if launch.dst_a:
+            a = launch.descs[-1]
+            self.need(a_buf, (a.to, a.ho, a.wo), a.cout)
+        dstore = (dc[0] // 2,) + tuple(dc[1:]) if tp else dc
+        self.need(nxt, dstore, ld)
+        return dstore, _Handoff(bool(launch.dst_a), launch.x_sub == 2), launch.tpool == 1
+
+    def _boundary(self, c: ConvSpec, nb, db, dc, c_src, res, nxt, a_buf) -> Optional[Launch]:
+        """The fused stage-boundary launch (cpa) into block ``nb`` of the next stage, or None.  x_sub = 2 when ``nb`` reads the
+        pooled trunk only through a 1x1x1 projection shortcut of stride (1,2,2) (and its a conv, which runs inside the launch)."""
+        b1 = nb.branch1
+        if nb.a.pool_after_bn is not None or dc[0] % 2 or b1 is None:
+            return None                    # (an identity shortcut would need the whole trunk AND block 0's residual add: not this launch)
+        sub = 2 if (b1.pool_after_bn is None and tuple(b1.kernel) == (1, 1, 1) and tuple(b1.stride) == (1, 2, 2)
+                    and tuple(b1.pad) == (0, 0, 0) and dc[1] % 2 == 0 and dc[2] % 2 == 0) else 1
+        dp = (dc[0] // 2,) + tuple(dc[1:])
+        return self.ask(self.make("cpa", [("c", c, db, dc, 1), ("a_next", nb.a, dp, nb.a.out_dims(*dp))],
+                                  src=c_src, res=res, dst=nxt, dst_a=a_buf, x_sub=sub))
 
 
 def _plan_i3d(plan: _Plan, spec: NetSpec, T, H, W, has_rgb3):
@@ -366,23 +403,21 @@ def _plan_i3d(plan: _Plan, spec: NetSpec, T, H, W, has_rgb3):
                       _is_pool(spec.stem_pool, (1, 3, 3), (1, 2, 2), (0, 1, 1)))
     plan.rgb3 = bool(fuse_stem_pool and spec.stem.conv in has_rgb3)
     if fuse_stem_pool:        # conv + BN + ReLU + max-pool in one launch; the conv output never reaches HBM
-        plan.add(kind="stem3_pool" if plan.rgb3 else "stem_pool", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur)
-        plan.need(cur, d2, spec.stem.cout)
+        plan.conv(spec.stem, (T, H, W), d, "IN", cur, kind="stem3_pool" if plan.rgb3 else "stem_pool"); plan.need(cur, d2, spec.stem.cout)
     else:
-        plan.add(kind="stem", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur); plan.need(cur, d, spec.stem.cout)
-        plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stem.cout, din=d, dout=d2, src=cur, dst=nxt)
-        plan.need(nxt, d2, spec.stem.cout)
+        plan.conv(spec.stem, (T, H, W), d, "IN", cur, kind="stem"); plan.need(cur, d, spec.stem.cout)
+        plan.pool("pool", spec.stem_pool, spec.stem.cout, d, d2, cur, dst=nxt); plan.need(nxt, d2, spec.stem.cout)
         cur, nxt = nxt, cur
     d = d2
     fuse_tpool = _is_pool(spec.pool_after_s2, (2, 1, 1), (2, 1, 1), (0, 0, 0))
     c = spec.stem.cout
     for si, stage in enumerate(spec.stages):
-        d, c, cur, nxt = plan.stage(stage, d, cur, nxt, "A", "B", tpool_last=(fuse_tpool and si == 0),
-                                    next_stage=spec.stages[1] if (si == 0 and len(spec.stages) > 1) else None)
-        if si == 0 and not plan.entries[-1].get("tpool"):
+        d, c, cur, nxt, tpooled = plan.stage(stage, d, cur, nxt, "A", "B", tpool_last=(fuse_tpool and si == 0),
+                                             next_stage=spec.stages[1] if (si == 0 and len(spec.stages) > 1) else None)
+        if si == 0 and not tpooled:
             # pathway0_pool as its own launch (odd frame counts / other pool shapes)
             d2 = _pool_out(d, spec.pool_after_s2)
-            plan.add(kind="pool", pool=spec.pool_after_s2, ch=c, din=d, dout=d2, src=cur, dst=nxt); plan.need(nxt, d2, c)
+            plan.pool("pool", spec.pool_after_s2, c, d, d2, cur, dst=nxt); plan.need(nxt, d2, c)
             cur, nxt = nxt, cur
             d = d2
     hp = tuple(spec.head_pool)
@@ -390,7 +425,7 @@ def _plan_i3d(plan: _Plan, spec: NetSpec, T, H, W, has_rgb3):
     if min(dh) < 1:
         raise ValueError("input %s too small for the head pool %s" % ((T, H, W), hp))
     plan.head_dims, plan.head_width = dh, c
-    plan.add(kind="head", pool=hp, ch=c, din=d, dout=dh, src=cur)
+    plan.pool("head", hp, c, d, dh, cur)
 
 
 def _plan_ftcn(plan: _Plan, spec: FtcnTTSpec, T, H, W, has_rgb3):
@@ -405,26 +440,26 @@ def _plan_ftcn(plan: _Plan, spec: FtcnTTSpec, T, H, W, has_rgb3):
             and _is_pool(spec.stem_pool, (1, 3, 3), (1, 2, 2), (0, 1, 1))):
         # 16-bit: the stem's own 1x3x3 / stride-2 max-pool rides behind the temporal stem (the half-resolution tensor -
         # 822 MB at 16 clips - is neither written nor read back)
-        plan.add(kind="tstem_pool3", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur); plan.need(cur, d2, spec.stem.cout)
+        plan.conv(spec.stem, (T, H, W), d, "IN", cur, kind="tstem_pool3"); plan.need(cur, d2, spec.stem.cout)
         d = d2
     else:
-        plan.add(kind="tstem", cv=spec.stem, din=(T, H, W), dout=d, src="IN", dst=cur); plan.need(cur, d, spec.stem.cout)
-        plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stem.cout, din=d, dout=d2, src=cur, dst=nxt); plan.need(nxt, d2, spec.stem.cout)
+        plan.conv(spec.stem, (T, H, W), d, "IN", cur, kind="tstem"); plan.need(cur, d, spec.stem.cout)
+        plan.pool("pool", spec.stem_pool, spec.stem.cout, d, d2, cur, dst=nxt); plan.need(nxt, d2, spec.stem.cout)
         cur, nxt, d = nxt, cur, d2
     fuse_tpool = _is_pool(spec.pool_after_s2, (2, 1, 1), (2, 1, 1), (0, 0, 0))
     c = spec.stem.cout
     for si, stage in enumerate(spec.stages):
-        d, c, cur, nxt = plan.stage(stage, d, cur, nxt, "A", "B", tpool_last=(fuse_tpool and si == 0))
-        if si == 0 and not plan.entries[-1].get("tpool"):
+        d, c, cur, nxt, tpooled = plan.stage(stage, d, cur, nxt, "A", "B", tpool_last=(fuse_tpool and si == 0))
+        if si == 0 and not tpooled:
             dp = _pool_out(d, spec.pool_after_s2)
-            plan.add(kind="pool", pool=spec.pool_after_s2, ch=c, din=d, dout=dp, src=cur, dst=nxt); plan.need(nxt, dp, c)
+            plan.pool("pool", spec.pool_after_s2, c, d, dp, cur, dst=nxt); plan.need(nxt, dp, c)
             cur, nxt, d = nxt, cur, dp
     # TransformerHead 'time' patches (:133-135): AvgPool3d((1, S, S)) sized from the crop, one token per frame
     if tuple(d[1:]) != tuple(spec.token_pool[1:]) or d[0] != spec.tokens or c != spec.dim:
         raise ValueError("FTCN-TT head expects a (%d,%d,%d)x%d feature map, got %s x %d"
                          % (spec.tokens, spec.token_pool[1], spec.token_pool[2], spec.dim, d, c))
     plan.head_dims, plan.head_width = (1, 1, 1), spec.dim
-    plan.add(kind="tt_head", ch=c, din=d, src=cur)
+    plan.pool("tt_head", spec.token_pool, c, d, (d[0], 1, 1), cur)           # its first op: one token per frame
 
 
 def _plan_slowfast(plan: _Plan, spec: SlowFastSpec, T, H, W, has_rgb3):
@@ -441,21 +476,21 @@ def _plan_slowfast(plan: _Plan, spec: SlowFastSpec, T, H, W, has_rgb3):
             and _is_pool(spec.stem_pool, (1, 3, 3), (1, 2, 2), (0, 1, 1)) and ds[2] <= 128):
         # 16-bit: the Slow stem + its max-pool as the K-packed fused stem (3-channel input layout), pooled rows at the widened stride
         plan.rgb3_inputs.add("IN_S")
-        plan.add(kind="stem3_pool", cv=spec.stems[0], din=(Ts, H, W), dout=ds, src="IN_S", dst="S0", ld=ld0)
+        plan.conv(spec.stems[0], (Ts, H, W), ds, "IN_S", "S0", kind="stem3_pool", ld=ld0)
         plan.need("S1", ds2, spec.stems[0].cout)
     else:
-        plan.add(kind="stem", cv=spec.stems[0], din=(Ts, H, W), dout=ds, src="IN_S", dst="S1"); plan.need("S1", ds, spec.stems[0].cout)
-        plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stems[0].cout, din=ds, dout=ds2, src="S1", dst="S0", ld=ld0)
+        plan.conv(spec.stems[0], (Ts, H, W), ds, "IN_S", "S1", kind="stem"); plan.need("S1", ds, spec.stems[0].cout)
+        plan.pool("pool", spec.stem_pool, spec.stems[0].cout, ds, ds2, "S1", dst="S0", ld=ld0)
     plan.need("S0", ds2, ld0)
-    plan.add(kind="stem", cv=spec.stems[1], din=(T, H, W), dout=df, src="IN_F", dst="F1"); plan.need("F1", df, spec.stems[1].cout)
-    plan.add(kind="pool", pool=spec.stem_pool, ch=spec.stems[1].cout, din=df, dout=df2, src="F1", dst="F0")
+    plan.conv(spec.stems[1], (T, H, W), df, "IN_F", "F1", kind="stem"); plan.need("F1", df, spec.stems[1].cout)
+    plan.pool("pool", spec.stem_pool, spec.stems[1].cout, df, df2, "F1", dst="F0")
     plan.need("F0", df2, spec.stems[1].cout)
     scur, snxt, fcur, fnxt = "S0", "S1", "F0", "F1"
     ds, df, cs = ds2, df2, spec.stems[0].cout
 
     def lateral(fz: ConvSpec, dfast, fbuf, sbuf, c_slow, ld):
         do = fz.out_dims(*dfast)                                   # FuseFastToSlow: conv + BN + ReLU into the Slow rows
-        plan.add(kind="conv", cv=fz, din=dfast, dout=do, src=fbuf, dst=sbuf, ld=ld, ch_off=c_slow)
+        plan.conv(fz, dfast, do, fbuf, sbuf, ld=ld, ch_off=c_slow)
         return do
 
     if lateral(spec.fuses[0], df, fcur, scur, cs, ld0) != ds:
@@ -464,8 +499,8 @@ def _plan_slowfast(plan: _Plan, spec: SlowFastSpec, T, H, W, has_rgb3):
     for si, (slow, fast) in enumerate(spec.stages):
         has_fuse = si + 1 < len(spec.fuses)
         ld = slow.blocks[-1].c.cout + (fuse_w[si + 1] if has_fuse else 0)
-        ds, cs, scur, snxt = plan.stage(slow, ds, scur, snxt, "A_S", "B_S", last_ld=ld)
-        df, cf, fcur, fnxt = plan.stage(fast, df, fcur, fnxt, "A_F", "B_F")
+        ds, cs, scur, snxt, _ = plan.stage(slow, ds, scur, snxt, "A_S", "B_S", last_ld=ld)
+        df, cf, fcur, fnxt, _ = plan.stage(fast, df, fcur, fnxt, "A_F", "B_F")
         if has_fuse and lateral(spec.fuses[si + 1], df, fcur, scur, cs, ld) != ds:
             raise ValueError("the Fast->Slow lateral does not land on the Slow grid")
     hs, hf = (tuple(p) for p in spec.head_pools)
@@ -474,9 +509,9 @@ def _plan_slowfast(plan: _Plan, spec: SlowFastSpec, T, H, W, has_rgb3):
     if min(dhs) < 1 or dhs != dhf:
         raise ValueError("input %s does not fit the SlowFast head pools %s / %s" % ((T, H, W), hs, hf))
     plan.head_dims, plan.head_width = dhs, cs + cf
-    plan.add(kind="avgpool", pool=hs, ch=cs, din=ds, dout=dhs, src=scur, ch_off=0)
-    plan.add(kind="avgpool", pool=hf, ch=cf, din=df, dout=dhf, src=fcur, ch_off=cs)
-    plan.add(kind="linear")
+    plan.pool("avgpool", hs, cs, ds, dhs, scur, ch_off=0)
+    plan.pool("avgpool", hf, cf, df, dhf, fcur, ch_off=cs)
+    plan.launches.append(Launch("linear"))
 
 
 def plan_network(spec, dtype: str, batch: int, dims, has_rgb3=()) -> _Plan:
@@ -524,11 +559,11 @@ class Engine:
                        if spec.num_classes in (1, 2) else None)
 
         n_pack = len(self.inputs)
-        self.n_ops = n_pack + len(plan.entries) + (self.TT_HEAD_OPS - 1 if isinstance(spec, FtcnTTSpec) else 0)
+        self.n_ops = n_pack + len(plan.launches) + (self.TT_HEAD_OPS - 1 if isinstance(spec, FtcnTTSpec) else 0)
         self.ops = (Op * self.n_ops)()
         self.op_names: List[str] = []
         self.op_macs: List[int] = []
-        self.op_dst: List[Optional[str]] = [name for name, _, _ in self.inputs] + [e.get("dst") for e in plan.entries]
+        self.op_dst: List[Optional[str]] = [name for name, _, _ in self.inputs] + [launch.dst for launch in plan.launches]
         for i, (name, dims, _) in enumerate(self.inputs):
             pk = self.ops[i]
             pk.kind, pk.tag = self.k_pack_f32[i], TAG_PACK
@@ -540,16 +575,18 @@ class Engine:
             pk = self.ops[0]
             pk.aux, pk.x_sub = self.buf[self.inputs[1][0]].data_ptr(), self.inputs[0][2]
             pk.pack_rgb3 = sum(1 << i for i, (name, _, _) in enumerate(self.inputs) if name in r3)
-        for k, e in enumerate(plan.entries):
+        for k, launch in enumerate(plan.launches):
             op = self.ops[n_pack + k]
-            if "src" in e:
-                op.in_ = self._at(e["src"])
-            if "dst" in e:
-                op.out = self._at(e["dst"]) + e.get("ch_off", 0) * es
-            if e["kind"] == "tt_head":
-                self._materialise_tt_head(n_pack + k, e)
+            op.in_, op.residual, op.aux = self._at(launch.src), self._at(launch.res), self._at(launch.dst_a)
+            op.out_ld, op.x_sub = launch.ld, launch.x_sub
+            if launch.pool is not None:
+                op.pool = launch.pool
+            if launch.dst:
+                op.out = self._at(launch.dst) + launch.ch_off * es
+            if launch.kind == "tt_head":
+                self._materialise_tt_head(n_pack + k, launch)
                 continue
-            name, macs = self._EMIT[e["kind"]](self, op, e)
+            name, macs = self._EMIT[launch.kind](self, op, launch)
             self.op_names.append(name)
             self.op_macs.append(batch * macs)
         # split-K scratch (small batches, long-K layers): sized by the library, owned by this engine (one per engine =
@@ -565,109 +602,76 @@ class Engine:
                 self.ops[i].workspace = self.workspace.data_ptr()
                 self.ops[i].workspace_bytes = need
 
-    # One function per plan-entry kind: fills ``op`` (in_ / out are already bound) and returns (op name, MACs per clip).
-    # Every conv of a fused launch is described with relu = 1, as the library's *_fusable predicates were asked.
+    # One function per launch kind: fills ``op`` (in_, out, residual, aux, out_ld, x_sub and pool are already bound) and returns (op
+    # name, MACs per clip).  The descriptors are the launch's own, copied: what the library's *_fusable predicate was asked with.
     def _at(self, buf: Optional[str]):
         return self.buf[buf].data_ptr() if buf else None
-
-    def _desc(self, cv: ConvSpec, din, dout, relu=True, tpool=0):
-        return _conv_desc(self.batch, self.code, cv, din, dout, relu, tpool)
-
-    def _pool_desc(self, e, kernel, stride=(1, 1, 1), pad=(0, 0, 0)):
-        return _lib.pool_desc(self.batch, e["din"], e["ch"], kernel, stride, pad, self.code, e["dout"], e.get("ld", 0))
 
     _CONV_KINDS = {"stem": _lib.AF_OP_STEM, "stem_pool": _lib.AF_OP_STEM_POOL, "stem3_pool": _lib.AF_OP_STEM3_POOL,
                    "tstem": _lib.AF_OP_TSTEM, "tstem_pool3": _lib.AF_OP_TSTEM_POOL3, "conv": _lib.AF_OP_CONV}
 
-    def _emit_conv(self, op, e):
-        cv: ConvSpec = e["cv"]
-        op.kind = self._CONV_KINDS[e["kind"]]
-        op.tag = TAG_STEM if e["kind"] != "conv" else _conv_tag(cv)
-        # a, b, stems and laterals carry their own ReLU; c (final_bn) takes the block's add + ReLU; the
-        # projection shortcut has neither (resnet_helper.py:311-326, 438-444; video_model_builder.py:136-143)
-        op.conv = self._desc(cv, e["din"], e["dout"], cv.relu or cv.final_bn, e.get("tpool") or 0)
+    def _emit_conv(self, op, launch):
+        cv = launch.convs["conv"]
+        op.kind, op.tag = self._CONV_KINDS[launch.kind], TAG_STEM if launch.kind != "conv" else _conv_tag(cv)
+        op.conv, = launch.descs
         op.weight, op.scale, op.shift = self.weights.bn(cv)
-        if e["kind"] == "stem3_pool":
+        if launch.kind == "stem3_pool":
             op.weight = self.weights.w3[cv.conv].data_ptr()
-        op.residual = self._at(e.get("res"))
-        op.out_ld = e.get("ld", cv.cout)
-        return cv.conv, cv.macs(*e["din"])
+        return cv.conv, launch.macs()
 
-    def _emit_ca(self, op, e):
-        cvc, cva, cv1 = e["cv"], e["cv2"], e.get("cv3")
+    def _emit_ca(self, op, launch):
+        cvc, cv1, cva = launch.convs.values()
         op.kind, op.tag = _lib.AF_OP_CONV_CA, TAG_CONV_CA
-        op.conv = self._desc(cvc, e["din"], e["dout"])
-        op.conv2 = self._desc(cva, e["dout"], cva.out_dims(*e["dout"]))
+        op.conv, d1, op.conv2 = launch.descs
         op.weight2, op.scale2, op.shift2 = self.weights.bn(cva)
-        macs = cvc.macs(*e["din"]) + cva.macs(*e["dout"])
         if cv1 is not None:                          # projection block: no residual tensor
-            op.conv3 = self._desc(cv1, e["din3"], e["dout"])
+            op.conv3 = d1
             op.weight, op.weight3, op.scale, op.shift = self.weights.folded(cvc, cv1)
-            op.in3 = self._at(e["src3"])
-            macs += cv1.macs(*e["din3"])
+            op.in3 = self._at(launch.src2)
         else:
             op.weight, op.scale, op.shift = self.weights.bn(cvc)
-            op.residual = self._at(e["res"])
-        op.aux = self._at(e["dst2"])
-        op.out_ld = cvc.cout
-        return cvc.conv + ("+branch1" if cv1 is not None else "") + "->" + cva.conv.split("resnet.")[-1], macs
+        return cvc.conv + ("+branch1" if cv1 is not None else "") + "->" + cva.conv.split("resnet.")[-1], launch.macs()
 
-    def _emit_cpa(self, op, e):
-        cvc, cva = e["cv"], e["cv2"]
-        dp = (e["dout"][0] // 2,) + tuple(e["dout"][1:])
+    def _emit_cpa(self, op, launch):
+        cvc, cva = launch.convs.values()
         op.kind, op.tag = _lib.AF_OP_CONV_CPA, TAG_CONV_CA
-        op.conv = self._desc(cvc, e["din"], e["dout"], tpool=1)
-        op.conv2 = self._desc(cva, dp, cva.out_dims(*dp))
+        op.conv, op.conv2 = launch.descs
         op.weight, op.scale, op.shift = self.weights.bn(cvc)
         op.weight2, op.scale2, op.shift2 = self.weights.bn(cva)
-        op.residual = self._at(e["res"])
-        op.aux = self._at(e["dst2"])
-        op.out_ld, op.x_sub = cvc.cout, e["x_sub"]
-        return cvc.conv + "+pool->" + cva.conv.split("resnet.")[-1], cvc.macs(*e["din"]) + cva.macs(*dp)
+        return cvc.conv + "+pool->" + cva.conv.split("resnet.")[-1], launch.macs()
 
-    def _emit_abc(self, op, e):
-        cva, cvb, cvc, cv1 = e["cv"], e["cv2"], e["cv3"], e.get("cv4")
-        d = e["din"]
+    def _emit_abc(self, op, launch):
+        cva, cvb, cvc, cv1 = launch.convs.values()
         op.kind, op.tag = _lib.AF_OP_BLOCK_ABC, TAG_BLOCK_ABC
-        op.conv, op.conv2, op.conv3 = self._desc(cva, d, d), self._desc(cvb, d, d), self._desc(cvc, d, d)
+        op.conv, op.conv2, op.conv3, d1 = launch.descs
         op.weight, op.scale, op.shift = self.weights.bn(cva)
         op.weight2, op.scale2, op.shift2 = self.weights.bn(cvb)
-        macs = cva.macs(*d) + cvb.macs(*d) + cvc.macs(*d)
         if cv1 is not None:                          # projection block
-            op.conv4 = self._desc(cv1, d, d)
+            op.conv4 = d1
             op.weight3, op.weight4, op.scale3, op.shift3 = self.weights.folded(cvc, cv1)
-            macs += cv1.macs(*d)
         else:
             op.weight3, op.scale3, op.shift3 = self.weights.bn(cvc)
-        op.out_ld = e.get("ld", cvc.cout)
-        return cva.conv.rsplit(".", 1)[0] + ".a+b+c" + ("+branch1" if cv1 is not None else ""), macs
+        return cva.conv.rsplit(".", 1)[0] + ".a+b+c" + ("+branch1" if cv1 is not None else ""), launch.macs()
 
-    def _emit_bc(self, op, e):
-        cvb, cvc = e["cv"], e["cv2"]
+    def _emit_bc(self, op, launch):
+        cvb, cvc = launch.convs.values()
         op.kind, op.tag = _lib.AF_OP_CONV_BC, TAG_CONV_BC
-        op.conv = self._desc(cvb, e["din"], e["dmid"])
-        op.conv2 = self._desc(cvc, e["dmid"], e["dout"])
+        op.conv, op.conv2 = launch.descs
         op.weight, op.scale, op.shift = self.weights.bn(cvb)
         op.weight2, op.scale2, op.shift2 = self.weights.bn(cvc)
-        op.residual = self._at(e["res"])
-        op.out_ld = e.get("ld", cvc.cout)
-        return cvb.conv + "+c", cvb.macs(*e["din"]) + cvc.macs(*e["dmid"])
+        return cvb.conv + "+c", launch.macs()
 
-    def _emit_dual(self, op, e):
-        cvc, cv1 = e["cv"], e["cv2"]
+    def _emit_dual(self, op, launch):
+        cvc, cv1 = launch.convs.values()
         op.kind, op.tag = _lib.AF_OP_CONV_DUAL, _conv_tag(cvc)
-        op.conv = self._desc(cvc, e["din"], e["dout"])
-        op.conv2 = self._desc(cv1, e["din2"], e["dout"])
+        op.conv, op.conv2 = launch.descs
         op.weight, op.weight2, op.scale, op.shift = self.weights.folded(cvc, cv1)
-        op.in2 = self._at(e["src2"])
-        op.out_ld = e.get("ld", cvc.cout)
-        return cvc.conv + "+branch1", cvc.macs(*e["din"]) + cv1.macs(*e["din2"])
+        op.in2 = self._at(launch.src2)
+        return cvc.conv + "+branch1", launch.macs()
 
-    def _emit_pool(self, op, e):
-        p = e["pool"]
+    def _emit_pool(self, op, launch):
         op.kind, op.tag = _lib.AF_OP_MAXPOOL, TAG_POOL
-        op.pool = self._pool_desc(e, p.kernel, p.stride, p.pad)
-        return "maxpool_%dx%dx%d" % tuple(p.kernel), 0
+        return "maxpool_%dx%dx%d" % (op.pool.kt, op.pool.kh, op.pool.kw), 0
 
     def _bind_fc(self, op):
         """the head's Linear (+ the score epilogue) into ``logits`` / ``scores``"""
@@ -677,26 +681,24 @@ class Engine:
         op.out = self.logits.data_ptr()
         op.scores = self.scores.data_ptr() if self.scores is not None else None
 
-    def _emit_head(self, op, e):
+    def _emit_head(self, op, launch):
         op.kind = _lib.AF_OP_HEAD
-        op.pool = self._pool_desc(e, e["pool"])
         op.aux = self.pooled.data_ptr()
         self._bind_fc(op)
         return "head", 0
 
-    def _emit_linear(self, op, e):
+    def _emit_linear(self, op, launch):
         op.kind = _lib.AF_OP_LINEAR
         op.in_ = self.pooled.data_ptr()
         op.pool.n, op.pool.c = self.batch * self.head_positions, self.head_width
         self._bind_fc(op)
         return "head_linear", 0
 
-    def _emit_avgpool(self, op, e):
+    def _emit_avgpool(self, op, launch):
         op.kind, op.tag = _lib.AF_OP_AVGPOOL, TAG_HEAD
-        op.pool = self._pool_desc(e, e["pool"])
-        op.out = self.pooled.data_ptr() + e["ch_off"] * 4
+        op.out = self.pooled.data_ptr() + launch.ch_off * 4
         op.out_ld = self.head_width
-        return "head_avgpool_%d" % e["ch_off"], 0
+        return "head_avgpool_%d" % launch.ch_off, 0
 
     _EMIT = {"stem": _emit_conv, "stem_pool": _emit_conv, "stem3_pool": _emit_conv, "tstem": _emit_conv, "tstem_pool3": _emit_conv,
              "conv": _emit_conv, "ca": _emit_ca, "cpa": _emit_cpa, "abc": _emit_abc, "bc": _emit_bc, "dual": _emit_dual,
@@ -704,7 +706,7 @@ class Engine:
 
     TT_HEAD_OPS = 12
 
-    def _materialise_tt_head(self, first: int, e):
+    def _materialise_tt_head(self, first: int, launch):
         """The FTCN-TT head as TT_HEAD_OPS ops starting at ops[first] (fp32 buffers of its own)."""
         spec, w, batch, dev = self.spec, self.weights, self.batch, self.device
         n1, dim, inner = spec.tokens + 1, spec.dim, spec.heads * spec.dim_head
@@ -744,8 +746,7 @@ class Engine:
 
         op = nxt("avgpool_tokens")                                         # (B, T/2, dim) per-frame tokens
         op.kind = _lib.AF_OP_AVGPOOL
-        op.pool = _lib.pool_desc(batch, e["din"], e["ch"], spec.token_pool, (1, 1, 1), (0, 0, 0), self.code, dout=(e["din"][0], 1, 1))
-        op.in_, op.out, op.out_ld = self.buf[e["src"]].data_ptr(), self.tokens_pooled.data_ptr(), dim
+        op.in_, op.out, op.out_ld = self.buf[launch.src].data_ptr(), self.tokens_pooled.data_ptr(), dim
         op = nxt("tokens")                                                 # class token + position embedding
         op.kind = _lib.AF_OP_TOKENS
         op.in_, op.weight, op.scale = self.tokens_pooled.data_ptr(), w.cls_token.data_ptr(), w.pos_embedding.data_ptr()

@@ -698,36 +698,68 @@ def _kinds(text):
 
 # launch kinds of the bf16 plans at 16 clips of 32 x 224 x 224, default switches (name*n = n launches in a row)
 PLAN_KINDS = {
-    "i3d": "stem3_pool conv*2 ca conv ca conv*4 dual conv*11 dual conv*17 dual conv*6 head",
-    "slowfast": "stem3_pool stem pool conv*3 dual conv*6 abc*3 conv*3 dual conv*11 dual abc*3 conv*3 dual conv*17 dual conv*18 dual "
-                "conv*8 dual conv*6 avgpool*2 linear",
+    "i3d_r50": "stem3_pool conv*2 ca conv ca conv*4 dual conv*11 dual conv*17 dual conv*6 head",
+    "slowfast_r50": "stem3_pool stem pool conv*3 dual conv*6 abc*3 conv*3 dual conv*11 dual abc*3 conv*3 dual conv*17 dual conv*18 dual "
+                    "conv*8 dual conv*6 avgpool*2 linear",
     "ftcn_tt": "tstem_pool3 conv*2 ca conv ca conv*34 tt_head",
 }
 PLAN_KINDS_I3D_CPA = "stem3_pool conv*2 ca conv ca conv cpa conv dual conv*11 dual conv*17 dual conv*6 head"
 
 
+def _main_and_shortcut(launch):
+    """(the conv, its projection shortcut or None) of a `conv` / `dual` launch"""
+    return (launch.convs["c"], launch.convs["branch1"]) if launch.kind == "dual" else (launch.convs["conv"], None)
+
+
+def _load_tests_module(name):
+    """a test module of this directory, for its CASES and case_key functions"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module
+
+
+def _gen_conv_paths_golden():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_conv_paths_golden", os.path.join(ROOT, "tools", "gen_conv_paths_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen
+
+
 def test_plans_need_no_device_and_keep_their_launch_kinds(monkeypatch):
     """planning is host logic (spec + the library's *_fusable predicates): a drifting switch default or fusion decision shows up
     here as a changed sequence of launch kinds"""
+    import plan_cases
     from af_mi355x import engine
-    for name in engine.SWITCHES:
-        monkeypatch.delenv(name, raising=False)
-    specs = {"i3d": arch.i3d_r50_spec(), "slowfast": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
-    rgb3 = {"i3d": {specs["i3d"].stem.conv}, "slowfast": {specs["slowfast"].stems[0].conv}, "ftcn_tt": set()}   # PackedWeights.w3 at 16 bits
-
-    def plan(net):
-        spec = specs[net]
-        return engine.plan_network(spec, "bf16", 16, (spec.num_frames, spec.crop, spec.crop), rgb3[net])
-
+    plan_cases.set_switches(monkeypatch, {})
     for net, want in PLAN_KINDS.items():
-        p = plan(net)
-        assert [e["kind"] for e in p.entries] == _kinds(want), net
-        assert p.rgb3 == (net == "i3d") and p.rgb3_inputs == ({"IN_S"} if net == "slowfast" else set())
-        assert len(p.inputs) == (2 if net == "slowfast" else 1) and p.head_dims is not None and p.head_width > 0
+        p = plan_cases.plan(net, "bf16", 16)
+        assert [launch.kind for launch in p.launches] == _kinds(want), net
+        assert p.rgb3 == (net == "i3d_r50") and p.rgb3_inputs == ({"IN_S"} if net == "slowfast_r50" else set())
+        assert len(p.inputs) == (2 if net == "slowfast_r50" else 1) and p.head_dims is not None and p.head_width > 0
     assert engine.SWITCHES == {"AF_FUSE_BC": False, "AF_FUSE_CA": True, "AF_FUSE_CPA": False, "AF_FUSE_ABC": True,
                                "AF_FUSE_TSTEM_POOL": True, "AF_SLOWFAST_STEM3": True}
     monkeypatch.setenv("AF_FUSE_CPA", "1")           # read when the plan is built
-    assert [e["kind"] for e in plan("i3d").entries] == _kinds(PLAN_KINDS_I3D_CPA)
+    assert [launch.kind for launch in plan_cases.plan("i3d_r50", "bf16", 16).launches] == _kinds(PLAN_KINDS_I3D_CPA)
+
+
+def test_plans_equal_the_recorded_ones():
+    """every launch plan of the three networks (f32 / bf16 / f16, batch 1 .. 32, default switches and each switch flipped) is the
+    recorded one: launch kinds, every integer of every conv and pool descriptor, buffers, row strides, buffer sizes, inputs, head
+    and the questions asked of the library (fixture: tests/golden/plan_launches.json, digests written by
+    tools/gen_conv_paths_golden.py --launches)"""
+    gen = _gen_conv_paths_golden()
+    want, got = load_json("plan_launches.json"), gen.collect_launches()
+    assert sorted(got) == sorted(want) == sorted(gen.LAUNCH_CONFIGS) and len(want) == 6
+    for config in sorted(want):
+        assert len(want[config]) == 3 * 3 * 10, config
+        changed = sorted(key for key in set(want[config]) | set(got[config]) if want[config].get(key) != got[config].get(key))
+        assert not changed, "%s: %d plans differ from the recorded ones: %s" % (config, len(changed), changed)
+    # the settings differ where their switch acts
+    assert want["AF_FUSE_CPA=1"]["i3d_r50/bf16/16"] != want["default"]["i3d_r50/bf16/16"]
+    assert want["unfused"]["ftcn_tt/bf16/16"] != want["default"]["ftcn_tt/bf16/16"]
 
 
 def test_conv_paths_and_fusion_answers_equal_the_recorded_ones():
@@ -736,10 +768,7 @@ def test_conv_paths_and_fusion_answers_equal_the_recorded_ones():
     answers in the recorded order (fixture: tests/golden/conv_paths.json, written by tools/gen_conv_paths_golden.py).  How the
     launches are cut is recorded as well (tests/golden/conv_work_units.json, same tool): per conv what af_conv_work_units returns
     - variant, units, workgroups, or its refusal in words -, per fusion answered yes what the pair's *_work_units function says."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("gen_conv_paths_golden", os.path.join(ROOT, "tools", "gen_conv_paths_golden.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
+    gen = _gen_conv_paths_golden()
     got_work = {}
     want, got, want_work = load_json("conv_paths.json"), gen.collect(got_work), load_json("conv_work_units.json")
     assert sorted(got) == sorted(want) and len(want) == 3 * 3 * 3
@@ -766,39 +795,27 @@ def test_conv_matrix_covers_what_ships(monkeypatch):
     tests/test_hip_conv_matrix.py (which runs it against fp64 on the GPU): a new layer shape or pick_variant threshold that ships
     an untested pair fails here.  The plans are built with the fusions off, as tools/gen_conv_paths_golden.py builds them; form =
     (two inputs, residual, tpool, out_ld != cout, split-K); K-steps S class as S up to 6 and as S mod 6 beyond."""
-    import ctypes as C
-    import importlib.util
-    from af_mi355x import engine
+    import plan_cases
     from af_mi355x._lib import lib
-    spec_ = importlib.util.spec_from_file_location("test_hip_conv_matrix", os.path.join(ROOT, "tests", "test_hip_conv_matrix.py"))
-    matrix = importlib.util.module_from_spec(spec_)
-    spec_.loader.exec_module(matrix)
+    matrix = _load_tests_module("test_hip_conv_matrix")
     covered = {matrix.case_key(c, dt) for dt in matrix.DTYPES for c in matrix.CASES if not c.nonfinite}
-    for name in ("AF_FUSE_BC", "AF_FUSE_CA", "AF_FUSE_CPA", "AF_FUSE_ABC"):
-        monkeypatch.setenv(name, "0")
     monkeypatch.delenv("AF_FORCE_VAR", raising=False)
-    specs = {"i3d_r50": arch.i3d_r50_spec(), "slowfast_r50": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
-    rgb3 = {"i3d_r50": {specs["i3d_r50"].stem.conv}, "slowfast_r50": {specs["slowfast_r50"].stems[0].conv}, "ftcn_tt": set()}
     shipped = {}
-    for net, spec in specs.items():
-        for dtype in ("f32", "bf16", "f16"):
-            bk = 32 if dtype == "f32" else 64
-            for batch in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32):
-                p = engine.plan_network(spec, dtype, batch, (spec.num_frames, spec.crop, spec.crop), rgb3[net] if dtype != "f32" else set())
-                for e in p.entries:
-                    if e["kind"] not in ("conv", "dual"):
-                        continue
-                    cv, dual, tpool = e["cv"], e["kind"] == "dual", int(e.get("tpool") or 0)
-                    d = p.desc(cv, e["din"], e["dout"], tpool)
-                    d2 = p.desc(e["cv2"], e["din2"], e["dout"]) if dual else None
-                    tile = lib.af_conv_variant(C.byref(d), C.byref(d2) if dual else None)
-                    if tile not in matrix.TILES:
-                        continue                                # a specialised kernel: its own tests pin the variant
-                    s = cv.kernel[0] * cv.kernel[1] * cv.kernel[2] * -(-cv.cin // bk) + (-(-e["cv2"].cin // bk) if dual else 0)
-                    split = not dual and lib.af_conv_workspace_bytes(C.byref(d)) > 0
-                    form = (dual, e.get("res") is not None, tpool, e.get("ld", cv.cout) != cv.cout, split)
-                    shipped.setdefault((tile, dtype, form, s if s <= 6 else ("big", s % 6)), "%s batch %d: %d -> %d %s, S = %d" % (
-                        net, batch, cv.cin, cv.cout, tuple(cv.kernel), s))
+    for net, dtype, batch, _, p in plan_cases.plans(monkeypatch, [plan_cases.UNFUSED]):
+        bk = 32 if dtype == "f32" else 64
+        for launch in p.launches:
+            if launch.kind not in ("conv", "dual"):
+                continue
+            cv, cv2 = _main_and_shortcut(launch)
+            dual, refs = cv2 is not None, (launch.refs() + [None])[:2]
+            tile = lib.af_conv_variant(*refs)
+            if tile not in matrix.TILES:
+                continue                                # a specialised kernel: its own tests pin the variant
+            s = cv.kernel[0] * cv.kernel[1] * cv.kernel[2] * -(-cv.cin // bk) + (-(-cv2.cin // bk) if dual else 0)
+            split = not dual and lib.af_conv_workspace_bytes(refs[0]) > 0
+            form = (dual, launch.res is not None, launch.tpool, launch.ld != cv.cout, split)
+            shipped.setdefault((tile, dtype, form, s if s <= 6 else ("big", s % 6)), "%s batch %d: %d -> %d %s, S = %d" % (
+                net, batch, cv.cin, cv.cout, tuple(cv.kernel), s))
     assert len(shipped) >= 200, len(shipped)
     missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
     assert not missing, "%d shipped tile x form pairs without a matrix case:\n%s" % (len(missing), "\n".join(missing))
@@ -811,42 +828,27 @@ def test_persist_matrix_covers_what_ships(monkeypatch):
     the temporal kernels or (h, w) of the spatial ones, rounds class).  (units, workgroups) come from af_conv_work_units, which
     answers for 256 CUs where there is no device."""
     import ctypes as C
-    import importlib.util
-    from af_mi355x import engine
+    import plan_cases
     from af_mi355x._lib import lib
-    spec_ = importlib.util.spec_from_file_location("test_hip_conv_persist", os.path.join(ROOT, "tests", "test_hip_conv_persist.py"))
-    matrix = importlib.util.module_from_spec(spec_)
-    spec_.loader.exec_module(matrix)
+    matrix = _load_tests_module("test_hip_conv_persist")
     covered = {matrix.case_key(c, dt) for c in matrix.CASES for dt in c.dtypes if c.form != "nonfinite"}
     monkeypatch.delenv("AF_FORCE_VAR", raising=False)
-    specs = {"i3d_r50": arch.i3d_r50_spec(), "slowfast_r50": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
-    rgb3 = {"i3d_r50": {specs["i3d_r50"].stem.conv}, "slowfast_r50": {specs["slowfast_r50"].stems[0].conv}, "ftcn_tt": set()}
     shipped = {}
-    for fusions in (True, False):
-        for name in ("AF_FUSE_BC", "AF_FUSE_CA", "AF_FUSE_CPA", "AF_FUSE_ABC"):
-            if fusions:
-                monkeypatch.delenv(name, raising=False)
-            else:
-                monkeypatch.setenv(name, "0")
-        for net, spec in specs.items():
-            for dtype in ("f32", "bf16", "f16"):
-                for batch in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32):
-                    p = engine.plan_network(spec, dtype, batch, (spec.num_frames, spec.crop, spec.crop), rgb3[net] if dtype != "f32" else set())
-                    for e in p.entries:
-                        if e["kind"] != "conv":
-                            continue
-                        cv = e["cv"]
-                        d = p.desc(cv, e["din"], e["dout"], int(e.get("tpool") or 0))
-                        v = lib.af_conv_variant(C.byref(d), None)
-                        if v not in (8, 11, 13):
-                            continue
-                        units, groups = C.c_int64(0), C.c_int(0)
-                        assert lib.af_conv_work_units(C.byref(d), None, C.byref(units), C.byref(groups)) == v
-                        assert 0 < groups.value <= 256 and groups.value == min(units.value, 256)
-                        key = (v, dtype, cv.cout, tuple(cv.kernel), matrix.kslabs(cv.cin, dtype), d.t if cv.kernel[1] == 1 else (d.h, d.w),
-                               matrix.rounds_class(units.value, groups.value))
-                        shipped.setdefault(key, "%s batch %d%s: %d -> %d %s, %d units on %d workgroups" % (
-                            net, batch, "" if fusions else " unfused", cv.cin, cv.cout, tuple(cv.kernel), units.value, groups.value))
+    for net, dtype, batch, setting, p in plan_cases.plans(monkeypatch, [{}, plan_cases.UNFUSED]):
+        for launch in p.launches:
+            if launch.kind != "conv":
+                continue
+            cv, (d,) = launch.convs["conv"], launch.descs
+            v = lib.af_conv_variant(C.byref(d), None)
+            if v not in (8, 11, 13):
+                continue
+            units, groups = C.c_int64(0), C.c_int(0)
+            assert lib.af_conv_work_units(C.byref(d), None, C.byref(units), C.byref(groups)) == v
+            assert 0 < groups.value <= 256 and groups.value == min(units.value, 256)
+            key = (v, dtype, cv.cout, tuple(cv.kernel), matrix.kslabs(cv.cin, dtype), d.t if cv.kernel[1] == 1 else (d.h, d.w),
+                   matrix.rounds_class(units.value, groups.value))
+            shipped.setdefault(key, "%s batch %d%s: %d -> %d %s, %d units on %d workgroups" % (
+                net, batch, setting, cv.cin, cv.cout, tuple(cv.kernel), units.value, groups.value))
     assert len(shipped) >= 60, len(shipped)
     missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
     assert not missing, "%d shipped persistent-kernel launches without a case:\n%s" % (len(missing), "\n".join(missing))
@@ -860,68 +862,52 @@ def test_fused_matrix_covers_what_ships(monkeypatch):
     af_conv_ca_work_units / af_conv_cpa_work_units / af_block_abc_work_units, which answer for 256 CUs where there is no device."""
     import collections
     import ctypes as C
-    import importlib.util
-    import sys
-    from af_mi355x import engine
-    from af_mi355x._lib import lib
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     import hip_helpers as hh
-    spec_ = importlib.util.spec_from_file_location("test_hip_conv_fused", os.path.join(ROOT, "tests", "test_hip_conv_fused.py"))
-    matrix = importlib.util.module_from_spec(spec_)
-    spec_.loader.exec_module(matrix)
+    import plan_cases
+    from af_mi355x._lib import lib
+    matrix = _load_tests_module("test_hip_conv_fused")
     covered = {matrix.case_key(c, dt) for c in matrix.CASES for dt in c.dtypes}
     for name in ("AF_FORCE_VAR", "AF_ABC_INNER32"):
         monkeypatch.delenv(name, raising=False)
-    specs = {"i3d_r50": arch.i3d_r50_spec(), "slowfast_r50": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
-    rgb3 = {"i3d_r50": {specs["i3d_r50"].stem.conv}, "slowfast_r50": {specs["slowfast_r50"].stems[0].conv}, "ftcn_tt": set()}
-    ref = lambda d: None if d is None else C.byref(d)
+    ref = C.byref
     shipped, kinds = {}, collections.Counter()
-    for switch in (None, "AF_FUSE_CPA", "AF_FUSE_BC"):
-        for name in ("AF_FUSE_BC", "AF_FUSE_CA", "AF_FUSE_CPA", "AF_FUSE_ABC"):
-            monkeypatch.delenv(name, raising=False)
-        if switch:
-            monkeypatch.setenv(switch, "1")
-        for net, spec in specs.items():
-            for dtype in ("bf16", "f16"):
-                for batch in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32):
-                    p = engine.plan_network(spec, dtype, batch, (spec.num_frames, spec.crop, spec.crop), rgb3[net])
-                    for e in p.entries:
-                        kind = e["kind"]
-                        if kind not in ("ca", "cpa", "abc", "bc"):
-                            continue
-                        cv, cv2 = e["cv"], e["cv2"]
-                        if kind == "ca":
-                            cv1 = e.get("cv3")
-                            dc, da = p.desc(cv, e["din"], e["dout"]), p.desc(cv2, e["dout"], cv2.out_dims(*e["dout"]))
-                            d1 = None if cv1 is None else p.desc(cv1, e["din3"], e["dout"])
-                            tiles, groups, form, pix = C.c_int64(0), C.c_int(0), C.c_int(-1), C.c_int(0)
-                            assert lib.af_conv_ca_work_units(ref(dc), ref(d1), ref(da), ref(tiles), ref(groups), ref(form), ref(pix)) == 1
-                            assert groups.value == 256 and pix.value * dc.t == 256 and (form.value == 2) == (cv1 is not None)
-                            key = ("ca", hh.CA_FORMS[form.value], dtype, dc.t, cv.cout // 64, matrix.rounds_class(tiles.value, groups.value))
-                            what = "%d -> %d -> %d, %d tiles on %d workgroups" % (cv.cin, cv.cout, cv2.cout, tiles.value, groups.value)
-                        elif kind == "cpa":
-                            dp = (e["dout"][0] // 2,) + tuple(e["dout"][1:])
-                            dc, da = p.desc(cv, e["din"], e["dout"], 1), p.desc(cv2, dp, cv2.out_dims(*dp))
-                            tiles, groups = C.c_int64(0), C.c_int(0)
-                            assert lib.af_conv_cpa_work_units(ref(dc), ref(da), e["x_sub"], ref(tiles), ref(groups)) == 1
-                            assert groups.value == 256
-                            key = ("cpa", dtype, cv.cout // 64, e["x_sub"], matrix.rounds_class(tiles.value, groups.value))
-                            what = "%d -> %d -> %d, %d tiles on %d workgroups" % (cv.cin, cv.cout, cv2.cout, tiles.value, groups.value)
-                        elif kind == "abc":
-                            d, cv3, cv4 = e["din"], e["cv3"], e.get("cv4")
-                            ds = [p.desc(c_, d, d) for c_ in (cv, cv2, cv3)] + [None if cv4 is None else p.desc(cv4, d, d)]
-                            rows, seg, units = C.c_int(0), C.c_int(0), C.c_int64(0)
-                            assert lib.af_block_abc_work_units(*(ref(x) for x in ds), ref(rows), ref(seg), ref(units)) == 1
-                            assert units.value == batch * -(-d[1] // rows.value) * -(-d[2] // 14) * seg.value
-                            key = ("abc", cv.cout, cv.kernel[0], cv4 is not None, dtype, rows.value, seg.value)
-                            what = "%d -> %d, %s frames of %d x %d, %d units" % (cv.cin, cv3.cout, d[0], d[1], d[2], units.value)
-                        else:
-                            db, dc = p.desc(cv, e["din"], e["dmid"]), p.desc(cv2, e["dmid"], e["dout"])
-                            assert lib.af_conv_bc_fusable(ref(db), ref(dc)) == 1
-                            key = ("bc", dtype, cv.cin, cv.cout, cv2.cout, (db.h, db.w))
-                            what = "%d -> %d -> %d" % (cv.cin, cv.cout, cv2.cout)
-                        kinds[kind] += 1
-                        shipped.setdefault(key, "%s batch %d%s: %s" % (net, batch, " with %s=1" % switch if switch else "", what))
+    settings = [{}, {"AF_FUSE_CPA": "1"}, {"AF_FUSE_BC": "1"}]
+    for net, dtype, batch, setting, p in plan_cases.plans(monkeypatch, settings, dtypes=("bf16", "f16")):
+        for launch in p.launches:
+            kind, convs = launch.kind, launch.convs
+            if kind == "ca":
+                cv, cv1, cv2 = convs["c"], convs["branch1"], convs["a_next"]
+                dc = launch.descs[0]
+                tiles, groups, form, pix = C.c_int64(0), C.c_int(0), C.c_int(-1), C.c_int(0)
+                assert lib.af_conv_ca_work_units(*launch.refs(), ref(tiles), ref(groups), ref(form), ref(pix)) == 1
+                assert groups.value == 256 and pix.value * dc.t == 256 and (form.value == 2) == (cv1 is not None)
+                key = ("ca", hh.CA_FORMS[form.value], dtype, dc.t, cv.cout // 64, matrix.rounds_class(tiles.value, groups.value))
+                what = "%d -> %d -> %d, %d tiles on %d workgroups" % (cv.cin, cv.cout, cv2.cout, tiles.value, groups.value)
+            elif kind == "cpa":
+                cv, cv2 = convs["c"], convs["a_next"]
+                tiles, groups = C.c_int64(0), C.c_int(0)
+                assert lib.af_conv_cpa_work_units(*launch.refs(), launch.x_sub, ref(tiles), ref(groups)) == 1
+                assert groups.value == 256
+                key = ("cpa", dtype, cv.cout // 64, launch.x_sub, matrix.rounds_class(tiles.value, groups.value))
+                what = "%d -> %d -> %d, %d tiles on %d workgroups" % (cv.cin, cv.cout, cv2.cout, tiles.value, groups.value)
+            elif kind == "abc":
+                cv, cv3, cv4 = convs["a"], convs["c"], convs["branch1"]
+                d = (launch.descs[0].t, launch.descs[0].h, launch.descs[0].w)
+                rows, seg, units = C.c_int(0), C.c_int(0), C.c_int64(0)
+                assert lib.af_block_abc_work_units(*launch.refs(), ref(rows), ref(seg), ref(units)) == 1
+                assert units.value == batch * -(-d[1] // rows.value) * -(-d[2] // 14) * seg.value
+                key = ("abc", cv.cout, cv.kernel[0], cv4 is not None, dtype, rows.value, seg.value)
+                what = "%d -> %d, %s frames of %d x %d, %d units" % (cv.cin, cv3.cout, d[0], d[1], d[2], units.value)
+            elif kind == "bc":
+                cv, cv2 = convs["b"], convs["c"]
+                db = launch.descs[0]
+                assert lib.af_conv_bc_fusable(*launch.refs()) == 1
+                key = ("bc", dtype, cv.cin, cv.cout, cv2.cout, (db.h, db.w))
+                what = "%d -> %d -> %d" % (cv.cin, cv.cout, cv2.cout)
+            else:
+                continue
+            kinds[kind] += 1
+            shipped.setdefault(key, "%s batch %d%s: %s" % (net, batch, setting, what))
     # today 40 keys: 8 ca (plain-CWL and projection, T = 32, 4 slabs, classes "4-5" and ">5"), 4 cpa, 24 abc, 4 bc
     assert len(shipped) >= 40 and all(kinds[k] for k in ("ca", "cpa", "abc", "bc")), (len(shipped), kinds)
     missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
@@ -937,58 +923,37 @@ def test_conv111_and_small_matrices_cover_what_ships(monkeypatch):
     256 CUs where there is no device.  conv_small: key = (dtype, cin, cout, kernel, stride, second segment, residual,
     out_ld != cout, M > 2 097 152: the grid-stride loop runs twice)."""
     import ctypes as C
-    import importlib.util
-    from af_mi355x import engine
+    import plan_cases
     from af_mi355x._lib import lib
-
-    def load(name):
-        spec_ = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
-        module = importlib.util.module_from_spec(spec_)
-        spec_.loader.exec_module(module)
-        return module
-
-    m111, msmall = load("test_hip_conv111"), load("test_hip_conv_small")
+    m111, msmall = _load_tests_module("test_hip_conv111"), _load_tests_module("test_hip_conv_small")
     covered111 = set().union(*(m111.case_keys(c, dt) for c in m111.CASES for dt in m111.DT16 if c.form != "nonfinite"))
     covered_small = {msmall.case_key(c, dt) for c in msmall.CASES for dt in msmall.DT16 if c.form != "nonfinite" and c.variant == 9}
     monkeypatch.delenv("AF_FORCE_VAR", raising=False)
-    specs = {"i3d_r50": arch.i3d_r50_spec(), "slowfast_r50": arch.slowfast_r50_spec(), "ftcn_tt": arch.ftcn_tt_spec()}
-    rgb3 = {"i3d_r50": {specs["i3d_r50"].stem.conv}, "slowfast_r50": {specs["slowfast_r50"].stems[0].conv}, "ftcn_tt": set()}
     shipped111, shipped_small = {}, {}
-    for fusions in (True, False):
-        for name in ("AF_FUSE_BC", "AF_FUSE_CA", "AF_FUSE_CPA", "AF_FUSE_ABC"):
-            if fusions:
-                monkeypatch.delenv(name, raising=False)
-            else:
-                monkeypatch.setenv(name, "0")
-        for net, spec in specs.items():
-            for dtype in ("f32", "bf16", "f16"):
-                for batch in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32):
-                    p = engine.plan_network(spec, dtype, batch, (spec.num_frames, spec.crop, spec.crop), rgb3[net] if dtype != "f32" else set())
-                    for e in p.entries:
-                        if e["kind"] not in ("conv", "dual"):
-                            continue
-                        cv, dual, tpool = e["cv"], e["kind"] == "dual", int(e.get("tpool") or 0)
-                        d = p.desc(cv, e["din"], e["dout"], tpool)
-                        d2 = C.byref(p.desc(e["cv2"], e["din2"], e["dout"])) if dual else None
-                        v = lib.af_conv_variant(C.byref(d), d2)
-                        if v not in (9, 10):
-                            continue
-                        assert dtype != "f32"
-                        cin2, res, ld = e["cv2"].cin if dual else 0, e.get("res") is not None, e.get("ld", cv.cout) != cv.cout
-                        where = "%s batch %d%s: %d%s -> %d %s" % (net, batch, "" if fusions else " unfused", cv.cin, " + %d" % cin2 if dual else "",
-                                                                   cv.cout, tuple(cv.kernel))
-                        if v == 9:
-                            m = d.n * d.to * d.ho * d.wo
-                            key = msmall.shipped_key(dtype, cv.cin, cv.cout, cv.kernel, cv.stride, dual, res, ld, m)
-                            shipped_small.setdefault(key, "%s stride %s, %d positions" % (where, tuple(cv.stride), m))
-                            continue
-                        tiles, groups = C.c_int64(0), C.c_int(0)
-                        assert lib.af_conv_work_units(C.byref(d), d2, C.byref(tiles), C.byref(groups)) == 10
-                        ncol = cv.cout // 256
-                        assert 0 < groups.value <= 256 and groups.value == 256 // ncol * ncol and tiles.value >= 4 * groups.value // ncol
-                        for residue in m111.residues_of(tiles.value, groups.value, cv.cin, cv.cout):
-                            key = m111.shipped_key(dtype, cv.cin, cin2, cv.cout, tpool, res, ld, residue)
-                            shipped111.setdefault(key, "%s, %d tiles on %d workgroups" % (where, tiles.value, groups.value))
+    for net, dtype, batch, setting, p in plan_cases.plans(monkeypatch, [{}, plan_cases.UNFUSED]):
+        for launch in p.launches:
+            if launch.kind not in ("conv", "dual"):
+                continue
+            cv, cv2 = _main_and_shortcut(launch)
+            dual, refs, d = cv2 is not None, (launch.refs() + [None])[:2], launch.descs[0]
+            v = lib.af_conv_variant(*refs)
+            if v not in (9, 10):
+                continue
+            assert dtype != "f32"
+            cin2, res, ld = cv2.cin if dual else 0, launch.res is not None, launch.ld != cv.cout
+            where = "%s batch %d%s: %d%s -> %d %s" % (net, batch, setting, cv.cin, " + %d" % cin2 if dual else "", cv.cout, tuple(cv.kernel))
+            if v == 9:
+                m = d.n * d.to * d.ho * d.wo
+                key = msmall.shipped_key(dtype, cv.cin, cv.cout, cv.kernel, cv.stride, dual, res, ld, m)
+                shipped_small.setdefault(key, "%s stride %s, %d positions" % (where, tuple(cv.stride), m))
+                continue
+            tiles, groups = C.c_int64(0), C.c_int(0)
+            assert lib.af_conv_work_units(*refs, C.byref(tiles), C.byref(groups)) == 10
+            ncol = cv.cout // 256
+            assert 0 < groups.value <= 256 and groups.value == 256 // ncol * ncol and tiles.value >= 4 * groups.value // ncol
+            for residue in m111.residues_of(tiles.value, groups.value, cv.cin, cv.cout):
+                key = m111.shipped_key(dtype, cv.cin, cin2, cv.cout, launch.tpool, res, ld, residue)
+                shipped111.setdefault(key, "%s, %d tiles on %d workgroups" % (where, tiles.value, groups.value))
     # today 34 conv111 keys (17 per dtype: K = 128 with all four residues, and three of them with out_ld) and 24 conv_small keys (the
     # eight shapes, four of them also beyond the launch cap)
     assert len(shipped111) >= 34 and len(shipped_small) >= 24, (len(shipped111), len(shipped_small))
