@@ -442,6 +442,33 @@ int af_dual_video_reduce(const float* logits, const int32_t* nvalid, int clips, 
                          float* video_prob, float* clip_prob, double* track_score, int32_t* track_pred, double* video_score,
                          int32_t* video_pred, int32_t* track_count, void* stream);
 
+/* ---- cli/test.py's LMKDisc path: landmarks alone, ragged clips, the mouth-line rotation, noisy-OR ---- */
+
+#define AF_DUALV_PAD_FIXT 0         /* VideoDataset._fixT: what af_dual_clip_features does                         */
+#define AF_DUALV_PAD_ZERO 1         /* vox_ds.collate_pad: the nvalid surviving rows, then T - nvalid rows of +0.0 */
+
+/* af_dual_clip_features with two options and an optional A.  rot_invariant = 1 is make_lmk_features.py's --rot-invariant
+ * (_frame_to_features / _rotate_to_mouth), applied to every surviving frame before padding and z-score: with (x, y) a normalised
+ * point and dx, dy = mr_c - ml_c in fp32, c = dx / h and s = -dy / h, h = sqrt(dx dx + dy dy), evaluated in fp64 and rounded to
+ * fp32 once (c = 1, s = 0 when dx = dy = 0); x' = fl(fl(x c) + fl(y (-s))), y' = fl(fl(x s) + fl(y c)).  A == NULL: landmarks
+ * alone; au_k, the delta flags, the AU statistics and the tracks' au pointers are not read.  AF_DUALV_PAD_ZERO needs A == NULL and
+ * AF_DUALV_ZSCORE_NONE; a clip longer than T is then a bad record (nvalid 0, zeros).  rot_invariant = 0 with AF_DUALV_PAD_FIXT
+ * and A given equals af_dual_clip_features bit for bit.  Arithmetic and its order: tests/lmkdisc_ref.py. */
+int af_dual_clip_features_ex(const af_dualv_track* tracks, int n_tracks, const af_dualv_clip* clips, int n_clips,
+                             const af_dualv_opts* opts, int rot_invariant, int pad_mode, float* A, float* L, int32_t* nvalid,
+                             void* stream);
+
+/* cli/test.py:86-94, 205-256 on clip logits, ONE launch (grid = videos), the CSR of af_dual_video_reduce (every track is its own
+ * entry: test.py keys by track path).  clip_score [clips] (fp64) = sigmoid(logit) as af_dual_video_reduce defines it, or
+ * 1.0 - it with invert, for every clip the CSR names; track_score [tracks] = np.median of the scores of its clips with
+ * nvalid > 0 (the midpoint on an even count), track_pred = score >= thresh, track_count = clips used (a track with none: score
+ * 0, pred 0, and it is skipped); video_score [videos] = 1 - exp(sum_t log1p(-clip(track_score_t, 1e-6, 1 - 1e-6))), summed in
+ * CSR order in fp64, 0.0 for a video left with no track; video_pred = score >= thresh; video_count [videos] = tracks used. */
+int af_lmk_video_reduce(const float* logits, const int32_t* nvalid, int clips, const int32_t* video_tracks, int videos,
+                        const int32_t* track_clips, int tracks, const int32_t* clip_index, int invert, double thresh,
+                        double* clip_score, double* track_score, int32_t* track_pred, int32_t* track_count, double* video_score,
+                        int32_t* video_pred, int32_t* video_count, void* stream);
+
 /* ---- clip aligner --------------------------------------------------- */
 
 /* Replaces the per-frame loop of FasterCropAlignXRay.__call__ / process_single

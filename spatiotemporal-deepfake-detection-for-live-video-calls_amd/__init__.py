@@ -21,9 +21,12 @@ def __getattr__(name):
     if name == "TilePicker":
         from . import tile_picker
         return tile_picker.TilePicker
-    if name in ("DualVideoScorer", "DualTrack"):
+    if name in ("DualVideoScorer", "LmkVideoScorer", "DualTrack"):
         from . import dual_video
         return getattr(dual_video, name)
+    if name == "LMKDisc":
+        from . import dualrun
+        return dualrun.LMKDisc
     if name == "ByteTracker":
         from . import tracker
         return tracker.ByteTracker

@@ -195,6 +195,7 @@ DUALV_FAMILY_FUSION, DUALV_FAMILY_BEST = 0, 1
 DUALV_TRACK = {"median": 0, "mean": 1}
 DUALV_VIDEO = {"max": 0, "median": 1, "mean": 2}
 DUALV_BEST = {"track_mean": 0, "track_median": 1, "track_majority": 2}
+DUALV_PAD_FIXT, DUALV_PAD_ZERO = 0, 1
 
 
 class PoolDesc(C.Structure):
@@ -364,6 +365,9 @@ ABI = {
     "af_dual_clip_features": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(DualvOpts)] + [C.c_void_p] * 4),
     "af_dual_video_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 11),
+    "af_dual_clip_features_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(DualvOpts), C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "af_lmk_video_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_int, C.c_double] + [C.c_void_p] * 8),
     "af_warp_affine_clip_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int,
                                          C.c_void_p, C.c_void_p]),
     "af_dual_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

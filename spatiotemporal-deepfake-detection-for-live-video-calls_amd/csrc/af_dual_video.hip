@@ -3,7 +3,8 @@
 // af_dual_clip_features - one workgroup per clip, per clip in the reference's order:
 //   landmarks  dualrun/data/make_lmk_features.py:39-52, 152-187: the 66 KEY_LANDMARKS_IDXS points (the last three are the nose tip 1
 //              and the mouth corners 78, 308) minus the nose; scale = ||ml - mr||; a frame whose scale is not finite or < 1e-8 is
-//              dropped and the survivors compacted in order; divided by scale + 1e-6.  rot_invariant is not built.
+//              dropped and the survivors compacted in order; divided by scale + 1e-6.  rot_invariant (:145-150, 173-176), collate_pad's
+//              zero rows (data/vox_ds.py:19-26) and landmarks without AUs: af_dual_clip_features_ex, statement tests/lmkdisc_ref.py.
 //   AUs        dualrun/data/make_au_features.py:41-53: X | diff(X, prepend=X[:1]) | the same of that, along the feature axis.
 //   fixT       dualrun/rgb/fusion.py:331-336, per modality on its own row count: more rows than T keep the centred T, fewer repeat
 //              the last row.
@@ -19,7 +20,7 @@
 //
 // af_dual_video_reduce - one workgroup per video: fusion.track_reduce / agg_video (fusion.py:118-130) on logits, or
 // cli/best.py:518-591 aggregate_video_predictions on sigmoid(logit).  Medians by rank count (exact, order-free), means sequential
-// in input order.  No atomics in either kernel.
+// in input order.  af_lmk_video_reduce - the same kernel on cli/test.py's rule: fp64 scores, np.median, noisy-OR.  No atomics anywhere.
 //
 // No stray access.  features: a clip record is used only if 0 <= track < n_tracks, 1 <= len <= 16, first >= 0, first + len <= n,
 // lmk_pitch >= 934, au_pitch >= K; reads are then rows first..first+len-1 of the track, floats < 934 (landmark index <= 466) and
@@ -86,16 +87,36 @@ __device__ __forceinline__ void dv_normalize(float* v, int T, int mode, bool app
     for (int t = 0; t < AF_DUALV_MAX_T; ++t) if (t < T) v[t] = dv_nan_to_num(v[t]);
 }
 
+// the mouth-line rotation of one surviving frame (make_lmk_features._rotate_to_mouth): c = cos(-theta), s = sin(-theta) with theta the
+// angle of mr_c - ml_c, stated as dx / h and -dy / h, h = sqrt(dx dx + dy dy), in fp64 (products exact, one rounding each for the sum, the
+// root and the quotients) and rounded to fp32 once; dx = dy = 0 is theta = 0
+__device__ __forceinline__ void dv_mouth_rotation(const float* p, float div, float* c, float* s) {
+    const float nx = p[2 * DV_NOSE], ny = p[2 * DV_NOSE + 1];
+    const float mlx = (p[2 * DV_ML] - nx) / div, mly = (p[2 * DV_ML + 1] - ny) / div;
+    const float mrx = (p[2 * DV_MR] - nx) / div, mry = (p[2 * DV_MR + 1] - ny) / div;
+    const float dx = mrx - mlx, dy = mry - mly;
+    if (dx == 0.f && dy == 0.f) { *c = 1.f; *s = 0.f; return; }
+    const double h = sqrt((double)dx * (double)dx + (double)dy * (double)dy);
+    *c = (float)((double)dx / h);
+    *s = (float)(-(double)dy / h);
+}
+
+// EXT = false is af_dual_clip_features as it always was (rot and pad_zero are not read).  EXT = true adds what cli/test.py's path needs:
+// A == nullptr (landmarks alone, the tracks' au pointers are not read), the mouth-line rotation, and collate_pad's zero rows.
+template <bool EXT>
 __global__ __launch_bounds__(DV_THREADS) void dual_clip_features_kernel(const af_dualv_track* tracks, int n_tracks, const af_dualv_clip* clips,
-                                                                        af_dualv_opts o, float* A, float* L, int32_t* nvalid) {
+                                                                        af_dualv_opts o, float* A, float* L, int32_t* nvalid, int rot, int pad_zero) {
     extern __shared__ float sm[];                      // pts [16][132] raw key points | au [16][K] raw action units
     __shared__ float scale[AF_DUALV_MAX_T];            // scale + 1e-6 per frame
+    __shared__ float rot_c[AF_DUALV_MAX_T], rot_s[AF_DUALV_MAX_T];   // EXT: the rotation of each surviving frame
     __shared__ int order[AF_DUALV_MAX_T];              // surviving frames, compacted
     __shared__ int nv_s;
     float* pts = sm;
     float* au = sm + AF_DUALV_MAX_T * DV_LMK;
     const int tid = threadIdx.x, clip = blockIdx.x;
-    const int T = o.frames, K = o.au_k;
+    const bool has_au = !EXT || A != nullptr;
+    const bool rotate = EXT && rot != 0, zero_rows = EXT && pad_zero != 0;
+    const int T = o.frames, K = has_au ? o.au_k : 0;
     const int f_au = K * (1 + (o.use_delta ? 1 : 0) + (o.use_delta2 ? 1 : 0));
     float* Aout = A + (long long)clip * T * f_au;
     float* Lout = L + (long long)clip * T * DV_LMK;
@@ -105,7 +126,9 @@ __global__ __launch_bounds__(DV_THREADS) void dual_clip_features_kernel(const af
     af_dualv_track tr = {nullptr, nullptr, 0, 0, 0};
     if (ok) {
         tr = tracks[c.track];
-        ok = tr.lmk && tr.au && (long long)c.first + c.len <= tr.n && tr.lmk_pitch >= 2 * AF_DUALV_MIN_POINTS && tr.au_pitch >= K;
+        ok = tr.lmk && (long long)c.first + c.len <= tr.n && tr.lmk_pitch >= 2 * AF_DUALV_MIN_POINTS;
+        if (has_au) ok = ok && tr.au && tr.au_pitch >= K;
+        if (zero_rows) ok = ok && c.len <= T;          // collate_pad never shortens a clip: a longer one is a bad record
     }
     const int len = ok ? c.len : 0;
 
@@ -127,6 +150,7 @@ __global__ __launch_bounds__(DV_THREADS) void dual_clip_features_kernel(const af
             if (s - s == 0.f && !(s < 1e-8f)) {        // finite and >= 1e-8
                 order[nv] = l;
                 scale[nv] = s + 1e-6f;
+                if (rotate) dv_mouth_rotation(p, s + 1e-6f, &rot_c[nv], &rot_s[nv]);
                 ++nv;
             }
         }
@@ -136,7 +160,8 @@ __global__ __launch_bounds__(DV_THREADS) void dual_clip_features_kernel(const af
     __syncthreads();
     const int nv = nv_s;
     if (nv == 0) {                                      // nothing survived (or a bad record): zeros, excluded downstream
-        for (int i = tid; i < T * f_au; i += DV_THREADS) Aout[i] = 0.f;
+        if (has_au)
+            for (int i = tid; i < T * f_au; i += DV_THREADS) Aout[i] = 0.f;
         for (int i = tid; i < T * DV_LMK; i += DV_THREADS) Lout[i] = 0.f;
         return;
     }
@@ -148,9 +173,15 @@ __global__ __launch_bounds__(DV_THREADS) void dual_clip_features_kernel(const af
 #pragma unroll
         for (int t = 0; t < AF_DUALV_MAX_T; ++t) {
             v[t] = 0.f;
-            if (t < T) {
-                const int r = dv_fixt_row(t, nv, T), l = order[r];
-                v[t] = (pts[l * DV_LMK + j] - pts[l * DV_LMK + 2 * DV_NOSE + (j & 1)]) / scale[r];
+            if (t < T && !(zero_rows && t >= nv)) {    // collate_pad: rows nv .. T-1 stay +0
+                const int r = zero_rows ? t : dv_fixt_row(t, nv, T), l = order[r];
+                if (rotate) {
+                    const float* q = pts + l * DV_LMK;
+                    const float x = (q[j & ~1] - q[2 * DV_NOSE]) / scale[r], y = (q[j | 1] - q[2 * DV_NOSE + 1]) / scale[r];
+                    const float cc = rot_c[r], ss = rot_s[r];
+                    v[t] = (j & 1) ? x * ss + y * cc : x * cc + y * (-ss);            // points @ R.T, R = [[c, -s], [s, c]]
+                } else
+                    v[t] = (pts[l * DV_LMK + j] - pts[l * DV_LMK + 2 * DV_NOSE + (j & 1)]) / scale[r];
             }
         }
         dv_normalize(v, T, o.zscore_mode, o.zscore_apply != AF_DUALV_APPLY_AU, global ? o.lmk_mean[j] : 0.f, global ? o.lmk_std[j] : 1.f);
@@ -158,6 +189,7 @@ __global__ __launch_bounds__(DV_THREADS) void dual_clip_features_kernel(const af
         for (int t = 0; t < AF_DUALV_MAX_T; ++t) if (t < T) Lout[t * DV_LMK + j] = v[t];
     }
 
+    if (!has_au) return;
     for (int f = tid; f < f_au; f += DV_THREADS) {
         const int blk = f / K, k = f - blk * K;
         const int kind = blk == 0 ? 0 : (blk == 1 && o.use_delta ? 1 : 2);          // X, first difference, second difference
@@ -199,14 +231,19 @@ struct DvReduceArgs {
     int family, track_mode, video_mode; double thresh;
     float* track_logit; float* track_prob; float* video_logit; float* video_prob;
     float* clip_prob; double* track_score; int32_t* track_pred; double* video_score; int32_t* video_pred; int32_t* track_count;
+    int invert; double* clip_score; int32_t* video_count;           // the lmk family (cli/test.py)
 };
+
+// the lmk family lives behind af_lmk_video_reduce alone: cli/test.py:86-94, 205-256.  clip_score = sigmoid(logit) or 1 - it, in fp64;
+// track = np.median; video = noisy-OR, 1 - exp(sum log1p(-clip(p, 1e-6, 1 - 1e-6))), summed in CSR order.
+#define DV_FAMILY_LMK 2
 
 // the value clip entry e of a track contributes (its logit, or in the best family its probability, which phase 0 stored), and
 // whether it takes part
 __device__ __forceinline__ bool dv_entry(const DvReduceArgs& a, int e, double* val) {
     const int ci = a.clip_index[e];
     if (ci < 0 || ci >= a.clips || a.nvalid[ci] <= 0) return false;
-    *val = a.family == AF_DUALV_FAMILY_BEST ? (double)a.clip_prob[ci] : (double)a.logits[ci];
+    *val = a.family == DV_FAMILY_LMK ? a.clip_score[ci] : a.family == AF_DUALV_FAMILY_BEST ? (double)a.clip_prob[ci] : (double)a.logits[ci];
     return true;
 }
 
@@ -219,14 +256,18 @@ __global__ __launch_bounds__(DV_THREADS) void dual_video_reduce_kernel(DvReduceA
     int t0 = a.video_tracks[video], t1 = a.video_tracks[video + 1];
     t0 = t0 < 0 ? 0 : t0;
     t1 = t1 > a.tracks ? a.tracks : t1;
-    const bool best = a.family == AF_DUALV_FAMILY_BEST;
+    const bool lmk = a.family == DV_FAMILY_LMK;
+    const bool best = a.family == AF_DUALV_FAMILY_BEST || lmk;                         // fp64 scores, np.median, preds at thresh
     const bool median = best ? a.track_mode == AF_DUALV_BEST_TRACK_MEDIAN : a.track_mode == AF_DUALV_TRACK_MEDIAN;
 
     // phase 0 (best family): the clip probabilities, best.py's y_score_clip, once per clip
     if (best && t0 < t1) {
         for (int e = a.track_clips[t0] + tid; e < a.track_clips[t1]; e += DV_THREADS) {
             const int ci = a.clip_index[e];
-            if (ci >= 0 && ci < a.clips) a.clip_prob[ci] = dv_sigmoid(a.logits[ci]);
+            if (ci < 0 || ci >= a.clips) continue;
+            const float s = dv_sigmoid(a.logits[ci]);
+            if (lmk) a.clip_score[ci] = a.invert ? 1.0 - (double)s : (double)s;
+            else a.clip_prob[ci] = s;
         }
         __syncthreads();
     }
@@ -320,6 +361,24 @@ __global__ __launch_bounds__(DV_THREADS) void dual_video_reduce_kernel(DvReduceA
     __syncthreads();
 
     // phase 3: the video over its tracks that kept a clip
+    if (lmk) {
+        if (tid == 0) {
+            int n = 0;
+            double acc = 0.0;
+            for (int t = t0; t < t1; ++t) {
+                if (a.track_count[t] == 0) continue;
+                double p = a.track_score[t];
+                p = p < 1e-6 ? 1e-6 : (p > 1.0 - 1e-6 ? 1.0 - 1e-6 : p);               // np.clip: a NaN stays
+                acc = acc + log1p(-p);
+                ++n;
+            }
+            const double score = n ? 1.0 - exp(acc) : 0.0;                             // noisy_or([]) = 0
+            a.video_score[video] = score;
+            a.video_pred[video] = score >= a.thresh ? 1 : 0;
+            a.video_count[video] = n;
+        }
+        return;
+    }
     if (best) {
         if (tid == 0) {
             bool any = false, fake = false;
@@ -394,9 +453,40 @@ extern "C" int af_dual_clip_features(const af_dualv_track* tracks, int n_tracks,
     if (n_clips == 0) return AF_OK;
     AF_REQUIRE(tracks && clips && A && L && nvalid && n_tracks >= 1, "dual_clip_features: null argument");
     const size_t lds = (size_t)AF_DUALV_MAX_T * (DV_LMK + o.au_k) * sizeof(float);
-    hipLaunchKernelGGL(dual_clip_features_kernel, dim3(n_clips), dim3(DV_THREADS), lds, (hipStream_t)stream, tracks, n_tracks, clips, o, A, L,
-                       nvalid);
+    hipLaunchKernelGGL(dual_clip_features_kernel<false>, dim3(n_clips), dim3(DV_THREADS), lds, (hipStream_t)stream, tracks, n_tracks, clips, o, A,
+                       L, nvalid, 0, 0);
     AF_CHECK_LAUNCH("dual_clip_features_kernel");
+    return AF_OK;
+}
+
+extern "C" int af_dual_clip_features_ex(const af_dualv_track* tracks, int n_tracks, const af_dualv_clip* clips, int n_clips,
+                                        const af_dualv_opts* opts, int rot_invariant, int pad_mode, float* A, float* L, int32_t* nvalid,
+                                        void* stream) {
+    using namespace af;
+    AF_REQUIRE(opts, "dual_clip_features_ex: null options");
+    af_dualv_opts o = *opts;
+    AF_REQUIRE(n_clips >= 0 && n_tracks >= 0, "dual_clip_features_ex: negative count");
+    AF_REQUIRE(o.frames >= 1 && o.frames <= AF_DUALV_MAX_T, "dual_clip_features_ex: 1..%d frames per clip (got %d)", AF_DUALV_MAX_T, o.frames);
+    AF_REQUIRE(pad_mode == AF_DUALV_PAD_FIXT || pad_mode == AF_DUALV_PAD_ZERO, "dual_clip_features_ex: pad_mode %d", pad_mode);
+    AF_REQUIRE(rot_invariant == 0 || rot_invariant == 1, "dual_clip_features_ex: rot_invariant %d", rot_invariant);
+    AF_REQUIRE(o.zscore_mode >= AF_DUALV_ZSCORE_NONE && o.zscore_mode <= AF_DUALV_ZSCORE_GLOBAL, "dual_clip_features_ex: zscore_mode %d", o.zscore_mode);
+    AF_REQUIRE(o.zscore_apply >= AF_DUALV_APPLY_BOTH && o.zscore_apply <= AF_DUALV_APPLY_LMK, "dual_clip_features_ex: zscore_apply %d", o.zscore_apply);
+    if (A) {
+        const int mult = 1 + (o.use_delta ? 1 : 0) + (o.use_delta2 ? 1 : 0);
+        AF_REQUIRE(o.au_k >= 1 && (long long)o.au_k * mult <= 256, "dual_clip_features_ex: 1..256 AU features (got %d x %d)", o.au_k, mult);
+    } else {
+        o.au_k = 0;                                     // landmarks alone: no AU row is read, no A is written
+    }
+    AF_REQUIRE(pad_mode == AF_DUALV_PAD_FIXT || (!A && o.zscore_mode == AF_DUALV_ZSCORE_NONE),
+               "dual_clip_features_ex: zero padding is cli/test.py's form: landmarks alone (A null) and no z-score");
+    AF_REQUIRE(o.zscore_mode != AF_DUALV_ZSCORE_GLOBAL || (o.lmk_mean && o.lmk_std && (!A || (o.au_mean && o.au_std))),
+               "dual_clip_features_ex: global z-score needs its stat vectors");
+    if (n_clips == 0) return AF_OK;
+    AF_REQUIRE(tracks && clips && L && nvalid && n_tracks >= 1, "dual_clip_features_ex: null argument");
+    const size_t lds = (size_t)AF_DUALV_MAX_T * (DV_LMK + o.au_k) * sizeof(float);
+    hipLaunchKernelGGL(dual_clip_features_kernel<true>, dim3(n_clips), dim3(DV_THREADS), lds, (hipStream_t)stream, tracks, n_tracks, clips, o, A,
+                       L, nvalid, rot_invariant, pad_mode == AF_DUALV_PAD_ZERO ? 1 : 0);
+    AF_CHECK_LAUNCH("dual_clip_features_kernel<ext>");
     return AF_OK;
 }
 
@@ -421,8 +511,28 @@ extern "C" int af_dual_video_reduce(const float* logits, const int32_t* nvalid, 
     else
         AF_REQUIRE(clip_prob && track_score && track_pred && video_score && video_pred, "dual_video_reduce: null best output");
     DvReduceArgs a = {logits, nvalid, clips, video_tracks, track_clips, tracks, clip_index, family, track_mode, video_mode, prob_thresh,
-                      track_logit, track_prob, video_logit, video_prob, clip_prob, track_score, track_pred, video_score, video_pred, track_count};
+                      track_logit, track_prob, video_logit, video_prob, clip_prob, track_score, track_pred, video_score, video_pred, track_count,
+                      0, nullptr, nullptr};
     hipLaunchKernelGGL(dual_video_reduce_kernel, dim3(videos), dim3(DV_THREADS), 0, (hipStream_t)stream, a);
     AF_CHECK_LAUNCH("dual_video_reduce_kernel");
+    return AF_OK;
+}
+
+extern "C" int af_lmk_video_reduce(const float* logits, const int32_t* nvalid, int clips, const int32_t* video_tracks, int videos,
+                                   const int32_t* track_clips, int tracks, const int32_t* clip_index, int invert, double thresh,
+                                   double* clip_score, double* track_score, int32_t* track_pred, int32_t* track_count,
+                                   double* video_score, int32_t* video_pred, int32_t* video_count, void* stream) {
+    using namespace af;
+    AF_REQUIRE(videos >= 0 && tracks >= 0 && clips >= 0, "lmk_video_reduce: negative count");
+    AF_REQUIRE(invert == 0 || invert == 1, "lmk_video_reduce: invert %d", invert);
+    if (videos == 0) return AF_OK;
+    AF_REQUIRE(video_tracks && track_clips && track_count && (clips == 0 || (logits && nvalid && clip_index && clip_score)),
+               "lmk_video_reduce: null argument");
+    AF_REQUIRE(track_score && track_pred && video_score && video_pred && video_count, "lmk_video_reduce: null output");
+    DvReduceArgs a = {logits, nvalid, clips, video_tracks, track_clips, tracks, clip_index, DV_FAMILY_LMK, AF_DUALV_BEST_TRACK_MEDIAN, 0, thresh,
+                      nullptr, nullptr, nullptr, nullptr, nullptr, track_score, track_pred, video_score, video_pred, track_count,
+                      invert, clip_score, video_count};
+    hipLaunchKernelGGL(dual_video_reduce_kernel, dim3(videos), dim3(DV_THREADS), 0, (hipStream_t)stream, a);
+    AF_CHECK_LAUNCH("dual_video_reduce_kernel<lmk>");
     return AF_OK;
 }

@@ -10,6 +10,7 @@ LayerNorm -> Linear -> GELU -> Linear.  Both branches are ONE HIP kernel launch 
 activations never leave LDS, weights streamed from L2 in a pre-transposed flat buffer), the head a second tiny kernel:
 csrc/af_dual.hip.  The module below only owns the parameters (same ``state_dict`` keys as the reference, 136 of them,
 including the auxiliary heads that inference never evaluates) and the launch plumbing - no CPU / eager fallback.
+``LMKDisc`` (cli/test.py:34-57) is the same launch with the landmark branch alone and a d_model-wide head.
 """
 import ctypes as C
 import math
@@ -33,9 +34,10 @@ class DualSpec:
     ff: int = 768                  # dim_feedforward = int(d_model * mlp_ratio), mlp_ratio = ff_dim / d_model (run.py:175)
     pool_tau: float = 1.0
     proj_dim: int = 128
+    lmk_only: bool = False         # the one-branch spec of ``LMKDisc``: the landmark encoder alone (au_dim is not used)
 
     def branches(self) -> List[Tuple[str, int]]:
-        return [("au_enc", self.au_dim), ("lmk_enc", self.lmk_dim)]
+        return ([] if self.lmk_only else [("au_enc", self.au_dim)]) + [("lmk_enc", self.lmk_dim)]
 
 
 def dual_state_dict_layout(spec: DualSpec):
@@ -66,13 +68,11 @@ def dual_state_dict_layout(spec: DualSpec):
     return out
 
 
-def dual_synthetic_state_dict(spec: DualSpec = None, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
-    """Seeded recipe weights in the reference layout (the trained ``best.pt`` files are not shipped: SURVEY 8c):
-    matrices N(0, 1/fan_in), LayerNorm gamma 1 + 0.1 N(0,1), every bias 0.05 N(0,1), pooling vector N(0,1)."""
-    spec = spec or DualSpec()
+def _recipe_state_dict(layout, stream: int) -> "OrderedDict[str, torch.Tensor]":
+    """the W(seed) recipe on a [(key, shape)] layout: entry idx draws from generator (stream, idx)"""
     sd = OrderedDict()
-    for idx, (key, shape) in enumerate(dual_state_dict_layout(spec)):
-        g = _gen(seed + 7000, idx)
+    for idx, (key, shape) in enumerate(layout):
+        g = _gen(stream, idx)
         leaf = key.rsplit(".", 1)[-1]
         if len(shape) >= 2:
             fan_in = 1
@@ -87,6 +87,12 @@ def dual_synthetic_state_dict(spec: DualSpec = None, seed: int = 0) -> "OrderedD
             t = 0.05 * torch.randn(shape, generator=g)
         sd[key] = t.contiguous()
     return sd
+
+
+def dual_synthetic_state_dict(spec: DualSpec = None, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded recipe weights in the reference layout (the trained ``best.pt`` files are not shipped: SURVEY 8c):
+    matrices N(0, 1/fan_in), LayerNorm gamma 1 + 0.1 N(0,1), every bias 0.05 N(0,1), pooling vector N(0,1)."""
+    return _recipe_state_dict(dual_state_dict_layout(spec or DualSpec()), seed + 7000)
 
 
 def synthetic_dual_inputs(batch: int, spec: DualSpec = None, frames: int = 8, seed: int = 0):
@@ -314,23 +320,34 @@ def dual_rgb_state_dict_layout(spec: DualSpec, vis_dim: int):
 
 def dual_rgb_synthetic_state_dict(spec: DualSpec, vis_dim: int, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
     """The W(seed) recipe of ``dual_synthetic_state_dict`` on the tri-modal layout."""
-    sd = OrderedDict()
-    for idx, (key, shape) in enumerate(dual_rgb_state_dict_layout(spec, vis_dim)):
-        g = _gen(seed + 7100, idx)
-        leaf = key.rsplit(".", 1)[-1]
-        if len(shape) >= 2:
-            fan_in = 1
-            for s in shape[1:]:
-                fan_in *= s
-            t = torch.randn(shape, generator=g) / math.sqrt(fan_in)
-        elif leaf == "weight":
-            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
-        elif leaf == "v":
-            t = torch.randn(shape, generator=g)
-        else:
-            t = 0.05 * torch.randn(shape, generator=g)
-        sd[key] = t.contiguous()
-    return sd
+    return _recipe_state_dict(dual_rgb_state_dict_layout(spec, vis_dim), seed + 7100)
+
+
+def _suffix_mask_lengths(owner, key_padding_mask, B, T, dev):
+    """(B,) int32 valid-frame counts of a (B,T) bool ``key_padding_mask`` (True = padding) that marks a suffix of every clip, or None
+    for no mask.  `owner` (a module with a ``_mask_checked`` slot) remembers the mask tensor that passed."""
+    if key_padding_mask is None:
+        return None
+    if key_padding_mask.shape != (B, T) or key_padding_mask.dtype != torch.bool:
+        raise ValueError("key_padding_mask must be a (B,T) bool tensor (True = padding)")
+    valid = ~key_padding_mask.to(dev)
+    lengths = valid.sum(dim=1).to(torch.int32)
+    # the two checks read a flag back from the device, i.e. wait for everything enqueued before (a whole AltFreezing forward
+    # in the two-stream model): the mask TENSOR that passed them is not checked again until it is modified.  The module keeps
+    # a strong reference to it and compares identity + version counter: an address or a shape identifies no contents (a new
+    # mask built per step lands at the freed address of the last one with the same version), an object that is still alive
+    # and unmodified does.  (An inference-mode tensor has no version counter: always checked.)
+    seen = owner._mask_checked
+    if (key_padding_mask.is_inference() or seen is None or seen[0] is not key_padding_mask
+            or seen[1] != key_padding_mask._version):
+        prefix = torch.arange(T, device=dev).expand(B, T) < lengths.view(-1, 1)
+        if not bool((prefix == valid).all()):
+            raise ValueError("key_padding_mask must mark a suffix of every clip as padding (lengths_to_mask form)")
+        if bool((lengths == 0).any()):
+            raise ValueError("a clip without any valid frame: upstream's softmax over an all-masked row is NaN; "
+                             "build the mask with lengths_to_mask, which keeps frame 0")
+        owner._mask_checked = None if key_padding_mask.is_inference() else (key_padding_mask, key_padding_mask._version)
+    return lengths.contiguous()
 
 
 class _Identity(nn.Module):
@@ -437,28 +454,7 @@ class DualEncoderRGB(nn.Module):
             raise ValueError("expected A (B,T,%d) and L (B,T,%d)" % (sp.au_dim, sp.lmk_dim))
         if T < 1 or T > self.max_frames:
             raise ValueError("1..%d frames per clip with %d heads (got %d)" % (self.max_frames, sp.heads, T))
-        lengths = None
-        if key_padding_mask is not None:
-            if key_padding_mask.shape != (B, T) or key_padding_mask.dtype != torch.bool:
-                raise ValueError("key_padding_mask must be a (B,T) bool tensor (True = padding)")
-            valid = ~key_padding_mask.to(dev)
-            lengths = valid.sum(dim=1).to(torch.int32)
-            # the two checks read a flag back from the device, i.e. wait for everything enqueued before (a whole AltFreezing forward
-            # in the two-stream model): the mask TENSOR that passed them is not checked again until it is modified.  The module keeps
-            # a strong reference to it and compares identity + version counter: an address or a shape identifies no contents (a new
-            # mask built per step lands at the freed address of the last one with the same version), an object that is still alive
-            # and unmodified does.  (An inference-mode tensor has no version counter: always checked.)
-            seen = self._mask_checked
-            if (key_padding_mask.is_inference() or seen is None or seen[0] is not key_padding_mask
-                    or seen[1] != key_padding_mask._version):
-                prefix = torch.arange(T, device=dev).expand(B, T) < lengths.view(-1, 1)
-                if not bool((prefix == valid).all()):
-                    raise ValueError("key_padding_mask must mark a suffix of every clip as padding (lengths_to_mask form)")
-                if bool((lengths == 0).any()):
-                    raise ValueError("a clip without any valid frame: upstream's softmax over an all-masked row is NaN; "
-                                     "build the mask with lengths_to_mask, which keeps frame 0")
-                self._mask_checked = None if key_padding_mask.is_inference() else (key_padding_mask, key_padding_mask._version)
-            lengths = lengths.contiguous()
+        lengths = _suffix_mask_lengths(self, key_padding_mask, B, T, dev)
         clips = None
         if not self.rgb_from_features:
             bb = self.rgb_backbone[0]
@@ -516,6 +512,119 @@ class DualEncoderRGB(nn.Module):
                                   None if scores is None else C.c_void_p(scores.data_ptr()), st), "af_mlp_head")
         out = (logits, scores) if return_scores else logits
         return (out, rgb) if return_rgb else out
+
+
+def lmk_disc_spec(in_dim: int, d_model: int = 256, nhead: int = 4, num_layers: int = 4, dim_ff: int = 512) -> DualSpec:
+    """``LMKDisc``'s one-branch spec: ``mlp_ratio = dim_ff / d_model`` and ``dim_feedforward = int(d_model * mlp_ratio)`` as
+    cli/test.py:37 and ``BranchEncoder`` compute them, ``pool_tau`` 0.7 (test.py:45)"""
+    return DualSpec(au_dim=0, lmk_dim=int(in_dim), d_model=int(d_model), depth=int(num_layers), heads=int(nhead),
+                    ff=int(d_model * (dim_ff / d_model)), pool_tau=0.7, lmk_only=True)
+
+
+def lmk_disc_state_dict_layout(spec: DualSpec):
+    """[(key, shape)] in the reference's ``LMKDisc.state_dict()`` order (cli/test.py:34-53): ``lmk_enc.*``, then the head"""
+    D = spec.d_model
+    branch = [(k, s) for k, s in dual_state_dict_layout(spec) if k.startswith("lmk_enc.")]
+    return branch + [("head.0.weight", (D,)), ("head.0.bias", (D,)), ("head.1.weight", (D, D)), ("head.1.bias", (D,)),
+                     ("head.4.weight", (1, D)), ("head.4.bias", (1,))]
+
+
+def lmk_disc_synthetic_state_dict(in_dim: int, d_model: int = 256, nhead: int = 4, num_layers: int = 4, dim_ff: int = 512,
+                                  seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """The W(seed) recipe of ``dual_synthetic_state_dict`` on ``LMKDisc``'s layout (the reference's ``best_lmk_only.pt`` /
+    ``best_lmk_ff512.pt`` are not shipped)."""
+    return _recipe_state_dict(lmk_disc_state_dict_layout(lmk_disc_spec(in_dim, d_model, nhead, num_layers, dim_ff)), seed + 7200)
+
+
+class LMKDisc(nn.Module):
+    """Drop-in for cli/test.py's ``LMKDisc`` (:34-57): one landmark ``BranchEncoder`` (``pool_tau`` 0.7) and the head
+    LayerNorm(d) -> Linear(d, d) -> GELU -> Linear(d, 1).  Same constructor arguments and ``state_dict`` (67 keys at four layers).
+    ``forward(x (B, T, in_dim), key_padding_mask=None) -> (B,)`` fp32 logits on the device: one af_dual_branch_encoders launch with
+    one branch and one af_dual_head launch with n = d_model.  ``key_padding_mask`` (True = padding) must mark a suffix of every clip,
+    which is what ``collate_pad`` builds; the kernels take the count of valid frames.  ``check_branch_spec``'s limits apply.  No
+    CPU / eager fallback."""
+
+    MAX_FRAMES = 16
+
+    def __init__(self, in_dim: int, d_model: int = 256, nhead: int = 4, num_layers: int = 4, dim_ff: int = 512, dropout: float = 0.20):
+        super().__init__()
+        self.spec = lmk_disc_spec(in_dim, d_model, nhead, num_layers, dim_ff)
+        self.max_frames = check_branch_spec(self.spec, self.MAX_FRAMES)
+        self.lmk_enc = _Branch(self.spec.lmk_dim, self.spec)
+        self.head = nn.Sequential(nn.LayerNorm(d_model), nn.Linear(d_model, d_model), nn.GELU(), nn.Dropout(dropout), nn.Linear(d_model, 1))
+        self._packed = None
+        self._pe = {}
+        self._mask_checked = None              # as in DualEncoderRGB
+
+    def load(self, path_or_state):
+        """cli/test.py:189-193: a checkpoint path or a dict, ``ck.get("model", ck)``, ``strict=False``; returns ``(missing, unexpected)``"""
+        ck = path_or_state if isinstance(path_or_state, dict) else torch.load(path_or_state, map_location="cpu")
+        missing, unexpected = self.load_state_dict(ck.get("model", ck), strict=False)
+        return list(missing), list(unexpected)
+
+    def _signature(self):
+        first = next(self.parameters())
+        return (str(first.device), first.data_ptr(), sum(t._version for t in self.parameters()))
+
+    def _pack(self, device):
+        sig = self._signature()
+        if self._packed is not None and self._packed[0] == sig:
+            return self._packed[1], self._packed[2]
+        D = self.spec.d_model
+        sd = {k: v.detach().to(device=device, dtype=torch.float32).contiguous() for k, v in self.state_dict().items()}
+        branch = _pack_branch_images(sd, self.spec, device)["lmk_enc"]
+        head = _flat([(sd["head.0.weight"], False, 0, 0), (sd["head.0.bias"], False, 0, 0),
+                      (sd["head.1.weight"], True, D, D), (sd["head.1.bias"], False, 0, 0),
+                      (sd["head.4.weight"].reshape(-1), False, 0, 0), (sd["head.4.bias"], False, 0, 0)], device)
+        torch.cuda.current_stream(device).synchronize()
+        self._packed = (sig, branch, head)
+        return branch, head
+
+    def forward(self, x, key_padding_mask=None):
+        if not x.is_cuda:
+            raise RuntimeError("the MI355X LMKDisc only runs on HIP device tensors (no CPU fallback)")
+        sp = self.spec
+        if x.dim() != 3 or x.shape[2] != sp.lmk_dim:
+            raise ValueError("expected x (B,T,%d)" % sp.lmk_dim)
+        B, T, _ = x.shape
+        return self.forward_lengths(x, _suffix_mask_lengths(self, key_padding_mask, B, T, x.device))
+
+    def forward_lengths(self, x, lengths=None):
+        """``forward`` with the mask given as (B,) int32 device counts of valid frames (1..T each; not checked), None for no mask"""
+        from ._lib import check, lib
+        if not x.is_cuda:
+            raise RuntimeError("the MI355X LMKDisc only runs on HIP device tensors (no CPU fallback)")
+        if self.training:
+            raise RuntimeError("inference only: call .eval() first")
+        sp = self.spec
+        if x.dim() != 3 or x.shape[2] != sp.lmk_dim:
+            raise ValueError("expected x (B,T,%d)" % sp.lmk_dim)
+        B, T, _ = x.shape
+        if T < 1 or T > self.max_frames:
+            raise ValueError("1..%d frames per clip with %d heads (got %d)" % (self.max_frames, sp.heads, T))
+        dev = x.device
+        if B == 0:
+            return x.new_zeros((0,), dtype=torch.float32)
+        with torch.cuda.device(dev):
+            branch, head = self._pack(dev)
+            if T not in self._pe or self._pe[T].device != dev:
+                self._pe[T] = sinusoid_table(T, sp.d_model).to(dev)
+            if lengths is not None:
+                if lengths.dim() != 1 or lengths.numel() != B:
+                    raise ValueError("lengths must be (B,) valid-frame counts")
+                lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            D = sp.d_model
+            z = torch.empty((B, D), dtype=torch.float32, device=dev)
+            logits = torch.empty((B,), dtype=torch.float32, device=dev)
+            xf = x.to(torch.float32).contiguous()
+            xp, wp, dins = (C.c_void_p * 1)(xf.data_ptr()), (C.c_void_p * 1)(branch.data_ptr()), (C.c_int * 1)(sp.lmk_dim)
+            check(lib.af_dual_branch_encoders(1, xp, wp, dins, None if lengths is None else C.c_void_p(lengths.data_ptr()),
+                                              C.c_void_p(self._pe[T].data_ptr()), B, T, D, sp.depth, sp.heads, sp.ff,
+                                              C.c_float(sp.pool_tau), C.c_void_p(z.data_ptr()), D, st), "af_dual_branch_encoders")
+            check(lib.af_dual_head(C.c_void_p(z.data_ptr()), C.c_void_p(head.data_ptr()), B, D, C.c_void_p(logits.data_ptr()), st),
+                  "af_dual_head")
+        return logits
 
 
 class GatedMoE(nn.Module):
