@@ -869,6 +869,37 @@ int af_tile_motion_u8(const af_tile_source* src, const void* prev_grey, void* gr
 int af_tile_components_u8(const void* mask, int64_t pitch, int h, int w, const void* g, const af_tile_params* params, void* workspace,
                           int64_t workspace_bytes, const af_tile_outputs* out, void* stream);
 
+/* ---- rank metrics of index rows over one scored pool (added within ABI 6) -----------------------------------------------------------
+ * AUROC and average precision of many resamples of ONE pool of n scored items, on integers (csrc/af_eval.hip; the
+ * numpy statement is tests/evalsuite_ref.py).  The caller sorts the pool once by descending score (stable) and uploads
+ *   rank_of_item[n]   each item's position in that order,
+ *   group_of_rank[n]  the tie-group id along the sorted scores: 0 at rank 0, non-decreasing, +1 where the score changes,
+ *   label_of_rank[n]  non-zero: a positive, along the sorted scores.
+ * A row is the indices idx[row_off[r] .. row_off[r + 1]) (items, repeats allowed; n_idx = the length of idx).  One workgroup per
+ * row counts the draws of every rank in LDS with integer atomics - hence n <= AF_RANK_MAX_POOL - and scans the sorted order:
+ *   u2      = sum_g pos_g (2 (N - fp_g) + neg_g)         exact; AUROC = u2 / (2 P N)
+ *   ap_sum  = sum_g pos_g (tp_g / (tp_g + fp_g))         fp64, groups with pos_g == 0 skipped; AP = ap_sum / P
+ *   tp_cut, fp_cut = the draws of rank < cut, by label   (cut in [0, n]: the pool items at or above a threshold)
+ * ap_sum is added in a fixed order (a thread's groups in rank order over contiguous chunks of ceil(n / AF_RANK_THREADS) ranks, a
+ * group belonging to the thread of its last rank, then the tree p[i] += p[i + h], h = AF_RANK_THREADS / 2 .. 1): runs repeat bit
+ * for bit.  An index or rank outside [0, n), or a row that leaves [0, n_idx], is never used as an address: it is skipped and
+ * counted into *error (one int32, DEVICE memory, zeroed by the call on `stream`); a caller treats non-zero as a failed call.
+ * AF_ERR_ARG: a null pointer, n outside [1, AF_RANK_MAX_POOL], rows < 0, n_idx outside [0, 2^31), cut outside [0, n].
+ *
+ * af_rank_curve: ONE row -> the cumulative counts at every group's end, tps[g] / fps[g] for g < *n_groups (tps, fps: n int32
+ * each; n_groups, error: one int32 each; all DEVICE memory) - the integer ROC curve a caller thins and normalises. */
+#define AF_RANK_MAX_POOL 16384
+#define AF_RANK_THREADS 256
+typedef struct af_rank_row {
+    int64_t u2;
+    double ap_sum;
+    int32_t P, N, tp_cut, fp_cut;
+} af_rank_row;
+int af_rank_metrics_rows(const int32_t* rank_of_item, const int32_t* group_of_rank, const uint8_t* label_of_rank, int n, const int32_t* idx,
+                         int64_t n_idx, const int64_t* row_off, int rows, int cut, af_rank_row* out, int32_t* error, void* stream);
+int af_rank_curve(const int32_t* rank_of_item, const int32_t* group_of_rank, const uint8_t* label_of_rank, int n, const int32_t* idx,
+                  int64_t n_idx, int32_t* tps, int32_t* fps, int32_t* n_groups, int32_t* error, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,

@@ -21,6 +21,9 @@ def __getattr__(name):
     if name == "TilePicker":
         from . import tile_picker
         return tile_picker.TilePicker
+    if name in ("EvalSuite", "RankMetrics"):
+        from . import eval_suite
+        return getattr(eval_suite, name)
     if name in ("DualVideoScorer", "LmkVideoScorer", "DualTrack"):
         from . import dual_video
         return getattr(dual_video, name)

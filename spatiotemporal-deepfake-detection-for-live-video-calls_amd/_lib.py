@@ -171,6 +171,14 @@ class TileOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("g", "cls", "edges", "mask", "labels", "boxes", "external")]
 
 
+class RankRow(C.Structure):
+    """af_rank_row: what af_rank_metrics_rows writes per index row"""
+    _fields_ = [("u2", C.c_int64), ("ap_sum", C.c_double), ("P", C.c_int32), ("N", C.c_int32), ("tp_cut", C.c_int32), ("fp_cut", C.c_int32)]
+
+
+RANK_MAX_POOL, RANK_THREADS = 16384, 256
+
+
 class DualvTrack(C.Structure):
     """af_dualv_track: one face track's raw landmark and AU rows on the device"""
     _fields_ = [("lmk", C.c_void_p), ("au", C.c_void_p), ("lmk_pitch", C.c_int64), ("au_pitch", C.c_int32), ("n", C.c_int32)]
@@ -323,6 +331,9 @@ ABI = {
                                     C.c_void_p]),
     "af_tile_components_u8": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(TileParams), C.c_void_p, C.c_int64,
                                         C.POINTER(TileOutputs), C.c_void_p]),
+    "af_rank_metrics_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "af_rank_curve": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6
