@@ -900,6 +900,43 @@ int af_rank_metrics_rows(const int32_t* rank_of_item, const int32_t* group_of_ra
 int af_rank_curve(const int32_t* rank_of_item, const int32_t* group_of_rank, const uint8_t* label_of_rank, int n, const int32_t* idx,
                   int64_t n_idx, int32_t* tps, int32_t* fps, int32_t* n_groups, int32_t* error, void* stream);
 
+/* ---- bootstrap rows from numpy's PCG64 stream (added within ABI 6) ------------------------------------------------------------------
+ * What `rows` rounds of rng.choice(A, count_a, True), rng.choice(B, count_b, True) of a numpy Generator over PCG64 return, drawn on
+ * the device (csrc/af_draw.hip; the numpy statement is tests/pcg64_ref.py).  `start` is bit_generator.state: the 128-bit
+ * state and increment in 64-bit halves, has_uint32 and uinteger.  The stream: s_j = s_(j-1) 0x2360ED051FC65DA44385DF649FCCF645 + inc
+ * (mod 2^128), out_j = rotr64(hi64(s_j) ^ lo64(s_j), s_j >> 122); 32-bit words are the buffered uinteger where has_uint32 is set, then
+ * the low and the high half of every output.  A draw with bound m takes a word w, rejects it where lo32(w m) < 2^32 mod m and takes the
+ * next, else yields hi32(w m); a bound of 1 yields 0 and takes NO word.  Row r is count_a draws under bound_a, then count_b under
+ * bound_b; rows follow one another on the stream.  Written, all DEVICE memory:
+ *   idx[rows (count_a + count_b)]   items_a[draw] / items_b[draw], or with a null items pointer the draw itself (uint32 bits);
+ *   row_off[rows + 1]               row_base + r (count_a + count_b): the row table af_rank_metrics_rows reads, so idx and row_off may
+ *                                   point behind rows that are already there;
+ *   result                          words consumed, outputs made, the buffer numpy would be left with, the rejections, `error`.
+ * Three launches on `stream` (scan, resolve, emit), no workgroup waits on another.  `max_rejects` (1 .. AF_DRAW_MAX_REJECTS) is the
+ * capacity of the list of words that EITHER bound would reject among the first rows (count_a + count_b) + ceil(max_rejects / 2) words;
+ * a list that overflows, or more than ceil(max_rejects / 2) rejections, sets result->error, result->consumed = -1 and nothing is drawn.  error also counts draws outside `items` (there are
+ * none).  A caller treats non-zero as a failed call.  The workspace (af_pcg64_draw_workspace_bytes(max_rejects), 8-byte aligned) is
+ * scratch.  AF_ERR_ARG: a null pointer other than items (and idx where nothing is drawn), a bound outside [1, 2^32 - 1] (numpy draws 2^32 another way), a negative
+ * count, rows (count_a + count_b) >= 2^31, items with bound != count, max_rejects out of range, a workspace too small. */
+#define AF_DRAW_MAX_REJECTS 8192
+typedef struct af_pcg64_state {
+    uint64_t state_hi, state_lo, inc_hi, inc_lo;
+    int32_t has_uint32;
+    uint32_t uinteger;
+} af_pcg64_state;
+typedef struct af_draw_result {
+    int64_t consumed;              /* 32-bit words taken from the stream, the buffered one included */
+    int64_t outputs;               /* 64-bit outputs made: the caller advances the state by this many steps */
+    int32_t has_uint32;            /* the buffer after the last word, */
+    uint32_t uinteger;             /*   as numpy leaves it (the high half of the last output, stale or not) */
+    int32_t rejected, listed;      /* words rejected; words listed by the scan */
+    int32_t error, reserved;
+} af_draw_result;
+int64_t af_pcg64_draw_workspace_bytes(int max_rejects);
+int af_pcg64_draw_rows(const af_pcg64_state* start, int64_t bound_a, int count_a, int64_t bound_b, int count_b, int rows,
+                       const int32_t* items_a, const int32_t* items_b, int max_rejects, int32_t* idx, int64_t* row_off, int64_t row_base,
+                       af_draw_result* result, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- whole-forward op list ------------------------------------------------------------ */
 
 enum af_op_kind { AF_OP_STEM = 0, AF_OP_CONV = 1, AF_OP_MAXPOOL = 2, AF_OP_HEAD = 3,

@@ -179,6 +179,21 @@ class RankRow(C.Structure):
 RANK_MAX_POOL, RANK_THREADS = 16384, 256
 
 
+class Pcg64State(C.Structure):
+    """af_pcg64_state: numpy's PCG64 bit_generator.state, the 128-bit words in 64-bit halves"""
+    _fields_ = [("state_hi", C.c_uint64), ("state_lo", C.c_uint64), ("inc_hi", C.c_uint64), ("inc_lo", C.c_uint64),
+                ("has_uint32", C.c_int32), ("uinteger", C.c_uint32)]
+
+
+class DrawResult(C.Structure):
+    """af_draw_result: what af_pcg64_draw_rows leaves on the device beside the rows"""
+    _fields_ = [("consumed", C.c_int64), ("outputs", C.c_int64), ("has_uint32", C.c_int32), ("uinteger", C.c_uint32),
+                ("rejected", C.c_int32), ("listed", C.c_int32), ("error", C.c_int32), ("reserved", C.c_int32)]
+
+
+DRAW_MAX_REJECTS = 8192
+
+
 class DualvTrack(C.Structure):
     """af_dualv_track: one face track's raw landmark and AU rows on the device"""
     _fields_ = [("lmk", C.c_void_p), ("au", C.c_void_p), ("lmk_pitch", C.c_int64), ("au_pitch", C.c_int32), ("n", C.c_int32)]
@@ -334,6 +349,9 @@ ABI = {
     "af_rank_metrics_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "af_rank_curve": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "af_pcg64_draw_workspace_bytes": (C.c_int64, [C.c_int]),
+    "af_pcg64_draw_rows": (C.c_int, [C.POINTER(Pcg64State), C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "af_conv_cpa_fusable": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int]),
     "af_conv3d_cpa_bn_act": (C.c_int, [C.POINTER(ConvDesc)] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(ConvDesc)] + [C.c_void_p] * 5),
     "af_conv3d_ca_bn_act": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.POINTER(ConvDesc)] + [C.c_void_p] * 6

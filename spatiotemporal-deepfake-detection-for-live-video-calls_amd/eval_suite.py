@@ -14,12 +14,19 @@ csrc/af_eval.hip computes them for all rows of a call in one launch, one workgro
 copy, one launch, one read-back.  The index rows are drawn on the host by the reference's own ``default_rng`` calls in its order -
 that is what makes its recorded confidence intervals reproducible, and it is most of what a run still costs.  The results equal
 tests/evalsuite_ref.py (numpy) - the integers exactly, ``ap_sum`` bit for bit - and repeat bit for bit.  There is no CPU fallback:
-without the HIP library the classes fail.  Not built: a device RNG, pools above 16 384, W&B logging, ``batch_eval.py``,
+without the HIP library the classes fail.
+
+``EvalSuite(draw="device")`` draws the B resample rows on the GPU instead, from numpy's own PCG64 stream (csrc/af_draw.hip, DESIGN 26;
+the numpy statement is tests/pcg64_ref.py): the ``bit_generator.state`` the host has reached after ratio-matching goes to the device,
+three launches (scan, resolve, emit) write the rows straight into the buffer the metrics launch reads, and the host sets the
+generator to where numpy would have left it.  Same dicts, same files; nothing proportional to B n is staged or touched by the host.
+``"host"`` stays the default.  Not built: pools above 16 384, generators other than PCG64, W&B logging, ``batch_eval.py``,
 ``results/gen_tables.py``."""
 import csv
 import ctypes as C
 import json
 import os
+import time
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -37,6 +44,33 @@ SUMMARY_HEADER = ["dataset", "method", "n_avail_real", "n_avail_fake", "fake_per
                   "gpu_alloc_p95", "gpu_reserved_p95", "cpu_peak_p95", "out_dir"]
 SEED_HEADER = ["seed", "n_pool", "n_real", "n_fake", "threshold", "auc_mean", "auc_sd", "ap_mean", "ap_sd", "f1_macro@tau_mean", "f1_macro@tau_sd",
                "precision_macro@tau_mean", "precision_macro@tau_sd", "recall_macro@tau_mean", "recall_macro@tau_sd"]
+
+
+PCG64_MULT = 0x2360ED051FC65DA44385DF649FCCF645
+DRAW_LIST_SHARE = 4                    # a draw is refused where the expected rejections exceed 1 / 4 of the default list
+
+
+# ---- numpy's PCG64 state ------------------------------------------------------------------------------------------------
+
+def pcg64_state(rng) -> Tuple[int, int, int, int]:
+    """(state, inc, has_uint32, uinteger) of a ``Generator`` over ``PCG64``; any other bit generator is a ``ValueError``"""
+    bg = getattr(rng, "bit_generator", None)
+    if not isinstance(bg, np.random.PCG64):
+        raise ValueError("eval: the device draw restates numpy's PCG64 stream; this generator runs on %s" % type(bg).__name__)
+    sd = bg.state
+    return int(sd["state"]["state"]), int(sd["state"]["inc"]), int(sd["has_uint32"]), int(sd["uinteger"])
+
+
+def pcg64_advance(s: int, inc: int, k: int) -> int:
+    """the 128-bit state k outputs on: the LCG's O(log k) jump"""
+    mask = (1 << 128) - 1
+    a, c, A, Cc = PCG64_MULT, inc, 1, 0
+    while k:
+        if k & 1:
+            A, Cc = (A * a) & mask, (Cc * a + c) & mask
+        a, c = (a * a) & mask, ((a + 1) * c) & mask
+        k >>= 1
+    return (A * s + Cc) & mask
 
 
 # ---- the launch ------------------------------------------------------------------------------------------------------------------------
@@ -63,14 +97,22 @@ class RankMetrics:
     ``(flat, offsets)`` pair -> dict of numpy arrays ``auc, ap, P, N, tp, fp, tn, fn, u2, ap_sum``, one entry per row; a row with
     ``P N == 0`` has NaN AUROC, one with ``P == 0`` NaN AP; tp .. fn count the draws against ``s >= threshold``.
     ``curve(pool)`` -> ``fpr, tpr, thresholds`` as sklearn's ``roc_curve`` returns them (``drop_intermediate`` applied on the host).
-    An index outside the pool is refused before the upload; the kernel skips and counts one all the same, and a non-zero count raises."""
+    An index outside the pool is refused before the upload; the kernel skips and counts one all the same, and a non-zero count raises.
+    ``drawn_rows(bound_a, count_a, bound_b, count_b, rows, rng, items_a=None, items_b=None, max_rejects=None)`` -> ``(flat int64 rows,
+    words consumed)``: what ``rows`` rounds of ``rng.choice(items_a, count_a)``, ``rng.choice(items_b, count_b)`` return (without items:
+    ``rng.integers(0, bound, count)``), drawn on the device from ``rng``'s PCG64 state; ``rng`` is left where numpy would leave it.
+    ``bootstrap_rows_raw(pool, folds, pos, neg, B, rng, cut)`` -> the records of the fold rows and of B such resamples of ``pos`` and
+    ``neg``, drawn and measured on the device: two small staging copies, four launches, one read-back.
+    ``staged_bytes`` counts what the row calls copied to the device (a pool's own upload apart)."""
 
     def __init__(self, device=None):
         from . import _lib                                        # fails loudly when libafhip.so is missing
         self.device = cuda_device(device)
         self.host_check = True
-        self._in = self._out = self._dev_in = self._dev_out = None
-        self.launches = self.uploads = self.readbacks = 0
+        self._in = self._out = self._dev_in = self._dev_out = self._draw_ws = None
+        self.launches = self.uploads = self.readbacks = self.staged_bytes = 0
+        self.queued_at = 0.0                                      # perf_counter() when bootstrap_rows_raw had queued its launches
+        self.last_draw: Dict[str, int] = {}
 
     def pool(self, y, s) -> Pool:
         from . import _lib
@@ -115,12 +157,15 @@ class RankMetrics:
         base, n = pool.dev.data_ptr(), pool.n
         return C.c_void_p(base), C.c_void_p(base + 4 * n), C.c_void_p(base + 12 * n), base + 8 * n      # rank, group, label, every index
 
-    def _finish(self, what: str, nbytes: int) -> np.ndarray:
-        """the one read-back of a call -> the bytes, the error word last"""
+    def _read_back(self, nbytes: int) -> np.ndarray:
         self._out[:nbytes].copy_(self._dev_out[:nbytes], non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         self.readbacks += 1
-        got = self._out[:nbytes].numpy().copy()
+        return self._out[:nbytes].numpy().copy()
+
+    def _finish(self, what: str, nbytes: int, got: Optional[np.ndarray] = None) -> np.ndarray:
+        """the one read-back of a call -> the bytes, the error word last"""
+        got = self._read_back(nbytes) if got is None else got
         err = int(got[-4:].view(np.int32)[0])
         if err:
             from . import _lib
@@ -161,6 +206,7 @@ class RankMetrics:
             used = off_bytes + 4 * n_idx
             self._dev_in[:used].copy_(self._in[:used], non_blocking=True)
             self.uploads += 1
+            self.staged_bytes += used
             base, out = self._dev_in.data_ptr(), self._dev_out.data_ptr()
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             _lib.check(_lib.lib.af_rank_metrics_rows(rank, group, label, pool.n, C.c_void_p(base + off_bytes), n_idx, C.c_void_p(base), R, int(cut),
@@ -171,6 +217,150 @@ class RankMetrics:
 
     def rows(self, pool: Pool, rows, threshold=None) -> Dict[str, np.ndarray]:
         return finish_rows(self.rows_raw(pool, rows, pool.cut(threshold)))
+
+    # ---- rows drawn on the device from numpy's PCG64 stream (csrc/af_draw.hip)
+    def _draw_plan(self, bound_a, count_a, bound_b, count_b, rows, rng, with_items, max_rejects):
+        """every host check of a draw, before anything is staged or launched -> (Pcg64State, (state, inc, has, uinteger), capacity)"""
+        from . import _lib
+        words = pcg64_state(rng)
+        bound_a, count_a, bound_b, count_b, rows = int(bound_a), int(count_a), int(bound_b), int(count_b), int(rows)
+        for m in (bound_a, bound_b):
+            if not 1 <= m <= 2 ** 32 - 1:
+                raise ValueError("eval: a bound of %d (1 to 2^32 - 1: numpy draws the bound 2^32 another way)" % m)
+        if count_a < 0 or count_b < 0 or rows < 0:
+            raise ValueError("eval: counts %d and %d, %d rows" % (count_a, count_b, rows))
+        if rows * (count_a + count_b) >= 2 ** 31:
+            raise ValueError("eval: %d rows of %d + %d draws (below 2^31 in one call)" % (rows, count_a, count_b))
+        for m, c, has in ((bound_a, count_a, with_items[0]), (bound_b, count_b, with_items[1])):
+            if has and m != c:
+                raise ValueError("eval: a bound of %d over %d items" % (m, c))
+        if max_rejects is None:
+            cap = _lib.DRAW_MAX_REJECTS
+            active = [(m, c) for m, c in ((bound_a, count_a), (bound_b, count_b)) if m > 1 and c > 0]
+            T = rows * sum(c for _, c in active)
+            thr = max([2 ** 32 % m for m, _ in active], default=0)
+            if DRAW_LIST_SHARE * T * thr > cap * (2 ** 32 - thr):
+                raise ValueError("eval: about %d of %d words would be rejected (2^32 mod bound = %d); the list of %d holds %d x that at most"
+                                 % (T * thr // (2 ** 32 - thr), T, thr, cap, DRAW_LIST_SHARE))
+        else:
+            cap = int(max_rejects)
+            if not 1 <= cap <= _lib.DRAW_MAX_REJECTS:
+                raise ValueError("eval: a rejection list of %d entries (1 to %d)" % (cap, _lib.DRAW_MAX_REJECTS))
+        s, inc, has, uinteger = words
+        m64 = (1 << 64) - 1
+        return _lib.Pcg64State(s >> 64, s & m64, inc >> 64, inc & m64, has, uinteger), words, cap
+
+    def _launch_draw(self, start, bounds, rows, items, cap, idx_ptr, row_off_ptr, row_base, result_ptr):
+        """queues the three draw launches on the current stream"""
+        from . import _lib
+        need = int(_lib.lib.af_pcg64_draw_workspace_bytes(cap))
+        with torch.inference_mode(False):
+            if self._draw_ws is None or self._draw_ws.numel() < need:
+                self._draw_ws = torch.empty(int(_lib.lib.af_pcg64_draw_workspace_bytes(_lib.DRAW_MAX_REJECTS)), dtype=torch.uint8, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(_lib.lib.af_pcg64_draw_rows(C.byref(start), bounds[0], bounds[1], bounds[2], bounds[3], rows, C.c_void_p(items[0]),
+                                               C.c_void_p(items[1]), cap, C.c_void_p(idx_ptr), C.c_void_p(row_off_ptr), row_base,
+                                               C.c_void_p(result_ptr), C.c_void_p(self._draw_ws.data_ptr()), self._draw_ws.numel(), stream),
+                   "pcg64_draw_rows")
+        self.launches += 3
+
+    def _finish_draw(self, raw: np.ndarray, words, rng) -> int:
+        """the read-back ``af_draw_result``: raises where the list overflowed, else moves ``rng`` to numpy's final state -> words consumed"""
+        from . import _lib
+        r = _lib.DrawResult.from_buffer_copy(raw.tobytes())
+        self.last_draw = {k: int(getattr(r, k)) for k in ("consumed", "outputs", "has_uint32", "uinteger", "rejected", "listed", "error")}
+        if r.error:
+            raise _lib.AfError("pcg64_draw_rows: error %d with %d words listed for rejection: the list overflowed and no rows were drawn" % (
+                r.error, r.listed))
+        s, inc, has, uinteger = words
+        if r.consumed > 0 and r.outputs != (r.consumed - has + 1) // 2:
+            raise _lib.AfError("pcg64_draw_rows: %d outputs for %d words" % (r.outputs, r.consumed))
+        if r.consumed > 0:
+            rng.bit_generator.state = {"bit_generator": "PCG64", "state": {"state": pcg64_advance(s, inc, int(r.outputs)), "inc": inc},
+                                       "has_uint32": int(r.has_uint32), "uinteger": int(r.uinteger)}
+        return int(r.consumed)
+
+    def drawn_rows(self, bound_a, count_a, bound_b, count_b, rows, rng, items_a=None, items_b=None, max_rejects=None):
+        """the draw alone, rows back on the host (tests and debugging) -> (flat int64 array in numpy's order, words consumed)"""
+        from . import _lib
+        items = [None if it is None else np.ascontiguousarray(np.asarray(it).ravel(), np.int32) for it in (items_a, items_b)]
+        counts = [int(count_a), int(count_b)]
+        for i, it in enumerate(items):
+            if it is not None and len(it) != int((bound_a, bound_b)[i]):
+                raise ValueError("eval: a bound of %d over %d items" % ((bound_a, bound_b)[i], len(it)))
+        start, words, cap = self._draw_plan(bound_a, counts[0], bound_b, counts[1], rows, rng, [it is not None for it in items], max_rejects)
+        rows, n = int(rows), int(rows) * (counts[0] + counts[1])
+        with torch.cuda.device(self.device), torch.inference_mode(False):
+            dev = [None if it is None or len(it) == 0 else torch.from_numpy(it).to(self.device) for it in items]
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+            off = torch.empty(rows + 1, dtype=torch.int64, device=self.device)
+            res = torch.empty(C.sizeof(_lib.DrawResult), dtype=torch.uint8, device=self.device)
+            self._launch_draw(start, (int(bound_a), counts[0], int(bound_b), counts[1]), rows, [0 if d is None else d.data_ptr() for d in dev],
+                              cap, idx.data_ptr(), off.data_ptr(), 0, res.data_ptr())
+            raw, flat, table = res.cpu().numpy(), idx[:n].cpu().numpy(), off.cpu().numpy()
+            self.readbacks += 1
+        consumed = self._finish_draw(raw, words, rng)
+        if not np.array_equal(table, np.arange(rows + 1, dtype=np.int64) * (counts[0] + counts[1])):
+            raise _lib.AfError("pcg64_draw_rows: a wrong row table")
+        out = flat.astype(np.int64)
+        for (lo, hi), it in zip(((0, counts[0]), (counts[0], counts[0] + counts[1])), items):
+            if it is None and n:                                             # value mode: the uint32 draw itself
+                v = out.reshape(rows, -1)
+                v[:, lo:hi] &= 0xffffffff
+        return out, consumed
+
+    def bootstrap_rows_raw(self, pool: Pool, folds, pos, neg, B: int, rng, cut: int = 0) -> np.ndarray:
+        """the fold rows and B resamples ``[rng.choice(pos, len(pos)), rng.choice(neg, len(neg))]`` of the pool: the resamples are drawn
+        on the device behind the fold rows and one ``af_rank_metrics_rows`` call covers both -> ``ROW_DTYPE`` records, folds first.
+        Staged: the fold rows and their offsets, ``pos`` and ``neg``; read back once: the records, the draw's result, the error word."""
+        from . import _lib
+        rank, group, label, _ = self._pool_pointers(pool)
+        folds = [np.asarray(f).ravel() for f in folds]
+        pos, neg, B = np.asarray(pos).ravel(), np.asarray(neg).ravel(), int(B)
+        F, a, b = len(folds), int(pos.size), int(neg.size)
+        for v in folds + [pos, neg]:
+            if v.size and v.dtype.kind not in "iu":
+                raise ValueError("eval: indices are integers, got %s" % v.dtype)
+            if self.host_check and v.size and (int(v.min()) < 0 or int(v.max()) >= pool.n):
+                raise ValueError("eval: an index outside the pool of %d items" % pool.n)
+        if not 0 <= int(cut) <= pool.n:
+            raise ValueError("eval: cut %d of a pool of %d" % (cut, pool.n))
+        if B < 0 or a < 1 or b < 1:
+            raise ValueError("eval: %d resamples of %d positives and %d negatives" % (B, a, b))
+        start, words, cap = self._draw_plan(a, a, b, b, B, rng, [True, True], None)
+        fold_off = np.full(F + 1, a + b, np.int64)                            # idx: pos, neg, the fold rows, then the rows drawn here -
+        if F:                                                                 # the rows of one table follow one another
+            fold_off[1:] += np.cumsum([f.size for f in folds])
+        row_base = int(fold_off[-1])
+        R, n_idx = F + B, row_base + B * (a + b)
+        if n_idx >= 2 ** 31:
+            raise ValueError("eval: %d indices in one call (below 2^31)" % n_idx)
+        off_bytes, rec_bytes = 8 * (R + 1), ROW_DTYPE.itemsize * R
+        res_bytes = C.sizeof(_lib.DrawResult)
+        out_bytes = rec_bytes + res_bytes + 8                                 # records, af_draw_result, padding, the error word last
+        with torch.cuda.device(self.device):
+            self._buffers(off_bytes + 4 * n_idx, out_bytes)
+            stage = self._in.numpy()
+            head = 8 * (F + 1)
+            stage[:head].view(np.int64)[:] = fold_off
+            staged = stage[head:head + 4 * row_base].view(np.int32)
+            staged[:] = np.concatenate([pos, neg] + folds)
+            self._dev_in[:head].copy_(self._in[:head], non_blocking=True)
+            self._dev_in[off_bytes:off_bytes + 4 * row_base].copy_(self._in[head:head + 4 * row_base], non_blocking=True)
+            self.uploads += 2
+            self.staged_bytes += head + 4 * row_base
+            base, out = self._dev_in.data_ptr(), self._dev_out.data_ptr()
+            idx = base + off_bytes
+            self._launch_draw(start, (a, a, b, b), B, [idx, idx + 4 * a], cap, idx + 4 * row_base, base + 8 * F, row_base, out + rec_bytes)
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(_lib.lib.af_rank_metrics_rows(rank, group, label, pool.n, C.c_void_p(idx), n_idx, C.c_void_p(base), R, int(cut),
+                                                     C.c_void_p(out), C.c_void_p(out + out_bytes - 4), stream), "rank_metrics_rows")
+            self.launches += 1
+            self.queued_at = time.perf_counter()
+            got = self._read_back(out_bytes)
+        self._finish_draw(got[rec_bytes:rec_bytes + res_bytes], words, rng)
+        self._finish("rank_metrics_rows", out_bytes, got)
+        return got[:rec_bytes].view(ROW_DTYPE)
 
     def curve_counts(self, pool: Pool) -> Tuple[np.ndarray, np.ndarray]:
         """cumulative (tps, fps) at every tie group's end over the whole pool, each item drawn once: the integer ROC curve"""
@@ -414,7 +604,7 @@ def summary_row(ds, method, fpr, results, out_dir) -> list:
 
 
 class EvalSuite:
-    """``EvalSuite(device=None)``: ``python ds.py`` on the GPU.
+    """``EvalSuite(device=None, draw="host")``: ``python ds.py`` on the GPU.
 
     ``run_one(y, s, fake_per_real, seed, bootstrap=2000, threshold=0.04, perf=None)`` -> ``ds.run_one``'s dict (``counts_available``,
     ``subset``, ``metrics_mean_sd``, ``bootstrap_ci``, ``per_fold``, ``hardware_stats``; ``config`` echoes the arguments): the subset,
@@ -425,9 +615,14 @@ class EvalSuite:
     a CSV path or the tuple ``load_per_video`` returns (or ``(y, s)``) -> ``(rows of summary_all.csv, header first,
     {(dataset, method): [run_one's dict per seed]})``; with ``outdir`` it writes ``<dataset>/<method>/summary_seed*.json``,
     ``metrics_seed*.csv`` and ``summary_all.csv`` in the reference's formats.  No W&B.
-    ``timing`` holds the host seconds of the last ``run_one``: ``draw`` (the index rows), ``rows`` (staging, launch, read-back) and ``total``."""
+    ``timing`` holds the host seconds of the last ``run_one``: ``draw`` (the index rows), ``rows`` (staging, launch, read-back) and ``total``.
+    ``draw="device"``: the B resamples are drawn on the GPU from the same PCG64 stream (``RankMetrics.bootstrap_rows_raw``) - the same
+    dicts and files; ``timing["draw"]`` is then the time until the launches are queued, ``rows`` the wait and the read-back."""
 
-    def __init__(self, device=None):
+    def __init__(self, device=None, draw: str = "host"):
+        if draw not in ("host", "device"):
+            raise ValueError("eval: draw is 'host' or 'device', got %r" % (draw,))
+        self.draw = draw
         self.metrics = RankMetrics(device)
         self.device = self.metrics.device
         self.timing: Dict[str, float] = {}
@@ -435,7 +630,6 @@ class EvalSuite:
     load_per_video = staticmethod(load_per_video)
 
     def run_one(self, y, s, fake_per_real, seed, bootstrap=2000, threshold=0.04, perf=None, config: Optional[Dict] = None) -> Dict:
-        import time
         t0 = time.perf_counter()
         y, s = np.asarray(y), np.asarray(s, float)
         rng = np.random.default_rng(seed)
@@ -443,10 +637,15 @@ class EvalSuite:
         yt_pool, st_pool = y[idx_pool], s[idx_pool]
         folds = stratified_test_folds(yt_pool, seed)
         pos, neg = np.where(yt_pool == 1)[0], np.where(yt_pool == 0)[0]
-        boots = [np.concatenate([rng.choice(pos, len(pos), True), rng.choice(neg, len(neg), True)]) for _ in range(bootstrap)]
-        t1 = time.perf_counter()
-        pool = self.metrics.pool(yt_pool, st_pool)
-        res = self.metrics.rows(pool, folds + boots, threshold)
+        if self.draw == "device":
+            pool = self.metrics.pool(yt_pool, st_pool)
+            res = finish_rows(self.metrics.bootstrap_rows_raw(pool, folds, pos, neg, bootstrap, rng, pool.cut(threshold)))
+            t1 = self.metrics.queued_at
+        else:
+            boots = [np.concatenate([rng.choice(pos, len(pos), True), rng.choice(neg, len(neg), True)]) for _ in range(bootstrap)]
+            t1 = time.perf_counter()
+            pool = self.metrics.pool(yt_pool, st_pool)
+            res = self.metrics.rows(pool, folds + boots, threshold)
         t2 = time.perf_counter()
         per_fold, precL, recL, f1L = [], [], [], []
         for k in range(len(folds)):
