@@ -275,6 +275,13 @@ int af_conv_ca_work_units(const af_conv_desc* dc, const af_conv_desc* d1, const 
 int af_conv_cpa_work_units(const af_conv_desc* dc, const af_conv_desc* da, int x_sub, int64_t* tiles, int* workgroups);
 int af_block_abc_work_units(const af_conv_desc* da, const af_conv_desc* db, const af_conv_desc* dc, const af_conv_desc* d1,
                             int* patch_rows, int* time_segments, int64_t* units);
+/* device-free: the (frame, band) units, bands per frame and workgroups that the fused stems launch for d; fused = 1 for
+ * af_stem_conv_bn_relu_maxpool, 2 for ..._rgb3[_ld]; answers for 256 CUs where there is no device (as af_conv_work_units).
+ * A frame of fewer pooled rows than 8, or a launch of at least as many frames as CUs, has one band; otherwise bands of at least 4
+ * pooled rows, the last one possibly shorter.  The launchers take their bands and their grid from the same function; workgroup b
+ * walks units b, b + workgroups, ... (the K-packed stem on a grid that is a multiple of 8: a contiguous eighth of the units per
+ * XCD).  AF_OK, or AF_ERR_ARG (added within ABI 6) */
+int af_stem_work_units(const af_conv_desc* d, int fused, int64_t* units, int* bands, int* workgroups);
 
 /* nn.MaxPool3d on NDHWC (stem_helper.py:168-170 [1,3,3]/[1,2,2]/[0,1,1];
  * video_model_builder.py:474-480 [2,1,1]/[2,1,1]); padding behaves as -inf. */

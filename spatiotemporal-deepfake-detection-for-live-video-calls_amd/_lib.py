@@ -368,6 +368,7 @@ ABI = {
     "af_conv_ca_work_units": (C.c_int, [C.POINTER(ConvDesc)] * 3 + [C.POINTER(C.c_int64)] + [C.POINTER(C.c_int)] * 3),
     "af_conv_cpa_work_units": (C.c_int, [C.POINTER(ConvDesc)] * 2 + [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "af_block_abc_work_units": (C.c_int, [C.POINTER(ConvDesc)] * 4 + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_int64)]),
+    "af_stem_work_units": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "af_maxpool3d": (C.c_int, [C.POINTER(PoolDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "af_avgpool_fc": (C.c_int, [C.POINTER(PoolDesc)] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
     "af_avgpool_fc_scores": (C.c_int, [C.POINTER(PoolDesc)] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4),

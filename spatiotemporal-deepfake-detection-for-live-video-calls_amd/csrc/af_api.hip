@@ -24,6 +24,21 @@ int device_cus() {
     return n;
 }
 
+// fewer frames than CUs (batch < 8 clips of 32 frames): every frame is cut into bands of pooled rows so that the whole chip
+// works; a band costs one extra (unstored) row pair, so no bands once the frames alone fill the CUs.  One resident workgroup per
+// CU (weights loaded once each)
+StemUnits stem_units(int frames, int hq) {
+    const int cus = device_cus();
+    StemUnits p;
+    int bands = frames >= cus ? 1 : cus / frames;
+    if (bands > hq / 4) bands = hq / 4 > 0 ? hq / 4 : 1;      // at least 4 pooled rows per band
+    p.band_rows = (hq + bands - 1) / bands;
+    p.bands = (hq + p.band_rows - 1) / p.band_rows;
+    p.units = frames * p.bands;
+    p.workgroups = p.units < cus ? p.units : cus;
+    return p;
+}
+
 static int run_one(const af_op& op, hipStream_t s) {
     switch (op.kind) {
         case AF_OP_STEM:

@@ -214,6 +214,11 @@ static inline int current_device() {
 struct DeviceOnce { bool done[kMaxDevices] = {}; };
 // compute units of the current device (cached per device; af_api.hip)
 int device_cus();
+// How the fused stems (af_stem_pool.hip, af_stem3.hip) cut `frames` frames of `hq` pooled rows into work units (frame, band of
+// pooled rows) and how many persistent workgroups walk them: both launchers run from this and af_stem_work_units answers from it
+// (af_api.hip)
+struct StemUnits { int bands, band_rows, units, workgroups; };
+StemUnits stem_units(int frames, int hq);
 
 // raise a kernel's dynamic-LDS limit once per (kernel instantiation, device)
 #define AF_SET_MAX_LDS(kernel_ptr, bytes, what)                                                                        \

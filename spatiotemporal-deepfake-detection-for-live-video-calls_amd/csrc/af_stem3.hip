@@ -291,23 +291,22 @@ struct Src3U8 {
 };
 
 template <int DT, int KT, bool PW>
-static int launch_stem3_pw(const Stem3Args& a, hipStream_t stream) {
+static int launch_stem3_pw(const Stem3Args& a, int grid, hipStream_t stream) {
     constexpr int NBLK = (KT * 21 + 3) / 4;
     // blocks per prefetch group: an even number of groups per row pair (27 blocks: 6 x 5; 16: 4 x 4; 6: 2 x 3; register budget: 2 x GB x 8 for the two sets)
     constexpr int GB = KT == 5 ? 5 : KT == 3 ? 4 : 3;
     const int lds = NBLK * 4 * 64 * 16 + (PW ? 3 : 1) * ((a.Wo + 15) / 16) * 16 * 64 * 2 + 2 * 64 * 4;
     if (lds > 160 * 1024) return set_error(AF_ERR_ARG, "stem3_pool: %d bytes of LDS needed", lds);
     AF_SET_MAX_LDS((&stem3_pool_kernel<DT, KT, PW, GB>), 160 * 1024, "stem3_pool");
-    const int cus = device_cus(), units = a.frames * a.bands;
-    hipLaunchKernelGGL((stem3_pool_kernel<DT, KT, PW, GB>), dim3(units < cus ? units : cus), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((stem3_pool_kernel<DT, KT, PW, GB>), dim3(grid), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("stem3_pool_kernel");
     return AF_OK;
 }
 
 template <int DT, int KT>
-static int launch_stem3_kt(const Stem3Args& a, hipStream_t stream) {
+static int launch_stem3_kt(const Stem3Args& a, int grid, hipStream_t stream) {
     // a free eighth wave (<= 7 column tiles) takes the pooling off the MFMA waves' critical path
-    return (a.Wo + 15) / 16 <= 7 ? launch_stem3_pw<DT, KT, true>(a, stream) : launch_stem3_pw<DT, KT, false>(a, stream);
+    return (a.Wo + 15) / 16 <= 7 ? launch_stem3_pw<DT, KT, true>(a, grid, stream) : launch_stem3_pw<DT, KT, false>(a, grid, stream);
 }
 
 template <typename Src>
@@ -401,18 +400,13 @@ extern "C" int af_stem_conv_bn_relu_maxpool_rgb3_ld(const af_conv_desc* d, const
     if (out_ld == 0) out_ld = 64;
     AF_REQUIRE(out_ld >= 64 && out_ld % 8 == 0, "stem3_pool: bad out_ld %d", out_ld);
     a.out_ld = out_ld;
-    {
-        const int cus = device_cus();
-        int bands = a.frames >= cus ? 1 : cus / a.frames;
-        if (bands > a.Hq / 4) bands = a.Hq / 4 > 0 ? a.Hq / 4 : 1;      // at least 4 pooled rows per band
-        a.band_rows = (a.Hq + bands - 1) / bands;
-        a.bands = (a.Hq + a.band_rows - 1) / a.band_rows;
-    }
+    const StemUnits cut = stem_units(a.frames, a.Hq);          // bands of pooled rows and the grid, as af_stem_pool.hip (af_api.hip)
+    a.bands = cut.bands; a.band_rows = cut.band_rows;
     a.in += (long long)(AF_STEM_PAD_T - d->pt) * a.Hp * a.row_bytes;
     hipStream_t s = (hipStream_t)stream;
     switch (d->kt) {
-        case 1: return with_dtype16(d->dtype, [&](auto dt) { return launch_stem3_kt<dt, 1>(a, s); });
-        case 3: return with_dtype16(d->dtype, [&](auto dt) { return launch_stem3_kt<dt, 3>(a, s); });
-        default: return with_dtype16(d->dtype, [&](auto dt) { return launch_stem3_kt<dt, 5>(a, s); });
+        case 1: return with_dtype16(d->dtype, [&](auto dt) { return launch_stem3_kt<dt, 1>(a, cut.workgroups, s); });
+        case 3: return with_dtype16(d->dtype, [&](auto dt) { return launch_stem3_kt<dt, 3>(a, cut.workgroups, s); });
+        default: return with_dtype16(d->dtype, [&](auto dt) { return launch_stem3_kt<dt, 5>(a, cut.workgroups, s); });
     }
 }

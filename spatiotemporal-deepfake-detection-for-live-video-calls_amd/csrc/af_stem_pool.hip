@@ -168,24 +168,21 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const StemPoolArgs a)
 }
 
 template <int DT, int KT>
-static int launch_stem_pool_kt(const StemPoolArgs& a, hipStream_t stream) {
-    const int g_cus = device_cus();
+static int launch_stem_pool_kt(const StemPoolArgs& a, int grid, hipStream_t stream) {
     const int lds = a.kt * 7 * 4 * 64 * 16 + ((a.Wo + 15) / 16) * 16 * 64 * 2;
     if (lds > 160 * 1024) return set_error(AF_ERR_ARG, "stem_pool: %d bytes of LDS needed", lds);
     AF_SET_MAX_LDS((&stem_pool_kernel<DT, KT>), 160 * 1024, "stem_pool");
-    const int units = a.frames * a.bands;
-    const int grid = units < g_cus ? units : g_cus;           // one resident workgroup per CU; weights loaded once each
     hipLaunchKernelGGL((stem_pool_kernel<DT, KT>), dim3(grid), dim3(512), lds, stream, a);
     AF_CHECK_LAUNCH("stem_pool_kernel");
     return AF_OK;
 }
 
 template <int DT>
-static int launch_stem_pool(const StemPoolArgs& a, hipStream_t stream) {
+static int launch_stem_pool(const StemPoolArgs& a, int grid, hipStream_t stream) {
     switch (a.kt) {
-        case 1: return launch_stem_pool_kt<DT, 1>(a, stream);
-        case 3: return launch_stem_pool_kt<DT, 3>(a, stream);
-        default: return launch_stem_pool_kt<DT, 5>(a, stream);
+        case 1: return launch_stem_pool_kt<DT, 1>(a, grid, stream);
+        case 3: return launch_stem_pool_kt<DT, 3>(a, grid, stream);
+        default: return launch_stem_pool_kt<DT, 5>(a, grid, stream);
     }
 }
 
@@ -212,16 +209,19 @@ extern "C" int af_stem_conv_bn_relu_maxpool(const af_conv_desc* d, const void* s
     a.kt = d->kt; a.To = to; a.Ho = ho; a.Wo = wo;
     a.Hq = (ho - 1) / 2 + 1; a.Wq = (wo - 1) / 2 + 1;
     a.frames = d->n * to;
-    // fewer frames than CUs (batch < 8 clips of 32 frames): cut every frame into bands of pooled rows so that the whole
-    // chip works; a band costs one extra (unstored) row pair, so no bands once the frames alone fill the CUs
-    {
-        const int cus = device_cus();
-        int bands = a.frames >= cus ? 1 : cus / a.frames;
-        if (bands > a.Hq / 4) bands = a.Hq / 4 > 0 ? a.Hq / 4 : 1;      // at least 4 pooled rows per band
-        a.band_rows = (a.Hq + bands - 1) / bands;
-        a.bands = (a.Hq + a.band_rows - 1) / a.band_rows;
-    }
+    const StemUnits cut = stem_units(a.frames, a.Hq);          // bands of pooled rows and the grid (af_api.hip)
+    a.bands = cut.bands; a.band_rows = cut.band_rows;
     a.in += (long long)(AF_STEM_PAD_T - d->pt) * a.Hp * a.Wp * 4 * dtype_size(d->dtype);
     hipStream_t s = (hipStream_t)stream;
-    return with_dtype16(d->dtype, [&](auto dt) { return launch_stem_pool<dt>(a, s); });
+    return with_dtype16(d->dtype, [&](auto dt) { return launch_stem_pool<dt>(a, cut.workgroups, s); });
+}
+
+extern "C" int af_stem_work_units(const af_conv_desc* d, int fused, int64_t* units, int* bands, int* workgroups) {
+    using namespace af;
+    AF_REQUIRE(d && units && bands && workgroups && (fused == 1 || fused == 2), "stem_work_units: bad argument");
+    AF_REQUIRE(d->dtype == AF_BF16 || d->dtype == AF_F16, "stem_work_units: 16-bit dtypes only");
+    AF_REQUIRE(d->n > 0 && d->to > 0 && d->ho > 0 && d->wo > 0 && d->wo <= 128, "stem_work_units: bad dims");
+    const StemUnits cut = stem_units(d->n * d->to, (d->ho - 1) / 2 + 1);
+    *units = cut.units; *bands = cut.bands; *workgroups = cut.workgroups;
+    return AF_OK;
 }

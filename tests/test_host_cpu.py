@@ -962,3 +962,49 @@ def test_conv111_and_small_matrices_cover_what_ships(monkeypatch):
     assert not missing, "%d shipped conv111 launches without a case in test_hip_conv111.py:\n%s" % (len(missing), "\n".join(missing))
     missing = sorted("%s (%s)" % (k, v) for k, v in shipped_small.items() if k not in covered_small)
     assert not missing, "%d shipped conv_small launches without a case in test_hip_conv_small.py:\n%s" % (len(missing), "\n".join(missing))
+
+
+def test_stem_matrix_covers_what_ships(monkeypatch):
+    """every stem launch of the three networks at batch 1..32 with the default switches - the first launch of every network - is a
+    case of tests/test_hip_stem_matrix.py, which runs it against fp64 on the GPU in the same class.  The fused stems (stem3_pool,
+    stem_pool): key = (kind, dtype, kT, 8-tile form, bands > 1, one-row last band, rounds class, unit map, out_ld != 64), with
+    (units, bands, workgroups) from af_stem_work_units - the function the launchers take their bands and grid from -, which answers
+    for 256 CUs where there is no device.  stem, tstem and tstem_pool3: key = (kind, dtype, kT, cout).  A change of the band rule,
+    the CU count or the 7-tile threshold that ships an untested class fails here."""
+    import ctypes as C
+    import plan_cases
+    from af_mi355x._lib import lib
+    matrix = _load_tests_module("test_hip_stem_matrix")
+    covered = matrix.covered_keys()
+    shipped = {}
+    for net, dtype, batch, setting, p in plan_cases.plans(monkeypatch):
+        stems = [launch for launch in p.launches if launch.kind in ("stem3_pool", "stem_pool", "stem", "tstem", "tstem_pool3")]
+        assert len(stems) == (2 if net == "slowfast_r50" else 1) and p.launches[0] in stems, (net, dtype, batch)
+        for launch in stems:
+            cv, (d,) = launch.convs["conv"], launch.descs
+            if launch.kind in ("stem3_pool", "stem_pool"):
+                units, bands, groups = C.c_int64(0), C.c_int(0), C.c_int(0)
+                fused = 2 if launch.kind == "stem3_pool" else 1
+                assert lib.af_stem_work_units(C.byref(d), fused, C.byref(units), C.byref(bands), C.byref(groups)) == 0
+                hq = (d.ho - 1) // 2 + 1
+                assert groups.value == min(units.value, 256) and units.value == d.n * d.to * bands.value and 1 <= bands.value <= max(1, hq // 4)
+                key = matrix.launch_key(launch.kind, dtype, cv.kernel[0], d.w, hq, bands.value, units.value, groups.value, launch.ld)
+                what = "%d units (%d bands) on %d workgroups, rows of %d" % (units.value, bands.value, groups.value, launch.ld)
+            else:
+                key = matrix.stem_case_key(launch.kind, dtype, cv.kernel[0], cv.cout)
+                what = "%d positions" % (d.n * d.to * d.ho * d.wo)
+            shipped.setdefault(key, "%s batch %d%s: %s" % (net, batch, setting, what))
+    # today 20 keys: stem3_pool per 16-bit dtype I3D's kT = 5 without bands on the XCD map in rounds "1", "1-2", "2", ">2" and with
+    # bands in "1", and SlowFast's kT = 1 with bands into rows of 80 (12); stem f32 kT 5 / 1 into 64 channels and kT 5 into 8 in all
+    # three dtypes (5); tstem f32 (1), tstem_pool3 (2)
+    assert len(shipped) >= 20, len(shipped)
+    assert {k[6] for k in shipped if k[0] == "stem3_pool"} == {"1", "1-2", "2", ">2"} and any(k[0] == "stem3_pool" and k[8] for k in shipped)
+    missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
+    assert not missing, "%d shipped stem launches without a case in test_hip_stem_matrix.py:\n%s" % (len(missing), "\n".join(missing))
+    # the query refuses what the launchers refuse
+    d = plan_cases.plan("i3d_r50", "bf16", 1).launches[0].descs[0]
+    units, bands, groups = C.c_int64(0), C.c_int(0), C.c_int(0)
+    assert lib.af_stem_work_units(C.byref(d), 3, C.byref(units), C.byref(bands), C.byref(groups)) == -1
+    assert lib.af_stem_work_units(C.byref(d), 2, None, C.byref(bands), C.byref(groups)) == -1
+    assert lib.af_stem_work_units(C.byref(d), 2, C.byref(units), C.byref(bands), C.byref(groups)) == 0
+    assert (units.value, bands.value, groups.value) == (256, 8, 256)
