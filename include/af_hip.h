@@ -1116,6 +1116,58 @@ int af_retinaface_postprocess_timed(const af_retinaface_desc* desc, const float*
                                     void* workspace, int64_t workspace_bytes, float* out_rows, int32_t* out_count, void* stream,
                                     float* ms);
 
+/* ---- device tracker (added within ABI 6) -----------------------------------------------------
+ * tracker.ByteTracker.update for many trackers in one launch (csrc/af_track_core.h, csrc/af_track.hip; the numpy statement
+ * is tests/bytetrack_ref.py): fp64, every sum in one written-down order, one wave per tracker.
+ *
+ * A tracker is af_bytetrack_state_bytes() bytes (8-byte aligned) that af_bytetrack_reset filled: reset writes a HOST block, a
+ * device tracker is a copy of one.  A state block belongs to one call of a launch.  An update writes one record of
+ * af_bytetrack_record_bytes() bytes per call:
+ *   int32 frame_id, overflow, n_online, n_tracked, n_lost, n_removed, reserved[2];
+ *   { double tlbr[4], score; int32 id, state, is_activated, reserved; } online[AF_TRACK_MAX_TRACKS];   the returned tracks, in order
+ *   int32 tracked_ids[AF_TRACK_MAX_TRACKS], lost_ids[AF_TRACK_MAX_TRACKS], removed_ids[AF_TRACK_MAX_TRACKS];
+ * removed_ids: the tracks removed by THIS update (a lost track that times out is named by two successive updates, as the
+ * reference appends it to removed_stracks twice).  overflow: 0, or AF_TRACK_OVERFLOW_DETS (more than AF_TRACK_MAX_DETS rows
+ * passed the start filter; the state is untouched), AF_TRACK_OVERFLOW_TRACKS (tracked + lost would exceed AF_TRACK_MAX_TRACKS;
+ * the tracker refuses every later update until it is reset), AF_TRACK_NOT_RESET.  Nothing is written outside the state blocks
+ * and the records.
+ *
+ * af_track_call.form: EMPTY (no detection: _nothing_detected); LIST (float32 rows x, y, w, h, score, ... `row_stride` floats
+ * apart, a detector's rows where it left them: a row is scaled back as YuNet.scale_rows does it - x, w and column 4 by scale_x,
+ * y, h by scale_y in fp64, cast to float32 - and enters when column 4 >= start_conf and max(w, h) >= start_min_size, compared in
+ * float32; column 4 is its score, as af_realtime.py:385 reads it; no second association); LIST64
+ * (fp64 rows x, y, w, h, score, no filter); ARRAY (fp64 rows x0, y0, x1, y1, score, divided by min(img_size[0] / img_info[1],
+ * img_size[1] / img_info[0]), split at track_thresh, with the second association).  The number of rows is *count_ptr when
+ * count_ptr is not NULL (device memory for af_bytetrack_update_calls), cut at max_rows, and `count` otherwise.
+ * af_bytetrack_update_calls: `calls` is a HOST array of 1 .. AF_TRACK_MAX_CALLS entries that travels in the launch arguments;
+ * states, rows, counts and records are device memory; one launch.  af_bytetrack_update_host runs the same source on the CPU
+ * for one call over host memory.  af_track_probe_f64: q[i] = x[i] / y[i], r[i] = sqrt(x[i]) in device code, one launch. */
+#define AF_TRACK_MAX_TRACKS 32
+#define AF_TRACK_MAX_DETS 32
+#define AF_TRACK_MAX_CALLS 64
+#define AF_TRACK_FORM_EMPTY 0
+#define AF_TRACK_FORM_LIST 1
+#define AF_TRACK_FORM_ARRAY 2
+#define AF_TRACK_FORM_LIST64 3
+#define AF_TRACK_OVERFLOW_DETS 1
+#define AF_TRACK_OVERFLOW_TRACKS 2
+#define AF_TRACK_NOT_RESET 3
+typedef struct af_track_call {
+    void* state;
+    const void* rows;
+    const int32_t* count_ptr;
+    int32_t count, max_rows, form, row_stride;
+    int32_t img_info[2], img_size[2];
+    float start_conf, start_min_size;
+    double scale_x, scale_y;
+} af_track_call;
+int64_t af_bytetrack_state_bytes(void);
+int64_t af_bytetrack_record_bytes(void);
+int af_bytetrack_reset(void* state, double track_thresh, double match_thresh, int buffer_size);
+int af_bytetrack_update_calls(const af_track_call* calls, int n_calls, void* records, void* stream);
+int af_bytetrack_update_host(const af_track_call* call, void* record);
+int af_track_probe_f64(const double* x, const double* y, double* q, double* r, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,4 +33,7 @@ def __getattr__(name):
     if name == "ByteTracker":
         from . import tracker
         return tracker.ByteTracker
+    if name == "DeviceByteTracker":
+        from . import device_tracker
+        return device_tracker.DeviceByteTracker
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -55,6 +55,18 @@ class FrameRect(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("frame", "rx", "ry", "ih", "iw", "x", "y", "reserved")]
 
 
+class TrackCall(C.Structure):
+    """af_track_call (include/af_hip.h, "device tracker")"""
+    _fields_ = [("state", C.c_void_p), ("rows", C.c_void_p), ("count_ptr", C.c_void_p), ("count", C.c_int32), ("max_rows", C.c_int32),
+                ("form", C.c_int32), ("row_stride", C.c_int32), ("img_info", C.c_int32 * 2), ("img_size", C.c_int32 * 2),
+                ("start_conf", C.c_float), ("start_min_size", C.c_float), ("scale_x", C.c_double), ("scale_y", C.c_double)]
+
+
+AF_TRACK_MAX_TRACKS, AF_TRACK_MAX_DETS, AF_TRACK_MAX_CALLS = 32, 32, 64
+AF_TRACK_FORM_EMPTY, AF_TRACK_FORM_LIST, AF_TRACK_FORM_ARRAY, AF_TRACK_FORM_LIST64 = 0, 1, 2, 3
+AF_TRACK_OVERFLOW_DETS, AF_TRACK_OVERFLOW_TRACKS, AF_TRACK_NOT_RESET = 1, 2, 3
+
+
 class QualitySums(C.Structure):
     _fields_ = [("s1", C.c_int64), ("s2", C.c_int64), ("n_px", C.c_int32), ("reserved", C.c_int32)]
 
@@ -419,6 +431,12 @@ ABI = {
     "af_retinaface_postprocess": (C.c_int, [C.POINTER(RetinafaceDesc)] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3),
     "af_retinaface_postprocess_timed": (C.c_int, [C.POINTER(RetinafaceDesc)] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3
                                         + [C.POINTER(C.c_float)]),
+    "af_bytetrack_state_bytes": (C.c_int64, []),
+    "af_bytetrack_record_bytes": (C.c_int64, []),
+    "af_bytetrack_reset": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "af_bytetrack_update_calls": (C.c_int, [C.POINTER(TrackCall), C.c_int, C.c_void_p, C.c_void_p]),
+    "af_bytetrack_update_host": (C.c_int, [C.POINTER(TrackCall), C.c_void_p]),
+    "af_track_probe_f64": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p]),
 }
 
 

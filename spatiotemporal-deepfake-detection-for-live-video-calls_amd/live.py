@@ -534,20 +534,29 @@ class _Detections:
 
     def __init__(self):
         self._host = None
+        self.extra = []                     # the host bytes of the last read's ``extra`` tensors, in order
 
-    def read(self, results, device, count=lambda key: None) -> List[np.ndarray]:
+    def read(self, results, device, count=lambda key: None, extra=()) -> List[np.ndarray]:
+        """``extra``: uint8 device tensors (a multiple of 4 bytes each, the device tracker's records) that ride in the same copy
+        and wait; their bytes are in ``self.extra`` afterwards"""
         packed, places, at = [], [], 0
         for rows, counts in results:                                                   # a result: its counts, then its first rows
             b, first = rows.shape[0], min(64, rows.shape[1])
             packed += [counts[:b].to(torch.float32), rows[:, :first].reshape(-1)]
             places.append((rows, first, at))
             at += b * (1 + first * 15)
+        riders = []
+        for t in extra:
+            riders.append((at, t.numel() // 4))
+            packed.append(t.reshape(-1).view(torch.float32))
+            at += t.numel() // 4
         if self._host is None or self._host.numel() < at:
             self._host = torch.empty(max(at, 16 * (1 + 64 * 15)), dtype=torch.float32, pin_memory=True)
         self._host[:at].copy_(torch.cat(packed), non_blocking=True)
         torch.cuda.current_stream(device).synchronize()
         count("wait")
         host, out = self._host.numpy(), []
+        self.extra = [host[lo:lo + n].view(np.uint8).copy() for lo, n in riders]
         for rows, first, at in places:
             for b in range(rows.shape[0]):
                 n = int(host[at + b])
@@ -580,14 +589,20 @@ class RealtimeCall:
 
     ``detect_size=(dw, dh)``: a detecting tick resizes the resident frame to dw x dh on the device (``frames.FrameResizer``,
     cv2.resize's arithmetic), runs the detector there and hands the tracker the rows scaled back to the frame (float64, YuNet's
-    row layout: ``YuNet.scale_rows`` with W / dw and H / dh, as demo2.py does).  ``None`` (the default) detects at full size."""
+    row layout: ``YuNet.scale_rows`` with W / dw and H / dh, as demo2.py does).  ``None`` (the default) detects at full size.
+
+    ``tracker="device"``: the tracker is a ``device_tracker.DeviceByteTracker`` - its launch follows the detector's on the rows where
+    they lie (the start filter and the scale-back happen there), its record rides in the read-back of the rows, so a step waits no
+    more often; a frame without detection enqueues the launch and reads nothing.  Every discrete result is the host tracker's, the
+    boxes agree to round-off.  ``"host"`` (the default) is ``tracker.ByteTracker``."""
 
     def __init__(self, network, detector=None, modelPath=None, conf: float = 0.8, clip_size: int = 32, stride: int = 52,
                  crop_scale: float = 0.6, drop_after: int = 90, detect_every: int = 1, mesh_every: int = 1, start_conf: float = 0.76,
                  start_min_size: int = 80, q_weighting: bool = True, q_min_size_soft: int = 64, q_min_size_hard: int = 32,
                  q_lap_soft: float = 20.0, q_lap_hard: float = 5.0, exclude_rect=(0.70, 0.70, 1.00, 1.00), score_is_real: bool = False,
                  track_thresh: float = 0.8, track_buffer: int = 90, match_thresh: float = 0.8, landmarks=None, size: int = 224,
-                 ring_frames: int = 128, max_batch: int = 16, channel_order: str = "bgr", detect_size=None):
+                 ring_frames: int = 128, max_batch: int = 16, channel_order: str = "bgr", detect_size=None,
+                 tracker: str = "host"):
         import collections
         from types import SimpleNamespace
         self.detect_size = _detect_size(detect_size)
@@ -600,8 +615,16 @@ class RealtimeCall:
         self.detector, self.landmarks = detector, landmarks
         self.call = self._ring_type(network, clip_size=clip_size, size=size, stride=stride, crop_scale=crop_scale, ring_frames=ring_frames,
                              max_batch=max_batch, drop_after=drop_after, channel_order=channel_order)
-        self.tracker = ByteTracker(SimpleNamespace(track_thresh=track_thresh, track_buffer=track_buffer, match_thresh=match_thresh,
-                                                   mot20=False), frame_rate=30.0)
+        if tracker not in ("host", "device"):
+            raise ValueError("realtime: tracker %r: \"host\" or \"device\"" % (tracker,))
+        tracker_args = SimpleNamespace(track_thresh=track_thresh, track_buffer=track_buffer, match_thresh=match_thresh, mot20=False)
+        self.tracker_mode = tracker
+        if tracker == "device":
+            from .device_tracker import DeviceByteTracker
+            self.tracker = DeviceByteTracker(tracker_args, frame_rate=30.0, device=_network_device(getattr(network, "network", network)))
+            self._track_pending = []             # [(records, [tracker])] enqueued and not read yet: they ride in the next read
+        else:
+            self.tracker = ByteTracker(tracker_args, frame_rate=30.0)
         self.detect_every, self.mesh_every = int(detect_every), int(mesh_every)
         self.start_conf, self.start_min_size = float(start_conf), int(start_min_size)
         self._gate = dict(q_weighting=bool(q_weighting), q_min_size_soft=int(q_min_size_soft), q_min_size_hard=int(q_min_size_hard),
@@ -621,8 +644,10 @@ class RealtimeCall:
     uploaded_bytes = property(lambda self: self.call.uploaded_bytes)
     purged = property(lambda self: self.call.purged)
 
-    def _detect(self, view) -> np.ndarray:
-        """the detector on the resident frame and the one read-back of its rows"""
+    def _detect(self, view, tracked=None) -> np.ndarray:
+        """the detector on the resident frame and the one read-back of its rows; with the device tracker (``tracked``: a list)
+        the tracker's launch follows the detector's on the rows where they lie, its record rides in the same read-back and the
+        tracks it returned are appended to ``tracked``"""
         if self.detect_size is not None:
             if self._resizer is None:
                 self._resizer = FrameResizer(view.device)
@@ -632,21 +657,38 @@ class RealtimeCall:
         else:
             rows, counts = self.detector.detect(view[None])
         with torch.cuda.device(rows.device):
-            found = self._detections.read([(rows, counts)], rows.device)[0]
+            if tracked is None:
+                found = self._detections.read([(rows, counts)], rows.device)[0]
+            else:
+                self._enqueue_tracker(self._rows_job(rows[0], counts[0:1], view.shape))
+                found = self._detections.read([(rows, counts)], rows.device, extra=[r for r, _ in self._track_pending])[0]
+                tracked += _absorb_records(self._track_pending, self._detections.extra)[self.tracker]
         return found if self.detect_size is None else _scale_back(found, view.shape, self.detect_size)
 
-    def _track(self, k: int, shape, dets):
+    def _rows_job(self, rows, count, shape):
+        """this call's device-tracker job on a detector's rows (N, 15) and count (1,), read in place"""
+        size = self.detect_size
+        return self.tracker.rows_job(rows, count, self.start_conf, self.start_min_size,
+                                     (1.0, 1.0) if size is None else (shape[1] / size[0], shape[0] / size[1]))
+
+    def _enqueue_tracker(self, job):
+        from .device_tracker import update_calls
+        self._track_pending.append((update_calls([job], self.tracker.device), [self.tracker]))
+
+    def _track(self, k: int, shape, dets, online=None):
         """:382-437 for frame `k`, whose detections are `dets` (None when the detector did not run on it): they are kept in
-        ``detections``, filtered into the tracker, and the tracks go through ``track_candidates``, whose result this returns"""
+        ``detections``, filtered into the tracker, and the tracks go through ``track_candidates``, whose result this returns.
+        ``online``: the tracks of this frame where the device tracker has filtered and tracked already"""
         H, W = shape[:2]
         tracks_in = []
         if dets is not None:
             self.detections = dets
-            for d in dets:                                                             # :382-386
+        if online is None:
+            for d in (dets if dets is not None else ()):                               # :382-386
                 d = np.asarray(d, dtype=np.float32)
                 if d[4] >= self.start_conf and max(d[2], d[3]) >= self.start_min_size:
                     tracks_in.append(STrack(d[:4], score=float(d[4])))
-        online = self.tracker.update(tracks_in, (H, W), (H, W))                        # :388
+            online = self.tracker.update(tracks_in, (H, W), (H, W))                    # :388
         return track_candidates(self.host, k, (H, W), dets, online, self.mesh_every, self.crop_scale, self.exclude_rect, self.landmarks,
                                 self.call.frame_view(k) if self.landmarks is not None else None)
 
@@ -663,8 +705,12 @@ class RealtimeCall:
     def step(self, frame: np.ndarray) -> List[Tuple]:
         call = self.call
         k = call.admit(frame)                                                          # :373-376, the one upload
-        dets = self._detect(call.frame_view(k)) if k % max(1, self.detect_every) == 0 else None      # :378-380
-        found = self._track(k, frame.shape, dets)
+        online = [] if self.tracker_mode == "device" else None
+        dets = self._detect(call.frame_view(k), online) if k % max(1, self.detect_every) == 0 else None      # :378-380
+        if online is not None and dets is None:                                        # no detection: enqueued, read with the next rows
+            with torch.cuda.device(self.tracker.device):
+                self._enqueue_tracker(self.tracker.empty_job())
+        found = self._track(k, frame.shape, dets, online)
         faces, alive, kept_boxes, _ = track_gate(self.host, found, self._frame_quality(found[0]) if found[0] else [], self._weight)
         results = call.advance(faces, alive)                                           # :445-499
         return self._after(results, kept_boxes)
@@ -704,6 +750,19 @@ class RealtimeCall:
         if not cand:
             cand = [(tid, area(b)) for tid, b in self.last_boxes.items()]
         return max(cand, key=lambda t: t[1])[0]
+
+
+def _absorb_records(pending, host_bytes) -> dict:
+    """the device tracker's records that came back: ``pending`` = [(records, [tracker, ...])] in the order they were enqueued,
+    ``host_bytes`` their bytes; every tracker absorbs its records in that order; -> {tracker: the tracks of its LAST record};
+    empties ``pending``"""
+    from .device_tracker import parse_records
+    last, came_back = {}, list(zip(pending, host_bytes))
+    del pending[:]                                                # before a tracker past its cap raises: a record is absorbed once
+    for (_, trackers), raw in came_back:
+        for tr, rec in zip(trackers, parse_records(raw)):
+            last[tr] = tr.absorb(rec)
+    return last
 
 
 # ---- many calls per device: the launches of one step shared by every call ---------------------------------------------------------
@@ -778,16 +837,17 @@ class ServerStats:
     """what a ``CallServer`` enqueued and waited for: ``last`` for the last step, ``total`` since the server was made, each with
     ``detect`` (calls of ``af_yunet_detect_frames``, or of a detector's ``detect_views``), ``quality``, ``warp`` (launches),
     ``replay`` (graph replays), ``wait`` (host waits for the device), ``convert`` (launches of ``af_yuv420_to_rgb_u8``),
-    ``yuv_copies`` (host-to-device copies of staged YUV planes), ``capture`` (launches of ``af_capture_to_stores_u8``) and ``resize``
-    (launches of ``af_resize_frames_u8``)"""
+    ``yuv_copies`` (host-to-device copies of staged YUV planes), ``capture`` (launches of ``af_capture_to_stores_u8``), ``resize``
+    (launches of ``af_resize_frames_u8``) and ``track`` (launches of ``af_bytetrack_update_calls``)"""
     KEYS = ("detect", "quality", "warp", "replay", "wait")
     YUV_KEYS = ("convert", "yuv_copies")       # appear in ``last`` / ``total`` once a step has YUV frames; read as 0 before
     CAPTURE_KEYS = ("capture",)                # likewise once a step has captured frames
     RESIZE_KEYS = ("resize",)                  # likewise once a call with a ``detect_size`` has detected
+    TRACK_KEYS = ("track",)                    # likewise once a call with ``tracker="device"`` has stepped: launches of ``af_bytetrack_update_calls``
 
     class _Counts(dict):
         def __missing__(self, key):
-            if key in ServerStats.YUV_KEYS or key in ServerStats.CAPTURE_KEYS or key in ServerStats.RESIZE_KEYS:
+            if key in ServerStats.YUV_KEYS or key in ServerStats.CAPTURE_KEYS or key in ServerStats.RESIZE_KEYS or key in ServerStats.TRACK_KEYS:
                 return 0
             raise KeyError(key)
 
@@ -820,7 +880,9 @@ class CallServer:
     ``CallState`` and frame ring.  ``detector``: a ``YuNet`` (or ``modelPath`` to build one with ``conf``), or any object with
     ``detect_views(views) -> (rows, counts)``.  ``detect_size=(dw, dh)`` (a call's own, ``None`` by default) detects that call's
     frames resized to dw x dh, as ``RealtimeCall`` does: calls of any frame sizes that share a detect size share one resize launch
-    and one ``detect_views``.
+    and one ``detect_views``.  ``tracker="device"`` (a call's own, ``"host"`` by default): the trackers of all such calls of a tick run
+    as one launch per 64 calls behind the ``detect_views`` launches - on their rows in place where they detected, without a detection
+    otherwise - and their records ride in the read-back of the rows; ``stats`` counts ``track``.
 
     A frame is a numpy array, a ``YuvFrame`` or a ``CapturedFrame`` (the mapping may mix them).  The ``CapturedFrame``s of a step are
     admitted together - one fill, one copy, one ``af_capture_to_stores_u8`` launch per 64 - as are its ``YuvFrame``s: the
@@ -865,6 +927,7 @@ class CallServer:
         self._scoring: Optional[_ClosedWindows] = None      # the clip buffer and the scorers, made when the first window closes
         self._done = None                  # recorded behind the last launch of every step
         self._detections = _Detections()
+        self._track_pending = []                  # the device trackers' records enqueued and not read yet
 
     _scorers = property(lambda self: self._scoring.scorers if self._scoring is not None else {})
 
@@ -934,11 +997,36 @@ class CallServer:
                 if key is not None:
                     self.stats.count(key, n)
         detecting = [i for i, (_, c, _) in enumerate(calls) if ticks[i] % max(1, c.detect_every) == 0]
+        on_device = [i for i, (_, c, _) in enumerate(calls) if c.tracker_mode == "device"]
+        online = {}
+
+        def trackers(places):
+            """behind the detector launches: one tracker launch per 64 calls with a device tracker - the calls that detected on
+            their rows where they lie (``places[j]`` = (rows, counts, b) of view j), the others without a detection"""
+            if not on_device:
+                return None
+            from .device_tracker import update_calls
+            view_of = {i: j for j, i in enumerate(detecting)}
+            jobs = []
+            for i in on_device:
+                c = calls[i][1]
+                if i in view_of:
+                    rows, counts, b = places[view_of[i]]
+                    jobs.append(c._rows_job(rows[b], counts[b:b + 1], calls[i][2].shape))
+                else:
+                    jobs.append(c.tracker.empty_job())
+            self._track_pending.append((update_calls(jobs, self.device), [calls[i][1].tracker for i in on_device]))
+            self.stats.count("track", -(-len(jobs) // 64))
+            return self._track_pending
+
+        def tracked():
+            got = _absorb_records(self._track_pending, self._detections.extra)
+            online.update({i: got[calls[i][1].tracker] for i in on_device})
         dets = dict(zip(detecting, self._detect([calls[i][1].call.frame_view(ticks[i]) for i in detecting],
-                                                [calls[i][1].detect_size for i in detecting])))                    # 2.
+                                                [calls[i][1].detect_size for i in detecting], trackers, tracked)))       # 2.
         found, wanted = [], []
         for i, (cid, c, frame) in enumerate(calls):                                        # 3. trackers, candidates
-            f = c._track(ticks[i], frame.shape, dets.get(i))
+            f = c._track(ticks[i], frame.shape, dets.get(i), online.get(i, []) if c.tracker_mode == "device" else None)
             found.append(f)
             ring, slot = c.call._ring.store, ticks[i] % c.call.ring_frames
             wanted += [(ring, c.call.channel_order, slot) + tuple(r) for r in f[0]]
@@ -960,12 +1048,14 @@ class CallServer:
             out[cid] = c._after(results, kept_boxes)
         return out
 
-    def _detect(self, views, sizes=None) -> List[np.ndarray]:
+    def _detect(self, views, sizes=None, trackers=None, tracked=None) -> List[np.ndarray]:
         """the rows of every view, in order: the views grouped by detect size where their call has one (``sizes[i]``) and by shape
         otherwise, one ``detect_views`` per 64 of a group, and the one read-back of all their rows (``_Detections``).  The views
         of one detect size, whatever their own sizes, are resized in one launch per 64 and detected where they land; their rows
         are scaled back per view."""
         if not views:
+            if trackers is not None:
+                trackers({})                       # enqueued; no rows, so nothing is read: the records ride in the next read
             return []
         from . import _lib
         sizes = list(sizes) if sizes is not None else [None] * len(views)
@@ -983,15 +1073,21 @@ class CallServer:
                 views[i] = small[at]
         for i, v in enumerate(views):
             groups.setdefault(("resized",) + sizes[i] if sizes[i] is not None else tuple(v.shape), []).append(i)
-        order, results = [], []
+        order, results, places = [], [], {}
         for members in groups.values():
             for lo in range(0, len(members), _lib.YUNET_MAX_LIST):
                 chunk = members[lo:lo + _lib.YUNET_MAX_LIST]
                 results.append(self.detector.detect_views([views[i] for i in chunk]))
                 self.stats.count("detect")
                 order += chunk
+                if trackers is not None:
+                    places.update({i: tuple(results[-1][:2]) + (b,) for b, i in enumerate(chunk)})
+        pending = trackers(places) if trackers is not None else None
+        read = self._detections.read(results, self.device, self.stats.count, [r for r, _ in pending or ()])
+        if pending:
+            tracked()
         out = [None] * len(views)
-        for i, rows in zip(order, self._detections.read(results, self.device, self.stats.count)):
+        for i, rows in zip(order, read):
             out[i] = rows if sizes[i] is None else _scale_back(rows, full[i].shape, sizes[i])
         return out
 

@@ -16,7 +16,13 @@ its score / quality read-back, a device synchronise).  Reported per N and leg: t
 the launches and waits per tick from server.stats (the in-turn leg's detector calls are counted, its waits follow from the code:
 2 per call, 3 on a close).  Both legs are warmed up by one whole run and alternate `--reps` times; `in_turn_spread` is the
 run-to-run spread of the in-turn leg's p50, against which a difference at N = 1 is to be read.  `ratio` = in_turn p50 / server
-p50.  Every phase runs under a time limit of its own.  Prints one JSON line and writes it to `--json`.  A run without a GPU fails."""
+p50.  Every phase runs under a time limit of its own.  Prints one JSON line and writes it to `--json`.  A run without a GPU fails.
+
+`--tracker host,device` measures something else with the same workload, ticks and repetitions: one CallServer per leg, the legs
+differing only in `tracker=`, alternating within the session after one warm-up run each; per N the tick times of both
+legs, `host_spread` (the run-to-run spread of the host leg's p50, the yardstick for a difference), `ratio` = host p50 / device p50
+and the launches and waits per tick; and `kernel`: the device time of one af_bytetrack_update_calls launch for 1, 4, 16, 32 and 64
+trackers that each follow two faces.  The default `--json` is then profiles/server_tracker_bench.json."""
 import argparse
 import json
 import os
@@ -83,7 +89,7 @@ def play_server(server, cids, frames, ticks):
         server.step(batch)
         times.append(time.perf_counter() - t0)
         for k, v in server.stats.last.items():
-            counts[k] += v
+            counts[k] = counts.get(k, 0) + v
     torch.cuda.synchronize()
     return times, {k: v / ticks for k, v in counts.items()}
 
@@ -100,6 +106,68 @@ def play_in_turn(calls, frames, ticks):
     return times, closes
 
 
+def tracker_kernel_times(n_list, launches=200):
+    """device time of one tracker launch: n trackers that each follow two faces, in steady state"""
+    from types import SimpleNamespace
+    from af_mi355x import device_tracker as dt
+    args = SimpleNamespace(track_thresh=0.8, track_buffer=90, match_thresh=0.8, mot20=False)
+    dev, out = torch.device("cuda:0"), {}
+    script = scripted_rows(launches + 20, FACES, seed=3000)
+    for n in n_list:
+        trackers = [dt.DeviceByteTracker(args, 30.0, device=dev) for _ in range(n)]
+        ticks = []
+        for rows in script:
+            batch = torch.from_numpy(np.stack([np.pad(rows, ((0, 16 - len(rows)), (0, 0)))] * n)).to(dev)
+            ticks.append((batch, torch.full((n,), len(rows), dtype=torch.int32, device=dev)))
+        records = torch.empty(n, dt.RECORD_BYTES, dtype=torch.uint8, device=dev)
+        start, stop = [torch.cuda.Event(enable_timing=True) for _ in script], [torch.cuda.Event(enable_timing=True) for _ in script]
+        for i, (batch, counts) in enumerate(ticks):
+            jobs = [tr.rows_job(batch[b], counts[b:b + 1], 0.76, 80) for b, tr in enumerate(trackers)]
+            start[i].record()
+            dt.update_calls(jobs, dev, records)
+            stop[i].record()
+        torch.cuda.synchronize()
+        online = [len(tr.absorb(rec)) for tr, rec in zip(trackers, dt.parse_records(records.cpu().numpy()))]
+        assert min(online) == FACES, online
+        ms = sorted(a.elapsed_time(b) for a, b in zip(start[20:], stop[20:]))
+        out["trackers%d" % n] = {"device_ms_p50": ms[len(ms) // 2], "device_ms_p95": ms[int(len(ms) * 0.95)], "launches": len(ms)}
+    return out
+
+
+def tracker_legs(args, net, yunet, frames, keywords, out):
+    from af_mi355x import live
+    legs = args.tracker.split(",")
+    assert legs[0] == "host" and set(legs) <= {"host", "device"} and len(legs) == 2, "--tracker host,device"
+    out.update(tool="bench_server --tracker", legs=legs)
+    for n in (int(v) for v in args.calls.split(",")):
+        scripts = scripts_for(n, args.ticks, args.stride)
+        runs, per_tick, p50s = {leg: [] for leg in legs}, {}, {leg: [] for leg in legs}
+        for rep in range(args.reps + 1):                          # repetition 0 warms up: rings, graphs, workspaces
+            for leg in legs:
+                with phase("calls %d: tracker=%s, repetition %d" % (n, leg, rep), args.phase_seconds):
+                    server = live.CallServer(net, detector=ScriptedYuNet(yunet, scripts), tracker=leg, **keywords)
+                    cids = [server.open() for _ in range(n)]
+                    times, per_tick[leg] = play_server(server, cids, frames, args.ticks)
+                    assert server.stats.total["replay"] > 0, "no window closed"
+                    for cid in cids:
+                        server.close(cid)
+                    del server
+                    torch.cuda.synchronize()
+                    torch.cuda.empty_cache()
+                    if rep:
+                        runs[leg].extend(times)
+                        p50s[leg].append(_pct(times, 0.5))
+        case = {leg: {"tick_s": _stats(runs[leg]), "ticks_per_s": len(runs[leg]) / sum(runs[leg]), "per_tick": per_tick[leg],
+                      "p50_per_repetition": p50s[leg]} for leg in legs}
+        case["host_spread"] = (max(p50s["host"]) - min(p50s["host"])) / min(p50s["host"]) if len(p50s["host"]) > 1 else None
+        case["ratio"] = case["host"]["tick_s"]["p50"] / case["device"]["tick_s"]["p50"]
+        out["cases"]["calls%d" % n] = case
+        print(n, json.dumps(case), file=sys.stderr, flush=True)
+    with phase("tracker kernel", args.phase_seconds):
+        out["kernel"] = tracker_kernel_times([1, 4, 16, 32, 64])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", default="1,4,16,32")
@@ -109,8 +177,11 @@ def main():
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--ring-frames", type=int, default=128)
     ap.add_argument("--phase-seconds", type=int, default=240)
-    ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "server_bench.json"))
+    ap.add_argument("--tracker", default=None, help="host,device: the two tracker modes of one CallServer instead of server / in_turn")
+    ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    if args.json is None:
+        args.json = os.path.join(ROOT, "profiles", "server_tracker_bench.json" if args.tracker else "server_bench.json")
     assert torch.cuda.is_available(), "bench_server needs a GPU"
     from af_mi355x import live, synth
     from af_mi355x.classifier import Classifier
@@ -130,7 +201,9 @@ def main():
            "dtype": args.dtype, "ring_frames": args.ring_frames,
            "detections": "scripted: the real YuNet runs on every frame for its cost, its rows are discarded (no face photographs)",
            "tick": "host-inclusive wall clock, all N calls, ends in a device synchronise", "cases": {}}
-    for n in (int(v) for v in args.calls.split(",")):
+    if args.tracker:
+        tracker_legs(args, net, yunet, frames, keywords, out)
+    for n in (int(v) for v in args.calls.split(",") if not args.tracker):
         scripts = scripts_for(n, args.ticks, args.stride)
         runs = {"server": [], "in_turn": []}
         per_tick, p50s, in_turn_detects, closes = {}, [], 0, 0
