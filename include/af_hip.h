@@ -1168,6 +1168,90 @@ int af_bytetrack_update_calls(const af_track_call* calls, int n_calls, void* rec
 int af_bytetrack_update_host(const af_track_call* call, void* record);
 int af_track_probe_f64(const double* x, const double* y, double* q, double* r, int n, void* stream);
 
+/* ---- the dataset evaluator's chunk stage on the device (added within ABI 6) -------------------------------------------------------
+ * What runner.VideoRunner does on the host per kept frame of a chunk - the detection rhythm, the smart start, the budget,
+ * filter_detections, ByteTracker.update, the id-switch count, the five-point pick with the mesh_every cache and get_crop_box
+ * (runner.py: the loop's host stage and track_stage) - for all frames of a chunk, in order, as ONE launch of one wave on
+ * the detector's rows where they lie (csrc/af_runner_core.h, csrc/af_runner.hip; the numpy statement is tests/runner_chunk_ref.py).
+ *
+ * A run is af_runner_state_bytes() bytes (8-byte aligned): the tracker's state block first, then the loop's scalars, prev_boxes /
+ * prev_ids and the five-point cache (one entry per tracker slot, tagged with the track id it belongs to, so a reused slot never
+ * serves another track's points).  af_runner_reset fills a HOST block; a device run is a copy of one.
+ *
+ * af_runner_chunk (host, travels in the launch arguments): rows - float32, frame j's rows at rows + j * max_rows * row_stride,
+ * row i `row_stride` (>= 15) floats on (x, y, w, h, score, five points); counts[j] rows of frame j, cut at max_rows; rows_floats
+ * - the floats readable behind `rows` (n_frames * max_rows * row_stride must fit); frame_idx[j] - the frame's index in the video;
+ * first_slot - frame j lies in slot first_slot + j of the frame store; the thresholds as the loop compares them: float32 for the
+ * detection filters and the start (a clause whose threshold is not positive is skipped; bottom_limit is
+ * float32(frame_h * (1 - exclude_bottom_frac)), formed by the caller, <= 0: no clause), fp64 for min_track_side and crop_scale.
+ *
+ * The chunk record, af_runner_record_bytes(n_frames) bytes (8-byte aligned):
+ *   af_runner_header;  af_runner_frame frames[AF_RUNNER_MAX_FRAMES];  af_runner_cand cands[n_frames * AF_TRACK_MAX_TRACKS];
+ * header: the loop's scalars after the chunk; overflow - 0 or an AF_TRACK_* code with overflow_frame the chunk position of the
+ * frame that refused (more than AF_TRACK_MAX_DETS rows past the filter: the state is untouched by that frame; more than
+ * AF_TRACK_MAX_TRACKS tracked + lost faces: the run refuses every later chunk); nothing of a later frame is written;
+ * n_cands; tiles_half / tiles_full - the tile totals of the quality launch in its two modes; bad - set by
+ * af_face_quality_table_u8 when it skipped a candidate.
+ * frames[j].flags: AF_RUNNER_NEED_DETECT, _DROPPED (before the start), _PROCESSED, _NOT_REACHED (behind the budget stop),
+ * _REFUSED; n_rows - the rows the filter left; ids[0 .. n_ids) - the tracks that passed min_track_side, in the tracker's order.
+ * cands, in track_stage's order: the frame's position in the chunk and its slot, the track id, the float32 box and five points
+ * in frame coordinates, the crop box (x1, y1, x2, y2), the first tile of its half-size and of its full-size image, flags
+ * (AF_RUNNER_CAND_BAD: the quality launch skipped it).
+ * af_runner_track_chunk: state, rows, counts and record are DEVICE memory; one workgroup of 64 lanes; nothing is written outside
+ * the state block and the record.  af_runner_track_chunk_host: the same source on the CPU over host memory.
+ *
+ * af_face_quality_table_u8: the quality launch (af_face_quality_stores_u8, or with `full` af_face_laplacian_stores_u8) with
+ * rectangles, slots and tile prefixes read from a chunk record in DEVICE memory: candidate k (k < min(n_cands, capacity)) is the
+ * rectangle (x1, y1) .. (x2, y2) of slot cands[k].slot of `store`, its sums go to sums[k]; sums[0 .. capacity) are cleared in
+ * front of the launch on `stream`.  A fixed grid strides over the record's tile total.  The kernel re-checks every candidate: a
+ * rectangle that leaves its frame, a slot outside the store or a tile prefix that does not fit is skipped - never read - and
+ * flagged (cands[k].flags, header.bad).  grey: null, or (tests) a DEVICE buffer of capacity * grey_stride bytes; candidate k's
+ * grey image goes to grey + k * grey_stride when it fits grey_stride. */
+#define AF_RUNNER_MAX_FRAMES 64
+#define AF_RUNNER_NEED_DETECT 1
+#define AF_RUNNER_DROPPED 2
+#define AF_RUNNER_PROCESSED 4
+#define AF_RUNNER_NOT_REACHED 8
+#define AF_RUNNER_REFUSED 16
+#define AF_RUNNER_CAND_BAD 1
+typedef struct af_runner_header {
+    int32_t started, consec, processed_after_start, stop;
+    int32_t id_switches, frames_seen, overflow, overflow_frame;
+    int32_t n_cands, tiles_half, tiles_full, bad;
+    int32_t n_frames, reserved[3];
+} af_runner_header;
+typedef struct af_runner_frame {
+    int32_t flags, n_rows, n_ids, reserved;
+    int32_t ids[AF_TRACK_MAX_TRACKS];
+} af_runner_frame;
+typedef struct af_runner_cand {
+    int32_t frame_pos, slot, tid, flags;
+    float tlbr[4];
+    float lm5[10];
+    int32_t box[4];
+    int32_t tile_half, tile_full;
+} af_runner_cand;
+typedef struct af_runner_chunk {
+    void* state;
+    const float* rows;
+    const int32_t* counts;
+    void* record;
+    int64_t rows_floats;
+    int32_t n_frames, max_rows, row_stride, first_slot;
+    int32_t frame_h, frame_w, detect_every, start_after_n;
+    int32_t mesh_every, budget_frames;
+    float start_conf, start_min_size, min_det_side, min_det_area, bottom_limit, reserved;
+    double min_track_side, crop_scale;
+    int32_t frame_idx[AF_RUNNER_MAX_FRAMES];
+} af_runner_chunk;
+int64_t af_runner_state_bytes(void);
+int64_t af_runner_record_bytes(int n_frames);
+int af_runner_reset(void* host_state, double track_thresh, double match_thresh, int buffer_size, int started);
+int af_runner_track_chunk(const af_runner_chunk* chunk, void* stream);
+int af_runner_track_chunk_host(const af_runner_chunk* chunk);
+int af_face_quality_table_u8(const af_store_ref* store, void* record, int capacity, int full, af_quality_sums* sums, void* grey,
+                             int64_t grey_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

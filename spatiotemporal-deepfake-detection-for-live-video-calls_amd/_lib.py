@@ -67,6 +67,22 @@ AF_TRACK_FORM_EMPTY, AF_TRACK_FORM_LIST, AF_TRACK_FORM_ARRAY, AF_TRACK_FORM_LIST
 AF_TRACK_OVERFLOW_DETS, AF_TRACK_OVERFLOW_TRACKS, AF_TRACK_NOT_RESET = 1, 2, 3
 
 
+AF_RUNNER_MAX_FRAMES = 64
+AF_RUNNER_NEED_DETECT, AF_RUNNER_DROPPED, AF_RUNNER_PROCESSED, AF_RUNNER_NOT_REACHED, AF_RUNNER_REFUSED = 1, 2, 4, 8, 16
+AF_RUNNER_CAND_BAD = 1
+
+
+class RunnerChunk(C.Structure):
+    """af_runner_chunk (include/af_hip.h, "chunk stage")"""
+    _fields_ = [("state", C.c_void_p), ("rows", C.c_void_p), ("counts", C.c_void_p), ("record", C.c_void_p), ("rows_floats", C.c_int64),
+                ("n_frames", C.c_int32), ("max_rows", C.c_int32), ("row_stride", C.c_int32), ("first_slot", C.c_int32),
+                ("frame_h", C.c_int32), ("frame_w", C.c_int32), ("detect_every", C.c_int32), ("start_after_n", C.c_int32),
+                ("mesh_every", C.c_int32), ("budget_frames", C.c_int32),
+                ("start_conf", C.c_float), ("start_min_size", C.c_float), ("min_det_side", C.c_float), ("min_det_area", C.c_float),
+                ("bottom_limit", C.c_float), ("reserved", C.c_float), ("min_track_side", C.c_double), ("crop_scale", C.c_double),
+                ("frame_idx", C.c_int32 * AF_RUNNER_MAX_FRAMES)]
+
+
 class QualitySums(C.Structure):
     _fields_ = [("s1", C.c_int64), ("s2", C.c_int64), ("n_px", C.c_int32), ("reserved", C.c_int32)]
 
@@ -437,6 +453,12 @@ ABI = {
     "af_bytetrack_update_calls": (C.c_int, [C.POINTER(TrackCall), C.c_int, C.c_void_p, C.c_void_p]),
     "af_bytetrack_update_host": (C.c_int, [C.POINTER(TrackCall), C.c_void_p]),
     "af_track_probe_f64": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p]),
+    "af_runner_state_bytes": (C.c_int64, []),
+    "af_runner_record_bytes": (C.c_int64, [C.c_int]),
+    "af_runner_reset": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int]),
+    "af_runner_track_chunk": (C.c_int, [C.POINTER(RunnerChunk), C.c_void_p]),
+    "af_runner_track_chunk_host": (C.c_int, [C.POINTER(RunnerChunk)]),
+    "af_face_quality_table_u8": (C.c_int, [C.POINTER(StoreRef), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 

@@ -189,6 +189,62 @@ __global__ __launch_bounds__(256) void face_quality_stores_kernel(const QualityS
     quality_tile<FULL>(r.first, r.pitch, r.w, r.h, tile - r.first_tile, r.bgr, a.sums + k, a.grey ? a.grey + r.grey_offset : nullptr);
 }
 
+// ---- the launch whose rectangles lie in a chunk record in device memory (af_hip.h, "chunk stage") ----
+// A fixed grid: workgroup b takes tiles b, b + gridDim.x, ... below the record's tile total, which it reads itself.  A tile finds
+// its candidate by bisection of the tile prefixes; the candidate is checked against the store before a byte of it is read.
+struct QualityTableArgs {
+    const unsigned char* base;
+    int64_t store_bytes, frame_stride, row_pitch;
+    int32_t n_frames, height, width, bgr;
+    af_runner_header* head;
+    af_runner_cand* cands;
+    af_quality_sums* sums;
+    unsigned char* grey;
+    int64_t grey_stride;
+    int32_t capacity, max_tiles;
+};
+constexpr int Q_TABLE_GRID = 1024;
+
+template <bool FULL>
+__global__ __launch_bounds__(256) void face_quality_table_kernel(const QualityTableArgs a) {
+    int n = a.head->n_cands;
+    n = n < 0 ? 0 : (n > a.capacity ? a.capacity : n);
+    int total = FULL ? a.head->tiles_full : a.head->tiles_half;
+    total = total < 0 ? 0 : (total > a.max_tiles ? a.max_tiles : total);
+    if (n == 0) return;
+    for (int tile = blockIdx.x; tile < total; tile += gridDim.x) {     // uniform in the workgroup
+        int lo = 0, hi = n - 1;                                        // the last candidate whose first tile is <= tile
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            const int first = FULL ? a.cands[mid].tile_full : a.cands[mid].tile_half;
+            if (first <= tile) lo = mid; else hi = mid - 1;
+        }
+        af_runner_cand* c = a.cands + lo;
+        const int x1 = c->box[0], y1 = c->box[1], x2 = c->box[2], y2 = c->box[3], slot = c->slot;
+        const int local = tile - (FULL ? c->tile_full : c->tile_half);
+        const long long w = (long long)x2 - x1, h = (long long)y2 - y1;
+        bool ok = slot >= 0 && slot < a.n_frames && x1 >= 0 && y1 >= 0 && w > 0 && h > 0 && x2 <= a.width && y2 <= a.height;
+        long long offset = 0;
+        if (ok) {
+            offset = (long long)slot * a.frame_stride + (long long)y1 * a.row_pitch + (long long)x1 * 3;
+            ok = offset + (h - 1) * a.row_pitch + w * 3 <= a.store_bytes;
+        }
+        if (ok) {
+            const int dw = FULL ? (int)w : max(1, (int)w / 2), dh = FULL ? (int)h : max(1, (int)h / 2);
+            ok = local >= 0 && local < ((dw + Q_TW - 1) / Q_TW) * ((dh + Q_TH - 1) / Q_TH);
+            if (ok) {
+                unsigned char* g = (a.grey && (long long)dw * dh <= a.grey_stride) ? a.grey + (long long)lo * a.grey_stride : nullptr;
+                quality_tile<FULL>(a.base + offset, a.row_pitch, (int)w, (int)h, local, a.bgr, a.sums + lo, g);
+            }
+        }
+        if (!ok && threadIdx.x == 0) {
+            atomicOr(&c->flags, AF_RUNNER_CAND_BAD);
+            atomicOr(&a.head->bad, 1);
+        }
+        __syncthreads();                                               // quality_tile's LDS is the next tile's too
+    }
+}
+
 // The host side of both entry points: the stores and the rectangles checked, one memset and one launch.  `listed`: a rectangle
 // names its store in af_frame_rect.reserved; otherwise every rectangle is of the one store and reserved is not read.  `full`: the
 // kernel's full-size mode.
@@ -252,4 +308,38 @@ extern "C" int af_face_quality_stores_u8(const af_store_ref* stores, int n_store
 extern "C" int af_face_laplacian_stores_u8(const af_store_ref* stores, int n_stores, const af_frame_rect* rects, int n, af_quality_sums* sums,
                                            void* grey, int64_t grey_bytes, void* stream) {
     return af::face_quality("face_laplacian_stores", stores, n_stores, true, true, rects, n, sums, grey, grey_bytes, stream);
+}
+
+extern "C" int af_face_quality_table_u8(const af_store_ref* store, void* record, int capacity, int full, af_quality_sums* sums, void* grey,
+                                        int64_t grey_stride, void* stream) {
+    using namespace af;
+    const char* who = "face_quality_table";
+    AF_REQUIRE(store && record && sums && store->base, "%s: null argument", who);
+    AF_REQUIRE(((uintptr_t)record & 7) == 0, "%s: the record is not 8-byte aligned", who);
+    AF_REQUIRE(capacity >= 0 && capacity <= AF_RUNNER_MAX_FRAMES * AF_TRACK_MAX_TRACKS, "%s: %d candidates (at most %d)", who, capacity,
+               AF_RUNNER_MAX_FRAMES * AF_TRACK_MAX_TRACKS);
+    AF_REQUIRE(!grey || grey_stride >= 1, "%s: a grey stride of %lld bytes", who, (long long)grey_stride);
+    const int rc = check_frame_store(who, -1, store->desc);
+    if (rc != AF_OK) return rc;
+    if (capacity == 0) return AF_OK;
+    const af_frame_store& d = store->desc;
+    const int64_t per_frame = (int64_t)((d.width + Q_TW - 1) / Q_TW) * ((d.height + Q_TH - 1) / Q_TH);
+    AF_REQUIRE(per_frame * capacity <= 0x7fffffff, "%s: too many pixels", who);
+    QualityTableArgs a;
+    a.base = (const unsigned char*)store->base;
+    a.store_bytes = d.store_bytes; a.frame_stride = d.frame_stride; a.row_pitch = d.row_pitch;
+    a.n_frames = d.n_frames; a.height = d.height; a.width = d.width; a.bgr = store->bgr ? 1 : 0;
+    a.head = (af_runner_header*)record;
+    a.cands = (af_runner_cand*)((char*)record + sizeof(af_runner_header) + AF_RUNNER_MAX_FRAMES * sizeof(af_runner_frame));
+    a.sums = sums; a.grey = (unsigned char*)grey; a.grey_stride = grey_stride;
+    a.capacity = capacity; a.max_tiles = (int32_t)(per_frame * capacity);
+    hipError_t e = hipMemsetAsync(sums, 0, sizeof(af_quality_sums) * (size_t)capacity, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(AF_ERR_LAUNCH, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
+    const unsigned grid = (unsigned)(a.max_tiles < Q_TABLE_GRID ? a.max_tiles : Q_TABLE_GRID);
+    if (full)
+        hipLaunchKernelGGL(face_quality_table_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(face_quality_table_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    AF_CHECK_LAUNCH("face_quality_table_kernel");
+    return AF_OK;
 }

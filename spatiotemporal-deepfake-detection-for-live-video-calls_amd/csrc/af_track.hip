@@ -44,6 +44,7 @@ __global__ __launch_bounds__(64) void bytetrack_kernel(TrkArgs a) {
     c.start_min_size = p.start_min_size;
     c.sx = p.sx;
     c.sy = p.sy;
+    c.pick = nullptr;
     trk::update(c, a.records + b, &sc);
 }
 
@@ -67,6 +68,7 @@ static int pack_call(const af_track_call& in, trk::Call* c, const char* who, int
     c->start_min_size = in.start_min_size;
     c->sx = in.scale_x;
     c->sy = in.scale_y;
+    c->pick = nullptr;
     if (in.form == AF_TRACK_FORM_EMPTY) {
         c->rows = nullptr;
         c->count_ptr = nullptr;

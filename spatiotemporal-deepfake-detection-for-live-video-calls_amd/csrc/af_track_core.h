@@ -62,7 +62,9 @@ struct Call {                                                 // af_track_call a
     int32_t limit, form, stride;
     float start_conf, start_min_size;
     double sx, sy;                                            // list form: the scale-back; array form: sx is the box divisor
+    const int32_t* pick;                                      // TRK_FORM_PICKED: the `limit` row indices that enter, in order
 };
+constexpr int32_t TRK_FORM_PICKED = 4;                        // the evaluator's loop (af_runner_core.h); not a form of af_track_call
 struct Scratch {                                              // LDS on the device
     double cost[TRK_T * TRK_D];
     double P[64], m[8], z[4];
@@ -310,7 +312,11 @@ TRK_HD void parse(const State* st, const Call& c, Scratch* sc) {
     for (int i = 0; i < n; ++i) {
         double t[4], score;
         int low = 0;
-        if (c.form == AF_TRACK_FORM_LIST) {
+        if (c.form == TRK_FORM_PICKED) {                       // runner.py:251: STrack(tlbr, score) - the corner enters as (w, h)
+            const float* r = (const float*)c.rows + (int64_t)c.pick[i] * c.stride;
+            const float x1 = r[0] + r[2], y1 = r[1] + r[3];
+            t[0] = r[0]; t[1] = r[1]; t[2] = x1; t[3] = y1; score = r[4];
+        } else if (c.form == AF_TRACK_FORM_LIST) {
             const float* r = (const float*)c.rows + (int64_t)i * c.stride;
             const float x = (float)((double)r[0] * c.sx), y = (float)((double)r[1] * c.sy);
             const float w = (float)((double)r[2] * c.sx), h = (float)((double)r[3] * c.sy);

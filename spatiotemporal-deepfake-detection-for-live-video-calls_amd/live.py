@@ -838,7 +838,8 @@ class ServerStats:
     ``detect`` (calls of ``af_yunet_detect_frames``, or of a detector's ``detect_views``), ``quality``, ``warp`` (launches),
     ``replay`` (graph replays), ``wait`` (host waits for the device), ``convert`` (launches of ``af_yuv420_to_rgb_u8``),
     ``yuv_copies`` (host-to-device copies of staged YUV planes), ``capture`` (launches of ``af_capture_to_stores_u8``), ``resize``
-    (launches of ``af_resize_frames_u8``) and ``track`` (launches of ``af_bytetrack_update_calls``)"""
+    (launches of ``af_resize_frames_u8``) and ``track`` (launches of ``af_bytetrack_update_calls``; in ``VideoRunner``, of
+    ``af_runner_track_chunk``)"""
     KEYS = ("detect", "quality", "warp", "replay", "wait")
     YUV_KEYS = ("convert", "yuv_copies")       # appear in ``last`` / ``total`` once a step has YUV frames; read as 0 before
     CAPTURE_KEYS = ("capture",)                # likewise once a step has captured frames

@@ -6,13 +6,16 @@ is marked "as written" where it stands), over device stages that already exist: 
 (csrc/af_quality.hip, both of its modes), the window warp out of a frame store and ``LiveScorer`` replays.  Where the live step
 (``live.RealtimeCall``) waits for the device twice per frame, this loop takes the frames ``detect_batch`` at a time: below the
 tracker (:540) nothing of the host stage depends on a quality result or a score, so a chunk goes through ONE detect, one round of
-host tracking, one half-size quality launch per 64 crop rectangles of the whole chunk, and the shared scoring.
+host tracking, one half-size quality launch per 64 crop rectangles of the whole chunk, and the shared scoring.  With
+``tracker="device"`` that round of host tracking is one launch on the detector's rows where they lie (csrc/af_runner_core.h),
+the quality launch takes its rectangles from that launch's record in device memory, and a chunk waits for the device once.
 
 Not built: ``cv2.VideoCapture`` (the caller decodes; ``frames`` is what ``cap.read()`` gives), FaceMesh (``landmarks`` is the hook
 where the reference has it; without it the loop behaves as the reference does when FaceMesh finds nothing), the CSV and metrics
 code of ``TEST2.main``, and ``flush_and_infer``'s skip of a clip whose alignment raises (a crop here is a rectangle of its frame and
 always fits its canvas; a planner refusal raises).  There is no CPU fallback: without the HIP library ``run`` fails.
 """
+import ctypes as C
 import platform
 import time
 from types import SimpleNamespace
@@ -44,7 +47,8 @@ DEFAULTS = dict(
 # detector's input size (YuNet here reads the frame at its own size, as :346 sets it), FaceMesh, autocast
 UNUSED = ("dataset_root", "out_csv_pervideo", "out_csv_summary", "list_path", "cfg_path", "ckpt_path", "detector_res", "dump_clip_scores",
           "dump_track_scores", "roi_scale", "mp_min_det", "mp_min_trk", "refine_size", "amp", "channels_last")
-OWN = dict(size=224, max_batch=16, frame_bytes=4 << 30, channel_order="bgr", detect_batch=16, landmarks=None)
+OWN = dict(size=224, max_batch=16, frame_bytes=4 << 30, channel_order="bgr", detect_batch=16, landmarks=None, tracker="host")
+TRACKERS = ("host", "device")
 POOL_METHODS = ("median", "mean", "topk", "topk_median", "percentile", "trimmed_mean", "logit_median", "adaptive")
 QSTAT_MAX = 50                                             # :297
 
@@ -309,6 +313,27 @@ def track_stage(st, frame_idx: int, slot: int, shape, dets, args, landmarks=None
     return out
 
 
+def record_candidates(st, rec, quality, frame_ids) -> List[_Candidate]:
+    """the chunk stage's record (``runner_device.parse_record``) and the figures ``[(min side, half-size lap, full-size lap or
+    None)]`` of its candidates as ``track_stage``'s candidates of the chunk's frames, measured; the records are formed with
+    ``track_stage``'s expressions"""
+    for fr in rec["frames"][:len(frame_ids)]:
+        for tid in fr["ids"][:int(fr["n_ids"])].tolist():
+            st.buffers.setdefault(tid, [])                                                     # :567
+    out = []
+    for i, cd in enumerate(rec["cands"][:int(rec["head"]["n_cands"])]):
+        if int(cd["flags"]):
+            raise RuntimeError("runner: the quality launch refused candidate %d of the chunk (slot %d, box %s)" % (i, int(cd["slot"]), cd["box"].tolist()))
+        x1, y1, x2, y2 = (int(v) for v in cd["box"])
+        top_left = np.array([[x1, y1]], dtype=np.float32)                                  # :600-606
+        record = ((cd["tlbr"].reshape(2, 2).astype(np.float32) - top_left).reshape(-1), cd["lm5"].astype(np.float32) - top_left,
+                  np.zeros((68, 2), np.float32), np.array([x1, y1, x2, y2], dtype=np.int32))
+        c = _Candidate(frame_ids[int(cd["frame_pos"])], int(cd["slot"]), int(cd["tid"]), record, (x1, y1, x2, y2))
+        c.min_side, c.lap, c.full = quality[i]
+        out.append(c)
+    return out
+
+
 def hard_limits_pass(min_side: float, lap: float, args) -> bool:
     """:292: the crop is neither too small nor too blurry to be used at all"""
     return not (min_side < args.q_min_size_hard or lap < args.q_lap_hard)
@@ -382,6 +407,65 @@ class _DeviceSide:
         self.count("wait")
         return out
 
+    # -- tracker="device" ---------------------------------------------------------------------------------------------------------
+    def open_tracker(self, plan):
+        """a fresh run on the device: the state block, and ONE buffer (with its pinned twin) for a chunk's record and the two
+        arrays of quality sums, so that all three come back in one copy"""
+        from . import _lib, runner_device as RD
+        from .frames import store_ref
+        self.plan, self._rd = plan, RD
+        frames = self.runner.detect_batch
+        self._cap, self._rec_bytes, rec = frames * RD.MAX_TRACKS, RD.record_bytes(frames), C.sizeof(_lib.QualitySums)
+        self._sums_bytes = self._cap * rec
+        with torch.cuda.device(self.device), torch.inference_mode(False):
+            self._run_state = torch.from_numpy(plan.reset()).to(self.device)
+            self._chunk_dev = torch.zeros(self._rec_bytes + 2 * self._sums_bytes, dtype=torch.uint8, device=self.device)
+            self._chunk_host = torch.zeros(self._chunk_dev.numel(), dtype=torch.uint8, pin_memory=True)
+        self._store_ref = store_ref(self.store, self.runner.channel_order)
+        self._rows = None                                             # the detector's tensors, alive until the next chunk
+
+    def track_chunk(self, frames, first_slot: int, frame_ids, full: bool):
+        """a chunk's upload, detection, host stage and quality measurement without a read-back in between: ``put``, ``detect``,
+        one ``af_runner_track_chunk`` on the rows where the detector left them, the half-size ``af_face_quality_table_u8`` on the
+        record where that launch left it - with ``full`` the full-size one as well -, one pinned copy of the record and both arrays
+        of sums, one wait.  Returns ``(record, [(min side, half-size lap, full-size lap or None)])``, a figure per candidate."""
+        from . import _lib
+        RD, n, lib = self._rd, len(frames), _lib.lib
+        with torch.cuda.device(self.device):
+            self.store.put(frames, first_slot)
+            rows, counts = self.runner.detector.detect(self.store.view(first_slot, n))
+            self.count("detect")
+            if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] < 15 or rows.dtype != torch.float32 or counts.dtype != torch.int32 or counts.numel() != n:
+                raise ValueError("runner: a detector's rows are (%d, N, >= 15) float32 with (%d,) int32 counts, got %s %s and %s %s"
+                                 % (n, n, tuple(rows.shape), rows.dtype, tuple(counts.shape), counts.dtype))
+            rows, counts = rows.contiguous(), counts.contiguous()
+            self._rows = (rows, counts)
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            base = self._chunk_dev.data_ptr()
+            chunk = self.plan.chunk(self._run_state.data_ptr(), rows.data_ptr(), counts.data_ptr(), base, rows.numel(), rows.shape[1], rows.shape[2],
+                                    first_slot, frame_ids)
+            _lib.check(lib.af_runner_track_chunk(C.byref(chunk), stream), "af_runner_track_chunk")
+            self.count("track")
+            for mode in ((0, 1) if full else (0,)):
+                sums = C.c_void_p(base + self._rec_bytes + mode * self._sums_bytes)
+                _lib.check(lib.af_face_quality_table_u8(C.byref(self._store_ref), C.c_void_p(base), n * RD.MAX_TRACKS, mode, sums, None, 0, stream),
+                           "af_face_quality_table_u8")
+                self.count("quality")
+            self._chunk_host.copy_(self._chunk_dev, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            self.count("wait")
+        host = self._chunk_host.numpy()
+        rec = RD.parse_record(host[:self._rec_bytes], n)
+        count = int(rec["head"]["n_cands"])
+        sums = np.frombuffer(host[self._rec_bytes:].tobytes(), dtype=live._SUMS_DTYPE).reshape(2, self._cap)
+        lap = lambda r: (int(r["n_px"]) * int(r["s2"]) - int(r["s1"]) * int(r["s1"])) / (int(r["n_px"]) * int(r["n_px"]))
+        quality = []
+        for i, cd in enumerate(rec["cands"][:count]):
+            x1, y1, x2, y2 = (int(v) for v in cd["box"])
+            bad = int(cd["flags"]) or int(sums[0, i]["n_px"]) == 0
+            quality.append((float(min(y2 - y1, x2 - x1)), None if bad else lap(sums[0, i]), lap(sums[1, i]) if full and not bad else None))
+        return rec, quality
+
     def score(self, group) -> np.ndarray:
         """the scores of one flush group ``[(tid, [(slot, record)])]``: per clip ONE fit over all of its buffered entries and the
         warp of its first ``clip_size`` frames (:401, :408-413), ``max_batch`` clips per warp launch and replay, one read-back"""
@@ -430,7 +514,16 @@ class VideoRunner:
     them as well, one read-back of both, then the gate and the bookkeeping in frame order.  A flush group is warped out of the store
     and replayed exactly as the reference forms it, so the padded batch sizes - and with them the score bits - do not depend on
     ``detect_batch``.  ``stats``: ``live.ServerStats`` (``last``: the last chunk or flush; ``chunks``: per chunk its counts and
-    ``closes``)."""
+    ``closes``).
+
+    ``tracker="device"`` (``"host"`` by default; no ``landmarks`` hook, ``detect_batch`` at most 64): the host stage of a chunk is
+    one launch of one wave (csrc/af_runner_core.h) that walks the chunk's frames on the detector's rows in device memory - the
+    rhythm, the start, the budget, the filters, the tracker in ``device_tracker``'s fixed-order fp64 (tests/bytetrack_ref.py), the
+    id-switch count, the five points and the crop boxes - and writes a chunk record; the quality launches take rectangles, slots
+    and tile prefixes from that record (``af_face_quality_table_u8``); the record and both arrays of sums come back in one pinned
+    copy behind ONE wait; the rows are not read back.  The gate and the books run on the host as before.  More than 32 rows past
+    the detection filters in a frame, or more than 32 tracked and lost faces, raise ``RuntimeError`` naming the frame.  ``stats``
+    counts ``track``, the chunk launches."""
 
     side_type = _DeviceSide
     DEFAULTS, UNUSED = DEFAULTS, UNUSED
@@ -449,6 +542,13 @@ class VideoRunner:
         self.clip_size = int(self.args.clip_size)
         if self.clip_size < 1 or self.detect_batch < 1 or self.args.batch_clips < 1 or self.args.mesh_every < 1:
             raise ValueError("runner: clip_size, detect_batch, batch_clips and mesh_every are at least 1")
+        self.tracker = own["tracker"]
+        if self.tracker not in TRACKERS:
+            raise ValueError("runner: tracker one of %s, not %r" % (", ".join(TRACKERS), self.tracker))
+        if self.tracker == "device" and self.landmarks is not None:
+            raise ValueError("runner: tracker=\"device\" has no landmarks hook (the hook reads a frame on the host between two tracker updates)")
+        if self.tracker == "device" and self.detect_batch > 64:
+            raise ValueError("runner: tracker=\"device\" takes at most 64 frames per chunk, detect_batch is %d" % self.detect_batch)
         if detector is None:
             if modelPath is None:
                 raise ValueError("runner: a detector, or the modelPath of the YuNet file to build one from")
@@ -491,6 +591,10 @@ class VideoRunner:
                              % (need, (need - _POOL_SLACK) // (H * W * 3), W, H, self.frame_bytes))
         self.stats, self.chunks, self.trace = live.ServerStats(), [], None                      # of this run
         side = self.side_type(self, shape, (need - _POOL_SLACK) // (H * W * 3))
+        on_device = self.tracker == "device"
+        if on_device:
+            from . import runner_device
+            side.open_tracker(runner_device.ChunkPlan(a, shape, detect_every, plan.budget_frames, real_fps))
 
         started, consec = (not a.smart_start), 0                                           # :349-352
         processed_after_start = frames_processed = 0
@@ -527,11 +631,27 @@ class VideoRunner:
             if not chunk:
                 break
             self.stats.begin()
-            side.put([f for _, f in chunk], base)
-            rows = side.detect(base, len(chunk))
-
             cands, kept_slots = [], False
-            for j, (k, _) in enumerate(chunk):                                             # the host stage, in frame order
+            if on_device:                                                                  # the host stage as one launch: DESIGN 28
+                short = bool(a.q_weighting) and len(st.qstat) < QSTAT_MAX
+                ids = [k for k, _ in chunk]
+                rec, quality = side.track_chunk([f for _, f in chunk], base, ids, short)
+                refused = runner_device.refusal(rec, ids)
+                if refused is not None:
+                    raise refused
+                head = rec["head"]
+                done = [k for k, fr in zip(ids, rec["frames"]) if int(fr["flags"]) & runner_device.PROCESSED]
+                started, consec, stop = bool(head["started"]), int(head["consec"]), bool(head["stop"])
+                processed_after_start = int(head["processed_after_start"])
+                frames_processed += len(done)
+                kept_slots = bool(done)
+                st.processed_ids += done
+                st.id_switches, st.frames_seen = int(head["id_switches"]), int(head["frames_seen"])
+                cands = record_candidates(st, rec, quality, ids)
+            else:
+                side.put([f for _, f in chunk], base)
+                rows = side.detect(base, len(chunk))
+            for j, (k, _) in enumerate(() if on_device else chunk):                        # the host stage, in frame order
                 need_detect = (not started) or (k % detect_every == 0) or (st.tracker.tracked_stracks == [])      # :496-500
                 dets = rows[j] if need_detect else None                                    # :503
                 if not started:                                                            # :505-508, as written: these frames are dropped
@@ -548,7 +668,7 @@ class VideoRunner:
                 st.processed_ids.append(k)
                 cands += track_stage(st, k, base + j, shape, dets, a, self.landmarks, side.view)
 
-            if cands:                                                                      # :598, for the whole chunk
+            if cands and not on_device:                                                    # :598, for the whole chunk
                 short = bool(a.q_weighting) and len(st.qstat) < QSTAT_MAX                  # :293, :297: is the second figure still wanted
                 for c, (min_side, lap, full) in zip(cands, side.quality(cands, short)):
                     c.min_side, c.lap, c.full = min_side, lap, full

@@ -2,6 +2,7 @@
 against RealtimeCall.step over the frames the loop keeps - the closest thing the tree offered before the runner.
 
     python tools/bench_runner.py [--frames 600] [--sizes 720,1080] [--reps 3] [--dtype f16] [--json profiles/runner_bench.json]
+    python tools/bench_runner.py --tracker host,device [--json profiles/runner_tracker_bench.json]
 
 Workload: a `--frames`-frame video of 720p and of 1080p (32 distinct seeded BGR noise frames in turn), 30 fps, with its frame
 count, and the evaluator's defaults (altfreezing/TEST2.py:963-1042: clip 32, stride 5, max_frame 400, detect_every 3, crop_scale 1,
@@ -17,7 +18,11 @@ are used only where that box and the detection overlap with IoU >= 0.4.
 Per size and leg: frames/s = frames processed / host-inclusive wall clock of the whole video (a leg ends in a score read-back, a
 device synchronise), the runner's latency_ms_clip_mean and its launches and waits.  Every leg is warmed up by one whole run; the
 legs then alternate `--reps` times; `spread` is (max - min) / min of a leg's frames/s over its repetitions, against which a
-difference between legs is to be read.  Every phase runs under a time limit of its own.  Prints one JSON line and writes it to
+difference between legs is to be read.
+`--tracker host,device`: the legs are runner1 and runner16 in each tracker mode (``VideoRunner(tracker=...)``: the host stage of a
+chunk on the host, or as one launch - DESIGN 28), alternating in one session, without the realtime leg; per leg also the launches
+and waits per chunk, and per size the device time of one ``af_runner_track_chunk`` launch over a 16-frame and a 1-frame chunk of
+the scripted rows (events around 200 launches, after 20 to warm up).  Every phase runs under a time limit of its own.  Prints one JSON line and writes it to
 `--json`.  A run without a GPU fails."""
 import argparse
 import json
@@ -73,6 +78,37 @@ class ScriptedYuNet:
         return rows.to(dev, non_blocking=True), counts.to(dev, non_blocking=True)
 
 
+def track_launch_ms(runner, shape, rows, n_frames, launches=200, warm=20):
+    """the device time of one ``af_runner_track_chunk`` over `n_frames` frames of the scripted rows: events around `launches`
+    launches that walk the video's frames in order (every frame processed, two tracked faces), after `warm` of them"""
+    import ctypes as C
+    from types import SimpleNamespace
+    from af_mi355x import _lib, runner_device as RD
+    plan = RD.ChunkPlan(SimpleNamespace(**runner.DEFAULTS), shape, runner.DEFAULTS["detect_every"], 1 << 30, 30.0)
+    state = torch.from_numpy(plan.reset()).cuda()
+    record = torch.zeros(RD.record_bytes(n_frames), dtype=torch.uint8, device="cuda")
+    chunks = []
+    for lo in range(0, (launches + warm) * n_frames, n_frames):
+        part = [rows[(lo + j) % len(rows)] for j in range(n_frames)]
+        laid = torch.zeros(n_frames, 16, 15, dtype=torch.float32)
+        for j, r in enumerate(part):
+            laid[j, :len(r)] = torch.from_numpy(r)
+        chunks.append((laid.cuda(), torch.tensor([len(r) for r in part], dtype=torch.int32).cuda(), list(range(lo, lo + n_frames))))
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    calls = [plan.chunk(state.data_ptr(), laid.data_ptr(), counts.data_ptr(), record.data_ptr(), laid.numel(), 16, 15, 0, ids)
+             for laid, counts, ids in chunks]
+    for i, c in enumerate(calls):
+        if i == warm:
+            begin.record()
+        _lib.check(_lib.lib.af_runner_track_chunk(C.byref(c), stream), "af_runner_track_chunk")
+    end.record()
+    torch.cuda.synchronize()
+    head = RD.parse_record(record.cpu().numpy(), n_frames)["head"]
+    assert not int(head["overflow"]) and int(head["frames_seen"]) == (launches + warm) * n_frames
+    return begin.elapsed_time(end) / launches
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=600)
@@ -80,8 +116,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--phase-seconds", type=int, default=240)
-    ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "runner_bench.json"))
+    ap.add_argument("--tracker", default="host", help="host (the legs above), or host,device: runner1 / runner16 in both tracker modes")
+    ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    trackers = args.tracker.split(",")
+    assert trackers in (["host"], ["host", "device"]), "--tracker host | host,device"
+    if args.json is None:
+        args.json = os.path.join(ROOT, "profiles", "runner_bench.json" if trackers == ["host"] else "runner_tracker_bench.json")
     assert torch.cuda.is_available(), "bench_runner needs a GPU"
     from af_mi355x import live, runner, synth
     from af_mi355x.classifier import Classifier
@@ -107,7 +148,8 @@ def main():
         with phase("%dp: detector" % size, args.phase_seconds):
             yunet = YuNet(MODEL, inputSize=[w, h], confThreshold=0.7, nmsThreshold=0.3, topK=5000)
         runners = {}
-        fps = {"runner1": [], "runner16": [], "realtime": []}
+        fps = {"runner1": [], "runner16": [], "realtime": []} if trackers == ["host"] else \
+            {"runner%d_%s" % (b, t): [] for b in (1, 16) for t in trackers}
         last = {}
         for rep in range(args.reps + 1):                          # repetition 0 warms up: stores, graphs, workspaces
             for leg in fps:
@@ -126,7 +168,8 @@ def main():
                         del call
                     else:
                         if leg not in runners:                        # one runner per leg, as batch_eval.py keeps its own for every video
-                            runners[leg] = runner.VideoRunner(net, detector=det, detect_batch=1 if leg == "runner1" else 16)
+                            runners[leg] = runner.VideoRunner(net, detector=det, detect_batch=1 if leg.startswith("runner1_") or leg == "runner1" else 16,
+                                                              tracker="device" if leg.endswith("_device") else "host")
                         r = runners[leg]
                         r.detector = det
                         t0 = time.perf_counter()
@@ -138,14 +181,24 @@ def main():
                         rate = res["frames_processed"] / elapsed
                         last[leg] = {"frames_processed": res["frames_processed"], "clips_scored": clips, "latency_ms_clip_mean": res["latency_ms_clip_mean"],
                                      "stats": res["stats"], "gpu_mem_alloc_peak_mb": res["gpu_mem_alloc_peak_mb"], "video_score": res["video_score"]}
+                        with_frames = [c for c in r.chunks if c["frames"]]
+                        last[leg]["per_chunk"] = {k: sum(c.get(k, 0) for c in with_frames) / len(with_frames)
+                                                  for k in ("detect", "track", "quality", "wait", "warp", "replay")}
                     if rep:
                         fps[leg].append(rate)
                     torch.cuda.empty_cache()
         case = {}
         for leg, v in fps.items():
             case[leg] = dict(last[leg], frames_per_s=statistics.median(v), frames_per_s_runs=v, spread=(max(v) - min(v)) / min(v))
-        case["runner16_over_runner1"] = case["runner16"]["frames_per_s"] / case["runner1"]["frames_per_s"]
-        case["runner16_over_realtime"] = case["runner16"]["frames_per_s"] / case["realtime"]["frames_per_s"]
+        if trackers == ["host"]:
+            case["runner16_over_runner1"] = case["runner16"]["frames_per_s"] / case["runner1"]["frames_per_s"]
+            case["runner16_over_realtime"] = case["runner16"]["frames_per_s"] / case["realtime"]["frames_per_s"]
+        else:
+            for b in (1, 16):
+                case["runner%d_device_over_host" % b] = case["runner%d_device" % b]["frames_per_s"] / case["runner%d_host" % b]["frames_per_s"]
+                assert case["runner%d_device" % b]["video_score"] == case["runner%d_host" % b]["video_score"], "the two modes disagree"
+            with phase("%dp: the track launch alone" % size, args.phase_seconds):
+                case["track_launch_device_ms"] = {str(n): track_launch_ms(runner, (h, w, 3), rows, n) for n in (16, 1)}
         case["frame_size"], case["frames_kept"] = [h, w], len(kept)
         out["cases"]["%dp" % size] = case
         print(size, json.dumps(case), file=sys.stderr, flush=True)
