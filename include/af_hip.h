@@ -654,7 +654,8 @@ int af_face_laplacian_stores_u8(const af_store_ref* stores, int n_stores, const 
  * of frame stores: one launch converts up to AF_YUV_MAX_FRAMES frames that may differ in size, format, destination store and byte
  * order.  Arithmetic: OpenCV's cvtColor(..., COLOR_YUV2BGR_NV12 / _I420) - fixed-point BT.601, limited range, integer only, one
  * (U, V) per 2 x 2 block of Y without interpolation; stated in csrc/af_yuv.hip and equal, byte for byte, to the numpy restatement
- * tests/yuv_ref.py (unpinned against cv2 itself, absent where this is built).  Not built: full range, BT.709, 4:2:2 / 4:4:4, 10-bit.
+ * tests/yuv_ref.py (unpinned against cv2 itself, absent where this is built).  Other layouts, depths and colours: af_yuv_to_rgb_ex_u8
+ * below.
  *
  * af_yuv_frame (host description of one frame): y - DEVICE pointer of the Y plane, h rows of w bytes y_pitch apart; u - the first
  * chroma plane: the interleaved plane (h / 2 rows of w bytes) when `interleaved`, else the first of two planes of h / 2 rows of
@@ -690,6 +691,83 @@ typedef struct af_yuv_item {
 } af_yuv_item;
 int af_yuv420_plan_u8(const af_yuv_frame* frames, int n, const af_store_ref* stores, int n_stores, af_yuv_item* items);
 int af_yuv420_to_rgb_u8(const af_yuv_item* items, int n, void* stream);
+
+/* ---- YUV frames of more layouts, depths and colours into frame stores (added within ABI 6) -------------------------------------------
+ * af_yuv420_to_rgb_u8's launch for what webcams (packed 4:2:2), MJPEG decoders (full range, planar 4:2:2 / 4:4:4), HD decoders (BT.709)
+ * and 10-bit decoders (P010) hand over: one launch converts up to AF_YUV_MAX_FRAMES frames that may differ in size, layout, bit depth,
+ * colour matrix, range, destination store and byte order.  It also converts the four 4:2:0 layouts of the launch above, to the same
+ * bytes at colour 0.  Nothing is interpolated: a (U, V) serves its 2 x 2, 2 x 1 or single pixel(s).  The output is 8-bit.
+ *
+ * layout (AF_YUV_LAYOUT_*)   planes                                                             chroma
+ *   420P   i420 / yv12       y (h, w), u, v (h / 2, w / 2)                                      2 x 2
+ *   420SP  nv12 / nv21       y (h, w), u = interleaved (h / 2, w)                               2 x 2
+ *   422P   i422              y (h, w), u, v (h, w / 2)                                          2 x 1
+ *   422SP  nv16              y (h, w), u = interleaved (h, w)                                   2 x 1
+ *   444P   i444              y, u, v (h, w)                                                     1 x 1
+ *   422PK  yuy2 uyvy yvyu    y = one packed plane (h, 2 w): 4 bytes per pixel pair              2 x 1
+ *   420SP16 p010             y (h, w), u = interleaved (h / 2, w) of uint16, value = v >> 6     2 x 2
+ *   420P16  i010             y (h, w), u, v (h / 2, w / 2) of uint16, value = min(v, 1023)      2 x 2
+ * order: planar and semi-planar layouts - 0: U is the first chroma byte / plane, 1: V is; 422PK - 0: Y0 U Y1 V, 1: U Y0 V Y1,
+ * 2: Y0 V Y1 U.  w is even; h is even where chroma is halved vertically; pitches are in bytes; the planes and pitches of the uint16
+ * layouts are even.  matrix - 0: BT.601, 1: BT.709; full_range - 0: limited (Y 16..235, or 64..940), 1: full.
+ *
+ * Arithmetic: OpenCV's form (color_yuv.simd.hpp), int32 with an arithmetic shift:
+ *     y = max(0, Y - Yoff) * CY;  u = U - Cmid;  v = V - Cmid
+ *     R = clamp((y + 2^19 + CVR v) >> 20)   G = clamp((y + 2^19 + CVG v + CUG u) >> 20)   B = clamp((y + 2^19 + CUB u) >> 20)
+ * Yoff: 16 (limited 8-bit), 64 (limited 10-bit), 0 (full); Cmid: 128 or 512.  Row 0 of AF_YUV_COLOUR_TABLES is OpenCV's own table
+ * (BT.601, limited, 8-bit), so the packed 4:2:2 layouts at colour 0 are OpenCV's COLOR_YUV2BGR_YUY2 / _UYVY / _YVYU.  Every other row
+ * is this library's: from Kr, Kb = 0.299, 0.114 (BT.601) or 0.2126, 0.0722 (BT.709) as exact rationals, scaled by 255/219 and 255/224
+ * (limited 8-bit), 255/876 and 255/896 (limited 10-bit), 1 (full 8-bit) or 255/1023 (full 10-bit), each coefficient rounded half up
+ * to 2^-20.  Rows: { CY, CVR, CVG, CUG, CUB } at index 4 * ten_bit + 2 * full_range + matrix.  Stated in numpy by
+ * tests/yuv_formats_ref.py, which re-derives the rows.
+ *
+ * af_yuv_plan_ex_u8 (host only) fills items[0 .. n) and refuses, with AF_ERR_ARG, what af_yuv420_plan_u8 refuses and an unknown
+ * layout, order, matrix or range, and an odd address or pitch of a uint16 plane.  af_yuv_to_rgb_ex_u8 takes the HOST table (it travels
+ * to the kernel by value), checks codes, sizes, pitches and the first_tile prefix again and trusts the pointers.  The kernel reads no
+ * byte outside [plane, plane + pitch * (rows - 1) + row bytes) and writes exactly the h rows of 3 w bytes of each destination frame.
+ * Not built: NV24 / NV42, packed 10-bit, 12-bit, BT.2020, chroma siting / interpolation. */
+#define AF_YUV_LAYOUT_420P 0
+#define AF_YUV_LAYOUT_420SP 1
+#define AF_YUV_LAYOUT_422P 2
+#define AF_YUV_LAYOUT_422SP 3
+#define AF_YUV_LAYOUT_444P 4
+#define AF_YUV_LAYOUT_422PK 5
+#define AF_YUV_LAYOUT_420SP16 6
+#define AF_YUV_LAYOUT_420P16 7
+#define AF_YUV_LAYOUTS 8
+#define AF_YUV_COLOUR_TABLES                                                                                  \
+    {                                                                                                         \
+        {1220542, 1673527, -852492, -409993, 2116026},     /* BT.601 limited  8-bit: OpenCV's */             \
+        {1220945, 1879825, -558796, -223607, 2215014},     /* BT.709 limited  8-bit */                       \
+        {1048576, 1470104, -748826, -360853, 1858077},     /* BT.601 full     8-bit */                       \
+        {1048576, 1651297, -490864, -196424, 1945738},     /* BT.709 full     8-bit */                       \
+        {305236, 418389, -213115, -102698, 528805},        /* BT.601 limited 10-bit */                       \
+        {305236, 469956, -139699, -55902, 553753},         /* BT.709 limited 10-bit */                       \
+        {261375, 366448, -186658, -89949, 463157},         /* BT.601 full    10-bit */                       \
+        {261375, 411614, -122356, -48962, 485008},         /* BT.709 full    10-bit */                       \
+    }
+typedef struct af_yuv_frame_ex {
+    const void* y;                 /* DEVICE pointers: the Y plane, or the packed plane of 422PK */
+    const void* u;                 /* the first chroma plane in memory (the interleaved one of a semi-planar layout); NULL for 422PK */
+    const void* v;                 /* the second chroma plane of a planar layout, else NULL */
+    int64_t y_pitch, c_pitch;      /* bytes */
+    int32_t h, w;
+    int32_t layout, order;
+    int32_t matrix, full_range;
+    int32_t store, slot;
+} af_yuv_frame_ex;
+typedef struct af_yuv_item_ex {
+    const void* y;
+    const void* c0;
+    const void* c1;
+    void* dst;
+    int32_t y_pitch, c_pitch, dst_pitch;
+    int32_t first_tile;
+    uint16_t h, w;
+    uint8_t layout, order, bgr, colour;      /* colour: 2 * full_range + matrix */
+} af_yuv_item_ex;
+int af_yuv_plan_ex_u8(const af_yuv_frame_ex* frames, int n, const af_store_ref* stores, int n_stores, af_yuv_item_ex* items);
+int af_yuv_to_rgb_ex_u8(const af_yuv_item_ex* items, int n, void* stream);
 
 /* ---- cv2.resize of resident frames (added within ABI 6) -----------------------------------------------------------------------
  * cv2.resize(frame, (dw, dh)) with the default INTER_LINEAR on frames that sit in frame stores: one launch resizes up to

@@ -115,6 +115,24 @@ class YuvItem(C.Structure):
 YUV_MAX_FRAMES, YUV_RUN, YUV_TILE = 64, 8, 256
 
 
+class YuvFrameEx(C.Structure):
+    """af_yuv_frame_ex: one YUV frame of any built layout, depth and colour on the device and the store slot it is converted into"""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_pitch", C.c_int64), ("c_pitch", C.c_int64),
+                ("h", C.c_int32), ("w", C.c_int32), ("layout", C.c_int32), ("order", C.c_int32), ("matrix", C.c_int32),
+                ("full_range", C.c_int32), ("store", C.c_int32), ("slot", C.c_int32)]
+
+
+class YuvItemEx(C.Structure):
+    """af_yuv_item_ex: what af_yuv_plan_ex_u8 fills and af_yuv_to_rgb_ex_u8 launches over"""
+    _fields_ = [("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p), ("dst", C.c_void_p), ("y_pitch", C.c_int32),
+                ("c_pitch", C.c_int32), ("dst_pitch", C.c_int32), ("first_tile", C.c_int32), ("h", C.c_uint16), ("w", C.c_uint16),
+                ("layout", C.c_uint8), ("order", C.c_uint8), ("bgr", C.c_uint8), ("colour", C.c_uint8)]
+
+
+# AF_YUV_LAYOUT_*
+YUV_420P, YUV_420SP, YUV_422P, YUV_422SP, YUV_444P, YUV_422PK, YUV_420SP16, YUV_420P16 = range(8)
+
+
 class ResizeJob(C.Structure):
     """af_resize_job: frame `frame` of store `store` -> dh rows of dw pixels at the device pointer dst"""
     _fields_ = [("store", C.c_int32), ("frame", C.c_int32), ("dst", C.c_void_p), ("dst_pitch", C.c_int64), ("dh", C.c_int32), ("dw", C.c_int32)]
@@ -362,6 +380,8 @@ ABI = {
     "af_face_laplacian_stores_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "af_yuv420_plan_u8":(C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "af_yuv420_to_rgb_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "af_yuv_plan_ex_u8":(C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "af_yuv_to_rgb_ex_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "af_resize_table_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
     "af_resize_plan_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "af_resize_frames_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

@@ -7,7 +7,8 @@
 //     y = max(0, Y - 16) * 1220542;  u = U - 128;  v = V - 128
 //     R = clamp((y + 2^19 + 1673527 v) >> 20)   G = clamp((y + 2^19 - 852492 v - 409993 u) >> 20)   B = clamp((y + 2^19 + 2116026 u) >> 20)
 // in int32 (the largest magnitude is 5.6e8) with arithmetic shifts; a 2 x 2 block of Y shares one (U, V), nothing is interpolated.
-// Full range, BT.709, 4:2:2 / 4:4:4 and 10-bit formats are not built.
+// Full range, BT.709, 4:2:2 / 4:4:4 and 10-bit formats are af_yuv_formats.hip's; not built: NV24 / NV42, 12-bit, BT.2020, chroma
+// siting / interpolation.
 //
 // Shape: memory-bound, 1.5 bytes in and 3 bytes out per pixel.  A lane owns a run of 8 pixels of two rows (one chroma row): 8 + 8
 // bytes of Y, 8 of chroma in, 24 + 24 bytes out.  The runs of an item are numbered row pair by row pair; a workgroup of 256 lanes
@@ -25,11 +26,10 @@
 // bytes.  No load is rounded down to an aligned address or widened past the pair, so no byte outside a plane's rows or outside the
 // h * w * 3 destination bytes is touched.
 #include "af_common.h"
+#include "af_yuv_runs.h"
 
 namespace af {
 
-constexpr int YUV_RUN = 8;                          // pixels of a row one lane converts
-constexpr int YUV_TILE = 256;                       // runs per workgroup
 constexpr int YUV_CY = 1220542, YUV_CUB = 2116026, YUV_CUG = -409993, YUV_CVG = -852492, YUV_CVR = 1673527;
 constexpr int YUV_SHIFT = 20, YUV_HALF = 1 << 19;
 
@@ -43,42 +43,6 @@ static_assert(sizeof(YuvArgs) <= 4096, "kernel arguments");
 static inline int64_t yuv_tiles(int h, int w) {
     const int64_t runs = (int64_t)(h / 2) * ((w + YUV_RUN - 1) / YUV_RUN);
     return (runs + YUV_TILE - 1) / YUV_TILE;
-}
-
-__device__ __forceinline__ unsigned clamp_u8(int v) { return (unsigned)min(max(v, 0), 255); }
-
-// N bytes (4 or 8) from p as little-endian dwords, by the widest naturally aligned loads p allows.  Reads [p, p + N) and no more.
-template <int N>
-__device__ __forceinline__ void load_bytes(const unsigned char* p, unsigned (&d)[N / 4]) {
-    const unsigned a = (unsigned)(uintptr_t)p;
-    if ((a & 3) == 0) {
-#pragma unroll
-        for (int i = 0; i < N / 4; ++i) d[i] = ((const unsigned*)p)[i];
-    } else if ((a & 1) == 0) {
-#pragma unroll
-        for (int i = 0; i < N / 4; ++i) d[i] = (unsigned)((const unsigned short*)p)[2 * i] | ((unsigned)((const unsigned short*)p)[2 * i + 1] << 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < N / 4; ++i)
-            d[i] = (unsigned)p[4 * i] | ((unsigned)p[4 * i + 1] << 8) | ((unsigned)p[4 * i + 2] << 16) | ((unsigned)p[4 * i + 3] << 24);
-    }
-}
-
-// 24 bytes (six little-endian dwords) to p.  Writes [p, p + 24) and no more.
-__device__ __forceinline__ void store_run(unsigned char* p, const unsigned (&d)[6]) {
-    const unsigned a = (unsigned)(uintptr_t)p;
-    if ((a & 3) == 0) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) ((unsigned*)p)[i] = d[i];
-    } else if ((a & 3) == 2) {
-        *(unsigned short*)p = (unsigned short)d[0];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) ((unsigned*)(p + 2))[i] = (d[i] >> 16) | (d[i + 1] << 16);
-        *(unsigned short*)(p + 22) = (unsigned short)(d[5] >> 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 24; ++i) p[i] = (unsigned char)(d[i >> 2] >> (8 * (i & 3)));
-    }
 }
 
 // the chroma terms of one (U, V): what is added to y for R, G and B
@@ -107,18 +71,6 @@ __device__ __forceinline__ void convert_run(const unsigned (&y)[2], const Chroma
         out[3 * q + 0] = px[4 * q] | (px[4 * q + 1] << 24);
         out[3 * q + 1] = (px[4 * q + 1] >> 8) | (px[4 * q + 2] << 16);
         out[3 * q + 2] = (px[4 * q + 2] >> 16) | (px[4 * q + 3] << 8);
-    }
-}
-
-// two pixels (6 bytes) to p, which need not be aligned at all
-__device__ __forceinline__ void store_pair(unsigned char* p, unsigned p0, unsigned p1) {
-    if (((unsigned)(uintptr_t)p & 1) == 0) {
-        ((unsigned short*)p)[0] = (unsigned short)p0;
-        ((unsigned short*)p)[1] = (unsigned short)((p0 >> 16) | (p1 << 8));
-        ((unsigned short*)p)[2] = (unsigned short)(p1 >> 8);
-    } else {
-        p[0] = (unsigned char)p0; p[1] = (unsigned char)(p0 >> 8); p[2] = (unsigned char)(p0 >> 16);
-        p[3] = (unsigned char)p1; p[4] = (unsigned char)(p1 >> 8); p[5] = (unsigned char)(p1 >> 16);
     }
 }
 

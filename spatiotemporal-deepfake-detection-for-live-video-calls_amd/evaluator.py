@@ -393,7 +393,7 @@ class FrameStore(_Resident):
         view) costs a strided host pass here instead of a memcpy per band.
 
         A list of ``YuvFrame`` (a list is all numpy or all ``YuvFrame``) is converted on the way: host planes go tightly into
-        a pinned slot (1.5 bytes per pixel), one copy moves them to the slot's device twin and one ``af_yuv420_to_rgb_u8`` launch
+        a pinned slot (1.5 to 3 bytes per pixel), one copy moves them to the slot's device twin and one ``YuvConverter`` launch
         per staging slot writes the store's slots in its ``channel_order``; device-resident planes are read where they are.
         A list of ``CapturedFrame`` goes the same way through ``af_capture_to_stores_u8``: only each frame's rectangle is staged."""
         from . import _lib

@@ -1,14 +1,17 @@
-"""Frames on their way into and out of the frame stores: YUV 4:2:0 frames in, downscaled detector batches out.
+"""Frames on their way into and out of the frame stores: YUV frames in, downscaled detector batches out.
 
-YUV 4:2:0 frames as a caller has them - what a WebRTC stack (I420), a hardware decoder (NV12) or ffmpeg / PyAV (yuv420p) hands over -
-and their way into the frame stores: ``YuvFrame`` names the planes, ``YuvConverter`` stages host planes through one pinned slot and
-one copy and converts every frame of a call to it, whatever its size, format, store and byte order, in one launch of
-``af_yuv420_to_rgb_u8`` per ``AF_YUV_MAX_FRAMES`` frames (csrc/af_yuv.hip).
+YUV frames as a caller has them - what a WebRTC stack (I420), a hardware decoder (NV12, P010), a webcam (YUY2 / UYVY), an MJPEG
+decoder (full-range planar 4:2:2 / 4:4:4) or ffmpeg / PyAV hands over - and their way into the frame stores: ``YuvFrame`` names the
+planes, the colour matrix and the range, ``YuvConverter`` stages host planes through one pinned slot and one copy and converts every
+frame of a call to it, whatever its size, format, depth, colour, store and byte order, in one launch per ``AF_YUV_MAX_FRAMES`` frames:
+``af_yuv420_to_rgb_u8`` (csrc/af_yuv.hip) when all frames are 8-bit 4:2:0 at OpenCV's colour, else ``af_yuv_to_rgb_ex_u8``
+(csrc/af_yuv_formats.hip).
 
-The conversion is OpenCV's ``cvtColor(..., COLOR_YUV2BGR_NV12 / _I420)``: fixed-point BT.601, limited range, one (U, V) per 2 x 2
-block of Y.  It equals the numpy restatement of OpenCV's code (tests/yuv_ref.py) byte for byte and is unpinned against cv2 itself,
-which is absent where this is built.  Not built: full-range and BT.709 matrices, 4:2:2 / 4:4:4, 10-bit formats.  There is no CPU
-fallback: without the HIP library the conversion fails.
+The conversion has OpenCV's fixed-point form; at BT.601 limited range it is OpenCV's ``cvtColor(..., COLOR_YUV2BGR_NV12 / _I420 /
+_YUY2 ...)``, the other tables (BT.709, full range, 10-bit) are derived in include/af_hip.h.  One (U, V) per chroma block, nothing
+interpolated.  It equals the numpy statements tests/yuv_ref.py and tests/yuv_formats_ref.py byte for byte and is unpinned against cv2
+itself, which is absent where this is built.  Not built: NV24 / NV42, packed 10-bit, 12-bit, BT.2020, chroma siting / interpolation.
+There is no CPU fallback: without the HIP library the conversion fails.
 
 ``FrameResizer`` is the other direction: ``cv2.resize(frame, (dw, dh))`` (the default ``INTER_LINEAR``) of frames that already sit on
 the device - slots of frame stores, views, a batch - into one detector batch, in one launch of ``af_resize_frames_u8`` per
@@ -30,31 +33,42 @@ import torch
 
 from ._staging import _COPY_THREADS, _SPLIT_BYTES, PinnedRing, cuda_device, stage_rects
 
-# format -> (chroma is one interleaved plane, the first chroma byte / plane in memory is V)
+# the 8-bit 4:2:0 formats of ``af_yuv420_to_rgb_u8``: format -> (chroma is one interleaved plane, the first chroma byte / plane in memory is V)
 FORMATS = {"nv12": (True, False), "nv21": (True, True), "i420": (False, False), "yv12": (False, True)}
+# every format ``YuvFrame`` takes -> (AF_YUV_LAYOUT_ code, component order code) of ``af_yuv_to_rgb_ex_u8`` (include/af_hip.h)
+YUV_FORMATS = {"nv12": (1, 0), "nv21": (1, 1), "i420": (0, 0), "yv12": (0, 1), "i422": (2, 0), "nv16": (3, 0), "i444": (4, 0),
+               "yuy2": (5, 0), "uyvy": (5, 1), "yvyu": (5, 2), "p010": (6, 0), "i010": (7, 0)}
+# layout code -> (planes: "planar" (y, u, v), "semi" (y, uv) or "packed" (y alone), rows of Y per chroma row, pixels per (U, V) in a row,
+# bytes per sample)
+YUV_LAYOUTS = {0: ("planar", 2, 2, 1), 1: ("semi", 2, 2, 1), 2: ("planar", 1, 2, 1), 3: ("semi", 1, 2, 1), 4: ("planar", 1, 1, 1),
+               5: ("packed", 1, 2, 1), 6: ("semi", 2, 2, 2), 7: ("planar", 2, 2, 2)}
+MATRICES = {"bt601": 0, "bt709": 1}
 _FRAME_ALIGN = 16         # a frame's planes start on a 16-byte boundary of the staging slot: aligned vector loads for the usual widths
 
 
-def _plane(name: str, p):
-    """checks one plane; returns (is a device tensor, rows, row bytes, pitch)"""
+def _plane(name: str, p, sample: int = 1):
+    """checks one plane of `sample`-byte samples; returns (is a device tensor, rows, row bytes, pitch in bytes)"""
+    np_type, torch_type = (np.uint8, torch.uint8) if sample == 1 else (np.uint16, torch.uint16)
     if isinstance(p, np.ndarray):
-        dev, dtype_ok, strides = False, p.dtype == np.uint8, p.strides
+        dev, dtype_ok, strides = False, p.dtype == np_type, p.strides
     elif isinstance(p, torch.Tensor):
         if not p.is_cuda:
             raise ValueError("yuv: plane %s is a CPU tensor: planes are numpy arrays or CUDA tensors" % name)
-        dev, dtype_ok, strides = True, p.dtype == torch.uint8, tuple(p.stride())
+        dev, dtype_ok, strides = True, p.dtype == torch_type, tuple(st * sample for st in p.stride())
     else:
         raise ValueError("yuv: plane %s is a %s: planes are numpy arrays or CUDA tensors" % (name, type(p).__name__))
     if not dtype_ok or p.ndim != 2:
-        raise ValueError("yuv: plane %s must be a 2-D uint8 array" % name)
-    rows, row = int(p.shape[0]), int(p.shape[1])
+        raise ValueError("yuv: plane %s must be a 2-D uint%d array" % (name, 8 * sample))
+    rows, row = int(p.shape[0]), int(p.shape[1]) * sample
     if rows < 1 or row < 1:
-        raise ValueError("yuv: plane %s is empty (%d x %d)" % (name, rows, row))
-    if row > 1 and strides[1] != 1:
+        raise ValueError("yuv: plane %s is empty (%d x %d)" % (name, rows, p.shape[1]))
+    if p.shape[1] > 1 and strides[1] != sample:
         raise ValueError("yuv: plane %s has element stride %d: the bytes of a row must be contiguous" % (name, strides[1]))
     pitch = int(strides[0]) if rows > 1 else row
     if pitch < row:
         raise ValueError("yuv: plane %s has row pitch %d, shorter than its row of %d bytes" % (name, pitch, row))
+    if sample == 2 and (pitch % 2 or _address(p) % 2):
+        raise ValueError("yuv: plane %s has an odd address or row pitch (%d): uint16 planes are 2-byte aligned" % (name, pitch))
     return dev, rows, row, pitch
 
 
@@ -73,26 +87,50 @@ class ConvertedFrame:
 
 
 class YuvFrame(ConvertedFrame):
-    """One YUV 4:2:0 frame: ``YuvFrame(fmt, y, u=None, v=None, uv=None)``.
+    """One YUV frame: ``YuvFrame(fmt, y, u=None, v=None, uv=None, *, matrix="bt601", full_range=False)``.
 
-    ``fmt``: ``"nv12"`` / ``"nv21"`` (``y`` and one interleaved plane ``uv`` of (h / 2, w) bytes: U, V, U, V ... - V first for nv21) or
-    ``"i420"`` / ``"yv12"`` (``y``, ``u`` and ``v`` of (h / 2, w / 2) bytes each; the two differ only in the order of the planes in
-    a packed buffer, which ``from_packed`` knows).  Planes are 2-D uint8 with unit element stride and a row stride of at least the
-    row; ``h`` and ``w`` are even, as OpenCV asks.  Either all planes are numpy arrays, or all are CUDA ``torch`` tensors on the
-    device of the store they go to.  ``shape`` is ``(h, w, 3)``, the shape of the converted frame.
+    ``fmt`` and the planes it takes (h rows, w pixels; ``w`` is even, ``h`` is even where chroma is halved vertically):
+
+    ==========================  ================================================================================  ========
+    ``nv12`` ``nv21``           ``y`` (h, w) and ``uv`` (h / 2, w): U, V, U, V ... - V first for nv21             2 x 2
+    ``i420`` ``yv12``           ``y``, ``u`` and ``v`` (h / 2, w / 2); the two differ only in ``from_packed``     2 x 2
+    ``yuy2`` ``uyvy`` ``yvyu``  one packed plane (h, 2 w), handed in as ``y``: Y0 U Y1 V / U Y0 V Y1 / Y0 V Y1 U  2 x 1
+    ``i422``                    ``y`` (h, w), ``u`` and ``v`` (h, w / 2)                                          2 x 1
+    ``nv16``                    ``y`` (h, w) and ``uv`` (h, w), U first                                           2 x 1
+    ``i444``                    ``y``, ``u`` and ``v`` (h, w)                                                     1 x 1
+    ``p010``                    ``y`` (h, w) and ``uv`` (h / 2, w) of uint16, the value in bits 15..6             2 x 2
+    ``i010``                    ``y`` (h, w), ``u`` and ``v`` (h / 2, w / 2) of uint16, the value in the low bits 2 x 2
+    ==========================  ================================================================================  ========
+
+    ``matrix``: ``"bt601"`` or ``"bt709"``; ``full_range``: Y spans 0..255 (JFIF) instead of 16..235.  At the defaults the four
+    4:2:0 formats and the packed 4:2:2 ones are OpenCV's ``cvtColor``; every other table is this project's (include/af_hip.h says
+    how it is derived).  A (U, V) serves the pixels of its block; nothing is interpolated.  The stored frame is 8-bit.
+
+    Planes are 2-D uint8 (uint16 for the 10-bit formats, at even addresses and pitches) with unit element stride and a row stride of
+    at least the row.  Either all planes are numpy arrays, or all are CUDA ``torch`` tensors on the device of the store they go to.
+    ``shape`` is ``(h, w, 3)``, the shape of the converted frame.
 
     Host planes are copied (into a pinned slot) before the call that takes the frame returns.  Device planes are read where they
     are, on the stream that is current when the frame is handed in: the caller guarantees they are ready on that stream and stay
     unchanged until the work the call enqueued has run."""
 
-    __slots__ = ("fmt", "y", "u", "v", "uv", "shape", "on_device", "interleaved", "swap_uv", "_planes")
+    __slots__ = ("fmt", "y", "u", "v", "uv", "shape", "on_device", "interleaved", "swap_uv", "matrix", "full_range", "layout", "order", "_planes")
 
-    def __init__(self, fmt: str, y, u=None, v=None, uv=None):
-        if fmt not in FORMATS:
-            raise ValueError("yuv: format %r is not one of %s" % (fmt, ", ".join(sorted(FORMATS))))
+    def __init__(self, fmt: str, y, u=None, v=None, uv=None, *, matrix: str = "bt601", full_range: bool = False):
+        if fmt not in YUV_FORMATS:
+            raise ValueError("yuv: format %r is not one of %s" % (fmt, ", ".join(sorted(YUV_FORMATS))))
+        if matrix not in MATRICES:
+            raise ValueError("yuv: format %r: matrix %r is not one of %s" % (fmt, matrix, ", ".join(sorted(MATRICES))))
         self.fmt, self.y, self.u, self.v, self.uv = fmt, y, u, v, uv
-        self.interleaved, self.swap_uv = FORMATS[fmt]
-        if self.interleaved:
+        self.matrix, self.full_range = matrix, bool(full_range)
+        self.layout, self.order = YUV_FORMATS[fmt]
+        kind, vdiv, hdiv, sample = YUV_LAYOUTS[self.layout]
+        self.interleaved, self.swap_uv = kind == "semi", kind == "semi" and self.order == 1
+        if kind == "packed":
+            if u is not None or v is not None or uv is not None:
+                raise ValueError("yuv: format %r takes one packed plane of (h, 2 w) bytes, handed in as y" % fmt)
+            named = [("y", y)]
+        elif kind == "semi":
             if uv is None or u is not None or v is not None:
                 raise ValueError("yuv: %s takes y and uv (one interleaved chroma plane)" % fmt)
             named = [("y", y), ("uv", uv)]
@@ -100,58 +138,80 @@ class YuvFrame(ConvertedFrame):
             if u is None or v is None or uv is not None:
                 raise ValueError("yuv: %s takes y, u and v" % fmt)
             named = [("y", y), ("u", u), ("v", v)]
-            self.swap_uv = False                                  # the planes are named: their order in memory does not matter
-        checked = [_plane(n, p) for n, p in named]
+            self.order = 0                                        # the planes are named: their order in memory does not matter
+        checked = [_plane(n, p) if sample == 1 else _plane(n, p, sample) for n, p in named]
         if len({c[0] for c in checked}) != 1:
             raise ValueError("yuv: planes are all numpy arrays or all CUDA tensors, not mixed")
         self.on_device = checked[0][0]
         if self.on_device and len({p.device for _, p in named}) != 1:
             raise ValueError("yuv: the planes are on different devices")
-        h, w = checked[0][1], checked[0][2]
-        if h % 2 or w % 2:
-            raise ValueError("yuv: a 4:2:0 frame has even height and width, not %d x %d" % (h, w))
-        want = (h // 2, w) if self.interleaved else (h // 2, w // 2)
+        h, w = checked[0][1], checked[0][2] // sample
+        if kind == "packed":
+            if w % 4:
+                raise ValueError("yuv: a packed %s plane has 4 bytes per pixel pair, not rows of %d bytes" % (fmt, w))
+            w //= 2
+        if w % 2 or (vdiv == 2 and h % 2):
+            if vdiv == 2:
+                raise ValueError("yuv: a 4:2:0 frame (%s) has even height and width, not %d x %d" % (fmt, h, w))
+            raise ValueError("yuv: a %s frame has even width, not %d x %d" % (fmt, h, w))
+        want = (h // vdiv, w if kind == "semi" else w // hdiv)
         for (n, _), c in zip(named[1:], checked[1:]):
-            if (c[1], c[2]) != want:
-                raise ValueError("yuv: plane %s is %d x %d, %d x %d for a %s frame of %d x %d" % (n, c[1], c[2], want[0], want[1], fmt, h, w))
-        if not self.interleaved and checked[1][3] != checked[2][3]:
+            if (c[1], c[2] // sample) != want:
+                raise ValueError("yuv: plane %s is %d x %d, %d x %d for a %s frame of %d x %d" % (n, c[1], c[2] // sample, want[0], want[1], fmt, h, w))
+        if kind == "planar" and checked[1][3] != checked[2][3]:
             raise ValueError("yuv: planes u and v have row pitches %d and %d: one chroma pitch per frame" % (checked[1][3], checked[2][3]))
         self.shape = (h, w, 3)
         self._planes = [(p, c[1], c[2], c[3]) for (_, p), c in zip(named, checked)]
 
     @classmethod
-    def from_packed(cls, buf, h: int, w: int, fmt: str) -> "YuvFrame":
-        """the ``(h * 3 / 2, w)`` uint8 array OpenCV and most decoders use for a 4:2:0 frame (numpy or a CUDA tensor): h rows of Y,
-        then the chroma as `fmt` lays it out.  Views of `buf`, no copies.  The planar formats need `buf` contiguous (a chroma row is
-        half a row of `buf`); nv12 / nv21 take any row pitch."""
-        if fmt not in FORMATS:
-            raise ValueError("yuv: format %r is not one of %s" % (fmt, ", ".join(sorted(FORMATS))))
+    def from_packed(cls, buf, h: int, w: int, fmt: str, *, matrix: str = "bt601", full_range: bool = False) -> "YuvFrame":
+        """the one 2-D array OpenCV and most decoders use for a planar or semi-planar frame (numpy or a CUDA tensor): h rows of Y, then
+        the chroma as `fmt` lays it out - ``(h * 3 / 2, w)`` for the 4:2:0 formats (uint16 for p010 / i010), ``(2 h, w)`` for i422 and
+        nv16, ``(3 h, w)`` for i444.  Views of `buf`, no copies.  The planar formats need `buf` contiguous (a chroma row is not a row of
+        `buf`); the semi-planar ones take any row pitch.  The packed formats are one plane already: hand it to ``YuvFrame``."""
+        if fmt not in YUV_FORMATS:
+            raise ValueError("yuv: format %r is not one of %s" % (fmt, ", ".join(sorted(YUV_FORMATS))))
+        kind, vdiv, hdiv, _ = YUV_LAYOUTS[YUV_FORMATS[fmt][0]]
+        if kind == "packed":
+            raise ValueError("yuv: format %r is one packed plane: YuvFrame(%r, plane)" % (fmt, fmt))
         h, w = int(h), int(w)
-        if h < 2 or w < 2 or h % 2 or w % 2:
-            raise ValueError("yuv: a 4:2:0 frame has even height and width, not %d x %d" % (h, w))
-        if buf.ndim != 2 or tuple(buf.shape) != (h * 3 // 2, w):
-            raise ValueError("yuv: a packed %d x %d frame is a (%d, %d) array, not %s" % (h, w, h * 3 // 2, w, tuple(buf.shape)))
-        if FORMATS[fmt][0]:
-            return cls(fmt, buf[:h], uv=buf[h:])
+        if h < 1 or w < 2 or w % 2 or (vdiv == 2 and h % 2):
+            if vdiv == 2:
+                raise ValueError("yuv: a 4:2:0 frame (%s) has even height and width, not %d x %d" % (fmt, h, w))
+            raise ValueError("yuv: a %s frame has even width, not %d x %d" % (fmt, h, w))
+        crows, ccols = h // vdiv, w // hdiv                       # of one of the two chroma planes
+        rows = h + 2 * crows * ccols // w
+        if buf.ndim != 2 or tuple(buf.shape) != (rows, w):
+            raise ValueError("yuv: a packed %s frame of %d x %d is a (%d, %d) array, not %s" % (fmt, h, w, rows, w, tuple(buf.shape)))
+        colour = dict(matrix=matrix, full_range=full_range)
+        if kind == "semi":
+            return cls(fmt, buf[:h], uv=buf[h:], **colour)
         contiguous = buf.flags.c_contiguous if isinstance(buf, np.ndarray) else buf.is_contiguous()
         if not contiguous:
             raise ValueError("yuv: a packed %s frame must be contiguous" % fmt)
         flat = buf.reshape(-1)
-        q = h * w // 4
-        first, second = (flat[h * w + k * q:h * w + (k + 1) * q].reshape(h // 2, w // 2) for k in (0, 1))
-        return cls(fmt, buf[:h], u=second if FORMATS[fmt][1] else first, v=first if FORMATS[fmt][1] else second)
+        q = crows * ccols
+        first, second = (flat[h * w + k * q:h * w + (k + 1) * q].reshape(crows, ccols) for k in (0, 1))
+        v_first = YUV_FORMATS[fmt][1] == 1
+        return cls(fmt, buf[:h], u=second if v_first else first, v=first if v_first else second, **colour)
+
+    @property
+    def legacy(self) -> bool:
+        """an 8-bit 4:2:0 frame at OpenCV's colour: what ``af_yuv420_to_rgb_u8`` converts"""
+        return self.fmt in FORMATS and self.matrix == "bt601" and not self.full_range
 
     @property
     def nbytes(self) -> int:
-        """the bytes of the frame's planes: 1.5 per pixel"""
-        return self.shape[0] * self.shape[1] * 3 // 2
+        """the bytes of the frame's planes: 1.5 per pixel at 8-bit 4:2:0, 2 at 4:2:2, 3 at 4:4:4 and at 10-bit 4:2:0"""
+        return sum(rows * row for _, rows, row, _ in self._planes)
 
     @property
     def device(self) -> Optional[torch.device]:
         return self.y.device if self.on_device else None
 
     def planes(self):
-        """``[(plane, rows, row bytes, pitch)]`` in staging order: Y, then the chroma plane(s) (U before V)"""
+        """``[(plane, rows, row bytes, pitch in bytes)]`` in staging order: Y (or the packed plane), then the chroma plane(s) (U
+        before V)"""
         return self._planes
 
 
@@ -395,8 +455,10 @@ class _Converter:
 
 
 class YuvConverter(_Converter):
-    """``_Converter`` for ``YuvFrame``s: one launch of ``af_yuv420_to_rgb_u8`` per ``AF_YUV_MAX_FRAMES`` frames; its table travels
-    to the kernel by value, so ``copies`` counts the copies of staged host planes alone"""
+    """``_Converter`` for ``YuvFrame``s: one launch per ``AF_YUV_MAX_FRAMES`` frames; its table travels to the kernel by value, so
+    ``copies`` counts the copies of staged host planes alone.  A ``convert`` whose frames are all 8-bit 4:2:0 at OpenCV's colour
+    (``YuvFrame.legacy``) launches ``af_yuv420_to_rgb_u8`` (csrc/af_yuv.hip); any other launches ``af_yuv_to_rgb_ex_u8``
+    (csrc/af_yuv_formats.hip) for all its frames, whatever the mix of layouts, depths and colours."""
     frame_type, what, holds, max_frames, stat_keys = YuvFrame, "yuv", "planes", 64, ("convert", "yuv_copies")
 
     @staticmethod
@@ -409,6 +471,9 @@ class YuvConverter(_Converter):
         store_arr, n_stores, index = launch_stores(stores)
         for i, (f, base, slot) in enumerate(zip(frames, addresses, slots)):
             h, w = f.shape[:2]
+            if not f.legacy:
+                raise ValueError("yuv: a %s frame (%s, %s range) is not one af_yuv420_to_rgb_u8 converts"
+                                 % (f.fmt, f.matrix, "full" if f.full_range else "limited"))
             if base is None:
                 ptrs = [_address(p) for p, _, _, _ in f.planes()]
                 y_pitch, c_pitch = f.planes()[0][3], f.planes()[1][3]
@@ -422,10 +487,43 @@ class YuvConverter(_Converter):
         _lib.check(_lib.lib.af_yuv420_plan_u8(C.byref(descs), len(frames), C.byref(store_arr), n_stores, C.byref(items)), "yuv420_plan_u8")
         return items
 
+    @staticmethod
+    def table_ex(frames: Sequence[YuvFrame], addresses: Sequence[int], stores, slots: Sequence[int]):
+        """``table`` for frames of any format and colour -> the ``YuvItemEx`` array of one launch of ``af_yuv_to_rgb_ex_u8``; staged
+        planes lie tight one behind the other in ``planes()`` order"""
+        from . import _lib
+        descs = (_lib.YuvFrameEx * max(1, len(frames)))()
+        store_arr, n_stores, index = launch_stores(stores)
+        for i, (f, base, slot) in enumerate(zip(frames, addresses, slots)):
+            h, w = f.shape[:2]
+            if base is None:
+                ptrs, pitches = [_address(p) for p, _, _, _ in f.planes()], [pitch for _, _, _, pitch in f.planes()]
+            else:
+                ptrs, pitches = [], []
+                for _, rows, row, _ in f.planes():
+                    ptrs.append(base)
+                    pitches.append(row)
+                    base += rows * row
+            ptrs, pitches = ptrs + [None, None], pitches + [0]
+            descs[i] = _lib.YuvFrameEx(ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], h, w, f.layout, f.order, MATRICES[f.matrix],
+                                       int(f.full_range), index[i], int(slot))
+        items = (_lib.YuvItemEx * max(1, len(frames)))()
+        _lib.check(_lib.lib.af_yuv_plan_ex_u8(C.byref(descs), len(frames), C.byref(store_arr), n_stores, C.byref(items)), "yuv_plan_ex_u8")
+        return items
+
+    def convert(self, jobs) -> None:
+        jobs = list(jobs)
+        self._legacy = all(getattr(j[0], "legacy", True) for j in jobs)       # decided for the whole batch: one kernel per convert
+        super().convert(jobs)
+
     def _plan(self, frames, addresses, refs, slots, table_host, table_dev, room):
         from . import _lib
-        items, n = self.table(frames, addresses, refs, slots), len(frames)
-        return 0, lambda stream: _lib.check(_lib.lib.af_yuv420_to_rgb_u8(C.byref(items), n, stream), "yuv420_to_rgb_u8")
+        n = len(frames)
+        if self._legacy:
+            items = self.table(frames, addresses, refs, slots)
+            return 0, lambda stream: _lib.check(_lib.lib.af_yuv420_to_rgb_u8(C.byref(items), n, stream), "yuv420_to_rgb_u8")
+        items = self.table_ex(frames, addresses, refs, slots)
+        return 0, lambda stream: _lib.check(_lib.lib.af_yuv_to_rgb_ex_u8(C.byref(items), n, stream), "yuv_to_rgb_ex_u8")
 
 
 class CaptureConverter(_Converter):

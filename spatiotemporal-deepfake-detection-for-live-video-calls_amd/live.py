@@ -836,7 +836,7 @@ class StoresQuality(_QualitySums):
 class ServerStats:
     """what a ``CallServer`` enqueued and waited for: ``last`` for the last step, ``total`` since the server was made, each with
     ``detect`` (calls of ``af_yunet_detect_frames``, or of a detector's ``detect_views``), ``quality``, ``warp`` (launches),
-    ``replay`` (graph replays), ``wait`` (host waits for the device), ``convert`` (launches of ``af_yuv420_to_rgb_u8``),
+    ``replay`` (graph replays), ``wait`` (host waits for the device), ``convert`` (launches of ``af_yuv420_to_rgb_u8`` / ``af_yuv_to_rgb_ex_u8``),
     ``yuv_copies`` (host-to-device copies of staged YUV planes), ``capture`` (launches of ``af_capture_to_stores_u8``), ``resize``
     (launches of ``af_resize_frames_u8``) and ``track`` (launches of ``af_bytetrack_update_calls``; in ``VideoRunner``, of
     ``af_runner_track_chunk``)"""
@@ -887,7 +887,7 @@ class CallServer:
 
     A frame is a numpy array, a ``YuvFrame`` or a ``CapturedFrame`` (the mapping may mix them).  The ``CapturedFrame``s of a step are
     admitted together - one fill, one copy, one ``af_capture_to_stores_u8`` launch per 64 - as are its ``YuvFrame``s: the
-    host planes of all calls fill one pinned slot and cross in one copy, and one ``af_yuv420_to_rgb_u8`` launch per 64 frames
+    host planes of all calls fill one pinned slot and cross in one copy, and one conversion launch (``YuvConverter``'s) per 64 frames
     converts them - and the device-resident ones where they lie - into the calls' own ring slots, each in its call's
     ``channel_order``.  The conversion needs no wait.
 
