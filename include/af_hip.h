@@ -1330,6 +1330,91 @@ int af_runner_track_chunk_host(const af_runner_chunk* chunk);
 int af_face_quality_table_u8(const af_store_ref* store, void* record, int capacity, int full, af_quality_sums* sums, void* grey,
                              int64_t grey_stride, void* stream);
 
+/* ---- a live tick's face stage on the device (added within ABI 6) ------------------------------------------------------------------
+ * What RealtimeCall / CallServer do on the host per call between the tracker and the quality launch - live.track_candidates: the
+ * self-view exclusion, the five-point pick, the mesh_every cache and get_crop_box (af_realtime.py:390-437) - behind
+ * the tracker's update in the SAME launch, one wave per call (csrc/af_live_core.h, csrc/af_live.hip; the statement is
+ * live.track_candidates itself, driven as tests/live_cands_ref.py drives it).
+ *
+ * A call's state is af_live_state_bytes() bytes (8-byte aligned): the tracker's state block first - every af_bytetrack_* entry
+ * works on it - then the five-point cache, one entry per tracker slot tagged with the track id it belongs to.  af_live_reset fills
+ * a HOST block; a device state is a copy of one.
+ *
+ * af_live_call (host, travels in the launch arguments): `track` is the tracker's call on that state, in any of its forms, and is
+ * run unchanged.  The candidate stage then walks the tracks the update returned, in the tracker's order:
+ *   exclusion  exclude = (x1n, y1n, x2n, y2n): a track whose fp64 centre (0.5 * (x1 + x2), 0.5 * (y1 + y2)) has
+ *              x1n * frame_w <= cx <= x2n * frame_w and y1n * frame_h <= cy <= y2n * frame_h, all in fp64, is neither alive nor kept;
+ *   rows       with the LIST form the frame's rows are ALL *count_ptr (or count) rows, cut at max_rows, not only those past the
+ *              start filter (row_stride >= 15; max_rows * row_stride <= rows_floats); column c of a row is scaled back as
+ *              YuNet.scale_rows does it - by scale_x for even c, scale_y for odd c, 1 for column 14, an fp64 product cast to float32 -
+ *              and a row's box is the float32 (x, y, x + w, y + h).  With any other form, or with no row, there are no points;
+ *   pick       the row of highest IoU (+ 1 convention, fp64 on the widened float32 boxes) with the float32 cast of the track's
+ *              box, the first of equals, if that IoU is 0.4 or more: its columns 5 .. 14 are the track's five points;
+ *   cache      on a frame with frame_idx % mesh_every == 0, or for a track without a cache entry: the picked points, which are
+ *              cached (flag REFRESHED), or, without any, the track is skipped (NO_POINTS) even when an entry exists; otherwise the
+ *              cached points.  Before the frame the entries of the tids in purged[0 .. n_purged) are dropped;
+ *   crop box   get_crop_box((frame_h, frame_w), the float32 box, crop_scale) in fp64; an empty one is skipped (EMPTY_BOX).
+ * An excluded track carries only EXCLUDED; every other one is alive and kept; the CANDIDATE ones are the frame's candidates.
+ *
+ * Per call the launch writes the tracker's record (af_bytetrack_record_bytes()) and one af_live_record: the header - frame_idx,
+ * slot (the ring slot of the frame, as handed in), n_online, n_cands, tiles (the tile total of the half-size quality launch),
+ * overflow (the tracker's code; then n_online is 0), bad (set by af_face_quality_records_u8) - and one entry per returned track:
+ * tid, flags, the float32 box, the ten float32 points, the crop box (x1, y1, x2, y2), the first tile of its half-size image (of
+ * every entry the tiles of the candidates in front of it, so the prefixes ascend) and its index among the frame's candidates
+ * (-1 for the others).  Entries behind n_online are zero.  Nothing is written outside the
+ * states and the records.
+ * af_live_update_calls: `calls` is a HOST array of 1 .. AF_TRACK_MAX_CALLS entries; states, rows, counts and records are DEVICE
+ * memory; as many launches as the calls need (af_live_calls_per_launch() calls fit one launch's arguments).
+ * af_live_update_host: the same source on the CPU for one call over host memory.
+ *
+ * af_face_quality_records_u8: af_face_quality_stores_u8 with its rectangles read from af_live_records in DEVICE memory.  jobs
+ * (HOST, 0 .. AF_QUALITY_MAX_RECTS of them): job j's candidates are those of jobs[j].record, rectangles of frame jobs[j].slot of
+ * stores[jobs[j].store].  Candidate k of job j adds to sums[j * AF_TRACK_MAX_TRACKS + k]; all n_jobs * AF_TRACK_MAX_TRACKS sums
+ * are cleared on `stream` first.  A fixed grid: a workgroup reads the jobs' tile totals, forms their prefix and finds the job and
+ * then the candidate of each of its tiles by bisection.  It re-checks every candidate against its store: a slot outside the
+ * store, a rectangle that leaves its frame or a tile prefix that does not fit is skipped - never read - and flagged (the entry's
+ * AF_LIVE_BAD, the header's bad).  Stores of different sizes, pitches and byte orders may share a launch.  grey: null, or (tests)
+ * a DEVICE buffer of n_jobs * AF_TRACK_MAX_TRACKS * grey_stride bytes; the half-size grey image of candidate k of job j goes to
+ * grey + (j * AF_TRACK_MAX_TRACKS + k) * grey_stride when it fits grey_stride. */
+#define AF_LIVE_EXCLUDED 1
+#define AF_LIVE_NO_POINTS 2
+#define AF_LIVE_EMPTY_BOX 4
+#define AF_LIVE_CANDIDATE 8
+#define AF_LIVE_REFRESHED 16
+#define AF_LIVE_BAD 32
+typedef struct af_live_call {
+    af_track_call track;
+    int64_t rows_floats;
+    int32_t frame_idx, slot, mesh_every, frame_h, frame_w, n_purged;
+    double crop_scale;
+    double exclude[4];
+    int32_t purged[AF_TRACK_MAX_TRACKS];
+} af_live_call;
+typedef struct af_live_entry {
+    int32_t tid, flags;
+    float tlbr[4];
+    float lm5[10];
+    int32_t box[4];
+    int32_t first_tile, cand;
+} af_live_entry;
+typedef struct af_live_record {
+    int32_t frame_idx, slot, n_online, n_cands;
+    int32_t tiles, bad, overflow, reserved;
+    af_live_entry online[AF_TRACK_MAX_TRACKS];
+} af_live_record;
+typedef struct af_live_quality_job {
+    void* record;                  /* device pointer of an af_live_record */
+    int32_t store, slot;
+} af_live_quality_job;
+int64_t af_live_state_bytes(void);
+int64_t af_live_record_bytes(void);
+int af_live_calls_per_launch(void);
+int af_live_reset(void* host_state, double track_thresh, double match_thresh, int buffer_size);
+int af_live_update_calls(const af_live_call* calls, int n_calls, void* track_records, void* records, void* stream);
+int af_live_update_host(const af_live_call* call, void* track_record, void* record);
+int af_face_quality_records_u8(const af_store_ref* stores, int n_stores, const af_live_quality_job* jobs, int n_jobs, af_quality_sums* sums,
+                               void* grey, int64_t grey_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,21 @@ AF_TRACK_FORM_EMPTY, AF_TRACK_FORM_LIST, AF_TRACK_FORM_ARRAY, AF_TRACK_FORM_LIST
 AF_TRACK_OVERFLOW_DETS, AF_TRACK_OVERFLOW_TRACKS, AF_TRACK_NOT_RESET = 1, 2, 3
 
 
+class LiveCall(C.Structure):
+    """af_live_call (include/af_hip.h, "a live tick's face stage")"""
+    _fields_ = [("track", TrackCall), ("rows_floats", C.c_int64), ("frame_idx", C.c_int32), ("slot", C.c_int32), ("mesh_every", C.c_int32),
+                ("frame_h", C.c_int32), ("frame_w", C.c_int32), ("n_purged", C.c_int32), ("crop_scale", C.c_double), ("exclude", C.c_double * 4),
+                ("purged", C.c_int32 * AF_TRACK_MAX_TRACKS)]
+
+
+class LiveQualityJob(C.Structure):
+    """af_live_quality_job: a candidate record in device memory, the index of its store in the launch and its frame's slot"""
+    _fields_ = [("record", C.c_void_p), ("store", C.c_int32), ("slot", C.c_int32)]
+
+
+AF_LIVE_EXCLUDED, AF_LIVE_NO_POINTS, AF_LIVE_EMPTY_BOX, AF_LIVE_CANDIDATE, AF_LIVE_REFRESHED, AF_LIVE_BAD = 1, 2, 4, 8, 16, 32
+
+
 AF_RUNNER_MAX_FRAMES = 64
 AF_RUNNER_NEED_DETECT, AF_RUNNER_DROPPED, AF_RUNNER_PROCESSED, AF_RUNNER_NOT_REACHED, AF_RUNNER_REFUSED = 1, 2, 4, 8, 16
 AF_RUNNER_CAND_BAD = 1
@@ -479,6 +494,14 @@ ABI = {
     "af_runner_track_chunk": (C.c_int, [C.POINTER(RunnerChunk), C.c_void_p]),
     "af_runner_track_chunk_host": (C.c_int, [C.POINTER(RunnerChunk)]),
     "af_face_quality_table_u8": (C.c_int, [C.POINTER(StoreRef), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "af_live_state_bytes": (C.c_int64, []),
+    "af_live_record_bytes": (C.c_int64, []),
+    "af_live_calls_per_launch": (C.c_int, []),
+    "af_live_reset": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "af_live_update_calls": (C.c_int, [C.POINTER(LiveCall), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "af_live_update_host": (C.c_int, [C.POINTER(LiveCall), C.c_void_p, C.c_void_p]),
+    "af_face_quality_records_u8": (C.c_int, [C.POINTER(StoreRef), C.c_int, C.POINTER(LiveQualityJob), C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.c_void_p]),
 }
 
 

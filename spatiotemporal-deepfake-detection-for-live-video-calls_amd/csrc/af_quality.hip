@@ -245,6 +245,94 @@ __global__ __launch_bounds__(256) void face_quality_table_kernel(const QualityTa
     }
 }
 
+// ---- the launch whose rectangles lie in the candidate records of live calls in device memory (af_hip.h, "a live tick's face stage") ----
+// Up to 64 jobs - a record, its frame's slot and its store, packed to 56 bytes each - travel in the arguments.  A fixed grid: every
+// workgroup reads the jobs' tile totals (cut at what the job's frame can hold), forms their prefix in LDS and takes tiles b,
+// b + gridDim.x, ...; a tile finds its job, then its entry in the job's record, by bisection of ascending tile prefixes.  The entry
+// is checked against the job's store before a byte of it is read.
+struct QualityRecordJob {
+    const unsigned char* base;
+    int64_t store_bytes, frame_stride;
+    af_live_record* rec;
+    int32_t row_pitch, n_frames, slot, max_tiles;
+    int16_t height, width;
+    int32_t bgr;
+};
+static_assert(sizeof(QualityRecordJob) == 56, "argument budget");
+struct QualityRecordsArgs {
+    af_quality_sums* sums;
+    unsigned char* grey;
+    int64_t grey_stride;
+    int32_t n, reserved;
+    QualityRecordJob j[AF_QUALITY_MAX_RECTS];
+};
+static_assert(sizeof(QualityRecordsArgs) <= 4096, "kernel arguments");
+
+__global__ __launch_bounds__(256) void face_quality_records_kernel(const QualityRecordsArgs a) {
+    __shared__ int first[AF_QUALITY_MAX_RECTS + 1];                    // first[j]: the first tile of job j; first[n]: the total
+    __shared__ int tiles[AF_QUALITY_MAX_RECTS];
+    if ((int)threadIdx.x < a.n) {
+        const int t = a.j[threadIdx.x].rec->tiles;
+        tiles[threadIdx.x] = t < 0 ? 0 : (t > a.j[threadIdx.x].max_tiles ? a.j[threadIdx.x].max_tiles : t);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;                                                 // the sum of the jobs' max_tiles is <= 0x7fffffff: checked on the host
+        for (int j = 0; j < a.n; ++j) {
+            first[j] = total;
+            total += tiles[j];
+        }
+        first[a.n] = total;
+    }
+    __syncthreads();
+    const int total = first[a.n];
+    for (int tile = blockIdx.x; tile < total; tile += gridDim.x) {     // uniform in the workgroup
+        int lo = 0, hi = a.n - 1;                                      // the last job whose first tile is <= tile
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (first[mid] <= tile) lo = mid; else hi = mid - 1;
+        }
+        const int job = lo, in_job = tile - first[job];
+        const QualityRecordJob& q = a.j[job];
+        int n = q.rec->n_online;
+        n = n < 0 ? 0 : (n > AF_TRACK_MAX_TRACKS ? AF_TRACK_MAX_TRACKS : n);
+        bool ok = n > 0;
+        af_live_entry* e = q.rec->online;
+        if (ok) {
+            lo = 0; hi = n - 1;                                        // the last entry whose first tile is <= in_job
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (q.rec->online[mid].first_tile <= in_job) lo = mid; else hi = mid - 1;
+            }
+            e = q.rec->online + lo;
+        }
+        const int x1 = e->box[0], y1 = e->box[1], x2 = e->box[2], y2 = e->box[3], k = e->cand;
+        const int local = in_job - e->first_tile;
+        const long long w = (long long)x2 - x1, h = (long long)y2 - y1;
+        ok = ok && (e->flags & AF_LIVE_CANDIDATE) && k >= 0 && k < AF_TRACK_MAX_TRACKS;
+        ok = ok && q.slot >= 0 && q.slot < q.n_frames && x1 >= 0 && y1 >= 0 && w > 0 && h > 0 && x2 <= q.width && y2 <= q.height;
+        long long offset = 0;
+        if (ok) {
+            offset = (long long)q.slot * q.frame_stride + (long long)y1 * q.row_pitch + (long long)x1 * 3;
+            ok = offset + (h - 1) * q.row_pitch + w * 3 <= q.store_bytes;
+        }
+        if (ok) {
+            const int dw = max(1, (int)w / 2), dh = max(1, (int)h / 2);
+            ok = local >= 0 && local < ((dw + Q_TW - 1) / Q_TW) * ((dh + Q_TH - 1) / Q_TH);
+            if (ok) {
+                const long long at = (long long)job * AF_TRACK_MAX_TRACKS + k;
+                unsigned char* g = (a.grey && (long long)dw * dh <= a.grey_stride) ? a.grey + at * a.grey_stride : nullptr;
+                quality_tile<false>(q.base + offset, q.row_pitch, (int)w, (int)h, local, q.bgr, a.sums + at, g);
+            }
+        }
+        if (!ok && threadIdx.x == 0) {
+            atomicOr(&e->flags, AF_LIVE_BAD);
+            atomicOr(&q.rec->bad, 1);
+        }
+        __syncthreads();                                               // quality_tile's LDS is the next tile's too
+    }
+}
+
 // The host side of both entry points: the stores and the rectangles checked, one memset and one launch.  `listed`: a rectangle
 // names its store in af_frame_rect.reserved; otherwise every rectangle is of the one store and reserved is not read.  `full`: the
 // kernel's full-size mode.
@@ -341,5 +429,43 @@ extern "C" int af_face_quality_table_u8(const af_store_ref* store, void* record,
     else
         hipLaunchKernelGGL(face_quality_table_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     AF_CHECK_LAUNCH("face_quality_table_kernel");
+    return AF_OK;
+}
+
+extern "C" int af_face_quality_records_u8(const af_store_ref* stores, int n_stores, const af_live_quality_job* jobs, int n_jobs, af_quality_sums* sums,
+                                          void* grey, int64_t grey_stride, void* stream) {
+    using namespace af;
+    const char* who = "face_quality_records";
+    AF_REQUIRE(stores && jobs && sums, "%s: null argument", who);
+    AF_REQUIRE(((uintptr_t)sums & 7) == 0, "%s: the sums are not 8-byte aligned", who);
+    AF_REQUIRE(n_jobs >= 0 && n_jobs <= AF_QUALITY_MAX_RECTS, "%s: %d jobs (at most %d per launch)", who, n_jobs, AF_QUALITY_MAX_RECTS);
+    AF_REQUIRE(n_stores > 0 && n_stores <= AF_MAX_STORES, "%s: %d stores (1 to %d per launch)", who, n_stores, AF_MAX_STORES);
+    AF_REQUIRE(!grey || grey_stride >= 1, "%s: a grey stride of %lld bytes", who, (long long)grey_stride);
+    if (n_jobs == 0) return AF_OK;
+    for (int i = 0; i < n_stores; ++i) {
+        AF_REQUIRE(stores[i].base, "%s: store %d: null base pointer", who, i);
+        const int rc = check_frame_store(who, i, stores[i].desc);
+        if (rc != AF_OK) return rc;
+    }
+    QualityRecordsArgs a;
+    a.sums = sums; a.grey = (unsigned char*)grey; a.grey_stride = grey_stride; a.n = n_jobs; a.reserved = 0;
+    int64_t max_total = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const af_live_quality_job& in = jobs[j];
+        AF_REQUIRE(in.record && ((uintptr_t)in.record & 7) == 0, "%s: job %d: the record is null or not 8-byte aligned", who, j);
+        AF_REQUIRE(in.store >= 0 && in.store < n_stores, "%s: job %d names store %d of %d", who, j, in.store, n_stores);
+        const af_store_ref& st = stores[in.store];
+        const af_frame_store& d = st.desc;
+        const int64_t per_frame = (int64_t)((d.width + Q_TW - 1) / Q_TW) * ((d.height + Q_TH - 1) / Q_TH);   // no half-size image has more tiles
+        max_total += per_frame * AF_TRACK_MAX_TRACKS;
+        a.j[j] = QualityRecordJob{(const unsigned char*)st.base, d.store_bytes, d.frame_stride, (af_live_record*)in.record, (int32_t)d.row_pitch, d.n_frames,
+                                  in.slot, (int32_t)(per_frame * AF_TRACK_MAX_TRACKS), (int16_t)d.height, (int16_t)d.width, st.bgr ? 1 : 0};
+    }
+    AF_REQUIRE(max_total <= 0x7fffffff, "%s: too many pixels", who);
+    hipError_t e = hipMemsetAsync(sums, 0, sizeof(af_quality_sums) * (size_t)n_jobs * AF_TRACK_MAX_TRACKS, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(AF_ERR_LAUNCH, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
+    const unsigned grid = (unsigned)(max_total < Q_TABLE_GRID ? max_total : Q_TABLE_GRID);
+    hipLaunchKernelGGL(face_quality_records_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    AF_CHECK_LAUNCH("face_quality_records_kernel");
     return AF_OK;
 }

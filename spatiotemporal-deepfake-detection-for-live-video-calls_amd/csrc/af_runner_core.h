@@ -51,6 +51,34 @@ TRK_HD int tiles_of(int w, int h) { return ((w + RUN_TILE_W - 1) / RUN_TILE_W) *
 TRK_HD double clamp_to(double v, double hi) { return fmin(fmax(v, 0.0), hi); }
 TRK_HD void widen(const float* b, double* o) { for (int k = 0; k < 4; ++k) o[k] = (double)b[k]; }
 
+// YuNet's five points for a track: of n rows - det(d, t) puts row d's float32 (x, y, x + w, y + h) into t - the first of highest
+// IoU with the track's float32 box, if that IoU is 0.4 or more; else -1.  Shared with the live candidate stage (af_live_core.h).
+template <class Det>
+TRK_HD int pick_row(const float* box, int n, Det det) {
+    double a[4], b[4], best = 0.0;
+    int at = -1;
+    widen(box, a);
+    for (int d = 0; d < n; ++d) {
+        float t[4];
+        det(d, t);
+        widen(t, b);
+        const double iou = 1.0 - trk::iou_cost(a, b);
+        if (at < 0 || iou > best) { best = iou; at = d; }
+    }
+    return (at >= 0 && best >= 0.4) ? at : -1;
+}
+
+// get_crop_box((frame_h, frame_w), b, scale), fp64: the box rounded, grown by scale times its sides, cut to the frame and rounded
+// again; false when the rectangle is empty
+TRK_HD bool crop_box(const double* b, double scale, int frame_w, int frame_h, int32_t* box) {
+    const double x0 = rint(b[0]), y0 = rint(b[1]), x1 = rint(b[2]), y1 = rint(b[3]);
+    const double gx = scale * (x1 - x0), gy = scale * (y1 - y0);
+    const double wm = (double)frame_w - 1.0, hm = (double)frame_h - 1.0;
+    box[0] = (int)rint(clamp_to(x0 - gx, wm)); box[1] = (int)rint(clamp_to(y0 - gy, hm));
+    box[2] = (int)rint(clamp_to(x1 + gx, wm)); box[3] = (int)rint(clamp_to(y1 + gy, hm));
+    return box[2] > box[0] && box[3] > box[1];
+}
+
 // lane 0: the frame's fate before the tracker.  Returns ACT_TRACK with sc->pick / sc->n_pick set when the tracker is to run.
 TRK_HD int before(const af_runner_chunk& c, int j, State* rs, Record* out, Scratch* sc) {
     const int k = c.frame_idx[j];
@@ -148,17 +176,8 @@ TRK_HD void after(const af_runner_chunk& c, int j, State* rs, Record* out, Scrat
     for (int q = 0; q < n_cur; ++q) {
         const int tid = sc->cur_ids[q];
         const float* lm = nullptr;
-        if (sc->n_pick > 0) {                                  // YuNet's five points: the row of highest IoU, if that is 0.4 or more
-            double a[4], b[4], best = 0.0;
-            int at = -1;
-            widen(sc->cur_boxes[q], a);
-            for (int d = 0; d < sc->n_pick; ++d) {
-                widen(sc->det_tlbr[d], b);
-                const double iou = 1.0 - trk::iou_cost(a, b);
-                if (at < 0 || iou > best) { best = iou; at = d; }
-            }
-            if (best >= 0.4) lm = rows + (int64_t)sc->pick[at] * c.row_stride + 5;
-        }
+        const int at = pick_row(sc->cur_boxes[q], sc->n_pick, [sc](int d, float* t) { for (int e = 0; e < 4; ++e) t[e] = sc->det_tlbr[d][e]; });
+        if (at >= 0) lm = rows + (int64_t)sc->pick[at] * c.row_stride + 5;
         int slot = -1;                                         // the track's slot carries its cache entry
         for (int i = 0; i < rs->trk.n_tracked && i < TRK_S && slot < 0; ++i) {
             const int s = rs->trk.tracked[i];
@@ -171,13 +190,9 @@ TRK_HD void after(const af_runner_chunk& c, int j, State* rs, Record* out, Scrat
             for (int e = 0; e < 10; ++e) rs->cache_lm[slot][e] = lm[e];
             rs->cache_tid[slot] = tid;
         }
-        const double* b = sc->rec.online[sc->cur_row[q]].tlbr; // get_crop_box, fp64
-        const double x0 = rint(b[0]), y0 = rint(b[1]), x1 = rint(b[2]), y1 = rint(b[3]);
-        const double gx = c.crop_scale * (x1 - x0), gy = c.crop_scale * (y1 - y0);
-        const double wm = (double)c.frame_w - 1.0, hm = (double)c.frame_h - 1.0;
-        const int bx1 = (int)rint(clamp_to(x0 - gx, wm)), by1 = (int)rint(clamp_to(y0 - gy, hm));
-        const int bx2 = (int)rint(clamp_to(x1 + gx, wm)), by2 = (int)rint(clamp_to(y1 + gy, hm));
-        if (bx2 <= bx1 || by2 <= by1) continue;
+        int32_t box[4];
+        if (!crop_box(sc->rec.online[sc->cur_row[q]].tlbr, c.crop_scale, c.frame_w, c.frame_h, box)) continue;
+        const int bx1 = box[0], by1 = box[1], bx2 = box[2], by2 = box[3];
         const int n = out->head.n_cands;
         if (n >= capacity) continue;                           // a frame appends at most TRK_T: not reached
         af_runner_cand& cd = out->cands[n];

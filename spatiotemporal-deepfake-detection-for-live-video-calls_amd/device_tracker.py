@@ -14,7 +14,13 @@ host memory and runs the same source on the CPU (``af_bytetrack_update_host``): 
 
 The arithmetic is fp64 in one written-down order (tests/bytetrack_ref.py states it in numpy), so a device tracker equals that
 statement bit for bit; it equals ``tracker.ByteTracker``, whose sums BLAS orders, in every discrete result and to round-off in the
-boxes.  More than ``MAX_DETS`` detections in one frame, or more than ``MAX_TRACKS`` tracked and lost faces, raise RuntimeError."""
+boxes.  More than ``MAX_DETS`` detections in one frame, or more than ``MAX_TRACKS`` tracked and lost faces, raise RuntimeError.
+
+``candidates=True``: the state block also holds the five-point cache, and ``update_live_calls`` runs the tracker and,
+behind it in the same launch, ``live.track_candidates`` on the tracks it returned (csrc/af_live_core.h): ``live_job`` wraps a
+tracker job with the frame index, the ring slot, the frame size, ``mesh_every``, ``crop_scale``, ``exclude_rect`` and the purged
+tids; the launch leaves the tracker's record and one candidate record per job, ``parse_live_records`` reads the latter and
+``candidates_of`` turns one into ``track_candidates``' tuple."""
 import ctypes as C
 
 import numpy as np
@@ -39,6 +45,17 @@ _RECORD = np.dtype([("frame_id", "<i4"), ("overflow", "<i4"), ("n_online", "<i4"
 if _STATE.itemsize != STATE_BYTES or _RECORD.itemsize != RECORD_BYTES:
     raise ImportError("device_tracker: libafhip.so lays a tracker out in %d + %d bytes, this module in %d + %d"
                       % (STATE_BYTES, RECORD_BYTES, _STATE.itemsize, _RECORD.itemsize))
+
+LIVE_STATE_BYTES, LIVE_RECORD_BYTES = int(_lib.lib.af_live_state_bytes()), int(_lib.lib.af_live_record_bytes())
+LIVE_PER_LAUNCH = int(_lib.lib.af_live_calls_per_launch())
+_LIVE_ENTRY = np.dtype([("tid", "<i4"), ("flags", "<i4"), ("tlbr", "<f4", 4), ("lm5", "<f4", (5, 2)), ("box", "<i4", 4), ("first_tile", "<i4"),
+                        ("cand", "<i4")])
+_LIVE_RECORD = np.dtype([("frame_idx", "<i4"), ("slot", "<i4"), ("n_online", "<i4"), ("n_cands", "<i4"), ("tiles", "<i4"), ("bad", "<i4"),
+                         ("overflow", "<i4"), ("reserved", "<i4"), ("online", _LIVE_ENTRY, MAX_TRACKS)])
+_LIVE_STATE = np.dtype([("trk", _STATE), ("cache_tid", "<i4", _SLOTS), ("cache_lm", "<f4", (_SLOTS, 10))])
+if _LIVE_STATE.itemsize != LIVE_STATE_BYTES or _LIVE_RECORD.itemsize != LIVE_RECORD_BYTES:
+    raise ImportError("device_tracker: libafhip.so lays a live call out in %d + %d bytes, this module in %d + %d"
+                      % (LIVE_STATE_BYTES, LIVE_RECORD_BYTES, _LIVE_STATE.itemsize, _LIVE_RECORD.itemsize))
 
 _OVERFLOW = {_lib.AF_TRACK_OVERFLOW_DETS: "more than AF_TRACK_MAX_DETS = %d detections passed the start filter in one frame" % MAX_DETS,
              _lib.AF_TRACK_OVERFLOW_TRACKS: "more than AF_TRACK_MAX_TRACKS = %d tracked and lost faces; reset() the tracker" % MAX_TRACKS,
@@ -67,26 +84,29 @@ def _aligned_bytes(n: int) -> np.ndarray:
 
 
 class DeviceByteTracker:
-    def __init__(self, args, frame_rate=30, device=None, host: bool = False):
+    def __init__(self, args, frame_rate=30, device=None, host: bool = False, candidates: bool = False):
         self.args = args
+        self.candidates = bool(candidates)                        # the state block carries the five-point cache (``live_job``)
+        self.state_bytes = LIVE_STATE_BYTES if self.candidates else STATE_BYTES
         self.track_thresh, self.match_thresh = float(args.track_thresh), float(args.match_thresh)
         self.buffer_size = int(frame_rate / 30.0 * args.track_buffer)
         self.host = bool(host)
         if self.host:
-            self.device, self._state = None, _aligned_bytes(STATE_BYTES)
+            self.device, self._state = None, _aligned_bytes(self.state_bytes)
         else:
             import torch
             self.device = torch.device("cuda" if device is None else device)
-            self._state = torch.empty(STATE_BYTES, dtype=torch.uint8, device=self.device)
+            self._state = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
         self._record = _aligned_bytes(RECORD_BYTES)
         self._keep = None                                         # the uploaded rows of the last ``update``, alive until the next
         self.reset()
 
     def reset(self):
         """a fresh tracker: no track, ``frame_id`` 0, the next id 1"""
-        fresh = self._state if self.host else _aligned_bytes(STATE_BYTES)
-        _lib.check(_lib.lib.af_bytetrack_reset(C.c_void_p(fresh.ctypes.data), self.track_thresh, self.match_thresh, self.buffer_size),
-                   "af_bytetrack_reset")
+        fresh = self._state if self.host else _aligned_bytes(self.state_bytes)
+        reset = _lib.lib.af_live_reset if self.candidates else _lib.lib.af_bytetrack_reset
+        _lib.check(reset(C.c_void_p(fresh.ctypes.data), self.track_thresh, self.match_thresh, self.buffer_size),
+                   "af_live_reset" if self.candidates else "af_bytetrack_reset")
         if not self.host:
             import torch
             self._state.copy_(torch.from_numpy(fresh))
@@ -122,6 +142,38 @@ class DeviceByteTracker:
         stride = rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]
         return self._job(AF_TRACK_FORM_LIST, rows.data_ptr(), count.data_ptr(), 0, rows.shape[0], stride, start_conf=start_conf,
                          start_min_size=start_min_size, scale=scale)
+
+    def live_job(self, job: _lib.TrackCall, frame_idx: int, slot: int, shape, mesh_every: int, crop_scale: float, exclude_rect, purged=(),
+                 rows_floats: int = 0) -> _lib.LiveCall:
+        """``job`` (``empty_job`` / ``rows_job`` of this tracker, made with ``candidates=True``) with what the candidate stage needs:
+        the frame's index, its ring slot and (H, W, ...) ``shape``; ``purged``: the tids the call's books dropped on the step
+        before - those the tracker's last record still names are sent, their cache entries go before the frame;
+        ``rows_floats``: the float32 values readable behind the job's rows"""
+        if not self.candidates:
+            raise ValueError("device_tracker: live_job needs a tracker made with candidates=True")
+        held = set(self.tracked_ids) | set(self.lost_ids)
+        gone = [int(t) for t in purged if t in held][:MAX_TRACKS]
+        c = _lib.LiveCall()
+        c.track, c.rows_floats = job, int(rows_floats)
+        c.frame_idx, c.slot, c.mesh_every = int(frame_idx), int(slot), int(mesh_every)
+        c.frame_h, c.frame_w, c.n_purged = int(shape[0]), int(shape[1]), len(gone)
+        c.crop_scale = float(crop_scale)
+        for k in range(4):
+            c.exclude[k] = float(exclude_rect[k])
+        for k, tid in enumerate(gone):
+            c.purged[k] = tid
+        return c
+
+    def live_rows_job(self, rows, count, start_conf: float, start_min_size: float, scale, **live) -> _lib.LiveCall:
+        """``live_job`` over ``rows_job`` of a detector's (N, 15) float32 rows read in place"""
+        floats = (rows.untyped_storage().nbytes() // 4 - rows.storage_offset()) if hasattr(rows, "untyped_storage") else rows.numel()
+        return self.live_job(self.rows_job(rows, count, start_conf, start_min_size, scale), rows_floats=floats, **live)
+
+    def cache_dump(self) -> dict:
+        """the five-point cache, for tests: ``{tid: float32 (5, 2)}`` (waits for the device)"""
+        raw = self._state if self.host else self._state.cpu().numpy()
+        st = np.frombuffer(raw.tobytes(), dtype=_LIVE_STATE, count=1)[0]
+        return {int(t): st["cache_lm"][i].reshape(5, 2).copy() for i, t in enumerate(st["cache_tid"]) if t != 0}
 
     def _input_job(self, tracks_in, img_info, img_size, to_memory):
         """``ByteTracker.update``'s ``tracks_in`` as a job; ``to_memory(numpy fp64 rows)`` -> (pointer, keep-alive)"""
@@ -173,7 +225,7 @@ class DeviceByteTracker:
     def state_dump(self) -> dict:
         """the state block, for tests: ``{"frame_id", "count", "tracked": [slot records], "lost": [slot records]}`` (waits for the device)"""
         raw = self._state if self.host else self._state.cpu().numpy()
-        st = np.frombuffer(raw.tobytes(), dtype=_STATE, count=1)[0]
+        st = np.frombuffer(raw.tobytes()[:STATE_BYTES], dtype=_STATE, count=1)[0]
         return {"frame_id": int(st["frame_id"]), "count": int(st["count"]),
                 "tracked": [st["slot"][i] for i in st["tracked"][:int(st["n_tracked"])]],
                 "lost": [st["slot"][i] for i in st["lost"][:int(st["n_lost"])]]}
@@ -199,3 +251,62 @@ def update_calls(jobs, device, records=None):
 def parse_records(raw) -> np.ndarray:
     """(n, RECORD_BYTES) uint8 host bytes -> n parsed records for ``absorb``"""
     return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=_RECORD)
+
+
+def update_live_calls(jobs, device, track_records=None, records=None):
+    """``af_live_update_calls`` per 64 ``jobs`` (``live_job``s of distinct trackers on ``device``) on the current stream: the tracker
+    and the candidate stage of every job; returns the (len(jobs), RECORD_BYTES) and (len(jobs), LIVE_RECORD_BYTES) uint8 device
+    tensors of the tracker's and the candidate records - the ones handed in, if any - without waiting.  ``live_launches(len(jobs))``
+    kernels are enqueued."""
+    import torch
+    n = len(jobs)
+    if track_records is None:
+        track_records = torch.empty(n, RECORD_BYTES, dtype=torch.uint8, device=device)
+    if records is None:
+        records = torch.empty(n, LIVE_RECORD_BYTES, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        for lo in range(0, n, AF_TRACK_MAX_CALLS):
+            chunk = jobs[lo:lo + AF_TRACK_MAX_CALLS]
+            table = (_lib.LiveCall * len(chunk))(*chunk)
+            _lib.check(_lib.lib.af_live_update_calls(table, len(chunk), C.c_void_p(track_records[lo].data_ptr()), C.c_void_p(records[lo].data_ptr()),
+                                                     stream), "af_live_update_calls")
+    return track_records, records
+
+
+def live_launches(n_jobs: int) -> int:
+    """the kernels ``update_live_calls`` enqueues for ``n_jobs`` jobs: the jobs of a launch travel in its arguments"""
+    full, rest = divmod(n_jobs, AF_TRACK_MAX_CALLS)
+    return full * -(-AF_TRACK_MAX_CALLS // LIVE_PER_LAUNCH) + -(-rest // LIVE_PER_LAUNCH)
+
+
+def update_live_host(job, track_record=None, record=None):
+    """one ``live_job`` of a ``host=True`` tracker through ``af_live_update_host``: -> (tracker record bytes, candidate record bytes)"""
+    track_record = _aligned_bytes(RECORD_BYTES) if track_record is None else track_record
+    record = _aligned_bytes(LIVE_RECORD_BYTES) if record is None else record
+    _lib.check(_lib.lib.af_live_update_host(C.byref(job), C.c_void_p(track_record.ctypes.data), C.c_void_p(record.ctypes.data)), "af_live_update_host")
+    return track_record, record
+
+
+def parse_live_records(raw) -> np.ndarray:
+    """(n, LIVE_RECORD_BYTES) uint8 host bytes -> n parsed candidate records"""
+    return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=_LIVE_RECORD)
+
+
+def candidates_of(rec):
+    """a parsed candidate record -> ``live.track_candidates``' tuple ``(rects, candidates, alive, kept_boxes)`` with the host's own
+    types: tids and rectangle sides as Python ints, boxes float32 (4,), points float32 (5, 2), in the tracker's order"""
+    code = int(rec["overflow"])
+    if code:
+        raise RuntimeError("device_tracker: %s" % _OVERFLOW.get(code, "overflow code %d" % code))
+    kept_boxes, candidates, alive = {}, [], set()
+    for e in rec["online"][:int(rec["n_online"])]:
+        flags = int(e["flags"])
+        if flags & _lib.AF_LIVE_EXCLUDED:
+            continue
+        tid, tlbr = int(e["tid"]), e["tlbr"].copy()
+        kept_boxes[tid] = tlbr
+        alive.add(tid)
+        if flags & _lib.AF_LIVE_CANDIDATE:
+            candidates.append((tid, tlbr, e["lm5"].copy(), tuple(int(v) for v in e["box"])))
+    return [c[3] for c in candidates], candidates, alive, kept_boxes

@@ -594,7 +594,15 @@ class RealtimeCall:
     ``tracker="device"``: the tracker is a ``device_tracker.DeviceByteTracker`` - its launch follows the detector's on the rows where
     they lie (the start filter and the scale-back happen there), its record rides in the read-back of the rows, so a step waits no
     more often; a frame without detection enqueues the launch and reads nothing.  Every discrete result is the host tracker's, the
-    boxes agree to round-off.  ``"host"`` (the default) is ``tracker.ByteTracker``."""
+    boxes agree to round-off.  ``"host"`` (the default) is ``tracker.ByteTracker``.
+
+    ``candidates="device"`` (needs ``tracker="device"`` and no ``landmarks`` hook): ``track_candidates`` - the self-view exclusion, the
+    five-point pick, the ``mesh_every`` cache and the crop box - runs behind the tracker in the tracker's launch
+    (csrc/af_live_core.h), the quality launch takes its rectangles from the record that stage leaves
+    (``af_face_quality_records_u8``), and rows, both records and the quality sums come back in ONE copy behind ONE wait: a step
+    waits once, twice when a window closes, where ``"host"`` (the default) waits once more.  Every result is that of
+    ``candidates="host"`` on the same tracker, bit for bit.  The five-point cache then lives in the tracker's device block
+    (``tracker.cache_dump()`` reads it, with a wait): ``host.last_lm`` stays empty in this mode."""
 
     def __init__(self, network, detector=None, modelPath=None, conf: float = 0.8, clip_size: int = 32, stride: int = 52,
                  crop_scale: float = 0.6, drop_after: int = 90, detect_every: int = 1, mesh_every: int = 1, start_conf: float = 0.76,
@@ -602,7 +610,7 @@ class RealtimeCall:
                  q_lap_soft: float = 20.0, q_lap_hard: float = 5.0, exclude_rect=(0.70, 0.70, 1.00, 1.00), score_is_real: bool = False,
                  track_thresh: float = 0.8, track_buffer: int = 90, match_thresh: float = 0.8, landmarks=None, size: int = 224,
                  ring_frames: int = 128, max_batch: int = 16, channel_order: str = "bgr", detect_size=None,
-                 tracker: str = "host"):
+                 tracker: str = "host", candidates: str = "host"):
         import collections
         from types import SimpleNamespace
         self.detect_size = _detect_size(detect_size)
@@ -617,11 +625,20 @@ class RealtimeCall:
                              max_batch=max_batch, drop_after=drop_after, channel_order=channel_order)
         if tracker not in ("host", "device"):
             raise ValueError("realtime: tracker %r: \"host\" or \"device\"" % (tracker,))
+        if candidates not in ("host", "device"):
+            raise ValueError("realtime: candidates %r: \"host\" or \"device\"" % (candidates,))
+        if candidates == "device" and tracker != "device":
+            raise ValueError("realtime: candidates=\"device\" needs tracker=\"device\": the candidate stage runs in the device tracker's launch, on the "
+                             "tracks where that leaves them")
+        if candidates == "device" and landmarks is not None:
+            raise ValueError("realtime: candidates=\"device\" needs landmarks=None: the hook reads a frame on the host between the tracker and the "
+                             "crop box, where this mode has no host trip")
         tracker_args = SimpleNamespace(track_thresh=track_thresh, track_buffer=track_buffer, match_thresh=match_thresh, mot20=False)
-        self.tracker_mode = tracker
+        self.tracker_mode, self.candidates_mode = tracker, candidates
         if tracker == "device":
             from .device_tracker import DeviceByteTracker
-            self.tracker = DeviceByteTracker(tracker_args, frame_rate=30.0, device=_network_device(getattr(network, "network", network)))
+            self.tracker = DeviceByteTracker(tracker_args, frame_rate=30.0, device=_network_device(getattr(network, "network", network)),
+                                             candidates=candidates == "device")
             self._track_pending = []             # [(records, [tracker])] enqueued and not read yet: they ride in the next read
         else:
             self.tracker = ByteTracker(tracker_args, frame_rate=30.0)
@@ -636,7 +653,7 @@ class RealtimeCall:
         self.clip_hist = collections.defaultdict(lambda: collections.deque(maxlen=5))
         self.state, self.last_boxes = {}, {}
         self.detections = None                       # the rows the last detect frame handed the tracker's filter (N, 15) float32
-        self._quality = self._quality_ring = None
+        self._quality = self._quality_ring = self._records_quality = None
         self._detections = _Detections()
 
     _ring_type = LiveCall
@@ -648,14 +665,7 @@ class RealtimeCall:
         """the detector on the resident frame and the one read-back of its rows; with the device tracker (``tracked``: a list)
         the tracker's launch follows the detector's on the rows where they lie, its record rides in the same read-back and the
         tracks it returned are appended to ``tracked``"""
-        if self.detect_size is not None:
-            if self._resizer is None:
-                self._resizer = FrameResizer(view.device)
-            with torch.cuda.device(view.device):
-                small = self._resizer.resize([view], self.detect_size)
-            rows, counts = self.detector.detect(small)
-        else:
-            rows, counts = self.detector.detect(view[None])
+        rows, counts = self._detector_rows(view)
         with torch.cuda.device(rows.device):
             if tracked is None:
                 found = self._detections.read([(rows, counts)], rows.device)[0]
@@ -664,6 +674,66 @@ class RealtimeCall:
                 found = self._detections.read([(rows, counts)], rows.device, extra=[r for r, _ in self._track_pending])[0]
                 tracked += _absorb_records(self._track_pending, self._detections.extra)[self.tracker]
         return found if self.detect_size is None else _scale_back(found, view.shape, self.detect_size)
+
+    def _detector_rows(self, view):
+        """the detector's launches on the resident frame, resized first where the call has a ``detect_size``: device (rows, counts)"""
+        if self.detect_size is not None:
+            if self._resizer is None:
+                self._resizer = FrameResizer(view.device)
+            with torch.cuda.device(view.device):
+                small = self._resizer.resize([view], self.detect_size)
+            return self.detector.detect(small)
+        return self.detector.detect(view[None])
+
+    def _live_job(self, k: int, shape, rows=None, count=None):
+        """this call's tracker-and-candidates job for frame `k` (``candidates="device"``): on a detector's rows (N, 15) and count
+        (1,) read in place, or without a detection"""
+        extra = dict(frame_idx=k, slot=k % self.call.ring_frames, shape=shape, mesh_every=self.mesh_every, crop_scale=self.crop_scale,
+                     exclude_rect=self.exclude_rect, purged=self.call.purged)
+        if rows is None:
+            return self.tracker.live_job(self.tracker.empty_job(), **extra)
+        size = self.detect_size
+        return self.tracker.live_rows_job(rows, count, self.start_conf, self.start_min_size,
+                                          (1.0, 1.0) if size is None else (shape[1] / size[0], shape[0] / size[1]), **extra)
+
+    def _came_back(self, dets, track_record, record, sums):
+        """the host side of a ``candidates="device"`` frame once its records are back: the rows kept in ``detections``, the tracker's
+        lists, ``track_candidates``' tuple from the candidate record and ``[(min_side, lap)]`` of its rectangles from `sums` (this
+        call's ``MAX_TRACKS`` parsed ``af_quality_sums``) -> ``(found, measured)`` for ``track_gate``"""
+        from .device_tracker import candidates_of
+        if dets is not None:
+            self.detections = dets
+        self.tracker.absorb(track_record)
+        found = candidates_of(record)
+        if int(record["bad"]):
+            raise RuntimeError("live: the quality launch refused a rectangle of frame %d: %r" % (int(record["frame_idx"]), found[0]))
+        measured = [(float(min(y1 - y0, x1 - x0)), (int(r["n_px"]) * int(r["s2"]) - int(r["s1"]) ** 2) / (int(r["n_px"]) * int(r["n_px"])))
+                    for r, (x0, y0, x1, y1) in zip(sums, found[0])]
+        return found, measured
+
+    def _step_device(self, frame) -> List[Tuple]:
+        """``step`` with ``candidates="device"``: detector, tracker and candidates, quality - enqueued one behind the other on
+        the resident frame - and ONE read-back of rows, records and sums"""
+        from .device_tracker import parse_live_records, parse_records, update_live_calls
+        call = self.call
+        k = call.admit(frame)
+        view, dev = call.frame_view(k), self.tracker.device
+        detect = k % max(1, self.detect_every) == 0
+        with torch.cuda.device(dev):
+            results = [self._detector_rows(view)] if detect else []
+            job = self._live_job(k, frame.shape, results[0][0][0], results[0][1][0:1]) if detect else self._live_job(k, frame.shape)
+            track_records, records = update_live_calls([job], dev)
+            if self._records_quality is None:
+                self._records_quality = RecordsQuality(dev)
+            sums = self._records_quality.enqueue([(records[0], call._ring.store, call.channel_order, k % call.ring_frames)])
+            read = self._detections.read(results, dev, extra=[track_records, records, sums])
+        dets = None
+        if detect:
+            dets = read[0] if self.detect_size is None else _scale_back(read[0], view.shape, self.detect_size)
+        raw_t, raw_r, raw_s = self._detections.extra
+        found, measured = self._came_back(dets, parse_records(raw_t)[0], parse_live_records(raw_r)[0], RecordsQuality.parse(raw_s))
+        faces, alive, kept_boxes, _ = track_gate(self.host, found, measured, self._weight)
+        return self._after(call.advance(faces, alive), kept_boxes)
 
     def _rows_job(self, rows, count, shape):
         """this call's device-tracker job on a detector's rows (N, 15) and count (1,), read in place"""
@@ -703,6 +773,8 @@ class RealtimeCall:
         return self._quality([(slot,) + tuple(r) for r in rects])
 
     def step(self, frame: np.ndarray) -> List[Tuple]:
+        if self.candidates_mode == "device":
+            return self._step_device(frame)
         call = self.call
         k = call.admit(frame)                                                          # :373-376, the one upload
         online = [] if self.tracker_mode == "device" else None
@@ -833,13 +905,51 @@ class StoresQuality(_QualitySums):
         return [(float(min(r[6] - r[4], r[5] - r[3])), lap(h), lap(f)) for r, h, f in zip(rects, half, full)]
 
 
+class RecordsQuality:
+    """The quality launch on the candidate records of live calls where the candidate stage left them
+    (``af_face_quality_records_u8``): ``enqueue([(record, store, channel_order, slot)])`` - ``record`` a call's
+    (LIVE_RECORD_BYTES,) uint8 device tensor, its frame in ``slot`` of ``store`` - enqueues one launch per 64 jobs on the current
+    stream and returns the uint8 device tensor of ``len(jobs) * MAX_TRACKS`` ``af_quality_sums`` without waiting; candidate k of
+    job j is entry ``j * MAX_TRACKS + k`` of ``parse``'s result.  ``launches`` counts the calls into the C function."""
+
+    def __init__(self, device):
+        from . import _lib                                        # fails loudly when libafhip.so is missing
+        self.device, self.launches = device, 0
+        self._fn = _lib.lib.af_face_quality_records_u8
+
+    def enqueue(self, jobs, grey=None, grey_stride: int = 0) -> torch.Tensor:
+        import ctypes as C
+        from . import _lib
+        per = _lib.AF_TRACK_MAX_TRACKS * C.sizeof(_lib.QualitySums)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            with torch.inference_mode(False):
+                sums = torch.empty(max(1, len(jobs)) * per, dtype=torch.uint8, device=self.device)
+            for lo in range(0, len(jobs), _lib.QUALITY_MAX_RECTS):                     # one launch for up to 64 calls
+                chunk, table = jobs[lo:lo + _lib.QUALITY_MAX_RECTS], StoreTable()
+                items = (_lib.LiveQualityJob * len(chunk))()
+                for item, (record, store, order, slot) in zip(items, chunk):
+                    item.record, item.store, item.slot = record.data_ptr(), table.index(store, order), int(slot)
+                gptr = None if grey is None else grey.data_ptr() + lo * _lib.AF_TRACK_MAX_TRACKS * int(grey_stride)
+                _lib.check(self._fn(table.array(), len(table.refs), items, len(chunk), C.c_void_p(sums.data_ptr() + lo * per), C.c_void_p(gptr),
+                                    int(grey_stride), C.c_void_p(cur.cuda_stream)), "face_quality_records_u8")
+                self.launches += 1
+        return sums[:len(jobs) * per]
+
+    @staticmethod
+    def parse(raw) -> np.ndarray:
+        """the host bytes of ``enqueue``'s tensor -> the parsed ``af_quality_sums``"""
+        return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=_SUMS_DTYPE)
+
+
 class ServerStats:
     """what a ``CallServer`` enqueued and waited for: ``last`` for the last step, ``total`` since the server was made, each with
     ``detect`` (calls of ``af_yunet_detect_frames``, or of a detector's ``detect_views``), ``quality``, ``warp`` (launches),
     ``replay`` (graph replays), ``wait`` (host waits for the device), ``convert`` (launches of ``af_yuv420_to_rgb_u8`` / ``af_yuv_to_rgb_ex_u8``),
     ``yuv_copies`` (host-to-device copies of staged YUV planes), ``capture`` (launches of ``af_capture_to_stores_u8``), ``resize``
-    (launches of ``af_resize_frames_u8``) and ``track`` (launches of ``af_bytetrack_update_calls``; in ``VideoRunner``, of
-    ``af_runner_track_chunk``)"""
+    (launches of ``af_resize_frames_u8``) and ``track`` (launches of ``af_bytetrack_update_calls``, and the kernels of
+    ``af_live_update_calls`` for the calls with ``candidates="device"``, whose ``af_face_quality_records_u8`` launch counts under
+    ``quality``; in ``VideoRunner``, of ``af_runner_track_chunk``)"""
     KEYS = ("detect", "quality", "warp", "replay", "wait")
     YUV_KEYS = ("convert", "yuv_copies")       # appear in ``last`` / ``total`` once a step has YUV frames; read as 0 before
     CAPTURE_KEYS = ("capture",)                # likewise once a step has captured frames
@@ -883,7 +993,12 @@ class CallServer:
     frames resized to dw x dh, as ``RealtimeCall`` does: calls of any frame sizes that share a detect size share one resize launch
     and one ``detect_views``.  ``tracker="device"`` (a call's own, ``"host"`` by default): the trackers of all such calls of a tick run
     as one launch per 64 calls behind the ``detect_views`` launches - on their rows in place where they detected, without a detection
-    otherwise - and their records ride in the read-back of the rows; ``stats`` counts ``track``.
+    otherwise - and their records ride in the read-back of the rows; ``stats`` counts ``track``.  ``candidates="device"``
+    (a call's own, ``"host"`` by default; needs ``tracker="device"`` and no ``landmarks`` hook): the tracker AND ``track_candidates``
+    of all such calls of a tick run in ``af_live_update_calls`` (as many launches as their arguments need), ONE
+    ``af_face_quality_records_u8`` launch measures their crops out of the records that leaves, and rows, records and sums come back
+    in the one read-back of the rows - on a tick without a detection too, since the candidates come from the record: a tick whose
+    calls are all in this mode waits once, twice when a window closes.  Calls in the other modes keep their launches.
 
     A frame is a numpy array, a ``YuvFrame`` or a ``CapturedFrame`` (the mapping may mix them).  The ``CapturedFrame``s of a step are
     admitted together - one fill, one copy, one ``af_capture_to_stores_u8`` launch per 64 - as are its ``YuvFrame``s: the
@@ -929,6 +1044,7 @@ class CallServer:
         self._done = None                  # recorded behind the last launch of every step
         self._detections = _Detections()
         self._track_pending = []                  # the device trackers' records enqueued and not read yet
+        self._records_quality: Optional[RecordsQuality] = None      # made when the first call with ``candidates="device"`` steps
 
     _scorers = property(lambda self: self._scoring.scorers if self._scoring is not None else {})
 
@@ -998,35 +1114,67 @@ class CallServer:
                 if key is not None:
                     self.stats.count(key, n)
         detecting = [i for i, (_, c, _) in enumerate(calls) if ticks[i] % max(1, c.detect_every) == 0]
-        on_device = [i for i, (_, c, _) in enumerate(calls) if c.tracker_mode == "device"]
-        online = {}
+        in_launch = [i for i, (_, c, _) in enumerate(calls) if c.candidates_mode == "device"]        # tracker and candidates in one launch
+        on_device = [i for i, (_, c, _) in enumerate(calls) if c.tracker_mode == "device" and c.candidates_mode != "device"]
+        online, came_back, riders = {}, {}, []
 
         def trackers(places):
             """behind the detector launches: one tracker launch per 64 calls with a device tracker - the calls that detected on
-            their rows where they lie (``places[j]`` = (rows, counts, b) of view j), the others without a detection"""
-            if not on_device:
-                return None
-            from .device_tracker import update_calls
+            their rows where they lie (``places[j]`` = (rows, counts, b) of view j), the others without a detection; for the calls
+            with ``candidates="device"`` the tracker-and-candidates launches and ONE quality launch on the records they leave.
+            -> (the device tensors to read back, whether this tick needs them)"""
             view_of = {i: j for j, i in enumerate(detecting)}
-            jobs = []
-            for i in on_device:
-                c = calls[i][1]
-                if i in view_of:
-                    rows, counts, b = places[view_of[i]]
-                    jobs.append(c._rows_job(rows[b], counts[b:b + 1], calls[i][2].shape))
-                else:
-                    jobs.append(c.tracker.empty_job())
-            self._track_pending.append((update_calls(jobs, self.device), [calls[i][1].tracker for i in on_device]))
-            self.stats.count("track", -(-len(jobs) // 64))
-            return self._track_pending
+            if on_device:
+                from .device_tracker import update_calls
+                jobs = []
+                for i in on_device:
+                    c = calls[i][1]
+                    if i in view_of:
+                        rows, counts, b = places[view_of[i]]
+                        jobs.append(c._rows_job(rows[b], counts[b:b + 1], calls[i][2].shape))
+                    else:
+                        jobs.append(c.tracker.empty_job())
+                self._track_pending.append((update_calls(jobs, self.device), [calls[i][1].tracker for i in on_device]))
+                self.stats.count("track", -(-len(jobs) // 64))
+            if in_launch:
+                from .device_tracker import live_launches, update_live_calls
+                jobs = []
+                for i in in_launch:
+                    c = calls[i][1]
+                    if i in view_of:
+                        rows, counts, b = places[view_of[i]]
+                        jobs.append(c._live_job(ticks[i], calls[i][2].shape, rows[b], counts[b:b + 1]))
+                    else:
+                        jobs.append(c._live_job(ticks[i], calls[i][2].shape))
+                track_records, records = update_live_calls(jobs, self.device)
+                self.stats.count("track", live_launches(len(jobs)))
+                if self._records_quality is None:
+                    self._records_quality = RecordsQuality(self.device)
+                launched = self._records_quality.launches
+                sums = self._records_quality.enqueue([(records[j], calls[i][1].call._ring.store, calls[i][1].call.channel_order,
+                                                       ticks[i] % calls[i][1].call.ring_frames) for j, i in enumerate(in_launch)])
+                self.stats.count("quality", self._records_quality.launches - launched)
+                riders[:] = [track_records, records, sums]
+            return [r for r, _ in self._track_pending] + riders, bool(riders)
 
         def tracked():
-            got = _absorb_records(self._track_pending, self._detections.extra)
+            from .device_tracker import MAX_TRACKS, parse_live_records, parse_records
+            n = len(self._track_pending)
+            got = _absorb_records(self._track_pending, self._detections.extra[:n])
             online.update({i: got[calls[i][1].tracker] for i in on_device})
+            if riders:
+                raw_t, raw_r, raw_s = self._detections.extra[n:n + 3]
+                sums = RecordsQuality.parse(raw_s)
+                came_back.update({i: (t, r, sums[j * MAX_TRACKS:(j + 1) * MAX_TRACKS])
+                                  for j, (i, t, r) in enumerate(zip(in_launch, parse_records(raw_t), parse_live_records(raw_r)))})
         dets = dict(zip(detecting, self._detect([calls[i][1].call.frame_view(ticks[i]) for i in detecting],
                                                 [calls[i][1].detect_size for i in detecting], trackers, tracked)))       # 2.
-        found, wanted = [], []
+        found, wanted, measured_here = [], [], {}
         for i, (cid, c, frame) in enumerate(calls):                                        # 3. trackers, candidates
+            if i in came_back:                                                             #    both ran on the device already
+                f, measured_here[i] = c._came_back(dets.get(i), *came_back[i])
+                found.append(f)
+                continue
             f = c._track(ticks[i], frame.shape, dets.get(i), online.get(i, []) if c.tracker_mode == "device" else None)
             found.append(f)
             ring, slot = c.call._ring.store, ticks[i] % c.call.ring_frames
@@ -1036,9 +1184,12 @@ class CallServer:
         self.stats.count("quality", self._quality.launches - launched)
         self.stats.count("wait", 1 if wanted else 0)
         ready, kept, at = [], [], 0
-        for (cid, c, frame), f in zip(calls, found):                                       # 5. the books
-            faces, alive, kept_boxes, _ = track_gate(c.host, f, measured[at:at + len(f[0])], c._weight)
-            at += len(f[0])
+        for i, ((cid, c, frame), f) in enumerate(zip(calls, found)):                       # 5. the books
+            if i in measured_here:
+                faces, alive, kept_boxes, _ = track_gate(c.host, f, measured_here[i], c._weight)
+            else:
+                faces, alive, kept_boxes, _ = track_gate(c.host, f, measured[at:at + len(f[0])], c._weight)
+                at += len(f[0])
             kept.append(kept_boxes)
             ready.append(c.call.advance_host(faces, alive))
         scores = self._score([(c.call, win) for (_, c, _), wins in zip(calls, ready) for _, win in wins])
@@ -1056,7 +1207,10 @@ class CallServer:
         are scaled back per view."""
         if not views:
             if trackers is not None:
-                trackers({})                       # enqueued; no rows, so nothing is read: the records ride in the next read
+                extra, needed = trackers({})       # enqueued; no rows, so the trackers' records ride in the next read - unless
+                if needed:                         # the tick's candidates come from them: then they are read now, in one wait
+                    self._detections.read([], self.device, self.stats.count, extra)
+                    tracked()
             return []
         from . import _lib
         sizes = list(sizes) if sizes is not None else [None] * len(views)
@@ -1083,9 +1237,9 @@ class CallServer:
                 order += chunk
                 if trackers is not None:
                     places.update({i: tuple(results[-1][:2]) + (b,) for b, i in enumerate(chunk)})
-        pending = trackers(places) if trackers is not None else None
-        read = self._detections.read(results, self.device, self.stats.count, [r for r, _ in pending or ()])
-        if pending:
+        extra = trackers(places)[0] if trackers is not None else []
+        read = self._detections.read(results, self.device, self.stats.count, extra)
+        if extra:
             tracked()
         out = [None] * len(views)
         for i, rows in zip(order, read):

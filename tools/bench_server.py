@@ -22,7 +22,12 @@ p50.  Every phase runs under a time limit of its own.  Prints one JSON line and 
 differing only in `tracker=`, alternating within the session after one warm-up run each; per N the tick times of both
 legs, `host_spread` (the run-to-run spread of the host leg's p50, the yardstick for a difference), `ratio` = host p50 / device p50
 and the launches and waits per tick; and `kernel`: the device time of one af_bytetrack_update_calls launch for 1, 4, 16, 32 and 64
-trackers that each follow two faces.  The default `--json` is then profiles/server_tracker_bench.json."""
+trackers that each follow two faces.  The default `--json` is then profiles/server_tracker_bench.json.
+
+`--candidates host,device` does the same for `candidates=` with `tracker="device"` in both legs - the host leg is the
+device-tracker leg of `--tracker` - and `kernel` is the device time of one af_live_update_calls call (tracker and candidate stage;
+its launches follow from the argument space) and of one af_face_quality_records_u8 launch on the records it left, for 1, 4, 16,
+32 and 64 calls.  The default `--json` is then profiles/server_candidates_bench.json."""
 import argparse
 import json
 import os
@@ -134,18 +139,62 @@ def tracker_kernel_times(n_list, launches=200):
     return out
 
 
+def live_kernel_times(n_list, launches=200):
+    """device time of one af_live_update_calls call and of the af_face_quality_records_u8 launch behind it: n calls that each
+    follow two faces on a resident 720p frame, in steady state"""
+    from types import SimpleNamespace
+    from af_mi355x import device_tracker as dt
+    from af_mi355x import evaluator, live
+    args = SimpleNamespace(track_thresh=0.8, track_buffer=90, match_thresh=0.8, mot20=False)
+    dev, out = torch.device("cuda:0"), {}
+    script = scripted_rows(launches + 20, FACES, seed=3000)
+    store = evaluator.FrameStore(dev, "bgr")
+    store.open((H, W, 3), 1)
+    store.put([np.random.default_rng(7).integers(0, 256, (H, W, 3), dtype=np.uint8)], 0)
+    quality = live.RecordsQuality(dev)
+    for n in n_list:
+        trackers = [dt.DeviceByteTracker(args, 30.0, device=dev, candidates=True) for _ in range(n)]
+        ticks = []
+        for rows in script:
+            batch = torch.from_numpy(np.stack([np.pad(rows, ((0, 16 - len(rows)), (0, 0)))] * n)).to(dev)
+            ticks.append((batch, torch.full((n,), len(rows), dtype=torch.int32, device=dev)))
+        trecs = torch.empty(n, dt.RECORD_BYTES, dtype=torch.uint8, device=dev)
+        recs = torch.empty(n, dt.LIVE_RECORD_BYTES, dtype=torch.uint8, device=dev)
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in script] for _ in range(3)]
+        for i, (batch, counts) in enumerate(ticks):
+            jobs = [tr.live_rows_job(batch[b], counts[b:b + 1], 0.76, 80, (1.0, 1.0), frame_idx=i, slot=0, shape=(H, W), mesh_every=1, crop_scale=0.6,
+                                     exclude_rect=EXCLUDE) for b, tr in enumerate(trackers)]
+            ev[0][i].record()
+            dt.update_live_calls(jobs, dev, trecs, recs)
+            ev[1][i].record()
+            quality.enqueue([(recs[b], store, "bgr", 0) for b in range(n)])
+            ev[2][i].record()
+        torch.cuda.synchronize()
+        cands = [int(r["n_cands"]) for r in dt.parse_live_records(recs.cpu().numpy())]
+        assert min(cands) >= 1, cands
+        case = {"launches": launches, "kernels_per_call": dt.live_launches(n)}
+        for name, a, b in (("live_update", 0, 1), ("quality_records", 1, 2)):
+            ms = sorted(x.elapsed_time(y) for x, y in zip(ev[a][20:], ev[b][20:]))
+            case[name] = {"device_ms_p50": ms[len(ms) // 2], "device_ms_p95": ms[int(len(ms) * 0.95)]}
+        out["calls%d" % n] = case
+    return out
+
+
 def tracker_legs(args, net, yunet, frames, keywords, out):
     from af_mi355x import live
-    legs = args.tracker.split(",")
-    assert legs[0] == "host" and set(legs) <= {"host", "device"} and len(legs) == 2, "--tracker host,device"
-    out.update(tool="bench_server --tracker", legs=legs)
+    what = "candidates" if args.candidates else "tracker"
+    legs = (args.candidates or args.tracker).split(",")
+    assert legs[0] == "host" and set(legs) <= {"host", "device"} and len(legs) == 2, "--%s host,device" % what
+    out.update(tool="bench_server --%s" % what, legs=legs)
+    if args.candidates:
+        keywords = dict(keywords, tracker="device")
     for n in (int(v) for v in args.calls.split(",")):
         scripts = scripts_for(n, args.ticks, args.stride)
         runs, per_tick, p50s = {leg: [] for leg in legs}, {}, {leg: [] for leg in legs}
         for rep in range(args.reps + 1):                          # repetition 0 warms up: rings, graphs, workspaces
             for leg in legs:
-                with phase("calls %d: tracker=%s, repetition %d" % (n, leg, rep), args.phase_seconds):
-                    server = live.CallServer(net, detector=ScriptedYuNet(yunet, scripts), tracker=leg, **keywords)
+                with phase("calls %d: %s=%s, repetition %d" % (n, what, leg, rep), args.phase_seconds):
+                    server = live.CallServer(net, detector=ScriptedYuNet(yunet, scripts), **dict(keywords, **{what: leg}))
                     cids = [server.open() for _ in range(n)]
                     times, per_tick[leg] = play_server(server, cids, frames, args.ticks)
                     assert server.stats.total["replay"] > 0, "no window closed"
@@ -159,12 +208,13 @@ def tracker_legs(args, net, yunet, frames, keywords, out):
                         p50s[leg].append(_pct(times, 0.5))
         case = {leg: {"tick_s": _stats(runs[leg]), "ticks_per_s": len(runs[leg]) / sum(runs[leg]), "per_tick": per_tick[leg],
                       "p50_per_repetition": p50s[leg]} for leg in legs}
-        case["host_spread"] = (max(p50s["host"]) - min(p50s["host"])) / min(p50s["host"]) if len(p50s["host"]) > 1 else None
+        for leg in legs:
+            case["%s_spread" % leg] = (max(p50s[leg]) - min(p50s[leg])) / min(p50s[leg]) if len(p50s[leg]) > 1 else None
         case["ratio"] = case["host"]["tick_s"]["p50"] / case["device"]["tick_s"]["p50"]
         out["cases"]["calls%d" % n] = case
         print(n, json.dumps(case), file=sys.stderr, flush=True)
-    with phase("tracker kernel", args.phase_seconds):
-        out["kernel"] = tracker_kernel_times([1, 4, 16, 32, 64])
+    with phase("%s kernel" % what, args.phase_seconds):
+        out["kernel"] = (live_kernel_times if args.candidates else tracker_kernel_times)([1, 4, 16, 32, 64])
     return out
 
 
@@ -178,10 +228,13 @@ def main():
     ap.add_argument("--ring-frames", type=int, default=128)
     ap.add_argument("--phase-seconds", type=int, default=240)
     ap.add_argument("--tracker", default=None, help="host,device: the two tracker modes of one CallServer instead of server / in_turn")
+    ap.add_argument("--candidates", default=None, help="host,device: the two candidate modes of one CallServer with device trackers")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    assert not (args.tracker and args.candidates), "--tracker or --candidates, not both"
     if args.json is None:
-        args.json = os.path.join(ROOT, "profiles", "server_tracker_bench.json" if args.tracker else "server_bench.json")
+        args.json = os.path.join(ROOT, "profiles", "server_candidates_bench.json" if args.candidates else
+                                 "server_tracker_bench.json" if args.tracker else "server_bench.json")
     assert torch.cuda.is_available(), "bench_server needs a GPU"
     from af_mi355x import live, synth
     from af_mi355x.classifier import Classifier
@@ -201,9 +254,9 @@ def main():
            "dtype": args.dtype, "ring_frames": args.ring_frames,
            "detections": "scripted: the real YuNet runs on every frame for its cost, its rows are discarded (no face photographs)",
            "tick": "host-inclusive wall clock, all N calls, ends in a device synchronise", "cases": {}}
-    if args.tracker:
+    if args.tracker or args.candidates:
         tracker_legs(args, net, yunet, frames, keywords, out)
-    for n in (int(v) for v in args.calls.split(",") if not args.tracker):
+    for n in (int(v) for v in args.calls.split(",") if not (args.tracker or args.candidates)):
         scripts = scripts_for(n, args.ticks, args.stride)
         runs = {"server": [], "in_turn": []}
         per_tick, p50s, in_turn_detects, closes = {}, [], 0, 0
