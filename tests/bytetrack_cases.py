@@ -4,7 +4,9 @@ A sequence is ``(args, frames)``; a frame is ``(form, rows)`` with ``form`` "str
 ``RealtimeCall._track`` builds), "array" ((n, 5) fp64 tlbr + score) or "empty".  ``golden()`` is the reference's own recording;
 the four scripts cover, between them, two faces crossing with IoU over 0.5, a face absent for longer than the buffer, alternate
 empty frames (``detect_every = 2``), a one-frame detection that dies unconfirmed, low-score rows for the second association and
-32 faces at once."""
+32 faces at once.  ``DENSE`` names the dense, contested sequences: seeded walks and packed crowds of overlapping faces (``dense``)
+and three scripts built by hand; ``dense_stats`` counts what a sequence makes the statement do.  ``run_batch`` steps many device
+trackers together, ``lone_run`` one alone."""
 import json
 import os
 import types
@@ -103,16 +105,255 @@ def crowd():
 SCRIPTS = {"crossing": crossing, "absent": absent, "alternate": alternate, "crowd": crowd}
 
 
+# ---- dense, contested sequences ----------------------------------------------------------------------------------------------------------
+# What the scripts above never give the solver: an augmenting path that re-routes at more than 8 x 5, more detections than tracks, a
+# tracked face dropped as the duplicate of a lost one, an id removed twice.  ``dense`` draws such frames from a seed; three scripts are
+# built by hand with the statement in the loop.  ``dense_stats(name)`` counts, on the statement alone, what a sequence reached.
+BANDS = ((0.60, 0.91, 0.99), (0.20, 0.15, 0.78), (0.12, 0.81, 0.89), (0.08, 0.01, 0.09))      # (probability, lowest, highest score)
+ORIGIN = 60.0                                                    # the arena's top left corner
+
+
+def _as_frame(form, rows):
+    """rows (x, y, w, h, score) as a frame of ``form``"""
+    if len(rows) == 0:
+        return ("empty", np.zeros((0, 5)))
+    r = np.asarray(rows, dtype=np.float64).reshape(-1, 5)
+    if form == "stracks":
+        return ("stracks", r.astype(np.float32))
+    return ("array", np.concatenate([r[:, :2], r[:, :2] + r[:, 2:4], r[:, 4:]], axis=1))
+
+
+def dense(seed, faces, frames, arena, form, buffer, p_seen, p_dup, p_fp, p_empty):
+    """``faces`` boxes of 70-130 px on a damped random walk (velocity += N(0, 1.5), then x 0.9) inside ``arena`` = (width, height),
+    bouncing off its edges, so that they overlap all the time.  Per frame a face is detected with probability ``p_seen`` (jitter
+    N(0, 2) on x, y, w, h; the score from ``BANDS``), with probability ``p_dup`` a second time (score 0.3-0.99); while a draw stays
+    under ``p_fp`` a false positive is added anywhere (score 0.05-0.99); the rows are shuffled; with probability ``p_empty`` the
+    frame is empty."""
+    rng = np.random.default_rng(seed)
+    span = np.asarray(arena, dtype=np.float64)
+    size = rng.uniform(70.0, 130.0, (faces, 2))
+    pos = rng.uniform(0.0, 1.0, (faces, 2)) * span               # the box's centre, relative to the arena's top left corner
+    vel = np.zeros((faces, 2))
+    chance = np.array([b[0] for b in BANDS])
+    out = []
+    for _ in range(frames):
+        vel = (vel + rng.normal(0.0, 1.5, (faces, 2))) * 0.9
+        pos = pos + vel
+        for lim, beyond in ((0.0, pos < 0.0), (span, pos > span)):
+            pos = np.where(beyond, 2.0 * lim - pos, pos)
+            vel = np.where(beyond, -vel, vel)
+        rows = []
+        for i in range(faces):
+            if rng.random() >= p_seen:
+                continue
+            _, lo, hi = BANDS[int(rng.choice(len(BANDS), p=chance))]
+            box = np.concatenate([ORIGIN + pos[i] - 0.5 * size[i], size[i]])
+            rows.append([*(box + rng.normal(0.0, 2.0, 4)), rng.uniform(lo, hi)])
+            if rng.random() < p_dup:
+                rows.append([*(box + rng.normal(0.0, 2.0, 4)), rng.uniform(0.3, 0.99)])
+        while rng.random() < p_fp:
+            rows.append([*(ORIGIN + rng.uniform(0.0, 1.0, 2) * span), *rng.uniform(70.0, 130.0, 2), rng.uniform(0.05, 0.99)])
+        order = rng.permutation(len(rows))
+        rows = [rows[k] for k in order]
+        out.append(_as_frame(form, [] if rng.random() < p_empty else rows))
+    return _args(track_buffer=buffer), out
+
+
+def walk(seed, frames=60, form=None):
+    """the seed's walk: 6 to 10 faces in 260 x 200 px, buffer 0, 2, 5 or 9; even seeds in the "stracks" form, odd ones as arrays"""
+    return dense(seed, 6 + seed % 5, frames, (260, 200), form or ("stracks", "array")[seed % 2], (0, 2, 5, 9)[seed % 4],
+                 p_seen=0.85, p_dup=0.15, p_fp=0.3, p_empty=0.05)
+
+
+PACKED = ((100, 22, "stracks", 1), (101, 23, "array", 0), (102, 24, "stracks", 2))       # (seed, faces, form, buffer)
+
+
+def packed(k):
+    """a packed crowd of 30 frames: 22 to 24 faces in 700 x 450 px"""
+    seed, faces, form, buffer = PACKED[k]
+    return dense(seed, faces, 30, (700, 450), form, buffer, p_seen=0.93, p_dup=0.04, p_fp=0.15, p_empty=0.03)
+
+
+class _Spy:
+    """the statement's ``linear_assignment`` and ``_drop_duplicates`` wrapped while a script runs: what they were asked and answered"""
+
+    def __init__(self):
+        self.solved, self.dropped = [], []                        # (cost, n, m, thresh, matches); (tracked + lost, tracked dropped)
+
+    def __enter__(self):
+        import bytetrack_ref as ref
+        self._ref, self._la, self._dd = ref, ref.linear_assignment, ref._drop_duplicates
+
+        def la(cost, n, m, thresh):
+            out = self._la(cost, n, m, thresh)
+            self.solved.append(([list(r) for r in cost], n, m, thresh, list(out[0])))
+            return out
+
+        def dd(a, b):
+            out = self._dd(a, b)
+            self.dropped.append((len(a) + len(b), len(a) - len(out[0])))
+            return out
+        ref.linear_assignment, ref._drop_duplicates = la, dd
+        return self
+
+    def __exit__(self, *exc):
+        self._ref.linear_assignment, self._ref._drop_duplicates = self._la, self._dd
+
+
+def _det(x, y, w, h, score):
+    return [float(x), float(y), float(w), float(h), float(score)]
+
+
+def usurper():
+    """buffer 30: face 1 moves right at 12 px per frame for 10 frames and is then no longer detected; from frame 10 on a face is
+    detected 8 steps ahead of it, standing still.  The lost track coasts onto the younger tracked one, ``_drop_duplicates`` drops the
+    TRACKED one, and the face is re-found under id 1."""
+    import bytetrack_ref as ref
+    args = _args(track_buffer=30)
+    tr, frames, seen = ref.RefByteTracker(args, 30.0), [], {}
+    with _Spy() as spy:
+        for f in range(24):
+            x = 100 + 12 * f if f < 10 else 100 + 12 * 9 + 12 * 8
+            frames.append(_as_frame("stracks", [_det(x, 200, 80, 100, 0.95)]))
+            tr.update(tracks_in(frames[-1]), SIZE, SIZE)
+            seen[f] = ([t.track_id for t in tr.tracked_stracks], [t.track_id for t in tr.lost_stracks], spy.dropped[-1][1])
+    assert seen[10][:2] == ([2], [1]), seen[10]
+    assert seen[18] == ([], [1], 1), seen[18]                      # the tracked face is dropped as the duplicate of the lost one
+    assert seen[19][0] == [1] and seen[23][:2] == ([1], []), (seen[19], seen[23])
+    return args, frames
+
+
+def back_at_once():
+    """buffer 2: two lost faces pass ``max_time_lost`` and are removed, stay in the lost list for one call, are detected again on
+    exactly that call and are re-found: their ids are in ``removed_ids`` although they are tracked.  The first is then lost on a
+    frame with detections and leaves the lost list at once, without a second entry; the second is lost on a frame without any,
+    stays lost for the buffer and is removed a second time: its id repeats in ``removed_ids``."""
+    import bytetrack_ref as ref
+    args = _args(track_buffer=2)
+    tr, frames = ref.RefByteTracker(args, 30.0), []
+    a, b, c = _det(100, 100, 100, 120, 0.95), _det(400, 150, 90, 110, 0.94), _det(700, 300, 110, 130, 0.93)
+
+    def step(rows):
+        frames.append(_as_frame("stracks", rows))
+        tr.update(tracks_in(frames[-1]), SIZE, SIZE)
+        return [t.track_id for t in tr.tracked_stracks], [t.track_id for t in tr.lost_stracks]
+    for f in range(4):
+        assert step([a, b, c]) == ([1, 2, 3], [])
+    assert step([c]) == ([3], [1, 2]) and step([c]) == ([3], [1, 2])
+    assert step([c]) == ([3], [1, 2]) and tr.removed_ids == [1, 2]               # past the buffer: removed, and lost for one more call
+    tracked, lost = step([a, b, c])
+    assert sorted(tracked) == [1, 2, 3] and lost == [] and tr.removed_ids == [1, 2]          # back on exactly that call, under their ids
+    for f in range(2):
+        step([a, b, c])
+    tracked, lost = step([b, c])
+    assert sorted(tracked) == [2, 3] and lost == [] and tr.removed_ids == [1, 2]             # lost among detections: it leaves at once
+    tracked, lost = step([])
+    assert tracked == [] and sorted(lost) == [2, 3]                              # lost on a frame without detections: it stays
+    step([])
+    tracked, lost = step([])
+    assert (tracked, lost) == ([], []) and sorted(tr.removed_ids) == [1, 2, 2, 3]            # the id's repeat
+    for f in range(2):
+        step([a, c])
+    assert [t.track_id for t in tr.tracked_stracks] == [4, 5]
+    return args, frames
+
+
+def twins():
+    """two detections with identical boxes and scores on one track, for several frames: the two costs are exactly equal.  A third
+    face is one frame old when two detections contest its unconfirmed association at 0.7."""
+    import bytetrack_ref as ref
+    args = _args(track_buffer=5)
+    tr, frames = ref.RefByteTracker(args, 30.0), []
+    equal = contested = 0
+    with _Spy() as spy:
+        for f in range(14):
+            a = _det(100 + 2 * f, 100, 100, 120, 0.95)
+            rows = [a, list(a)] if 3 <= f < 10 else [a]
+            if f == 6:
+                rows.append(_det(500, 300, 100, 120, 0.94))        # the third face
+            if f == 7:
+                rows += [_det(508, 300, 100, 120, 0.93), _det(494, 302, 100, 120, 0.92)]
+            at = len(spy.solved)
+            frames.append(_as_frame("stracks", rows))
+            tr.update(tracks_in(frames[-1]), SIZE, SIZE)
+            first, _, unconfirmed = spy.solved[at:at + 3]
+            equal += any(len(set(r)) < len(r) and min(r) <= first[3] and r.count(min(r)) > 1 for r in first[0])
+            contested += any(sum(c <= 0.7 for c in r) >= 2 for r in unconfirmed[0])
+    assert equal >= 5 and contested >= 1, (equal, contested)
+    return args, frames
+
+
+HAND = {"usurper": usurper, "back_at_once": back_at_once, "twins": twins}
+WALKS = tuple("walk%d" % s for s in range(8))
+CROWDS = tuple("packed%d" % k for k in range(len(PACKED)))
+DENSE = WALKS + CROWDS + tuple(HAND)
+_dense = {}
+
+
 def sequence(name):
-    """``(args, frames, frame_rate)`` of "golden" or a script"""
+    """``(args, frames, frame_rate)`` of "golden", a script or a name of ``DENSE``"""
     if name == "golden":
         args, frames, g = golden()
         return args, frames, g["frame_rate"]
+    if name in DENSE:
+        if name not in _dense:
+            _dense[name] = walk(int(name[4:])) if name in WALKS else packed(int(name[6:])) if name in CROWDS else HAND[name]()
+        return _dense[name][0], list(_dense[name][1]), 30.0
     args, frames = SCRIPTS[name]()
     return args, frames, 30.0
 
 
 ALL = ("golden",) + tuple(SCRIPTS)
+
+
+def _row_greedy(cost, n, m, thresh):
+    """every row in turn takes its cheapest free column under the limit"""
+    taken, out = set(), []
+    for i in range(n):
+        free = [j for j in range(m) if j not in taken and cost[i][j] <= thresh]
+        if free:
+            j = min(free, key=lambda j: cost[i][j])
+            taken.add(j)
+            out.append((i, j))
+    return out
+
+
+_stats = {}
+
+
+def dense_stats(name):
+    """what sequence ``name`` makes the statement do, from the statement alone: ``problems`` [(cost, n, m, thresh)] every
+    association it solved with n, m > 0; of those ``non_greedy`` whose solution differs from row-greedy, ``n_lt_m``, ``n_gt_m``,
+    ``largest`` (n, m) with the greatest min(n, m); ``refound`` tracks that went from the lost to the tracked list, ``repeated``
+    ids more than once in ``removed_ids``, ``second_frames`` with a second-association match, ``tracked_dropped`` by
+    ``_drop_duplicates``, ``held`` the most tracked + lost (in front of ``_drop_duplicates``), ``rows`` the most rows of a frame"""
+    if name in _stats:
+        return _stats[name]
+    import bytetrack_ref as ref
+    args, frames, rate = sequence(name)
+    tr = ref.RefByteTracker(args, rate)
+    s = dict(problems=[], non_greedy=0, n_lt_m=0, n_gt_m=0, largest=(0, 0), refound=0, repeated=0, second_frames=0, tracked_dropped=0,
+             held=0, rows=0, frames=len(frames))
+    with _Spy() as spy:
+        for frame in frames:
+            lost_before = {t.track_id for t in tr.lost_stracks}
+            tr.update(tracks_in(frame), SIZE, SIZE)
+            s["refound"] += len(lost_before & {t.track_id for t in tr.tracked_stracks})
+            s["rows"] = max(s["rows"], len(frame[1]))
+    s["second_frames"] = tr.second_matches
+    s["repeated"] = sum(tr.removed_ids.count(t) > 1 for t in set(tr.removed_ids))
+    s["held"], s["tracked_dropped"] = max(h for h, _ in spy.dropped), sum(d for _, d in spy.dropped)
+    for cost, n, m, thresh, matches in spy.solved:
+        if n == 0 or m == 0:
+            continue
+        s["problems"].append((cost, n, m, thresh))
+        s["non_greedy"] += sorted(matches) != sorted(_row_greedy(cost, n, m, thresh))
+        s["n_lt_m"] += n < m
+        s["n_gt_m"] += n > m
+        if min(n, m) > min(s["largest"]):
+            s["largest"] = (n, m)
+    _stats[name] = s
+    return s
 
 
 def tracks_in(frame):
@@ -199,3 +440,58 @@ def rows_in_place(make_tracker, to_tensor, launch):
             got = devs[b].absorb(records[b])
             assert_same_frame(refs[b], devs[b], want, got, devs[b].state_dump(), (tick, b))
     assert cut["conf"] >= 10 and cut["size"] >= 10 and cut["empty"] >= 8 and cut["kept"] > 60, cut
+
+
+# ---- many device trackers stepped together -----------------------------------------------------------------------------------------------
+def shifted(name, shift):
+    """``sequence(name)`` with ``shift`` empty frames in front"""
+    args, frames, rate = sequence(name)
+    return args, [("empty", None)] * shift + list(frames), rate
+
+
+def log_entry(tr, online):
+    """what a ``DeviceByteTracker`` returned and kept after a frame, as plain values"""
+    return ([(o.track_id, o.tlbr.tobytes(), o.score, o.state, o.is_activated) for o in online], tr.frame_id, list(tr.tracked_ids),
+            list(tr.lost_ids), list(tr.removed_ids))
+
+
+def lone_run(script):
+    """``script`` = (args, frames, rate) on a lone device tracker: (the ``log_entry`` of every frame, the final state bytes)"""
+    from af_mi355x import device_tracker as dt
+    args, frames, rate = script
+    tr, log = dt.DeviceByteTracker(args, rate, device="cuda"), []
+    for frame in frames:
+        log.append(log_entry(tr, tr.update(tracks_in(frame), SIZE, SIZE)))
+    return log, tr._state.cpu().numpy().tobytes()
+
+
+def run_batch(scripts, guard):
+    """one device tracker per script = (args, frames, rate), stepped together by ``update_calls`` (one launch per 64 of them), with
+    ``guard`` bytes of 0xA5 around every state block and around the records.  Returns the record bytes of every tick, the
+    trackers, their ``log_entry`` per tick and the guarded buffers as host arrays."""
+    import torch
+    from af_mi355x import device_tracker as dt
+    n, stride = len(scripts), dt.STATE_BYTES + guard
+    states = torch.full((guard + n * stride,), 0xA5, dtype=torch.uint8, device="cuda")
+    records = torch.full((2 * guard + n * dt.RECORD_BYTES,), 0xA5, dtype=torch.uint8, device="cuda")
+    rec_view = records[guard:guard + n * dt.RECORD_BYTES].view(n, dt.RECORD_BYTES)
+    trackers = []
+    for t, (args, frames, rate) in enumerate(scripts):
+        tr = dt.DeviceByteTracker(args, rate, device="cuda")
+        tr._state = states[guard + t * stride:guard + t * stride + dt.STATE_BYTES]
+        tr.reset()
+        trackers.append(tr)
+    raw, logs = [], [[] for _ in range(n)]
+
+    def upload(rows):
+        dev = torch.from_numpy(rows).cuda()
+        return dev.data_ptr(), dev
+    for tick in range(max(len(s[1]) for s in scripts)):
+        live_now = [t for t in range(n) if tick < len(scripts[t][1])]
+        jobs = [trackers[t]._input_job(tracks_in(scripts[t][1][tick]), SIZE, SIZE, upload) for t in live_now]
+        out = dt.update_calls(jobs, torch.device("cuda"), rec_view[:len(jobs)])
+        host = out.cpu().numpy()
+        raw.append(host.tobytes())
+        for t, rec in zip(live_now, dt.parse_records(host)):
+            logs[t].append(log_entry(trackers[t], trackers[t].absorb(rec)))
+    return raw, trackers, logs, states.cpu().numpy(), records.cpu().numpy()

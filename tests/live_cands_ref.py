@@ -330,7 +330,7 @@ def _with_points(name):
 
 
 BUILDERS = {"exclusion": exclusion, "threshold": threshold, "cache": cache, "edges": edges, "reuse": reuse}
-BUILDERS.update({name: (lambda name=name: _with_points(name)) for name in cases.ALL})
+BUILDERS.update({name: (lambda name=name: _with_points(name)) for name in cases.ALL + cases.DENSE})
 _built = {}
 
 
@@ -343,6 +343,11 @@ def script(name):
 
 
 ALL = tuple(BUILDERS)
+
+
+def has_points(name) -> bool:
+    """whether any frame of the script carries five points: not so a sequence of arrays"""
+    return any(fr["form"] == "list" and len(fr["rows"]) for fr in script(name)[1])
 
 
 # ---- a frame as a job of a DeviceByteTracker ---------------------------------------------------------------------------------------------

@@ -182,6 +182,19 @@ def _too_many_tracks():
     return Case("too_many_tracks", rows, reached, shape=(720, 1280, 3), exclude_bottom_frac=0.0)
 
 
+def _dense(name, seed, **args):
+    """a walk of tests/bytetrack_cases.py (40 frames of 6 to 10 faces that overlap all the time, with doubles, false positives and
+    empty frames), moved to the origin - where a track's box still overlaps its own detection - and clamped there"""
+    import bytetrack_cases
+    _, walked = bytetrack_cases.walk(seed, frames=40, form="stracks")
+    shift = bytetrack_cases.ORIGIN
+    rows = [frame(*[row(max(x - shift, 0.0), max(y - shift, 0.0), w, h, s) for x, y, w, h, s in r.tolist()]) for _, r in walked]
+    def reached(chunks, run):
+        assert not any(c["overflow"] for c in chunks) and len(_frames(chunks)) == 40
+        assert len(_cands(chunks)) >= 80 and run.st.id_switches >= 10 and max(len(f["ids"]) for f in _frames(chunks)) >= 6
+    return Case(name, rows, reached, min_det_area=0, min_det_side=0, min_track_side=60, exclude_bottom_frac=0.0, **args)
+
+
 def golden_case(name, run):
     """a run of tests/golden/runner_video.json as a case: the frames its window plan keeps, with the rows the file holds for them"""
     args = {k: v for k, v in run["args"].items() if k != "mot20"}
@@ -195,5 +208,6 @@ def golden_case(name, run):
     return case
 
 
-CASES = [_filters(), _start(), _budget(), _mesh(), _switch(), _crop(), _sliver(), _many(), _too_many_rows(), _too_many_tracks()]
+CASES = [_filters(), _start(), _budget(), _mesh(), _switch(), _crop(), _sliver(), _many(), _too_many_rows(), _too_many_tracks(),
+         _dense("dense_walk4", 4, track_buffer=0, mesh_every=1), _dense("dense_walk3", 3, track_buffer=5, mesh_every=3)]
 REFUSING = ("too_many_rows", "too_many_tracks")

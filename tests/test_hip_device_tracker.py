@@ -85,59 +85,16 @@ def test_h_the_kernel_equals_the_statement(name):
 BATCH, SHIFTS, KINDS = 65, 7, ("crossing", "absent", "alternate")
 
 
-def _shifted(kind, shift):
-    args, frames, rate = cases.sequence(kind)
-    return args, [("empty", None)] * shift + list(frames), rate
-
-
 @pytest.fixture(scope="module")
 def lone_runs():
     """per (kind, shift): after every frame what a lone DeviceByteTracker.update returned and kept"""
-    out = {}
-    for kind in KINDS:
-        for shift in range(SHIFTS):
-            args, frames, rate = _shifted(kind, shift)
-            tr, log = dt.DeviceByteTracker(args, rate, device="cuda"), []
-            for frame in frames:
-                online = tr.update(cases.tracks_in(frame), cases.SIZE, cases.SIZE)
-                log.append(([(t.track_id, t.tlbr.tobytes(), t.score, t.state, t.is_activated) for t in online], tr.frame_id, list(tr.tracked_ids),
-                            list(tr.lost_ids), list(tr.removed_ids)))
-            out[kind, shift] = (log, tr._state.cpu().numpy().tobytes())
-    return out
+    return {(kind, shift): cases.lone_run(cases.shifted(kind, shift)) for kind in KINDS for shift in range(SHIFTS)}
 
 
 def _run_batch():
     """65 trackers, tracker t on kind t % 3 shifted by t % 7 frames, stepped together: two launches per tick.  Returns the record
     bytes of every tick, the trackers, their per-tick results and the guarded buffers."""
-    stride = dt.STATE_BYTES + GUARD
-    states = torch.full((GUARD + BATCH * stride,), 0xA5, dtype=torch.uint8, device="cuda")
-    records = torch.full((2 * GUARD + BATCH * dt.RECORD_BYTES,), 0xA5, dtype=torch.uint8, device="cuda")
-    rec_view = records[GUARD:GUARD + BATCH * dt.RECORD_BYTES].view(BATCH, dt.RECORD_BYTES)
-    trackers, scripts = [], []
-    for t in range(BATCH):
-        args, frames, rate = _shifted(KINDS[t % 3], t % SHIFTS)
-        tr = dt.DeviceByteTracker(args, rate, device="cuda")
-        tr._state = states[GUARD + t * stride:GUARD + t * stride + dt.STATE_BYTES]
-        tr.reset()
-        trackers.append(tr)
-        scripts.append(frames)
-    raw, logs = [], [[] for _ in range(BATCH)]
-
-    def upload(rows):
-        dev = torch.from_numpy(rows).cuda()
-        return dev.data_ptr(), dev
-    for tick in range(max(len(s) for s in scripts)):
-        live_now = [t for t in range(BATCH) if tick < len(scripts[t])]
-        jobs = [trackers[t]._input_job(cases.tracks_in(scripts[t][tick]), cases.SIZE, cases.SIZE, upload) for t in live_now]
-        out = dt.update_calls(jobs, torch.device("cuda"), rec_view[:len(jobs)])
-        host = out.cpu().numpy()
-        raw.append(host.tobytes())
-        for t, rec in zip(live_now, dt.parse_records(host)):
-            tr = trackers[t]
-            online = tr.absorb(rec)
-            logs[t].append(([(o.track_id, o.tlbr.tobytes(), o.score, o.state, o.is_activated) for o in online], tr.frame_id, list(tr.tracked_ids),
-                            list(tr.lost_ids), list(tr.removed_ids)))
-    return raw, trackers, logs, states.cpu().numpy(), records.cpu().numpy()
+    return cases.run_batch([cases.shifted(KINDS[t % 3], t % SHIFTS) for t in range(BATCH)], GUARD)
 
 
 @pytest.fixture(scope="module")

@@ -1,8 +1,8 @@
 """CPU: the live candidate stage's host entry (af_live_update_host, the launch's own source compiled for the CPU) against its
 statement - live.track_candidates behind bytetrack_ref.RefByteTracker, with the purge list (tests/live_cands_ref.py).
 
-Every script - the reference's ByteTrack recording and the scripts of tests/bytetrack_cases.py, their list frames as YuNet rows with
-five points each, and the scripts of live_cands_ref.py that reach the exclusion edges, the 0.4 limit of the pick, equal IoUs, the
+Every script - the reference's ByteTrack recording and the scripts and dense sequences of tests/bytetrack_cases.py, their list frames
+as YuNet rows with five points each, and the scripts of live_cands_ref.py that reach the exclusion edges, the 0.4 limit of the pick, equal IoUs, the
 cache rule's branches, a purge and a return, frames without detection, the scale-back, the clamp, an empty crop, 32 tracks, a
 reused slot and a frame of more than 32 rows - is replayed frame by frame: the candidate record equals the statement's field for
 field, ``candidates_of`` equals ``track_candidates``' tuple with its types, the cache holds the statement's points for every track
@@ -73,7 +73,7 @@ def test_the_host_entry_equals_track_candidates(name):
         for i, tid in enumerate(st["cache_tid"]):
             if tid:
                 slots.setdefault(i, set()).add(int(tid))
-    if name != "absent":                                                     # all of its frames are arrays without points
+    if L.has_points(name):                                                   # a sequence of arrays has no points
         assert cands > 0 and refreshed > 0, name
     if name == "reuse":
         assert any(len(tids) >= 2 for tids in slots.values())                # a tracker slot served two tracks, one after the other

@@ -7,7 +7,7 @@ launch runs: csrc/af_runner_core.h) - no GPU is needed.
            record and state against the statement (tests/runner_chunk_ref.py: the loop's lines with ``RefByteTracker``)
   scripts  tests/runner_chunk_cases.py: the twin against the statement after every chunk, on scripts that reach the filter and
            start limits, the start and the budget in mid-chunk, the five-point cache, the id switch, the crop box's corners, 32
-           faces and both refusals; the guard bytes around the state and the record hold
+           faces, both refusals and two dense walks of overlapping faces; the guard bytes around the state and the record hold
   errors   what the constructor and a refusal raise
 """
 import types
