@@ -559,6 +559,7 @@ class Engine:
                        if spec.num_classes in (1, 2) else None)
 
         n_pack = len(self.inputs)
+        self.launches = plan.launches        # launch k is ops[n_pack + k] (a tt_head launch: TT_HEAD_OPS ops from there)
         self.n_ops = n_pack + len(plan.launches) + (self.TT_HEAD_OPS - 1 if isinstance(spec, FtcnTTSpec) else 0)
         self.ops = (Op * self.n_ops)()
         self.op_names: List[str] = []
@@ -830,6 +831,12 @@ class Engine:
         """Runs ops[0:n_ops] of the currently bound forward (tests read intermediate activations)."""
         check(lib.af_run_ops(self.ops, n_ops, _stream_ptr(self.device)), "af_run_ops")
 
+    def run_ops(self, first: int, count: int):
+        """Runs ops[first:first + count] of the currently bound forward (tests step a forward launch by launch)."""
+        assert 0 <= first and count >= 1 and first + count <= self.n_ops, (first, count, self.n_ops)
+        ops = C.cast(C.addressof(self.ops) + first * C.sizeof(Op), C.POINTER(Op))
+        check(lib.af_run_ops(ops, count, _stream_ptr(self.device)), "af_run_ops")
+
     def run_timed(self, first_op: int = 0):
         """Re-runs the currently bound forward with hipEvents around every op; returns ms per op."""
         ms = (C.c_float * self.n_ops)()
@@ -844,7 +851,7 @@ class Engine:
         into a wider, concatenated row return the full-width rows)."""
         op = self.ops[op_index]
         if op.kind in (_lib.AF_OP_STEM_POOL, _lib.AF_OP_STEM3_POOL, _lib.AF_OP_TSTEM_POOL3):
-            shape = (op.conv.n, op.conv.to, (op.conv.ho - 1) // 2 + 1, (op.conv.wo - 1) // 2 + 1, op.conv.cout)
+            shape = (op.conv.n, op.conv.to, (op.conv.ho - 1) // 2 + 1, (op.conv.wo - 1) // 2 + 1, op.out_ld or op.conv.cout)
         elif op.kind == _lib.AF_OP_CONV_BC:
             shape = (op.conv2.n, op.conv2.to, op.conv2.ho, op.conv2.wo, op.out_ld or op.conv2.cout)
         elif op.kind == _lib.AF_OP_BLOCK_ABC:

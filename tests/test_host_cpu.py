@@ -1008,3 +1008,38 @@ def test_stem_matrix_covers_what_ships(monkeypatch):
     assert lib.af_stem_work_units(C.byref(d), 2, None, C.byref(bands), C.byref(groups)) == -1
     assert lib.af_stem_work_units(C.byref(d), 2, C.byref(units), C.byref(bands), C.byref(groups)) == 0
     assert (units.value, bands.value, groups.value) == (256, 8, 256)
+
+
+def test_engine_replay_covers_every_launch_form_that_ships(monkeypatch):
+    """every launch kind of engine._ROLES, and every stem, pool and head kind, that a default or switched plan of the three networks
+    produces at batch 1..32 - as the form (kind, projection shortcut, fused pool, x_sub, channel offset, residual) - is launched by a
+    case of tests/test_hip_engine_replay.py, and engine_replay_ref has a reference and a tolerance for its kind.  A new launch kind
+    without a replay reference fails here, on the CPU."""
+    import plan_cases
+    from af_mi355x import engine
+    replay = _load_tests_module("test_hip_engine_replay")
+    ref = _load_tests_module("engine_replay_ref")
+
+    def form(launch):
+        return (launch.kind, bool(launch.convs.get("branch1")), launch.tpool, launch.x_sub, launch.ch_off > 0, launch.res is not None)
+    covered = set()
+    for net, dtype, batch, env in replay.CASES:
+        plan_cases.set_switches(monkeypatch, env)
+        p = plan_cases.plan(net, dtype, batch)
+        replay.expected_kinds((net, dtype, batch, env), p)             # what each case says it is there for, from its plan
+        covered |= {form(launch) for launch in p.launches}
+    assert {k[0] for k in covered} <= set(ref.REFERENCED_KINDS)
+    assert set(engine._ROLES) <= {k[0] for k in covered}
+    settings = [{}, plan_cases.UNFUSED] + [{name: "0" if on else "1"} for name, on in engine.SWITCHES.items()]
+    shipped = {}
+    for net, dtype, batch, setting, p in plan_cases.plans(monkeypatch, settings):
+        for launch in p.launches:
+            shipped.setdefault(form(launch), "%s %s batch %d%s" % (net, dtype, batch, setting))
+            if launch.kind not in ref.HEAD_KINDS and not (launch.kind in ("ca", "cpa", "bc", "abc") and dtype == "f32"):
+                assert ref.tolerance(launch, "dst", dtype) > 0
+    # every kind the engine can emit ships in some plan, but stem_pool (the fused 16-bit stem without K-packed weights, which a
+    # PackedWeights always has); the replay has a reference for that one too
+    assert len(shipped) >= 20 and {k[0] for k in shipped} == (set(engine.Engine._EMIT) - {"stem_pool"}) | {"tt_head"}
+    assert set(engine.Engine._EMIT) | {"tt_head"} <= set(ref.REFERENCED_KINDS)
+    missing = sorted("%s (%s)" % (k, v) for k, v in shipped.items() if k not in covered)
+    assert not missing, "%d shipped launch forms without a case in test_hip_engine_replay.py:\n%s" % (len(missing), "\n".join(missing))
